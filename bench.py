@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: simulated msgs/sec (+ histories/sec passing the checker), broadcast n=25.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg4]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg4] [--dump-outputs DIR]
     (N>1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` — the driver's
     way — or plainly as `python bench.py --gpus N`, which starts those N ranks itself; it refuses to run on fewer devices than N
     and never reports an n_gpus other than --gpus.)
@@ -204,6 +204,8 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="steps in flight together, one engine context and HIP stream each (default: 3 for cfg2, 1 for cfg4)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-fetch", action="store_true", help="skip the PCIe-inclusive leg (value_incl_fetch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's batch) to DIR/<name>.npy, float64 (dump_outputs)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)   # the measuring process under supervise()
     args = ap.parse_args()
     respawn_if_needed(args)
@@ -313,6 +315,10 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # outside the timed region, before anything else runs on the contexts
+        k_last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, engs[k_last % depth], k_last * world * n + EN.shard(world * n, rank, world)[0], n, args.seed,
+                     torch, dev, torch_view)
     rows_tot, words_tot = int(acc[3]), int(acc[4])
     # the workload checker alone on the chip (outside the timed region): five launches over the batch the first context still holds —
     # check_kernel / lin_check_kernel is the one kernel of a step that IS bandwidth work (it reads every history once), so its own
@@ -502,6 +508,39 @@ def main():
         dist.destroy_process_group()
     for e in engs:
         e.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 64   # instances whose whole histories are written
+
+
+def dump_outputs(path, e, first, n, seed, torch, dev, torch_view):
+    """--dump-outputs: the batch of the last timed step, as the engine context `e` holds it after the timed region (read from its HBM
+    slabs, nothing is re-run), written as float64 .npy files so that two builds can be compared output for output.  Per instance of
+    the batch (instances first .. first + n - 1, in order): net_stats (the 6 counters of msim_net_stats), meta (n_rows,
+    n_payload_words, flags, n_rounds, n_events) and check (the 17 fields of msim_check_result).  Whole histories for a fixed sample
+    drawn with --seed: sample_instances (their instance numbers), history_rows (the 16-byte rows as four u32 words, zero past n_rows)
+    and history_payload (zero past n_payload_words).  Every value is an integer below 2**53, so float64 holds it exactly."""
+    import numpy as np
+    db = e.device_buffers()
+    u32 = lambda t: t.cpu().numpy().view(np.uint32)
+    stats = torch_view(db.stats, db.stats_bytes, torch.int64, dev).view(-1, 6)[:n].cpu().numpy()
+    meta = u32(torch_view(db.meta, db.meta_bytes, torch.int32, dev).view(-1, 8)[:n])[:, :5]
+    check = u32(torch_view(db.check, db.check_bytes, torch.int32, dev).view(-1, 17)[:n])
+    out = {"net_stats": stats, "meta": meta, "check": check}
+    per_instance = (db.max_rows * 4 + db.max_payload_words) * 8
+    k = min(n, DUMP_SAMPLE, (DUMP_LIMIT_BYTES - sum(a.size * 8 for a in out.values())) // per_instance)
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    sel = torch.as_tensor(idx, device=dev)
+    rows = u32(torch_view(db.rows, db.rows_bytes, torch.int32, dev).view(db.n_instances, db.max_rows, 4)[sel]).copy()
+    pay = u32(torch_view(db.payload, db.payload_bytes, torch.int32, dev).view(db.n_instances, db.max_payload_words)[sel]).copy()
+    rows[np.arange(db.max_rows)[None, :] >= meta[idx, 0][:, None]] = 0        # what lies past the used prefix is not output
+    pay[np.arange(db.max_payload_words)[None, :] >= meta[idx, 1][:, None]] = 0
+    out.update(sample_instances=first + idx, history_rows=rows, history_payload=pay)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    assert sum(a.size for a in out.values()) * 8 <= DUMP_LIMIT_BYTES
 
 
 def fetch_inclusive(E, cfg, torch, dev, local_rank, n, steps, first0, torch_view):

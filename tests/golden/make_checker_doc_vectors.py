@@ -6,16 +6,16 @@ the reference's own documentation prints, turned into minimal histories -> tests
 `histories_per_sec` were so far pinned only by this repository's own restatements (tests/setfull_ref.py, tests/linearizable_ref.py).
 The tutorial chapters DO print runs of the real checkers: the final reads of a run in their invocation / completion order together
 with the result map (which elements were stable, stale, lost), and a non-linearizable pair of operations.  Every vector quotes the
-lines it is taken from; when /root/reference is present the script checks that each quoted fragment really occurs in the named file
+lines it is taken from; when the reference tree is at hand (MAELSTROM_REFERENCE) the script checks that each quoted fragment really occurs in the named file
 (whitespace-insensitive), so the fixture cannot drift from the docs.  What a vector asserts is what the doc shows and nothing more;
 what the doc elides ("...": the main phase's operations) is filled in minimally and marked `filler`.
 
-    python tests/golden/make_checker_doc_vectors.py        (run in the build container; needs /root/reference for the quote check)"""
+    MAELSTROM_REFERENCE=<reference tree> python tests/golden/make_checker_doc_vectors.py"""
 import json
 import os
 import re
 
-REF = "/root/reference"
+REF = os.environ.get("MAELSTROM_REFERENCE", "")
 HERE = os.path.dirname(os.path.abspath(__file__))
 MS = 1_000_000   # history :time is in nanoseconds
 
@@ -123,9 +123,17 @@ def squash(s):
     return re.sub(r"\s+", " ", s).strip()
 
 
+def fixture_text(checked):
+    """the fixture file's content: every vector with its operations numbered, and how many quoted fragments were verified"""
+    for v in VECTORS:
+        for i, op in enumerate(v["history"]):
+            op["index"] = i
+    return json.dumps({"source": "tests/golden/make_checker_doc_vectors.py", "quotes_checked": checked, "vectors": VECTORS}, indent=1)
+
+
 def main():
     checked = 0
-    if os.path.isdir(REF):
+    if REF and os.path.isdir(REF):
         for v in VECTORS:
             path = os.path.join(REF, v["doc"].split(":")[0])
             txt = squash(open(path).read())
@@ -133,13 +141,10 @@ def main():
                 assert squash(q) in txt, (v["doc"], q)
                 checked += 1
     else:
-        print("warning: /root/reference absent — quotes NOT checked")
-    for v in VECTORS:
-        for i, op in enumerate(v["history"]):
-            op["index"] = i
+        print("warning: no reference tree (MAELSTROM_REFERENCE) — quotes NOT checked")
     out = os.path.join(HERE, "checker_doc_vectors.json")
     with open(out, "w") as f:
-        json.dump({"source": "tests/golden/make_checker_doc_vectors.py", "quotes_checked": checked, "vectors": VECTORS}, f, indent=1)
+        f.write(fixture_text(checked))
     print(f"wrote {out}: {len(VECTORS)} vectors, {checked} quoted fragments verified against {REF}")
 
 

@@ -1,14 +1,16 @@
 """The oracle's CRDT nodes against the reference's own JavaScript: real `node demo/js/crdt_gset.js` / `crdt_pn_counter.js`
-processes (from /root/reference — this container only; the test skips elsewhere) are driven over their pipes with the oracle's
+processes (from the reference tree) are driven over their pipes with the oracle's
 complete network schedule of a run (its journal), and everything they print — add_ok, read_ok with the set / the counter
 value, the replicate messages with the whole state — must be what the oracle's node sent, in order.  The processes' only
 timer (setInterval 5 s, crdt_gset.js:50-58) is taken over by a preload shim and fired when the oracle's node ticks, so the
 run is in virtual time.  The engine follows demo/ruby/g_set.rb for WHEN the first tick happens (at start-up; the JS waits 5 s):
-the shim fires the callback whenever the oracle ticks, the payloads are the processes' own.  Test infrastructure only."""
+the shim fires the callback whenever the oracle ticks, the payloads are the processes' own.  Test infrastructure only.
+
+The replays (replay_*) need node.js and the reference tree; tests/golden/make_reference_runs.py runs them and records a digest of
+every run they reproduced (tests/reference_runs.py).  The tests hold the oracle to those recorded runs."""
 import json
 import os
 import select
-import shutil
 import signal
 import subprocess
 
@@ -18,9 +20,7 @@ import pytest
 from maelstrom_amd import _abi as A
 from maelstrom_amd import engine as E
 import oracle_lib as O
-
-JS = "/root/reference/demo/js"
-needs_reference = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(JS), reason="needs node.js and the reference tree")
+import reference_runs as R
 
 SHIM = """
 const cbs = [];
@@ -32,7 +32,7 @@ process.on('SIGUSR1', () => { for (const f of cbs) f(); });
 
 class Proc:
     def __init__(self, script, shim):
-        self.p = subprocess.Popen(["node", "-r", shim, os.path.join(JS, script)], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
+        self.p = subprocess.Popen(["node", "-r", shim, R.reference_path("demo", "js", script)], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
                                   stderr=subprocess.DEVNULL, bufsize=0)
         self.buf, self.ping = b"", 0
 
@@ -68,18 +68,25 @@ def _bitmap(words):
     return {w * 32 + b for w, x in enumerate(words) for b in range(32) if (int(x) >> b) & 1}
 
 
-@needs_reference
-@pytest.mark.parametrize("workload,script,kw", [
+CRDT_CASES = [
     ("g-set", "crdt_gset.js", dict(node_count=5, rate=30, time_limit=12, latency=20, latency_dist="exponential", p_loss=0.05)),
     ("g-set", "crdt_gset.js", dict(node_count=3, rate=40, time_limit=8)),
     ("pn-counter", "crdt_pn_counter.js", dict(node_count=5, rate=30, time_limit=12, latency=30, latency_dist="uniform", p_loss=0.1)),
     ("g-counter", "crdt_pn_counter.js", dict(node_count=3, rate=40, time_limit=8, latency=5)),
-    # further shapes for the replay only (the recorded digests stay as they are)
+    # further shapes (js_crdt_replay_digests.json holds the first four only)
     ("g-set", "crdt_gset.js", dict(node_count=7, rate=40, time_limit=14, latency=40, latency_dist="exponential", nemesis=["partition"], nemesis_interval=2)),
     ("pn-counter", "crdt_pn_counter.js", dict(node_count=4, concurrency=12, rate=60, time_limit=12, latency=10, nemesis=["partition"], nemesis_interval=3)),
     ("g-set", "crdt_gset.js", dict(node_count=2, rate=20, time_limit=22, latency=300)),
-])
-def test_reference_js_crdt_processes_print_what_the_oracle_sends(workload, script, kw, tmp_path):
+]
+
+
+@pytest.mark.parametrize("workload,script,kw", CRDT_CASES)
+def test_reference_js_crdt_processes_print_what_the_oracle_sends(workload, script, kw):
+    """the run in which real crdt_gset.js / crdt_pn_counter.js processes printed what the oracle's node sent (replay_crdt)"""
+    assert run_digest(workload, kw) == R.recorded("js-crdt", workload, script, kw)
+
+
+def replay_crdt(workload, script, kw, tmp_path):
     shim = tmp_path / "shim.js"
     shim.write_text(SHIM)
     cfg = E.test_config(workload, seed=61, journal_capacity=400000, **kw)
@@ -183,12 +190,19 @@ def test_runs_still_match_the_recorded_js_replays():
         assert run_digest(workload, kw) == gold[str(i)]["digest"], f"case {i}: regenerate with tests/golden/make_golden_js_replay.py after checking the replay"
 
 
-@needs_reference
-def test_reference_echo_js_process_prints_what_the_oracle_sends(tmp_path):
+ECHO_CASE = dict(seed=62, journal_capacity=100000, node_count=2, rate=60, time_limit=8, p_loss=0.1)
+
+
+def test_reference_echo_js_process_prints_what_the_oracle_sends():
+    """the run in which a real echo.js process printed what the oracle's node sent (replay_echo)"""
+    assert run_digest("echo", ECHO_CASE) == R.recorded("js-echo", ECHO_CASE)
+
+
+def replay_echo(tmp_path):
     """demo/js/echo.js over a whole run of the echo workload (echo.clj:72-75 payloads), lossy network"""
     shim = tmp_path / "shim.js"
     shim.write_text(SHIM)
-    cfg = E.test_config("echo", seed=62, journal_capacity=100000, node_count=2, rate=60, time_limit=8, p_loss=0.1)
+    cfg = E.test_config("echo", **ECHO_CASE)
     N = cfg.n_nodes
     name = lambda e: f"n{e}" if e < N else f"c{e}"
     r = O.run(cfg, 0, 1)
@@ -222,10 +236,13 @@ def test_reference_echo_js_process_prints_what_the_oracle_sends(tmp_path):
             p.close()
 
 
-@needs_reference
-@pytest.mark.parametrize("kw", [dict(), dict(node_count=3, rate=150, latency=2), dict(latency=15, latency_dist="exponential"),
-                                dict(key_count=2, max_txn_length=8, max_writes_per_key=40, rate=120)])   # = TXN_CASES
-def test_reference_single_key_txn_js_processes_print_what_the_oracle_sends(kw, tmp_path):
+@pytest.mark.parametrize("kw", TXN_CASES)
+def test_reference_single_key_txn_js_processes_print_what_the_oracle_sends(kw):
+    """the run in which real single_key_txn.js processes printed what the oracle's node sent (replay_single_key_txn)"""
+    assert run_digest("txn-list-append", kw) == R.recorded("js-single-key-txn", kw)
+
+
+def replay_single_key_txn(kw, tmp_path):
     """txn-list-append: real `node demo/js/single_key_txn.js` processes (the runnable twin of single_key_txn.clj) against a
     transliteration of service.clj's lin-kv that keeps the REAL database value, driven with the oracle's schedule.  The two
     known differences between the reference's own twins are mapped, not hidden: JS numbers its RPCs from 0, Clojure (and the
@@ -316,7 +333,7 @@ class ClockedProc(Proc):
     def __init__(self, script, shim, clock_file):
         self.clock_file, self.now, self.lines = clock_file, 0, []
         env = dict(os.environ, MSIM_CLOCK_FILE=clock_file)
-        self.p = subprocess.Popen(["node", "-r", shim, os.path.join(JS, script)], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
+        self.p = subprocess.Popen(["node", "-r", shim, R.reference_path("demo", "js", script)], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
                                   stderr=subprocess.DEVNULL, bufsize=0, env=env)
         self.buf, self.ping = b"", 0
 
@@ -344,9 +361,13 @@ GOSSIP_CASES = [dict(node_count=5, rate=30, time_limit=10, latency=20, latency_d
                 dict(node_count=5, rate=20, time_limit=10, latency=50, topology="line", p_loss=0.2)]
 
 
-@needs_reference
 @pytest.mark.parametrize("kw", GOSSIP_CASES)
-def test_reference_gossip_js_processes_print_what_the_oracle_sends(kw, tmp_path):
+def test_reference_gossip_js_processes_print_what_the_oracle_sends(kw):
+    """the run in which real gossip.js processes printed what the oracle's node sent (replay_gossip)"""
+    assert run_digest("broadcast", kw) == R.recorded("js-gossip", kw)
+
+
+def replay_gossip(kw, tmp_path):
     """The acknowledged, retrying broadcast node (doc/03-broadcast/02-performance.md:406-441 ≡ demo/js/gossip.js) against real
     gossip.js processes whose RPC timeouts run in the oracle's virtual time.  Mapped differences: gossip.js gossips first and
     acknowledges last, the tutorial's final version (which the engine follows) acknowledges first — what a node emits for one

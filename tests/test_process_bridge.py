@@ -2,9 +2,9 @@
 over pipes, in virtual time.  A run is reproducible from its seed, and — because the bridge restates the same rounds and draws the
 same random numbers as the engine's specification — a node program that behaves like a built-in node yields exactly the history
 the oracle (and therefore the GPU engine) emits: broadcast with this repository's fire-and-forget node process, echo with the
-REFERENCE's own demo/python/echo.py when the reference tree is present."""
+REFERENCE's own demo/python/echo.py.  The runs of the reference's own programs (replay_*: they need the reference tree and node.js) are
+recorded by tests/golden/make_reference_runs.py (tests/reference_runs.py); the tests hold the oracle to them."""
 import os
-import shutil
 import sys
 
 import pytest
@@ -12,11 +12,11 @@ import pytest
 from maelstrom_amd import bridge as B
 from maelstrom_amd import engine as E
 import oracle_lib as O
+import reference_runs as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FF_NODE = [sys.executable, os.path.join(ROOT, "tools", "harness_node.py")]
 TSO_NODE = [sys.executable, os.path.join(ROOT, "tools", "harness_tso_node.py")]
-REF_ECHO = "/root/reference/demo/python/echo.py"
 
 
 def _norm(ops):
@@ -52,6 +52,14 @@ def _against_oracle(workload, argv, oracle_bin=None, **kw):
     return b
 
 
+def _oracle_run(workload, oracle_bin=None, **kw):
+    """digest of what _against_oracle compares: the oracle's history, round count and net stats"""
+    cfg = E.test_config(workload, bin=oracle_bin, **kw)
+    ora = O.run(cfg, 0, 1)
+    want = E.decode_history(*ora.history(0), cfg.n_nodes, cfg.workload, cfg.node_program)
+    return R.digest(_norm(want), int(ora.meta["n_rounds"][0]), [int(x) for x in ora.stats[0]])
+
+
 @pytest.mark.parametrize("kw", [
     dict(node_count=5, rate=10, time_limit=5, seed=7),
     dict(node_count=5, rate=20, time_limit=5, latency=20, latency_dist="exponential", p_loss=0.05, nemesis=["partition"], nemesis_interval=2, seed=8),
@@ -64,11 +72,18 @@ def test_broadcast_node_processes_reproduce_the_oracle_history(kw):
     assert m["all"]["send-count"] == b.stats["all_send"] and m["servers"]["msgs-per-op"] > 0
 
 
-@pytest.mark.skipif(not os.path.exists(REF_ECHO), reason="needs the reference tree (demo/python/echo.py)")
+ECHO_CASES = [dict(node_count=3, rate=10, time_limit=5, seed=1),
+              dict(node_count=3, rate=20, time_limit=6, p_loss=0.1, seed=2)]   # timeouts -> :info, new processes
+
+
 def test_reference_echo_py_reproduces_the_oracle_history():
-    """BASELINE configs[0]: echo, 3 nodes, the reference's own demo binary"""
-    _against_oracle("echo", [sys.executable, REF_ECHO], node_count=3, rate=10, time_limit=5, seed=1)
-    _against_oracle("echo", [sys.executable, REF_ECHO], node_count=3, rate=20, time_limit=6, p_loss=0.1, seed=2)   # timeouts -> :info, new processes
+    """BASELINE configs[0]: echo, 3 nodes — the runs in which the reference's own demo binary reproduced the oracle's history (replay_echo_py)"""
+    for kw in ECHO_CASES:
+        assert _oracle_run("echo", **kw) == R.recorded("bridge-echo-py", kw)
+
+
+def replay_echo_py(kw):
+    _against_oracle("echo", [sys.executable, R.reference_path("demo", "python", "echo.py")], **kw)
 
 
 def test_runs_are_reproducible_and_journalled():
@@ -132,32 +147,33 @@ def test_cli(tmp_path):
     assert lines and lines[0].startswith("{:index 0, :time ") and ":f :broadcast" in "".join(lines)
 
 
-REF_JS = "/root/reference/demo/js"
-_NODE = shutil.which("node")
-needs_js = pytest.mark.skipif(not (_NODE and os.path.exists(os.path.join(REF_JS, "single_key_txn.js"))), reason="needs node.js and the reference tree (demo/js)")
-
-
-@needs_js
-@pytest.mark.parametrize("kw", [
+SINGLE_KEY_CASES = [
     dict(node_count=3, rate=20, time_limit=4, seed=5),
     dict(node_count=5, rate=50, time_limit=8, latency=5, nemesis=["partition"], nemesis_interval=2, seed=8),
     dict(node_count=3, rate=100, time_limit=5, latency=20, latency_dist="exponential", p_loss=0.05, seed=9),
     dict(node_count=2, rate=200, time_limit=3, latency=2, key_count=3, max_txn_length=4, max_writes_per_key=8, seed=10),
     dict(node_count=2, concurrency=8, rate=200, time_limit=3, latency=2, key_count=3, seed=11),   # several workers per node (--concurrency 4n)
     dict(node_count=1, concurrency=10, rate=100, time_limit=3, latency=1, seed=12),
-])
+]
+
+
+@pytest.mark.parametrize("kw", SINGLE_KEY_CASES)
 def test_reference_single_key_txn_js_reproduces_the_oracle_history(kw):
+    """the run in which single_key_txn.js reproduced the oracle's history on the bridge (replay_single_key_txn_js)"""
+    assert _oracle_run("txn-list-append", **kw) == R.recorded("bridge-single-key-txn-js", kw)
+
+
+def replay_single_key_txn_js(kw):
     """BASELINE configs[4]'s node program: the REFERENCE's own demo/js/single_key_txn.js as real node.js processes, with the bridge's
     lin-kv service, yields the history, round count and net stats of the oracle's txn-list-append (restated from
     demo/clojure/single_key_txn.clj) — over whole runs, under partitions and loss.  (One corner is the two demos' own: when the
     root does not exist yet, the JS node compares `[]` and the Clojure node `nil` against a root another read-only transaction has
     just created as `[]` — the JS cas succeeds, the Clojure one, and the oracle, report a conflict.  The seeds here do not start
     with such a race.)"""
-    _against_oracle("txn-list-append", [_NODE, os.path.join(REF_JS, "single_key_txn.js")], **kw)
+    _against_oracle("txn-list-append", ["node", R.reference_path("demo", "js", "single_key_txn.js")], **kw)
 
 
-@needs_js
-@pytest.mark.parametrize("kw", [
+MULTI_KEY_CASES = [
     dict(node_count=2, rate=20, time_limit=2, latency=2, key_count=3, seed=5),
     dict(node_count=3, rate=50, time_limit=3, latency=5, seed=6),
     dict(node_count=5, rate=60, time_limit=3, latency=10, latency_dist="exponential", nemesis=["partition"], nemesis_interval=1, seed=7),
@@ -165,14 +181,22 @@ def test_reference_single_key_txn_js_reproduces_the_oracle_history(kw):
     dict(node_count=7, rate=100, time_limit=2, latency=0, seed=9),
     dict(node_count=2, concurrency=8, rate=200, time_limit=3, latency=2, key_count=3, seed=11),   # several workers per node (--concurrency 4n): transactions of one node race for the root
     dict(node_count=1, concurrency=10, rate=100, time_limit=3, latency=1, seed=12),               # --concurrency 10n (doc/05-datomic/01-single-node.md:257)
-])
+]
+
+
+@pytest.mark.parametrize("kw", MULTI_KEY_CASES)
 def test_reference_multi_key_txn_js_reproduces_the_oracle_history(kw):
+    """the run in which multi_key_txn.js reproduced the oracle's history on the bridge (replay_multi_key_txn_js)"""
+    assert _oracle_run("txn-list-append", oracle_bin="multi-key-txn", **kw) == R.recorded("bridge-multi-key-txn-js", kw)
+
+
+def replay_multi_key_txn_js(kw):
     """The canonical txn-list-append node (row a18): the REFERENCE's own demo/js/multi_key_txn.js as real node.js processes — thunks in
     the bridge's lww-kv, the root map in its lin-kv, retries after a lost root cas, thunk reads repeated while the other lww-kv replica
     answers — yields the history, the round count and the net stats of the oracle's restatement (oracle/mk_nodes.inc) over whole runs:
     contended keys, long transactions, partitions between the nodes, random latency.  Loss-free on purpose: node.js's rpc() gives up
     after one second of wall-clock time, which no virtual-time run can share."""
-    _against_oracle("txn-list-append", [_NODE, os.path.join(REF_JS, "multi_key_txn.js")], oracle_bin="multi-key-txn", **kw)
+    _against_oracle("txn-list-append", ["node", R.reference_path("demo", "js", "multi_key_txn.js")], oracle_bin="multi-key-txn", **kw)
 
 
 DATOMIC_NODE = [sys.executable, os.path.join(ROOT, "tools", "datomic_node.py")]
@@ -196,21 +220,29 @@ def test_datomic_node_process_reproduces_the_oracle_history(kw):
     _against_oracle("txn-list-append", DATOMIC_NODE, oracle_bin="datomic", **kw)
 
 
-@needs_js
+STRICT_CASE = dict(node_count=5, rate=40, time_limit=3, latency=5, nemesis=["partition"], nemesis_interval=1, seed=8)
+
+
 def test_reference_multi_key_txn_js_runs_strict_serializably_on_the_bridge():
     """demo/js/multi_key_txn.js (thunks in lww-kv, the root map in lin-kv, retry on a lost root cas) is not a built-in node of the
     GPU engine; on the bridge it runs as it is, against the bridge's lin-kv and eventually consistent lww-kv services, and the
-    list-append analysis finds its histories clean — also under partitions; runs are reproducible from the seed."""
-    for kw in (dict(node_count=5, rate=40, time_limit=3, latency=5, nemesis=["partition"], nemesis_interval=1, seed=8),):
-        hist = []
-        for _ in range(2):
-            b = B.Bridge("txn-list-append", [_NODE, os.path.join(REF_JS, "multi_key_txn.js")], **kw)
-            h = b.run()
-            assert b.errors == []
-            hist.append(h)
-        assert hist[0] == hist[1]
-        ops = [o for o in hist[0] if o["process"] != ":nemesis"]
-        assert sum(o["type"] == ":ok" for o in ops) > 50
-        res = E.check_txn_history(*E.encode_txn_history(ops))
-        assert res["valid?"] is True and res["anomalies"] == [], res
-        assert b.stats["servers_send"] > 6 * res["ok-count"]   # per transaction: root read / cas + thunk reads and writes
+    list-append analysis finds its histories clean — also under partitions.  The history is the one replay_multi_key_txn_js_strict
+    recorded (two runs from the seed, identical)."""
+    rec = R.recorded("bridge-multi-key-txn-js-strict", STRICT_CASE)
+    ops = [o for o in rec["history"] if o["process"] != ":nemesis"]
+    assert sum(o["type"] == ":ok" for o in ops) > 50
+    res = E.check_txn_history(*E.encode_txn_history(ops))
+    assert res["valid?"] is True and res["anomalies"] == [], res
+    assert rec["servers_send"] > 6 * res["ok-count"]   # per transaction: root read / cas + thunk reads and writes
+
+
+def replay_multi_key_txn_js_strict():
+    """two bridge runs of multi_key_txn.js from STRICT_CASE's seed: the same history; returns what the test above checks"""
+    hist = []
+    for _ in range(2):
+        b = B.Bridge("txn-list-append", ["node", R.reference_path("demo", "js", "multi_key_txn.js")], **STRICT_CASE)
+        h = b.run()
+        assert b.errors == []
+        hist.append(h)
+    assert hist[0] == hist[1]
+    return {"history": hist[0], "servers_send": b.stats["servers_send"]}

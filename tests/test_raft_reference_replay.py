@@ -1,5 +1,4 @@
-"""The oracle's Raft node against the reference's own code: demo/python/raft.py is loaded from /root/reference (this container
-only — the test skips elsewhere), its clock and random source replaced by the simulation's, its stdin / stdout by in-memory
+"""The oracle's Raft node against the reference's own code: demo/python/raft.py is loaded from the reference tree, its clock and random source replaced by the simulation's, its stdin / stdout by in-memory
 queues, and the oracle's complete schedule of a run — which node's main loop handled which message or took a timer / commit /
 apply action at which microsecond (oracle_raft_schedule) — is fed to five real RaftNode objects.  Every message they emit
 (votes, append_entries with their entries, acknowledgements, proxied client requests, client replies with their values and
@@ -8,7 +7,11 @@ something for raft.py to do at that instant.
 
 One line of raft.py is changed on load: the callback closure of replicate_log binds `_ni`, `_entries`, `_node` late, so every
 append_entries acknowledgement is credited to the LAST peer (raft.py:391-410) — demo/ruby/raft.rb, which the
-engine follows, does not have that slip; the three names are bound at definition time here.  Test infrastructure only."""
+engine follows, does not have that slip; the three names are bound at definition time here.  Test infrastructure only.
+
+The replay (replay_raft) needs the reference tree; tests/golden/make_reference_runs.py runs it and records the digests of every run
+raft.py reproduced (tests/reference_runs.py), and checks there that raft.py as shipped does diverge.  The tests hold the oracle to
+the recorded runs."""
 import collections
 import ctypes as C
 import fractions
@@ -21,9 +24,7 @@ import pytest
 from maelstrom_amd import _abi as A
 from maelstrom_amd import engine as E
 import oracle_lib as O
-
-REF = "/root/reference/demo/python/raft.py"
-needs_reference = pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is only mounted in the build container")
+import reference_runs as R
 ACTION = 0xFFFFFFFF
 
 
@@ -57,7 +58,8 @@ class _Stdin:
 
 
 def _load_reference(lib, cfg, inst, patch=True):
-    src = open(REF).read()
+    ref = R.reference_path("demo", "python", "raft.py")
+    src = open(ref).read()
     assert src.rstrip().endswith("RaftNode().main()")
     src = src.rstrip()[: -len("RaftNode().main()")]
     late = "                    def handler(res):\n"
@@ -65,7 +67,7 @@ def _load_reference(lib, cfg, inst, patch=True):
     if patch:
         src = src.replace(late, "                    def handler(res, _ni=_ni, _entries=_entries, _node=_node):\n")
     ns = {"__name__": "reference_raft"}
-    exec(compile(src, REF, "exec"), ns)
+    exec(compile(src, ref, "exec"), ns)
     clock, rnd, stdin = _Clock(), _Random(lib, cfg, inst), _Stdin()
     ns["time"], ns["random"], ns["log"] = clock, rnd, (lambda *a: None)
     ns["sys"] = type("S", (), {"stdin": stdin, "stdout": None, "stderr": None})()
@@ -89,9 +91,13 @@ EXTRA_CASES = [dict(latency=30, latency_dist="uniform", p_loss=0.2), dict(latenc
                dict(node_count=7, latency=5, rate=60), dict(latency=300, time_limit=30)]
 
 
-@needs_reference
 @pytest.mark.parametrize("kw", CASES + EXTRA_CASES)
-def test_reference_raft_py_emits_what_the_oracle_emits(kw, patch=True):
+def test_reference_raft_py_emits_what_the_oracle_emits(kw):
+    """the runs (two instances) in which raft.py emitted every message the oracle's node emitted (replay_raft)"""
+    assert run_digests(kw) == R.recorded("raft-py", kw)
+
+
+def replay_raft(kw, patch=True):
     lib = O.load()
     base = dict(bin="raft", node_count=5, rate=30, time_limit=20, seed=57, journal_capacity=600000)
     base.update(kw)
@@ -210,10 +216,9 @@ def test_runs_still_match_the_recorded_reference_replays():
         assert run_digests(kw) == gold[str(i)]["digests"], f"case {i}: regenerate with tests/golden/make_golden_raft_replay.py after checking the replay"
 
 
-@needs_reference
-def test_unpatched_raft_py_diverges_in_a_five_node_cluster():
-    """the reference quirk of DESIGN.md §2.4, as a test: raft.py as shipped credits every append_entries acknowledgement to the
-    LAST peer of the loop (late-bound closure, raft.py:391-410), so a 5-node cluster stops behaving like demo/ruby/raft.rb —
-    and like the engine — as soon as acknowledgements matter"""
+def replay_unpatched_raft_diverges():
+    """the reference quirk of DESIGN.md §2.4: raft.py as shipped credits every append_entries acknowledgement to the LAST peer of
+    the loop (late-bound closure, raft.py:391-410), so a 5-node cluster stops behaving like demo/ruby/raft.rb — and like the
+    engine — as soon as acknowledgements matter"""
     with pytest.raises(AssertionError):
-        test_reference_raft_py_emits_what_the_oracle_emits(dict(latency=10), patch=False)
+        replay_raft(dict(latency=10), patch=False)
