@@ -287,52 +287,55 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   }
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));   // (the launch's duration is read from these events on its own stream: msim_last_kernel_ms)
   hipError_t e;
+  const char *kname = "?";   // the kernel this launch took: named on stderr under MSIM_DEV_FLAGS bit 12
+  auto took = [&](hipError_t r, const char *k) { if (r != MSIM_LAYOUT_DOES_NOT_FIT) kname = k; return r; };
   // the headline layout: two clusters per wavefront (duo.hip); MSIM_DEV_FLAGS bit 9 keeps the one-cluster kernels
   e = MSIM_LAYOUT_DOES_NOT_FIT;
   if (msim_duo_eligible(c) && !(kp.dev_flags & 0x200u) && !((kp.dev_flags & 0x8000u) && msim_bcast8_eligible(c))) {   // (bit 15: small clusters eight per wavefront instead)
-    e = msim_launch_duo(kp, n, st);
+    e = took(msim_launch_duo(kp, n, st), "duo");
     if (e == MSIM_LAYOUT_DOES_NOT_FIT && (kp.dev_flags & 0x400u)) { ctx->err = "MSIM_DEV_FLAGS bit 10: the two-clusters-per-wavefront layout was required but this cluster state does not fit it"; return MSIM_E_UNSUPPORTED; }
   }
   // the broadcast programs at the tutorial's cluster sizes: eight clusters per wavefront (bcast8.hip) where the headline layout does not apply
-  if (e == MSIM_LAYOUT_DOES_NOT_FIT && msim_bcast8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_bcast8(kp, n, st);
+  if (e == MSIM_LAYOUT_DOES_NOT_FIT && msim_bcast8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_bcast8(kp, n, st), "bcast8");
   // Raft: four clusters per wavefront (raft4.hip) when a cluster fits a 16-lane group
-  if (msim_raft4_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_raft4(kp, n, st);
+  if (msim_raft4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_raft4(kp, n, st), "raft4");
   // the lin-kv proxy over lin-kv / lww-kv: four clusters per wavefront (svc4.hip) for large batches when a cluster and its service fit a 16-lane group
-  if (msim_svc4_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_svc4(kp, n, st);
+  if (msim_svc4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_svc4(kp, n, st), c.node_program == MSIM_NODE_TSO_IDS ? "svc4<TSO>" : "svc4");
   // txn-list-append, single-root node with several workers per node: four clusters per wavefront (txng4.hip) for large batches when nodes + workers + lin-kv fit a 16-lane group
-  if (msim_txng4_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_txng4(kp, n, st);
+  if (msim_txng4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_txng4(kp, n, st), "txng4");
   // the Datomic-style node with several workers per node: four clusters per wavefront (dtg4.hip) for large batches when nodes + workers + the two services fit a 16-lane group
-  if (msim_dtg4_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_dtg4(kp, n, st);
+  if (msim_dtg4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_dtg4(kp, n, st), "dtg4");
   // txn-list-append: eight clusters per wavefront (txn8.hip) when a cluster fits an 8-lane group
-  if (msim_txn8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_txn8(kp, n, st);
+  if (msim_txn8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_txn8(kp, n, st), "txn8");
   // the canonical txn-list-append node: eight clusters per wavefront (mk8.hip) when a cluster fits an 8-lane group
-  if (msim_mk8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_mk8(kp, n, st);
+  if (msim_mk8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_mk8(kp, n, st), "mk8");
   // the Datomic-style txn-list-append node: eight clusters per wavefront (dt8.hip) when a cluster fits an 8-lane group
-  if (msim_dt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_dt8(kp, n, st);
+  if (msim_dt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_dt8(kp, n, st), "dt8");
   // txn-rw-register over the highly-available-transactions node: eight clusters per wavefront (hat8.hip)
-  if (msim_hat8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_hat8(kp, n, st);
+  if (msim_hat8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_hat8(kp, n, st), "hat8");
   // kafka: eight clusters per wavefront (kafka8.hip) for large batches
-  if (msim_kafka8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_kafka8(kp, n, st);
+  if (msim_kafka8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_kafka8(kp, n, st), "kafka8");
   // echo / unique-ids (flake ids): eight clusters per wavefront (uid8.hip) for large batches of small clusters
-  if (msim_uid8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_uid8(kp, n, st);
+  if (msim_uid8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_uid8(kp, n, st), "uid8");
   // g-set / pn-counter / g-counter: eight clusters per wavefront (crdt8.hip) for large batches of small clusters
-  if (msim_crdt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = msim_launch_crdt8(kp, n, st);
+  if (msim_crdt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_crdt8(kp, n, st), "crdt8");
   if (e == MSIM_LAYOUT_DOES_NOT_FIT && (kp.dev_flags & 0x400u) && is_raft) { ctx->err = "MSIM_DEV_FLAGS bit 10: the four-clusters-per-wavefront Raft layout was required but does not apply"; return MSIM_E_UNSUPPORTED; }
   if (e == MSIM_LAYOUT_DOES_NOT_FIT) switch (c.node_program) {   // not eligible, or the cluster state does not fit the dense layout: one cluster per wavefront (k_*.hip)
-    case MSIM_NODE_ECHO: case MSIM_NODE_FLAKE_IDS: e = msim_launch_general_a(kp, n, lds, st); break;
-    case MSIM_NODE_G_SET: e = wide ? msim_launch_wide_gset(kp, n, lds, st) : msim_launch_general_a(kp, n, lds, st); break;
-    case MSIM_NODE_PN_COUNTER: e = wide ? msim_launch_wide_pn(kp, n, lds, st) : msim_launch_general_a(kp, n, lds, st); break;
-    case MSIM_NODE_BCAST_FF: case MSIM_NODE_BCAST_FF_ECHOBACK: e = wide ? msim_launch_wide_bcast(kp, n, lds, st) : msim_launch_general_b(kp, n, lds, st); break;
-    case MSIM_NODE_BCAST_ACK_RETRY: case MSIM_NODE_BCAST_RPC_ALL: e = wide ? msim_launch_wide_ack(kp, n, lds, st) : msim_launch_general_c(kp, n, lds, st); break;
-    case MSIM_NODE_RAFT: e = msim_launch_raft1(kp, n, lds, st); break;
-    case MSIM_NODE_LIN_KV_PROXY: case MSIM_NODE_TSO_IDS: e = msim_launch_svc1(kp, n, lds, st); break;   // (lin-tso ids: the proxy's layout with the timestamp oracle on the service lane)
-    case MSIM_NODE_TXN_SINGLE_KEY: e = txn_many ? msim_launch_txng(kp, n, lds, st) : msim_launch_txn1(kp, n, lds, st); break;
-    case MSIM_NODE_TXN_MULTI_KEY: e = dt_many ? msim_launch_mkg(kp, n, lds, st) : msim_launch_mk1(kp, n, lds, st); break;
-    case MSIM_NODE_TXN_DATOMIC: e = dt_many ? msim_launch_dtg(kp, n, lds, st) : msim_launch_dt1(kp, n, lds, st); break;
-    case MSIM_NODE_KAFKA: e = txn_many ? msim_launch_kafkag(kp, n, lds, st) : msim_launch_kafka1(kp, n, lds, st); break;
-    case MSIM_NODE_TXN_RW_HAT: e = c.concurrency > c.n_nodes ? msim_launch_hatg(kp, n, lds, st) : msim_launch_hat1(kp, n, lds, st); break;
+    case MSIM_NODE_ECHO: case MSIM_NODE_FLAKE_IDS: e = took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
+    case MSIM_NODE_G_SET: e = wide ? took(msim_launch_wide_gset(kp, n, lds, st), "wide_gset") : took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
+    case MSIM_NODE_PN_COUNTER: e = wide ? took(msim_launch_wide_pn(kp, n, lds, st), "wide_pn") : took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
+    case MSIM_NODE_BCAST_FF: case MSIM_NODE_BCAST_FF_ECHOBACK: e = wide ? took(msim_launch_wide_bcast(kp, n, lds, st), "wide_bcast") : took(msim_launch_general_b(kp, n, lds, st), "general_b"); break;
+    case MSIM_NODE_BCAST_ACK_RETRY: case MSIM_NODE_BCAST_RPC_ALL: e = wide ? took(msim_launch_wide_ack(kp, n, lds, st), "wide_ack") : took(msim_launch_general_c(kp, n, lds, st), "general_c"); break;
+    case MSIM_NODE_RAFT: e = took(msim_launch_raft1(kp, n, lds, st), "raft1"); break;
+    case MSIM_NODE_LIN_KV_PROXY: case MSIM_NODE_TSO_IDS: e = took(msim_launch_svc1(kp, n, lds, st), "svc1"); break;   // (lin-tso ids: the proxy's layout with the timestamp oracle on the service lane)
+    case MSIM_NODE_TXN_SINGLE_KEY: e = txn_many ? took(msim_launch_txng(kp, n, lds, st), "txng") : took(msim_launch_txn1(kp, n, lds, st), "txn1"); break;
+    case MSIM_NODE_TXN_MULTI_KEY: e = dt_many ? took(msim_launch_mkg(kp, n, lds, st), "mkg") : took(msim_launch_mk1(kp, n, lds, st), "mk1"); break;
+    case MSIM_NODE_TXN_DATOMIC: e = dt_many ? took(msim_launch_dtg(kp, n, lds, st), "dtg") : took(msim_launch_dt1(kp, n, lds, st), "dt1"); break;
+    case MSIM_NODE_KAFKA: e = txn_many ? took(msim_launch_kafkag(kp, n, lds, st), "kafkag") : took(msim_launch_kafka1(kp, n, lds, st), "kafka1"); break;
+    case MSIM_NODE_TXN_RW_HAT: e = c.concurrency > c.n_nodes ? took(msim_launch_hatg(kp, n, lds, st), "hatg") : took(msim_launch_hat1(kp, n, lds, st), "hat1"); break;
     default: ctx->err = "node program not built into this engine"; return MSIM_E_UNSUPPORTED;
   }
+  if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[layout] %s %u\n", kname, n);   // developer / tests: which kernel this launch took
   if (e != hipSuccess) { ctx->err = std::string("kernel launch: ") + hipGetErrorString(e); return MSIM_E_HIP; }
   ctx->n_inst = n; ctx->first_instance = first;
   ctx->fetched = false; ctx->fetch_pending = false; ctx->checked = false; ctx->check_fetched = false; ctx->ran = true;

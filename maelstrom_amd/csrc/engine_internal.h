@@ -78,7 +78,9 @@ static inline unsigned msim_host_threads() {
 
 // The developer switches in force for a context: those set through msim_set_dev_flags ORed with MSIM_DEV_FLAGS of the environment
 // (read once per process).  0x100 round limit x20, 0x200 one cluster per wavefront, 0x400 fail instead of falling back to it,
-// 0x800 checkers on the host cores, 0x1000 time the checkers' passes on stderr.
+// 0x800 checkers on the host cores, 0x1000 time the checkers' passes (and count their launches) on stderr and name the kernel each launch
+// took (`[layout] <kernel> <n>`), 0x2000 the checkers' HBM-table kernels / the lin-kv search's tiny pools, 0x10000 at most 7 histories per
+// launch in the chunked checker loops (txn LDS and HBM-table passes, rw, unique-ids HBM tables: a partial last chunk, first > 0).
 static inline uint32_t msim_dev_flags(const msim_ctx *ctx) {
   static const uint32_t env = []() { const char *e = std::getenv("MSIM_DEV_FLAGS"); return e ? (uint32_t)std::strtoul(e, nullptr, 0) : 0u; }();   // (decimal, 0x.. or 0..)
   return env | (ctx ? ctx->dev_flags : 0u);

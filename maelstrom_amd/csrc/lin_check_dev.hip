@@ -370,8 +370,9 @@ __device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Ou
       // by its own :ok / :fail — have exactly one linearization, their order.  Every lane checks its own pair against the value the nearest
       // earlier write / cas of the run leaves (a prefix maximum over the lanes) and the run's last one is the register afterwards (round 6;
       // before, every row of such a run went through the loop below: 4000 cycles a row, and such runs are most of a healthy history).  A
-      // pair that does not check leaves everything to the search below, which then finds the key not linearizable.
-      if (fast_ok && pending == 0 && !in_pool && S.alive && !(S.alive & (S.alive - 1ull))) {
+      // pair that does not check leaves everything to the search below, which then finds the key not linearizable.  (An :info call keeps
+      // its pending bit for the rest of the key, so pending == 0 implies info_bits == 0; the second test states that precondition.)
+      if (fast_ok && pending == 0 && info_bits == 0 && !in_pool && S.alive && !(S.alive & (S.alive - 1ull))) {
         fast_ok = false;
         const u32 a = (u32)__builtin_ctzll(S.alive), cur = rl(S.c_val, a);
         const u64 below = m & ((1ull << lane) - 1ull);

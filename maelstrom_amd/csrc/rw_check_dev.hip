@@ -370,7 +370,8 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
   if (rp.wmax == 0 || rp.wmax > WMAX) rp.wmax = WMAX;
   rp.ws_words = rw_ws_words(rp.nmax, rp.emax, rp.kmax, rp.wmax);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold
-  const u32 chunk = (u32)std::min<uint64_t>(n, std::max<uint64_t>(1, budget / (rp.ws_words * 4)));
+  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;   // MSIM_DEV_FLAGS bit 16: at most 7 histories per launch
+  const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
   const size_t need = (size_t)chunk * rp.ws_words * 4;
   if (*ws_cap < need) {
     if (*ws_buf) (void)msim_dev_free(*ws_buf);
@@ -379,7 +380,8 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
     *ws_cap = need;
   }
   rp.ws = static_cast<u32 *>(*ws_buf);
-  for (u32 first = 0; first < n; first += chunk) {
+  u32 launches = 0;
+  for (u32 first = 0; first < n; first += chunk, launches++) {
     rp.first = first;
     hipLaunchKernelGGL(rw_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, rp);
     MSIM_HIP_TRY(ctx, hipGetLastError());
@@ -388,7 +390,7 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   std::vector<u32> todo;
   for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-  if (trace) std::fprintf(stderr, "[rw-check] device pass: %.2f ms, %zu of %u histories for the host\n", ms(), todo.size(), n);
+  if (trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories for the host\n", launches, ms(), todo.size(), n);
   if (!todo.empty()) {
     std::vector<uint64_t> ro, po;
     if (rp.row_off) { ro.resize(n + 1); po.resize(n + 1);

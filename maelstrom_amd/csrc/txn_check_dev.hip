@@ -891,16 +891,19 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
   const auto t0 = std::chrono::steady_clock::now();
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold (every one of them has its own slice)
+  // MSIM_DEV_FLAGS bit 16 (0x10000): at most 7 histories per launch, so that small batches reach the chunk loops (a partial last chunk, first > 0)
+  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;
   int rc;
   std::vector<u32> big;   // histories for txn_check_kernel
   if (!hbm_only) {
     // pass 1: tables in LDS
     tp.ws_words = ws_words_lds(tp.nmax); tp.list = nullptr;
-    const u32 chunk = (u32)std::min<uint64_t>(n, std::max<uint64_t>(1, budget / (tp.ws_words * 4)));
+    const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (tp.ws_words * 4))});
     if ((rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
     tp.ws = static_cast<u32 *>(*ws_buf);
     if (tp.lds_bytes > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(txn_check_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds_bytes));
-    for (u32 first = 0; first < n; first += chunk) {
+    u32 launches = 0;
+    for (u32 first = 0; first < n; first += chunk, launches++) {
       tp.first = first;
       hipLaunchKernelGGL(txn_check_lds_kernel, dim3(std::min(chunk, n - first)), dim3(wg_threads), tp.lds_bytes, st, tp);
       MSIM_HIP_TRY(ctx, hipGetLastError());
@@ -908,7 +911,7 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
     for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HBM) big.push_back(i);
-    if (trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, ms(), big.size(), n);
+    if (trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup, %u launches): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, launches, ms(), big.size(), n);
   } else { big.resize(n); for (u32 i = 0; i < n; i++) big[i] = i; }
   if (!big.empty()) {
     // pass 2: the histories whose tables do not fit LDS, tables in an HBM workspace
@@ -917,11 +920,12 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     MSIM_HIP_TRY(ctx, hipMemcpy(d_list, big.data(), big.size() * 4, hipMemcpyHostToDevice));
     tp.ws_words = ws_words_for(tp.nmax, tp.emax); tp.list = d_list;
     const u32 nb = (u32)big.size();
-    const u32 chunk = (u32)std::min<uint64_t>(nb, std::max<uint64_t>(1, budget / (tp.ws_words * 4)));
+    const u32 chunk = (u32)std::min<uint64_t>({nb, max_chunk, std::max<uint64_t>(1, budget / (tp.ws_words * 4))});
     rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4);
+    u32 launches = 0;
     if (rc == MSIM_OK) {
       tp.ws = static_cast<u32 *>(*ws_buf);
-      for (u32 first = 0; first < nb; first += chunk) {
+      for (u32 first = 0; first < nb; first += chunk, launches++) {
         tp.first = first;
         hipLaunchKernelGGL(txn_check_kernel, dim3(std::min(chunk, nb - first)), dim3(64), 0, st, tp);
         if (hipGetLastError() != hipSuccess) { rc = MSIM_E_HIP; ctx->err = "txn_check_kernel launch"; break; }
@@ -930,7 +934,7 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     if (rc == MSIM_OK && (hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { rc = MSIM_E_HIP; ctx->err = "txn check: copy of the results"; }
     (void)msim_dev_free(d_list);
     if (rc != MSIM_OK) return rc;
-    if (trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories: done at %.2f ms\n", nb, ms());
+    if (trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories (%u launches): done at %.2f ms\n", nb, launches, ms());
   }
   if (ctx) ctx->txn_big = (u32)big.size();
   std::vector<u32> todo;

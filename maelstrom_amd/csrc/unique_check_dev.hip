@@ -160,7 +160,8 @@ static int unique_dev_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *w
   u32 slots = 64; while (slots < (paired ? up.max_rows : 2 * up.max_rows)) slots <<= 1;   // >= 2 x the ids a history can acknowledge
   up.table_slots = slots;
   const uint64_t budget = 4ull << 30;
-  const u32 chunk = (u32)std::min<uint64_t>(n, std::max<uint64_t>(1, budget / ((uint64_t)slots * 8)));
+  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;   // MSIM_DEV_FLAGS bit 16: at most 7 histories per launch
+  const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / ((uint64_t)slots * 8))});
   const size_t need = (size_t)chunk * slots * 8;
   if (*ws_cap < need) {
     if (*ws) (void)msim_dev_free(*ws);
@@ -169,11 +170,13 @@ static int unique_dev_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *w
     *ws_cap = need;
   }
   up.ws = static_cast<uint2 *>(*ws);
-  for (u32 first = 0; first < n; first += chunk) {
+  u32 launches = 0;
+  for (u32 first = 0; first < n; first += chunk, launches++) {
     up.first = first;
     hipLaunchKernelGGL(unique_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, up);
     MSIM_HIP_TRY(ctx, hipGetLastError());
   }
+  if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[unique-check] HBM tables (%u slots) over %u histories (%u launches)\n", slots, n, launches);   // developer trace bit
   return MSIM_OK;
 }
 

@@ -1,37 +1,13 @@
 """Parity at the shapes the benchmarks time: the exact `bench.headline_config` (n=25, inbox_capacity=6,
 rate 100, 20 s) and the cfg3 / cfg4 / cfg5 shapes of tools/bench_configs.py, bit-compared with the CPU oracle through the
 C-ABI — rows, payload, net stats, flags and round counts of every instance."""
-import hashlib
-
-import numpy as np
 import pytest
 
-from maelstrom_amd import _abi as A
 from maelstrom_amd import engine as E
+from launch_digests import digest_engine as _digest_engine, digest_oracle as _digest_oracle
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
-
-
-def _digest_engine(eng, i):
-    rows, pay = eng.raw_history(i)
-    st = eng.net_stats_raw(i)
-    m = eng.meta(i)
-    h = hashlib.sha256(rows.tobytes())
-    h.update(pay.tobytes())
-    h.update(np.array([getattr(st, f) for f, _ in A.NetStats._fields_], dtype=np.uint64).tobytes())
-    h.update(np.array([m.n_rows, m.n_payload_words, m.flags, m.n_rounds], dtype=np.uint32).tobytes())
-    return h.hexdigest()
-
-
-def _digest_oracle(ora, i):
-    rows, pay = ora.history(i)
-    m = ora.meta[i]
-    h = hashlib.sha256(rows.tobytes())
-    h.update(pay.tobytes())
-    h.update(np.array([int(x) for x in ora.stats[i]], dtype=np.uint64).tobytes())
-    h.update(np.array([m["n_rows"], m["n_payload_words"], m["flags"], m["n_rounds"]], dtype=np.uint32).tobytes())
-    return h.hexdigest()
 
 
 def _compare_digests(cfg, first, n, batch=None):

@@ -258,6 +258,43 @@ def test_unique_ids_device_checker_equals_host(lib):
     assert int(dev[0]["valid"]) == 1 and (dev["valid"][1:n] == 0).all()
 
 
+# a seed per case: no earlier context of this process held these histories' records (a chunk that writes nothing cannot return them)
+@pytest.mark.parametrize("flags,seed", [(0x10000, 17), (0x12000, 18)])
+def test_unique_ids_chunked_hbm_tables_equal_one_launch_and_the_host(lib, capfd, flags, seed):
+    """MSIM_DEV_FLAGS bit 16: at most 7 histories per launch of the HBM-table kernel (up.first > 0, a partial last chunk of 5) on 61
+    engine histories (partitions, loss).  Only with bit 13 does every history take that kernel and the chunk loop; without it the LDS
+    kernel (one launch, no chunks) checks them and bit 16 changes nothing.  The chunked check runs first on the fresh context; its
+    records are field by field the host checker's and byte for byte those of the same launch checked again without bit 16."""
+    import ctypes as C
+    import re
+    from maelstrom_amd import _abi as A
+    cfg = E.test_config("unique-ids", node_count=3, rate=300, time_limit=4, latency=5, nemesis=["partition"], nemesis_interval=1, p_loss=0.05, seed=seed)
+    n = 61
+    with E.Engine(cfg) as eng:
+        eng.run(0, n)
+        eng.set_dev_flags(flags | 0x1000)
+        capfd.readouterr()
+        eng.check()
+        err = capfd.readouterr().err
+        chunked = eng.check_results()
+        eng.set_dev_flags(flags & 0x2000)
+        eng.check()
+        whole = eng.check_results()
+        eng.fetch()
+        hs = [eng.raw_history(i)[0].copy() for i in range(n)]
+    assert chunked.tobytes() == whole.tobytes()
+    fields = ("valid", "attempt_count", "duplicated_count", "op_count", "ok_count", "fail_count", "info_count")
+    for i, rows in enumerate(hs):
+        h = A.CheckResult()
+        assert A.load().msim_check_unique_rows(rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(h)) == 0
+        for f in fields:
+            assert int(chunked[i][f]) == int(getattr(h, f)), (i, f)
+        assert [int(x) for x in chunked[i]["stable_latency_ms"][:2]] == [int(h.stable_latency_ms[0]), int(h.stable_latency_ms[1])]
+    assert (chunked["valid"] == 1).all()
+    launches = [int(x) for x in re.findall(r"\[unique-check\] HBM tables \(\d+ slots\) over 61 histories \((\d+) launches\)", err)]
+    assert launches == ([9] if flags & 0x2000 else []), err
+
+
 def test_unique_ids_batch_of_completions_only_history_terminates(lib):
     """A caller's history may be ALL acknowledgements (filtered to its completions): 36000 distinct :ok ids in 36000 rows are more than the
     LDS table's 32768 slots — the batch entry sizes by the rows, not by rows / 2 (the LDS kernel's probe loop spun for ever

@@ -84,7 +84,7 @@ def test_kernel_sources_on_the_emulator_equal_the_oracle(emu_lib):
 @pytest.mark.timeout(1800)
 def test_list_append_check_kernels_on_the_emulator_equal_the_host_analysis(emu_lib):
     """tests/test_txn_check_gpu.py's hand-made anomalies and corrupted histories through the emulated device pass (both kernels)."""
-    for flags in ("0", "0x2000"):
+    for flags in ("0", "0x2000", "0x10000", "0x12000"):   # (bit 16: at most 7 histories per launch, the chunk loops of both passes)
         env = dict(os.environ, MSIM_LIB=emu_lib, HIPEMU_DIVERGENT="1", MSIM_DEV_FLAGS=flags, MSIM_TXN_WG="256")
         r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_txn_check_gpu.py"), "-k", "hand_made"],
                            cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
@@ -107,9 +107,11 @@ def test_device_checkers_on_the_emulator_equal_the_host_checkers(emu_lib):
     (tests/test_rw_check_gpu.py), the wide keys of the lin-kv search (tests/test_lin_check_gpu.py) and the reference-held set-full / linearizability vectors (tests/test_checker_reference_vectors.py)
     through the emulated device kernels."""
     env = dict(os.environ, MSIM_LIB=emu_lib, HIPEMU_DIVERGENT="1")
-    for args in ([os.path.join(ROOT, "tests", "test_checker_gpu.py"), "-k", "unique"], [os.path.join(ROOT, "tests", "test_rw_check_gpu.py")],
-                 [os.path.join(ROOT, "tests", "test_lin_check_gpu.py")],   # the linearizability search beyond 64 configurations: LDS pools, the host for the rest
-                 [os.path.join(ROOT, "tests", "test_checker_reference_vectors.py")],   # set-full / linearizability against the runs the reference docs print
-                 [os.path.join(ROOT, "tests", "test_set_full_synthetic_gpu.py")]):   # check_kernel on synthetic histories: overtaking reads, failures, > 1024 elements, the slab's end
-        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    for args, flags in (([os.path.join(ROOT, "tests", "test_checker_gpu.py"), "-k", "unique"], None), ([os.path.join(ROOT, "tests", "test_rw_check_gpu.py")], None),
+                        ([os.path.join(ROOT, "tests", "test_rw_check_gpu.py")], "0x10000"),   # the batch entry's chunk loop too (it reads the bit from the environment)
+                        ([os.path.join(ROOT, "tests", "test_lin_check_gpu.py")], None),   # the linearizability search beyond 64 configurations: LDS pools, the host for the rest
+                        ([os.path.join(ROOT, "tests", "test_checker_reference_vectors.py")], None),   # set-full / linearizability against the runs the reference docs print
+                        ([os.path.join(ROOT, "tests", "test_set_full_synthetic_gpu.py")], None)):   # check_kernel on synthetic histories: overtaking reads, failures, > 1024 elements, the slab's end
+        run_env = dict(env, MSIM_DEV_FLAGS=flags) if flags else env
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + args, cwd=ROOT, env=run_env, capture_output=True, text=True, timeout=1500)
         assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -150,3 +150,65 @@ def test_synthetic_histories_device_equals_host(lib):
             assert int(dev[i][f]) == int(getattr(h, f)), (i, f, int(dev[i][f]), int(getattr(h, f)))
         verdicts.add(int(dev[i]["valid"]))
     assert {0, 1} <= verdicts
+
+
+def _info_then_pairs(reads, f_info="write", completion="end", second_key=False):
+    """Key 0 holds 1; process 0's write of 3 (or cas 1 -> 3) never returns — an :info row right after it, at the end, or none — and
+    process 1 then runs clean invoke / :ok pairs on key 0 (the device's pair fast path once nothing is pending): reads of `reads` (a list
+    of values), then a cas from the last value read and reads of what it wrote.  `second_key`: process 2's clean pairs on key 1 in between."""
+    ops, t = [], [0]
+
+    def op(typ, p, f, val):
+        t[0] += 1000
+        ops.append({"type": typ, "f": f, "process": p, "value": val, "time": t[0]})
+
+    def pair(p, f, val, out=None):
+        op(":invoke", p, f, val if f != ":read" else [val[0], None])
+        op(":ok", p, f, out if out is not None else val)
+
+    def other(j):
+        if second_key:
+            pair(2, ":write", [1, j % 7]) if j % 3 == 0 else pair(2, ":read", [1, None], [1, (j - j % 3) % 7])
+
+    pair(1, ":write", [0, 1])
+    info = [0, 3] if f_info == "write" else [0, [1, 3]]
+    op(":invoke", 0, ":" + f_info, info)
+    if completion == "early":
+        op(":info", 0, ":" + f_info, info)
+    for j, v in enumerate(reads):
+        pair(1, ":read", [0, None], [0, v])
+        other(j)
+    last = reads[-1]
+    pair(1, ":cas", [0, [last, 4]])
+    for j in range(40):
+        pair(1, ":read", [0, None], [0, 4])
+        other(len(reads) + j)
+    if completion == "end":
+        op(":info", 0, ":" + f_info, info)
+    return ops
+
+
+@pytest.mark.parametrize("second_key", [False, True])
+@pytest.mark.parametrize("completion", ["early", "end", "none"])
+@pytest.mark.parametrize("f_info", ["write", "cas"])
+def test_info_call_then_clean_pairs_device_equals_host_and_reference(lib, f_info, completion, second_key):
+    """the pair fast path of the device search (csrc/lin_check_dev.hip) runs only while no call is open; an :info write / cas
+    never returns, so it stays open for the rest of its key.  Long runs of clean pairs after one: reads consistent only if it took effect
+    (at once, or only after many reads of the old value), only if it did not, and reads that see it and then the old value again (not
+    linearizable) — device, host search and tests/linearizable_ref.py agree on every key."""
+    import linearizable_ref as L
+    shapes = {"took": ([3] * 60, True), "took-late": ([1] * 60 + [3] * 60, True), "not": ([1] * 120, True),
+              "back": ([3] * 30 + [1] * 30, False), "late-back": ([1] * 30 + [3] * 30 + [1], False)}
+    hs = {name: _info_then_pairs(reads, f_info, completion, second_key) for name, (reads, _) in shapes.items()}
+    rows = [E.encode_lin_kv_history(h) for h in hs.values()]
+    dev = E.check_lin_kv_batch(rows)
+    for i, (name, h) in enumerate(hs.items()):
+        host = _host(rows[i])
+        for f in FIELDS:
+            assert int(dev[i][f]) == int(getattr(host, f)), (name, f, int(dev[i][f]), int(getattr(host, f)))
+        ref = L.check(h)
+        want = shapes[name][1]
+        assert ref[0] is want, (name, ref)
+        assert all(ref[k] for k in ref if k != 0), (name, ref)
+        assert int(dev[i]["attempt_count"]) == len(ref) and int(dev[i]["error_count"]) == sum(1 for ok in ref.values() if not ok), (name, dev[i], ref)
+        assert int(dev[i]["valid"]) == int(all(ref.values())), (name, dev[i], ref)

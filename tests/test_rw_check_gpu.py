@@ -2,6 +2,8 @@
 against the host analysis (msim_check_rw_rows, itself compared with tests/elle_ref.py in test_txn_rw_register.py; [upstream] elle is
 not vendored: parity unpinned): the same :valid?, the same counts, and never an anomaly the host does not see; whatever the device
 cannot prove valid it hands to the host, whose result is then the result."""
+import re
+
 import numpy as np
 import pytest
 
@@ -91,3 +93,36 @@ def test_engine_check_uses_the_device_pass(lib):
             rows, pay = eng.raw_history(i)
             host = E.check_rw_history(rows.copy(), pay.copy(), "read-committed")
             assert host["valid?"] is True and int(res[i]["ok_count"]) == host["ok-count"]
+
+
+# a seed per case: no earlier context of this process held these histories' records (a chunk that writes nothing cannot return them)
+@pytest.mark.parametrize("flags,seed", [(0x10000, 41), (0x12000, 42)])
+def test_chunked_device_pass_equals_one_launch_and_the_host(lib, capfd, flags, seed):
+    """MSIM_DEV_FLAGS bit 16: at most 7 histories per launch of rw_check_kernel (rp.first > 0, a partial last chunk of 5) on 61 engine
+    histories (partitions, loss).  The chunked check runs first on the fresh context; its records agree with the host analysis and are
+    byte for byte those of the same launch checked again in one launch."""
+    cfg = _cfg(node_count=3, time_limit=5.0, latency=5, nemesis=("partition",), nemesis_interval=1.5, p_loss=0.03, seed=seed)
+    n = 61
+    with E.Engine(cfg) as eng:
+        eng.run(0, n)
+        eng.set_dev_flags(flags | 0x1000)
+        capfd.readouterr()
+        eng.check()
+        err = capfd.readouterr().err
+        chunked = eng.check_results()
+        eng.set_dev_flags(0)
+        eng.check()
+        whole = eng.check_results()
+        eng.fetch()
+        hs = [(eng.raw_history(i)[0].copy(), eng.raw_history(i)[1].copy()) for i in range(n)]
+    model = {v: k for k, v in E.CONSISTENCY_MODELS.items()}[cfg.consistency_model]
+    for i, (rows, pay) in enumerate(hs):
+        host = E.check_rw_history(rows, pay, model)
+        g = chunked[i]
+        assert {1: True, 0: False, 2: "unknown"}[int(g["valid"])] == host["valid?"], (i, g, host)
+        assert int(g["ok_count"]) == host["ok-count"] and int(g["attempt_count"]) == host["txn-count"], (i, g, host)
+        assert int(g["error_count"]) & ~int(host["anomaly-bits"]) == 0, (i, g, host)
+    assert (chunked["valid"] == 1).all()
+    assert chunked.tobytes() == whole.tobytes()
+    launches = [int(x) for x in re.findall(r"\[rw-check\] device pass \((\d+) launches\)", err)]
+    assert launches == [9], err

@@ -2,6 +2,7 @@
 msim_check_txn_rows — itself held against tests/elle_ref.py and hand-made anomalies in tests/test_txn_list_append.py): every field of
 every history's result, on engine histories (partitions, loss, timeouts), on corrupted ones and on the hand-made anomalous ones."""
 import copy
+import re
 import ctypes as C
 import random
 
@@ -117,3 +118,62 @@ def test_hand_made_anomalies_and_corrupted_histories(lib):
         n_bad += int(dev[i]["valid"]) == 0
     assert [int(v) for v in dev["valid"][:3]] == [1, 0, 0]
     assert n_bad > 40
+
+
+# at most 7 histories per launch: the LDS pass / the HBM-table pass in 9 launches, the last of 5.  A seed per case: no earlier context of
+# this process held these histories' records, so that a check buffer a chunk fails to write cannot hold the right ones by chance
+@pytest.mark.parametrize("flags,seed", [(0x10000, 29), (0x12000, 30)])
+def test_chunked_device_passes_equal_one_launch_and_the_host(lib, capfd, flags, seed):
+    """MSIM_DEV_FLAGS bit 16 makes the chunk loops of txn_dev_run (tp.first > 0, a partial last chunk) reachable at 61 histories.  The
+    chunked check runs FIRST on the fresh context (a chunk whose blocks write nothing leaves what the allocation held, not a record an
+    earlier check wrote); its records are field by field the host analysis, and byte for byte those of the same launch checked again
+    in one launch per pass."""
+    cfg = E.test_config("txn-list-append", node_count=5, rate=100, time_limit=10, latency=5, nemesis=["partition"], nemesis_interval=3, p_loss=0.02, seed=seed)
+    n = 61
+    with E.Engine(cfg) as eng:
+        eng.run(0, n)
+        eng.set_dev_flags(flags | 0x1000)
+        capfd.readouterr()
+        eng.check()
+        err = capfd.readouterr().err
+        chunked = eng.check_results()
+        eng.set_dev_flags(0)
+        eng.check()
+        whole = eng.check_results()
+        eng.fetch()
+        hs = [tuple(a.copy() for a in eng.raw_history(i)) for i in range(n)]   # (copies: the views die with the context)
+    for i, (rows, pay) in enumerate(hs):
+        _same(chunked[i], _host(rows, pay), i)
+    assert (chunked["valid"] == 1).all()
+    assert chunked.tobytes() == whole.tobytes()
+    pass_line = r"LDS pass \(\d+ B per workgroup, (\d+) launches\)" if flags == 0x10000 else r"HBM-table pass over 61 histories \((\d+) launches\)"
+    assert [int(x) for x in re.findall(pass_line, err)] == [9], err
+
+
+@pytest.mark.timeout(300)
+def test_hbm_table_pass_chunks_at_the_cfg5_bench_size(lib, capfd):
+    """cfg5 (tools/bench_configs.py) at its bench size, 32768 histories, all on the HBM-table kernel (bit 13): 32768 workspaces of
+    ws_words_for(nmax, emax) words are far more than the pass's 6 GiB budget, so the pass runs in several launches with no developer bit,
+    the last one partial.  The histories on both sides of every chunk boundary and the last ones equal the host analysis."""
+    cfg = E.test_config("txn-list-append", node_count=5, rate=100, time_limit=30, latency=5, nemesis=["partition"], nemesis_interval=10, seed=99)
+    n = 32768
+    nmax = cfg.max_rows // 2 + 1
+    ws_bytes = (nmax * 11 + 4 + 4096 + 65536 + nmax * 16) * 4    # txn_check_dev.hip: ws_words_for(nmax, emax = 16 nmax), KMAX 4096, WMAX 65536
+    assert n * ws_bytes > 6 << 30
+    chunk = (6 << 30) // ws_bytes
+    launches = -(-n // chunk)
+    assert launches > 1 and n % chunk
+    with E.Engine(cfg) as eng:
+        eng.run(0, n)
+        eng.set_dev_flags(0x3000)
+        capfd.readouterr()
+        eng.check()
+        err = capfd.readouterr().err
+        res = eng.check_results()
+        eng.fetch()
+        assert [int(x) for x in re.findall(r"HBM-table pass over 32768 histories \((\d+) launches\)", err)] == [launches], err
+        assert (res["valid"] == 1).all()
+        idx = sorted({i for b in range(chunk, n, chunk) for i in range(b - 3, b + 3)} | set(range(8)) | set(range(n - 8, n)))
+        for i in idx:
+            rows, pay = eng.raw_history(i)
+            _same(res[i], _host(rows, pay), i)
