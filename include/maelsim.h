@@ -87,7 +87,10 @@ enum {
   MSIM_NODE_TSO_IDS = 13        /* unique-ids over the `lin-tso` timestamp oracle (service.clj:116-132,290-296; doc/services.md): every
                                    `generate` becomes a {type "ts"} RPC to lin-tso, the timestamp is the id.  The reference ships the
                                    service but no demo that uses it; this node (tools/harness_tso_node.py is its process form) is what
-                                   exercises it                                                                                  */
+                                   exercises it                                                                                  */,
+  MSIM_NODE_BCAST_BATCH = 16    /* demo/python/broadcast.py:12-60: one gossip task per topology neighbour, at most one RPC in flight per
+                                   link, carrying everything the neighbour has not acknowledged in one broadcast_many; a 1 s RPC timeout
+                                   (maelstrom.py:89) re-sends.  At most 32 nodes, one cluster per wavefront           */
 };
 
 enum { MSIM_LAT_CONSTANT = 0, MSIM_LAT_UNIFORM = 1, MSIM_LAT_EXPONENTIAL = 2 };  /* net.clj:65-77 */
@@ -207,7 +210,7 @@ typedef struct msim_net_stats {
  * 16 bytes; the event's :id is its position.  Feeds maelstrom.net.checker / net.viz.
  *   time_us : :time in microseconds since test start
  *   msg     : bits 8-31 message :id (net.clj:197), bit 7 = 1 for :recv / 0 for :send, bits 0-6 body :type (MSIM_M_*)
- *   a       : body payload (element / echo k / read payload ref (offset | words<<24) / replicate tick)
+ *   a       : body payload (element / echo k / read payload ref (offset | words<<24) / replicate tick / broadcast_many range from | to<<16)
  *   route   : bits 0-7 src endpoint, 8-15 dest endpoint (nodes 0..n-1, then client slots), 16-31 low 16 bits of
  *             the body's msg_id (requests) or in_reply_to (replies); 0 = none */
 typedef struct msim_event {
@@ -223,7 +226,9 @@ enum { MSIM_M_INIT = 1, MSIM_M_INIT_OK, MSIM_M_TOPOLOGY, MSIM_M_TOPOLOGY_OK, MSI
        MSIM_M_TXN, MSIM_M_TXN_OK, MSIM_M_GENERATE, MSIM_M_GENERATE_OK, MSIM_M_REPLICATE_ACK,
        MSIM_M_TS, MSIM_M_TS_OK /* lin-tso, service.clj:121-123 */,
        MSIM_M_SEND, MSIM_M_SEND_OK, MSIM_M_POLL, MSIM_M_POLL_OK, MSIM_M_LIST_COMMITTED_OFFSETS, MSIM_M_LIST_COMMITTED_OFFSETS_OK,
-       MSIM_M_COMMIT_OFFSETS, MSIM_M_COMMIT_OFFSETS_OK /* workload/kafka.clj:89-139 */ };
+       MSIM_M_COMMIT_OFFSETS, MSIM_M_COMMIT_OFFSETS_OK /* workload/kafka.clj:89-139 */,
+       MSIM_M_BROADCAST_MANY, MSIM_M_BROADCAST_MANY_OK /* demo/python/broadcast.py:27-31,57: the event's `a` is the range
+                                                          [from, to) of the sender's arrival log, from | to << 16 */ };
 
 /* Per-instance bookkeeping (not part of the algorithmic output bytes). */
 typedef struct msim_inst_meta {

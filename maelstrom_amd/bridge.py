@@ -336,7 +336,12 @@ class Bridge:
 
     def __init__(self, workload, bin, node_count=5, concurrency=None, rate=5.0, time_limit=60.0, latency=0, latency_dist="constant",
                  topology="grid", nemesis=(), nemesis_interval=10.0, p_loss=0.0, seed=0, instance=0, client_timeout_ms=5000, quiesce_ms=10000,
-                 settle_ms=3.0, clock="virtual", log_dir=None, journal=False, key_count=10, max_txn_length=4, max_writes_per_key=16):
+                 settle_ms=3.0, clock="virtual", log_dir=None, journal=False, key_count=10, max_txn_length=4, max_writes_per_key=16,
+                 node_factory=None):
+        """`node_factory` (opt-in): node_factory(node_name) -> an in-process node object instead of a process of `bin` per node.  Such a node
+        has handle(message, T) -> [messages it sends] (message = {src, dest, body}, T = virtual microseconds) and may have timers in
+        virtual time: next_timer() -> the earliest one (INF = none) and on_timer(T) -> [messages].  A due timer is the node's one input of
+        the round (R3, before a due envelope) and counts in R0's choice of the next time."""
         if workload not in WORKLOADS:
             raise ValueError(f"workload {workload!r} is not bridged (one of {WORKLOADS})")
         if latency_dist == "exponential" and latency == 0:
@@ -364,8 +369,9 @@ class Bridge:
         self.E = len(self.names)
         self.services = default_services()
         self.svc_ctr = {s: 0 for s in SERVICES}
+        self.nodes = [node_factory(self.names[i]) for i in range(self.N)] if node_factory is not None else None
         argv = bin if isinstance(bin, (list, tuple)) else [bin]
-        self.procs = [NodeProcess(list(argv), self.names[i], log_dir) for i in range(self.N)]
+        self.procs = [] if self.nodes is not None else [NodeProcess(list(argv), self.names[i], log_dir) for i in range(self.N)]
         # net (net.clj:79-103)
         self.inbox = [[] for _ in range(self.E)]
         self.committed = [None] * self.E
@@ -818,6 +824,8 @@ class Bridge:
                 for e in range(E):
                     if self.committed[e] is not None and self.deliver_at[e] < tn:
                         tn = self.deliver_at[e]
+                if self.nodes is not None:
+                    tn = min([tn] + [self.node_timer(n) for n in range(N)])
                 tt = min([c["timeout_at"] for c in self.cl if c["busy"]], default=INF)
                 if tn == INF and tt == INF and not self.out:
                     self.errors.append("stuck: nothing will ever happen")
@@ -851,7 +859,7 @@ class Bridge:
                     self.poll(e)
                 # R3: one input per node, then the services (endpoint order)
                 wrote, owing = False, []
-                for n in range(N):
+                for n in range(N if self.nodes is None else 0):
                     q = self.committed[n]
                     if q is not None and self.deliver_at[n] <= T:
                         self.committed[n] = None
@@ -861,6 +869,8 @@ class Bridge:
                         if q[3].get("type") == "init":
                             owing.append(n)
                 got = self.collect(wrote, owing) if (wrote or self.clock == "real") else {}
+                if self.nodes is not None:
+                    got = self.step_nodes(T)
                 for n in sorted(got):
                     self.ingest(n, got[n])
                 for e in range(N + self.CS, E):
@@ -887,6 +897,27 @@ class Bridge:
             for p in self.procs:
                 p.stop()
         return self.history
+
+    def node_timer(self, n):
+        nt = getattr(self.nodes[n], "next_timer", None)
+        return nt() if nt is not None else INF
+
+    def step_nodes(self, T):
+        """R3 for in-process nodes: a due timer, else the due committed envelope; returns {node: [lines printed]} like collect()"""
+        got = {}
+        for n in range(self.N):
+            if self.node_timer(n) <= T:
+                out = self.nodes[n].on_timer(T)
+            else:
+                q = self.committed[n]
+                if q is None or self.deliver_at[n] > T:
+                    continue
+                self.committed[n] = None
+                self.recv_log(n, q)
+                out = self.nodes[n].handle({"src": self.names[q[2]], "dest": self.names[n], "body": q[3]}, T)
+            if out:
+                got[n] = [json.dumps(m).encode() for m in out]
+        return got
 
     def flush_completions(self):
         for k in sorted(self.pend):

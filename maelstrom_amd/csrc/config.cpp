@@ -94,7 +94,7 @@ extern "C" int msim_config_finalize(msim_config *c, char *err, size_t errlen) {
   bool ok = false;
   switch (c->workload) {
     case MSIM_WL_ECHO: ok = c->node_program == MSIM_NODE_ECHO; break;
-    case MSIM_WL_BROADCAST: ok = c->node_program >= MSIM_NODE_BCAST_FF && c->node_program <= MSIM_NODE_BCAST_RPC_ALL; break;
+    case MSIM_WL_BROADCAST: ok = (c->node_program >= MSIM_NODE_BCAST_FF && c->node_program <= MSIM_NODE_BCAST_RPC_ALL) || c->node_program == MSIM_NODE_BCAST_BATCH; break;
     case MSIM_WL_G_SET: ok = c->node_program == MSIM_NODE_G_SET; break;
     case MSIM_WL_LIN_KV: ok = c->node_program == MSIM_NODE_RAFT || c->node_program == MSIM_NODE_LIN_KV_PROXY; break;
     case MSIM_WL_TXN_LIST_APPEND: ok = c->node_program == MSIM_NODE_TXN_SINGLE_KEY || c->node_program == MSIM_NODE_TXN_MULTI_KEY || c->node_program == MSIM_NODE_TXN_DATOMIC; break;
@@ -184,6 +184,9 @@ extern "C" int msim_config_finalize(msim_config *c, char *err, size_t errlen) {
     uint32_t depth = 32 + 2 * deg + (uint32_t)(per_s * lat_s * 6.0);  // x6: fan-in bursts (every neighbour forwards at once)
     // retrying gossip under partitions: at heal time every neighbour re-sends everything it could not deliver
     if (c->node_program == MSIM_NODE_BCAST_ACK_RETRY && c->nemesis_mask) depth += (deg < 4 ? deg : 4) * adds;
+    // batched gossip: at most one request in flight per directed link (its reply comes back on the same link), + the replies to RPCs that
+    // timed out: one RPC per link per second, each late by up to the latency's tail
+    if (c->node_program == MSIM_NODE_BCAST_BATCH) depth = 32 + 4 * deg + (uint32_t)(2.0 * deg * (lat_s + 1.0));
     // one replicate_full per peer per 5 s tick (g_set.rb:33-38): two ticks' worth, + one per 5 s a message can be under way (1 s exponential: 25 of 4096
     // instances of cfg3's shape overflowed the two-tick queues, profiles/r05_cfg3_latency_sweep.jsonl)
     if (c->node_program == MSIM_NODE_G_SET || c->node_program == MSIM_NODE_PN_COUNTER) depth = 16 + (2 + (uint32_t)(lat_s / 5.0)) * deg;

@@ -113,6 +113,12 @@ extern "C" int msim_create(const msim_config *cfg, int device, msim_ctx **out, c
   }
   if (dt_many && c.n_nodes + c.concurrency + 2 > 64) { set_err(err, errlen, "multi_key_txn / datomic with several workers per node: nodes + workers + 2 services <= 64"); return MSIM_E_UNSUPPORTED; }
   const bool txn_many = (c.node_program == MSIM_NODE_TXN_SINGLE_KEY || c.node_program == MSIM_NODE_KAFKA) && c.concurrency > c.n_nodes;   // txng_kernel<> / kafkag_kernel<>: + the lin-kv lane
+  // (the generic one-cluster-per-wavefront check below refuses the same configurations — `wide` excludes this program; this one only
+  // names the program in the message)
+  if (c.node_program == MSIM_NODE_BCAST_BATCH && (c.n_nodes > 32 || c.n_nodes + (c.concurrency > c.n_nodes ? c.concurrency : c.n_nodes) > 64)) {
+    set_err(err, errlen, "broadcast-batch: one cluster per wavefront only: n_nodes <= 32 and n_nodes + max(concurrency, n_nodes) <= 64");
+    return MSIM_E_UNSUPPORTED;
+  }
   const uint32_t slots = (c.concurrency > c.n_nodes ? c.concurrency : c.n_nodes) + (dt_many ? 2 : txn_many ? 1 : 0);
   // wide clusters (33..127 nodes): two node/client pairs per lane, one worker per node: the g-set CRDT and fire-and-forget broadcast
   const bool wide_prog = c.node_program == MSIM_NODE_G_SET || c.node_program == MSIM_NODE_BCAST_FF || c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK ||
@@ -160,6 +166,8 @@ static uint64_t proto_scratch_words(const msim_config &c) {
   uint64_t w = 4;
   if (c.node_program == MSIM_NODE_RAFT) w = (uint64_t)c.n_nodes * raft_log_cap(c) * 2 + (uint64_t)c.n_nodes * R_ARENA_WORDS;
   if (c.node_program == MSIM_NODE_BCAST_ACK_RETRY) w = (uint64_t)c.n_nodes * c.max_values * 3;
+  // batched gossip: the nodes' u16 arrival logs, then 16 bytes per (node, peer) link (sim_kernel_general.inc g_log / g_link)
+  if (c.node_program == MSIM_NODE_BCAST_BATCH) w = (uint64_t)c.n_nodes * (c.max_values / 2) + (uint64_t)c.n_nodes * c.n_nodes * 4;
   if (c.node_program == MSIM_NODE_TXN_SINGLE_KEY) w = (uint64_t)c.max_values * (c.max_writes_per_key + 1);  // elements + counts per key
   if (c.node_program == MSIM_NODE_TXN_MULTI_KEY)   // elements, counts, map position, entry version, thunk counts, thunk versions + ids, the nodes' caches, the replica bytes
     w = (uint64_t)c.max_values * (c.max_writes_per_key + 4 + 2 * (c.max_writes_per_key + 1)) + (uint64_t)c.n_nodes * mk_ccap(c) + (uint64_t)c.n_nodes * mk_tcap(c) / 4 + 4 +
@@ -326,6 +334,7 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
     case MSIM_NODE_PN_COUNTER: e = wide ? took(msim_launch_wide_pn(kp, n, lds, st), "wide_pn") : took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
     case MSIM_NODE_BCAST_FF: case MSIM_NODE_BCAST_FF_ECHOBACK: e = wide ? took(msim_launch_wide_bcast(kp, n, lds, st), "wide_bcast") : took(msim_launch_general_b(kp, n, lds, st), "general_b"); break;
     case MSIM_NODE_BCAST_ACK_RETRY: case MSIM_NODE_BCAST_RPC_ALL: e = wide ? took(msim_launch_wide_ack(kp, n, lds, st), "wide_ack") : took(msim_launch_general_c(kp, n, lds, st), "general_c"); break;
+    case MSIM_NODE_BCAST_BATCH: e = took(msim_launch_general_d(kp, n, lds, st), "general_d"); break;
     case MSIM_NODE_RAFT: e = took(msim_launch_raft1(kp, n, lds, st), "raft1"); break;
     case MSIM_NODE_LIN_KV_PROXY: case MSIM_NODE_TSO_IDS: e = took(msim_launch_svc1(kp, n, lds, st), "svc1"); break;   // (lin-tso ids: the proxy's layout with the timestamp oracle on the service lane)
     case MSIM_NODE_TXN_SINGLE_KEY: e = txn_many ? took(msim_launch_txng(kp, n, lds, st), "txng") : took(msim_launch_txn1(kp, n, lds, st), "txn1"); break;

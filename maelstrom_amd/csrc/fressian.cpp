@@ -101,13 +101,15 @@ std::string endpoint(uint32_t e, uint32_t n_nodes, uint32_t slots, const msim_co
 const char *const MSG_TYPES[] = {"", "init", "init_ok", "topology", "topology_ok", "echo", "echo_ok", "broadcast", "broadcast_ok", "read", "read_ok",
                                  "add", "add_ok", "replicate", "write", "write_ok", "cas", "cas_ok", "error", "request_vote", "request_vote_res",
                                  "append_entries", "append_entries_res", "txn", "txn_ok", "generate", "generate_ok", "replicate_ack", "ts", "ts_ok",
-                                 "send", "send_ok", "poll", "poll_ok", "list_committed_offsets", "list_committed_offsets_ok", "commit_offsets", "commit_offsets_ok"};
+                                 "send", "send_ok", "poll", "poll_ok", "list_committed_offsets", "list_committed_offsets_ok", "commit_offsets", "commit_offsets_ok",
+                                 "broadcast_many", "broadcast_many_ok"};
 
 bool is_reply(uint32_t t) {
   switch (t) {
     case MSIM_M_INIT_OK: case MSIM_M_TOPOLOGY_OK: case MSIM_M_ECHO_OK: case MSIM_M_BROADCAST_OK: case MSIM_M_READ_OK: case MSIM_M_ADD_OK:
     case MSIM_M_WRITE_OK: case MSIM_M_CAS_OK: case MSIM_M_ERROR: case MSIM_M_REQUEST_VOTE_RES: case MSIM_M_APPEND_ENTRIES_RES: case MSIM_M_TXN_OK:
-    case MSIM_M_GENERATE_OK: case MSIM_M_TS_OK: case MSIM_M_SEND_OK: case MSIM_M_POLL_OK: case MSIM_M_LIST_COMMITTED_OFFSETS_OK: case MSIM_M_COMMIT_OFFSETS_OK: return true;
+    case MSIM_M_GENERATE_OK: case MSIM_M_TS_OK: case MSIM_M_SEND_OK: case MSIM_M_POLL_OK: case MSIM_M_LIST_COMMITTED_OFFSETS_OK: case MSIM_M_COMMIT_OFFSETS_OK:
+    case MSIM_M_BROADCAST_MANY_OK: return true;
     default: return false;
   }
 }
@@ -197,6 +199,7 @@ extern "C" int msim_journal_fressian_rows(const msim_config *cfg, const msim_eve
         else kv_int("value", wl == MSIM_WL_PN_COUNTER || wl == MSIM_WL_G_COUNTER ? (int64_t)(int32_t)e.a : (int64_t)e.a);
         break;
       case MSIM_M_ERROR: kv_int("code", e.a); break;
+      case MSIM_M_BROADCAST_MANY_OK: break;   // (a broadcast_many is written elided: its values are a range of the sender's arrival log in engine scratch)
       case MSIM_M_TS: break;
       case MSIM_M_TS_OK: kv_int("ts", e.a); break;   // service.clj:123
       case MSIM_M_GENERATE_OK:

@@ -22,7 +22,9 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
   u32 *const seen = reinterpret_cast<u32 *>(smem + p.off_seen);
   u32 *const misc = reinterpret_cast<u32 *>(smem + p.off_misc);
 
-  constexpr bool IS_BCAST = PROG >= MSIM_NODE_BCAST_FF && PROG <= MSIM_NODE_BCAST_RPC_ALL;
+  // batched gossip (broadcast.py, DESIGN.md §2.4): per link an acknowledged prefix of the node's arrival log, one RPC in flight
+  constexpr bool IS_BATCH = PROG == MSIM_NODE_BCAST_BATCH;
+  constexpr bool IS_BCAST = (PROG >= MSIM_NODE_BCAST_FF && PROG <= MSIM_NODE_BCAST_RPC_ALL) || IS_BATCH;
   constexpr bool IS_RPC = PROG == MSIM_NODE_BCAST_ACK_RETRY || PROG == MSIM_NODE_BCAST_RPC_ALL;
   constexpr bool IS_ACK = PROG == MSIM_NODE_BCAST_ACK_RETRY;
   constexpr bool IS_PN = PROG == MSIM_NODE_PN_COUNTER;    // pn_counter.rb: same replication skeleton as g-set, counters instead of a set
@@ -31,11 +33,11 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
   constexpr bool IS_FLAKE = PROG == MSIM_NODE_FLAKE_IDS;  // flake_ids.clj: unique-ids workload, Reusable clients (unique_ids.clj:59-61)
   constexpr bool HAS_FINAL = IS_BCAST || IS_GSET;
   constexpr bool FINAL_FLAG = IS_BCAST || IS_PN;  // :final? true on the last reads (broadcast.clj:240, pn_counter.clj:137)
-  constexpr bool HAS_TIMERS = IS_ACK || IS_GSET;
-  constexpr bool REP_FIRST = IS_ACK;  // the ack variant replies before it gossips
-  constexpr u32 FAN_TYPE = IS_GSET ? M_REPLICATE : M_BROADCAST;
+  constexpr bool HAS_TIMERS = IS_ACK || IS_GSET || IS_BATCH;
+  constexpr bool REP_FIRST = IS_ACK || IS_BATCH;  // the ack variant and batched gossip reply before they gossip
+  constexpr u32 FAN_TYPE = IS_GSET ? M_REPLICATE : IS_BATCH ? M_BROADCAST_MANY : M_BROADCAST;
   // fan-outs of these programs only ever go to topology neighbours
-  constexpr bool TOPO_BOUND = PROG == MSIM_NODE_BCAST_FF || PROG == MSIM_NODE_BCAST_FF_ECHOBACK || IS_ACK;
+  constexpr bool TOPO_BOUND = PROG == MSIM_NODE_BCAST_FF || PROG == MSIM_NODE_BCAST_FF_ECHOBACK || IS_ACK || IS_BATCH;
   // programs whose server<->server traffic is plain gossip (no msg_id, no reply): eligible for the cascade loop
   constexpr bool FAST_OK = PROG == MSIM_NODE_BCAST_FF || PROG == MSIM_NODE_BCAST_FF_ECHOBACK;
 
@@ -61,6 +63,10 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
   // ack/retry scratch: unacked[N][V], fifo[N][V][2]; g-set scratch: snapshots[tick][N][W]
   u32 *const g_unacked = g_scr + (size_t)lane * max_values;
   u32 *const g_fifo = g_scr + (size_t)N * max_values + (size_t)lane * max_values * 2;
+  // batched gossip scratch: arrival logs u16[N][V], then links uint4[N][N] = {acknowledged prefix, end of the batch in flight,
+  // its RPC id, its deadline} of link (node, peer)
+  uint16_t *const g_log = reinterpret_cast<uint16_t *>(g_scr);
+  uint4 *const g_link = reinterpret_cast<uint4 *>(g_scr + (size_t)N * (max_values / 2));
 
   const u32 jcap = p.cfg.journal_capacity;  // net journal (journal.clj:53,220-239); 0 = off
   uint4 *const g_ev = p.journal + (size_t)inst * jcap;
@@ -72,6 +78,7 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
 
   for (u32 i = lane; i < N * W; i += 64) seen[i] = 0;
   if (IS_ACK) { if (is_node) for (u32 v = 0; v < max_values; v++) g_unacked[v] = 0; }
+  if (IS_BATCH) { if (is_node) for (u32 k = 0; k < N; k++) g_link[lane * N + k] = make_uint4(0, 0, 0, INF); }
   __syncthreads();
 
   const u32 adj = is_node ? topo_adj(p.cfg.topology, N, lane) : 0;
@@ -86,6 +93,7 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
   u32 node_msgid = 0, timer_next = INF, tick = 0, part = 0;
   u32 flake_time = 0, flake_count = 0;  // flake_ids.clj:10-14
   u32 fifo_head = 0, fifo_tail = 0, retry_time = INF;
+  u32 logn = 0, infl = 0;  // batched gossip: length of the arrival log, links with an RPC in flight (bit = peer)
   bool busy = false, mark = false; u32 kind = K_NONE;
   u32 want = 0, timeout_at = 0, next_msg_id = 0, c_f = 0, c_value = 0, process = slot, c_final = 0;
   u32 dest_node = is_client ? slot % N : 0;  // nodes[process mod n] [upstream], kept incrementally
@@ -165,10 +173,12 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
       const u32 as = lane_get(fan_a, s);
       const u32 os = lane_get(id_off, s);
       u32 bs = 0;
-      if (IS_RPC) bs = lane_get(fan_b0, s);
+      if (IS_RPC || IS_BATCH) bs = lane_get(fan_b0, s);
       if (has && ((fs >> lane) & 1)) {
         const u32 rank = __popc(fs & lt32);
-        arrive(next_id + os + rank, FAN_TYPE, as, IS_RPC ? bs + rank : 0u, s);
+        // batched gossip: the batch is [acknowledged prefix of link (s, lane), fan_a = s's log length), the RPC ids ascend with the peer
+        const u32 a = IS_BATCH ? (g_link[s * N + lane].x | (as << 16)) : as;
+        arrive(next_id + os + rank, FAN_TYPE, a, (IS_RPC || IS_BATCH) ? bs + rank : 0u, s);
       }
     }
   };
@@ -393,7 +403,9 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
       bool rep = false; u32 rep_dest = 0, rep_type = 0, rep_a = 0, rep_b = 0;
       bool rd = false;
       u64 jd_mask = 0;  // nodes delivering an envelope this round (their :recv events come first, node order)
-      if (jcap) jd_mask = __ballot(is_node && !(IS_GSET && timer_next <= T) && !(IS_ACK && retry_time <= T) && has_c && deliver_at <= T);
+      if (jcap) jd_mask = __ballot(is_node && !((IS_GSET || IS_BATCH) && timer_next <= T) && !(IS_ACK && retry_time <= T) && has_c && deliver_at <= T);
+      u32 bsend = 0;                                  // batched gossip: links that send a new batch in this input
+      bool grew = false, mrg = false; u32 mrg_a = 0;  // ... the log grew / a broadcast_many range to merge (wavefront pass below)
       if (is_node) {
         if (IS_GSET && timer_next <= T) {  // g_set.rb:33-38
           timer_next = T + 5000000u;
@@ -411,11 +423,34 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
             g_fifo[ts] = v; g_fifo[ts + 1] = T + 1000000u; fifo_tail++;
           }
           retry_time = fifo_head < fifo_tail ? g_fifo[(fifo_head % max_values) * 2 + 1] : INF;
+        } else if (IS_BATCH && timer_next <= T) {  // the node's timer input: every RPC whose 1 s ran out (maelstrom.py:89-98) is sent again
+          u32 m = infl, tmin = INF;
+          while (m) {
+            const u32 k = (u32)__builtin_ctz(m); m &= m - 1;
+            const u32 dl = g_link[lane * N + k].w;
+            if (dl <= T) bsend |= 1u << k; else tmin = min(tmin, dl);
+          }
+          timer_next = tmin;
         } else if (has_c && deliver_at <= T) {
           const uint4 q = cm; has_c = false;
           const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
           if (qsrc >= N) s_recv_cl++; else s_recv_sv++;  // journal :recv (net.clj:244)
           if (jcap) jwrite(n_ev + (u32)__popcll(jd_mask & lt_mask), 1, q.y, qa, qb, qsrc, lane);
+          if (IS_BATCH && qtype == M_BROADCAST_MANY) {  // broadcast.py:27-31: merged by the wavefront below, then broadcast_many_ok
+            mrg = true; mrg_a = qa; rep = true; rep_dest = qsrc; rep_type = M_BROADCAST_MANY_OK; rep_b = qb;
+          } else if (IS_BATCH && qtype == M_BROADCAST_MANY_OK) {  // broadcast.py:59-60: the batch in flight is acknowledged; a late reply (maelstrom.py:100,153) does nothing
+            if ((infl >> qsrc) & 1) {
+              uint4 l = g_link[lane * N + qsrc];
+              if (l.z == qb) {
+                l.x = l.y; l.w = INF; g_link[lane * N + qsrc] = l;
+                infl &= ~(1u << qsrc);
+                if (l.x < logn) bsend = 1u << qsrc;  // more arrived meanwhile: the next batch goes at once
+                u32 m = infl, tmin = INF;
+                while (m) { const u32 k = (u32)__builtin_ctz(m); m &= m - 1; tmin = min(tmin, g_link[lane * N + k].w); }
+                timer_next = tmin;
+              }
+            }
+          } else
           switch (qtype) {
             case M_INIT:
               if (IS_GSET) timer_next = T;
@@ -444,6 +479,12 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
             } break;
             case M_BROADCAST: {
               const u32 v = qa, bitm = 1u << (v & 31);
+              if (IS_BATCH) {  // broadcast.py:12-24
+                const u32 wv = my_seen[v >> 5];
+                if (!(wv & bitm)) { my_seen[v >> 5] = wv | bitm; if (logn < max_values) g_log[(size_t)lane * max_values + logn] = (uint16_t)v; logn++; grew = true; }
+                rep = true; rep_dest = qsrc; rep_type = M_BROADCAST_OK; rep_a = v; rep_b = qb;
+                break;
+              }
               const u32 wv = my_seen[v >> 5];
               if (!(wv & bitm)) {
                 my_seen[v >> 5] = wv | bitm;
@@ -467,6 +508,53 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
         }
       }
 
+      if (IS_BATCH) {
+        // merge the received ranges, one receiver at a time, 64 values per step: every lane tests one value against the receiver's
+        // set, the new ones are compacted by a prefix count and appended to its arrival log (a batch has no duplicates)
+        u64 mm = __ballot(mrg);
+        if (mm) {
+          __syncthreads();  // the senders' logs and the sets in LDS were written by other lanes
+          while (mm) {
+            const u32 r = (u32)__builtin_ctzll(mm); mm &= mm - 1;
+            const u32 s = rdlane(rep_dest, r), ra = rdlane(mrg_a, r);
+            const u32 from = ra & 0xFFFFu, to = min(ra >> 16, max_values);
+            const uint16_t *src_log = g_log + (size_t)s * max_values;
+            uint16_t *dst_log = g_log + (size_t)r * max_values;
+            u32 *rset = seen + r * W;
+            const u32 n0 = rdlane(logn, r);
+            u32 n = n0;
+            for (u32 b = from; b < to; b += 64) {
+              const u32 i = b + lane;
+              const u32 v = i < to ? (u32)src_log[i] : 0u;
+              const bool fresh = i < to && !((rset[v >> 5] >> (v & 31)) & 1u);
+              const u64 fm = __ballot(fresh);
+              if (fresh) {
+                const u32 at = n + (u32)__popcll(fm & lt_mask);
+                if (at < max_values) dst_log[at] = (uint16_t)v;
+                atomicOr(&rset[v >> 5], 1u << (v & 31));
+              }
+              n += (u32)__popcll(fm);
+            }
+            if (lane == r) { logn = n; grew = n != n0; }
+          }
+        }
+        // a grown log wakes every idle link (broadcast.py:16-17,51-56); new RPCs in ascending peer order, ids from the node's one counter
+        if (is_node) {
+          if (grew) bsend = adj & ~infl;
+          if (bsend) {
+            u32 m = bsend, id = node_msgid;
+            while (m) {
+              const u32 k = (u32)__builtin_ctz(m); m &= m - 1;
+              uint4 l = g_link[lane * N + k];
+              l.y = logn; l.z = ++id; l.w = T + 1000000u;
+              g_link[lane * N + k] = l;
+            }
+            fan_mask = bsend; fan_a = logn; fan_b0 = node_msgid + 1; node_msgid = id;
+            infl |= bsend; timer_next = min(timer_next, T + 1000000u);
+          }
+        }
+        if (__ballot(bsend != 0)) __syncthreads();  // the receivers read the senders' acknowledged prefixes (commit_fan)
+      }
       n_ev += (u32)__popcll(jd_mask);
       // read results: the whole wave copies the node's set LDS -> HBM payload (256 B per instruction)
       {

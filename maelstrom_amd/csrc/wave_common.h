@@ -16,6 +16,8 @@
 enum { M_INIT = 1, M_INIT_OK, M_TOPOLOGY, M_TOPOLOGY_OK, M_ECHO, M_ECHO_OK, M_BROADCAST, M_BROADCAST_OK,
        M_READ, M_READ_OK, M_ADD, M_ADD_OK, M_REPLICATE };
 enum { M_GENERATE = 25, M_GENERATE_OK = 26 };  // unique-ids (after the raft and txn types, include/maelsim.h MSIM_M_*)
+enum { M_BROADCAST_MANY = 38, M_BROADCAST_MANY_OK = 39 };  // batched gossip (after the kafka types)
+static_assert(M_BROADCAST_MANY == MSIM_M_BROADCAST_MANY && M_BROADCAST_MANY_OK == MSIM_M_BROADCAST_MANY_OK, "kernel message types mirror include/maelsim.h");
 // RNG streams
 enum { S_GEN = 1, S_GEN2 = 2, S_LATENCY = 4, S_LOSS = 5,
        S_NEM_STAGGER = 7, S_NEM_SPEC = 8, S_NEM_SHUFFLE = 9, S_NEM_PICK = 10 };
@@ -166,6 +168,7 @@ static const hipError_t MSIM_LAYOUT_DOES_NOT_FIT = static_cast<hipError_t>(0x7F0
 hipError_t msim_launch_general_a(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);   // echo, flake ids, g-set, the counters
 hipError_t msim_launch_general_b(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);   // fire-and-forget broadcast
 hipError_t msim_launch_general_c(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);   // acknowledged gossip, rpc-to-all
+hipError_t msim_launch_general_d(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);   // batched gossip
 hipError_t msim_launch_wide_gset(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);
 hipError_t msim_launch_wide_bcast(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);
 hipError_t msim_launch_wide_ack(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);

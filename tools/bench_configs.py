@@ -18,6 +18,9 @@ CONFIGS = {
     "cfg2 broadcast n=25 total lat100": (dict(workload="broadcast", node_count=25, rate=100, time_limit=20, latency=100, topology="total"), 1024),
     "broadcast n=25 ack-retry + partitions": (dict(workload="broadcast", bin="broadcast-ack-retry", node_count=25, rate=100, time_limit=20, latency=10,
                                                    nemesis=["partition"], nemesis_interval=10), 2048),
+    # demo/python/broadcast.py: batched gossip (one broadcast_many in flight per link), cfg2's shape
+    "broadcast-batch n=25 grid lat0": (dict(workload="broadcast", bin="broadcast-batch", node_count=25, rate=100, time_limit=20), 4096),
+    "broadcast-batch n=25 grid lat100": (dict(workload="broadcast", bin="broadcast-batch", node_count=25, rate=100, time_limit=20, latency=100), 4096),
     "g-set n=25 lat100 exponential p_loss 0.05": (dict(workload="g-set", node_count=25, rate=100, time_limit=20, latency=100, latency_dist="exponential", p_loss=0.05), 4096),
     "cfg3 g-set n=100 lat100 exponential": (dict(workload="g-set", node_count=100, rate=100, time_limit=20, latency=100, latency_dist="exponential"), 16384),
     "cfg3 g-set n=100 lat100 exponential p_loss 0.05": (dict(workload="g-set", node_count=100, rate=100, time_limit=20, latency=100, latency_dist="exponential", p_loss=0.05), 16384),
