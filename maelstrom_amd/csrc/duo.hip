@@ -101,6 +101,10 @@ __device__ __forceinline__ u32 half_min(u32 v, bool hi) {
   const u32 lo = min(rdlane(v, 0), rdlane(v, 16)), up = min(rdlane(v, 32), rdlane(v, 48));
   return hi ? up : lo;
 }
+// A ballot of one compare is that compare's lane mask; a ballot of a bool built from several compares (a & b, a | b) costs two more
+// vector instructions (the mask is turned into 0 / 1 and compared again).  Hot paths therefore combine the ballots of single compares
+// with scalar operations: bal(a) & bal(b) == bal(a & b), bal(a) | bal(b) == bal(a | b).
+__device__ __forceinline__ u64 bal(bool pred) { return __ballot(pred); }
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
 
 template <bool LAT0, bool DEG4, bool RND>
@@ -333,7 +337,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     DUO_SW_PREFETCH();                                                                                                    \
   } while (0)
   // R3 for a broadcast envelope (gossip or the client's own): dedup against the node's set; pub_ = what the node publishes
-  // to its neighbours: bit 31 | value | src to skip << 16, or 0
+  // to its neighbours: bit 31 | value | src to skip << 16, or 0; hball_ = the ballot of handle_, pubb_ = the ballot of pub_ != 0
 #ifdef DUO_NO_SWPF   /* A/B build: the set word is read where it is used */
 #define DUO_SW_PREFETCH() do { } while (0)
 #define DUO_SW_NOW() do { sw = *DUO_SEEN_WORD(); } while (0)
@@ -341,10 +345,11 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 #define DUO_SW_PREFETCH() do { sw = *DUO_SEEN_WORD(); } while (0)
 #define DUO_SW_NOW() do { } while (0)
 #endif
-#define DUO_R3_SEEN(handle_, pub_) do {                                                                                   \
+#define DUO_R3_SEEN(handle_, hball_, pub_, pubb_) do {                                                                    \
     DUO_SW_NOW();                                                                                                         \
     const u32 r3_bit = 1u << (cm & 31u);                                                                                  \
     const bool r3_new = (handle_) & ((sw & r3_bit) == 0);                                                                 \
+    pubb_ = (hball_) & bal((sw & r3_bit) == 0);                                                                           \
     if (r3_new) *DUO_SEEN_WORD() = sw | r3_bit;                                                                           \
     pub_ = r3_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                                \
   } while (0)
@@ -391,16 +396,21 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
           }                                                                                                               \
         }                                                                                                                 \
       } else if (__builtin_expect(!__ballot((in_n + 4u > R) | (sp_n != 0)), 1)) {                                         \
-        /* every ring has room for a full round of arrivals: plain stores at the tail, the count decides what stays */    \
+        /* every ring has room for a full round of arrivals: plain stores at the tail, the count decides what stays; the     \
+           tail runs unwrapped (head + in_n) and in_n is recovered from it once */                                        \
         const u32 ar_in0 = in_n;                                                                                          \
+        u32 ar_s = head + in_n;                                                                                           \
+        bool ar_g[4]; u32 ar_e[4];                                                                                        \
         _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                          \
-          const bool ar_got = (int)((ar_x[ar_k] & 0x803F0000u) ^ ar_zk) > 0;                                              \
-          const u32 ar_e = (ar_x[ar_k] & 0xFFFFu) | kc[ar_k];                                                             \
-          DUO_RING_STORE((head + in_n) & Rm, ar_e, ar_dl);                                                                \
-          const bool ar_first = ar_got & (in_n == 0);                                                                     \
-          nx = ar_first ? ar_e : nx; if (!LAT0) nx_dl = ar_first ? ar_dl : nx_dl;                                         \
-          in_n += ar_got ? 1u : 0u;                                                                                       \
+          ar_g[ar_k] = (int)((ar_x[ar_k] & 0x803F0000u) ^ ar_zk) > 0;                                                     \
+          ar_e[ar_k] = (ar_x[ar_k] & 0xFFFFu) | kc[ar_k];                                                                 \
+          DUO_RING_STORE(ar_s & Rm, ar_e[ar_k], ar_dl);                                                                   \
+          ar_s += ar_g[ar_k] ? 1u : 0u;                                                                                   \
         }                                                                                                                 \
+        /* an empty ring's new head entry is its first arrival (nx means nothing while the ring stays empty) */          \
+        const u32 ar_f = ar_g[0] ? ar_e[0] : ar_g[1] ? ar_e[1] : ar_g[2] ? ar_e[2] : ar_e[3];                             \
+        nx = ar_in0 == 0 ? ar_f : nx; if (!LAT0) nx_dl = ar_in0 == 0 ? ar_dl : nx_dl;                                     \
+        in_n = ar_s - head;                                                                                               \
         n_arr += in_n - ar_in0;                                                                                           \
       } else {                                                                                                            \
         _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                          \
@@ -479,14 +489,16 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0, 0)) {
           const bool none_due = hi ? (u32)(db >> 32) == 0 : (u32)db == 0;
           const bool idle_h = (alive != 0) & (sched_at > T) & none_due;
-          if (__ballot(idle_h)) {
+          const u64 nd_b = ((u32)db == 0 ? 0xFFFFFFFFull : 0ull) | ((u32)(db >> 32) == 0 ? 0xFFFFFFFF00000000ull : 0ull);
+          const u64 idle_b = bal(alive != 0) & bal(sched_at > T) & nd_b;
+          if (idle_b) {
             const u32 km = min(half_min(deliver_at, hi), sched_at);
             const bool stuck = idle_h & (km == INF);   // nothing will ever happen (oracle: same flag, the round counts)
             flags |= stuck ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u;
             alive = stuck ? 0u : alive; sched_at = stuck ? INF : sched_at; force_general = stuck ? 0u : force_general;
             rounds += stuck ? 1u : 0u;
             T = (idle_h & !stuck) ? km : T;
-            stuck_any = __ballot(stuck) != 0;
+            stuck_any = (idle_b & bal(km == INF)) != 0;
             due_n = deliver_at <= T;
           }
           // the round limit is looked at here and in GENERAL rounds (a stretch of pure gossip always ends in one of the two)
@@ -494,16 +506,17 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         }
       }
       rounds += alive;
-      const bool special = due_n & ((cm >> 24) != DK_PLAIN);
-      const bool gen = (alive != 0) & ((force_general != 0) | (sched_at <= T) | special);
-      if (__ballot(gen) != 0 || stuck_any) break;   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
+      // GENERAL if alive & (force_general | sched_at <= T | special), special = due_n & (cm >> 24) != DK_PLAIN
+      const u64 due_b = bal(due_n);
+      const u64 gen_b = bal(alive != 0) & (bal(force_general != 0) | bal(sched_at <= T) | (due_b & bal(cm > 0xFFFFFFu)));
+      if (gen_b != 0 || stuck_any) break;   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
       {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
-        u32 pub; DUO_R3_SEEN(due_n, pub);
+        u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
         deliver_at = due_n ? INF : deliver_at;
         n_rsv += due_n ? 1u : 0u;
         P2_MARK(1)
-        if (__ballot(pub != 0)) {
+        if (pub_b) {
           if (RND) DUO_RND_IDS(pub, false);
           P2_MARK(2)
           DUO_ARRIVALS(pub);
@@ -523,12 +536,13 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     // ---- R1: scheduler (core.clj:67-80): phase actions, one generated op ----
     u32 mark = 0, m_kind = 0, m_val = 0;
     const bool act = alive != 0 && sched_at <= T;
-    if (__ballot(act && phase != PH_MAIN)) {   // rare: db setup, topology, final reads
+    const u64 act_b = bal(alive != 0) & bal(sched_at <= T);
+    if (act_b & bal(phase != PH_MAIN)) {   // rare: db setup, topology, final reads
       if (act && phase == PH_INIT) { mark = is_node; m_kind = DK_INIT; phase = PH_INIT_WAIT; }
       else if (act && phase == PH_TOPO) { mark = is_node; m_kind = DK_TOPO; phase = PH_TOPO_WAIT; }
       else if (act && (phase == PH_SLEEP || phase == PH_FINAL)) { mark = is_node; m_kind = DK_READ_FINAL; phase = PH_FINAL_WAIT; }  // broadcast.clj:240
     }
-    if (__ballot(act && phase == PH_MAIN)) {
+    if (act_b & bal(phase == PH_MAIN)) {
       const u32 free_mask = all_nodes & ~hb(busy != 0, hi);
       const bool gen = act && phase == PH_MAIN && rate > 0 && gen_next < cutoff && gen_next <= T && free_mask != 0;
       // one 64-bit draw per generated op: high word -> stagger, low word -> worker pick / gen/mix
@@ -552,7 +566,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     }
     P3_MARK(1)   // [1] = R1 scheduler
     // ---- R2: marked clients invoke; the request reaches this lane's own node (no latency: a client is involved) ----
-    if (__ballot(mark != 0 && alive != 0)) {
+    if (bal(mark != 0) & bal(alive != 0)) {
       const bool inv = mark != 0 && alive != 0;
       busy = inv ? 1u : busy;
       const bool is_op = inv && m_kind <= DK_READ_FINAL;
@@ -577,9 +591,10 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     P3_MARK(2)   // [2] = R2 invoke + poll
     // ---- R3: one input per node: the due envelope ----
     const bool due_n = alive != 0 && deliver_at <= T;
+    const u64 due_b = bal(alive != 0) & bal(deliver_at <= T);
     const u32 kind = cm >> 24;
     const u32 v = cm & 0xFFFFu;
-    u32 pub; DUO_R3_SEEN(due_n & (kind <= DK_BCAST), pub);
+    u32 pub; u64 pub_b; DUO_R3_SEEN(due_n & (kind <= DK_BCAST), due_b & bal(kind <= DK_BCAST), pub, pub_b);
     deliver_at = due_n ? INF : deliver_at;
     n_rsv += (due_n && kind == DK_PLAIN) ? 1u : 0u;
     const bool req = due_n && kind != DK_PLAIN;   // a request of this lane's client: handled, answered and completed in this round
@@ -589,7 +604,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     cmp_row = (req && kind == DK_BCAST) ? 1u : 0u;
     cmp_packed = MSIM_T_OK | (MSIM_F_BROADCAST << 2) | (i << 12); cmp_value = v;
     // read -> read_ok with the whole set: the cluster's lanes copy the node's set LDS -> HBM payload
-    if (__ballot(rd)) {
+    if (due_b & bal(kind - (u32)DK_READ < 2u)) {   // (= ballot of rd: kind is DK_READ or DK_READ_FINAL)
       wave_lds_fence();
       const u32 rdm = hb(rd, hi);
       const u32 words = (next_value + 31u) >> 5;
@@ -622,7 +637,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 
     P3_MARK(3)   // [3] = R3 (dedup, read copies)
     if (RND) { if (__ballot((pub != 0) | req)) DUO_RND_IDS(pub, req); }
-    if (__ballot(pub != 0)) DUO_ARRIVALS(pub);
+    if (pub_b) DUO_ARRIVALS(pub);
     P3_MARK(4)   // [4] = ids + arrivals
     DUO_POLL();
     P3_MARK(5)   // [5] = poll
@@ -660,7 +675,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     // ---- the scheduler's view for the rounds to come: time-free phase transitions (oracle: sched_resolve), when it
     //      acts next (sched_due), and whether plain gossip rounds may run meanwhile ----
     const u32 hbusy = hb(busy != 0, hi);
-    if (__ballot(alive != 0 && (phase != PH_MAIN || !(rate > 0 && gen_next < cutoff) || rounds > round_limit))) {
+    if (bal(alive != 0) & (bal(phase != PH_MAIN) | (rate > 0 ? bal(gen_next >= cutoff) : bal(true)) | bal(rounds > round_limit))) {
       for (;;) {
         bool ch = false;
         if (alive != 0) {
