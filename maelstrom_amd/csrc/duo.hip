@@ -105,6 +105,10 @@ __device__ __forceinline__ u32 half_min(u32 v, bool hi) {
 // vector instructions (the mask is turned into 0 / 1 and compared again).  Hot paths therefore combine the ballots of single compares
 // with scalar operations: bal(a) & bal(b) == bal(a & b), bal(a) | bal(b) == bal(a | b).
 __device__ __forceinline__ u64 bal(bool pred) { return __ballot(pred); }
+// A per-cluster boolean kept as a lane mask in SGPRs (all 32 bits of a half set or clear): a test of it costs scalar work only, bal() of it is
+// the mask itself, and a per-lane use reads the lane's bit (lane_in)
+__device__ __forceinline__ u64 hm2(bool lo, bool up) { return (lo ? 0xFFFFFFFFull : 0ull) | (up ? 0xFFFFFFFF00000000ull : 0ull); }
+__device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
 
 template <bool LAT0, bool DEG4, bool RND>
@@ -197,10 +201,11 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   u32 pbase = 0;             // RND (per lane): id of the first message this node sends in the current round
   const u32 lat_mean = p.cfg.latency_mean_ms;
   const bool lat_uniform = p.cfg.latency_dist == MSIM_LAT_UNIFORM;
-  u32 alive = real ? 1u : 0u;
-  // when the scheduler next acts (INF: it only waits), and whether every round has to be a GENERAL one until it says otherwise;
-  // both change in GENERAL rounds only
-  u32 sched_at = real ? 0u : INF, force_general = alive;
+  // the clusters still running, and those whose every round has to be a GENERAL one until the scheduler says otherwise: lane masks
+  // (hm2 / lane_in); when the scheduler next acts (INF: it only waits).  All three change in GENERAL rounds and at time jumps only.
+  u64 alive_m = bal(real), fg_m = alive_m;
+  u32 alive_v = real ? 1u : 0u;   // lane_in(alive_m) as 0 / 1, for the round count of every wave-round (one add, no select)
+  u32 sched_at = real ? 0u : INF;
   // The generator's draws (one 64-bit draw per generated op, stream S_GEN, counter gen_k) are computed 32 at a time: lane i of a cluster
   // holds draw dc_base + i, the scheduler fetches the one it needs with two ds_bpermute (mix64's three 64-bit multiplications cost a
   // round of the scheduler a quarter of its cycles when every lane computed the same draw)
@@ -474,6 +479,9 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 #define P3_MARK(i_)
 #endif
   for (;;) {
+    // the halves whose scheduler wants a GENERAL round, alive & (force_general | sched_at <= T): recomputed where its parts change (after a
+    // GENERAL round, at a time jump, at the round limit); a gossip round adds the halves with a special envelope due
+    u64 want_m = alive_m & (fg_m | bal(sched_at <= T));
     // ---- gossip rounds of both clusters, until one of them needs a GENERAL round ----
     for (;;) {
 #ifdef DUO_PROF
@@ -482,34 +490,33 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
       // R0: the cluster's time: stay at T while something is due, else jump to the next delivery / scheduler event.
       // Only looked at when one of the two clusters has nothing due (a scalar test on the halves of one ballot).
       P2_MARK(4)
-      bool due_n = deliver_at <= T;
+      u64 due_b = bal(deliver_at <= T);   // (a mask, not a bool: a bool two paths define is turned into 0 / 1 and compared again)
       bool stuck_any = false;
       {
-        const u64 db = __ballot(due_n);
+        const u64 db = due_b;
         if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0, 0)) {
-          const bool none_due = hi ? (u32)(db >> 32) == 0 : (u32)db == 0;
-          const bool idle_h = (alive != 0) & (sched_at > T) & none_due;
-          const u64 nd_b = ((u32)db == 0 ? 0xFFFFFFFFull : 0ull) | ((u32)(db >> 32) == 0 ? 0xFFFFFFFF00000000ull : 0ull);
-          const u64 idle_b = bal(alive != 0) & bal(sched_at > T) & nd_b;
+          const u64 idle_b = alive_m & bal(sched_at > T) & hm2((u32)db == 0, (u32)(db >> 32) == 0);
           if (idle_b) {
             const u32 km = min(half_min(deliver_at, hi), sched_at);
-            const bool stuck = idle_h & (km == INF);   // nothing will ever happen (oracle: same flag, the round counts)
+            const u64 stuck_b = idle_b & bal(km == INF);   // nothing will ever happen (oracle: same flag, the round counts)
+            const bool stuck = lane_in(stuck_b);
             flags |= stuck ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u;
-            alive = stuck ? 0u : alive; sched_at = stuck ? INF : sched_at; force_general = stuck ? 0u : force_general;
+            sched_at = stuck ? INF : sched_at;
             rounds += stuck ? 1u : 0u;
-            T = (idle_h & !stuck) ? km : T;
-            stuck_any = (idle_b & bal(km == INF)) != 0;
-            due_n = deliver_at <= T;
+            alive_m &= ~stuck_b; fg_m &= ~stuck_b; alive_v = stuck ? 0u : alive_v;
+            T = lane_in(idle_b & ~stuck_b) ? km : T;
+            stuck_any = stuck_b != 0;
+            due_b = bal(deliver_at <= T);
           }
           // the round limit is looked at here and in GENERAL rounds (a stretch of pure gossip always ends in one of the two)
-          force_general = (alive != 0 && rounds >= round_limit) ? 1u : force_general;
+          fg_m |= alive_m & bal(rounds >= round_limit);
+          want_m = alive_m & (fg_m | bal(sched_at <= T));
         }
       }
-      rounds += alive;
+      rounds += alive_v;
+      const bool due_n = lane_in(due_b);
       // GENERAL if alive & (force_general | sched_at <= T | special), special = due_n & (cm >> 24) != DK_PLAIN
-      const u64 due_b = bal(due_n);
-      const u64 gen_b = bal(alive != 0) & (bal(force_general != 0) | bal(sched_at <= T) | (due_b & bal(cm > 0xFFFFFFu)));
-      if (gen_b != 0 || stuck_any) break;   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
+      if ((want_m | (alive_m & due_b & bal(cm > 0xFFFFFFu))) != 0 || stuck_any) break;   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
       {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
         u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
@@ -525,7 +532,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         DUO_POLL();
       }
     }
-    if (!__ballot(alive != 0)) break;
+    if (!alive_m) break;
 #ifdef DUO_PROF
     const u64 pf_a = __builtin_readcyclecounter();
 #endif
@@ -535,8 +542,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     u32 cmp_row = 0, cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     // ---- R1: scheduler (core.clj:67-80): phase actions, one generated op ----
     u32 mark = 0, m_kind = 0, m_val = 0;
-    const bool act = alive != 0 && sched_at <= T;
-    const u64 act_b = bal(alive != 0) & bal(sched_at <= T);
+    const u64 act_b = alive_m & bal(sched_at <= T);
+    const bool act = lane_in(act_b);
     if (act_b & bal(phase != PH_MAIN)) {   // rare: db setup, topology, final reads
       if (act && phase == PH_INIT) { mark = is_node; m_kind = DK_INIT; phase = PH_INIT_WAIT; }
       else if (act && phase == PH_TOPO) { mark = is_node; m_kind = DK_TOPO; phase = PH_TOPO_WAIT; }
@@ -556,7 +563,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
       const bool sel = gen && is_node && busy == 0 && (u32)__popc(free_mask & lt) == pick;
       const bool is_rd = (r_lo & 1u) != 0;
       const bool ovf = gen && !is_rd && next_value >= max_values;
-      if (ovf) { flags |= MSIM_FLAG_VALUES_OVERFLOW; alive = 0; }
+      if (bal(next_value >= max_values)) { flags |= ovf ? (u32)MSIM_FLAG_VALUES_OVERFLOW : 0u; alive_m &= ~bal(ovf); }   // (rare: out of values)
       mark = sel && !ovf ? 1u : mark;
       m_kind = gen ? (is_rd ? DK_READ : DK_BCAST) : m_kind;
       m_val = gen && !is_rd ? next_value : m_val;
@@ -566,8 +573,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     }
     P3_MARK(1)   // [1] = R1 scheduler
     // ---- R2: marked clients invoke; the request reaches this lane's own node (no latency: a client is involved) ----
-    if (bal(mark != 0) & bal(alive != 0)) {
-      const bool inv = mark != 0 && alive != 0;
+    if (const u64 inv_b = bal(mark != 0) & alive_m) {
+      const bool inv = lane_in(inv_b);
       busy = inv ? 1u : busy;
       const bool is_op = inv && m_kind <= DK_READ_FINAL;
       inv_row = is_op ? 1u : 0u;
@@ -590,8 +597,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 
     P3_MARK(2)   // [2] = R2 invoke + poll
     // ---- R3: one input per node: the due envelope ----
-    const bool due_n = alive != 0 && deliver_at <= T;
-    const u64 due_b = bal(alive != 0) & bal(deliver_at <= T);
+    const u64 due_b = alive_m & bal(deliver_at <= T);
+    const bool due_n = lane_in(due_b);
     const u32 kind = cm >> 24;
     const u32 v = cm & 0xFFFFu;
     u32 pub; u64 pub_b; DUO_R3_SEEN(due_n & (kind <= DK_BCAST), due_b & bal(kind <= DK_BCAST), pub, pub_b);
@@ -600,28 +607,32 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     const bool req = due_n && kind != DK_PLAIN;   // a request of this lane's client: handled, answered and completed in this round
     n_cl += req ? 1u : 0u;
     busy = req ? 0u : busy;
-    const bool rd = req && (kind == DK_READ || kind == DK_READ_FINAL);
     cmp_row = (req && kind == DK_BCAST) ? 1u : 0u;
     cmp_packed = MSIM_T_OK | (MSIM_F_BROADCAST << 2) | (i << 12); cmp_value = v;
     // read -> read_ok with the whole set: the cluster's lanes copy the node's set LDS -> HBM payload
-    if (due_b & bal(kind - (u32)DK_READ < 2u)) {   // (= ballot of rd: kind is DK_READ or DK_READ_FINAL)
+    // (the readers' and the copying clusters' masks come from ballots of single compares: a ballot of a bool built from several costs two
+    //  vector instructions more)
+    if (const u64 rd_b = due_b & bal(kind - (u32)DK_READ < 2u)) {   // the lanes whose request is a read (kind DK_READ or DK_READ_FINAL)
       wave_lds_fence();
-      const u32 rdm = hb(rd, hi);
+      const bool rd = lane_in(rd_b);
+      const u32 rdm = hi ? (u32)(rd_b >> 32) : (u32)rd_b;
       const u32 words = (next_value + 31u) >> 5;
       const u32 my_rank = __popc(rdm & lt);
       const bool ok = n_payload + (my_rank + 1u) * words <= max_pay;   // payload_alloc of the oracle, reader by reader
       const u32 my_off = ok ? n_payload + my_rank * words : 0u;
+      const u64 ok_b = rd_b & bal(ok);
       if (rd) {
         if (!ok) my_flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
         cmp_row = 1; cmp_packed = MSIM_T_OK | (MSIM_F_READ << 2) | ((kind == DK_READ_FINAL ? 1u : 0u) << 11) | (i << 12);
         cmp_value = my_off; cmp_len = words;
       }
-      const u32 okm = hb(rd && ok, hi);
+      const u32 ok_lo = (u32)ok_b, ok_up = (u32)(ok_b >> 32), okm = hi ? ok_up : ok_lo;
       u32 m = okm;
-      if (!__ballot((okm & (okm - 1u)) != 0)) {   // the usual round: at most one reader per cluster — lane w copies word w of its set
+      if (((ok_lo & (ok_lo - 1u)) | (ok_up & (ok_up - 1u))) == 0) {   // the usual round: at most one reader per cluster — lane w copies word w of its set
         const u32 r1 = okm ? (u32)__builtin_ctz(okm) : 0u;
-        for (u32 w = i; __ballot(okm != 0 && w < words); w += 32)
-          if (okm != 0 && w < words) g_pay[n_payload + w] = seen[r1 * Wp + w];
+        const u64 cp_b = hm2(ok_lo != 0, ok_up != 0);   // the clusters that copy a set
+        for (u32 w = i; cp_b & bal(w < words); w += 32)
+          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = seen[r1 * Wp + w];
         m = 0;
       }
       while (__ballot(m != 0)) {
@@ -646,8 +657,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     if (__ballot((inv_row | cmp_row) != 0)) {
       const u32 imask = hb(inv_row != 0, hi), cmask = hb(cmp_row != 0, hi);
       const u32 ni = __popc(imask), nr = ni + __popc(cmask);
-      const bool ovf = alive != 0 && nr != 0 && n_rows + nr > max_rows;
-      if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = 0; }
+      const bool ovf = lane_in(alive_m) && nr != 0 && n_rows + nr > max_rows;
+      if (bal(n_rows + nr > max_rows)) { flags |= ovf ? (u32)MSIM_FLAG_ROWS_OVERFLOW : 0u; alive_m &= ~bal(ovf); }   // (rare: out of rows)
       const u64 tns = (u64)T * 1000ull;
       const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
       if (RND || DUO_DIRECT) {   // the bags of the random-latency layout take the LDS a staging area would need: rows go straight to HBM
@@ -674,11 +685,12 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     P3_MARK(6)   // [6] = rows
     // ---- the scheduler's view for the rounds to come: time-free phase transitions (oracle: sched_resolve), when it
     //      acts next (sched_due), and whether plain gossip rounds may run meanwhile ----
-    const u32 hbusy = hb(busy != 0, hi);
-    if (bal(alive != 0) & (bal(phase != PH_MAIN) | (rate > 0 ? bal(gen_next >= cutoff) : bal(true)) | bal(rounds > round_limit))) {
+    const u64 hbusy_b = bal(busy != 0);
+    const u32 hbusy = hi ? (u32)(hbusy_b >> 32) : (u32)hbusy_b;
+    if (alive_m & (bal(phase != PH_MAIN) | (rate > 0 ? bal(gen_next >= cutoff) : bal(true)) | bal(rounds > round_limit))) {
       for (;;) {
         bool ch = false;
-        if (alive != 0) {
+        if (lane_in(alive_m)) {
           if (phase == PH_INIT_WAIT && hbusy == 0) { phase = PH_TOPO; ch = true; }
           if (phase == PH_TOPO_WAIT && hbusy == 0) { phase = PH_MAIN_START; ch = true; }
           if (phase == PH_MAIN_START) { cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; phase = PH_MAIN; ch = true; }
@@ -688,8 +700,9 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         }
         if (!__ballot(ch)) break;
       }
-      if (phase == PH_DONE) alive = 0;
-      if (alive != 0 && rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = 0; }
+      alive_m &= ~bal(phase == PH_DONE);
+      const u64 lim_b = alive_m & bal(rounds > round_limit);
+      flags |= lane_in(lim_b) ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u; alive_m &= ~lim_b;
       const bool gen_live = rate > 0 && gen_next < cutoff;
       u32 sa = INF;
       if (phase == PH_MAIN) {
@@ -697,23 +710,24 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         if (rate == 0) sa = min(sa, cutoff);
       } else if (phase == PH_INIT || phase == PH_TOPO || phase == PH_FINAL) sa = T;
       else if (phase == PH_SLEEP) sa = sleep_until;
-      sched_at = alive != 0 ? sa : INF;
-      force_general = (alive != 0 && !((phase == PH_MAIN && gen_live) || phase == PH_SLEEP)) ? 1u : 0u;
+      sched_at = lane_in(alive_m) ? sa : INF;
+      fg_m = alive_m & ~((rate > 0 ? bal(phase == PH_MAIN) & bal(gen_next < cutoff) : 0ull) | bal(phase == PH_SLEEP));
     } else {
       // every live cluster of the wavefront is in the main phase with its generator running (nearly every GENERAL round): the
       // scheduler acts again when the generator's next op is due and a worker is free, plain gossip rounds may run meanwhile
-      sched_at = (alive != 0 && (all_nodes & ~hbusy) != 0) ? gen_next : INF;
-      force_general = 0;
+      sched_at = lane_in(alive_m & hm2((all_nodes & ~(u32)hbusy_b) != 0, (all_nodes & ~(u32)(hbusy_b >> 32)) != 0)) ? gen_next : INF;
+      fg_m = 0;
     }
-    if (__ballot(alive == 0)) {
-      if (alive == 0) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
+    alive_v = lane_in(alive_m) ? 1u : 0u;
+    if (~alive_m) {
+      if (!lane_in(alive_m)) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
     }
     P3_MARK(7)   // [7] = the scheduler's view
     }
 #ifdef DUO_PROF
     pf_gen += __builtin_readcyclecounter() - pf_a; pf_ngen++;
 #endif
-    if (!__ballot(alive != 0)) break;
+    if (!alive_m) break;
   }
 #ifdef DUO_PROF
   const u64 pf_tot = __builtin_readcyclecounter() - pf_t0;
