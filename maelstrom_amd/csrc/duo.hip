@@ -27,6 +27,7 @@
 //   R3  every node with a due envelope handles it (dedup, fan-out);
 //       COMMIT: receivers PULL the senders' fan-outs with ds_bpermute (one per topology neighbour), append to their
 //       own LDS ring; idle receivers poll (pop the ring head / the pending client request);
+//       the nodes' seen sets live in HBM scratch, one region per cluster (the LDS holds the queues alone);
 //   R4  completions -> history rows (staged in LDS, 1 KiB coalesced appends)   — GENERAL rounds only
 // A wave-round is GENERAL if either cluster needs it; pure gossip rounds of both clusters take the short body.
 #include <hip/hip_runtime.h>
@@ -52,6 +53,9 @@ constexpr bool DUO_DIRECT = false;
 #else
 constexpr bool DUO_DIRECT = true;
 #endif
+#ifndef DUO_LDS_PAD
+#define DUO_LDS_PAD 0   // A/B builds (-DDUO_LDS_PAD=<bytes>): unused LDS per wavefront, fewer wavefronts per CU (msim_launch_duo)
+#endif
 
 struct DuoParams {
   KParams k;
@@ -59,7 +63,9 @@ struct DuoParams {
   u32 R;             // LDS ring entries per node (power of two >= inbox_capacity)
   u32 S;             // HBM spill entries per node behind the ring (R + S = inbox_capacity + spill_capacity)
   u32 half_bytes;    // LDS bytes per cluster
-  u32 off_ring, off_seen;  // byte offsets inside a cluster's LDS region
+  u32 off_ring;      // byte offset of the queues inside a cluster's LDS region
+  u32 sets_off;      // word offset of the cluster's set region inside its instance's scratch (msim_duo_extra_scratch_words)
+  u32 inst_bytes;    // scratch bytes per instance: the distance between the set regions of a wavefront's two clusters
   u32 deg;           // maximum degree of the topology
   u32 echoback;      // node program without skip-sender
   u32 round_limit;
@@ -139,12 +145,17 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   u64 *const my_spill = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)inst * p.scratch_words + p.spill_off) +
                                                     (size_t)(is_node ? i : 0) * p.spill_cap);
 
-  // LDS of one cluster: [row staging][32 rings][N node sets][32 dummy words for the lanes that hold no node]
+  // LDS of one cluster: [row staging][32 rings]
   unsigned char *const hmem = smem + (hi ? dp.half_bytes : 0u);
   uint4 *const stage = reinterpret_cast<uint4 *>(hmem);
-  u32 *const seen = reinterpret_cast<u32 *>(hmem + dp.off_seen);
-  const u32 Wp = W | 1u;   // odd stride between the nodes' sets: word w of every node sits on a different LDS bank
-  u32 *const my_seen = is_node ? seen + i * Wp : seen + N * Wp + i;
+  // The nodes' seen sets: W x 32 words of HBM scratch per cluster, word-major ([word][lane]: lane i's column is node i's set, or a
+  // dummy set of a lane that holds no node), so that a wave-wide access to one word of every node's set is one 128-byte line per
+  // cluster.  Addressed as the wavefront's base (SGPRs: the set region of its lower cluster) + a 32-bit byte offset per lane; the
+  // upper half's region lies inst_bytes further on (an upper half without a cluster shares the lower one's region and writes nothing).
+  unsigned char *const sets = reinterpret_cast<unsigned char *>(p.scratch + (size_t)(blockIdx.x * 2u) * p.scratch_words + dp.sets_off);
+  const u32 set_half = (inst - blockIdx.x * 2u) * dp.inst_bytes;   // byte offset of the cluster's region
+  const u32 set_lane = set_half + i * 4u;                           // byte offset of word 0 of this lane's set
+#define DUO_SET(boff_) (*reinterpret_cast<u32 *>(sets + (size_t)(u32)(boff_)))
   // slot-major rings: slot s of lane i at [s * 32 + i] (a wave-wide access to one slot position is contiguous)
   u32 *const ring32 = reinterpret_cast<u32 *>(hmem + dp.off_ring) + i;       // LAT0: the envelope word
   u64 *const ring64 = reinterpret_cast<u64 *>(hmem + dp.off_ring) + i;       // else deadline | envelope << 32
@@ -162,7 +173,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   u32 *const my_spill12 = p.scratch + (size_t)inst * p.scratch_words + p.spill_off + (size_t)(is_node ? i : 0) * p.spill_cap * 4;   // {deadline, envelope, sequence} x S
   u32 *const log2_tab = reinterpret_cast<u32 *>(smem + dp.off_log2);
 
-  for (u32 k = i; k < N * Wp + 32u; k += 32) seen[k] = 0;
+  if (real) for (u32 w = 0; w < W; w++) DUO_SET(set_lane + w * 128u) = 0;   // (whatever the scratch held before: nothing is read unwritten)
   if (RND) for (u32 k = lane; k < 257u; k += 64) log2_tab[k] = duo_log2_q24[k];
   if (RND) for (u32 k = i; k < DUO_BAG * BS; k += 32) reinterpret_cast<u32 *>(hmem + dp.off_ring)[k] = INF;   // every bag slot is free
   __syncthreads();
@@ -215,9 +226,9 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   // instructions.  Lane i of a cluster holds the latency (ms) of message id lc_base + i; DUO_RND_IDS keeps the block under the round's ids.
   u32 lc_base = 0xFFFFFFC0u, lc = 0; bool lc_all = false;   // (no block yet: the first round with a send draws one)
 
-  // Two LDS reads are kept one round ahead of their use, so that a round's dependent chain holds one LDS round trip
+  // Two reads are kept one round ahead of their use, so that a round's dependent chain holds one LDS round trip
   // (the ds_bpermute exchange) instead of three:
-  //   sw = the word of the node's set that cm's value falls in (re-read after every change of cm or of the set);
+  //   sw = the word of the node's set that cm's value falls in (re-read after every change of cm or of the set; an L1 / L2 hit);
   //   nx = the head entry of the ring (valid while in_n != 0; an append to an empty ring sets it from registers).
   u32 sw = 0;
   u32 nx = 0, nx_dl = 0;
@@ -227,7 +238,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   // recv! took an envelope: (Thread/sleep (long dt)), net.clj:236-238
 #define DUO_COMMIT_TIME(dl_) (LAT0 ? T : ((dl_) <= T ? T : T + (((dl_) - T) / 1000u) * 1000u))
 #define DUO_RING_STORE(slot_, e_, dl_) do { if (LAT0) ring32[(slot_) * 32u] = (e_); else ring64[(slot_) * 32u] = (u64)(dl_) | ((u64)(e_) << 32); } while (0)
-#define DUO_SEEN_WORD() (reinterpret_cast<u32 *>(reinterpret_cast<unsigned char *>(my_seen) + ((cm >> 3) & 0x1FFCu)))   /* word (value >> 5) */
+#define DUO_SEEN_WORD() DUO_SET(set_lane + ((cm & 0xFFE0u) << 2))   /* word (value >> 5) of the node's set */
   // slow, checked append: ring, then spill; used when a ring may fill up this round
 #define DUO_PUSH_CHECKED(got_, e_, dl_) do {                                                                              \
     const bool pc_got = (got_); const u32 pc_e = (e_), pc_dl = (dl_);                                                     \
@@ -345,9 +356,9 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   // to its neighbours: bit 31 | value | src to skip << 16, or 0; hball_ = the ballot of handle_, pubb_ = the ballot of pub_ != 0
 #ifdef DUO_NO_SWPF   /* A/B build: the set word is read where it is used */
 #define DUO_SW_PREFETCH() do { } while (0)
-#define DUO_SW_NOW() do { sw = *DUO_SEEN_WORD(); } while (0)
+#define DUO_SW_NOW() do { sw = DUO_SEEN_WORD(); } while (0)
 #else
-#define DUO_SW_PREFETCH() do { sw = *DUO_SEEN_WORD(); } while (0)
+#define DUO_SW_PREFETCH() do { sw = DUO_SEEN_WORD(); } while (0)
 #define DUO_SW_NOW() do { } while (0)
 #endif
 #define DUO_R3_SEEN(handle_, hball_, pub_, pubb_) do {                                                                    \
@@ -355,7 +366,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     const u32 r3_bit = 1u << (cm & 31u);                                                                                  \
     const bool r3_new = (handle_) & ((sw & r3_bit) == 0);                                                                 \
     pubb_ = (hball_) & bal((sw & r3_bit) == 0);                                                                           \
-    if (r3_new) *DUO_SEEN_WORD() = sw | r3_bit;                                                                           \
+    if (r3_new) DUO_SEEN_WORD() = sw | r3_bit;                                                                           \
     pub_ = r3_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                                \
   } while (0)
   // COMMIT of the fan-outs, receiver side: every node pulls what its neighbours publish, in ascending sender order (= id order,
@@ -609,7 +620,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     busy = req ? 0u : busy;
     cmp_row = (req && kind == DK_BCAST) ? 1u : 0u;
     cmp_packed = MSIM_T_OK | (MSIM_F_BROADCAST << 2) | (i << 12); cmp_value = v;
-    // read -> read_ok with the whole set: the cluster's lanes copy the node's set LDS -> HBM payload
+    // read -> read_ok with the whole set: the cluster's lanes copy the node's set (scratch) -> HBM payload
     // (the readers' and the copying clusters' masks come from ballots of single compares: a ballot of a bool built from several costs two
     //  vector instructions more)
     if (const u64 rd_b = due_b & bal(kind - (u32)DK_READ < 2u)) {   // the lanes whose request is a read (kind DK_READ or DK_READ_FINAL)
@@ -632,7 +643,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         const u32 r1 = okm ? (u32)__builtin_ctz(okm) : 0u;
         const u64 cp_b = hm2(ok_lo != 0, ok_up != 0);   // the clusters that copy a set
         for (u32 w = i; cp_b & bal(w < words); w += 32)
-          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = seen[r1 * Wp + w];
+          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = DUO_SET(set_half + w * 128u + r1 * 4u);
         m = 0;
       }
       while (__ballot(m != 0)) {
@@ -641,7 +652,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
         m &= m - 1u;
         const u32 r_off = bperm(hbase4 + (r << 2), my_off);
         for (u32 w = i; __ballot(on && w < words); w += 32)
-          if (on && w < words) g_pay[r_off + w] = seen[r * Wp + w];
+          if (on && w < words) g_pay[r_off + w] = DUO_SET(set_half + w * 128u + r * 4u);
       }
       n_payload += __popc(okm) * words;
     }
@@ -768,6 +779,9 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 
 }  // namespace
 
+// Extra per-instance scratch words: the cluster's node sets, W words x 32 lanes (duo.hip's set region; 128-byte aligned by scratch_words())
+uint64_t msim_duo_extra_scratch_words(const msim_config &c) { return (uint64_t)(c.max_values / 32u) * 32u; }
+
 // Whether the duo layout simulates this configuration (see the header of this file).
 bool msim_duo_eligible(const msim_config &c) {
   if (c.node_program != MSIM_NODE_BCAST_FF && c.node_program != MSIM_NODE_BCAST_FF_ECHOBACK) return false;
@@ -818,14 +832,18 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT;
   const bool lat0 = !rnd && c.latency_mean_ms == 0;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;
-  // LDS of one cluster = [row staging (not RND)] [queues] [node sets + a dummy word per lane].  The queues take what keeps EIGHT
-  // wavefronts on a CU (20 KiB each: BASELINE's 4096 clusters are 2048 wavefronts on 256 CUs — a ninth would run alone in a second
-  // pass), at least 8 entries per node; what does not fit goes to the HBM spill area.
-  const size_t seen_bytes = (((size_t)kp.N * (kp.W | 1u) + 32) * 4 + 15) & ~(size_t)15;   // odd stride between the nodes' sets
+  // LDS of one cluster = [row staging (not RND)] [queues]; the node sets live in HBM scratch (msim_duo_extra_scratch_words).  The
+  // queues are sized by the rule of the layout that kept the sets in LDS too: as many ring entries per node as fit beside the sets in
+  // 10 KiB per cluster, at least 8, at most inbox_capacity (rounded up to a power of two); what does not fit goes to the HBM spill area.
+  // R, S and with them the fit test below (and so which kernel runs a configuration) are the same as then; only the sets' bytes left.
+  // Three launches of 4096 clusters resident at once want 24 wavefronts per CU (6 per SIMD, what the registers of the lat-0
+  // instantiation allow), at most 6.8 KB of LDS each.  The headline shape (lat 0, inbox 6: R = 8) takes 2 KiB per wavefront; constant
+  // latency > 0 (R = 16: 8 KiB, 20 per CU = the 5 per SIMD its registers allow) and RND (9.4 KB) shrink by the sets as well.
+  const size_t set_bytes_v1 = (((size_t)kp.N * (kp.W | 1u) + 32) * 4 + 15) & ~(size_t)15;   // what the sets took of the LDS budget
   const size_t stage_bytes = (rnd || DUO_DIRECT) ? 0 : DUO_STAGE_ROWS * 16;   // (rows are staged only in the -DDUO_STAGED_ROWS build)
-  const size_t fixed = seen_bytes + stage_bytes;
+  const size_t fixed = set_bytes_v1 + stage_bytes;
   const size_t per_entry = rnd ? 0 : (size_t)32 * (lat0 ? 4 : 8);   // (RND: bags of a fixed 16 entries)
-  const size_t budget = (20 * 1024 - (rnd ? 257 * 4 + 16 : 0)) / 2;   // (RND with DUO_BAG = 8: 13 KiB per wavefront, twelve per CU)
+  const size_t budget = (20 * 1024 - (rnd ? 257 * 4 + 16 : 0)) / 2;
   uint32_t R = rnd ? DUO_BAG : 8;
   while (!rnd && R < 64 && R < cap_tot && fixed + ((per_entry * (R * 2) + 15) & ~(size_t)15) + 32 <= budget && (rnd || R < c.inbox_capacity)) R <<= 1;
   if (!rnd && R > cap_tot) { R = 2; while (R * 2 <= cap_tot) R <<= 1; }
@@ -839,14 +857,22 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   dp.off_seq = (u32)off; if (rnd) off += (((size_t)(kp.N + 1) * DUO_BAG * 2) + 15) & ~(size_t)15;
   dp.R = R;
   off = (off + 15) & ~(size_t)15;
-  dp.off_seen = (u32)off; off += seen_bytes;
   dp.half_bytes = (u32)off;
+  // the fit test of the layout that kept the sets in LDS, unchanged: which kernel runs a configuration does not depend on where the sets live
+  if (2 * (off + set_bytes_v1) + (rnd ? 257 * 4 + 12 : 0) > 160 * 1024) return MSIM_LAYOUT_DOES_NOT_FIT;
+  // the set regions: the last msim_duo_extra_scratch_words(c) words of every instance's scratch (scratch_words() of engine.hip adds them
+  // last), reached with 32-bit byte offsets from the wavefront's lower cluster.  A finalized configuration's scratch stays far below
+  // 2 GiB per instance (spill <= 32 nodes x 65536 envelopes x 16 B, queues bounded by the LDS check of msim_run, max_values <= 8160):
+  // the test below cannot fail for one that reaches this kernel.
+  if (kp.scratch_words * 4 >= (1ull << 31)) return MSIM_LAYOUT_DOES_NOT_FIT;
+  dp.sets_off = (u32)(kp.scratch_words - msim_duo_extra_scratch_words(c));
+  dp.inst_bytes = (u32)(kp.scratch_words * 4);
   dp.off_log2 = (u32)(2 * off);
   dp.deg = duo_degree(c);
   dp.echoback = c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK;
   dp.round_limit = (kp.dev_flags & 0x100u) ? 2000000u : ROUND_LIMIT;
-  const size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
-  if (lds > 160 * 1024) return MSIM_LAYOUT_DOES_NOT_FIT;
+  size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
+  lds = std::min(lds + (size_t)DUO_LDS_PAD, (size_t)160 * 1024);
   const bool deg4 = dp.deg <= 4 && kp.N <= 31;   // (lane 31 must hold no node: unused neighbour slots point at it)
   const dim3 grid((n + 1) / 2);
   if (rnd) return deg4 ? duo_launch<false, true, true>(dp, grid, lds, st) : duo_launch<false, false, true>(dp, grid, lds, st);

@@ -208,6 +208,8 @@ static uint64_t scratch_words(const msim_config &c) {
   if (msim_uid8_eligible(c)) w += msim_uid8_extra_scratch_words(c);     // uid8.hip likewise
   if (msim_crdt8_eligible(c)) w += msim_crdt8_extra_scratch_words(c);   // crdt8.hip likewise
   if (msim_bcast8_eligible(c)) w += msim_bcast8_extra_scratch_words(c); // bcast8.hip likewise
+  // duo.hip: the nodes' sets, last and on a 128-byte boundary of the instance's scratch (the total stays a multiple of 32 words)
+  if (msim_duo_eligible(c)) w = ((w + 31) & ~31ull) + msim_duo_extra_scratch_words(c);
   return w;
 }
 

@@ -187,6 +187,7 @@ hipError_t msim_launch_hatg(const KParams &kp, uint32_t n, size_t lds, hipStream
 hipError_t msim_launch_kafkag(const KParams &kp, uint32_t n, size_t lds, hipStream_t st);
 // duo.hip: two clusters per wavefront (fire-and-forget broadcast, constant latency, colocated clients)
 bool msim_duo_eligible(const msim_config &c);
+uint64_t msim_duo_extra_scratch_words(const msim_config &c);
 hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st);
 // raft4.hip: four Raft clusters per wavefront (lin-kv over the Raft node program, clusters of <= 16 endpoints)
 bool msim_raft4_eligible(const msim_config &c);
