@@ -424,7 +424,7 @@ hipError_t msim_launch_bcast8(const KParams &kp, uint32_t n, hipStream_t st) {
   const size_t lds = off;
   if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[bcast8] %u clusters, eight per wavefront, %zu B of LDS per wavefront\n", n, lds);   // developer trace bit
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(g8_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const bool nem = c.nemesis_mask != 0;
   switch (c.node_program) {
     case MSIM_NODE_BCAST_FF: return b8_launch<MSIM_NODE_BCAST_FF>(up, n, lds, nem, rnd, st);

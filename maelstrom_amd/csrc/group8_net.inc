@@ -14,7 +14,7 @@
     if (src < N) {  // neither end is a client
       if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
       else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * g8_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
+      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
     }
     if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
     uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));

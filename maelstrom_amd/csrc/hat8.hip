@@ -594,7 +594,7 @@ hipError_t msim_launch_hat8(const KParams &kp, uint32_t n, hipStream_t st) {
   const size_t lds = off;
   if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[hat8] %u clusters, several per wavefront, %zu B of LDS per wavefront\n", n, lds);   // developer trace bit
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(g8_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   // 8-lane groups for every cluster size: 4-lane groups halve the wavefronts again, and a wavefront's run is a chain of dependent round
   // trips that only other wavefronts hide (16384 clusters of 2 nodes: 58 ms in 4-lane groups, 45 ms in 8-lane groups, 84 ms one per
   // wavefront; at 65536 clusters 139 / 143 / 317 ms).  MSIM_DEV_FLAGS bit 15 selects the 4-lane groups.

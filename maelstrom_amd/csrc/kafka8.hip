@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(64) kafka8_kernel(const K8Params up) {
     if (src < N || src == SVC) {  // neither end is a client
       if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
       else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * g8_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
+      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
     }
     if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
     uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
@@ -772,7 +772,7 @@ hipError_t msim_launch_kafka8(const KParams &kp, uint32_t n, hipStream_t st) {
   const size_t lds = off;
   if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[kafka8] %u clusters, eight per wavefront, %zu B of LDS per wavefront\n", n, lds);   // developer trace bit
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(g8_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const dim3 grid((n + 7) / 8), block(64);
   if (c.nemesis_mask) { if (rnd) hipLaunchKernelGGL((kafka8_kernel<true, true>), grid, block, lds, st, up); else hipLaunchKernelGGL((kafka8_kernel<true, false>), grid, block, lds, st, up); }
   else { if (rnd) hipLaunchKernelGGL((kafka8_kernel<false, true>), grid, block, lds, st, up); else hipLaunchKernelGGL((kafka8_kernel<false, false>), grid, block, lds, st, up); }

@@ -22,11 +22,9 @@
 #include <cstdio>
 
 #include "wave_common.h"
-#include "log2_table.h"
+#include "latency_sampler.h"
 
 namespace {
-
-__constant__ u32 m8_log2_q24[257];
 
 constexpr u32 GS = 8u;            // lanes per cluster
 #ifndef M8_RQ
@@ -59,18 +57,6 @@ struct M8Params {
   u32 round_limit;
 };
 
-__device__ __forceinline__ u32 m8_neg_ln_q16(u32 r) {
-  if (r == 0xFFFFFFFFu) return 0;
-  const u32 v = r + 1;
-  const u32 e = 31 - __clz(v);
-  const u32 m = v << (31 - e);
-  const u32 idx = (m >> 23) & 0xFF;
-  const u32 f = (m >> 7) & 0xFFFF;
-  const u32 l0 = m8_log2_q24[idx], l1 = m8_log2_q24[idx + 1];
-  const u32 lg = (e << 24) + l0 + (u32)(((u64)(l1 - l0) * f) >> 16);
-  const u32 d = (32u << 24) - lg;
-  return (u32)(((u64)d * 2977044472ull) >> 40);
-}
 // min over the 8 lanes of the caller's group, in every lane of it
 __device__ __forceinline__ u32 m8_oct_min(u32 v) {
   v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
@@ -175,7 +161,7 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
     if (src < N || src >= LIN) {  // neither end is a client
       if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
       else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * m8_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
+      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
     }
     if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
     uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
@@ -956,7 +942,7 @@ hipError_t msim_launch_mk8(const KParams &kp, uint32_t n, hipStream_t st) {
   tp.round_limit = (kp.dev_flags & 0x100u) ? 4000000u : ROUND_LIMIT;
   const size_t lds = off;
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(m8_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const dim3 grid((n + 7) / 8), block(64);
   if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[mk8] %u clusters, eight per wavefront, %zu B of LDS per wavefront\n", n, lds);   // developer trace bit
   if (c.nemesis_mask) { if (rnd) hipLaunchKernelGGL((mk8_kernel<true, true>), grid, block, lds, st, tp); else hipLaunchKernelGGL((mk8_kernel<true, false>), grid, block, lds, st, tp); }

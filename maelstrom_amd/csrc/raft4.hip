@@ -10,6 +10,9 @@
 // lives in VGPRs, a "ballot" is the cluster's 16-bit slice of the wave ballot, a lane of another group is never addressed
 // (`ds_bpermute` inside the group replaces `v_readlane`), reductions and prefix sums are DPP row operations (a row = a group).
 //
+// The time step, the network and the partition nemesis are shared with svc4.hip, txng4.hip and dtg4.hip (group16.h, group16_*.inc);
+// the row staging ring is this file's own.
+//
 // Scope (engine.hip picks this kernel when all of it holds, else raft_kernel<> runs): n_nodes + max(concurrency, n_nodes) <= 16,
 // net journal off.  Latency models, loss and the partition nemesis are all here.
 //
@@ -42,11 +45,9 @@
 #include <hip/hip_runtime.h>
 
 #include "wave_common.h"
-#include "log2_table.h"
+#include "group16.h"
 
 namespace {
-
-__constant__ u32 r4_log2_q24[257];
 
 constexpr u32 GS = 16u;           // lanes per cluster
 constexpr u32 RQ = 8u;            // LDS envelopes per endpoint
@@ -68,35 +69,6 @@ struct R4Params {
   u64 client_spill_off;                       // word offset of the clients' spill area inside the per-instance scratch
   u32 round_limit;
 };
-
-__device__ __forceinline__ u32 r4_neg_ln_q16(u32 r) {
-  if (r == 0xFFFFFFFFu) return 0;
-  const u32 v = r + 1;
-  const u32 e = 31 - __clz(v);
-  const u32 m = v << (31 - e);
-  const u32 idx = (m >> 23) & 0xFF;
-  const u32 f = (m >> 7) & 0xFFFF;
-  const u32 l0 = r4_log2_q24[idx], l1 = r4_log2_q24[idx + 1];
-  const u32 lg = (e << 24) + l0 + (u32)(((u64)(l1 - l0) * f) >> 16);
-  const u32 d = (32u << 24) - lg;
-  return (u32)(((u64)d * 2977044472ull) >> 40);
-}
-// min over the 16 lanes of the caller's DPP row (= its group), in every lane of the row
-__device__ __forceinline__ u32 row_min(u32 v) {
-  v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_mov<0x4E, 0xF, 0xF, false>(v, v));   // quad_perm [2,3,0,1]
-  v = min(v, dpp_mov<0x141, 0xF, 0xF, false>(v, v));  // row_half_mirror
-  v = min(v, dpp_mov<0x140, 0xF, 0xF, false>(v, v));  // row_mirror
-  return v;
-}
-// inclusive prefix sum over the 16 lanes of the row
-__device__ __forceinline__ u32 row_scan(u32 v) {
-  v += dpp_mov<0x111, 0xF, 0xF, true>(0, v);   // row_shr:1
-  v += dpp_mov<0x112, 0xF, 0xF, true>(0, v);   // row_shr:2
-  v += dpp_mov<0x114, 0xF, 0xF, true>(0, v);   // row_shr:4
-  v += dpp_mov<0x118, 0xF, 0xF, true>(0, v);   // row_shr:8
-  return v;
-}
 
 template <bool NEM, bool NET_RANDOM, int NN>   // NN: static bound of the loops over peers (n_nodes <= NN)
 __global__ void __launch_bounds__(64) raft4_kernel(const R4Params rp) {
@@ -148,9 +120,6 @@ __global__ void __launch_bounds__(64) raft4_kernel(const R4Params rp) {
   my_runs[0] = 1u;                                        // ... is the first run: index 1, term 0
   __syncthreads();
 
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFFFu; };            // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
-
   // ---- endpoint state ----
   bool has_c = false; u32 deliver_at = 0; uint4 cm = make_uint4(0, 0, 0, 0);
   bool have_pm = false; uint4 pm = make_uint4(0, 0, 0, 0);
@@ -174,54 +143,10 @@ __global__ void __launch_bounds__(64) raft4_kernel(const R4Params rp) {
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
 
-  auto q_push = [&](const uint4 m) {
-    if (in_n < RQ) { my_q[in_n * 64u] = m; in_n++; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) {
-    u32 lat = 0;
-    if (src < N && is_node) {
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * r4_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    q_push(m);
-  };
-  auto try_commit = [&](const uint4 e) {
-    const u32 src = e.w >> 24;
-    if (NEM && is_node && src < N && ((part >> src) & 1)) return;
-    cm = e; has_c = true;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;
-  };
-  auto poll = [&]() {
-    const bool elig = alive && (is_node || busy);
-    if (have_pm) {
-      have_pm = false;
-      if (elig && !has_c && (in_n | sp_n) == 0) try_commit(pm);
-      else q_push(pm);
-    }
-    while (elig && !has_c && (in_n | sp_n) != 0) {
-      u32 best = 0; bool in_spill = false;
-      uint2 bk = make_uint2(INF, INF);
-      for (u32 i = 0; i < in_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_q[i * 64u]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-      }
-      for (u32 i = 0; i < sp_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_spill[i]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-      }
-      uint4 e;
-      if (in_spill) { e = my_spill[best]; sp_n--; if (best != sp_n) my_spill[best] = my_spill[sp_n]; }
-      else { e = my_q[best * 64u]; in_n--; if (best != in_n) my_q[best * 64u] = my_q[in_n * 64u]; }
-      try_commit(e);
-    }
-  };
+#define SERVER_SRC(src) ((src) < N)   // whether sender lane src is a server: the nodes
+#define is_server is_node             // (raft has no service lane: the nodes are the servers)
+  #include "group16_net.inc"
+#undef is_server
 
   // ---- raft helpers (node lanes) ----
   auto reset_election_deadline = [&]() {  // raft.py:251-253: now + 2 s * (random + 1)
@@ -311,53 +236,11 @@ __global__ void __launch_bounds__(64) raft4_kernel(const R4Params rp) {
 #ifdef R4_PROF
     wave_rounds++;
 #endif
-    const u32 busy_mask = GB(busy);
+    #include "group16_phase.inc"
 
-    // ---- time-free phase transitions: lin-kv has no final generator (core.clj:74-80 applies only with one) ----
-    if (__ballot(alive && !(phase == PH_MAIN && ((rate > 0 && gen_next < cutoff) || (NEM && nem_next < cutoff))))) {
-      for (;;) {
-        bool ch = false;
-        if (alive) {
-          if (phase == PH_INIT_WAIT && !busy_mask) { phase = PH_MAIN_START; ch = true; }
-          if (phase == PH_MAIN_START) { cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; nem_next = T; next_msg_id = 0; loss_on = 1; phase = PH_MAIN; ch = true; }
-          if (phase == PH_MAIN && !((rate > 0 && gen_next < cutoff) || (NEM && nem_next < cutoff)) && !(rate == 0 && T < cutoff)) { phase = PH_DRAIN; ch = true; }
-          if (phase == PH_DRAIN && !(busy_mask & worker_mask)) { phase = PH_DONE; ch = true; }
-        }
-        if (!__ballot(ch)) break;
-      }
-      if (phase == PH_DONE) alive = false;
-      if (!__ballot(alive)) break;
-    }
-    if (alive && ++rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = worker_mask & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
-    u32 my_t = has_c ? deliver_at : INF;
+    #include "group16_time.inc"
     if (is_node) my_t = min(my_t, act_time);
-    bool timeout_round = false;
-    {
-      const bool none_due = GB(my_t <= T) == 0;
-      const bool jump = alive && due > T && none_due;
-      if (__ballot(jump)) {
-        u32 k = my_t == INF ? INF : my_t * 2;
-        if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = row_min(k);
-        if (due != INF) km = min(km, due * 2);
-        if (jump) {
-          if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-          else { timeout_round = (km & 1) != 0; T = max(T, km >> 1); }
-        }
-      }
-    }
+    #include "group16_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0;
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0;
@@ -388,62 +271,7 @@ __global__ void __launch_bounds__(64) raft4_kernel(const R4Params rp) {
       if (__ballot(act && phase == PH_INIT)) {
         if (act && phase == PH_INIT) { if (is_client && slot < N) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; }
       }
-      if (NEM) {
-        const bool nem_act = act && phase == PH_MAIN && nem_live && nem_next <= T;
-        if (__ballot(nem_act)) {
-          const u32 j = nem_j;
-          const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-          const bool start = nem_act && (j & 1) == 0;
-          if (nem_act) { nem_j++; nem_rows = 2; }
-          if (__ballot(start)) {
-            misc[l] = l;
-            wave_lds_fence();
-            if (start && l == 0 && spec != MSIM_SPEC_ONE) {
-              for (u32 i = N - 1; i >= 1; i--) {
-                const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-              }
-            }
-            wave_lds_fence();
-            u32 my_part = 0;
-            if (start && is_node) {
-              if (spec == MSIM_SPEC_ONE) {
-                const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                my_part = l == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-              } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                u32 comp = 0;
-                for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                my_part = ((comp >> l) & 1) ? (all_nodes & ~comp) : comp;
-              } else {
-                const u32 m = N / 2 + 1;
-                u32 pos = 0;
-                for (u32 i = 0; i < N; i++) if (misc[i] == l) pos = i;
-                const u32 i0 = (pos + N - (m / 2) % N) % N;
-                u32 vis = 0;
-                for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                my_part = all_nodes & ~vis;
-              }
-            }
-            if (start) {
-              part |= my_part;
-              const u32 words = N * MSIM_MASK_WORDS;
-              u32 off = 0;
-              if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-              else {
-                off = n_payload; n_payload += words;
-                if (is_node) { g_pay[off + l * 4] = part; g_pay[off + l * 4 + 1] = 0; g_pay[off + l * 4 + 2] = 0; g_pay[off + l * 4 + 3] = 0; }
-              }
-              nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-            }
-          }
-          if (nem_act && (j & 1) != 0) {
-            part = 0;
-            nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-          }
-          if (nem_act) nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-        }
-      }
+      #include "group8_nemesis.inc"
       {
         const bool gen = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
         if (__ballot(gen)) {
@@ -877,7 +705,7 @@ hipError_t msim_launch_raft4(const KParams &kp, uint32_t n, hipStream_t st) {
   const size_t lds = off;
   if (lds > 64 * 1024) return MSIM_LAYOUT_DOES_NOT_FIT;
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(r4_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const dim3 grid((n + 3) / 4);
   if (kp.N <= 5) raft4_launch<5>(rp, c.nemesis_mask != 0, rnd, grid, lds, st);
   else raft4_launch<8>(rp, c.nemesis_mask != 0, rnd, grid, lds, st);

@@ -9,28 +9,12 @@
 
 #include "engine_internal.h"
 #include "wave_common.h"
-#include "log2_table.h"
+#include "latency_sampler.h"
 
-// the Q24 log2 table of the exponential latency sampler: one copy per translation unit, uploaded by msim_upload_tables() before the
-// unit's first launch on a device
-static __constant__ u32 d_log2_q24[257];
+// the latency sampler's table is uploaded by msim_upload_tables() before the unit's first launch on a device
 static inline hipError_t msim_upload_tables() {
   MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));
   return hipSuccess;
-}
-
-// -ln(u), u = (r+1)/2^32, Q16, integer only
-__device__ __forceinline__ u32 neg_ln_q16(u32 r) {
-  if (r == 0xFFFFFFFFu) return 0;
-  const u32 v = r + 1;
-  const u32 e = 31 - __clz(v);
-  const u32 m = v << (31 - e);
-  const u32 idx = (m >> 23) & 0xFF;
-  const u32 f = (m >> 7) & 0xFFFF;
-  const u32 l0 = d_log2_q24[idx], l1 = d_log2_q24[idx + 1];
-  const u32 lg = (e << 24) + l0 + (u32)(((u64)(l1 - l0) * f) >> 16);
-  const u32 d = (32u << 24) - lg;
-  return (u32)(((u64)d * 2977044472ull) >> 40);
 }
 
 // min (deadline, id) over the n envelopes of an HBM spill area.  The scan is latency-bound — with one dependent load per

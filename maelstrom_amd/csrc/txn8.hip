@@ -23,11 +23,9 @@
 #include <hip/hip_runtime.h>
 
 #include "wave_common.h"
-#include "log2_table.h"
+#include "latency_sampler.h"
 
 namespace {
-
-__constant__ u32 t8_log2_q24[257];
 
 constexpr u32 GS = 8u;            // lanes per cluster
 constexpr u32 RQ = 3u;            // LDS envelopes per node / service queue
@@ -50,18 +48,6 @@ struct T8Params {
   u32 round_limit;
 };
 
-__device__ __forceinline__ u32 t8_neg_ln_q16(u32 r) {
-  if (r == 0xFFFFFFFFu) return 0;
-  const u32 v = r + 1;
-  const u32 e = 31 - __clz(v);
-  const u32 m = v << (31 - e);
-  const u32 idx = (m >> 23) & 0xFF;
-  const u32 f = (m >> 7) & 0xFFFF;
-  const u32 l0 = t8_log2_q24[idx], l1 = t8_log2_q24[idx + 1];
-  const u32 lg = (e << 24) + l0 + (u32)(((u64)(l1 - l0) * f) >> 16);
-  const u32 d = (32u << 24) - lg;
-  return (u32)(((u64)d * 2977044472ull) >> 40);
-}
 // min over the 8 lanes of the caller's group, in every lane of it
 __device__ __forceinline__ u32 oct_min(u32 v) {
   v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
@@ -142,7 +128,7 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
     if (src < N || src == SVC) {  // neither end is a client
       if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
       else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * t8_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
+      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
     }
     if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
     uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
@@ -734,7 +720,7 @@ hipError_t msim_launch_txn8(const KParams &kp, uint32_t n, hipStream_t st) {
   tp.round_limit = (kp.dev_flags & 0x100u) ? 4000000u : ROUND_LIMIT;
   const size_t lds = off;
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(t8_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const dim3 grid((n + 7) / 8), block(64);
   if (c.nemesis_mask) { if (rnd) hipLaunchKernelGGL((txn8_kernel<true, true>), grid, block, lds, st, tp); else hipLaunchKernelGGL((txn8_kernel<true, false>), grid, block, lds, st, tp); }
   else { if (rnd) hipLaunchKernelGGL((txn8_kernel<false, true>), grid, block, lds, st, tp); else hipLaunchKernelGGL((txn8_kernel<false, false>), grid, block, lds, st, tp); }

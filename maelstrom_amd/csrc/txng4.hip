@@ -4,8 +4,8 @@
 // Same program and the same rounds as txng_kernel<> (sim_kernel_txng.inc; specification: oracle/txn_nodes.inc): node =
 // demo/clojure/single_key_txn.clj:116-180 == demo/js/single_key_txn.js (every request in its own future: read the root, apply, cas with
 // create_if_not_exists; a lost race answers error 30), service = lin-kv over the key "root" (service.clj:31-61), client =
-// workload/txn_list_append.clj:94-126, generator = [upstream] elle list-append.  What changes is the mapping, as in txng4.hip (whose time /
-// scheduler / COMMIT / client machinery this file shares line for line): a cluster is n nodes + its worker slots + lin-kv <= 16 endpoints, one
+// workload/txn_list_append.clj:94-126, generator = [upstream] elle list-append.  What changes is the mapping, as in svc4.hip (the time step,
+// the network, the partition nemesis and the history rows are shared: group16.h, group16_*.inc): a cluster is n nodes + its worker slots + lin-kv <= 16 endpoints, one
 // lane each of a 16-lane group — 1 node with 10 workers is 12, 5 nodes with 10 workers are 16 — and a wavefront carries four clusters.
 //
 // Scope (engine.hip picks this kernel when all of it holds, else txng_kernel<> runs): concurrency a multiple of n above n,
@@ -19,12 +19,10 @@
 #include <hip/hip_runtime.h>
 
 #include "wave_common.h"
-#include "log2_table.h"
+#include "group16.h"
 #include "layout_thresholds.h"
 
 namespace {
-
-__constant__ u32 g4_log2_q24[257];
 
 constexpr u32 GS = 16u;           // lanes per cluster
 #ifndef G4_RQ
@@ -52,35 +50,6 @@ struct G4Params {
   u32 ls;                                     // transaction slots per node in LDS
   u32 round_limit;
 };
-
-__device__ __forceinline__ u32 g4_neg_ln_q16(u32 r) {
-  if (r == 0xFFFFFFFFu) return 0;
-  const u32 v = r + 1;
-  const u32 e = 31 - __clz(v);
-  const u32 m = v << (31 - e);
-  const u32 idx = (m >> 23) & 0xFF;
-  const u32 f = (m >> 7) & 0xFFFF;
-  const u32 l0 = g4_log2_q24[idx], l1 = g4_log2_q24[idx + 1];
-  const u32 lg = (e << 24) + l0 + (u32)(((u64)(l1 - l0) * f) >> 16);
-  const u32 d = (32u << 24) - lg;
-  return (u32)(((u64)d * 2977044472ull) >> 40);
-}
-// min over the 16 lanes of the caller's DPP row (= its group), in every lane of the row
-__device__ __forceinline__ u32 row_min(u32 v) {
-  v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_mov<0x4E, 0xF, 0xF, false>(v, v));   // quad_perm [2,3,0,1]
-  v = min(v, dpp_mov<0x141, 0xF, 0xF, false>(v, v));  // row_half_mirror
-  v = min(v, dpp_mov<0x140, 0xF, 0xF, false>(v, v));  // row_mirror
-  return v;
-}
-// inclusive prefix sum over the 16 lanes of the row
-__device__ __forceinline__ u32 row_scan(u32 v) {
-  v += dpp_mov<0x111, 0xF, 0xF, true>(0, v);   // row_shr:1
-  v += dpp_mov<0x112, 0xF, 0xF, true>(0, v);   // row_shr:2
-  v += dpp_mov<0x114, 0xF, 0xF, true>(0, v);   // row_shr:4
-  v += dpp_mov<0x118, 0xF, 0xF, true>(0, v);   // row_shr:8
-  return v;
-}
 
 template <bool NEM, bool NET_RANDOM>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVES))) txng4_kernel(const G4Params rp) {
@@ -136,9 +105,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVE
   if (real) for (u32 i = l; i < mv; i += GS) g_kvn[i] = 0;
   __syncthreads();
 
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFFFu; };            // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
-
   // ---- endpoint state ----
   bool has_c = false; u32 deliver_at = 0; uint4 cm = make_uint4(0, 0, 0, 0);
   bool have_pm = false; uint4 pm = make_uint4(0, 0, 0, 0);
@@ -155,54 +121,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVE
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
 
-  auto q_push = [&](const uint4 m) {
-    if (in_n < RQ) { my_q[in_n * 64u] = m; in_n++; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) {
-    u32 lat = 0;
-    if ((src < N || src == SVC) && is_server) {  // neither end is a client (util.clj:7-16)
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * g4_neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    q_push(m);
-  };
-  auto try_commit = [&](const uint4 e) {
-    const u32 src = e.w >> 24;
-    if (NEM && is_node && src < N && ((part >> src) & 1)) return;
-    cm = e; has_c = true;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;
-  };
-  auto poll = [&]() {
-    const bool elig = alive && (is_server || busy);
-    if (have_pm) {
-      have_pm = false;
-      if (elig && !has_c && (in_n | sp_n) == 0) try_commit(pm);
-      else q_push(pm);
-    }
-    while (elig && !has_c && (in_n | sp_n) != 0) {
-      u32 best = 0; bool in_spill = false;
-      uint2 bk = make_uint2(INF, INF);
-      for (u32 i = 0; i < in_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_q[i * 64u]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-      }
-      for (u32 i = 0; i < sp_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_spill[i]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-      }
-      uint4 e;
-      if (in_spill) { e = my_spill[best]; sp_n--; if (best != sp_n) my_spill[best] = my_spill[sp_n]; }
-      else { e = my_q[best * 64u]; in_n--; if (best != in_n) my_q[best * 64u] = my_q[in_n * 64u]; }
-      try_commit(e);
-    }
-  };
+#define SERVER_SRC(src) ((src) < N || (src) == SVC)   // whether sender lane src is a server: the nodes and lin-kv
+  #include "group16_net.inc"
   // elements of `k` visible at version `from`
   auto visible = [&](u32 k, u32 from) -> u32 {
     if (from == V_NIL) return 0u;
@@ -215,52 +135,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVE
   for (;;) {
     if (!__ballot(alive)) break;
 
-    const u32 busy_mask = GB(busy);
+    #include "group16_phase.inc"
 
-    // ---- time-free phase transitions: lin-kv has no final generator (core.clj:74-80 applies only with one) ----
-    if (__ballot(alive && !(phase == PH_MAIN && ((rate > 0 && gen_next < cutoff) || (NEM && nem_next < cutoff))))) {
-      for (;;) {
-        bool ch = false;
-        if (alive) {
-          if (phase == PH_INIT_WAIT && !busy_mask) { phase = PH_MAIN_START; ch = true; }
-          if (phase == PH_MAIN_START) { cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; nem_next = T; next_msg_id = 0; loss_on = 1; phase = PH_MAIN; ch = true; }
-          if (phase == PH_MAIN && !((rate > 0 && gen_next < cutoff) || (NEM && nem_next < cutoff)) && !(rate == 0 && T < cutoff)) { phase = PH_DRAIN; ch = true; }
-          if (phase == PH_DRAIN && !(busy_mask & worker_mask)) { phase = PH_DONE; ch = true; }
-        }
-        if (!__ballot(ch)) break;
-      }
-      if (phase == PH_DONE) alive = false;
-      if (!__ballot(alive)) break;
-    }
-    if (alive && ++rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = worker_mask & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
-    u32 my_t = has_c ? deliver_at : INF;
-    bool timeout_round = false;
-    {
-      const bool none_due = GB(my_t <= T) == 0;
-      const bool jump = alive && due > T && none_due;
-      if (__ballot(jump)) {
-        u32 k = my_t == INF ? INF : my_t * 2;
-        if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = row_min(k);
-        if (due != INF) km = min(km, due * 2);
-        if (jump) {
-          if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-          else { timeout_round = (km & 1) != 0; T = max(T, km >> 1); }
-        }
-      }
-    }
+    #include "group16_time.inc"
+    #include "group16_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0, inv_len = 0;
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
@@ -284,62 +162,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVE
       if (__ballot(act && phase == PH_INIT)) {
         if (act && phase == PH_INIT) { if (is_client && slot < N) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; }
       }
-      if (NEM) {
-        const bool nem_act = act && phase == PH_MAIN && nem_live && nem_next <= T;
-        if (__ballot(nem_act)) {
-          const u32 j = nem_j;
-          const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-          const bool start = nem_act && (j & 1) == 0;
-          if (nem_act) { nem_j++; nem_rows = 2; }
-          if (__ballot(start)) {
-            misc[l] = l;
-            wave_lds_fence();
-            if (start && l == 0 && spec != MSIM_SPEC_ONE) {
-              for (u32 i = N - 1; i >= 1; i--) {
-                const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-              }
-            }
-            wave_lds_fence();
-            u32 my_part = 0;
-            if (start && is_node) {
-              if (spec == MSIM_SPEC_ONE) {
-                const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                my_part = l == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-              } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                u32 comp = 0;
-                for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                my_part = ((comp >> l) & 1) ? (all_nodes & ~comp) : comp;
-              } else {
-                const u32 m = N / 2 + 1;
-                u32 pos = 0;
-                for (u32 i = 0; i < N; i++) if (misc[i] == l) pos = i;
-                const u32 i0 = (pos + N - (m / 2) % N) % N;
-                u32 vis = 0;
-                for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                my_part = all_nodes & ~vis;
-              }
-            }
-            if (start) {
-              part |= my_part;
-              const u32 words = N * MSIM_MASK_WORDS;
-              u32 off = 0;
-              if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-              else {
-                off = n_payload; n_payload += words;
-                if (is_node) { g_pay[off + l * 4] = part; g_pay[off + l * 4 + 1] = 0; g_pay[off + l * 4 + 2] = 0; g_pay[off + l * 4 + 3] = 0; }
-              }
-              nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-            }
-          }
-          if (nem_act && (j & 1) != 0) {
-            part = 0;
-            nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-          }
-          if (nem_act) nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-        }
-      }
+      #include "group8_nemesis.inc"
       {
         const bool gen = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
         if (__ballot(gen)) {
@@ -554,45 +377,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G4_WAVE
         }
       }
     }
-    // ---- history rows: nemesis rows, invocations (slot order), completions (slot order) ----
-    {
-      const u32 imask = GB(inv_row), cmask = GB(cmp_row);
-      const u32 ni = __popc(imask);
-      const u32 nr = nem_rows + ni + __popc(cmask);
-      if (__ballot(alive && nr != 0)) {
-        const bool ovf = alive && nr != 0 && n_rows + nr > max_rows;
-        if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = false; }
-        const bool wr = alive && nr != 0;
-        const u64 tns = (u64)T * 1000ull;
-        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-        // rows straight to HBM: the rows of a round are adjacent 16-byte stores (a staging ring of 64 rows per cluster was 4 KiB of LDS and a wavefront per SIMD less)
-        msim_op *const gr = g_rows;
-        if (NEM && wr && nem_rows && l == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          reinterpret_cast<uint4 *>(gr)[n_rows] = make_uint4(tlo, thi, pk, nem_v1);
-          reinterpret_cast<uint4 *>(gr)[n_rows + 1] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (wr && inv_row) reinterpret_cast<uint4 *>(gr)[n_rows + nem_rows + __popc(imask & lt)] = make_uint4(tlo, thi | (inv_len << 16), inv_packed, inv_value);
-        if (wr && cmp_row) reinterpret_cast<uint4 *>(gr)[n_rows + nem_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        const u32 new_n = wr ? n_rows + nr : n_rows;
-        n_rows = new_n;
-      }
-    }
+    #include "group16_rows.inc"
   }
 
-  const u32 t_send_cl = GGET(row_scan(s_send_cl), GS - 1u), t_send_sv = GGET(row_scan(s_send_sv), GS - 1u);
-  const u32 t_recv_cl = GGET(row_scan(s_recv_cl), GS - 1u), t_recv_sv = GGET(row_scan(s_recv_sv), GS - 1u);
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (GB((my_flags & b) != 0)) flags |= b;
-  if (real && l == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
-    p.meta[inst] = m;
-  }
+  #include "group16_stats.inc"
 }
 
 }  // namespace
@@ -628,7 +416,7 @@ hipError_t msim_launch_txng4(const KParams &kp, uint32_t n, hipStream_t st) {
   const size_t lds = off;
   if (lds > 64 * 1024) return MSIM_LAYOUT_DOES_NOT_FIT;
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT || c.p_loss_q32 != 0;
-  if (rnd) MSIM_UPLOAD_ONCE(g4_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
+  if (rnd) MSIM_UPLOAD_ONCE(d_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
   const dim3 grid((n + 3) / 4), block(64);
   if (c.nemesis_mask) { if (rnd) hipLaunchKernelGGL((txng4_kernel<true, true>), grid, block, lds, st, rp); else hipLaunchKernelGGL((txng4_kernel<true, false>), grid, block, lds, st, rp); }
   else { if (rnd) hipLaunchKernelGGL((txng4_kernel<false, true>), grid, block, lds, st, rp); else hipLaunchKernelGGL((txng4_kernel<false, false>), grid, block, lds, st, rp); }
