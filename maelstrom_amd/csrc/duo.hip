@@ -29,7 +29,9 @@
 //       own LDS ring; idle receivers poll (pop the ring head / the pending client request);
 //       the nodes' seen sets live in HBM scratch, one region per cluster (the LDS holds the queues alone);
 //   R4  completions -> history rows (staged in LDS, 1 KiB coalesced appends)   — GENERAL rounds only
-// A wave-round is GENERAL if either cluster needs it; pure gossip rounds of both clusters take the short body.
+// A wave-round is GENERAL if either cluster needs it; pure gossip rounds of both clusters take the short body.  At latency 0 a GENERAL
+// round whose every acting cluster is quiescent and only runs its generator's op (nearly all of them) is an OP ROUND instead: the
+// gossip body plus the op's pick, broadcast or read and two history rows, without R1-R4's general machinery.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
@@ -117,8 +119,10 @@ __device__ __forceinline__ u64 hm2(bool lo, bool up) { return (lo ? 0xFFFFFFFFul
 __device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
 
+// Latency 0: at least 6 wavefronts per SIMD (<= 80 VGPRs), what three launches of 2048 wavefronts in flight need; with the op round
+// beside the GENERAL body the register allocator otherwise takes 86 to 92 (no spills at 80)
 template <bool LAT0, bool DEG4, bool RND>
-__global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
+__global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoParams dp) {
   static_assert(!(RND && LAT0), "random latency needs deadlines");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const KParams &p = dp.k;
@@ -473,7 +477,7 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
   } while (0)
 
 #ifdef DUO_PROF   // developer build (tools/variant_lib.sh prof duo.hip -DDUO_PROF): wave-round counts and cycles of the two round bodies -> meta
-  u64 pf_t0 = __builtin_readcyclecounter(), pf_gen = 0; u32 pf_ngen = 0, pf_nwave = 0;
+  u64 pf_t0 = __builtin_readcyclecounter(), pf_gen = 0, pf_op = 0; u32 pf_ngen = 0, pf_nop = 0, pf_nwave = 0;
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)  // developer builds: cycles of the sections of the gossip round (PROF2) or of the GENERAL round (PROF3)
   u64 p2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, p2_t = __builtin_readcyclecounter();   // -> meta of the wavefront's two instances (replaces DUO_PROF's numbers)
@@ -489,10 +493,40 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 #else
 #define P3_MARK(i_)
 #endif
+  // the scheduler's view for the rounds to come (oracle: sched_resolve, sched_due): time-free phase transitions, the round limit, when
+  // the scheduler acts next and which clusters have to run GENERAL rounds meanwhile; hbusy_b = bal(busy != 0)
+#define DUO_SCHED_VIEW(hbusy_b_) do {                                                                                     \
+    const u32 sv_hbusy = hi ? (u32)((hbusy_b_) >> 32) : (u32)(hbusy_b_);                                                  \
+    for (;;) {                                                                                                            \
+      bool sv_ch = false;                                                                                                 \
+      if (lane_in(alive_m)) {                                                                                             \
+        if (phase == PH_INIT_WAIT && sv_hbusy == 0) { phase = PH_TOPO; sv_ch = true; }                                    \
+        if (phase == PH_TOPO_WAIT && sv_hbusy == 0) { phase = PH_MAIN_START; sv_ch = true; }                              \
+        if (phase == PH_MAIN_START) { cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; phase = PH_MAIN; sv_ch = true; } \
+        if (phase == PH_MAIN && !(rate > 0 && gen_next < cutoff) && !(rate == 0 && T < cutoff)) { phase = PH_DRAIN; sv_ch = true; } \
+        if (phase == PH_DRAIN && sv_hbusy == 0) { phase = PH_SLEEP; sleep_until = T + p.cfg.quiesce_ms * 1000u; sv_ch = true; } \
+        if (phase == PH_FINAL_WAIT && sv_hbusy == 0) { phase = PH_DONE; sv_ch = true; }                                   \
+      }                                                                                                                   \
+      if (!__ballot(sv_ch)) break;                                                                                        \
+    }                                                                                                                     \
+    alive_m &= ~bal(phase == PH_DONE);                                                                                    \
+    const u64 sv_lim_b = alive_m & bal(rounds > round_limit);                                                             \
+    flags |= lane_in(sv_lim_b) ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u; alive_m &= ~sv_lim_b;                                   \
+    const bool sv_gen_live = rate > 0 && gen_next < cutoff;                                                               \
+    u32 sv_sa = INF;                                                                                                      \
+    if (phase == PH_MAIN) {                                                                                               \
+      if (sv_gen_live && (all_nodes & ~sv_hbusy) != 0) sv_sa = gen_next;                                                  \
+      if (rate == 0) sv_sa = min(sv_sa, cutoff);                                                                          \
+    } else if (phase == PH_INIT || phase == PH_TOPO || phase == PH_FINAL) sv_sa = T;                                      \
+    else if (phase == PH_SLEEP) sv_sa = sleep_until;                                                                      \
+    sched_at = lane_in(alive_m) ? sv_sa : INF;                                                                            \
+    fg_m = alive_m & ~((rate > 0 ? bal(phase == PH_MAIN) & bal(gen_next < cutoff) : 0ull) | bal(phase == PH_SLEEP));      \
+  } while (0)
   for (;;) {
     // the halves whose scheduler wants a GENERAL round, alive & (force_general | sched_at <= T): recomputed where its parts change (after a
     // GENERAL round, at a time jump, at the round limit); a gossip round adds the halves with a special envelope due
     u64 want_m = alive_m & (fg_m | bal(sched_at <= T));
+    u64 op_m = 0, op_due = 0;   // LAT0: the halves that take an op round (see below; 0: the GENERAL body runs), the due envelopes
     // ---- gossip rounds of both clusters, until one of them needs a GENERAL round ----
     for (;;) {
 #ifdef DUO_PROF
@@ -527,7 +561,19 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
       rounds += alive_v;
       const bool due_n = lane_in(due_b);
       // GENERAL if alive & (force_general | sched_at <= T | special), special = due_n & (cm >> 24) != DK_PLAIN
-      if ((want_m | (alive_m & due_b & bal(cm > 0xFFFFFFu))) != 0 || stuck_any) break;   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
+      if (const u64 gw_m = want_m | (alive_m & due_b & bal(cm > 0xFFFFFFu)); gw_m != 0 || stuck_any) {   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
+        if (LAT0 && !RND && rate > 0 && !stuck_any) {
+          // The steady state of latency 0: the scheduler acts right after its time jump, so the acting cluster is quiescent — no envelope
+          // due (at latency 0 a node that holds one has it due), hence every node idle with an empty queue and every client free.  Its
+          // generator's op is then all the cluster does this round: an op round.  Every half that wants a GENERAL round has to be in
+          // that state (main phase, not forced, nothing due, no client busy, room for a value and two rows); else the GENERAL body runs.
+          const u64 bz_b = bal(busy != 0);
+          const u64 st_m = ~fg_m & bal(phase == PH_MAIN) & bal(next_value < max_values) & bal(n_rows + 2u <= max_rows) & bal(gen_k - dc_base < 32u) &
+                           hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
+          op_m = (gw_m & ~st_m) == 0 ? gw_m : 0ull; op_due = due_b;
+        }
+        break;
+      }
       {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
         u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
@@ -547,7 +593,76 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
 #ifdef DUO_PROF
     const u64 pf_a = __builtin_readcyclecounter();
 #endif
-    {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
+    if (LAT0 && !RND && op_m != 0) {
+      // ---- an op round: the gossip round of both clusters, plus the op of each cluster in op_m.  It computes what the GENERAL body
+      //      computes for such a cluster: every worker is free, so the pick is the node of that rank, and it is idle, so its recv! takes
+      //      the request at once and the node completes it in this round (busy goes 1 -> 0 within the round) ----
+      const bool opn = lane_in(op_m);
+      // the word of the nodes' sets that the op's value falls in, fetched first: only the picked node's store at the end of the round
+      // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
+      u32 op_w = 0;
+      if (opn) op_w = DUO_SET(set_lane + ((next_value & 0xFFE0u) << 2));
+      const u32 dc_at = hbase4 + ((gen_k - dc_base) << 2);   // (the op's draw is in the cluster's block of 32; the GENERAL body draws the next block)
+      const u32 r_hi = bperm(dc_at, (u32)(dc >> 32)), r_lo = bperm(dc_at, (u32)dc);
+      const bool sel = opn && i == scale32(r_lo, N);
+      const bool is_rd = (r_lo & 1u) != 0;
+      const bool bc = sel & !is_rd;
+      const u32 val = next_value;
+      next_value += opn && !is_rd ? 1u : 0u;
+      gen_k += opn ? 1u : 0u;
+      gen_next = opn ? T + __umulhi(r_hi, p.gen_period2_us) : gen_next;
+      n_cl += sel ? 1u : 0u;
+      // R3: the gossip of both clusters (the picked nodes are idle: due_n is false there), then the picked node's broadcast
+      const bool due_n = lane_in(op_due);
+      u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, op_due, pub, pub_b);
+      deliver_at = due_n ? INF : deliver_at;
+      n_rsv += due_n ? 1u : 0u;
+      pub = bc ? (0x80000000u | (63u << 16) | val) : pub;
+      pub_b |= bal(bc);
+      // a read -> read_ok with the whole set, copied by the cluster's lanes (one reader per cluster)
+      u32 cmp_value = val, cmp_len = 0;
+      if (const u64 rd_b = bal(sel) & bal(is_rd)) {
+        wave_lds_fence();
+        const u32 words = (next_value + 31u) >> 5;
+        const bool ok = n_payload + words <= max_pay;   // payload_alloc of the oracle
+        const u64 ok_b = rd_b & bal(ok);
+        if (sel && is_rd) {
+          if (!ok) my_flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
+          cmp_value = ok ? n_payload : 0u; cmp_len = words;
+        }
+        const u32 ok_lo = (u32)ok_b, ok_up = (u32)(ok_b >> 32), okm = hi ? ok_up : ok_lo;
+        const u32 r1 = okm ? (u32)__builtin_ctz(okm) : 0u;
+        const u64 cp_b = hm2(ok_lo != 0, ok_up != 0);   // the clusters that copy a set
+        for (u32 w = i; cp_b & bal(w < words); w += 32)
+          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = DUO_SET(set_half + w * 128u + r1 * 4u);
+        n_payload += okm ? words : 0u;
+      }
+      // R4: the invocation and the completion row
+      if (sel) {
+        const u64 tns = (u64)T * 1000ull;
+        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
+        const u32 fk = is_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
+        reinterpret_cast<uint4 *>(g_rows)[n_rows] = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (i << 12), is_rd ? MSIM_NO_VALUE : val);
+        reinterpret_cast<uint4 *>(g_rows)[n_rows + 1u] = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (i << 12), cmp_value);
+      }
+      n_rows += opn ? 2u : 0u;
+      if (pub_b) DUO_ARRIVALS(pub);
+      if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w | (1u << (val & 31u));
+      DUO_POLL();
+      // the scheduler's view: an acting cluster acts again at its generator's next op (every worker is free again); the others are as
+      // they were.  The full view runs when it would run in the GENERAL body (an op moved gen_next to or past cutoff)
+      if (alive_m & (bal(phase != PH_MAIN) | bal(gen_next >= cutoff) | bal(rounds > round_limit))) {
+        const u64 hbusy_b = bal(busy != 0);
+        DUO_SCHED_VIEW(hbusy_b);
+        alive_v = lane_in(alive_m) ? 1u : 0u;
+        if (~alive_m) {
+          if (!lane_in(alive_m)) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
+        }
+      } else sched_at = opn ? gen_next : sched_at;
+#ifdef DUO_PROF
+      pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++;
+#endif
+    } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
     u32 inv_row = 0, inv_packed = 0, inv_value = 0;
     u32 cmp_row = 0, cmp_packed = 0, cmp_value = 0, cmp_len = 0;
@@ -697,32 +812,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     // ---- the scheduler's view for the rounds to come: time-free phase transitions (oracle: sched_resolve), when it
     //      acts next (sched_due), and whether plain gossip rounds may run meanwhile ----
     const u64 hbusy_b = bal(busy != 0);
-    const u32 hbusy = hi ? (u32)(hbusy_b >> 32) : (u32)hbusy_b;
     if (alive_m & (bal(phase != PH_MAIN) | (rate > 0 ? bal(gen_next >= cutoff) : bal(true)) | bal(rounds > round_limit))) {
-      for (;;) {
-        bool ch = false;
-        if (lane_in(alive_m)) {
-          if (phase == PH_INIT_WAIT && hbusy == 0) { phase = PH_TOPO; ch = true; }
-          if (phase == PH_TOPO_WAIT && hbusy == 0) { phase = PH_MAIN_START; ch = true; }
-          if (phase == PH_MAIN_START) { cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; phase = PH_MAIN; ch = true; }
-          if (phase == PH_MAIN && !(rate > 0 && gen_next < cutoff) && !(rate == 0 && T < cutoff)) { phase = PH_DRAIN; ch = true; }
-          if (phase == PH_DRAIN && hbusy == 0) { phase = PH_SLEEP; sleep_until = T + p.cfg.quiesce_ms * 1000u; ch = true; }
-          if (phase == PH_FINAL_WAIT && hbusy == 0) { phase = PH_DONE; ch = true; }
-        }
-        if (!__ballot(ch)) break;
-      }
-      alive_m &= ~bal(phase == PH_DONE);
-      const u64 lim_b = alive_m & bal(rounds > round_limit);
-      flags |= lane_in(lim_b) ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u; alive_m &= ~lim_b;
-      const bool gen_live = rate > 0 && gen_next < cutoff;
-      u32 sa = INF;
-      if (phase == PH_MAIN) {
-        if (gen_live && (all_nodes & ~hbusy) != 0) sa = gen_next;
-        if (rate == 0) sa = min(sa, cutoff);
-      } else if (phase == PH_INIT || phase == PH_TOPO || phase == PH_FINAL) sa = T;
-      else if (phase == PH_SLEEP) sa = sleep_until;
-      sched_at = lane_in(alive_m) ? sa : INF;
-      fg_m = alive_m & ~((rate > 0 ? bal(phase == PH_MAIN) & bal(gen_next < cutoff) : 0ull) | bal(phase == PH_SLEEP));
+      DUO_SCHED_VIEW(hbusy_b);
     } else {
       // every live cluster of the wavefront is in the main phase with its generator running (nearly every GENERAL round): the
       // scheduler acts again when the generator's next op is due and a worker is free, plain gossip rounds may run meanwhile
@@ -734,10 +825,10 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
       if (!lane_in(alive_m)) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
     }
     P3_MARK(7)   // [7] = the scheduler's view
-    }
 #ifdef DUO_PROF
     pf_gen += __builtin_readcyclecounter() - pf_a; pf_ngen++;
 #endif
+    }
     if (!alive_m) break;
   }
 #ifdef DUO_PROF
@@ -767,7 +858,8 @@ __global__ void __launch_bounds__(64) sim_kernel_duo(const DuoParams dp) {
     msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
     m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
 #ifdef DUO_PROF
-    m.n_events = pf_ngen; m.reserved[0] = pf_nwave; m.reserved[1] = (u32)(pf_gen >> 6); m.reserved[2] = (u32)(pf_tot >> 6);
+    // GENERAL bodies | op rounds << 16, wave-rounds, their cycles / 1024 (GENERAL | op << 16), all cycles / 64 (tools/duo_prof_report.py)
+    m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave; m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6);
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): runs the headline batch with the DUO_PROF build (tools/variant_lib.sh prof duo.hip -DDUO_PROF) and prints, per wavefront,
-the number of wave-rounds, how many of them were GENERAL rounds, and the cycles spent in each kind."""
+the number of wave-rounds, how many of them were GENERAL rounds (op rounds and full GENERAL bodies), and the cycles spent in each kind."""
 import os
 import sys
 
@@ -22,9 +22,16 @@ with E.Engine(cfg) as eng:
     sim_ms = eng.kernel_ms()[0]
     eng.fetch()
     m = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2], eng.meta(i).n_rounds] for i in range(0, n, 2)], dtype=np.float64)
-ngen, nwave, cgen, ctot, rounds = m.T
-cgen *= 64; ctot *= 64
+ev, nwave, cyc, ctot, rounds = m.T
+ev = ev.astype(np.int64); cyc = cyc.astype(np.int64)
+ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, op rounds
+cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, (cyc >> 16).astype(np.float64) * 1024
+ctot *= 64
 print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms")
-print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.mean():.0f}), GENERAL {ngen.mean():.0f} ({100 * ngen.mean() / nwave.mean():.1f} %)")
-print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL rounds {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %)")
-print(f"cycles per GENERAL round {cgen.mean() / ngen.mean():.0f}, per gossip round {(ctot.mean() - cgen.mean()) / (nwave.mean() - ngen.mean()):.0f}")
+nsched = ngen.mean() + nop.mean()
+print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.mean():.0f}), GENERAL {nsched:.0f} ({100 * nsched / nwave.mean():.1f} %): "
+      f"op rounds {nop.mean():.0f} ({100 * nop.mean() / max(nsched, 1):.1f} % of them), full GENERAL bodies {ngen.mean():.0f}")
+print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL bodies {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %), "
+      f"in op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
+print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per op round {cop.mean() / max(nop.mean(), 1):.0f}, "
+      f"per gossip round {(ctot.mean() - cgen.mean() - cop.mean()) / (nwave.mean() - nsched):.0f}")
