@@ -32,6 +32,13 @@
 // A wave-round is GENERAL if either cluster needs it; pure gossip rounds of both clusters take the short body.  At latency 0 a GENERAL
 // round whose every acting cluster is quiescent and only runs its generator's op (nearly all of them) is an OP ROUND instead: the
 // gossip body plus the op's pick, broadcast or read and two history rows, without R1-R4's general machinery.
+// Between two such ops every envelope in flight in the cluster carries the op's value, and the latency-0 DEG4 instantiation keeps
+// the cluster in FLOOD MODE: a node's queue is a count, its set word stays in a register.  A wave-round is then one of
+//   flood gossip round   every live cluster in flood mode, none wants a GENERAL round: R0, dedup from the register, the pulls, a count
+//   flood op round       the same plus the op of each acting cluster, which (re-)enters flood mode with the op's value
+//   gossip / op round    the generic bodies (rings in LDS, set word re-read): some cluster is not in flood mode; they take one that is as it is
+//   GENERAL round        the full body; it first writes the queues of the clusters in flood mode out to their rings
+// (details at "FLOOD MODE" below; every round, delivery and message is still simulated: only the queue's representation differs).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
@@ -54,6 +61,12 @@ constexpr u32 DUO_BAG = DUO_BAG_N;   // random latencies: envelopes of a node's 
 constexpr bool DUO_DIRECT = false;
 #else
 constexpr bool DUO_DIRECT = true;
+#endif
+// Flood mode of the latency-0 kernel (see "flood mode" in sim_kernel_duo); -DDUO_NO_FLOOD compiles it out for A/B runs.
+#ifdef DUO_NO_FLOOD
+constexpr bool DUO_FLOOD_ON = false;
+#else
+constexpr bool DUO_FLOOD_ON = true;
 #endif
 #ifndef DUO_LDS_PAD
 #define DUO_LDS_PAD 0   // A/B builds (-DDUO_LDS_PAD=<bytes>): unused LDS per wavefront, fewer wavefronts per CU (msim_launch_duo)
@@ -143,8 +156,16 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   const u32 me16 = dp.echoback ? (64u << 16) : (i << 16);
   const u32 round_limit = dp.round_limit;
 
+  constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;   // the instantiations with a flood mode (see below)
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
+  // FLOOD: the cluster's rows and payload are addressed like its sets, from the wavefront's base (SGPRs: the lower cluster's) and the
+  // half's 0 / 1, so that no lane keeps a 64-bit pointer to them (the registers: 80 with room for the flood bodies)
+  const bool up_half = hi && real;   // the cluster is the wavefront's second one
+  msim_op *const w_rows = p.rows + (size_t)(blockIdx.x * 2u) * max_rows;
+  u32 *const w_pay = p.payload + (size_t)(blockIdx.x * 2u) * max_pay;
+#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? w_rows + (size_t)((up_half ? max_rows : 0u) + (idx_)) : g_rows + (idx_))[0])
+#define DUO_PAY(idx_) ((FLOOD ? w_pay + (size_t)((up_half ? max_pay : 0u) + (idx_)) : g_pay + (idx_))[0])
   // HBM spill behind the LDS ring: {deadline, envelope} pairs in the node's slice of the spill area
   u64 *const my_spill = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)inst * p.scratch_words + p.spill_off) +
                                                     (size_t)(is_node ? i : 0) * p.spill_cap);
@@ -236,6 +257,23 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   //   nx = the head entry of the ring (valid while in_n != 0; an append to an empty ring sets it from registers).
   u32 sw = 0;
   u32 nx = 0, nx_dl = 0;
+  // FLOOD MODE (latency 0, DEG4, rings of at least 8 entries).  At latency 0 an op round runs its op only when the cluster is quiescent:
+  // nothing is held, nothing queued.  From then until the cluster's next op every server envelope in flight carries the op's value (the
+  // flood of that broadcast), so a node's queue is a run of equal envelopes and need not be written out: it is the count in_n, nx is the
+  // word of its head (only the first envelope a node ever handles for the value can be new to it, so only that one's src matters: a later
+  // entry is a duplicate whatever its src), and "seen" is one bit of a word the node itself last wrote.  A node sends the value at most
+  // once, so at most 4 envelopes ever reach a node during a flood: in_n <= 4 <= R - 4, the fast-path condition of DUO_ARRIVALS cannot
+  // fail and sp_n stays 0 (overflow and the spill are only ever handled by the generic code).
+  // fl_m = the halves in flood mode (a lane mask like alive_m).  For such a half
+  //   * deliver_at, cm, in_n, n_arr, n_rsv, rounds mean what they always mean; sp_n == 0;
+  //   * the ring slots [head, head + in_n) are NOT valid (nobody reads them), every queued envelope is DK_PLAIN with the flood's value;
+  //   * sw is the node's set word for the flood value's word in EVERY lane, kept current in the register: no set word is loaded.
+  // An op round puts its acting halves into flood mode (op_w, the word it loads for every lane, becomes sw).  When every live half is in
+  // flood mode a wave-round runs a FLOOD body: no LDS store, no LDS load besides the pulls, no global load.  The generic gossip and op
+  // rounds take a half in flood mode as it is (they keep its sw and nx in registers; what they store in its ring is never read); the
+  // GENERAL body first MATERIALISES every such half: its in_n entries are written to the ring and the flag is cleared.
+  const bool fl_ok = FLOOD && R >= 8u;
+  u64 fl_m = 0;
   // The helpers below are macros on purpose: as lambdas capturing the state by reference they left the closures (and with
   // them every captured variable) in scratch memory once the optimizer turned a select of two captured values into a select
   // of their addresses.
@@ -352,7 +390,8 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
           in_n++;                                                                                                         \
         }                                                                                                                 \
       }                                                                                                                   \
-      if (LAT0) nx = ring32[head * 32u]; else { const u64 pl_h = ring64[head * 32u]; nx_dl = (u32)pl_h; nx = (u32)(pl_h >> 32); } \
+      if (LAT0) { const u32 pl_h = ring32[head * 32u]; nx = (FLOOD && lane_in(fl_m)) ? nx : pl_h; }   /* (flood mode: the head entry stays in nx) */ \
+      else { const u64 pl_h = ring64[head * 32u]; nx_dl = (u32)pl_h; nx = (u32)(pl_h >> 32); }                          \
     }                                                                                                                     \
     DUO_SW_PREFETCH();                                                                                                    \
   } while (0)
@@ -360,11 +399,13 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   // to its neighbours: bit 31 | value | src to skip << 16, or 0; hball_ = the ballot of handle_, pubb_ = the ballot of pub_ != 0
 #ifdef DUO_NO_SWPF   /* A/B build: the set word is read where it is used */
 #define DUO_SW_PREFETCH() do { } while (0)
-#define DUO_SW_NOW() do { sw = DUO_SEEN_WORD(); } while (0)
+#define DUO_SW_NOW() DUO_SW_LOAD()
 #else
-#define DUO_SW_PREFETCH() do { sw = DUO_SEEN_WORD(); } while (0)
+#define DUO_SW_PREFETCH() DUO_SW_LOAD()
 #define DUO_SW_NOW() do { } while (0)
 #endif
+  // (a half in flood mode keeps its set word in the register)
+#define DUO_SW_LOAD() do { const u32 sl_w = DUO_SEEN_WORD(); sw = (FLOOD && lane_in(fl_m)) ? sw : sl_w; } while (0)
 #define DUO_R3_SEEN(handle_, hball_, pub_, pubb_) do {                                                                    \
     DUO_SW_NOW();                                                                                                         \
     const u32 r3_bit = 1u << (cm & 31u);                                                                                  \
@@ -372,6 +413,47 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     pubb_ = (hball_) & bal((sw & r3_bit) == 0);                                                                           \
     if (r3_new) DUO_SEEN_WORD() = sw | r3_bit;                                                                           \
     pub_ = r3_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                                \
+    if (FLOOD) sw = r3_new ? (sw | r3_bit) : sw;                                                                          \
+  } while (0)
+  // ---- the flood bodies' parts (every live half in flood mode) ----
+  // R3: the dedup from the register; the node's one store of its set word stays (reads copy the sets from HBM)
+#define DUO_FLOOD_R3(due_n_, due_b_, pub_, pubb_) do {                                                                    \
+    const u32 fr_w = sw | (1u << (cm & 31u));                                                                             \
+    const bool fr_new = (due_n_) & (fr_w != sw);                                                                          \
+    pubb_ = (due_b_) & bal(fr_w != sw);                                                                                   \
+    if (fr_new) DUO_SEEN_WORD() = fr_w;                                                                                   \
+    pub_ = fr_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                                \
+    sw = fr_new ? fr_w : sw;                                                                                              \
+  } while (0)
+  // COMMIT: the pulls of DUO_ARRIVALS; the arrivals are only counted, an empty queue's head entry is its first arrival
+#define DUO_FLOOD_ARRIVALS(pub_) do {                                                                                     \
+    const u32 fa_zk = 0x80000000u | me16;                                                                                 \
+    const u32 fa_x[4] = {bperm(nbl[0], pub_), bperm(nbl[1], pub_), bperm(nbl[2], pub_), bperm(nbl[3], pub_)};             \
+    bool fa_g[4]; u32 fa_c = 0;                                                                                           \
+    _Pragma("unroll") for (int fa_k = 0; fa_k < 4; fa_k++) { fa_g[fa_k] = (int)((fa_x[fa_k] & 0x803F0000u) ^ fa_zk) > 0; fa_c += fa_g[fa_k] ? 1u : 0u; } \
+    const u32 fa_fx = fa_g[0] ? fa_x[0] : fa_g[1] ? fa_x[1] : fa_g[2] ? fa_x[2] : fa_x[3];                                \
+    const u32 fa_fk = fa_g[0] ? kc[0] : fa_g[1] ? kc[1] : fa_g[2] ? kc[2] : kc[3];                                        \
+    nx = in_n == 0 ? ((fa_fx & 0xFFFFu) | fa_fk) : nx;                                                                    \
+    in_n += fa_c; n_arr += fa_c;                                                                                          \
+  } while (0)
+  // the poll.  At latency 0 a node that holds an envelope has it due (deliver_at is the T of its commit or INF, and T never falls), so
+  // after R3 every node is idle: the node takes the head of its queue if there is one.  No ring-head reload, no set-word prefetch.
+#define DUO_FLOOD_POLL() do {                                                                                             \
+    const bool fp_can = in_n != 0;                                                                                        \
+    cm = fp_can ? nx : cm; deliver_at = fp_can ? T : INF; in_n -= fp_can ? 1u : 0u;                                       \
+  } while (0)
+  // leaving flood mode: the queued envelopes of every half in flood mode go to their ring (nx for each: see above); the fence orders
+  // the stores before the reload of the ring head by the poll that follows
+#define DUO_MATERIALISE() do {                                                                                            \
+    if (FLOOD && fl_m != 0) {                                                                                             \
+      PF_MAT_BEGIN                                                                                                        \
+      const bool mt_on = lane_in(fl_m);                                                                                   \
+      for (u32 mt_k = 0; __ballot(mt_on & (mt_k < in_n)); mt_k++)                                                         \
+        if (mt_on & (mt_k < in_n)) ring32[((head + mt_k) & Rm) * 32u] = nx;                                               \
+      wave_lds_fence();                                                                                                   \
+      fl_m = 0;                                                                                                           \
+      PF_MAT_END                                                                                                          \
+    }                                                                                                                     \
   } while (0)
   // COMMIT of the fan-outs, receiver side: every node pulls what its neighbours publish, in ascending sender order (= id order,
   // net.clj:197), and appends it to its own queue.  got <=> the neighbour sends and does not skip this node:
@@ -478,6 +560,13 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
 
 #ifdef DUO_PROF   // developer build (tools/variant_lib.sh prof duo.hip -DDUO_PROF): wave-round counts and cycles of the two round bodies -> meta
   u64 pf_t0 = __builtin_readcyclecounter(), pf_gen = 0, pf_op = 0; u32 pf_ngen = 0, pf_nop = 0, pf_nwave = 0;
+  u64 pf_it = 0, pf_fg = 0, pf_fop = 0, pf_mat = 0; u32 pf_nfg = 0, pf_nfop = 0, pf_nmat = 0;   // flood gossip rounds, flood op rounds, materialisations
+  u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
+#define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
+#define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
+#else
+#define PF_MAT_BEGIN
+#define PF_MAT_END
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)  // developer builds: cycles of the sections of the gossip round (PROF2) or of the GENERAL round (PROF3)
   u64 p2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, p2_t = __builtin_readcyclecounter();   // -> meta of the wavefront's two instances (replaces DUO_PROF's numbers)
@@ -530,7 +619,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     // ---- gossip rounds of both clusters, until one of them needs a GENERAL round ----
     for (;;) {
 #ifdef DUO_PROF
-      pf_nwave++;
+      pf_nwave++; pf_it = __builtin_readcyclecounter();
 #endif
       // R0: the cluster's time: stay at T while something is due, else jump to the next delivery / scheduler event.
       // Only looked at when one of the two clusters has nothing due (a scalar test on the halves of one ballot).
@@ -574,7 +663,15 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         }
         break;
       }
-      {   // ---- a round in which both clusters only gossip ----
+      if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
+        u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
+        n_rsv += due_n ? 1u : 0u;
+        if (pub_b) DUO_FLOOD_ARRIVALS(pub);
+        DUO_FLOOD_POLL();
+#ifdef DUO_PROF
+        pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg++;
+#endif
+      } else {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
         u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
         deliver_at = due_n ? INF : deliver_at;
@@ -592,6 +689,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     if (!alive_m) break;
 #ifdef DUO_PROF
     const u64 pf_a = __builtin_readcyclecounter();
+    pf_exit += pf_a - pf_it;
 #endif
     if (LAT0 && !RND && op_m != 0) {
       // ---- an op round: the gossip round of both clusters, plus the op of each cluster in op_m.  It computes what the GENERAL body
@@ -602,6 +700,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
       u32 op_w = 0;
       if (opn) op_w = DUO_SET(set_lane + ((next_value & 0xFFE0u) << 2));
+      const bool fl_round = FLOOD && (alive_m & ~fl_m) == 0;   // every live half is in flood mode: the flood op round
       const u32 dc_at = hbase4 + ((gen_k - dc_base) << 2);   // (the op's draw is in the cluster's block of 32; the GENERAL body draws the next block)
       const u32 r_hi = bperm(dc_at, (u32)(dc >> 32)), r_lo = bperm(dc_at, (u32)dc);
       const bool sel = opn && i == scale32(r_lo, N);
@@ -614,8 +713,9 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       n_cl += sel ? 1u : 0u;
       // R3: the gossip of both clusters (the picked nodes are idle: due_n is false there), then the picked node's broadcast
       const bool due_n = lane_in(op_due);
-      u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, op_due, pub, pub_b);
-      deliver_at = due_n ? INF : deliver_at;
+      u32 pub; u64 pub_b;
+      if (fl_round) DUO_FLOOD_R3(due_n, op_due, pub, pub_b);
+      else { DUO_R3_SEEN(due_n, op_due, pub, pub_b); deliver_at = due_n ? INF : deliver_at; }
       n_rsv += due_n ? 1u : 0u;
       pub = bc ? (0x80000000u | (63u << 16) | val) : pub;
       pub_b |= bal(bc);
@@ -634,7 +734,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         const u32 r1 = okm ? (u32)__builtin_ctz(okm) : 0u;
         const u64 cp_b = hm2(ok_lo != 0, ok_up != 0);   // the clusters that copy a set
         for (u32 w = i; cp_b & bal(w < words); w += 32)
-          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = DUO_SET(set_half + w * 128u + r1 * 4u);
+          if (lane_in(cp_b) && w < words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + r1 * 4u);
         n_payload += okm ? words : 0u;
       }
       // R4: the invocation and the completion row
@@ -642,13 +742,30 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         const u64 tns = (u64)T * 1000ull;
         const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
         const u32 fk = is_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
-        reinterpret_cast<uint4 *>(g_rows)[n_rows] = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (i << 12), is_rd ? MSIM_NO_VALUE : val);
-        reinterpret_cast<uint4 *>(g_rows)[n_rows + 1u] = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (i << 12), cmp_value);
+        DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (i << 12), is_rd ? MSIM_NO_VALUE : val);
+        DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (i << 12), cmp_value);
       }
       n_rows += opn ? 2u : 0u;
-      if (pub_b) DUO_ARRIVALS(pub);
-      if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w | (1u << (val & 31u));
-      DUO_POLL();
+      // FLOOD: the picked node's new set word and every other lane's (unchanged) one: what the store writes and what sw becomes
+      const u32 op_w1 = FLOOD ? (op_w | (bc ? 1u << (val & 31u) : 0u)) : 0u;
+      if (fl_round) {
+        if (pub_b) DUO_FLOOD_ARRIVALS(pub);
+        if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w1;
+        DUO_FLOOD_POLL();
+      } else {
+        if (pub_b) DUO_ARRIVALS(pub);
+        if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = FLOOD ? op_w1 : (op_w | (1u << (val & 31u)));
+        DUO_POLL();
+      }
+      // the acting clusters are quiescent but for this op: they are in flood mode from here on (a read: with nothing in flight).  The word
+      // of the op's value is every lane's set word for the flood to come (no node has handled anything in this round)
+      if (fl_ok) { sw = opn ? op_w1 : sw; fl_m |= op_m; }
+      // FLOOD: a cluster that has used up its block of the generator's draws draws the next one here (once per 32 ops), where the round's
+      // temporaries are dead; without flood mode its next op takes the GENERAL body, which draws it and leaves flood mode
+      if (FLOOD) {
+        const bool dc_refill = opn & (gen_k - dc_base >= 32u);
+        if (__ballot(dc_refill)) { const u64 dc_new = draw64(key, S_GEN, (u64)gen_k + i); dc = dc_refill ? dc_new : dc; dc_base = dc_refill ? gen_k : dc_base; }
+      }
       // the scheduler's view: an acting cluster acts again at its generator's next op (every worker is free again); the others are as
       // they were.  The full view runs when it would run in the GENERAL body (an op moved gen_next to or past cutoff)
       if (alive_m & (bal(phase != PH_MAIN) | bal(gen_next >= cutoff) | bal(rounds > round_limit))) {
@@ -660,10 +777,11 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         }
       } else sched_at = opn ? gen_next : sched_at;
 #ifdef DUO_PROF
-      pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++;
+      if (fl_round) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
 #endif
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
+    DUO_MATERIALISE();
     u32 inv_row = 0, inv_packed = 0, inv_value = 0;
     u32 cmp_row = 0, cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     // ---- R1: scheduler (core.clj:67-80): phase actions, one generated op ----
@@ -758,7 +876,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         const u32 r1 = okm ? (u32)__builtin_ctz(okm) : 0u;
         const u64 cp_b = hm2(ok_lo != 0, ok_up != 0);   // the clusters that copy a set
         for (u32 w = i; cp_b & bal(w < words); w += 32)
-          if (lane_in(cp_b) && w < words) g_pay[n_payload + w] = DUO_SET(set_half + w * 128u + r1 * 4u);
+          if (lane_in(cp_b) && w < words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + r1 * 4u);
         m = 0;
       }
       while (__ballot(m != 0)) {
@@ -767,7 +885,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         m &= m - 1u;
         const u32 r_off = bperm(hbase4 + (r << 2), my_off);
         for (u32 w = i; __ballot(on && w < words); w += 32)
-          if (on && w < words) g_pay[r_off + w] = DUO_SET(set_half + w * 128u + r * 4u);
+          if (on && w < words) DUO_PAY(r_off + w) = DUO_SET(set_half + w * 128u + r * 4u);
       }
       n_payload += __popc(okm) * words;
     }
@@ -788,8 +906,8 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       const u64 tns = (u64)T * 1000ull;
       const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
       if (RND || DUO_DIRECT) {   // the bags of the random-latency layout take the LDS a staging area would need: rows go straight to HBM
-        if (inv_row != 0 && !ovf) reinterpret_cast<uint4 *>(g_rows)[n_rows + __popc(imask & lt)] = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row != 0 && !ovf) reinterpret_cast<uint4 *>(g_rows)[n_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
+        if (inv_row != 0 && !ovf) DUO_ROW(n_rows + __popc(imask & lt)) = make_uint4(tlo, thi, inv_packed, inv_value);
+        if (cmp_row != 0 && !ovf) DUO_ROW(n_rows + ni + __popc(cmask & lt)) = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
       } else {
         if (inv_row != 0 && !ovf) stage[(n_rows + __popc(imask & lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi, inv_packed, inv_value);
         if (cmp_row != 0 && !ovf) stage[(n_rows + ni + __popc(cmask & lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
@@ -848,24 +966,27 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   const u32 t_arr = hi ? rdlane(sc_arr, 63) - lo_arr : lo_arr;
   const u32 t_rsv = hi ? rdlane(sc_rsv, 63) - lo_rsv : lo_rsv;
   for (u32 b = 1; b <= MSIM_FLAG_JOURNAL_OVERFLOW; b <<= 1) if (hb((my_flags & b) != 0, hi)) flags |= b;
+  const u32 inst_out = FLOOD ? inst_raw : inst;   // (real: the same; FLOOD: recomputed from the lane, nothing is kept across the rounds for it)
   if (real && i == 0) {
     // every client RPC is a request and a reply, each sent and received once (no loss, no timeouts in this layout)
     msim_net_stats st;
     st.clients_send = 2ull * t_cl; st.clients_recv = 2ull * t_cl;
     st.servers_send = t_arr; st.servers_recv = t_rsv;
     st.all_send = st.clients_send + st.servers_send; st.all_recv = st.clients_recv + st.servers_recv;
-    p.stats[inst] = st;
+    p.stats[inst_out] = st;
     msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
     m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
 #ifdef DUO_PROF
     // GENERAL bodies | op rounds << 16, wave-rounds, their cycles / 1024 (GENERAL | op << 16), all cycles / 64 (tools/duo_prof_report.py)
-    m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave; m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6);
+    // the wavefront's upper instance: flood gossip rounds, flood op rounds | materialisations << 16, cycles / 1024 (flood gossip rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | materialisations << 16)
+    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave; m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6); }
+    else { m.n_events = pf_nfg; m.reserved[0] = pf_nfop | (pf_nmat << 16); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16); m.reserved[2] = (u32)(pf_fop >> 10) | ((u32)(pf_mat >> 10) << 16); }
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }
     else { m.n_events = (u32)(p2[4] >> 6); m.reserved[0] = (u32)(p2[5] >> 6); m.reserved[1] = (u32)(p2[6] >> 6); m.reserved[2] = (u32)(p2[7] >> 6); }
 #endif
-    p.meta[inst] = m;
+    p.meta[inst_out] = m;
   }
 }
 

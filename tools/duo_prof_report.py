@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): runs the headline batch with the DUO_PROF build (tools/variant_lib.sh prof duo.hip -DDUO_PROF) and prints, per wavefront,
-the number of wave-rounds, how many of them were GENERAL rounds (op rounds and full GENERAL bodies), and the cycles spent in each kind."""
+the number of wave-rounds, how many of them were GENERAL rounds (op rounds and full GENERAL bodies), and the cycles spent in each kind; then the
+flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries."""
 import os
 import sys
 
@@ -22,16 +23,29 @@ with E.Engine(cfg) as eng:
     sim_ms = eng.kernel_ms()[0]
     eng.fetch()
     m = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2], eng.meta(i).n_rounds] for i in range(0, n, 2)], dtype=np.float64)
+    up = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2]] for i in range(1, n, 2)], dtype=np.int64)
 ev, nwave, cyc, ctot, rounds = m.T
 ev = ev.astype(np.int64); cyc = cyc.astype(np.int64)
-ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, op rounds
+ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, generic op rounds
 cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, (cyc >> 16).astype(np.float64) * 1024
 ctot *= 64
+# flood gossip rounds, flood op rounds, materialisations and their cycles (a build without flood mode leaves the generic numbers there: zero them)
+flood = os.environ.get("FLOOD", "1") != "0"
+nfg, nfop, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, up[:, 1] >> 16)]
+cfg_, cexit, cfop, cmat = [x.astype(np.float64) * 1024 * flood for x in (up[:, 2] & 0xFFFF, up[:, 2] >> 16, up[:, 3] & 0xFFFF, up[:, 3] >> 16)]
+nop_all = nop.mean() + nfop.mean()
 print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms")
-nsched = ngen.mean() + nop.mean()
+nsched = ngen.mean() + nop_all
 print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.mean():.0f}), GENERAL {nsched:.0f} ({100 * nsched / nwave.mean():.1f} %): "
-      f"op rounds {nop.mean():.0f} ({100 * nop.mean() / max(nsched, 1):.1f} % of them), full GENERAL bodies {ngen.mean():.0f}")
+      f"op rounds {nop_all:.0f} ({100 * nop_all / max(nsched, 1):.1f} % of them), full GENERAL bodies {ngen.mean():.0f}")
 print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL bodies {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %), "
-      f"in op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
-print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per op round {cop.mean() / max(nop.mean(), 1):.0f}, "
-      f"per gossip round {(ctot.mean() - cgen.mean() - cop.mean()) / (nwave.mean() - nsched):.0f}")
+      f"in generic op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
+ngos = nwave.mean() - nsched - nfg.mean()          # generic gossip rounds: the loop's rest
+cgos = ctot.mean() - cgen.mean() - cop.mean() - cfop.mean() - cfg_.mean() - cmat.mean() - cexit.mean()   # (without flood mode: with the leaving rounds' R0, as ever)
+print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per generic op round ({nop.mean():.0f}) {cop.mean() / max(nop.mean(), 1):.0f}, "
+      f"per generic gossip round ({ngos:.0f}) {cgos / max(ngos, 1):.0f}")
+nfl = nfg.mean() + nfop.mean()
+print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / nwave.mean():.1f} %): flood gossip rounds {nfg.mean():.0f} at {cfg_.mean() / max(nfg.mean(), 1):.0f} cycles "
+      f"({100 * cfg_.mean() / ctot.mean():.1f} % of the cycles), flood op rounds {nfop.mean():.0f} at {cfop.mean() / max(nfop.mean(), 1):.0f} ({100 * cfop.mean() / ctot.mean():.1f} %), "
+      f"materialisations {nmat.mean():.1f} at {cmat.mean() / max(nmat.mean(), 1):.0f}; R0 and exit test of the {nsched:.0f} rounds that leave the gossip loop "
+      f"{cexit.mean() / max(nsched, 1):.0f} each ({100 * cexit.mean() / ctot.mean():.1f} %)")
