@@ -39,7 +39,14 @@
 //   gossip / op round    the generic bodies (rings in LDS, set word re-read): some cluster is not in flood mode; they take one that is as it is
 //   GENERAL round        the full body; it first writes the queues of the clusters in flood mode out to their rings
 // (details at "FLOOD MODE" below; every round, delivery and message is still simulated: only the queue's representation differs).
+// In that instantiation an op round also takes a RUN OF READS at once: a read leaves a quiescent cluster quiescent, so its next round is
+// its generator's next op; while the op at hand is a read and the one behind it is again an op round's, the read is executed as a cluster
+// round of its own (its rows at its own time, its payload from its own node's set, the time jump, the round count) before the wave-round's
+// one gossip round and the op that ends the run.  The block of 32 generator draws of a cluster lives in LDS there, and what the rare paths
+// derive from the lane number alone (the spill pointer, the instance's key, constant row words) is computed where it is used: the
+// registers that frees are what the run needs at 80 VGPRs (see "READ RUNS" below; -DDUO_NO_PLAN compiles all of it out).
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <type_traits>
 
 #include "wave_common.h"
@@ -68,6 +75,13 @@ constexpr bool DUO_FLOOD_ON = false;
 #else
 constexpr bool DUO_FLOOD_ON = true;
 #endif
+// Read runs of the flood instantiation (see "READ RUNS" in the op round of sim_kernel_duo) and the latency-0 time jump without the
+// minimum over the nodes; -DDUO_NO_PLAN compiles both out for A/B runs.
+#ifdef DUO_NO_PLAN
+constexpr bool DUO_PLAN_ON = false;
+#else
+constexpr bool DUO_PLAN_ON = true;
+#endif
 #ifndef DUO_LDS_PAD
 #define DUO_LDS_PAD 0   // A/B builds (-DDUO_LDS_PAD=<bytes>): unused LDS per wavefront, fewer wavefronts per CU (msim_launch_duo)
 #endif
@@ -86,6 +100,7 @@ struct DuoParams {
   u32 round_limit;
   u32 off_seq;       // RND: byte offset of the arrival-sequence array (u16 per ring entry) inside a cluster's LDS region
   u32 off_log2;      // RND: byte offset of the Q24 log2 table (one per wavefront, behind both clusters)
+  u32 off_dc;        // flood instantiation: byte offset of the block of 32 generator draws inside a cluster's LDS region
 };
 
 // -ln(u), u = (r+1)/2^32, Q16, integer only: the sampler of engine.hip / the oracle over a copy of the table in LDS
@@ -157,6 +172,8 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   const u32 round_limit = dp.round_limit;
 
   constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;   // the instantiations with a flood mode (see below)
+  constexpr bool RUNS = DUO_PLAN_ON && FLOOD;                    // ... whose op rounds take a run of reads at once
+  constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
   // FLOOD: the cluster's rows and payload are addressed like its sets, from the wavefront's base (SGPRs: the lower cluster's) and the
@@ -164,12 +181,29 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   const bool up_half = hi && real;   // the cluster is the wavefront's second one
   msim_op *const w_rows = p.rows + (size_t)(blockIdx.x * 2u) * max_rows;
   u32 *const w_pay = p.payload + (size_t)(blockIdx.x * 2u) * max_pay;
-#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? w_rows + (size_t)((up_half ? max_rows : 0u) + (idx_)) : g_rows + (idx_))[0])
-#define DUO_PAY(idx_) ((FLOOD ? w_pay + (size_t)((up_half ? max_pay : 0u) + (idx_)) : g_pay + (idx_))[0])
+  // (RUNS: the half's share of the offset is computed at the access, from a lane number the optimizer cannot see through, so that it is not
+  //  kept in a register across the rounds; only live clusters write rows or payload, and an upper half that holds no cluster is never live)
+#define DUO_UP(x_) (RUNS ? ({ u32 du_l = threadIdx.x; MSIM_OPAQUE(du_l); du_l >= 32u ? (x_) : 0u; }) : (up_half ? (x_) : 0u))
+#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? w_rows + (size_t)(DUO_UP(max_rows) + (idx_)) : g_rows + (idx_))[0])
+#define DUO_PAY(idx_) ((FLOOD ? w_pay + (size_t)(DUO_UP(max_pay) + (idx_)) : g_pay + (idx_))[0])
   // HBM spill behind the LDS ring: {deadline, envelope} pairs in the node's slice of the spill area
   u64 *const my_spill = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)inst * p.scratch_words + p.spill_off) +
                                                     (size_t)(is_node ? i : 0) * p.spill_cap);
 
+  // RUNS: what the rare paths derive from the lane number alone is computed where it is used, from a lane number the optimizer cannot
+  // see through, so that no register holds it across the rounds.  These two are the ONLY second definitions of `lane` and `inst` (above):
+  // whoever changes how a lane finds its instance changes them here as well.
+#define DUO_LANE_NOW(l_) u32 l_ = threadIdx.x; MSIM_OPAQUE(l_)
+#define DUO_INST_OF(l_) (blockIdx.x * 2u + ((l_) >> 5) < dp.n_inst ? blockIdx.x * 2u + ((l_) >> 5) : dp.n_inst - 1u)
+  // The flood instantiation computes the pointer where the (rare) spill code uses it, from a lane number the optimizer cannot see through:
+  // no register pair holds it across the rounds
+#define DUO_MY_SPILL(ptr_)                                                                                                \
+    u64 *ptr_ = my_spill;                                                                                                 \
+    if (RUNS) {                                                                                                           \
+      DUO_LANE_NOW(ms_l); const u32 ms_i = ms_l & 31u;                                                                    \
+      ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)DUO_INST_OF(ms_l) * p.scratch_words + p.spill_off) + \
+                                     (size_t)(ms_i < N ? ms_i : 0) * p.spill_cap);                                          \
+    }
   // LDS of one cluster: [row staging][32 rings]
   unsigned char *const hmem = smem + (hi ? dp.half_bytes : 0u);
   uint4 *const stage = reinterpret_cast<uint4 *>(hmem);
@@ -245,7 +279,30 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   // The generator's draws (one 64-bit draw per generated op, stream S_GEN, counter gen_k) are computed 32 at a time: lane i of a cluster
   // holds draw dc_base + i, the scheduler fetches the one it needs with two ds_bpermute (mix64's three 64-bit multiplications cost a
   // round of the scheduler a quarter of its cycles when every lane computed the same draw)
+  // The flood instantiation keeps the block in LDS (256 bytes per cluster; a cluster's draw is one ds_read_b64 of an address all its
+  // lanes share) and so has two registers more for its op rounds.
   u32 dc_base = 0; u64 dc = draw64(key, S_GEN, (u64)i);
+  // (addressed from a lane number the optimizer cannot see through: no register holds an address of it across the rounds)
+#define DUO_DCL(idx_) (reinterpret_cast<u64 *>(smem + ({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); dl_l >= 32u ? dp.half_bytes : 0u; }) + dp.off_dc)[idx_])
+#define DUO_DCL_MINE() (reinterpret_cast<u64 *>(smem + ({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); (dl_l >= 32u ? dp.half_bytes : 0u) + (dl_l & 31u) * 8u; }) + dp.off_dc)[0])
+  if (RUNS) { DUO_DCL_MINE() = dc; dc = 0; wave_lds_fence(); }
+#define DUO_DRAW(k_, hi_, lo_) do {                                                                                       \
+    if (RUNS) { const u64 dd_v = DUO_DCL(((k_) - dc_base) & 31u); hi_ = (u32)(dd_v >> 32); lo_ = (u32)dd_v; }                 \
+    else { const u32 dd_at = hbase4 + (((k_) - dc_base) << 2); hi_ = bperm(dd_at, (u32)(dc >> 32)); lo_ = bperm(dd_at, (u32)dc); } \
+  } while (0)
+#define DUO_DRAW_REFILL(cond_) do {                                                                                       \
+    const bool dr_c = (cond_);                                                                                            \
+    if (__ballot(dr_c)) {                                                                                                 \
+      u64 dr_key = key;                                                                                                   \
+      if (RUNS) {   /* the instance's key again, from a lane number the optimizer cannot see through: once per 32 ops, no register between them */ \
+        DUO_LANE_NOW(dr_l);                                                                                               \
+        dr_key = mix64(p.cfg.seed + 0x9E3779B97F4A7C15ull * (p.first_instance + DUO_INST_OF(dr_l) + 1));                  \
+      }                                                                                                                   \
+      const u64 dr_new = draw64(dr_key, S_GEN, (u64)gen_k + i);                                                           \
+      if (RUNS) { if (dr_c) DUO_DCL_MINE() = dr_new; wave_lds_fence(); } else dc = dr_c ? dr_new : dc;                            \
+      dc_base = dr_c ? gen_k : dc_base;                                                                                   \
+    }                                                                                                                     \
+  } while (0)
   // RND: the same for the messages' latency draws (stream S_LATENCY, counter = message id, net.clj:178-187): a gossip round sends 1.3
   // messages on average, and every lane of the wavefront computed a draw (mix64, the logarithm) for them — a third of the round's vector
   // instructions.  Lane i of a cluster holds the latency (ms) of message id lc_base + i; DUO_RND_IDS keeps the block under the round's ids.
@@ -307,7 +364,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       }                                                                                                                   \
       if (pc_got & !pc_fit) {                                                                                             \
         if (sp_n >= S) my_flags |= MSIM_FLAG_INBOX_OVERFLOW;                                                              \
-        else { u32 pc_idx = s_head + sp_n; if (pc_idx >= S) pc_idx -= S; my_spill[pc_idx] = (u64)pc_dl | ((u64)pc_e << 32); sp_n++; } \
+        else { u32 pc_idx = s_head + sp_n; if (pc_idx >= S) pc_idx -= S; DUO_MY_SPILL(pc_sp) pc_sp[pc_idx] = (u64)pc_dl | ((u64)pc_e << 32); sp_n++; } \
       }                                                                                                                   \
     }                                                                                                                     \
   } while (0)
@@ -383,8 +440,9 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     }                                                                                                                     \
     if (!RND) {                                                                                                           \
       if (__ballot(sp_n != 0)) {   /* refill the ring from the spill: "ring empty" always means "queue empty" (rare) */    \
+        DUO_MY_SPILL(pl_sp)                                                                                               \
         while (sp_n != 0 && in_n < R) {                                                                                   \
-          const u64 pl_s = my_spill[s_head];                                                                              \
+          const u64 pl_s = pl_sp[s_head];                                                                                 \
           s_head++; if (s_head >= S) s_head = 0; sp_n--;                                                                  \
           DUO_RING_STORE((head + in_n) & Rm, (u32)(pl_s >> 32), (u32)pl_s);                                               \
           in_n++;                                                                                                         \
@@ -561,6 +619,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
 #ifdef DUO_PROF   // developer build (tools/variant_lib.sh prof duo.hip -DDUO_PROF): wave-round counts and cycles of the two round bodies -> meta
   u64 pf_t0 = __builtin_readcyclecounter(), pf_gen = 0, pf_op = 0; u32 pf_ngen = 0, pf_nop = 0, pf_nwave = 0;
   u64 pf_it = 0, pf_fg = 0, pf_fop = 0, pf_mat = 0; u32 pf_nfg = 0, pf_nfop = 0, pf_nmat = 0;   // flood gossip rounds, flood op rounds, materialisations
+  u32 pf_nrun = 0;   // reads of this lane's cluster that ran ahead of their wave-round's op (read runs)
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -631,7 +690,9 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0, 0)) {
           const u64 idle_b = alive_m & bal(sched_at > T) & hm2((u32)db == 0, (u32)(db >> 32) == 0);
           if (idle_b) {
-            const u32 km = min(half_min(deliver_at, hi), sched_at);
+            // latency 0: deliver_at is the T of the envelope's commit or INF, and T never falls, so a half with nothing due holds no
+            // envelope at all: the next event is the scheduler's
+            const u32 km = R0_SCHED ? sched_at : min(half_min(deliver_at, hi), sched_at);
             const u64 stuck_b = idle_b & bal(km == INF);   // nothing will ever happen (oracle: same flag, the round counts)
             const bool stuck = lane_in(stuck_b);
             flags |= stuck ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u;
@@ -696,13 +757,58 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       //      computes for such a cluster: every worker is free, so the pick is the node of that rank, and it is idle, so its recv! takes
       //      the request at once and the node completes it in this round (busy goes 1 -> 0 within the round) ----
       const bool opn = lane_in(op_m);
+      // READ RUNS.  An acting cluster is quiescent, and a read leaves it so: the picked node copies its set to the payload, two rows
+      // appear, and the cluster's next round is its generator's next op.  While the op at hand is a read AND the op after it will
+      // again be an op round's (its draw is in the cluster's block, it falls before the cutoff, its rows and this read's payload fit,
+      // the round limit is not reached: what the exit test and the scheduler's view would find), the read is executed here, as a
+      // cluster round of its own: rows at its own time, the payload from the set of its own node, then the time jump to the next op
+      // and the round count.  The op that ends the run (a broadcast, or the last read before one of the conditions fails) is the op
+      // of the round below, so a run of k reads and the broadcast behind it cost the wavefront one wave-round instead of k + 1; the
+      // other half gets its one gossip round from it either way.
+      // What the condition leans on: next_value < max_values was checked by st_m when this op round was chosen, and a read does not
+      // change next_value; the payload of the op that ENDS the run is checked by the round below (its overflow flag and all); DUO_DRAW
+      // masks its index with 31, so a lane of a half that does not act reads some draw of the block and never outside it; and the three
+      // places that look at the round limit agree: a read runs ahead only while rounds < round_limit, which is exactly when R0 of the
+      // cluster's next round would not force a GENERAL round (rounds >= round_limit) and the scheduler's view would not stop it (>).
+      if (RUNS) {
+        for (;;) {
+          const u32 rr_k = gen_k - dc_base;
+          u32 rr_hi, rr_lo; DUO_DRAW(gen_k, rr_hi, rr_lo);
+          const u32 rr_next = T + __umulhi(rr_hi, p.gen_period2_us);
+          const u32 rr_words = (next_value + 31u) >> 5;
+          const u64 rr_b = op_m & bal((rr_lo & 1u) != 0) & bal(rr_k < 31u) & bal(rr_next < cutoff) & bal(n_rows + 4u <= max_rows) &
+                           bal(n_payload + rr_words <= max_pay) & bal(rounds < round_limit);
+          if (!rr_b) break;
+          const bool rr_go = lane_in(rr_b);
+          const u32 rr_node = scale32(rr_lo, N);
+          const bool rr_sel = rr_go && i == rr_node;
+          n_cl += rr_sel ? 1u : 0u;
+          wave_lds_fence();
+          for (u32 w = i; rr_b & bal(w < rr_words); w += 32)
+            if (rr_go && w < rr_words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + rr_node * 4u);
+          if (rr_sel) {
+            u32 rr_i = i; MSIM_OPAQUE(rr_i);   // (the rows' constant words are built here, not kept in registers across the rounds)
+            const u64 tns = (u64)T * 1000ull;
+            const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
+            DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | ((u32)MSIM_F_READ << 2) | (rr_i << 12), MSIM_NO_VALUE);
+            DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (rr_words << 16), MSIM_T_OK | ((u32)MSIM_F_READ << 2) | (rr_i << 12), n_payload);
+          }
+          n_payload += rr_go ? rr_words : 0u;
+          n_rows += rr_go ? 2u : 0u;
+          gen_k += rr_go ? 1u : 0u;
+          T = rr_go ? rr_next : T;      // (the next round's R0: nothing is due, the scheduler acts at the generator's next op)
+          rounds += rr_go ? 1u : 0u;
+#ifdef DUO_PROF
+          pf_nrun += rr_go ? 1u : 0u;
+#endif
+        }
+      }
       // the word of the nodes' sets that the op's value falls in, fetched first: only the picked node's store at the end of the round
       // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
       u32 op_w = 0;
       if (opn) op_w = DUO_SET(set_lane + ((next_value & 0xFFE0u) << 2));
       const bool fl_round = FLOOD && (alive_m & ~fl_m) == 0;   // every live half is in flood mode: the flood op round
-      const u32 dc_at = hbase4 + ((gen_k - dc_base) << 2);   // (the op's draw is in the cluster's block of 32; the GENERAL body draws the next block)
-      const u32 r_hi = bperm(dc_at, (u32)(dc >> 32)), r_lo = bperm(dc_at, (u32)dc);
+      u32 r_hi, r_lo; DUO_DRAW(gen_k, r_hi, r_lo);   // (the op's draw is in the cluster's block of 32; the GENERAL body draws the next block)
       const bool sel = opn && i == scale32(r_lo, N);
       const bool is_rd = (r_lo & 1u) != 0;
       const bool bc = sel & !is_rd;
@@ -739,11 +845,12 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       }
       // R4: the invocation and the completion row
       if (sel) {
+        u32 r4_i = i; if (RUNS) MSIM_OPAQUE(r4_i);   // (RUNS: the rows' constant words are built here, not kept in registers across the rounds)
         const u64 tns = (u64)T * 1000ull;
         const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
         const u32 fk = is_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
-        DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (i << 12), is_rd ? MSIM_NO_VALUE : val);
-        DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (i << 12), cmp_value);
+        DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (r4_i << 12), is_rd ? MSIM_NO_VALUE : val);
+        DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (r4_i << 12), cmp_value);
       }
       n_rows += opn ? 2u : 0u;
       // FLOOD: the picked node's new set word and every other lane's (unchanged) one: what the store writes and what sw becomes
@@ -763,8 +870,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       // FLOOD: a cluster that has used up its block of the generator's draws draws the next one here (once per 32 ops), where the round's
       // temporaries are dead; without flood mode its next op takes the GENERAL body, which draws it and leaves flood mode
       if (FLOOD) {
-        const bool dc_refill = opn & (gen_k - dc_base >= 32u);
-        if (__ballot(dc_refill)) { const u64 dc_new = draw64(key, S_GEN, (u64)gen_k + i); dc = dc_refill ? dc_new : dc; dc_base = dc_refill ? gen_k : dc_base; }
+        DUO_DRAW_REFILL(opn & (gen_k - dc_base >= 32u));
       }
       // the scheduler's view: an acting cluster acts again at its generator's next op (every worker is free again); the others are as
       // they were.  The full view runs when it would run in the GENERAL body (an op moved gen_next to or past cutoff)
@@ -782,6 +888,9 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
     DUO_MATERIALISE();
+    // (RUNS: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
+    u32 gi = i; if (RUNS) MSIM_OPAQUE(gi);
+    const u32 g_lt = RUNS ? (1u << gi) - 1u : lt;
     u32 inv_row = 0, inv_packed = 0, inv_value = 0;
     u32 cmp_row = 0, cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     // ---- R1: scheduler (core.clj:67-80): phase actions, one generated op ----
@@ -797,14 +906,10 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       const u32 free_mask = all_nodes & ~hb(busy != 0, hi);
       const bool gen = act && phase == PH_MAIN && rate > 0 && gen_next < cutoff && gen_next <= T && free_mask != 0;
       // one 64-bit draw per generated op: high word -> stagger, low word -> worker pick / gen/mix
-      {
-        const bool dc_refill = gen_k - dc_base >= 32u;   // (uniform within a cluster)
-        if (__ballot(dc_refill)) { const u64 dc_new = draw64(key, S_GEN, (u64)gen_k + i); dc = dc_refill ? dc_new : dc; dc_base = dc_refill ? gen_k : dc_base; }
-      }
-      const u32 dc_at = hbase4 + ((gen_k - dc_base) << 2);
-      const u32 r_hi = bperm(dc_at, (u32)(dc >> 32)), r_lo = bperm(dc_at, (u32)dc);
+      DUO_DRAW_REFILL(gen_k - dc_base >= 32u);   // (uniform within a cluster)
+      u32 r_hi, r_lo; DUO_DRAW(gen_k, r_hi, r_lo);
       const u32 pick = scale32(r_lo, __popc(free_mask));
-      const bool sel = gen && is_node && busy == 0 && (u32)__popc(free_mask & lt) == pick;
+      const bool sel = gen && is_node && busy == 0 && (u32)__popc(free_mask & g_lt) == pick;
       const bool is_rd = (r_lo & 1u) != 0;
       const bool ovf = gen && !is_rd && next_value >= max_values;
       if (bal(next_value >= max_values)) { flags |= ovf ? (u32)MSIM_FLAG_VALUES_OVERFLOW : 0u; alive_m &= ~bal(ovf); }   // (rare: out of values)
@@ -822,7 +927,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       busy = inv ? 1u : busy;
       const bool is_op = inv && m_kind <= DK_READ_FINAL;
       inv_row = is_op ? 1u : 0u;
-      inv_packed = MSIM_T_INVOKE | ((m_kind == DK_BCAST ? MSIM_F_BROADCAST : MSIM_F_READ) << 2) | ((m_kind == DK_READ_FINAL ? 1u : 0u) << 11) | (i << 12);
+      inv_packed = MSIM_T_INVOKE | ((m_kind == DK_BCAST ? MSIM_F_BROADCAST : MSIM_F_READ) << 2) | ((m_kind == DK_READ_FINAL ? 1u : 0u) << 11) | (gi << 12);
       inv_value = m_kind == DK_BCAST ? m_val : MSIM_NO_VALUE;
       const u32 e = (m_kind == DK_BCAST ? m_val : 0u) | (63u << 16) | (m_kind << 24);
       if (RND) next_id += __popc(hb(inv, hi));   // the requests' ids, slot order (their latency is 0: no draw)
@@ -852,7 +957,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     n_cl += req ? 1u : 0u;
     busy = req ? 0u : busy;
     cmp_row = (req && kind == DK_BCAST) ? 1u : 0u;
-    cmp_packed = MSIM_T_OK | (MSIM_F_BROADCAST << 2) | (i << 12); cmp_value = v;
+    cmp_packed = MSIM_T_OK | (MSIM_F_BROADCAST << 2) | (gi << 12); cmp_value = v;
     // read -> read_ok with the whole set: the cluster's lanes copy the node's set (scratch) -> HBM payload
     // (the readers' and the copying clusters' masks come from ballots of single compares: a ballot of a bool built from several costs two
     //  vector instructions more)
@@ -861,13 +966,13 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       const bool rd = lane_in(rd_b);
       const u32 rdm = hi ? (u32)(rd_b >> 32) : (u32)rd_b;
       const u32 words = (next_value + 31u) >> 5;
-      const u32 my_rank = __popc(rdm & lt);
+      const u32 my_rank = __popc(rdm & g_lt);
       const bool ok = n_payload + (my_rank + 1u) * words <= max_pay;   // payload_alloc of the oracle, reader by reader
       const u32 my_off = ok ? n_payload + my_rank * words : 0u;
       const u64 ok_b = rd_b & bal(ok);
       if (rd) {
         if (!ok) my_flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-        cmp_row = 1; cmp_packed = MSIM_T_OK | (MSIM_F_READ << 2) | ((kind == DK_READ_FINAL ? 1u : 0u) << 11) | (i << 12);
+        cmp_row = 1; cmp_packed = MSIM_T_OK | (MSIM_F_READ << 2) | ((kind == DK_READ_FINAL ? 1u : 0u) << 11) | (gi << 12);
         cmp_value = my_off; cmp_len = words;
       }
       const u32 ok_lo = (u32)ok_b, ok_up = (u32)(ok_b >> 32), okm = hi ? ok_up : ok_lo;
@@ -906,11 +1011,11 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       const u64 tns = (u64)T * 1000ull;
       const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
       if (RND || DUO_DIRECT) {   // the bags of the random-latency layout take the LDS a staging area would need: rows go straight to HBM
-        if (inv_row != 0 && !ovf) DUO_ROW(n_rows + __popc(imask & lt)) = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row != 0 && !ovf) DUO_ROW(n_rows + ni + __popc(cmask & lt)) = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
+        if (inv_row != 0 && !ovf) DUO_ROW(n_rows + __popc(imask & g_lt)) = make_uint4(tlo, thi, inv_packed, inv_value);
+        if (cmp_row != 0 && !ovf) DUO_ROW(n_rows + ni + __popc(cmask & g_lt)) = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
       } else {
-        if (inv_row != 0 && !ovf) stage[(n_rows + __popc(imask & lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row != 0 && !ovf) stage[(n_rows + ni + __popc(cmask & lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
+        if (inv_row != 0 && !ovf) stage[(n_rows + __popc(imask & g_lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi, inv_packed, inv_value);
+        if (cmp_row != 0 && !ovf) stage[(n_rows + ni + __popc(cmask & g_lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
       }
       const u32 new_n = ovf ? n_rows : n_rows + nr;
       const bool flush = !RND && !DUO_DIRECT && (new_n >> 6) != (n_rows >> 6);   // a 64-row block completed (at most one per round: nr <= 64)
@@ -966,7 +1071,8 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   const u32 t_arr = hi ? rdlane(sc_arr, 63) - lo_arr : lo_arr;
   const u32 t_rsv = hi ? rdlane(sc_rsv, 63) - lo_rsv : lo_rsv;
   for (u32 b = 1; b <= MSIM_FLAG_JOURNAL_OVERFLOW; b <<= 1) if (hb((my_flags & b) != 0, hi)) flags |= b;
-  const u32 inst_out = FLOOD ? inst_raw : inst;   // (real: the same; FLOOD: recomputed from the lane, nothing is kept across the rounds for it)
+  u32 eo_l = lane; if (RUNS) MSIM_OPAQUE(eo_l);   // (RUNS: not even the lane-derived index is carried through the rounds)
+  const u32 inst_out = RUNS ? blockIdx.x * 2u + (eo_l >> 5) : FLOOD ? inst_raw : inst;   // (real: the same; FLOOD: recomputed from the lane, nothing is kept across the rounds for it)
   if (real && i == 0) {
     // every client RPC is a request and a reply, each sent and received once (no loss, no timeouts in this layout)
     msim_net_stats st;
@@ -978,9 +1084,10 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
 #ifdef DUO_PROF
     // GENERAL bodies | op rounds << 16, wave-rounds, their cycles / 1024 (GENERAL | op << 16), all cycles / 64 (tools/duo_prof_report.py)
+    // (wave-rounds and flood gossip rounds: the low 16 bits; above them the reads of the instance's own cluster that ran inside a read run)
     // the wavefront's upper instance: flood gossip rounds, flood op rounds | materialisations << 16, cycles / 1024 (flood gossip rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | materialisations << 16)
-    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave; m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6); }
-    else { m.n_events = pf_nfg; m.reserved[0] = pf_nfop | (pf_nmat << 16); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16); m.reserved[2] = (u32)(pf_fop >> 10) | ((u32)(pf_mat >> 10) << 16); }
+    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun << 16); m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6); }
+    else { m.n_events = pf_nfg | (pf_nrun << 16); m.reserved[0] = pf_nfop | (pf_nmat << 16); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16); m.reserved[2] = (u32)(pf_fop >> 10) | ((u32)(pf_mat >> 10) << 16); }
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }
@@ -1080,13 +1187,20 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   if (kp.scratch_words * 4 >= (1ull << 31)) return MSIM_LAYOUT_DOES_NOT_FIT;
   dp.sets_off = (u32)(kp.scratch_words - msim_duo_extra_scratch_words(c));
   dp.inst_bytes = (u32)(kp.scratch_words * 4);
+  const bool deg4 = duo_degree(c) <= 4 && kp.N <= 31;   // (lane 31 must hold no node: unused neighbour slots point at it)
+  // the flood instantiation keeps each cluster's block of 32 generator draws in LDS, behind its queues (256 bytes; lat 0 rings are at most
+  // 8 KiB per cluster, so this never decides the fit test above: which kernel runs a configuration stays as it was)
+  dp.off_dc = 0;
+  if (DUO_PLAN_ON && DUO_FLOOD_ON && lat0 && deg4) { dp.off_dc = (u32)off; off += 32 * 8; dp.half_bytes = (u32)off; }
   dp.off_log2 = (u32)(2 * off);
   dp.deg = duo_degree(c);
   dp.echoback = c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK;
   dp.round_limit = (kp.dev_flags & 0x100u) ? 2000000u : ROUND_LIMIT;
+  // developer / tests: MSIM_DUO_ROUND_LIMIT=<rounds> stops every cluster of this layout at that round (MSIM_FLAG_ROUND_LIMIT), so that the
+  // limit can be made to fall anywhere, e.g. inside a run of reads (read at every launch: a test sweeps it within one process)
+  if (const char *rl = std::getenv("MSIM_DUO_ROUND_LIMIT")) { const unsigned long v = std::strtoul(rl, nullptr, 0); if (v > 0 && v < ROUND_LIMIT) dp.round_limit = (u32)v; }
   size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
   lds = std::min(lds + (size_t)DUO_LDS_PAD, (size_t)160 * 1024);
-  const bool deg4 = dp.deg <= 4 && kp.N <= 31;   // (lane 31 must hold no node: unused neighbour slots point at it)
   const dim3 grid((n + 1) / 2);
   if (rnd) return deg4 ? duo_launch<false, true, true>(dp, grid, lds, st) : duo_launch<false, false, true>(dp, grid, lds, st);
   if (lat0) return deg4 ? duo_launch<true, true, false>(dp, grid, lds, st) : duo_launch<true, false, false>(dp, grid, lds, st);

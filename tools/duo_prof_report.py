@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): runs the headline batch with the DUO_PROF build (tools/variant_lib.sh prof duo.hip -DDUO_PROF) and prints, per wavefront,
 the number of wave-rounds, how many of them were GENERAL rounds (op rounds and full GENERAL bodies), and the cycles spent in each kind; then the
-flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries."""
+flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries; and the
+wave-rounds with an op, the ops they executed, and how many of those were reads that ran ahead of their wave-round's op (read runs)."""
 import os
 import sys
 
@@ -23,8 +24,15 @@ with E.Engine(cfg) as eng:
     sim_ms = eng.kernel_ms()[0]
     eng.fetch()
     m = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2], eng.meta(i).n_rounds] for i in range(0, n, 2)], dtype=np.float64)
+    # the counts that share a word with the read-run counter have 16 bits each: a wavefront runs at most the rounds of its two clusters together
+    assert 2 * max(eng.meta(i).n_rounds for i in range(n)) < 65536, "this shape runs too many rounds for the 16-bit fields of the DUO_PROF build"
     up = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2]] for i in range(1, n, 2)], dtype=np.int64)
 ev, nwave, cyc, ctot, rounds = m.T
+# the upper 16 bits of the wave-round count (lower instance) and of the flood gossip round count (upper instance): the reads of the
+# instance's own cluster that a read run executed
+nrun = (nwave.astype(np.int64) >> 16).astype(np.float64) + (up[:, 0] >> 16).astype(np.float64)
+nwave = (nwave.astype(np.int64) & 0xFFFF).astype(np.float64)
+up[:, 0] &= 0xFFFF
 ev = ev.astype(np.int64); cyc = cyc.astype(np.int64)
 ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, generic op rounds
 cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, (cyc >> 16).astype(np.float64) * 1024
@@ -49,3 +57,6 @@ print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / n
       f"({100 * cfg_.mean() / ctot.mean():.1f} % of the cycles), flood op rounds {nfop.mean():.0f} at {cfop.mean() / max(nfop.mean(), 1):.0f} ({100 * cfop.mean() / ctot.mean():.1f} %), "
       f"materialisations {nmat.mean():.1f} at {cmat.mean() / max(nmat.mean(), 1):.0f}; R0 and exit test of the {nsched:.0f} rounds that leave the gossip loop "
       f"{cexit.mean() / max(nsched, 1):.0f} each ({100 * cexit.mean() / ctot.mean():.1f} %)")
+nopw = ngen.mean() + nop_all   # wave-rounds with an op (a GENERAL body of the main phase carries one as well)
+print(f"wave-rounds with an op {nopw:.0f} per wavefront; reads executed ahead of such a round's op (read runs) {nrun.mean():.0f} per wavefront, "
+      f"{nrun.mean() / max(nopw, 1):.2f} per wave-round with an op")

@@ -78,6 +78,18 @@ def build(force=False, only=None):
     return OUT
 
 
+def build_variant(tag, unit, extra):
+    """libmaelsim_emu_<tag>.so: the emulator library with ONE unit recompiled with extra flags (the emulator's tools/variant_lib.sh)."""
+    build()
+    obj = os.path.join(OBJ, f"{unit}_{tag}.o")
+    out = os.path.join(OBJ, f"libmaelsim_emu_{tag}.so")
+    subprocess.run([CXX] + FLAGS + list(extra) + ["-x", "c++", "-c", "-o", obj, os.path.join(CSRC, unit)], check=True)
+    from maelstrom_amd.build import SOURCES
+    objs = [os.path.join(OBJ, s + ".o") for s in SOURCES if s != unit and os.path.exists(os.path.join(CSRC, s))] + [os.path.join(OBJ, "hipemu.cpp.o"), obj]
+    subprocess.run([CXX, "-shared", "-fPIC", "-o", out] + objs + ["-ldl", "-pthread"], check=True)
+    return out
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     build(force="--force" in sys.argv, only=set(args) or None)
