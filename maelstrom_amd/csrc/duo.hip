@@ -45,6 +45,9 @@
 // one gossip round and the op that ends the run.  The block of 32 generator draws of a cluster lives in LDS there, and what the rare paths
 // derive from the lane number alone (the spill pointer, the instance's key, constant row words) is computed where it is used: the
 // registers that frees are what the run needs at 80 VGPRs (see "READ RUNS" below; -DDUO_NO_PLAN compiles all of it out).
+// There, too, the two clusters PAIR their op rounds: a half that is ready for its op while its partner is in the middle of a flood waits
+// (it is parked: the wave-rounds are the partner's gossip rounds) until the partner is ready as well, so that one op wave-round serves
+// both (see "PAIRED OP ROUNDS" at the exit test of the gossip loop; -DDUO_NO_PAIR compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -82,6 +85,21 @@ constexpr bool DUO_PLAN_ON = false;
 #else
 constexpr bool DUO_PLAN_ON = true;
 #endif
+// Paired op rounds of the flood instantiation (see "PAIRED OP ROUNDS" at the exit test of the gossip loop in sim_kernel_duo): a half that
+// is ready for its op waits up to DUO_PAIR_WAIT wave-rounds for its partner's flood to end; -DDUO_NO_PAIR compiles it out for A/B runs.
+#ifdef DUO_NO_PAIR
+constexpr bool DUO_PAIR_ON = false;
+#else
+constexpr bool DUO_PAIR_ON = true;
+#endif
+#ifndef DUO_PAIR_WAIT
+// Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
+// difference of two floods' lengths); one that runs out was paid for nothing and leaves them out of step.  Measured, the longer the
+// better, on the headline grid (no wait there exceeds 10) and on a line of 24 nodes, whose floods take up to 25 rounds: 24 is the first
+// cap that does not cost that shape anything (profiles/r13_pair_wait_sweep.jsonl).  It bounds the wait where floods are longer still.
+#define DUO_PAIR_WAIT 24
+#endif
+static_assert(DUO_PAIR_WAIT >= 1 && DUO_PAIR_WAIT <= 1024, "the wait cap of a parked half");
 #ifndef DUO_LDS_PAD
 #define DUO_LDS_PAD 0   // A/B builds (-DDUO_LDS_PAD=<bytes>): unused LDS per wavefront, fewer wavefronts per CU (msim_launch_duo)
 #endif
@@ -173,6 +191,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
 
   constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;   // the instantiations with a flood mode (see below)
   constexpr bool RUNS = DUO_PLAN_ON && FLOOD;                    // ... whose op rounds take a run of reads at once
+  constexpr bool PAIR = DUO_PAIR_ON && RUNS;                     // ... and wait for each other, so that one op round serves both halves
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -331,6 +350,10 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   // GENERAL body first MATERIALISES every such half: its in_n entries are written to the ring and the flag is cleared.
   const bool fl_ok = FLOOD && R >= 8u;
   u64 fl_m = 0;
+  // PAIR: the half that is parked, i.e. ready for its op and waiting for its partner (a lane mask like fl_m; 0: nobody), and the
+  // wave-rounds it may still wait (counted down in every wave-round; far from 0 while nobody is parked)
+  constexpr u32 PARK_IDLE = 0x7FFFFFFFu;
+  u64 park_m = 0; u32 park_left = PARK_IDLE;
   // The helpers below are macros on purpose: as lambdas capturing the state by reference they left the closures (and with
   // them every captured variable) in scratch memory once the optimizer turned a select of two captured values into a select
   // of their addresses.
@@ -620,6 +643,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   u64 pf_t0 = __builtin_readcyclecounter(), pf_gen = 0, pf_op = 0; u32 pf_ngen = 0, pf_nop = 0, pf_nwave = 0;
   u64 pf_it = 0, pf_fg = 0, pf_fop = 0, pf_mat = 0; u32 pf_nfg = 0, pf_nfop = 0, pf_nmat = 0;   // flood gossip rounds, flood op rounds, materialisations
   u32 pf_nrun = 0;   // reads of this lane's cluster that ran ahead of their wave-round's op (read runs)
+  u64 pf_pk = 0; u32 pf_npark = 0, pf_npk = 0, pf_wmax = 0, pf_nop2 = 0;   // parked gossip rounds and their cycles, the parks, the longest wait, op wave-rounds that carried two ops
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -678,7 +702,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     // ---- gossip rounds of both clusters, until one of them needs a GENERAL round ----
     for (;;) {
 #ifdef DUO_PROF
-      pf_nwave++; pf_it = __builtin_readcyclecounter();
+      pf_nwave++; pf_it = __builtin_readcyclecounter(); bool pf_parked = park_m != 0;
 #endif
       // R0: the cluster's time: stay at T while something is due, else jump to the next delivery / scheduler event.
       // Only looked at when one of the two clusters has nothing due (a scalar test on the halves of one ballot).
@@ -686,8 +710,15 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       u64 due_b = bal(deliver_at <= T);   // (a mask, not a bool: a bool two paths define is turned into 0 / 1 and compared again)
       bool stuck_any = false;
       {
-        const u64 db = due_b;
-        if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0, 0)) {
+        // PAIR: a parked half is quiescent with T at its sched_at: there is nothing for it in this block, so it counts as a half with
+        // something due, and a parked round comes by here only when the partner has nothing due any more (its flood has ended) or the
+        // wait has run out.  That is all a parked round adds to a gossip round: one scalar OR, the count-down and its test.  The parked
+        // half is not in want_m meanwhile (see the exit test), so the round takes the gossip body; the block puts it back (T stands at
+        // its sched_at), and the exit test releases it.
+        const u64 db = PAIR ? due_b | park_m : due_b;
+        if (PAIR) park_left--;
+        if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0 || (PAIR && park_left == 0), 0)) {
+          {
           const u64 idle_b = alive_m & bal(sched_at > T) & hm2((u32)db == 0, (u32)(db >> 32) == 0);
           if (idle_b) {
             // latency 0: deliver_at is the T of the envelope's commit or INF, and T never falls, so a half with nothing due holds no
@@ -704,14 +735,20 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
             due_b = bal(deliver_at <= T);
           }
           // the round limit is looked at here and in GENERAL rounds (a stretch of pure gossip always ends in one of the two)
-          fg_m |= alive_m & bal(rounds >= round_limit);
+          // (PAIR: not for a parked half: its round is counted, its op round decided; the limit is looked at again behind its op)
+          fg_m |= alive_m & bal(rounds >= round_limit) & (PAIR ? ~park_m : ~0ull);
           want_m = alive_m & (fg_m | bal(sched_at <= T));
+          }
         }
       }
       rounds += alive_v;
       const bool due_n = lane_in(due_b);
       // GENERAL if alive & (force_general | sched_at <= T | special), special = due_n & (cm >> 24) != DK_PLAIN
       if (const u64 gw_m = want_m | (alive_m & due_b & bal(cm > 0xFFFFFFu)); gw_m != 0 || stuck_any) {   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
+        // PAIR: a parked half (below) is released here, whatever this round turns out to be; its round is not counted again
+        bool released = false;
+        if (PAIR && park_m != 0) { alive_v = lane_in(park_m) ? 1u : alive_v; park_m = 0; park_left = PARK_IDLE; released = true; }
+        bool parks = false;
         if (LAT0 && !RND && rate > 0 && !stuck_any) {
           // The steady state of latency 0: the scheduler acts right after its time jump, so the acting cluster is quiescent — no envelope
           // due (at latency 0 a node that holds one has it due), hence every node idle with an empty queue and every client free.  Its
@@ -721,8 +758,29 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
           const u64 st_m = ~fg_m & bal(phase == PH_MAIN) & bal(next_value < max_values) & bal(n_rows + 2u <= max_rows) & bal(gen_k - dc_base < 32u) &
                            hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
           op_m = (gw_m & ~st_m) == 0 ? gw_m : 0ull; op_due = due_b;
+          // PAIRED OP ROUNDS.  The two clusters are independent, so the order in which they take their rounds is free, and an op wave-round
+          // costs the wavefront the same whether it carries the op of one half or of both.  So when exactly one half wants a round, an op
+          // round's, and its partner is alive (gw_m is a whole half, so nothing special is due anywhere; the partner does not want a
+          // round, so at latency 0 it has envelopes due: it is in the middle of a flood), the ready half is PARKED: it leaves want_m, this
+          // wave-round and the next ones take the gossip body, and R0's block (above) ends the wait when nothing is due at the partner
+          // any more (its flood has ended: the block moves it to its own next op, or stops it, and this test chooses op_m from both halves
+          // as ever) or after DUO_PAIR_WAIT wave-rounds (then the op goes alone).  A special envelope at the partner ends it here.
+          // The invariant of a parked half: its round was counted by this iteration's R0 and alive_v is 0 for it until it is released
+          // (above: after the releasing iteration's count), so rounds stays; T stands at its sched_at, and R0 leaves it there (sched_at
+          // > T fails) and does not look at the round limit for it; it is quiescent (nothing held, nothing queued, no client busy),
+          // so the flood and the generic gossip bodies do nothing for it: due is false in its lanes, it publishes nothing, pulls
+          // nothing, the poll finds in_n == 0, and n_rsv, n_arr stay.  Nothing st_m looks at changes while it waits, so the releasing
+          // test finds it eligible again.  Waiting is bounded twice: by the cap, and at latency 0 by the partner's flood, which handles
+          // something in every round until it ends, within the topology's eccentricity + 2 rounds of its op.
+          if (PAIR && !released && op_m != 0 && alive_m == ~0ull && (gw_m == 0xFFFFFFFFull || gw_m == 0xFFFFFFFF00000000ull)) {
+            park_m = gw_m; park_left = (u32)DUO_PAIR_WAIT; want_m &= ~gw_m; op_m = 0; parks = true;
+            alive_v = lane_in(gw_m) ? 0u : alive_v;
+#ifdef DUO_PROF
+            pf_npark++; pf_parked = true; { const u64 pf_p0 = __builtin_readcyclecounter(); pf_exit += pf_p0 - pf_it; pf_it = pf_p0; }   // (R0 and the exit test of the parking round: with the leaving rounds')
+#endif
+          }
         }
-        break;
+        if (!parks) break;
       }
       if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
         u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
@@ -730,7 +788,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         if (pub_b) DUO_FLOOD_ARRIVALS(pub);
         DUO_FLOOD_POLL();
 #ifdef DUO_PROF
-        pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg++;
+        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk++; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); } else { pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg++; }
 #endif
       } else {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
@@ -745,6 +803,9 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         }
         P2_MARK(3)
         DUO_POLL();
+#ifdef DUO_PROF
+        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk++; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); }   // (the generic gossip rounds are the loop's rest: the report takes these out)
+#endif
       }
     }
     if (!alive_m) break;
@@ -884,6 +945,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       } else sched_at = opn ? gen_next : sched_at;
 #ifdef DUO_PROF
       if (fl_round) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
+      pf_nop2 += op_m == ~0ull ? 1u : 0u;
 #endif
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
@@ -1056,6 +1118,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   }
 #ifdef DUO_PROF
   const u64 pf_tot = __builtin_readcyclecounter() - pf_t0;
+  const u32 pf_nrun_all = rdlane(pf_nrun, 0) + rdlane(pf_nrun, 32);
 #endif
 
   // ---- epilogue: the partial row block, net stats, meta ----
@@ -1083,11 +1146,16 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
     m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
 #ifdef DUO_PROF
-    // GENERAL bodies | op rounds << 16, wave-rounds, their cycles / 1024 (GENERAL | op << 16), all cycles / 64 (tools/duo_prof_report.py)
-    // (wave-rounds and flood gossip rounds: the low 16 bits; above them the reads of the instance's own cluster that ran inside a read run)
-    // the wavefront's upper instance: flood gossip rounds, flood op rounds | materialisations << 16, cycles / 1024 (flood gossip rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | materialisations << 16)
-    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun << 16); m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16); m.reserved[2] = (u32)(pf_tot >> 6); }
-    else { m.n_events = pf_nfg | (pf_nrun << 16); m.reserved[0] = pf_nfop | (pf_nmat << 16); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16); m.reserved[2] = (u32)(pf_fop >> 10) | ((u32)(pf_mat >> 10) << 16); }
+    // GENERAL bodies | op rounds << 16, wave-rounds | the reads of both clusters that ran inside a read run << 16, their cycles / 1024
+    // (GENERAL | op << 16), all cycles / 4096 | parks << 16 (11 bits) | the longest wait of a parked half << 27 (5 bits, saturating) (tools/duo_prof_report.py)
+    // the wavefront's upper instance: flood gossip rounds | parked gossip rounds << 16, flood op rounds | op wave-rounds with two ops << 16
+    // (12 bits) | materialisations << 28 (4 bits, saturating; their cycles are part of the GENERAL bodies'), cycles / 1024 (flood gossip
+    // rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | parked gossip rounds << 16)
+    (void)pf_mat;
+    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16);
+               m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27); }
+    else { m.n_events = pf_nfg | (pf_npk << 16); m.reserved[0] = pf_nfop | (min(pf_nop2, 4095u) << 16) | (min(pf_nmat, 15u) << 28); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16);
+           m.reserved[2] = ((u32)(pf_fop >> 10) & 0xFFFFu) | ((u32)(pf_pk >> 10) << 16); }
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }

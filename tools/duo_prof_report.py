@@ -2,7 +2,9 @@
 """Developer tool (GPU box): runs the headline batch with the DUO_PROF build (tools/variant_lib.sh prof duo.hip -DDUO_PROF) and prints, per wavefront,
 the number of wave-rounds, how many of them were GENERAL rounds (op rounds and full GENERAL bodies), and the cycles spent in each kind; then the
 flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries; and the
-wave-rounds with an op, the ops they executed, and how many of those were reads that ran ahead of their wave-round's op (read runs)."""
+wave-rounds with an op, the ops they executed, and how many of those were reads that ran ahead of their wave-round's op (read runs); and
+the paired op rounds: parks, parked gossip rounds per park and their cycles, the longest wait, op wave-rounds that carried one op or two.
+TOPOLOGY / NODES choose another shape (e.g. TOPOLOGY=line NODES=24, the long floods the wait cap is for)."""
 import os
 import sys
 
@@ -13,9 +15,11 @@ os.environ.setdefault("MSIM_LIB", os.path.join(ROOT, "maelstrom_amd", "libmaelsi
 sys.path.insert(0, ROOT)
 from maelstrom_amd import engine as E  # noqa: E402
 
-kw = dict(workload="broadcast", bin="broadcast-ff", node_count=25, rate=100, time_limit=20, latency=int(os.environ.get("LAT", "0")), latency_dist=os.environ.get("DIST", "constant"), seed=2026)
+kw = dict(workload="broadcast", bin="broadcast-ff", node_count=int(os.environ.get("NODES", "25")), rate=100, time_limit=20, latency=int(os.environ.get("LAT", "0")), latency_dist=os.environ.get("DIST", "constant"), seed=2026)
 if kw["latency"] == 0:
     kw["inbox_capacity"] = 6
+if os.environ.get("TOPOLOGY"):
+    kw["topology"] = os.environ["TOPOLOGY"]
 n = int(os.environ.get("N", "4096"))
 cfg = E.test_config(**kw)
 with E.Engine(cfg) as eng:
@@ -28,19 +32,24 @@ with E.Engine(cfg) as eng:
     assert 2 * max(eng.meta(i).n_rounds for i in range(n)) < 65536, "this shape runs too many rounds for the 16-bit fields of the DUO_PROF build"
     up = np.array([[eng.meta(i).n_events, eng.meta(i).reserved[0], eng.meta(i).reserved[1], eng.meta(i).reserved[2]] for i in range(1, n, 2)], dtype=np.int64)
 ev, nwave, cyc, ctot, rounds = m.T
-# the upper 16 bits of the wave-round count (lower instance) and of the flood gossip round count (upper instance): the reads of the
-# instance's own cluster that a read run executed
-nrun = (nwave.astype(np.int64) >> 16).astype(np.float64) + (up[:, 0] >> 16).astype(np.float64)
+# the upper 16 bits of the wave-round count (lower instance): the reads of both clusters that a read run executed; of the flood gossip
+# round count (upper instance): the parked gossip rounds; beside all cycles / 4096: the parks (11 bits) and the longest wait (5 bits)
+nrun = (nwave.astype(np.int64) >> 16).astype(np.float64)
 nwave = (nwave.astype(np.int64) & 0xFFFF).astype(np.float64)
+npk = (up[:, 0] >> 16).astype(np.float64)
 up[:, 0] &= 0xFFFF
+npark, wmax = ((ctot.astype(np.int64) >> 16) & 0x7FF).astype(np.float64), int((ctot.astype(np.int64) >> 27).max())
+assert npark.max() < 2047, "this shape parks too often for the 11-bit field of the DUO_PROF build"
+ctot = (ctot.astype(np.int64) & 0xFFFF).astype(np.float64)
 ev = ev.astype(np.int64); cyc = cyc.astype(np.int64)
 ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, generic op rounds
 cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, (cyc >> 16).astype(np.float64) * 1024
-ctot *= 64
+ctot *= 4096
 # flood gossip rounds, flood op rounds, materialisations and their cycles (a build without flood mode leaves the generic numbers there: zero them)
 flood = os.environ.get("FLOOD", "1") != "0"
-nfg, nfop, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, up[:, 1] >> 16)]
-cfg_, cexit, cfop, cmat = [x.astype(np.float64) * 1024 * flood for x in (up[:, 2] & 0xFFFF, up[:, 2] >> 16, up[:, 3] & 0xFFFF, up[:, 3] >> 16)]
+nfg, nfop, nop2, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, (up[:, 1] >> 16) & 0xFFF, (up[:, 1] >> 28) & 0xF)]
+cfg_, cexit, cfop, cpk = [x.astype(np.float64) * 1024 * flood for x in (up[:, 2] & 0xFFFF, up[:, 2] >> 16, up[:, 3] & 0xFFFF, up[:, 3] >> 16)]
+cpk += 512 * (npk > 0)   # (the fields are truncated to 1024 cycles; it matters for this small one alone)
 nop_all = nop.mean() + nfop.mean()
 print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms")
 nsched = ngen.mean() + nop_all
@@ -48,15 +57,19 @@ print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.me
       f"op rounds {nop_all:.0f} ({100 * nop_all / max(nsched, 1):.1f} % of them), full GENERAL bodies {ngen.mean():.0f}")
 print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL bodies {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %), "
       f"in generic op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
-ngos = nwave.mean() - nsched - nfg.mean()          # generic gossip rounds: the loop's rest
-cgos = ctot.mean() - cgen.mean() - cop.mean() - cfop.mean() - cfg_.mean() - cmat.mean() - cexit.mean()   # (without flood mode: with the leaving rounds' R0, as ever)
+ngos = nwave.mean() - nsched - nfg.mean() - npk.mean()          # generic gossip rounds: the loop's rest (a parked round in a generic body is counted as parked)
+cgos = ctot.mean() - cgen.mean() - cop.mean() - cfop.mean() - cfg_.mean() - cpk.mean() - cexit.mean()   # (without flood mode: with the leaving rounds' R0, as ever; materialisations are part of the GENERAL bodies)
 print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per generic op round ({nop.mean():.0f}) {cop.mean() / max(nop.mean(), 1):.0f}, "
       f"per generic gossip round ({ngos:.0f}) {cgos / max(ngos, 1):.0f}")
 nfl = nfg.mean() + nfop.mean()
 print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / nwave.mean():.1f} %): flood gossip rounds {nfg.mean():.0f} at {cfg_.mean() / max(nfg.mean(), 1):.0f} cycles "
       f"({100 * cfg_.mean() / ctot.mean():.1f} % of the cycles), flood op rounds {nfop.mean():.0f} at {cfop.mean() / max(nfop.mean(), 1):.0f} ({100 * cfop.mean() / ctot.mean():.1f} %), "
-      f"materialisations {nmat.mean():.1f} at {cmat.mean() / max(nmat.mean(), 1):.0f}; R0 and exit test of the {nsched:.0f} rounds that leave the gossip loop "
-      f"{cexit.mean() / max(nsched, 1):.0f} each ({100 * cexit.mean() / ctot.mean():.1f} %)")
+      f"materialisations {nmat.mean():.1f} (counted to 15); R0 and exit test of the {nsched + npark.mean():.0f} rounds that leave the gossip loop or park a half "
+      f"{cexit.mean() / max(nsched + npark.mean(), 1):.0f} each ({100 * cexit.mean() / ctot.mean():.1f} %)")
 nopw = ngen.mean() + nop_all   # wave-rounds with an op (a GENERAL body of the main phase carries one as well)
 print(f"wave-rounds with an op {nopw:.0f} per wavefront; reads executed ahead of such a round's op (read runs) {nrun.mean():.0f} per wavefront, "
       f"{nrun.mean() / max(nopw, 1):.2f} per wave-round with an op")
+nop1 = nop_all - nop2.mean()
+wmax_s = f"{wmax} or more" if wmax == 31 else str(wmax)   # (the field saturates)
+print(f"paired op rounds: parks {npark.mean():.0f} per wavefront, parked gossip rounds {npk.mean():.0f} ({npk.mean() / max(npark.mean(), 1):.2f} per park, longest wait {wmax_s}) at "
+      f"{cpk.mean() / max(npk.mean(), 1):.0f} cycles ({100 * cpk.mean() / ctot.mean():.1f} % of the cycles); op wave-rounds with one op {nop1:.0f}, with two {nop2.mean():.0f}")
