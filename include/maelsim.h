@@ -296,8 +296,17 @@ int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances,
  * set-full (broadcast, g-set), echo, lin-kv's per-key linearizability (one wavefront per history; a history that
  * exceeds what a wavefront's registers hold is finished by the host search) and the clean case of list-append (elle: no
  * anomaly + acyclic dependency graph; a history that is not provably clean is analysed by the host) — see
- * msim_check_host_rechecks.  On the host cores, after a fetch: rw-register (elle), pn-counter, unique-ids.  Blocking.  Results via msim_check_results. */
+ * msim_check_host_rechecks.  txn-rw-register (elle's rw-register analysis): a first device pass proves a history free of everything the
+ * consistency model proscribes; a history it cannot prove valid is analysed in full by a second device pass (every edge kind, the
+ * non-cycle anomalies, the cycle class: G0 / G1c / G-single / G2, -realtime), whose record is the one msim_check_rw_rows gives; only
+ * shapes beyond the device capacities, duplicate writes and cyclic components of more than 256 transactions go to the host.  Blocking.
+ * Results via msim_check_results. */
 int msim_check(msim_ctx *ctx);
+
+/* txn-rw-register only (else MSIM_E_UNSUPPORTED): on != 0 makes the next msim_check give, for EVERY history, the full record of
+ * msim_check_rw_rows — the histories the consistency model accepts name their allowed cycle classes and carry the full graph's edge and
+ * cycle counts (an anomaly census of an ensemble).  Off (the default), a history the first pass proves valid keeps that pass's record. */
+int msim_set_check_classify(msim_ctx *ctx, uint32_t on);
 
 /* Developer switches of a context (A/B comparisons, tracing; never needed for normal use) — the same bits the environment variable
  * MSIM_DEV_FLAGS carries, which is ORed in: 0x100 round limit x 20, 0x200 run the one-cluster-per-wavefront kernels, 0x400 fail
@@ -305,7 +314,8 @@ int msim_check(msim_ctx *ctx);
 int msim_set_dev_flags(msim_ctx *ctx, uint32_t flags);
 
 /* How many histories of the last msim_check the device handed to the host (lin-kv: the search needed more than 512
- * configurations; txn-list-append: not provably clean, i.e. the host analysed and classified it; else 0). */
+ * configurations; txn-list-append: not provably clean, i.e. the host analysed and classified it; txn-rw-register: beyond the device
+ * capacities, see msim_check_rw_batch; else 0). */
 uint32_t msim_check_host_rechecks(const msim_ctx *ctx);
 
 /* txn-list-append: checks `n_histories` histories given on the host — rows / payload words of history i at row_offsets[i] /
@@ -316,11 +326,19 @@ int msim_check_txn_batch(int device, const msim_op *rows, const uint64_t *row_of
                          uint32_t n_histories, msim_check_result *out);
 
 /* txn-rw-register: the same for the rw-register analysis under `consistency_model` (MSIM_CM_*): the device proves a history free of
- * everything the model proscribes (csrc/rw_check_dev.hip), the host analysis of msim_check_rw_rows finishes the others; *n_host (may be
- * null) = how many went to the host.  For a history the device proves valid, out[i] carries :valid?, the counts, the non-cycle anomalies
- * seen (none proscribed) in error_count and the edges built in lost_count; the allowed cycle classes are not searched for. */
+ * everything the model proscribes (csrc/rw_check_dev.hip, rw_check_kernel); the others are analysed and their cycles classified by
+ * rw_classify_kernel, byte for byte the record of msim_check_rw_rows; the host analysis finishes only what exceeds the device
+ * capacities (values >= 64, the key / writer / transaction / edge tables, 64 open calls), histories with duplicate writes, and cyclic
+ * components of more than 256 transactions; *n_host (may be null) = how many those were.  For a history the first pass proves valid,
+ * out[i] carries :valid?, the counts, the non-cycle anomalies seen (none proscribed) in error_count and the edges that pass built in
+ * lost_count; its allowed cycle classes are not searched for (msim_classify_rw_batch does). */
 int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                         uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host);
+
+/* txn-rw-register: the full analysis of every history on the device: out[i] is byte for byte what msim_check_rw_rows writes for history
+ * i under `consistency_model`, the histories the model accepts included (their allowed cycle classes named); *n_host as above. */
+int msim_classify_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                           uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host);
 
 /* pn-counter / g-counter: the same for the counter checker (workload/pn_counter.clj:84-123); out[i] is what msim_check_pn_rows gives. */
 int msim_check_pn_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out);

@@ -11,10 +11,13 @@
 //   * the cycle anomalies by Kahn's algorithm over the edge kinds whose cycles the model proscribes: read-uncommitted ww (G0),
 //     read-committed ww + wr (G0, G1c); the stronger models every kind (ww, wr, rw, and the realtime order for strict-serializable) —
 //     there an acyclic graph is the only thing this pass can prove, anything else goes to the host.
-// A history it cannot prove valid — a proscribed anomaly, a cycle in the subgraph, a shape beyond the capacities below — is handed to
-// check_rw, whose verdict and anomaly set are then the result.  For a history it does prove valid the result carries :valid? and the
-// counts of the host's analysis, the non-cycle anomalies it saw (none of them proscribed) and the edges it built; the ALLOWED cycle classes
-// are not searched for (msim_check_rw_rows gives the full classification of one history).
+// A history it cannot prove valid — a proscribed anomaly, a cycle in the subgraph — goes to rw_classify_kernel, which builds every
+// edge kind, accumulates the non-cycle anomalies and classifies the cycles (G0 / G1c / G-single / G2, -realtime): the record of check_rw
+// byte for byte.  Only a shape beyond the capacities below, duplicate writes (check_rw's writer table is last-writer-wins in row order)
+// and a strongly connected component beyond CCAP transactions are handed to check_rw on the host.  For a history the first pass does prove
+// valid the result carries :valid? and the counts of the host's analysis, the non-cycle anomalies it saw (none of them proscribed) and the
+// edges it built; its ALLOWED cycle classes are not searched for unless the caller asks for every history's full record
+// (msim_classify_rw_batch, msim_set_check_classify).
 //
 // Steps (lane = transaction unless said otherwise), tables in an HBM workspace as in txn_check_kernel:
 //   A  rows -> transactions, completions paired by process (the walk of txn_check_kernel);
@@ -22,7 +25,7 @@
 //   D  per :ok transaction: internal consistency, G1a / G1b, wr edges, "writes follow reads" version edges (64-bit sets by atomics);
 //   E  per key (lane = key): nil precedes every version; a cyclic version order is found by peeling the versions without predecessor;
 //      ww edges along the version order; rw edges from the external reads (stronger models only);
-//   F  Kahn's algorithm over the edges built.
+//   F  Kahn's algorithm over the edges built;  G (rw_classify_kernel only)  the cycle classes: rw_classify below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,7 +55,11 @@ struct RParams {
   uint64_t ws_words;
   u32 max_rows, max_pay, nmax, emax, first, cm, proscribed;
   u32 kmax, wmax;                // keys / writer-table entries the workspace of a history holds (<= KMAX / WMAX: what the configuration can name)
+  const u32 *list;               // rw_classify_kernel: the histories of this launch (block b takes list[first + b])
+  u32 ccap;                      // rw_classify_kernel: transactions of one strongly connected component the reachability matrix holds (<= CCAP)
 };
+constexpr u32 CCAP = 256u;       // 256 x 256 bits of LDS: 8 KB per history
+constexpr u32 E_WW = 1u, E_WR = 2u, E_RW = 4u, E_RT = 8u, E_TO = 0x0FFFFFFFu;   // the full graph's edges: to | kind << 28
 
 __device__ __forceinline__ u32 r_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ u32 r_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
@@ -68,8 +75,195 @@ __device__ __forceinline__ u32 r_excl_scan(u32 v, u32 lane) {
 #define M_KEY(w_) (((w_) >> 1) & 0x7FFFu)
 #define M_VAL(w_) (((w_) >> 16) & 0xFFu)
 
-__global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
-  const u32 lane = threadIdx.x, hist = p.first + blockIdx.x;
+// ---- the classification of one history's cycles (lane = transaction unless said otherwise) ---------------------------------------------
+// What finish() and classify() of txn_check.cpp do with Tarjan's algorithm, restated for one wavefront over the tagged edges (off / adj)
+// and their reverse (roff / radj):
+//   * "is there a cycle over these edge kinds" is Kahn's algorithm over the masked edges (peel);
+//   * the transactions in strongly connected components of more than one transaction: peel forwards and backwards until every
+//     transaction left has a predecessor and a successor left; any chain of predecessors then ends in a cycle, so pointer doubling over
+//     one predecessor each finds a transaction ON a cycle; its component is what a search along the edges and one against them both
+//     reach; count it, take it out, peel again.  Every search is a queue, O(edges): the realtime edges form chains as long as the
+//     history, which a sweep to a fixpoint would walk once per link;
+//   * G-single: in a component, some rw edge u -> v whose v reaches u over ww + wr (+ realtime).  Such a path lies inside the component,
+//     so reachability is closed (Warshall, rows of bits in LDS) over the component's transactions alone — ccap of them at the most, a
+//     larger component is the host's.
+__device__ __forceinline__ void rw_classify(const RParams &p, const u32 hist, msim_check_result &res, const u32 anomalies, const u32 n, const u32 n_edges,
+                                            const u32 flags, const u32 c_ok, u32 *const deg, const u32 *const off, const u32 *const adj,
+                                            const u32 *const roff, const u32 *const radj, u32 *const st, u32 *const jump, u32 *const queue) {
+  __shared__ u64 mat[CCAP * CCAP / 64];
+  constexpr u32 GONE = 1u, FWD = 2u, BWD = 4u;
+  const u32 lane = threadIdx.x;
+  const u64 lt = (1ull << lane) - 1ull;
+  auto reset = [&]() { for (u32 t = lane; t < n; t += 64) st[t] = 0; __syncthreads(); };
+  // takes out (GONE), among the transactions left, those that no edge of `mask` enters from a transaction left, until there is none;
+  // o / a: the edges followed, ro / ra: the same edges reversed.  Returns how many it took.
+  auto peel = [&](const u32 *o, const u32 *a, const u32 *ro, const u32 *ra, const u32 mask) -> u32 {
+    u32 tail = 0;
+    for (u32 base = 0; base < n; base += 64) {
+      const u32 t = base + lane;
+      bool z = false;
+      if (t < n && !(st[t] & GONE)) {
+        u32 d = 0;
+        for (u32 e = ro[t]; e < ro[t + 1]; e++) { const u32 x = ra[e]; d += ((x >> 28) & mask) && !(st[x & E_TO] & GONE); }
+        deg[t] = d; z = d == 0;
+      }
+      const u64 zm = __ballot(z);
+      if (z) queue[tail + (u32)__popcll(zm & lt)] = t;
+      tail += (u32)__popcll(zm);
+    }
+    __syncthreads();
+    u32 head = 0;
+    while (head < tail) {
+      const u32 cnt = min(64u, tail - head);
+      const bool on = lane < cnt;
+      const u32 v = on ? queue[head + lane] : 0u;
+      const u32 a0 = on ? o[v] : 0u, a1 = on ? o[v + 1] : 0u;
+      for (u32 k = 0; __ballot(a0 + k < a1); k++) {
+        bool push = false; u32 wv = 0;
+        if (a0 + k < a1) {
+          const u32 x = a[a0 + k]; wv = x & E_TO;
+          if (((x >> 28) & mask) && !(st[wv] & GONE)) push = atomicSub(&deg[wv], 1u) == 1u;   // (one taken in this call has no counted edge left)
+        }
+        const u64 pm = __ballot(push);
+        if (push) queue[tail + (u32)__popcll(pm & lt)] = wv;
+        tail += (u32)__popcll(pm);
+      }
+      head += cnt;
+      __syncthreads();
+    }
+    for (u32 i = lane; i < tail; i += 64) st[queue[i]] |= GONE;
+    __syncthreads();
+    return tail;
+  };
+  // marks `bit` on what `src` reaches over `mask` among the transactions left that carry `need`; the queue then lists them; returns how many
+  auto search = [&](const u32 *o, const u32 *a, const u32 mask, const u32 src, const u32 need, const u32 bit) -> u32 {
+    if (lane == 0) { queue[0] = src; st[src] |= bit; }
+    __syncthreads();
+    u32 head = 0, tail = 1;
+    while (head < tail) {
+      const u32 cnt = min(64u, tail - head);
+      const bool on = lane < cnt;
+      const u32 v = on ? queue[head + lane] : 0u;
+      const u32 a0 = on ? o[v] : 0u, a1 = on ? o[v + 1] : 0u;
+      for (u32 k = 0; __ballot(a0 + k < a1); k++) {
+        bool push = false; u32 wv = 0;
+        if (a0 + k < a1) {
+          const u32 x = a[a0 + k]; wv = x & E_TO;
+          if ((x >> 28) & mask) { const u32 s = st[wv]; if (!(s & (GONE | bit)) && (s & need) == need) push = !(atomicOr(&st[wv], bit) & bit); }
+        }
+        const u64 pm = __ballot(push);
+        if (push) queue[tail + (u32)__popcll(pm & lt)] = wv;
+        tail += (u32)__popcll(pm);
+      }
+      head += cnt;
+      __syncthreads();
+    }
+    return tail;
+  };
+  // the transactions in components of more than one transaction over `mask`; want_single: is there, in one of them, a rw edge u -> v
+  // whose v reaches u without a rw edge (single)?  over: a component beyond the matrix
+  bool single = false, over = false;
+  auto components = [&](const u32 mask, const bool want_single) -> u32 {
+    reset();
+    u32 left = n - peel(off, adj, roff, radj, mask);
+    if (left) left -= peel(roff, radj, off, adj, mask);
+    u32 cyc = 0;
+    while (left) {
+      for (u32 t = lane; t < n; t += 64) {   // one predecessor each (there is one: the peel is done)
+        if (st[t] & GONE) continue;
+        u32 pr = t;
+        for (u32 e = roff[t]; e < roff[t + 1]; e++) { const u32 x = radj[e]; if (((x >> 28) & mask) && !(st[x & E_TO] & GONE)) { pr = x & E_TO; break; } }
+        jump[t] = pr;
+      }
+      __syncthreads();
+      for (u32 r = 1; r < left; r <<= 1) {   // after these rounds jump[t] is at least `left` predecessors back: past every tail, on a cycle
+        for (u32 t = lane; t < n; t += 64) if (!(st[t] & GONE)) jump[t] = jump[jump[t]];
+        __syncthreads();
+      }
+      u32 pivot = NONE;
+      for (u32 base = 0; base < n && pivot == NONE; base += 64) {
+        const u32 t = base + lane;
+        const u64 m = __ballot(t < n && !(st[t] & GONE));
+        if (m) pivot = jump[base + (u32)__builtin_ctzll(m)];
+      }
+      if (pivot == NONE) break;
+      (void)search(off, adj, mask, pivot, 0u, FWD);
+      const u32 s = search(roff, radj, mask, pivot, FWD, BWD);   // the queue now lists the pivot's component
+      cyc += s;
+      if (want_single && !single && !over) {
+        if (s > p.ccap) over = true;
+        else {
+          const u32 W = (s + 63u) >> 6;
+          for (u32 i = lane; i < s; i += 64) jump[queue[i]] = i;
+          for (u32 i = lane; i < s * W; i += 64) mat[i] = 0;
+          __syncthreads();
+          for (u32 i = lane; i < s; i += 64) {   // lane = a row
+            const u32 u = queue[i];
+            for (u32 e = off[u]; e < off[u + 1]; e++) {
+              const u32 x = adj[e], w = x & E_TO;
+              if (((x >> 28) & mask & ~E_RW) && (st[w] & BWD)) mat[i * W + (jump[w] >> 6)] |= 1ull << (jump[w] & 63u);
+            }
+          }
+          __syncthreads();
+          for (u32 k = 0; k < s; k++) {
+            for (u32 i = lane; i < s; i += 64)
+              if ((mat[i * W + (k >> 6)] >> (k & 63u)) & 1ull) for (u32 w = 0; w < W; w++) mat[i * W + w] |= mat[k * W + w];
+            __syncthreads();
+          }
+          bool hit = false;
+          for (u32 i = lane; i < s; i += 64) {
+            const u32 u = queue[i];
+            for (u32 e = off[u]; e < off[u + 1]; e++) {
+              const u32 x = adj[e], w = x & E_TO;
+              if (((x >> 28) & E_RW) && w != u && (st[w] & BWD)) hit |= ((mat[jump[w] * W + (i >> 6)] >> (i & 63u)) & 1ull) != 0;
+            }
+          }
+          if (__ballot(hit)) single = true;
+        }
+      }
+      for (u32 i = lane; i < s; i += 64) st[queue[i]] = GONE;
+      __syncthreads();
+      for (u32 t = lane; t < n; t += 64) st[t] &= GONE;
+      __syncthreads();
+      left -= s;
+      if (left) left -= peel(off, adj, roff, radj, mask);
+      if (left) left -= peel(roff, radj, off, adj, mask);
+    }
+    return cyc;
+  };
+
+  u32 bits = 0, cyc = 0;
+  reset();
+  if (peel(off, adj, roff, radj, E_WW | E_WR | E_RW | E_RT) != n) {   // else acyclic over every edge kind (the common case elsewhere): nothing to classify
+    for (u32 x = 0; x <= E_RT && !bits; x += E_RT) {   // the dependency edges alone first; with the realtime edges only if that finds nothing
+      if (x == 0) { reset(); if (peel(off, adj, roff, radj, E_WW | E_WR | E_RW) == n) continue; }
+      reset();
+      u32 cls = 0;
+      if (peel(off, adj, roff, radj, E_WW | x) != n) cls = MSIM_ANOMALY_G0;
+      else { reset(); if (peel(off, adj, roff, radj, E_WW | E_WR | x) != n) cls = MSIM_ANOMALY_G1C; }
+      cyc = components(E_WW | E_WR | E_RW | x, cls == 0);
+      if (over) { if (lane == 0) p.out[hist] = res; return; }   // (res.valid is NEEDS_HOST)
+      if (!cls) cls = single ? MSIM_ANOMALY_G_SINGLE : MSIM_ANOMALY_G2;
+      bits = cls | (x ? MSIM_ANOMALY_REALTIME : 0u);
+    }
+  }
+  if (lane == 0) {
+    const u32 all = anomalies | bits;
+    const u32 cycles = MSIM_ANOMALY_G0 | MSIM_ANOMALY_G1C | MSIM_ANOMALY_G_SINGLE | MSIM_ANOMALY_G2;
+    u32 judged = all;   // judge(): cycles that need a realtime edge count under strict-serializable only
+    if ((judged & MSIM_ANOMALY_REALTIME) && p.cm != MSIM_CM_STRICT_SERIALIZABLE) judged &= ~(cycles | MSIM_ANOMALY_REALTIME);
+    res.lost_count = n_edges; res.stale_count = cyc; res.error_count = all;
+    res.valid = flags ? 0u : (judged & p.proscribed) ? 0u : (c_ok == 0 ? 2u : 1u);
+    p.out[hist] = res;
+  }
+}
+
+// FULL = false: the pass that proves a history free of what the model proscribes (rw_check_kernel).  FULL = true: the classification
+// (rw_classify_kernel): every edge kind whatever the model is, the non-cycle anomalies accumulated, the cycles classified — the record
+// of check_rw + finish + classify + judge (txn_check.cpp), field for field.
+template <bool FULL>
+__device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
+  const u32 lane = threadIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
   const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
   const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
@@ -77,9 +271,9 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
   const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
   const u32 flags = p.meta ? p.meta[hist].flags : 0u;
   const u32 NM = p.nmax;
-  const bool strong = p.cm <= MSIM_CM_SNAPSHOT_ISOLATION;            // every edge kind counts
-  const bool want_rt = p.cm == MSIM_CM_STRICT_SERIALIZABLE;
-  const bool want_wr = p.cm != MSIM_CM_READ_UNCOMMITTED;
+  const bool strong = FULL || p.cm <= MSIM_CM_SNAPSHOT_ISOLATION;            // every edge kind counts
+  const bool want_rt = FULL || p.cm == MSIM_CM_STRICT_SERIALIZABLE;
+  const bool want_wr = FULL || p.cm != MSIM_CM_READ_UNCOMMITTED;
   u32 *const ws = p.ws + (u64)blockIdx.x * p.ws_words;
   u32 *const t_inv = ws, *const t_cmp = t_inv + NM, *const t_off = t_cmp + NM, *const t_lt = t_off + NM;   // t_lt: words | type << 16
   u32 *const t_first = t_lt + NM;            // transactions invoked before this one's completion row
@@ -90,6 +284,8 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
   u32 *const writer = vseen + 2 * p.kmax;    // [wmax]
   u32 *const vsucc = writer + p.wmax;        // [wmax][2] successors of (key, version) in the key's version order
   u32 *const adj = vsucc + 2 * p.wmax;       // [emax]
+  // FULL only: the edges reversed (radj / roff / rcur), a transaction's state in the searches, the pivot search's pointers
+  u32 *const radj = adj + p.emax, *const roff = radj + p.emax, *const rcur = roff + NM + 1, *const st = rcur + NM, *const jump = st + NM;
 
   msim_check_result res;
   res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
@@ -100,7 +296,7 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
   if (n_words >= (1u << 24)) TO_HOST();
 
   // ---- A: transactions (txn_check_kernel's pairing) ---------------------------------------------------------------------------------
-  u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0;
+  u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0, anomalies = 0;
   {
     bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // lane = one open call (o_len: words of its request)
     for (u32 base = 0; base < n_rows; base += 64) {
@@ -108,8 +304,10 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
       uint4 row = make_uint4(0, 0, 0, 0);
       if (idx < n_rows) row = r[idx];
       const u32 type = row.z & 3u, f = (row.z >> 2) & 31u, proc = row.z >> 12, len = row.y >> 16, woff = row.w;
-      const bool is = idx < n_rows && proc != MSIM_PROCESS_NEMESIS && f == MSIM_F_TXN;
-      if (__ballot(is && (u64)woff + len > n_words)) { bad = true; break; }
+      const bool txn_row = idx < n_rows && proc != MSIM_PROCESS_NEMESIS && f == MSIM_F_TXN;
+      const bool outside = txn_row && (u64)woff + len > n_words;   // a payload outside its area: collect() skips the row and says internal
+      if (__ballot(outside)) { if constexpr (FULL) anomalies |= MSIM_ANOMALY_INTERNAL; else { bad = true; break; } }
+      const bool is = txn_row && !outside;
       const bool inv = is && type == MSIM_T_INVOKE;
       const u64 im = __ballot(inv);
       const u32 my_t = n + (u32)__popcll(im & lt);
@@ -159,25 +357,25 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
   if (max_val >= 64u || max_key >= p.kmax || (u64)(max_key + 1u) * stride > p.wmax) TO_HOST();   // (check_rw answers :unknown for values >= 64)
   for (u32 k = lane; k <= max_key; k += 64) { vseen[2 * k] = 0; vseen[2 * k + 1] = 0; }
   for (u32 k = lane; k < (max_key + 1u) * stride; k += 64) { writer[k] = NONE; vsucc[2 * k] = 0; vsucc[2 * k + 1] = 0; }
-  for (u32 t = lane; t <= n; t += 64) { off[t] = 0; if (t < n) { indeg[t] = 0; cur[t] = 0; } }
+  for (u32 t = lane; t <= n; t += 64) { off[t] = 0; if (t < n) { indeg[t] = 0; cur[t] = 0; if constexpr (FULL) rcur[t] = 0; } }
   __syncthreads();
 #define TYPE(t_) (t_lt[t_] >> 16)
 #define SETBIT(arr_, idx_, v_) atomicOr(&(arr_)[2 * (idx_) + ((v_) >> 5)], 1u << ((v_) & 31u))
 
   // ---- C: writers (every transaction, whatever became of it); versions written by transactions that did not fail -----------------------
-  u32 anomalies = 0;
+  bool for_host = false;
   for (u32 t = lane; t < n; t += 64) {
     const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu; const bool failed = TYPE(t) == MSIM_T_FAIL;
     for (u32 i = 0; i < wn; i++) {
       const u32 x = w[i];
       if (!M_F(x)) continue;
-      if (M_VAL(x) == 0xFFu) { anomalies |= MSIM_ANOMALY_INTERNAL; continue; }    // (a write of nil: the generator has none; let the host say what it is)
-      if (atomicCAS(&writer[M_KEY(x) * stride + M_VAL(x)], NONE, t) != NONE) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;   // the generator never repeats (k, v)
+      if (M_VAL(x) == 0xFFu) { for_host = true; continue; }    // (a write of nil: the generator has none; let the host say what it is)
+      if (atomicCAS(&writer[M_KEY(x) * stride + M_VAL(x)], NONE, t) != NONE) for_host = true;   // duplicate writes: the generator never repeats (k, v); the host's writer table is last-writer-wins
       if (!failed) SETBIT(vseen, M_KEY(x), M_VAL(x));
     }
   }
   __syncthreads();
-  if (__ballot(anomalies != 0)) TO_HOST();   // (duplicate writes are proscribed by every model)
+  if (__ballot(for_host)) TO_HOST();   // (duplicate writes are proscribed by every model)
 
   // the last value transaction t_ writes to key k_ (NONE: it does not write it)
   auto final_of = [&](u32 t_, u32 k_) -> u32 {
@@ -207,8 +405,9 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
   }
   for (int pass = 0; pass < 2; pass++) {
     u32 my_edges = 0;
-#define ADD(a_, b_) do { const u32 ea = (a_), eb = (b_); if (ea != eb) { if (pass == 0) { atomicAdd(&off[ea], 1u); atomicAdd(&indeg[eb], 1u); my_edges++; } \
-                                                                         else adj[off[ea] + atomicAdd(&cur[ea], 1u)] = eb; } } while (0)
+#define ADD(a_, b_, kind_) do { const u32 ea = (a_), eb = (b_); if (ea != eb) { if (pass == 0) { atomicAdd(&off[ea], 1u); atomicAdd(&indeg[eb], 1u); my_edges++; } \
+      else if constexpr (FULL) { adj[off[ea] + atomicAdd(&cur[ea], 1u)] = eb | ((kind_) << 28); radj[roff[eb] + atomicAdd(&rcur[eb], 1u)] = ea | ((kind_) << 28); } \
+      else adj[off[ea] + atomicAdd(&cur[ea], 1u)] = eb; } } while (0)
     // per :ok transaction: the reads
     for (u32 t = lane; t < n; t += 64) {
       if (TYPE(t) != MSIM_T_OK) continue;
@@ -234,7 +433,7 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
           else {
             if (wr != t) {
               if (final_of(wr, key) != val) anomalies |= MSIM_ANOMALY_G1B;
-              if (want_wr) ADD(wr, t);
+              if (want_wr) ADD(wr, t, E_WR);
             }
             const u32 fw = final_of(t, key);   // writes follow reads
             if (pass == 0 && fw != NONE && fw != val) SETBIT(vsucc, key * stride + val, fw);
@@ -244,7 +443,7 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
       if (want_rt) {
         const u32 first = t_first[t];                          // the transactions invoked after t completed start here ...
         const u32 last = sm[first] == NONE ? n : smf[first];   // ... and end where the first of them to complete :ok did
-        for (u32 v = first; v < last; v++) if (TYPE(v) != MSIM_T_FAIL) ADD(t, v);
+        for (u32 v = first; v < last; v++) if (TYPE(v) != MSIM_T_FAIL) ADD(t, v, E_RT);
       }
     }
     __syncthreads();
@@ -253,17 +452,28 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
       for (u32 key = lane; key <= max_key; key += 64) {
         const u64 seen = (((u64)vseen[2 * key + 1] << 32) | vseen[2 * key]) & ~1ull;
         u64 alive = seen;   // (nil precedes everything and follows nothing: it never sits on a cycle)
+        if constexpr (FULL) {   // as check_rw has it: nil's successors in the table, version 0 a version like any other
+          vsucc[2 * (key * stride)] |= (u32)seen; vsucc[2 * (key * stride) + 1] |= (u32)(seen >> 32);
+          alive = seen | 1ull;
+        }
         while (alive) {
           u64 has_in = 0;
           for (u64 b = alive; b; b &= b - 1) { const u32 v = (u32)__builtin_ctzll(b); if (v < stride) has_in |= ((u64)vsucc[2 * (key * stride + v) + 1] << 32) | vsucc[2 * (key * stride + v)]; }
           const u64 roots = alive & ~has_in;
-          if (!roots) { anomalies |= MSIM_ANOMALY_CYCLIC_VERSIONS; break; }
+          if (!roots) {
+            anomalies |= MSIM_ANOMALY_CYCLIC_VERSIONS;
+            if constexpr (FULL) for (u32 v = 0; v < stride; v++) { vsucc[2 * (key * stride + v)] = 0; vsucc[2 * (key * stride + v) + 1] = 0; }   // the key contributes no ww and no rw edges
+            break;
+          }
           alive &= ~roots;
         }
       }
     }
-    if (__ballot((anomalies & p.proscribed) != 0)) TO_HOST();
-    if (__ballot((anomalies & MSIM_ANOMALY_CYCLIC_VERSIONS) != 0)) TO_HOST();
+    if constexpr (FULL) { if (pass == 0) __syncthreads(); }   // nil's successors and the cleared keys, written by the keys' lanes, are read by the transactions' lanes below
+    if constexpr (!FULL) {
+      if (__ballot((anomalies & p.proscribed) != 0)) TO_HOST();
+      if (__ballot((anomalies & MSIM_ANOMALY_CYCLIC_VERSIONS) != 0)) TO_HOST();
+    }
     // ww along the version order of every key (lane = key); nil has no writer
     for (u32 key = lane; key <= max_key; key += 64) {
       for (u32 v1 = 1; v1 < stride; v1++) {
@@ -274,7 +484,7 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
         for (; su; su &= su - 1) {
           const u32 v2 = (u32)__builtin_ctzll(su);
           const u32 b = v2 < stride ? writer[key * stride + v2] : NONE;
-          if (b != NONE && TYPE(b) != MSIM_T_FAIL) ADD(a, b);
+          if (b != NONE && TYPE(b) != MSIM_T_FAIL) ADD(a, b, E_WW);
         }
       }
     }
@@ -291,12 +501,12 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
           for (u32 e = 0; e < k; e++) if (M_KEY(w[e]) == key) first = false;
           if (!first) continue;
           const u32 v1 = M_VAL(x) == 0xFFu ? 0u : M_VAL(x);
-          u64 su = v1 == 0 ? ((((u64)vseen[2 * key + 1] << 32) | vseen[2 * key]) & ~1ull)
-                           : (((u64)vsucc[2 * (key * stride + v1) + 1] << 32) | vsucc[2 * (key * stride + v1)]);
+          u64 su = (v1 == 0 && !FULL) ? ((((u64)vseen[2 * key + 1] << 32) | vseen[2 * key]) & ~1ull)
+                                      : (((u64)vsucc[2 * (key * stride + v1) + 1] << 32) | vsucc[2 * (key * stride + v1)]);
           for (; su; su &= su - 1) {
             const u32 v2 = (u32)__builtin_ctzll(su);
             const u32 b = v2 < stride ? writer[key * stride + v2] : NONE;
-            if (b != NONE && TYPE(b) != MSIM_T_FAIL) ADD(t, b);
+            if (b != NONE && TYPE(b) != MSIM_T_FAIL) ADD(t, b, E_RW);
           }
         }
       }
@@ -314,11 +524,25 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
         if (t <= n) off[t] = carry + ex;
         carry += r_sum(d);
       }
+      if constexpr (FULL) {   // in-degrees -> offsets of the reversed edges
+        carry = 0;
+        for (u32 base = 0; base <= n; base += 64) {
+          const u32 t = base + lane;
+          const u32 d = t < n ? indeg[t] : 0u;
+          const u32 ex = r_excl_scan(d, lane);
+          if (t <= n) roff[t] = carry + ex;
+          carry += r_sum(d);
+        }
+      }
       __syncthreads();
     }
   }
   anomalies = r_or(anomalies);
 
+  if constexpr (FULL) {
+    rw_classify(p, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue);
+    return;
+  }
   // ---- F: acyclic?  Kahn's algorithm, 64 ready transactions per step ---------------------------------------------------------------------
   u32 tail = 0;
   for (u32 base = 0; base < n; base += 64) {
@@ -359,10 +583,17 @@ __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) {
 #undef SETBIT
 }
 
+__global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) { rw_body<false>(p, p.first + blockIdx.x); }
+__global__ void __launch_bounds__(64) rw_classify_kernel(const RParams p) { rw_body<true>(p, p.list[p.first + blockIdx.x]); }
+
 uint64_t rw_ws_words(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return (uint64_t)nmax * 11 + 4 + 2 * (uint64_t)kmax + 3 * (uint64_t)wmax + emax; }
 
+uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws_words(nmax, emax, kmax, wmax) + emax + 4 * (uint64_t)nmax + 4; }
+
+// full: every history's record comes from the classification (msim_classify_rw_batch, msim_set_check_classify); otherwise only the
+// records of the histories that rw_check_kernel could not prove valid do
 int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-               void **ws_buf, size_t *ws_cap) {
+               void **ws_buf, size_t *ws_cap, bool full = false) {
   const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   const auto t0 = std::chrono::steady_clock::now();
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -371,26 +602,56 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
   rp.ws_words = rw_ws_words(rp.nmax, rp.emax, rp.kmax, rp.wmax);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold
   const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;   // MSIM_DEV_FLAGS bit 16: at most 7 histories per launch
-  const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
-  const size_t need = (size_t)chunk * rp.ws_words * 4;
-  if (*ws_cap < need) {
-    if (*ws_buf) (void)msim_dev_free(*ws_buf);
-    *ws_buf = nullptr; *ws_cap = 0;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(ws_buf, need));
-    *ws_cap = need;
-  }
-  rp.ws = static_cast<u32 *>(*ws_buf);
-  u32 launches = 0;
-  for (u32 first = 0; first < n; first += chunk, launches++) {
-    rp.first = first;
-    hipLaunchKernelGGL(rw_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, rp);
-    MSIM_HIP_TRY(ctx, hipGetLastError());
-  }
-  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-  MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+  auto reserve = [&](size_t need) -> int {
+    if (*ws_cap < need) {
+      if (*ws_buf) (void)msim_dev_free(*ws_buf);
+      *ws_buf = nullptr; *ws_cap = 0;
+      MSIM_HIP_TRY(ctx, msim_dev_malloc(ws_buf, need));
+      *ws_cap = need;
+    }
+    return MSIM_OK;
+  };
   std::vector<u32> todo;
-  for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-  if (trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories for the host\n", launches, ms(), todo.size(), n);
+  if (!full) {
+    const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
+    if (int rc = reserve((size_t)chunk * rp.ws_words * 4)) return rc;
+    rp.ws = static_cast<u32 *>(*ws_buf);
+    u32 launches = 0;
+    for (u32 first = 0; first < n; first += chunk, launches++) {
+      rp.first = first;
+      hipLaunchKernelGGL(rw_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, rp);
+      MSIM_HIP_TRY(ctx, hipGetLastError());
+    }
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
+    if (trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories not proved valid\n", launches, ms(), todo.size(), n);
+  } else {
+    todo.resize(n);
+    for (u32 i = 0; i < n; i++) todo[i] = i;
+  }
+  if (!todo.empty()) {   // the classification, over the list of histories that need it: the list first in the workspace, then a slice per block
+    const u32 m = (u32)todo.size();
+    const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
+    rp.ws_words = rw_ws_words_full(rp.nmax, rp.emax, rp.kmax, rp.wmax);
+    rp.ccap = (msim_dev_flags(ctx) & 0x2000u) ? 16u : CCAP;   // MSIM_DEV_FLAGS bit 13: a tiny matrix, so that tests reach the host
+    const u32 chunk = (u32)std::min<uint64_t>({m, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
+    if (int rc = reserve(list_bytes + (size_t)chunk * rp.ws_words * 4)) return rc;
+    rp.list = static_cast<const u32 *>(*ws_buf);
+    rp.ws = reinterpret_cast<u32 *>(static_cast<char *>(*ws_buf) + list_bytes);
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+    u32 launches = 0;
+    for (u32 first = 0; first < m; first += chunk, launches++) {
+      rp.first = first;
+      hipLaunchKernelGGL(rw_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
+      MSIM_HIP_TRY(ctx, hipGetLastError());
+    }
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    todo.clear();
+    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
+    if (trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, ms(), todo.size());
+  }
   if (!todo.empty()) {
     std::vector<uint64_t> ro, po;
     if (rp.row_off) { ro.resize(n + 1); po.resize(n + 1);
@@ -446,7 +707,7 @@ int msim_check_rw_device(msim_ctx *ctx) {
   rp.kmax = ctx->cfg.max_values ? ctx->cfg.max_values : 1u;
   rp.wmax = (u32)std::min<uint64_t>(WMAX, (uint64_t)rp.kmax * (ctx->cfg.max_writes_per_key + 2u));
   u32 redone = 0;
-  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch);
+  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->check_classify);
   if (rc != MSIM_OK) return rc;
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
@@ -456,8 +717,8 @@ int msim_check_rw_device(msim_ctx *ctx) {
 
 // Checks `n_histories` rw-register histories given on the host (rows / payload words of history i at row_offsets[i] /
 // payload_offsets[i]) as msim_check does for the histories of a run.
-extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
-                                   uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host) {
+static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                    uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool full) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
   msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
@@ -479,9 +740,29 @@ extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64
     RParams rp;
     std::memset(&rp, 0, sizeof rp);
     rp.rows = d_rows; rp.payload = d_pay; rp.row_off = d_ro; rp.pay_off = d_po; rp.out = d_out;
-    rp.nmax = max_r / 2 + 65; rp.emax = rp.nmax * 16; rp.cm = consistency_model; rp.proscribed = msim_proscribed_anomalies(consistency_model);
-    rc = rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, &ws, &ws_cap);
+    rp.nmax = max_r / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
+     rp.proscribed = msim_proscribed_anomalies(consistency_model);
+    rc = rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, &ws, &ws_cap, full);
   } while (false);
   for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, ws}) if (q) (void)msim_dev_free(q);
   return rc;
+}
+
+extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                   uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host) {
+  return rw_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, false);
+}
+
+// As msim_check_rw_batch, but every record is the full one of msim_check_rw_rows: the histories the model accepts name their allowed
+// cycle classes too.
+extern "C" int msim_classify_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                      uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host) {
+  return rw_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true);
+}
+
+extern "C" int msim_set_check_classify(msim_ctx *ctx, uint32_t on) {
+  if (!ctx) return MSIM_E_INVALID;
+  if (ctx->cfg.workload != MSIM_WL_TXN_RW_REGISTER) { ctx->err = "msim_set_check_classify: only txn-rw-register has a classification"; return MSIM_E_UNSUPPORTED; }
+  ctx->check_classify = on != 0;
+  return MSIM_OK;
 }

@@ -134,7 +134,12 @@ class Engine:
         self._chk(self.lib.msim_run_async(self._ctx, first_instance, n_instances, stream), "msim_run_async")
         self.n = n_instances
 
-    def check(self):
+    def check(self, classify=False):
+        """msim_check.  classify=True (txn-rw-register only): every history's record is the full analysis of check_rw_history, its allowed
+        cycle classes named (msim_set_check_classify); see anomaly_census."""
+        if classify or getattr(self, "_classify", False):
+            self._chk(self.lib.msim_set_check_classify(self._ctx, 1 if classify else 0), "msim_set_check_classify")
+            self._classify = bool(classify)
         self._chk(self.lib.msim_check(self._ctx), "msim_check")
 
     def set_dev_flags(self, flags):
@@ -698,9 +703,10 @@ def check_txn_batch(histories, device=0):
     return out
 
 
-def check_rw_batch(histories, consistency_model="read-committed", device=0):
-    """txn-rw-register: several histories, each (rows, payload), through the device pass behind Engine.check() with the host analysis for
-    what it cannot prove valid (msim_check_rw_batch).  Returns (CHECK_DT records, how many histories went to the host)."""
+def check_rw_batch(histories, consistency_model="read-committed", device=0, _entry="msim_check_rw_batch"):
+    """txn-rw-register: several histories, each (rows, payload), through the device passes behind Engine.check(): one proves a history
+    free of what the model proscribes, the other analyses and classifies the rest (msim_check_rw_batch); the host analysis only takes
+    what exceeds the device capacities.  Returns (CHECK_DT records, how many histories went to the host)."""
     rs = [np.ascontiguousarray(h[0]) for h in histories]
     ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
     ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
@@ -711,11 +717,25 @@ def check_rw_batch(histories, consistency_model="read-committed", device=0):
         pay = np.zeros(1, dtype=np.uint32)
     out = np.zeros(len(rs), dtype=CHECK_DT)
     n_host = C.c_uint32()
-    rc = A.load().msim_check_rw_batch(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs),
-                                      CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host))
+    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs),
+                                   CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host))
     if rc:
-        raise EngineError(f"msim_check_rw_batch: {rc}")
+        raise EngineError(f"{_entry}: {rc}")
     return out, n_host.value
+
+
+def classify_rw_batch(histories, consistency_model="read-committed", device=0):
+    """txn-rw-register: the full analysis of every history on the device (msim_classify_rw_batch): each record is what
+    check_rw_history's msim_check_rw_rows writes, the allowed cycle classes of valid histories included.  Returns (records, n_host)."""
+    return check_rw_batch(histories, consistency_model, device, _entry="msim_classify_rw_batch")
+
+
+def anomaly_census(results):
+    """How many records of a txn check (CHECK_DT) carry each anomaly of A.ANOMALIES (by name), and how many none ("clean")."""
+    bits = np.asarray(results["error_count"], dtype=np.uint32)
+    census = {name: int(((bits & np.uint32(b)) != 0).sum()) for b, name in A.ANOMALIES.items()}
+    census["clean"] = int((bits == 0).sum())
+    return census
 
 
 

@@ -1,0 +1,36 @@
+"""tests/test_rw_classify_gpu.py (the device classification of rw-register dependency cycles, csrc/rw_check_dev.hip rw_classify_kernel)
+through the host wavefront emulator: the kernel sources compiled by tools/hipemu/build_emu.py with the host compiler and loaded through
+MSIM_LIB in a child process, lanes out of lockstep (HIPEMU_DIVERGENT: a barrier the kernel lacks shows as a wrong record).  Once as it
+is, once with at most 7 histories per launch (MSIM_DEV_FLAGS bit 16: the batch entries read it from the environment), where the
+classification's chunk loop takes several launches and a partial last one."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, "tools", "hipemu", "_build", "libmaelsim_emu.so")
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    if shutil.which(os.environ.get("HIPEMU_CXX", "g++")) is None:
+        pytest.skip("no host C++ compiler for the emulator build")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "hipemu", "build_emu.py")], cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert os.path.exists(EMU)
+    return EMU
+
+
+@pytest.mark.timeout(1800)
+@pytest.mark.parametrize("flags,passed", [(None, 10), ("0x10000", 10)])
+def test_classification_on_the_emulator_equals_the_host_analysis(emu_lib, flags, passed):
+    env = dict(os.environ, MSIM_LIB=emu_lib, HIPEMU_DIVERGENT="1")
+    env.pop("MSIM_DEV_FLAGS", None)
+    if flags:
+        env["MSIM_DEV_FLAGS"] = flags
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_rw_classify_gpu.py")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0 and f"{passed} passed" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

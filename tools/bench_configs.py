@@ -54,6 +54,14 @@ CONFIGS = {
                                                                nemesis=["partition"], nemesis_interval=10), 16384),
     "txn-rw-register hat n=5 rate100 30s lat5 + partitions": (dict(workload="txn-rw-register", node_count=5, rate=100, time_limit=30, latency=5,
                                                                     nemesis=["partition"], nemesis_interval=10), 4096),
+    # the same histories judged by a model they violate: every history has a G2 cycle, which the device classifies (csrc/rw_check_dev.hip, rw_classify_kernel)
+    "txn-rw-register hat n=2 rate100 30s + partitions, serializable": (dict(workload="txn-rw-register", node_count=2, rate=100, time_limit=30,
+                                                                             nemesis=["partition"], nemesis_interval=10, consistency_model="serializable"), 16384),
+    "txn-rw-register hat n=5 rate100 30s lat5 + partitions, serializable": (dict(workload="txn-rw-register", node_count=5, rate=100, time_limit=30, latency=5,
+                                                                                  nemesis=["partition"], nemesis_interval=10, consistency_model="serializable"), 4096),
+    # read-committed with the allowed cycle classes named too (Engine.check(classify=True)): the line carries the anomaly census
+    "txn-rw-register hat n=2 rate100 30s + partitions, classify": (dict(workload="txn-rw-register", node_count=2, rate=100, time_limit=30,
+                                                                         nemesis=["partition"], nemesis_interval=10, classify=True), 16384),
 }
 
 
@@ -87,13 +95,15 @@ def main():
     only = sys.argv[1:] or list(CONFIGS)
     for name in only:
         kw, n = CONFIGS[name]
+        kw = dict(kw)
+        classify = kw.pop("classify", False)
         cfg = E.test_config(seed=99, **kw)
         with E.Engine(cfg) as eng:
             eng.run(0, n)                      # warm-up (allocation, code load, pinned host buffers of the host-side checkers)
-            eng.check()
+            eng.check(classify=classify)
             t0 = time.perf_counter()
             eng.run(n, n)
-            eng.check()
+            eng.check(classify=classify)
             dt = time.perf_counter() - t0
             sim_ms, chk_ms = eng.kernel_ms()
             eng.fetch()
@@ -107,6 +117,8 @@ def main():
             host_rechecks = eng.check_host_rechecks()
         out = {"config": name, "instances": n, "msgs_per_s": msgs / dt, "histories_per_s": valid / dt, "valid": valid, "flagged": flagged, "flags_seen": flag_or,
                "msgs_per_instance": msgs / n, "sim_ms": sim_ms, "check_ms": chk_ms, "check_host_rechecks": host_rechecks}
+        if classify:
+            out["anomaly_census"] = E.anomaly_census(res)
         if name in IN_FLIGHT and not os.environ.get("MSIM_BENCH_CONFIGS_NO_OVERLAP"):
             am = amortised_ms(cfg, n)
             out.update({"three_in_flight_ms_per_batch": am, "three_in_flight_msgs_per_s": msgs / (am * 1e-3), "three_in_flight_histories_per_s": valid / (am * 1e-3)})
