@@ -48,6 +48,10 @@
 // There, too, the two clusters PAIR their op rounds: a half that is ready for its op while its partner is in the middle of a flood waits
 // (it is parked: the wave-rounds are the partner's gossip rounds) until the partner is ready as well, so that one op wave-round serves
 // both (see "PAIRED OP ROUNDS" at the exit test of the gossip loop; -DDUO_NO_PAIR compiles it out).
+// And there the flood gossip rounds of a wavefront run in a loop of their own, the FLOOD STRETCH: between two such rounds nothing that R0 and
+// the exit test look at can change unless a half runs out of due envelopes or a parked half's count-down ends, so the loop's back edge
+// tests just that; inside it the flood bodies publish fan-out masks instead of envelopes (see "FLOOD STRETCH" at the flood gossip body and
+// DUO_FLOOD_ARRIVALS; -DDUO_NO_STRETCH compiles both out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -91,6 +95,13 @@ constexpr bool DUO_PLAN_ON = true;
 constexpr bool DUO_PAIR_ON = false;
 #else
 constexpr bool DUO_PAIR_ON = true;
+#endif
+// The flood stretch of the paired instantiation (see "FLOOD STRETCH" at the flood gossip body of sim_kernel_duo) and the fan-out masks the
+// flood bodies publish there; -DDUO_NO_STRETCH compiles both out for A/B runs.
+#ifdef DUO_NO_STRETCH
+constexpr bool DUO_STRETCH_ON = false;
+#else
+constexpr bool DUO_STRETCH_ON = true;
 #endif
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
@@ -167,8 +178,16 @@ __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__built
 
 // Latency 0: at least 6 wavefronts per SIMD (<= 80 VGPRs), what three launches of 2048 wavefronts in flight need; with the op round
 // beside the GENERAL body the register allocator otherwise takes 86 to 92 (no spills at 80)
+// (the -DDUO_PROF builds: 4 per SIMD, 128 VGPRs.  Their counters are per-lane registers, and at 80 they went to scratch memory, 36 bytes per
+//  lane before the flood stretch and 156 with its counters: the cycles such a build reported were its own spills' as much as the kernel's.
+//  tools/duo_prof_report.py runs one launch at a time, two wavefronts per SIMD, so the bound costs its figures nothing)
+#ifdef DUO_PROF
+#define DUO_LAT0_WAVES 4
+#else
+#define DUO_LAT0_WAVES 6
+#endif
 template <bool LAT0, bool DEG4, bool RND>
-__global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoParams dp) {
+__global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(const DuoParams dp) {
   static_assert(!(RND && LAT0), "random latency needs deadlines");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const KParams &p = dp.k;
@@ -192,6 +211,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;   // the instantiations with a flood mode (see below)
   constexpr bool RUNS = DUO_PLAN_ON && FLOOD;                    // ... whose op rounds take a run of reads at once
   constexpr bool PAIR = DUO_PAIR_ON && RUNS;                     // ... and wait for each other, so that one op round serves both halves
+  constexpr bool STRETCH = DUO_STRETCH_ON && PAIR;               // ... and take the gossip rounds of a flood in a loop of their own
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -271,6 +291,13 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       if (RND) nb_adj[k] = s < N ? topo_adj(p.cfg.topology, N, s) : 0u;
     }
   }
+  // STRETCH: the four neighbours' node numbers in one register (8 bits each, ascending like nbl), for the flood bodies, and what a node
+  // leaves out of its fan-out: the bit of the envelope's src, or nothing without skip-sender
+  // (there the generic bodies take an envelope's constant part from it as well: kc's four registers are what the stretch needs)
+  u32 nbp = 0;
+  if (STRETCH) nbp = (kc[0] >> 16) | (kc[1] >> 8) | kc[2] | (kc[3] << 8);
+#define DUO_KC(k_) (STRETCH ? ({ u32 kc_p = nbp; MSIM_OPAQUE(kc_p); ((kc_p >> (8 * (k_))) & 31u) << 16; }) : kc[k_])   /* (computed where it is used: not hoisted into four registers again) */
+  const u32 fan_skip = dp.echoback ? 0u : 1u;
 
   // ---- per-lane state: node i and its client (u32 throughout: flags are 0 / 1) ----
   u32 deliver_at = INF;      // INF = recv! holds no envelope (then the queue is empty too: idle receivers poll at once)
@@ -503,11 +530,25 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     const bool fr_new = (due_n_) & (fr_w != sw);                                                                          \
     pubb_ = (due_b_) & bal(fr_w != sw);                                                                                   \
     if (fr_new) DUO_SEEN_WORD() = fr_w;                                                                                   \
-    pub_ = fr_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                                \
+    if (STRETCH) pub_ = fr_new ? (adj & ~(fan_skip << ((cm >> 16) & 31u))) : 0u;   /* the fan-out mask (see DUO_FLOOD_ARRIVALS) */ \
+    else pub_ = fr_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                           \
     sw = fr_new ? fr_w : sw;                                                                                              \
   } while (0)
   // COMMIT: the pulls of DUO_ARRIVALS; the arrivals are only counted, an empty queue's head entry is its first arrival
+  // STRETCH: in the flood bodies a node publishes its FAN-OUT MASK, adj without the envelope's src (all of adj without skip-sender and
+  // for the client's own broadcast; bit 31 is never set: lane 31 holds no node), not the envelope: the value is the flood's, the cluster's
+  // next_value - 1, and need not travel.  "Neighbour k sends to me" is bit i of the word pulled from it; the arrivals are the number of
+  // such k, and the first arrival's src is the lowest one's node number, from nbp.  The generic bodies keep the envelope format: the
+  // publisher and the receivers of one wave-round are always in the same body, so the two formats never meet.
 #define DUO_FLOOD_ARRIVALS(pub_) do {                                                                                     \
+    if (STRETCH) {                                                                                                        \
+      const u32 fa_x[4] = {bperm(nbl[0], pub_), bperm(nbl[1], pub_), bperm(nbl[2], pub_), bperm(nbl[3], pub_)};           \
+      const u32 fa_m = ((fa_x[0] >> i) & 1u) | (((fa_x[1] >> i) & 1u) << 8) | (((fa_x[2] >> i) & 1u) << 16) | (((fa_x[3] >> i) & 1u) << 24); \
+      const u32 fa_src = (nbp >> (u32)__builtin_ctz(fa_m | 0x80000000u)) & 31u;   /* (no arrival: some number; nx means nothing while the queue stays empty) */ \
+      nx = in_n == 0 ? ((next_value - 1u) | (fa_src << 16)) : nx;                                                         \
+      in_n += (u32)__popc(fa_m); n_arr += (u32)__popc(fa_m);                                                              \
+      break;                                                                                                              \
+    }                                                                                                                     \
     const u32 fa_zk = 0x80000000u | me16;                                                                                 \
     const u32 fa_x[4] = {bperm(nbl[0], pub_), bperm(nbl[1], pub_), bperm(nbl[2], pub_), bperm(nbl[3], pub_)};             \
     bool fa_g[4]; u32 fa_c = 0;                                                                                           \
@@ -566,7 +607,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
           u32 ar_xx = 0, ar_bb = 0, ar_aa = 0, ar_cc = 0;                                                                 \
           _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                        \
             ar_xx = ar_g[ar_k] ? ar_x[ar_k] : ar_xx; ar_bb = ar_g[ar_k] ? ar_b[ar_k] : ar_bb;                             \
-            ar_aa = ar_g[ar_k] ? nb_adj[ar_k] : ar_aa; ar_cc = ar_g[ar_k] ? kc[ar_k] : ar_cc;                             \
+            ar_aa = ar_g[ar_k] ? nb_adj[ar_k] : ar_aa; ar_cc = ar_g[ar_k] ? DUO_KC(ar_k) : ar_cc;                             \
           }                                                                                                               \
           u32 ar_d; DUO_RND_DEADLINE(ar_xx, ar_bb, ar_aa, ar_d);                                                          \
           DUO_PUSH_CHECKED(ar_cnt != 0u, (ar_xx & 0xFFFFu) | ar_cc, ar_d);                                                \
@@ -574,7 +615,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
           _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                        \
             if (__ballot(ar_g[ar_k])) {                                                                                   \
               u32 ar_d; DUO_RND_DEADLINE(ar_x[ar_k], ar_b[ar_k], nb_adj[ar_k], ar_d);                                     \
-              DUO_PUSH_CHECKED(ar_g[ar_k], (ar_x[ar_k] & 0xFFFFu) | kc[ar_k], ar_d);                                      \
+              DUO_PUSH_CHECKED(ar_g[ar_k], (ar_x[ar_k] & 0xFFFFu) | DUO_KC(ar_k), ar_d);                                      \
             }                                                                                                             \
           }                                                                                                               \
         }                                                                                                                 \
@@ -586,7 +627,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         bool ar_g[4]; u32 ar_e[4];                                                                                        \
         _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                          \
           ar_g[ar_k] = (int)((ar_x[ar_k] & 0x803F0000u) ^ ar_zk) > 0;                                                     \
-          ar_e[ar_k] = (ar_x[ar_k] & 0xFFFFu) | kc[ar_k];                                                                 \
+          ar_e[ar_k] = (ar_x[ar_k] & 0xFFFFu) | DUO_KC(ar_k);                                                                 \
           DUO_RING_STORE(ar_s & Rm, ar_e[ar_k], ar_dl);                                                                   \
           ar_s += ar_g[ar_k] ? 1u : 0u;                                                                                   \
         }                                                                                                                 \
@@ -599,7 +640,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         _Pragma("unroll") for (int ar_k = 0; ar_k < 4; ar_k++) {                                                          \
           const bool ar_got = (int)((ar_x[ar_k] & 0x803F0000u) ^ ar_zk) > 0;                                              \
           n_arr += ar_got ? 1u : 0u;                                                                                      \
-          DUO_PUSH_CHECKED(ar_got, (ar_x[ar_k] & 0xFFFFu) | kc[ar_k], ar_dl);                                             \
+          DUO_PUSH_CHECKED(ar_got, (ar_x[ar_k] & 0xFFFFu) | DUO_KC(ar_k), ar_dl);                                             \
         }                                                                                                                 \
       }                                                                                                                   \
     } else {                                                                                                              \
@@ -644,6 +685,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
   u64 pf_it = 0, pf_fg = 0, pf_fop = 0, pf_mat = 0; u32 pf_nfg = 0, pf_nfop = 0, pf_nmat = 0;   // flood gossip rounds, flood op rounds, materialisations
   u32 pf_nrun = 0;   // reads of this lane's cluster that ran ahead of their wave-round's op (read runs)
   u64 pf_pk = 0; u32 pf_npark = 0, pf_npk = 0, pf_wmax = 0, pf_nop2 = 0;   // parked gossip rounds and their cycles, the parks, the longest wait, op wave-rounds that carried two ops
+  u32 pf_nst = 0, pf_nstr = 0, pf_ngg = 0; u64 pf_gg = 0;   // flood stretches, the rounds taken inside them, generic gossip rounds and their cycles
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -782,7 +824,62 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         }
         if (!parks) break;
       }
-      if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
+      if (STRETCH && (alive_m & ~fl_m) == 0) {
+        // ---- FLOOD STRETCH: the flood gossip rounds of both clusters, one after the other, until something else than such a round is next.
+        // This round is a flood gossip round: R0 and the exit test above have been through it.  What they would find in the NEXT one:
+        //   * R0's block is entered exactly when a half has nothing due and is not parked, or the count-down reaches 0.  At latency 0 the
+        //     poll leaves deliver_at = T in the lanes that took an envelope and INF in the others, and T stands outside the block, so the
+        //     next round's due_b is this round's bal(in_n != 0), taken before the poll's decrement.  While both halves of that mask | park_m
+        //     are non-zero and park_left is not about to reach 0, the block is not entered: T, sched_at, fg_m, alive_m, want_m and due_b
+        //     stay what they are, stuck_any is false, and the round limit, which only that block looks at, is not looked at.
+        //   * the exit test's gw_m is want_m, which is 0 here (else this round had left or parked: a parked half is out of want_m), or a
+        //     special envelope due.  THE FLOOD INVARIANT: a half in flood mode holds DK_PLAIN envelopes only (nx is value | src << 16 with
+        //     src < 32, whichever body set it), and every live half is in flood mode here, so no special envelope can be due (a build
+        //     with -DDUO_PROF, or for the host emulator, asserts it).  fl_m and alive_m change in op rounds and GENERAL bodies only.
+        // So the next round is again a flood gossip round, and all it needs of this one is the mask of the lanes with something due: the
+        // loop carries that mask, cm, nx, in_n, sw and the two counters, and its back edge tests the two halves and the count-down.
+        // deliver_at is not kept inside: on leaving it is T where the mask is set and INF elsewhere, what the polls would have left.
+        // rounds gets the rounds of the stretch at once (alive_v each: 0 for a parked or finished half, as in R0), park_left goes down by
+        // one per round.  The round that ends the stretch is not begun here: it enters the loop at its head, as ever, with the state R0
+        // expects, so the limit is looked at, the time moved, a half parked or released at the very rounds it was before.
+        // A half that is finished (or holds no cluster) is NOT counted as a half with something due, although R0's block does nothing FOR
+        // it: the block also looks at the round limit of its live partner, in every round of such a wavefront, and so stops that partner
+        // at rounds == round_limit exactly; a stretch over those rounds would stop it later (the one-cluster round-limit sweep of
+        // tests/test_duo_op_plan_hipemu.py sees the difference).  A wavefront with one live cluster therefore takes its rounds one by one.
+        u64 st_due = due_b; u32 st_more = 0;
+#ifdef DUO_PROF
+        pf_nst++;
+#endif
+        for (;;) {
+          const bool st_n = lane_in(st_due);
+#if defined(DUO_PROF) || defined(MSIM_HIPEMU)
+          if (st_n && lane_in(alive_m) && cm > 0xFFFFFFu) __builtin_trap();   // the flood invariant
+#endif
+          u32 pub; u64 pub_b; DUO_FLOOD_R3(st_n, st_due, pub, pub_b);
+          n_rsv += st_n ? 1u : 0u;
+          if (pub_b) DUO_FLOOD_ARRIVALS(pub);
+          st_due = bal(in_n != 0);   // the poll (DUO_FLOOD_POLL without deliver_at): whoever has a queue takes its head
+          const bool st_can = lane_in(st_due);
+          cm = st_can ? nx : cm; in_n -= st_can ? 1u : 0u;
+          // the back edge: the head of the next round (its count-down, its count) and the test that would send it into R0's block
+          const u64 st_db = st_due | park_m;
+          park_left--; st_more++;
+          if (min((u32)st_db, (u32)(st_db >> 32)) == 0 || park_left == 0) break;
+#ifdef DUO_PROF
+          pf_nwave++;
+#endif
+        }
+        park_left++; st_more--;   // (the round that ends the stretch begins at the loop's head: its count-down and its count are taken there)
+#ifdef DUO_PROF
+        // one reading per stretch (one per round cost a round of this loop more than the round itself); a half is parked or released at the
+        // exit test only, so a stretch is parked as a whole or not at all
+        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk += st_more + 1u; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); }
+        else { pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg += st_more + 1u; }
+        pf_nstr += st_more + 1u;
+#endif
+        rounds += st_more * alive_v;
+        deliver_at = lane_in(st_due) ? T : INF;
+      } else if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
         u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
         n_rsv += due_n ? 1u : 0u;
         if (pub_b) DUO_FLOOD_ARRIVALS(pub);
@@ -804,7 +901,8 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
         P2_MARK(3)
         DUO_POLL();
 #ifdef DUO_PROF
-        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk++; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); }   // (the generic gossip rounds are the loop's rest: the report takes these out)
+        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk++; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); }
+        else { pf_gg += __builtin_readcyclecounter() - pf_it; pf_ngg++; }   // (the generic gossip rounds, counted directly: -DDUO_PROF_STRETCH reports them)
 #endif
       }
     }
@@ -884,7 +982,7 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
       if (fl_round) DUO_FLOOD_R3(due_n, op_due, pub, pub_b);
       else { DUO_R3_SEEN(due_n, op_due, pub, pub_b); deliver_at = due_n ? INF : deliver_at; }
       n_rsv += due_n ? 1u : 0u;
-      pub = bc ? (0x80000000u | (63u << 16) | val) : pub;
+      pub = bc ? ((STRETCH && fl_round) ? adj : (0x80000000u | (63u << 16) | val)) : pub;   // (the flood bodies publish fan-out masks)
       pub_b |= bal(bc);
       // a read -> read_ok with the whole set, copied by the cluster's lanes (one reader per cluster)
       u32 cmp_value = val, cmp_len = 0;
@@ -1151,9 +1249,15 @@ __global__ void __launch_bounds__(64, LAT0 ? 6 : 1) sim_kernel_duo(const DuoPara
     // the wavefront's upper instance: flood gossip rounds | parked gossip rounds << 16, flood op rounds | op wave-rounds with two ops << 16
     // (12 bits) | materialisations << 28 (4 bits, saturating; their cycles are part of the GENERAL bodies'), cycles / 1024 (flood gossip
     // rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | parked gossip rounds << 16)
-    (void)pf_mat;
+    // with -DDUO_PROF_STRETCH as well, the lower instance carries instead of the GENERAL bodies' and op rounds' figures: flood stretches |
+    // the rounds taken inside them << 16, and generic gossip rounds | their cycles / 1024 << 16 (tools/duo_prof_report.py with STRETCH=1)
+    (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg;
     if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16);
-               m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27); }
+               m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27);
+#ifdef DUO_PROF_STRETCH
+               m.n_events = min(pf_nst, 65535u) | (min(pf_nstr, 65535u) << 16); m.reserved[1] = min(pf_ngg, 65535u) | (min((u32)(pf_gg >> 10), 65535u) << 16);
+#endif
+             }
     else { m.n_events = pf_nfg | (pf_npk << 16); m.reserved[0] = pf_nfop | (min(pf_nop2, 4095u) << 16) | (min(pf_nmat, 15u) << 28); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16);
            m.reserved[2] = ((u32)(pf_fop >> 10) & 0xFFFFu) | ((u32)(pf_pk >> 10) << 16); }
 #endif

@@ -4,7 +4,10 @@ the number of wave-rounds, how many of them were GENERAL rounds (op rounds and f
 flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries; and the
 wave-rounds with an op, the ops they executed, and how many of those were reads that ran ahead of their wave-round's op (read runs); and
 the paired op rounds: parks, parked gossip rounds per park and their cycles, the longest wait, op wave-rounds that carried one op or two.
-TOPOLOGY / NODES choose another shape (e.g. TOPOLOGY=line NODES=24, the long floods the wait cap is for)."""
+TOPOLOGY / NODES choose another shape (e.g. TOPOLOGY=line NODES=24, the long floods the wait cap is for).
+STRETCH=1: the library is a -DDUO_PROF -DDUO_PROF_STRETCH build (tools/variant_lib.sh profstretch duo.hip -DDUO_PROF -DDUO_PROF_STRETCH), whose lower
+instance carries the flood stretches, the rounds taken inside them and the generic gossip rounds with their cycles, counted directly, in place of
+the GENERAL bodies' and generic op rounds' figures: the lines about those are left out, the stretch lines are printed."""
 import os
 import sys
 
@@ -50,6 +53,18 @@ flood = os.environ.get("FLOOD", "1") != "0"
 nfg, nfop, nop2, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, (up[:, 1] >> 16) & 0xFFF, (up[:, 1] >> 28) & 0xF)]
 cfg_, cexit, cfop, cpk = [x.astype(np.float64) * 1024 * flood for x in (up[:, 2] & 0xFFFF, up[:, 2] >> 16, up[:, 3] & 0xFFFF, up[:, 3] >> 16)]
 cpk += 512 * (npk > 0)   # (the fields are truncated to 1024 cycles; it matters for this small one alone)
+stretch = os.environ.get("STRETCH", "0") != "0"
+if stretch:
+    nst, nstr, ngg, cgg = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64), (cyc & 0xFFFF).astype(np.float64), (cyc >> 16).astype(np.float64) * 1024
+    assert max(nstr.max(), ngg.max(), (cyc >> 16).max()) < 65535, "this shape overflows the 16-bit fields of the DUO_PROF_STRETCH build"
+    nin = nfg.mean() + npk.mean()   # flood gossip rounds, parked ones included: all of them run inside a stretch in a build with the stretch
+    print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms")
+    print(f"per wavefront: wave-rounds {nwave.mean():.0f}, cycles {ctot.mean():.3e}; flood stretches {nst.mean():.0f}, rounds taken inside them {nstr.mean():.0f} "
+          f"({nstr.mean() / max(nst.mean(), 1):.2f} per stretch; {100 * nstr.mean() / max(nin, 1):.1f} % of the {nin:.0f} flood gossip and parked rounds) at "
+          f"{(cfg_.mean() + cpk.mean()) / max(nin, 1):.0f} cycles per round ({100 * (cfg_.mean() + cpk.mean()) / ctot.mean():.1f} % of the cycles)")
+    print(f"generic gossip rounds, counted directly: {ngg.mean():.1f} per wavefront at {cgg.mean() / max(ngg.mean(), 1e-9):.0f} cycles each "
+          f"({cgg.mean():.3e} cycles per wavefront, {100 * cgg.mean() / ctot.mean():.2f} %; the fields are truncated to 1024 cycles)")
+    sys.exit(0)
 nop_all = nop.mean() + nfop.mean()
 print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms")
 nsched = ngen.mean() + nop_all
