@@ -52,6 +52,9 @@
 // the exit test look at can change unless a half runs out of due envelopes or a parked half's count-down ends, so the loop's back edge
 // tests just that; inside it the flood bodies publish fan-out masks instead of envelopes (see "FLOOD STRETCH" at the flood gossip body and
 // DUO_FLOOD_ARRIVALS; -DDUO_NO_STRETCH compiles both out).
+// That instantiation is TRIMMED of vector instructions the result does not need: no body counts the delivered envelopes (servers_recv follows
+// from the arrivals and what is left undelivered when the cluster stops), a flood's set word goes to HBM once, before something can read it
+// there, and an op wave-round derives its half's offsets once (see "TRIM" in sim_kernel_duo; -DDUO_NO_TRIM compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -65,6 +68,8 @@ __constant__ u32 duo_log2_q24[257];
 
 enum { DK_PLAIN = 0, DK_BCAST = 1, DK_READ = 2, DK_READ_FINAL = 3, DK_INIT = 4, DK_TOPO = 5 };  // kind of an envelope (bits 24-26)
 constexpr u32 DUO_STAGE_ROWS = 128u;
+constexpr u32 DUO_DROP_ONE = 1u << 8;   // TRIM: a lane's my_flags counts the envelopes it dropped in units of this, above the flag bits
+static_assert(DUO_DROP_ONE > MSIM_FLAG_JOURNAL_OVERFLOW, "the drop count lies above every flag");
 #ifndef DUO_BAG_N
 #define DUO_BAG_N 16
 #endif
@@ -102,6 +107,14 @@ constexpr bool DUO_PAIR_ON = true;
 constexpr bool DUO_STRETCH_ON = false;
 #else
 constexpr bool DUO_STRETCH_ON = true;
+#endif
+// The trims of the stretch instantiation (see "TRIM" in sim_kernel_duo): servers_recv by conservation instead of a count per round, the
+// flood's set word written back once instead of by every handling node, the half's offsets once per op wave-round; -DDUO_NO_TRIM compiles
+// all three out for A/B runs.
+#ifdef DUO_NO_TRIM
+constexpr bool DUO_TRIM_ON = false;
+#else
+constexpr bool DUO_TRIM_ON = true;
 #endif
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
@@ -170,11 +183,27 @@ __device__ __forceinline__ u32 half_min(u32 v, bool hi) {
 // vector instructions (the mask is turned into 0 / 1 and compared again).  Hot paths therefore combine the ballots of single compares
 // with scalar operations: bal(a) & bal(b) == bal(a & b), bal(a) | bal(b) == bal(a | b).
 __device__ __forceinline__ u64 bal(bool pred) { return __ballot(pred); }
+// The lane mask of ONE unsigned compare as one instruction: the compare intrinsic is its own ballot.  bal(a == b) is a compare and a ballot;
+// where a and b stand through a loop the optimizer hoists the compare out of it as a bool, and the ballot left behind turns that bool into
+// 0 / 1 and compares again (two vector instructions per use).  code_: 32 ==, 33 !=, 36 <, 37 <= (unsigned).
+#ifdef MSIM_HIPEMU
+#define DUO_BAL_CMP(a_, op_, b_, code_) bal((u32)(a_) op_ (u32)(b_))
+#else
+#define DUO_BAL_CMP(a_, op_, b_, code_) ((u64)__builtin_amdgcn_uicmp((u32)(a_), (u32)(b_), code_))
+#endif
 // A per-cluster boolean kept as a lane mask in SGPRs (all 32 bits of a half set or clear): a test of it costs scalar work only, bal() of it is
 // the mask itself, and a per-lane use reads the lane's bit (lane_in)
 __device__ __forceinline__ u64 hm2(bool lo, bool up) { return (lo ? 0xFFFFFFFFull : 0ull) | (up ? 0xFFFFFFFF00000000ull : 0ull); }
 __device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
+
+// element idx_ of an array; BYTES32: as the base plus a 32-bit BYTE offset (the whole array is below 4 GiB), the form whose address is the
+// base in SGPRs and one VGPR
+template <bool BYTES32, typename Tp>
+__device__ __forceinline__ Tp *duo_at(Tp *base, u32 idx) {
+  if constexpr (BYTES32) return reinterpret_cast<Tp *>(reinterpret_cast<unsigned char *>(base) + (size_t)(u32)(idx * (u32)sizeof(Tp)));
+  else return base + (size_t)idx;
+}
 
 // Latency 0: at least 6 wavefronts per SIMD (<= 80 VGPRs), what three launches of 2048 wavefronts in flight need; with the op round
 // beside the GENERAL body the register allocator otherwise takes 86 to 92 (no spills at 80)
@@ -212,6 +241,21 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   constexpr bool RUNS = DUO_PLAN_ON && FLOOD;                    // ... whose op rounds take a run of reads at once
   constexpr bool PAIR = DUO_PAIR_ON && RUNS;                     // ... and wait for each other, so that one op round serves both halves
   constexpr bool STRETCH = DUO_STRETCH_ON && PAIR;               // ... and take the gossip rounds of a flood in a loop of their own
+  // TRIM (of the stretch instantiation; every part is output-identical):
+  //   (A) n_rsv is not counted round by round.  Every server envelope counted in n_arr at its commit is received exactly once unless it is
+  //       still queued or held when its cluster stops, or was dropped at a full queue (MSIM_FLAG_INBOX_OVERFLOW).  At latency 0 a lane's queue and hand hold in_n + sp_n + [deliver_at != INF] envelopes, of which `busy` is its own client's
+  //       request (a busy client's request is queued or held: the node completes it in the round it handles it).  The two places that clear
+  //       a stopped half's queue put that number into n_rsv first, an envelope dropped at a full queue adds one (a dropped request: one, which
+  //       `busy` takes off again), and servers_recv = sum(n_arr) - sum(n_rsv): what the count gave, for flagged instances too.
+  //   (B) the flood bodies do not store sw.  A half in flood mode holds in sw, in EVERY lane, its column's word of value next_value - 1 (word 0
+  //       while next_value == 0), and writes it back with one wave-wide store at the points after which its HBM copy can be read: the head
+  //       of an op round in which it acts (before the read runs and the read op's copy) and DUO_MATERIALISE.  An acting half in flood
+  //       mode takes the op's word from sw instead of loading it; any acting half loads THAT word, not the op's value's: the two differ only
+  //       when the value opens a new word, and a word no value has fallen in yet is 0 in every lane (a broadcast value is fresh).
+  //   (C) the half's 0 / ~0 is derived once per op wave-round and GENERAL body (duo_upm, from a lane number the optimizer cannot see
+  //       through, so that nothing of it lives across the gossip loop), and rows and payload are addressed as the wavefront's base plus a
+  //       32-bit byte offset (msim_launch_duo checks that the two slabs of a wavefront stay below 4 GiB).
+  constexpr bool TRIM = DUO_TRIM_ON && STRETCH;
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -222,9 +266,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u32 *const w_pay = p.payload + (size_t)(blockIdx.x * 2u) * max_pay;
   // (RUNS: the half's share of the offset is computed at the access, from a lane number the optimizer cannot see through, so that it is not
   //  kept in a register across the rounds; only live clusters write rows or payload, and an upper half that holds no cluster is never live)
-#define DUO_UP(x_) (RUNS ? ({ u32 du_l = threadIdx.x; MSIM_OPAQUE(du_l); du_l >= 32u ? (x_) : 0u; }) : (up_half ? (x_) : 0u))
-#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? w_rows + (size_t)(DUO_UP(max_rows) + (idx_)) : g_rows + (idx_))[0])
-#define DUO_PAY(idx_) ((FLOOD ? w_pay + (size_t)(DUO_UP(max_pay) + (idx_)) : g_pay + (idx_))[0])
+#define DUO_UP(x_) (TRIM ? (duo_upm & (x_)) : (u32)(RUNS ? ({ u32 du_l = threadIdx.x; MSIM_OPAQUE(du_l); du_l >= 32u ? (x_) : 0u; }) : (up_half ? (x_) : 0u)))
+#define DUO_UPM_NOW() u32 duo_upm = 0; if (TRIM) { DUO_LANE_NOW(um_l); duo_upm = 0u - (um_l >> 5); }
+#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? duo_at<TRIM>(w_rows, DUO_UP(max_rows) + (idx_)) : g_rows + (idx_))[0])
+#define DUO_PAY(idx_) ((FLOOD ? duo_at<TRIM>(w_pay, DUO_UP(max_pay) + (idx_)) : g_pay + (idx_))[0])
   // HBM spill behind the LDS ring: {deadline, envelope} pairs in the node's slice of the spill area
   u64 *const my_spill = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)inst * p.scratch_words + p.spill_off) +
                                                     (size_t)(is_node ? i : 0) * p.spill_cap);
@@ -329,7 +374,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // lanes share) and so has two registers more for its op rounds.
   u32 dc_base = 0; u64 dc = draw64(key, S_GEN, (u64)i);
   // (addressed from a lane number the optimizer cannot see through: no register holds an address of it across the rounds)
-#define DUO_DCL(idx_) (reinterpret_cast<u64 *>(smem + ({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); dl_l >= 32u ? dp.half_bytes : 0u; }) + dp.off_dc)[idx_])
+#define DUO_DCL(idx_) (reinterpret_cast<u64 *>(smem + (TRIM ? (duo_upm & dp.half_bytes) : (u32)({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); dl_l >= 32u ? dp.half_bytes : 0u; })) + dp.off_dc)[idx_])
 #define DUO_DCL_MINE() (reinterpret_cast<u64 *>(smem + ({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); (dl_l >= 32u ? dp.half_bytes : 0u) + (dl_l & 31u) * 8u; }) + dp.off_dc)[0])
   if (RUNS) { DUO_DCL_MINE() = dc; dc = 0; wave_lds_fence(); }
 #define DUO_DRAW(k_, hi_, lo_) do {                                                                                       \
@@ -413,7 +458,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         in_n++;                                                                                                           \
       }                                                                                                                   \
       if (pc_got & !pc_fit) {                                                                                             \
-        if (sp_n >= S) my_flags |= MSIM_FLAG_INBOX_OVERFLOW;                                                              \
+        if (sp_n >= S) my_flags = (my_flags | MSIM_FLAG_INBOX_OVERFLOW) + (TRIM ? DUO_DROP_ONE : 0u);   /* (TRIM: the dropped envelopes are counted above the flag bits) */ \
         else { u32 pc_idx = s_head + sp_n; if (pc_idx >= S) pc_idx -= S; DUO_MY_SPILL(pc_sp) pc_sp[pc_idx] = (u64)pc_dl | ((u64)pc_e << 32); sp_n++; } \
       }                                                                                                                   \
     }                                                                                                                     \
@@ -529,10 +574,14 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     const u32 fr_w = sw | (1u << (cm & 31u));                                                                             \
     const bool fr_new = (due_n_) & (fr_w != sw);                                                                          \
     pubb_ = (due_b_) & bal(fr_w != sw);                                                                                   \
-    if (fr_new) DUO_SEEN_WORD() = fr_w;                                                                                   \
+    if (!TRIM) { if (fr_new) DUO_SEEN_WORD() = fr_w; }   /* (TRIM: written back later, see DUO_FLOOD_WB) */                    \
     if (STRETCH) pub_ = fr_new ? (adj & ~(fan_skip << ((cm >> 16) & 31u))) : 0u;   /* the fan-out mask (see DUO_FLOOD_ARRIVALS) */ \
     else pub_ = fr_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                           \
     sw = fr_new ? fr_w : sw;                                                                                              \
+  } while (0)
+  // TRIM: the write-back of sw by the lanes of wb_m_ (halves in flood mode), to the word of value next_value - 1
+#define DUO_FLOOD_WB(wb_m_) do {                                                                                          \
+    if (lane_in(wb_m_)) DUO_SET(set_lane + (((max(next_value, 1u) - 1u) & 0xFFE0u) << 2)) = sw;                           \
   } while (0)
   // COMMIT: the pulls of DUO_ARRIVALS; the arrivals are only counted, an empty queue's head entry is its first arrival
   // STRETCH: in the flood bodies a node publishes its FAN-OUT MASK, adj without the envelope's src (all of adj without skip-sender and
@@ -562,7 +611,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // after R3 every node is idle: the node takes the head of its queue if there is one.  No ring-head reload, no set-word prefetch.
 #define DUO_FLOOD_POLL() do {                                                                                             \
     const bool fp_can = in_n != 0;                                                                                        \
-    cm = fp_can ? nx : cm; deliver_at = fp_can ? T : INF; in_n -= fp_can ? 1u : 0u;                                       \
+    cm = fp_can ? nx : cm; deliver_at = fp_can ? T : INF; if (TRIM) in_n = max(in_n, 1u) - 1u; else in_n -= fp_can ? 1u : 0u; \
   } while (0)
   // leaving flood mode: the queued envelopes of every half in flood mode go to their ring (nx for each: see above); the fence orders
   // the stores before the reload of the ring head by the poll that follows
@@ -570,6 +619,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (FLOOD && fl_m != 0) {                                                                                             \
       PF_MAT_BEGIN                                                                                                        \
       const bool mt_on = lane_in(fl_m);                                                                                   \
+      if (TRIM) DUO_FLOOD_WB(fl_m);                                                                                       \
       for (u32 mt_k = 0; __ballot(mt_on & (mt_k < in_n)); mt_k++)                                                         \
         if (mt_on & (mt_k < in_n)) ring32[((head + mt_k) & Rm) * 32u] = nx;                                               \
       wave_lds_fence();                                                                                                   \
@@ -796,9 +846,18 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           // due (at latency 0 a node that holds one has it due), hence every node idle with an empty queue and every client free.  Its
           // generator's op is then all the cluster does this round: an op round.  Every half that wants a GENERAL round has to be in
           // that state (main phase, not forced, nothing due, no client busy, room for a value and two rows); else the GENERAL body runs.
-          const u64 bz_b = bal(busy != 0);
-          const u64 st_m = ~fg_m & bal(phase == PH_MAIN) & bal(next_value < max_values) & bal(n_rows + 2u <= max_rows) & bal(gen_k - dc_base < 32u) &
-                           hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
+          // (TRIM: each of the five masks is one compare; as bal() they were five compares hoisted to the head of the outer loop and ten
+          //  instructions here that turned the bools into masks again)
+          u64 bz_b, st_m;
+          if (TRIM) {
+            bz_b = DUO_BAL_CMP(busy, !=, 0u, 33);
+            st_m = ~fg_m & DUO_BAL_CMP(phase, ==, PH_MAIN, 32) & DUO_BAL_CMP(next_value, <, max_values, 36) & DUO_BAL_CMP(n_rows + 2u, <=, max_rows, 37) & DUO_BAL_CMP(gen_k - dc_base, <, 32u, 36) &
+                   hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
+          } else {
+            bz_b = bal(busy != 0);
+            st_m = ~fg_m & bal(phase == PH_MAIN) & bal(next_value < max_values) & bal(n_rows + 2u <= max_rows) & bal(gen_k - dc_base < 32u) &
+                   hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
+          }
           op_m = (gw_m & ~st_m) == 0 ? gw_m : 0ull; op_due = due_b;
           // PAIRED OP ROUNDS.  The two clusters are independent, so the order in which they take their rounds is free, and an op wave-round
           // costs the wavefront the same whether it carries the op of one half or of both.  So when exactly one half wants a round, an op
@@ -856,11 +915,11 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           if (st_n && lane_in(alive_m) && cm > 0xFFFFFFu) __builtin_trap();   // the flood invariant
 #endif
           u32 pub; u64 pub_b; DUO_FLOOD_R3(st_n, st_due, pub, pub_b);
-          n_rsv += st_n ? 1u : 0u;
+          if (!TRIM) n_rsv += st_n ? 1u : 0u;
           if (pub_b) DUO_FLOOD_ARRIVALS(pub);
           st_due = bal(in_n != 0);   // the poll (DUO_FLOOD_POLL without deliver_at): whoever has a queue takes its head
           const bool st_can = lane_in(st_due);
-          cm = st_can ? nx : cm; in_n -= st_can ? 1u : 0u;
+          cm = st_can ? nx : cm; if (TRIM) in_n = max(in_n, 1u) - 1u; else in_n -= st_can ? 1u : 0u;   /* (TRIM: one saturating subtraction) */
           // the back edge: the head of the next round (its count-down, its count) and the test that would send it into R0's block
           const u64 st_db = st_due | park_m;
           park_left--; st_more++;
@@ -881,7 +940,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         deliver_at = lane_in(st_due) ? T : INF;
       } else if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
         u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
-        n_rsv += due_n ? 1u : 0u;
+        if (!TRIM) n_rsv += due_n ? 1u : 0u;
         if (pub_b) DUO_FLOOD_ARRIVALS(pub);
         DUO_FLOOD_POLL();
 #ifdef DUO_PROF
@@ -891,7 +950,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         P2_MARK(0)
         u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
         deliver_at = due_n ? INF : deliver_at;
-        n_rsv += due_n ? 1u : 0u;
+        if (!TRIM) n_rsv += due_n ? 1u : 0u;
         P2_MARK(1)
         if (pub_b) {
           if (RND) DUO_RND_IDS(pub, false);
@@ -916,6 +975,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       //      computes for such a cluster: every worker is free, so the pick is the node of that rank, and it is idle, so its recv! takes
       //      the request at once and the node completes it in this round (busy goes 1 -> 0 within the round) ----
       const bool opn = lane_in(op_m);
+      DUO_UPM_NOW();   // (C)
+      if (TRIM && (op_m & fl_m) != 0) DUO_FLOOD_WB(op_m & fl_m);   // (B): the read runs, the read op's copy read the sets from HBM
       // READ RUNS.  An acting cluster is quiescent, and a read leaves it so: the picked node copies its set to the payload, two rows
       // appear, and the cluster's next round is its generator's next op.  While the op at hand is a read AND the op after it will
       // again be an op round's (its draw is in the cluster's block, it falls before the cutoff, its rows and this read's payload fit,
@@ -965,6 +1026,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // the word of the nodes' sets that the op's value falls in, fetched first: only the picked node's store at the end of the round
       // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
       u32 op_w = 0;
+      if (TRIM) {   // (B): the word of value next_value - 1: in sw already in flood mode, and 0 where the op's value opens a new word
+        op_w = sw;
+        if (op_m & ~fl_m) { if (opn && !lane_in(fl_m)) op_w = DUO_SET(set_lane + (((max(next_value, 1u) - 1u) & 0xFFE0u) << 2)); }
+      } else
       if (opn) op_w = DUO_SET(set_lane + ((next_value & 0xFFE0u) << 2));
       const bool fl_round = FLOOD && (alive_m & ~fl_m) == 0;   // every live half is in flood mode: the flood op round
       u32 r_hi, r_lo; DUO_DRAW(gen_k, r_hi, r_lo);   // (the op's draw is in the cluster's block of 32; the GENERAL body draws the next block)
@@ -981,7 +1046,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       u32 pub; u64 pub_b;
       if (fl_round) DUO_FLOOD_R3(due_n, op_due, pub, pub_b);
       else { DUO_R3_SEEN(due_n, op_due, pub, pub_b); deliver_at = due_n ? INF : deliver_at; }
-      n_rsv += due_n ? 1u : 0u;
+      if (!TRIM) n_rsv += due_n ? 1u : 0u;
       pub = bc ? ((STRETCH && fl_round) ? adj : (0x80000000u | (63u << 16) | val)) : pub;   // (the flood bodies publish fan-out masks)
       pub_b |= bal(bc);
       // a read -> read_ok with the whole set, copied by the cluster's lanes (one reader per cluster)
@@ -1013,10 +1078,11 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       }
       n_rows += opn ? 2u : 0u;
       // FLOOD: the picked node's new set word and every other lane's (unchanged) one: what the store writes and what sw becomes
+      if (TRIM) op_w = lane_in(op_m & DUO_BAL_CMP(r_lo & 1u, ==, 0u, 32) & DUO_BAL_CMP(val & 31u, ==, 0u, 32)) ? 0u : op_w;
       const u32 op_w1 = FLOOD ? (op_w | (bc ? 1u << (val & 31u) : 0u)) : 0u;
       if (fl_round) {
         if (pub_b) DUO_FLOOD_ARRIVALS(pub);
-        if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w1;
+        if (!TRIM) { if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w1; }
         DUO_FLOOD_POLL();
       } else {
         if (pub_b) DUO_ARRIVALS(pub);
@@ -1038,7 +1104,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         DUO_SCHED_VIEW(hbusy_b);
         alive_v = lane_in(alive_m) ? 1u : 0u;
         if (~alive_m) {
-          if (!lane_in(alive_m)) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
+          if (!lane_in(alive_m)) { if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   /* what stays undelivered (A) */
+                                   deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
         }
       } else sched_at = opn ? gen_next : sched_at;
 #ifdef DUO_PROF
@@ -1049,6 +1116,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     P3_MARK(0)   // [0] = the gossip rounds
     DUO_MATERIALISE();
     // (RUNS: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
+    DUO_UPM_NOW();   // TRIM (C)
     u32 gi = i; if (RUNS) MSIM_OPAQUE(gi);
     const u32 g_lt = RUNS ? (1u << gi) - 1u : lt;
     u32 inv_row = 0, inv_packed = 0, inv_value = 0;
@@ -1112,7 +1180,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     const u32 v = cm & 0xFFFFu;
     u32 pub; u64 pub_b; DUO_R3_SEEN(due_n & (kind <= DK_BCAST), due_b & bal(kind <= DK_BCAST), pub, pub_b);
     deliver_at = due_n ? INF : deliver_at;
-    n_rsv += (due_n && kind == DK_PLAIN) ? 1u : 0u;
+    if (!TRIM) n_rsv += (due_n && kind == DK_PLAIN) ? 1u : 0u;
     const bool req = due_n && kind != DK_PLAIN;   // a request of this lane's client: handled, answered and completed in this round
     n_cl += req ? 1u : 0u;
     busy = req ? 0u : busy;
@@ -1205,7 +1273,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     }
     alive_v = lane_in(alive_m) ? 1u : 0u;
     if (~alive_m) {
-      if (!lane_in(alive_m)) { deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
+      if (!lane_in(alive_m)) { if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   // what stays undelivered (A)
+                               deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
     }
     P3_MARK(7)   // [7] = the scheduler's view
 #ifdef DUO_PROF
@@ -1226,6 +1295,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (!RND && !DUO_DIRECT && real && g0 < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0] = stage[g0 % DUO_STAGE_ROWS];
     if (!RND && !DUO_DIRECT && real && g0 + 32u < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0 + 32u] = stage[(g0 + 32u) % DUO_STAGE_ROWS];
   }
+  if (TRIM) n_rsv += my_flags / DUO_DROP_ONE;   // (a dropped envelope is not received either)
   const u32 sc_cl = wave_incl_scan(n_cl), sc_arr = wave_incl_scan(n_arr), sc_rsv = wave_incl_scan(n_rsv);
   const u32 lo_cl = rdlane(sc_cl, 31), lo_arr = rdlane(sc_arr, 31), lo_rsv = rdlane(sc_rsv, 31);
   const u32 t_cl = hi ? rdlane(sc_cl, 63) - lo_cl : lo_cl;
@@ -1238,7 +1308,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     // every client RPC is a request and a reply, each sent and received once (no loss, no timeouts in this layout)
     msim_net_stats st;
     st.clients_send = 2ull * t_cl; st.clients_recv = 2ull * t_cl;
-    st.servers_send = t_arr; st.servers_recv = t_rsv;
+    st.servers_send = t_arr; st.servers_recv = TRIM ? t_arr - t_rsv : t_rsv;   // (TRIM: n_rsv holds what stayed undelivered)
     st.all_send = st.clients_send + st.servers_send; st.all_recv = st.clients_recv + st.servers_recv;
     p.stats[inst_out] = st;
     msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
@@ -1357,6 +1427,8 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   // 2 GiB per instance (spill <= 32 nodes x 65536 envelopes x 16 B, queues bounded by the LDS check of msim_run, max_values <= 8160):
   // the test below cannot fail for one that reaches this kernel.
   if (kp.scratch_words * 4 >= (1ull << 31)) return MSIM_LAYOUT_DOES_NOT_FIT;
+  // TRIM (C): rows and payload of a wavefront's two clusters are reached with 32-bit byte offsets from the lower cluster's
+  if (2ull * c.max_rows * 16ull >= (1ull << 32) || 2ull * c.max_payload_words * 4ull >= (1ull << 32)) return MSIM_LAYOUT_DOES_NOT_FIT;
   dp.sets_off = (u32)(kp.scratch_words - msim_duo_extra_scratch_words(c));
   dp.inst_bytes = (u32)(kp.scratch_words * 4);
   const bool deg4 = duo_degree(c) <= 4 && kp.N <= 31;   // (lane 31 must hold no node: unused neighbour slots point at it)
