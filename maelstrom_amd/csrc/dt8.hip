@@ -20,8 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
-#include "wave_common.h"
-#include "latency_sampler.h"
+#include "group8.h"
 #include "layout_thresholds.h"
 
 namespace {
@@ -74,14 +73,6 @@ __device__ __forceinline__ u32 d8_hash(u32 k) {
     for (u32 b = 0; b < 8; b++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
   }
   return (~c) & 127u;
-}
-
-// min over the 8 lanes of the caller's group, in every lane of it
-__device__ __forceinline__ u32 m8_oct_min(u32 v) {
-  v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_mov<0x4E, 0xF, 0xF, false>(v, v));   // quad_perm [2,3,0,1]
-  v = min(v, dpp_mov<0x141, 0xF, 0xF, false>(v, v));  // row_half_mirror
-  return v;
 }
 
 // ---- apply_txn as a function of its own ---------------------------------------------------------------------------------------------------
@@ -361,16 +352,16 @@ __device__ D8_APPLY_ATTR D8ApplyIO d8_apply(D8ApplyIO io, const D8ApplyK kc, u32
 #endif
 #define D8_OCC __attribute__((amdgpu_waves_per_eu(D8_WAVES_PER_EU)))
 template <bool NEM, bool NET_RANDOM>
-__global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
+__global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params up) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const KParams &p = tp.k;
+  const KParams &p = up.k;
   const u32 lane = threadIdx.x, l = lane & (GS - 1u), grp = lane >> 3, gbase = lane & 56u;
   const u32 N = p.N;
   const bool is_node = l < N, is_lin = l == N;
   const u32 LIN = 2 * N;   // endpoint index of lin-kv (lane N of the group); lww-kv is LIN + 1 (lane N + 1)
   const u32 inst_raw = blockIdx.x * 8u + grp;
-  const bool real = inst_raw < tp.n_inst;
-  const u32 inst = real ? inst_raw : tp.n_inst - 1u;
+  const bool real = inst_raw < up.n_inst;
+  const u32 inst = real ? inst_raw : up.n_inst - 1u;
   const u64 key = mix64(p.cfg.seed + 0x9E3779B97F4A7C15ull * (p.first_instance + inst + 1));
   const u32 lt = (1u << l) - 1u;
   const u32 all_nodes = (1u << N) - 1u;
@@ -378,7 +369,7 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
   const u32 p_loss = p.cfg.p_loss_q32, lat_mean = p.cfg.latency_mean_ms, lat_dist = p.cfg.latency_dist;
   const u32 rate = p.cfg.rate_mhz, mw = p.cfg.max_writes_per_key, mv = p.cfg.max_values;
   const u32 TC = p.mk_tcap;   // tree nodes a node may create
-  const u32 round_limit = tp.round_limit;
+  const u32 round_limit = up.round_limit;
 
   // A register diet for four wavefronts per SIMD (128 registers): nothing that can be recomputed is carried through the round loop.  Every
   // address in an instance's slabs is the slab's base (a kernel argument: scalar registers) + the instance's offset, formed where it is used from
@@ -386,9 +377,9 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
   // the offsets of the regions inside an instance's scratch (dt_kernel<>'s layout, sim_kernel_dt.inc) are the same for every cluster: scalars.
   const u32 OFF_KVN = mv * mw, OFF_FIRST = OFF_KVN + mv, OFF_HASHW = OFF_FIRST + mv, OFF_REC = (OFF_HASHW + (mv + 3u) / 4u + 3u) & ~3u;   // (records are read and written 16 bytes at a time)
   const u32 OFF_WL = OFF_REC + N * TC * DT_RW, OFF_CAS = OFF_WL + N * DT_MAXW;
-  const u32 OFF_SPILL = (u32)p.spill_off, OFF_CSPILL = (u32)tp.client_spill_off, OFF_AUX = (u32)tp.stack_off;
+  const u32 OFF_SPILL = (u32)p.spill_off, OFF_CSPILL = (u32)up.client_spill_off, OFF_AUX = (u32)up.stack_off;
   const u32 qlane = l <= N + 1u ? l : 0u;
-  const u32 my_spill_cap = l <= N + 1u ? tp.node_spill : 0u;
+  const u32 my_spill_cap = l <= N + 1u ? up.node_spill : 0u;
   const u32 my_node = is_node ? l : 0u;
 #define D8_INST ([&]() -> size_t { u32 i_ = inst; MSIM_OPAQUE(i_); return (size_t)i_; }())
 #define g_rows (p.rows + D8_INST * max_rows)
@@ -400,19 +391,19 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
 #define g_rec (g_scr + OFF_REC)                                     /* [N][TC][DT_RW] tree nodes by pointer */
 #define g_wl (g_scr + OFF_WL)                                       /* [N][DT_MAXW] the pointers a node writes this round */
 #define g_cas (g_scr + OFF_CAS)                                     /* [N][DT_CASQ] x {msg_id, from, transaction}: what a node's cas requests carry beside `to` */
-#define my_spill (reinterpret_cast<uint4 *>(g_scr + OFF_SPILL) + qlane * tp.node_spill)
-#define my_cspill (reinterpret_cast<uint4 *>(g_scr + OFF_CSPILL) + my_node * tp.client_spill)
+#define my_spill (reinterpret_cast<uint4 *>(g_scr + OFF_SPILL) + qlane * up.node_spill)
+#define my_cspill (reinterpret_cast<uint4 *>(g_scr + OFF_CSPILL) + my_node * up.client_spill)
 #define aux (g_scr + OFF_AUX + my_node * D8_AUX)
 #define my_wl (g_scr + OFF_WL + my_node * DT_MAXW)
 
   uint4 *const my_q = reinterpret_cast<uint4 *>(smem) + lane;                                   // node / service queue: slot s at my_q[s * 64]
-  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + tp.off_cq) + lane;                      // client inbox
-  u32 *const curs_g = reinterpret_cast<u32 *>(smem + tp.off_cur) + grp * (N * D8_CW);           // [node of the group][D8_CW]
-  u32 *const gen = reinterpret_cast<u32 *>(smem + tp.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
-  u32 *const misc = reinterpret_cast<u32 *>(smem + tp.off_misc) + grp * GS;
+  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + up.off_cq) + lane;                      // client inbox
+  u32 *const curs_g = reinterpret_cast<u32 *>(smem + up.off_cur) + grp * (N * D8_CW);           // [node of the group][D8_CW]
+  u32 *const gen = reinterpret_cast<u32 *>(smem + up.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
+  u32 *const misc = reinterpret_cast<u32 *>(smem + up.off_misc) + grp * GS;
   u32 *const cu = curs_g + my_node * D8_CW;
 
-  for (u32 i = lane; i < 8 * N * D8_CW; i += 64) reinterpret_cast<u32 *>(smem + tp.off_cur)[i] = 0;
+  for (u32 i = lane; i < 8 * N * D8_CW; i += 64) reinterpret_cast<u32 *>(smem + up.off_cur)[i] = 0;
   for (u32 i = l; i < 16; i += GS) { gen[i] = i; gen[16 + i] = 1; }
   if (l == 0) gen[32] = p.cfg.key_count;
   if (real) {
@@ -446,7 +437,7 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
   // ... and what a round only looks at briefly lives in LDS, one copy per cluster (written by the cluster's lane 0, or or-ed in): rounds so far,
   // the end of the main phase, the generator's and the nemesis' next times and counters, "losses are on", the instance's flags
   enum { CS_ROUNDS = 0, CS_CUTOFF, CS_GEN_NEXT, CS_NEM_NEXT, CS_GEN_K, CS_NEM_J, CS_LOSS_ON, CS_FLAGS, CS_WORDS };
-  u32 *const cs = reinterpret_cast<u32 *>(smem + tp.off_cs) + grp * CS_WORDS;
+  u32 *const cs = reinterpret_cast<u32 *>(smem + up.off_cs) + grp * CS_WORDS;
   if (l < CS_WORDS) cs[l] = 0;
   wave_lds_fence();
 #define CFLAG(x_) atomicOr(&cs[CS_FLAGS], (x_))
@@ -544,26 +535,16 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
     if (alive) { const u32 r = rounds_before + 1u; if (l == 0) cs[CS_ROUNDS] = r; if (r > round_limit) { CFLAG(MSIM_FLAG_ROUND_LIMIT); alive = false; } }
     if (GB((my_flags & MSIM_FLAG_ARENA_OVERRUN) != 0)) alive = false;   // an engine capacity was exceeded: what follows would not be the program's behaviour
 
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = all_nodes & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
+    #include "group8_time.inc"
     bool timeout_round = false;
     {
-      const bool none_due = GB(deliver_at <= T || wait_until <= T) == 0;
+      const bool none_due = GB(my_t <= T || wait_until <= T) == 0;
       const bool jump = alive && due > T && none_due;
       if (__ballot(jump)) {
-        u32 k = deliver_at == INF ? INF : deliver_at * 2;
+        u32 k = my_t == INF ? INF : my_t * 2;
         if (wait_until != INF) k = min(k, wait_until * 2);   // (a node's timer is a normal event)
         if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = m8_oct_min(k);
+        u32 km = g8_min<GS>(k);
         if (due != INF) km = min(km, due * 2);
         if (jump) {
           if (km == INF) { CFLAG(MSIM_FLAG_ROUND_LIMIT); alive = false; }
@@ -945,7 +926,7 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
         io.n_out = n_out; io.o_dest = o_dest; io.o1_type = o1_type; io.o1_a = o1_a; io.o1_b = o1_b; io.o_wlo = o_wlo; io.done = 0;
         D8ApplyK kc;
         kc.scratch = p.scratch; kc.payload = p.payload; kc.scratch_words = p.scratch_words; kc.max_pay = max_pay; kc.N = N; kc.TC = TC; kc.mv = mv; kc.mw = mw;
-        kc.off_aux = OFF_AUX; kc.off_cur = tp.off_cur; kc.off_gen = tp.off_gen;
+        kc.off_aux = OFF_AUX; kc.off_cur = up.off_cur; kc.off_gen = up.off_gen;
         io = d8_apply(io, kc, inst, lane, T, do_apply);
         next_p = io.np; node_msgid = io.mid; my_flags = io.my_flags; wait_until = io.wait_until;
         n_out = io.n_out; o_dest = io.o_dest; o1_type = io.o1_type; o1_a = io.o1_a; o1_b = io.o1_b; o_wlo = io.o_wlo;
@@ -1055,41 +1036,7 @@ __global__ void __launch_bounds__(64) D8_OCC dt8_kernel(const M8Params tp) {
 
       M8_MARK(5)
       M8_MARK2(6)
-      // ---- R4: the clients' recv! loops (client.clj:94-107) ----
-      if (__ballot(c_arr || (busy && (cin_n | csp_n) != 0))) {
-        for (;;) {
-          const bool stale = normal && busy && (cin_n | csp_n) != 0;
-          const bool fresh = normal && !stale && busy && c_arr;
-          if (!__ballot(stale || fresh)) break;
-          if (stale) {
-            u32 best = 0; bool in_spill = false;
-            uint2 bk = make_uint2(INF, INF);
-            for (u32 i = 0; i < cin_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cq[i * 64u]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-            }
-            for (u32 i = 0; i < csp_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cspill[i]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-            }
-            uint4 e;
-            if (in_spill) { e = my_cspill[best]; csp_n--; if (best != csp_n) my_cspill[best] = my_cspill[csp_n]; }
-            else { e = my_cq[best * 64u]; cin_n--; if (best != cin_n) my_cq[best * 64u] = my_cq[cin_n * 64u]; }
-            client_deliver(e.y & 0xFFu, e.z, e.w & 0xFFFFFFu);
-          } else if (fresh) {
-            c_arr = false;
-            client_deliver(ca_y & 0xFFu, ca_a, ca_b);
-          }
-        }
-        if (c_arr && normal) {  // nobody is in recv!: the envelope waits for the next RPC (and is skipped there as stale)
-          const uint4 e = make_uint4(T, ca_y, ca_a, ca_b | (l << 24));
-          if (cin_n < CQ) { my_cq[cin_n * 64u] = e; cin_n++; }
-          else if (csp_n < tp.client_spill) my_cspill[csp_n++] = e;
-          else my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-        }
-      }
-    }
-
+      #include "group8_clients.inc"
     M8_MARK(6)
     // ---- history rows: nemesis rows, invocations (lane order), completions (lane order) ----
     {

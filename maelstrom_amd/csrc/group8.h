@@ -1,5 +1,6 @@
-// group8.h — device helpers shared by the eight-clusters-per-wavefront kernels (hat8.hip, uid8.hip, crdt8.hip, bcast8.hip): the latency
-// sampler (latency_sampler.h), the minimum over the lanes of a group.
+// group8.h — device helpers shared by the eight-clusters-per-wavefront kernels (hat8.hip, uid8.hip, crdt8.hip, bcast8.hip, kafka8.hip,
+// txn8.hip, mk8.hip, dt8.hip): the latency sampler (latency_sampler.h), the minimum over the lanes of a group.  The round machinery they
+// share is in the body fragments group8_*.inc (docs/KERNELS.md §4.10 lists which kernel takes which).
 #ifndef MSIM_GROUP8_H
 #define MSIM_GROUP8_H
 #include "wave_common.h"

@@ -1,4 +1,4 @@
-// group8_clients.inc — body fragment shared by the eight-clusters-per-wavefront kernels, included after the COMMIT of the round: the
+// group8_clients.inc — body fragment shared by all eight eight-clusters-per-wavefront kernels, included after the COMMIT of the round: the
 // clients' recv! loops (client.clj:94-107) — queued (stale, older) envelopes first, then the fresh reply of this round; an envelope that
 // finds nobody in recv! waits in the client's inbox (CQ envelopes in LDS, up.client_spill more in HBM).  Uses the kernel's names:
 // c_arr, ca_y, ca_a, ca_b, busy, normal, cin_n, csp_n, my_cq, my_cspill, up, client_deliver, my_flags, T, l.

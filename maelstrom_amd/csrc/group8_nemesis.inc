@@ -1,4 +1,4 @@
-// group8_nemesis.inc — body fragment shared by the eight-clusters-per-wavefront kernels and the four-clusters-per-wavefront ones
+// group8_nemesis.inc — body fragment shared by the eight-clusters-per-wavefront kernels (all but dt8.hip, whose nemesis words live in LDS) and the four-clusters-per-wavefront ones
 // (raft4.hip, svc4.hip, txng4.hip, dtg4.hip), included in R1 (scheduler) of the round: the
 // partition nemesis' flip-flop (nemesis.clj:10-16 + [upstream] jepsen.nemesis.combined/partition-package: one / majority / majorities-ring /
 // minority-third grudges drawn per start, the shuffle done by lane 0 of the group in `misc`), its two history rows and the payload

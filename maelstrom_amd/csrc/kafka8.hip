@@ -110,9 +110,6 @@ __global__ void __launch_bounds__(64) kafka8_kernel(const K8Params up) {
   klen[l] = 0; nupd[l] = 0;   // (GS == KF_KEYS)
   __syncthreads();
 
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFu; };            // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
-
   // ---- node / service state ----
   u32 deliver_at = INF; uint4 cm = make_uint4(0, 0, 0, 0);
   bool have_pm = false; uint4 pm = make_uint4(0, 0, 0, 0);
@@ -128,57 +125,11 @@ __global__ void __launch_bounds__(64) kafka8_kernel(const K8Params up) {
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
 
-  auto q_push = [&](const uint4 m) {
-    if (in_n < RQ) { my_q[in_n * 64u] = m; in_n++; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  // an envelope for THIS lane's node/service arrives (net.clj:189-221)
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) {
-    u32 lat = 0;
-    if (src < N || src == SVC) {  // neither end is a client
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    q_push(m);
-  };
-  auto try_commit = [&](const uint4 e) {
-    const u32 src = e.w >> 24;
-    if (NEM && src < N && ((part >> src) & 1)) return;  // partitioned (node <-> node only; never happens in this program)
-    cm = e;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;  // (Thread/sleep (long dt)) net.clj:236-238
-  };
-  auto poll = [&]() {
-    if (have_pm) {
-      have_pm = false;
-      if (alive && deliver_at == INF && (in_n | sp_n) == 0) try_commit(pm);
-      else q_push(pm);
-    }
-    while (alive && l <= N && deliver_at == INF && (in_n | sp_n) != 0) {
-      u32 best = 0; bool in_spill = false;
-      uint2 bk = make_uint2(INF, INF);
-      for (u32 i = 0; i < in_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_q[i * 64u]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-      }
-      for (u32 i0 = 0; i0 < sp_n; i0 += 8) {   // (the service takes every RPC of the cluster: eight keys per round trip)
-        uint2 kq[8];
-#pragma unroll
-        for (u32 t = 0; t < 8; t++) kq[t] = *reinterpret_cast<const uint2 *>(&my_spill[min(i0 + t, sp_n - 1)]);
-#pragma unroll
-        for (u32 t = 0; t < 8; t++) if (i0 + t < sp_n && (kq[t].x < bk.x || (kq[t].x == bk.x && kq[t].y < bk.y))) { bk = kq[t]; best = i0 + t; in_spill = true; }
-      }
-      uint4 e;
-      if (in_spill) { e = my_spill[best]; sp_n--; if (best != sp_n) my_spill[best] = my_spill[sp_n]; }
-      else { e = my_q[best * 64u]; in_n--; if (best != in_n) my_q[best * 64u] = my_q[in_n * 64u]; }
-      try_commit(e);
-    }
-  };
+#define SERVER_SRC(src) ((src) < N || (src) == SVC)
+#define QUEUE_LANE (l <= N)
+  #include "group8_net.inc"
+#undef SERVER_SRC
+#undef QUEUE_LANE
   // lin-kv: elements of chunk `ch` of key `k` (0: the lin-kv key does not exist)
   auto chunk_count = [&](u32 k, u32 ch) -> u32 {
     const u32 lo = ch * KF_CHUNK, len = klen[k];
@@ -691,49 +642,19 @@ __global__ void __launch_bounds__(64) kafka8_kernel(const K8Params up) {
       K8_MARK(5)   // [5] = COMMIT + polls
       #include "group8_clients.inc"
     K8_MARK(6)   // [6] = R4 clients
-    // ---- history rows: nemesis rows, invocations (lane order), completions (lane order) ----
-    {
-      const u32 imask = GB(inv_row), cmask = GB(cmp_row);
-      const u32 ni = __popc(imask);
-      const u32 nr = nem_rows + ni + __popc(cmask);
-      if (__ballot(alive && nr != 0)) {
-        const bool ovf = alive && nr != 0 && n_rows + nr > max_rows;
-        if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = false; }
-        const bool wr = alive && nr != 0;
-        const u64 tns = (u64)T * 1000ull;
-        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-        uint4 *const out = reinterpret_cast<uint4 *>(g_rows) + n_rows;   // (no staging: a few 16-byte rows per round; the L2 merges them into lines)
-        if (NEM && wr && nem_rows && l == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          out[0] = make_uint4(tlo, thi, pk, nem_v1);
-          out[1] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (wr && inv_row) out[nem_rows + __popc(imask & lt)] = make_uint4(tlo, thi | (inv_len << 16), inv_packed, inv_value);
-        if (wr && cmp_row) out[nem_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        n_rows = wr ? n_rows + nr : n_rows;
-      }
-    }
+    #include "group8_rows.inc"
     K8_MARK(7)   // [7] = rows
   }
 
-  // ---- epilogue ----
-  u32 t_send_cl = 0, t_send_sv = 0, t_recv_cl = 0, t_recv_sv = 0;
-  for (u32 s = 0; s < GS; s++) { t_send_cl += GGET(s_send_cl, s); t_send_sv += GGET(s_send_sv, s); t_recv_cl += GGET(s_recv_cl, s); t_recv_sv += GGET(s_recv_sv, s); }
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (GB((my_flags & b) != 0)) flags |= b;
-  if (real && l == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
+  #include "group8_stats.inc"
 #ifdef K8_PROF
-    if (grp == 0) { st.all_send = kp[0]; st.all_recv = kp[1]; st.clients_send = kp[2]; st.clients_recv = kp[3]; st.servers_send = kp[4]; st.servers_recv = kp[5]; p.stats[inst] = st;
-                    m.reserved[0] = (u32)(kp[6] >> 6); m.reserved[1] = (u32)(kp[7] >> 6); m.n_events = kp_rounds; }
-#endif
-    p.meta[inst] = m;
+  if (real && l == 0 && grp == 0) {
+    msim_net_stats st;
+    st.all_send = kp[0]; st.all_recv = kp[1]; st.clients_send = kp[2]; st.clients_recv = kp[3]; st.servers_send = kp[4]; st.servers_recv = kp[5]; p.stats[inst] = st;
+    msim_inst_meta &m = p.meta[inst];
+    m.reserved[0] = (u32)(kp[6] >> 6); m.reserved[1] = (u32)(kp[7] >> 6); m.n_events = kp_rounds;
   }
+#endif
 }
 
 }  // namespace

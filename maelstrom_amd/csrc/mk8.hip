@@ -21,8 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
-#include "wave_common.h"
-#include "latency_sampler.h"
+#include "group8.h"
 
 namespace {
 
@@ -57,25 +56,17 @@ struct M8Params {
   u32 round_limit;
 };
 
-// min over the 8 lanes of the caller's group, in every lane of it
-__device__ __forceinline__ u32 m8_oct_min(u32 v) {
-  v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_mov<0x4E, 0xF, 0xF, false>(v, v));   // quad_perm [2,3,0,1]
-  v = min(v, dpp_mov<0x141, 0xF, 0xF, false>(v, v));  // row_half_mirror
-  return v;
-}
-
 template <bool NEM, bool NET_RANDOM>
-__global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
+__global__ void __launch_bounds__(64) mk8_kernel(const M8Params up) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const KParams &p = tp.k;
+  const KParams &p = up.k;
   const u32 lane = threadIdx.x, l = lane & (GS - 1u), grp = lane >> 3, gbase = lane & 56u;
   const u32 N = p.N;
   const bool is_node = l < N, is_lin = l == N;
   const u32 LIN = 2 * N;   // endpoint index of lin-kv (lane N of the group); lww-kv is LIN + 1 (lane N + 1)
   const u32 inst_raw = blockIdx.x * 8u + grp;
-  const bool real = inst_raw < tp.n_inst;
-  const u32 inst = real ? inst_raw : tp.n_inst - 1u;
+  const bool real = inst_raw < up.n_inst;
+  const u32 inst = real ? inst_raw : up.n_inst - 1u;
   const u64 key = mix64(p.cfg.seed + 0x9E3779B97F4A7C15ull * (p.first_instance + inst + 1));
   const u32 lt = (1u << l) - 1u;
   const u32 all_nodes = (1u << N) - 1u;
@@ -83,7 +74,7 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
   const u32 p_loss = p.cfg.p_loss_q32, lat_mean = p.cfg.latency_mean_ms, lat_dist = p.cfg.latency_dist;
   const u32 rate = p.cfg.rate_mhz, mw = p.cfg.max_writes_per_key, mw1 = mw + 1u, mv = p.cfg.max_values;
   const u32 TC = p.mk_tcap, CC = p.mk_ccap;   // thunks a node may create; slots of its thunk cache (a power of two)
-  const u32 round_limit = tp.round_limit;
+  const u32 round_limit = up.round_limit;
 
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -100,16 +91,16 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
   unsigned char *const g_rep = reinterpret_cast<unsigned char *>(g_cache + (size_t)N * CC);   // [N][TC] replica holding thunk <node>.<i>
   u32 *const xslots = g_cache + (size_t)N * CC + (((size_t)N * TC + 15u) / 16u) * 4u;         // [N][M8_SLOTS - M8_SL][82]: room for slots of 8 keys; used with MKW
   const u32 qlane = l <= N + 1u ? l : 0u;
-  uint4 *const my_spill = reinterpret_cast<uint4 *>(g_scr + p.spill_off) + (size_t)qlane * tp.node_spill;
-  uint4 *const my_cspill = reinterpret_cast<uint4 *>(g_scr + tp.client_spill_off) + (size_t)(is_node ? l : 0u) * tp.client_spill;
-  const u32 my_spill_cap = l <= N + 1u ? tp.node_spill : 0u;
+  uint4 *const my_spill = reinterpret_cast<uint4 *>(g_scr + p.spill_off) + (size_t)qlane * up.node_spill;
+  uint4 *const my_cspill = reinterpret_cast<uint4 *>(g_scr + up.client_spill_off) + (size_t)(is_node ? l : 0u) * up.client_spill;
+  const u32 my_spill_cap = l <= N + 1u ? up.node_spill : 0u;
 
   uint4 *const my_q = reinterpret_cast<uint4 *>(smem) + lane;                                   // node / service queue: slot s at my_q[s * 64]
-  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + tp.off_cq) + lane;                      // client inbox
-  u32 *const slots_g = reinterpret_cast<u32 *>(smem + tp.off_slots) + grp * (N * M8_SL * MKW);    // [node of the group][M8_SL][MKW]
-  u32 *const mout_g = reinterpret_cast<u32 *>(smem + tp.off_mout) + grp * (N * KEYS * 3u);        // [node of the group][KEYS][3]: what a node sends to a service this round {type, a, b}
-  u32 *const gen = reinterpret_cast<u32 *>(smem + tp.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
-  u32 *const misc = reinterpret_cast<u32 *>(smem + tp.off_misc) + grp * GS;
+  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + up.off_cq) + lane;                      // client inbox
+  u32 *const slots_g = reinterpret_cast<u32 *>(smem + up.off_slots) + grp * (N * M8_SL * MKW);    // [node of the group][M8_SL][MKW]
+  u32 *const mout_g = reinterpret_cast<u32 *>(smem + up.off_mout) + grp * (N * KEYS * 3u);        // [node of the group][KEYS][3]: what a node sends to a service this round {type, a, b}
+  u32 *const gen = reinterpret_cast<u32 *>(smem + up.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
+  u32 *const misc = reinterpret_cast<u32 *>(smem + up.off_misc) + grp * GS;
   // slot si of node nd: LDS for the first M8_SL, HBM scratch beyond (a generic pointer: flat loads / stores reach both)
   // (Every handler runs on one or the other through a lambda inlined at both call sites, so that the LDS slots — the ones in use nearly
   //  always — are read and written with ds_ instructions: through a generic pointer they cost flat accesses, which wait for every global
@@ -120,7 +111,7 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
   const u32 my_node = is_node ? l : 0u;
   u32 *const my_cache = g_cache + (size_t)my_node * CC;
 
-  for (u32 i = lane; i < 8 * N * M8_SL * MKW; i += 64) reinterpret_cast<u32 *>(smem + tp.off_slots)[i] = 0;
+  for (u32 i = lane; i < 8 * N * M8_SL * MKW; i += 64) reinterpret_cast<u32 *>(smem + up.off_slots)[i] = 0;
   if (real && is_node) for (u32 i = 0; i < M8_SLOTS - M8_SL; i++) xslots[((size_t)l * (M8_SLOTS - M8_SL) + i) * MKW + SK_HDR] = 0;
   for (u32 i = l; i < 16; i += GS) { gen[i] = i; gen[16 + i] = 1; }
   if (l == 0) gen[32] = p.cfg.key_count;
@@ -130,9 +121,6 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
     for (u32 i = l; i < N * TC / 4u; i += GS) reinterpret_cast<u32 *>(g_rep)[i] = 0xFFFFFFFFu;
   }
   __syncthreads();
-
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFu; };            // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
 
   // ---- node / service state ----
   u32 deliver_at = INF; uint4 cm = make_uint4(0, 0, 0, 0);
@@ -150,60 +138,11 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
 
-  auto q_push = [&](const uint4 m) __attribute__((always_inline)) {
-    if (in_n < RQ) { my_q[in_n * 64u] = m; in_n++; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  // an envelope for THIS lane's node/service arrives (net.clj:189-221)
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) __attribute__((always_inline)) {
-    u32 lat = 0;
-    if (src < N || src >= LIN) {  // neither end is a client
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    q_push(m);
-  };
-  auto try_commit = [&](const uint4 e) __attribute__((always_inline)) {
-    const u32 src = e.w >> 24;
-    if (NEM && src < N && ((part >> src) & 1)) return;  // partitioned (node <-> node only; never happens in this program)
-    cm = e;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;  // (Thread/sleep (long dt)) net.clj:236-238
-  };
-  auto poll = [&]() __attribute__((always_inline)) {
-    if (have_pm) {
-      have_pm = false;
-      if (alive && deliver_at == INF && (in_n | sp_n) == 0) try_commit(pm);
-      else q_push(pm);
-    }
-    while (alive && l <= N + 1u && deliver_at == INF && (in_n | sp_n) != 0) {
-      u32 best = 0; bool in_spill = false;
-      uint2 bk = make_uint2(INF, INF);
-      for (u32 i = 0; i < in_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_q[i * 64u]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-      }
-      for (u32 i0 = 0; i0 < sp_n; i0 += 8) {   // eight spilled keys per round trip
-        uint2 k8[8];
-#pragma unroll
-        for (u32 t = 0; t < 8; t++) k8[t] = *reinterpret_cast<const uint2 *>(&my_spill[min(i0 + t, sp_n - 1u)]);
-#pragma unroll
-        for (u32 t = 0; t < 8; t++) {
-          const uint2 kk = k8[t];
-          if (i0 + t < sp_n && (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y))) { bk = kk; best = i0 + t; in_spill = true; }
-        }
-      }
-      uint4 e;
-      if (in_spill) { e = my_spill[best]; sp_n--; if (best != sp_n) my_spill[best] = my_spill[sp_n]; }
-      else { e = my_q[best * 64u]; in_n--; if (best != in_n) my_q[best * 64u] = my_q[in_n * 64u]; }
-      try_commit(e);
-    }
-  };
+#define SERVER_SRC(src) ((src) < N || (src) >= LIN)
+#define QUEUE_LANE (l <= N + 1u)
+  #include "group8_net.inc"
+#undef SERVER_SRC
+#undef QUEUE_LANE
   // elements of `k` visible at version `from`: versions only grow along a key's row, so the answer is a count — the row is read with
   // independent loads (one round trip) instead of one dependent load per element
   auto visible = [&](u32 k, u32 from) __attribute__((always_inline)) -> u32 {
@@ -253,32 +192,8 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
     }
     if (alive && ++rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
 
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = all_nodes & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
-    bool timeout_round = false;
-    {
-      const bool none_due = GB(deliver_at <= T) == 0;
-      const bool jump = alive && due > T && none_due;
-      if (__ballot(jump)) {
-        u32 k = deliver_at == INF ? INF : deliver_at * 2;
-        if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = m8_oct_min(k);
-        if (due != INF) km = min(km, due * 2);
-        if (jump) {
-          if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-          else { timeout_round = (km & 1) != 0; T = max(T, km >> 1); }
-        }
-      }
-    }
+    #include "group8_time.inc"
+    #include "group8_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0, inv_len = 0;
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
@@ -313,62 +228,7 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
       if (__ballot(act && phase == PH_INIT)) {
         if (act && phase == PH_INIT) { if (is_node) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; }
       }
-      if (NEM) {
-        const bool nem_act = act && phase == PH_MAIN && nem_live && nem_next <= T;
-        if (__ballot(nem_act)) {   // flip-flop start/stop (nemesis.clj:10-16 + [upstream] partition package)
-          const u32 j = nem_j;
-          const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-          const bool start = nem_act && (j & 1) == 0;
-          if (nem_act) { nem_j++; nem_rows = 2; }
-          if (__ballot(start)) {
-            misc[l] = l;
-            wave_lds_fence();
-            if (start && l == 0 && spec != MSIM_SPEC_ONE) {
-              for (u32 i = N - 1; i >= 1; i--) {
-                const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-              }
-            }
-            wave_lds_fence();
-            u32 my_part = 0;
-            if (start && is_node) {
-              if (spec == MSIM_SPEC_ONE) {
-                const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                my_part = l == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-              } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                u32 comp = 0;
-                for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                my_part = ((comp >> l) & 1) ? (all_nodes & ~comp) : comp;
-              } else {
-                const u32 m = N / 2 + 1;
-                u32 pos = 0;
-                for (u32 i = 0; i < N; i++) if (misc[i] == l) pos = i;
-                const u32 i0 = (pos + N - (m / 2) % N) % N;
-                u32 vis = 0;
-                for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                my_part = all_nodes & ~vis;
-              }
-            }
-            if (start) {
-              part |= my_part;
-              const u32 words = N * MSIM_MASK_WORDS;
-              u32 off = 0;
-              if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-              else {
-                off = n_payload; n_payload += words;
-                if (is_node) { g_pay[off + l * 4] = part; g_pay[off + l * 4 + 1] = 0; g_pay[off + l * 4 + 2] = 0; g_pay[off + l * 4 + 3] = 0; }
-              }
-              nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-            }
-          }
-          if (nem_act && (j & 1) != 0) {
-            part = 0;
-            nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-          }
-          if (nem_act) nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-        }
-      }
+      #include "group8_nemesis.inc"
       {
         const bool gen_on = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
         if (__ballot(gen_on)) {
@@ -827,87 +687,21 @@ __global__ void __launch_bounds__(64) mk8_kernel(const M8Params tp) {
       }
 
       M8_MARK(5)
-      // ---- R4: the clients' recv! loops (client.clj:94-107) ----
-      if (__ballot(c_arr || (busy && (cin_n | csp_n) != 0))) {
-        for (;;) {
-          const bool stale = normal && busy && (cin_n | csp_n) != 0;
-          const bool fresh = normal && !stale && busy && c_arr;
-          if (!__ballot(stale || fresh)) break;
-          if (stale) {
-            u32 best = 0; bool in_spill = false;
-            uint2 bk = make_uint2(INF, INF);
-            for (u32 i = 0; i < cin_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cq[i * 64u]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-            }
-            for (u32 i = 0; i < csp_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cspill[i]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-            }
-            uint4 e;
-            if (in_spill) { e = my_cspill[best]; csp_n--; if (best != csp_n) my_cspill[best] = my_cspill[csp_n]; }
-            else { e = my_cq[best * 64u]; cin_n--; if (best != cin_n) my_cq[best * 64u] = my_cq[cin_n * 64u]; }
-            client_deliver(e.y & 0xFFu, e.z, e.w & 0xFFFFFFu);
-          } else if (fresh) {
-            c_arr = false;
-            client_deliver(ca_y & 0xFFu, ca_a, ca_b);
-          }
-        }
-        if (c_arr && normal) {  // nobody is in recv!: the envelope waits for the next RPC (and is skipped there as stale)
-          const uint4 e = make_uint4(T, ca_y, ca_a, ca_b | (l << 24));
-          if (cin_n < CQ) { my_cq[cin_n * 64u] = e; cin_n++; }
-          else if (csp_n < tp.client_spill) my_cspill[csp_n++] = e;
-          else my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-        }
-      }
-    }
-
+      #include "group8_clients.inc"
     M8_MARK(6)
-    // ---- history rows: nemesis rows, invocations (lane order), completions (lane order) ----
-    {
-      const u32 imask = GB(inv_row), cmask = GB(cmp_row);
-      const u32 ni = __popc(imask);
-      const u32 nr = nem_rows + ni + __popc(cmask);
-      if (__ballot(alive && nr != 0)) {
-        const bool ovf = alive && nr != 0 && n_rows + nr > max_rows;
-        if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = false; }
-        const bool wr = alive && nr != 0;
-        const u64 tns = (u64)T * 1000ull;
-        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-        uint4 *const out = reinterpret_cast<uint4 *>(g_rows) + n_rows;   // (no staging: a few 16-byte rows per round; the L2 merges them into lines)
-        if (NEM && wr && nem_rows && l == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          out[0] = make_uint4(tlo, thi, pk, nem_v1);
-          out[1] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (wr && inv_row) out[nem_rows + __popc(imask & lt)] = make_uint4(tlo, thi | (inv_len << 16), inv_packed, inv_value);
-        if (wr && cmp_row) out[nem_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        const u32 new_n = wr ? n_rows + nr : n_rows;
-        n_rows = new_n;
-      }
-    }
+    #include "group8_rows.inc"
     M8_MARK(7)
   }
 
-  // ---- epilogue ----
-  u32 t_send_cl = 0, t_send_sv = 0, t_recv_cl = 0, t_recv_sv = 0;
-  for (u32 s = 0; s < GS; s++) { t_send_cl += GGET(s_send_cl, s); t_send_sv += GGET(s_send_sv, s); t_recv_cl += GGET(s_recv_cl, s); t_recv_sv += GGET(s_recv_sv, s); }
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (GB((my_flags & b) != 0)) flags |= b;
-  if (real && l == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
-#ifdef M8_PROF
+  #include "group8_stats.inc"
+#ifdef M8_PROF   // developer build (tools/variant_lib.sh m8prof mk8.hip -DM8_PROF): cycle counters of the round's sections in the meta of the wavefront's first three clusters
+  if (real && l == 0 && grp <= 2) {
+    msim_inst_meta &m = p.meta[inst];
     if (grp == 0) { m.n_events = (u32)(pacc[0] >> 6); m.reserved[0] = (u32)(pacc[1] >> 6); m.reserved[1] = (u32)(pacc[2] >> 6); m.reserved[2] = (u32)(pacc[3] >> 6); }
     if (grp == 1) { m.n_events = (u32)(pacc[4] >> 6); m.reserved[0] = (u32)(pacc[5] >> 6); m.reserved[1] = (u32)(pacc[6] >> 6); m.reserved[2] = (u32)(pacc[7] >> 6); }
     if (grp == 2) { m.n_events = wave_rounds; }
-#endif
-    p.meta[inst] = m;
   }
+#endif
 }
 
 }  // namespace

@@ -22,8 +22,7 @@
 // with independent loads (versions only grow along a row: "visible at version v" is a count, not a search).
 #include <hip/hip_runtime.h>
 
-#include "wave_common.h"
-#include "latency_sampler.h"
+#include "group8.h"
 
 namespace {
 
@@ -48,32 +47,24 @@ struct T8Params {
   u32 round_limit;
 };
 
-// min over the 8 lanes of the caller's group, in every lane of it
-__device__ __forceinline__ u32 oct_min(u32 v) {
-  v = min(v, dpp_mov<0xB1, 0xF, 0xF, false>(v, v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_mov<0x4E, 0xF, 0xF, false>(v, v));   // quad_perm [2,3,0,1]
-  v = min(v, dpp_mov<0x141, 0xF, 0xF, false>(v, v));  // row_half_mirror
-  return v;
-}
-
 template <bool NEM, bool NET_RANDOM>
-__global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
+__global__ void __launch_bounds__(64) txn8_kernel(const T8Params up) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const KParams &p = tp.k;
+  const KParams &p = up.k;
   const u32 lane = threadIdx.x, l = lane & (GS - 1u), grp = lane >> 3, gbase = lane & 56u;
   const u32 N = p.N;
   const bool is_node = l < N, is_svc = l == N;
   const u32 SVC = 2 * N;   // the service's endpoint index
   const u32 inst_raw = blockIdx.x * 8u + grp;
-  const bool real = inst_raw < tp.n_inst;
-  const u32 inst = real ? inst_raw : tp.n_inst - 1u;
+  const bool real = inst_raw < up.n_inst;
+  const u32 inst = real ? inst_raw : up.n_inst - 1u;
   const u64 key = mix64(p.cfg.seed + 0x9E3779B97F4A7C15ull * (p.first_instance + inst + 1));
   const u32 lt = (1u << l) - 1u;
   const u32 all_nodes = (1u << N) - 1u;
   const u32 max_rows = p.cfg.max_rows, max_pay = p.cfg.max_payload_words;
   const u32 p_loss = p.cfg.p_loss_q32, lat_mean = p.cfg.latency_mean_ms, lat_dist = p.cfg.latency_dist;
   const u32 rate = p.cfg.rate_mhz, mw = p.cfg.max_writes_per_key;
-  const u32 round_limit = tp.round_limit;
+  const u32 round_limit = up.round_limit;
 
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -81,28 +72,25 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
   u32 *const g_kv = g_scr;                                           // [max_values][mw]: element | version << 8
   u32 *const g_kvn = g_scr + (size_t)p.cfg.max_values * mw;          // [max_values]
   const u32 qlane = l <= N ? l : 0u;
-  uint4 *const my_spill = reinterpret_cast<uint4 *>(g_scr + p.spill_off) + (size_t)qlane * tp.node_spill;
-  uint4 *const my_cspill = reinterpret_cast<uint4 *>(g_scr + tp.client_spill_off) + (size_t)(is_node ? l : 0u) * tp.client_spill;
-  const u32 my_spill_cap = l <= N ? tp.node_spill : 0u;
+  uint4 *const my_spill = reinterpret_cast<uint4 *>(g_scr + p.spill_off) + (size_t)qlane * up.node_spill;
+  uint4 *const my_cspill = reinterpret_cast<uint4 *>(g_scr + up.client_spill_off) + (size_t)(is_node ? l : 0u) * up.client_spill;
+  const u32 my_spill_cap = l <= N ? up.node_spill : 0u;
 
   uint4 *const my_q = reinterpret_cast<uint4 *>(smem) + lane;                                   // node / service queue: slot s at my_q[s * 64]
-  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + tp.off_cq) + lane;                      // client inbox
-  uint4 *const slots_g = reinterpret_cast<uint4 *>(smem + tp.off_slots) + grp * GS * SL;       // [lane of the group][SL] {client_msg, txn_ref, rpc_id, from | stage << 16 | used << 24}
-  uint4 *const xslots = reinterpret_cast<uint4 *>(g_scr + tp.xslots_off);                       // [node][T8_SLOTS - SL]
+  uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + up.off_cq) + lane;                      // client inbox
+  uint4 *const slots_g = reinterpret_cast<uint4 *>(smem + up.off_slots) + grp * GS * SL;       // [lane of the group][SL] {client_msg, txn_ref, rpc_id, from | stage << 16 | used << 24}
+  uint4 *const xslots = reinterpret_cast<uint4 *>(g_scr + up.xslots_off);                       // [node][T8_SLOTS - SL]
   // slot i of node nd (LDS for the first SL, HBM beyond: only reached while a node has more than SL transactions in flight)
 #define SLOT_PTR(nd_, i_) ((i_) < SL ? slots_g + (nd_) * SL + (i_) : xslots + (nd_) * (T8_SLOTS - SL) + ((i_) - SL))
-  u32 *const gen = reinterpret_cast<u32 *>(smem + tp.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
-  u32 *const misc = reinterpret_cast<u32 *>(smem + tp.off_misc) + grp * GS;
+  u32 *const gen = reinterpret_cast<u32 *>(smem + up.off_gen) + grp * 36;                       // active[16], next_val[16], next_key
+  u32 *const misc = reinterpret_cast<u32 *>(smem + up.off_misc) + grp * GS;
 
-  for (u32 i = lane; i < 8 * GS * SL; i += 64) reinterpret_cast<uint4 *>(smem + tp.off_slots)[i] = make_uint4(0, 0, 0, 0);
+  for (u32 i = lane; i < 8 * GS * SL; i += 64) reinterpret_cast<uint4 *>(smem + up.off_slots)[i] = make_uint4(0, 0, 0, 0);
   if (real && is_node) for (u32 i = 0; i < T8_SLOTS - SL; i++) xslots[l * (T8_SLOTS - SL) + i] = make_uint4(0, 0, 0, 0);
   for (u32 i = l; i < 16; i += GS) { gen[i] = i; gen[16 + i] = 1; }
   if (l == 0) gen[32] = p.cfg.key_count;
   if (real) for (u32 i = l; i < p.cfg.max_values; i += GS) g_kvn[i] = 0;
   __syncthreads();
-
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFu; };            // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
 
   // ---- node / service state ----
   u32 deliver_at = INF; uint4 cm = make_uint4(0, 0, 0, 0);
@@ -116,6 +104,14 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
   u32 T = 0, phase = PH_INIT, cutoff = 0, gen_next = 0, gen_k = 0, nem_next = 0, nem_j = 0;
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
+
+  // This kernel's own copy of group8_net.inc (GB, GGET, the queue, arrive, try_commit, poll): the shared text differs in the scan of the
+  // spill area, eight keys per round trip there, one key at a time here — and with it this kernel is slower where it matters.  Measured on
+  // an MI355X, median of five launches (max - min), this copy against the shared text: BASELINE configs[4] (5 nodes, rate 100, 30 s, 5 ms,
+  // partitions) x 32768 clusters 206.3 (0.6) against 211.6 (0.3) ms; 7 nodes with a service queue 41 deep x 16384 clusters 6.63 (0.07)
+  // against 5.75 (0.02) ms; histories identical (profiles/r26_txn8_ab.jsonl).  Queues that deep come with clients that time out.
+  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & 0xFFu; };            // the cluster's slice of a ballot
+  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
 
   auto q_push = [&](const uint4 m) {
     if (in_n < RQ) { my_q[in_n * 64u] = m; in_n++; return; }
@@ -244,32 +240,8 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
     }
     if (alive && ++rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
 
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = all_nodes & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
-    bool timeout_round = false;
-    {
-      const bool none_due = GB(deliver_at <= T) == 0;
-      const bool jump = alive && due > T && none_due;
-      if (__ballot(jump)) {
-        u32 k = deliver_at == INF ? INF : deliver_at * 2;
-        if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = oct_min(k);
-        if (due != INF) km = min(km, due * 2);
-        if (jump) {
-          if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-          else { timeout_round = (km & 1) != 0; T = max(T, km >> 1); }
-        }
-      }
-    }
+    #include "group8_time.inc"
+    #include "group8_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0, inv_len = 0;
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
@@ -304,62 +276,7 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
       if (__ballot(act && phase == PH_INIT)) {
         if (act && phase == PH_INIT) { if (is_node) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; }
       }
-      if (NEM) {
-        const bool nem_act = act && phase == PH_MAIN && nem_live && nem_next <= T;
-        if (__ballot(nem_act)) {   // flip-flop start/stop (nemesis.clj:10-16 + [upstream] partition package)
-          const u32 j = nem_j;
-          const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-          const bool start = nem_act && (j & 1) == 0;
-          if (nem_act) { nem_j++; nem_rows = 2; }
-          if (__ballot(start)) {
-            misc[l] = l;
-            wave_lds_fence();
-            if (start && l == 0 && spec != MSIM_SPEC_ONE) {
-              for (u32 i = N - 1; i >= 1; i--) {
-                const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-              }
-            }
-            wave_lds_fence();
-            u32 my_part = 0;
-            if (start && is_node) {
-              if (spec == MSIM_SPEC_ONE) {
-                const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                my_part = l == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-              } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                u32 comp = 0;
-                for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                my_part = ((comp >> l) & 1) ? (all_nodes & ~comp) : comp;
-              } else {
-                const u32 m = N / 2 + 1;
-                u32 pos = 0;
-                for (u32 i = 0; i < N; i++) if (misc[i] == l) pos = i;
-                const u32 i0 = (pos + N - (m / 2) % N) % N;
-                u32 vis = 0;
-                for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                my_part = all_nodes & ~vis;
-              }
-            }
-            if (start) {
-              part |= my_part;
-              const u32 words = N * MSIM_MASK_WORDS;
-              u32 off = 0;
-              if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-              else {
-                off = n_payload; n_payload += words;
-                if (is_node) { g_pay[off + l * 4] = part; g_pay[off + l * 4 + 1] = 0; g_pay[off + l * 4 + 2] = 0; g_pay[off + l * 4 + 3] = 0; }
-              }
-              nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-            }
-          }
-          if (nem_act && (j & 1) != 0) {
-            part = 0;
-            nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-          }
-          if (nem_act) nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-        }
-      }
+      #include "group8_nemesis.inc"
       {
         const bool gen_on = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
         if (__ballot(gen_on)) {
@@ -605,87 +522,21 @@ __global__ void __launch_bounds__(64) txn8_kernel(const T8Params tp) {
       }
 
       T8_MARK(5)
-      // ---- R4: the clients' recv! loops (client.clj:94-107) ----
-      if (__ballot(c_arr || (busy && (cin_n | csp_n) != 0))) {
-        for (;;) {
-          const bool stale = normal && busy && (cin_n | csp_n) != 0;
-          const bool fresh = normal && !stale && busy && c_arr;
-          if (!__ballot(stale || fresh)) break;
-          if (stale) {
-            u32 best = 0; bool in_spill = false;
-            uint2 bk = make_uint2(INF, INF);
-            for (u32 i = 0; i < cin_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cq[i * 64u]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-            }
-            for (u32 i = 0; i < csp_n; i++) {
-              const uint2 kk = *reinterpret_cast<const uint2 *>(&my_cspill[i]);
-              if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-            }
-            uint4 e;
-            if (in_spill) { e = my_cspill[best]; csp_n--; if (best != csp_n) my_cspill[best] = my_cspill[csp_n]; }
-            else { e = my_cq[best * 64u]; cin_n--; if (best != cin_n) my_cq[best * 64u] = my_cq[cin_n * 64u]; }
-            client_deliver(e.y & 0xFFu, e.z, e.w & 0xFFFFFFu);
-          } else if (fresh) {
-            c_arr = false;
-            client_deliver(ca_y & 0xFFu, ca_a, ca_b);
-          }
-        }
-        if (c_arr && normal) {  // nobody is in recv!: the envelope waits for the next RPC (and is skipped there as stale)
-          const uint4 e = make_uint4(T, ca_y, ca_a, ca_b | (l << 24));
-          if (cin_n < CQ) { my_cq[cin_n * 64u] = e; cin_n++; }
-          else if (csp_n < tp.client_spill) my_cspill[csp_n++] = e;
-          else my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-        }
-      }
-    }
-
+      #include "group8_clients.inc"
     T8_MARK(6)
-    // ---- history rows: nemesis rows, invocations (lane order), completions (lane order) ----
-    {
-      const u32 imask = GB(inv_row), cmask = GB(cmp_row);
-      const u32 ni = __popc(imask);
-      const u32 nr = nem_rows + ni + __popc(cmask);
-      if (__ballot(alive && nr != 0)) {
-        const bool ovf = alive && nr != 0 && n_rows + nr > max_rows;
-        if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = false; }
-        const bool wr = alive && nr != 0;
-        const u64 tns = (u64)T * 1000ull;
-        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-        uint4 *const out = reinterpret_cast<uint4 *>(g_rows) + n_rows;   // (no staging: a few 16-byte rows per round; the L2 merges them into lines)
-        if (NEM && wr && nem_rows && l == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          out[0] = make_uint4(tlo, thi, pk, nem_v1);
-          out[1] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (wr && inv_row) out[nem_rows + __popc(imask & lt)] = make_uint4(tlo, thi | (inv_len << 16), inv_packed, inv_value);
-        if (wr && cmp_row) out[nem_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        const u32 new_n = wr ? n_rows + nr : n_rows;
-        n_rows = new_n;
-      }
-    }
+    #include "group8_rows.inc"
     T8_MARK(7)
   }
 
-  // ---- epilogue ----
-  u32 t_send_cl = 0, t_send_sv = 0, t_recv_cl = 0, t_recv_sv = 0;
-  for (u32 s = 0; s < GS; s++) { t_send_cl += GGET(s_send_cl, s); t_send_sv += GGET(s_send_sv, s); t_recv_cl += GGET(s_recv_cl, s); t_recv_sv += GGET(s_recv_sv, s); }
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (GB((my_flags & b) != 0)) flags |= b;
-  if (real && l == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
+  #include "group8_stats.inc"
 #ifdef T8_PROF   // developer build (tools/variant_lib.sh t8prof txn8.hip -DT8_PROF): cycle counters of the round's sections in the meta of the wavefront's first three clusters
+  if (real && l == 0 && grp <= 2) {
+    msim_inst_meta &m = p.meta[inst];
     if (grp == 0) { m.n_events = (u32)(pacc[0] >> 6); m.reserved[0] = (u32)(pacc[1] >> 6); m.reserved[1] = (u32)(pacc[2] >> 6); m.reserved[2] = (u32)(pacc[3] >> 6); }
     if (grp == 1) { m.n_events = (u32)(pacc[4] >> 6); m.reserved[0] = (u32)(pacc[5] >> 6); m.reserved[1] = (u32)(pacc[6] >> 6); m.reserved[2] = (u32)(pacc[7] >> 6); }
     if (grp == 2) { m.n_events = wave_rounds; }
-#endif
-    p.meta[inst] = m;
   }
+#endif
 }
 
 }  // namespace

@@ -43,7 +43,7 @@ struct U8Params {
 template <bool FLAKE, bool NEM, bool NET_RANDOM>
 __global__ void __launch_bounds__(64) uid8_kernel(const U8Params up) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr u32 GM = (1u << GS) - 1u, NG = 64u / GS;
+  constexpr u32 NG = 64u / GS;
   const KParams &p = up.k;
   const u32 lane = threadIdx.x, l = lane & (GS - 1u), grp = lane / GS, gbase = lane & ~(GS - 1u);
   const u32 N = p.N;
@@ -71,9 +71,6 @@ __global__ void __launch_bounds__(64) uid8_kernel(const U8Params up) {
   uint4 *const my_cq = reinterpret_cast<uint4 *>(smem + up.off_cq) + lane;                      // client inbox
   u32 *const misc = reinterpret_cast<u32 *>(smem + up.off_misc) + grp * GS;
 
-  auto GB = [&](bool pred) -> u32 { return (u32)(__ballot(pred) >> gbase) & GM; };              // the cluster's slice of a ballot
-  auto GGET = [&](u32 v, u32 s) -> u32 { return (u32)__builtin_amdgcn_ds_bpermute((int)((gbase + s) << 2), (int)v); };   // v of lane s of my group
-
   // ---- node state ----
   u32 deliver_at = INF; uint4 cm = make_uint4(0, 0, 0, 0);
   bool have_pm = false; uint4 pm = make_uint4(0, 0, 0, 0);
@@ -88,7 +85,11 @@ __global__ void __launch_bounds__(64) uid8_kernel(const U8Params up) {
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   bool alive = real;
 
+#define SERVER_SRC(src) ((src) < N)
+#define QUEUE_LANE is_node
   #include "group8_net.inc"
+#undef SERVER_SRC
+#undef QUEUE_LANE
   for (;;) {
     if (!__ballot(alive)) break;
     const u32 busy_mask = GB(busy);
@@ -110,35 +111,11 @@ __global__ void __launch_bounds__(64) uid8_kernel(const U8Params up) {
     }
     if (alive && ++rounds > round_limit) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
 
-    // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u32 free_mask = all_nodes & ~busy_mask;
-    u32 due = INF;
-    if (phase == PH_INIT) due = T;
-    else if (phase == PH_MAIN) {
-      if (nem_live) due = max(nem_next, T);
-      if (gen_live && free_mask) due = min(due, max(gen_next, T));
-      if (rate == 0 && !nem_live) due = min(due, cutoff);
-    }
-    bool timeout_round = false;
-    {
-      const bool none_due = GB(deliver_at <= T) == 0;
-      const bool jump = alive && due > T && none_due;
-      if (__ballot(jump)) {
-        u32 k = deliver_at == INF ? INF : deliver_at * 2;
-        if (busy) k = min(k, timeout_at * 2 + 1);
-        u32 km = g8_min<8>(k);
-        if (due != INF) km = min(km, due * 2);
-        if (jump) {
-          if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; alive = false; }
-          else { timeout_round = (km & 1) != 0; T = max(T, km >> 1); }
-        }
-      }
-    }
+    #include "group8_time.inc"
+    #include "group8_jump.inc"
 
-    bool inv_row = false; u32 inv_packed = 0, inv_value = 0;
-    bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0;
+    bool inv_row = false; u32 inv_packed = 0, inv_value = 0; const u32 inv_len = 0;
+    bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0; const u32 cmp_len = 0;   // (rows without a length)
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
     auto complete = [&](u32 type, u32 err, u32 value) {
@@ -237,44 +214,10 @@ __global__ void __launch_bounds__(64) uid8_kernel(const U8Params up) {
       }
 
       #include "group8_clients.inc"
-    // ---- history rows: nemesis rows, invocations (lane order), completions (lane order) ----
-    {
-      const u32 imask = GB(inv_row), cmask = GB(cmp_row);
-      const u32 ni = __popc(imask);
-      const u32 nr = nem_rows + ni + __popc(cmask);
-      if (__ballot(alive && nr != 0)) {
-        const bool ovf = alive && nr != 0 && n_rows + nr > max_rows;
-        if (ovf) { flags |= MSIM_FLAG_ROWS_OVERFLOW; alive = false; }
-        const bool wr = alive && nr != 0;
-        const u64 tns = (u64)T * 1000ull;
-        const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-        uint4 *const out = reinterpret_cast<uint4 *>(g_rows) + n_rows;   // (no staging: a few 16-byte rows per round; the L2 merges them into lines)
-        if (NEM && wr && nem_rows && l == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          out[0] = make_uint4(tlo, thi, pk, nem_v1);
-          out[1] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (wr && inv_row) out[nem_rows + __popc(imask & lt)] = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (wr && cmp_row) out[nem_rows + ni + __popc(cmask & lt)] = make_uint4(tlo, thi, cmp_packed, cmp_value);
-        n_rows = wr ? n_rows + nr : n_rows;
-      }
-    }
+    #include "group8_rows.inc"
   }
 
-  // ---- epilogue ----
-  u32 t_send_cl = 0, t_send_sv = 0, t_recv_cl = 0, t_recv_sv = 0;
-  for (u32 s = 0; s < GS; s++) { t_send_cl += GGET(s_send_cl, s); t_send_sv += GGET(s_send_sv, s); t_recv_cl += GGET(s_recv_cl, s); t_recv_sv += GGET(s_recv_sv, s); }
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (GB((my_flags & b) != 0)) flags |= b;
-  if (real && l == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
-    p.meta[inst] = m;
-  }
+  #include "group8_stats.inc"
 }
 
 

@@ -25,6 +25,7 @@ CASES = [
     "{'workload':'broadcast','node_count':36,'rate':20,'time_limit':3,'latency':10,'topology':'tree3','n':1}",
     "{'workload':'txn-list-append','bin':'multi-key-txn','node_count':5,'rate':60,'time_limit':5,'latency':5,'nemesis':['partition'],'nemesis_interval':2,'n':9}",
     "{'workload':'txn-list-append','node_count':5,'rate':60,'time_limit':5,'latency':5,'nemesis':['partition'],'nemesis_interval':2,'n':9}",
+    "{'workload':'txn-list-append','node_count':7,'rate':2000,'time_limit':2,'latency':150,'client_timeout_ms':100,'n':9}",   # clients give up: the lin-kv queue's spill area reaches 38 entries
     "{'workload':'txn-list-append','bin':'datomic','node_count':5,'rate':60,'time_limit':5,'latency':5,'nemesis':['partition'],'nemesis_interval':2,'n':3,'journal_capacity':100000}",   # (journal on: one cluster per wavefront)
     "{'workload':'txn-list-append','bin':'datomic','node_count':3,'rate':150,'time_limit':6,'latency':0,'key_count':16,'max_writes_per_key':2,'n':2}",   # ~600 keys: splits at every level, chains; one cluster per wavefront
     "{'workload':'txn-list-append','bin':'datomic','node_count':3,'rate':150,'time_limit':6,'latency':0,'key_count':16,'max_writes_per_key':2,'n':3,'flags':0x400}",   # the same, eight per wavefront (dt8.hip)

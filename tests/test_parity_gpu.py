@@ -505,6 +505,17 @@ def test_txn_list_append_parity(lib, kw):
     _compare(cfg, 0, 6)
 
 
+def test_txn_list_append_deep_service_queue_parity(lib):
+    """A lin-kv service queue far deeper than txn8_kernel<>'s LDS slots plus eight spilled envelopes (RQ + 8 = 11): 7 nodes
+    (the layout's maximum), a latency of 150 ms against a client timeout of 100 ms, so that clients give up and every node holds up to 6 of
+    its 8 transactions in flight, 2 simulated seconds.  Observed on the emulator (a print of sp_n, not kept): the service's spill area
+    reaches 38 entries (a scan that reads eight keys per trip, as csrc/group8_net.inc does, takes five trips there and clamps a partial batch).
+    Both layouts: eight clusters per wavefront (9 clusters: a full wavefront and a partial one) and one cluster per wavefront."""
+    cfg = E.test_config("txn-list-append", node_count=7, rate=2000, time_limit=2, latency=150, client_timeout_ms=100, seed=7)
+    _compare(cfg, 0, 9)
+    _compare(cfg, 0, 4, dev_flags=0x200)
+
+
 def test_txn_list_append_journal_parity(lib):
     cfg = E.test_config("txn-list-append", node_count=5, rate=50, time_limit=6, latency=5, nemesis=["partition"], nemesis_interval=2,
                         seed=62, journal_capacity=40000)
