@@ -932,55 +932,7 @@ __global__ void __launch_bounds__(64, COLO_MIN_WAVES) sim_kernel_colo(const KPar
           case PH_INIT: if (is_node) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; break;
           case PH_TOPO: if (is_node) { mark = true; kind = K_TOPO; } phase = PH_TOPO_WAIT; break;
           case PH_MAIN: {
-            if (NEM && nem_live && nem_next <= T) {
-              const u32 j = nem_j++;
-              nem_rows = 2;
-              if ((j & 1) == 0) {
-                const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-                if (lane < N) misc[lane] = lane;
-                __syncthreads();
-                if (lane == 0 && spec != MSIM_SPEC_ONE) {
-                  for (u32 i = N - 1; i >= 1; i--) {
-                    const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                    const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-                  }
-                }
-                __syncthreads();
-                u32 my_part = 0;
-                if (is_node) {
-                  if (spec == MSIM_SPEC_ONE) {
-                    const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                    my_part = lane == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-                  } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                    const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                    u32 comp = 0;
-                    for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                    my_part = ((comp >> lane) & 1) ? (all_nodes & ~comp) : comp;
-                  } else {
-                    const u32 m = N / 2 + 1;
-                    u32 pos = 0;
-                    for (u32 i = 0; i < N; i++) if (misc[i] == lane) pos = i;
-                    const u32 i0 = (pos + N - (m / 2) % N) % N;
-                    u32 vis = 0;
-                    for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                    my_part = all_nodes & ~vis;
-                  }
-                }
-                part |= my_part;
-                const u32 words = N * MSIM_MASK_WORDS;
-                u32 off = 0;
-                if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-                else {
-                  off = n_payload; n_payload += words;
-                  if (is_node) { g_pay[off + lane * 4] = part; g_pay[off + lane * 4 + 1] = 0; g_pay[off + lane * 4 + 2] = 0; g_pay[off + lane * 4 + 3] = 0; }
-                }
-                nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-              } else {
-                part = 0;
-                nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-              }
-              nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-            }
+            #include "group64_nemesis.inc"
             if (gen_live && gen_next <= T && free_mask) {
               const u32 nfree = __popc(free_mask);
               const u32 kk = gen_k++;

@@ -104,39 +104,10 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
   u32 sleep_until = 0, loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   u32 n_ev = 0, ev_base = 0, id_base = 0;  // journal cursor; :send events of a COMMIT sit at ev_base + (id - id_base)
 
-  // one journal event (event :id = idx); y = (message id << 8) | body type
-  auto jwrite = [&](u32 idx, u32 recv, u32 y, u32 a, u32 b, u32 src, u32 dest) {
-    if (idx < jcap) g_ev[idx] = make_uint4(T, (y & ~0x80u) | (recv << 7), a, src | (dest << 8) | ((b & 0xFFFFu) << 16));
-    else my_flags |= MSIM_FLAG_JOURNAL_OVERFLOW;
-  };
-  // queue an envelope in this lane's LDS inbox
-  auto lds_push = [&](const uint4 m) {
-    if (in_n < my_cap) { my_inbox[in_n++] = m; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  // a message addressed to this lane arrives (net.clj:189-221: latency, loss, enqueue)
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) {
-    u32 lat = 0;
-    if (src < N && is_node) {  // latency only between servers (net.clj:178-187)
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (jcap) jwrite(ev_base + (id - id_base), 0, (id << 8) | type, a, b, src, lane);  // journal :send precedes the loss decision (net.clj:208)
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;  // net.clj:214
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    lds_push(m);
-  };
-  // commit an envelope to this receiver: partition check at poll time (net.clj:234), sleep floor(dt) ms (:236-238)
-  auto try_commit = [&](const uint4 e) {
-    const u32 src = e.w >> 24;
-    if (NEM && is_node && src < N && ((part >> src) & 1)) return;  // dropped, no :recv
-    cm = e; has_c = true;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;
-  };
+#define PAYS_LATENCY(src) ((src) < N && is_node)   // neither end is a client (group64_net.inc)
+#define ENDPOINT_LANES   // a lane is one endpoint: node, worker slot or service
+#define COMMIT_FLAG   // has_c says whether an envelope is committed
+  #include "group64_net.inc"
   // idle receivers poll (net.clj:223-247): min (deadline, id) over queued + just-arrived envelopes
   auto poll = [&]() {
     const bool elig = is_node || busy;  // clients only poll inside recv! (client.clj:94-95)
@@ -232,18 +203,10 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
     }
     u32 my_t = has_c ? deliver_at : INF;  // this lane's next "normal" event
     if (HAS_TIMERS && is_node) my_t = min(my_t, min(timer_next, retry_time));
-    bool timeout_round = false;
-    if (due > T && !__ballot(my_t <= T)) {  // nothing due now: jump to the next event
-      u32 k = my_t == INF ? INF : my_t * 2;
-      if (busy) k = min(k, timeout_at * 2 + 1);
-      u32 km = wave_min(k);
-      if (due != INF) km = min(km, due * 2);
-      if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; break; }  // stuck
-      timeout_round = (km & 1) != 0;
-      T = max(T, km >> 1);
-    }
+    #include "group64_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0;               // invoke row of this round
+    const u32 inv_len = 0;   // an invocation carries no length (group64_rows.inc)
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;  // completion row of this round
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
@@ -271,56 +234,7 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
           case PH_INIT: if (is_client && slot < N) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; break;
           case PH_TOPO: if (is_client && slot < N) { mark = true; kind = K_TOPO; } phase = PH_TOPO_WAIT; break;
           case PH_MAIN: {
-            if (NEM && nem_live && nem_next <= T) {
-              const u32 j = nem_j++;
-              nem_rows = 2;
-              if ((j & 1) == 0) {  // :start-partition (jepsen.nemesis.combined partition-package, restated)
-                const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-                // shuffle (Fisher-Yates) in LDS by lane 0; every node lane then derives its own grudge row
-                if (lane < N) misc[lane] = lane;
-                __syncthreads();
-                if (lane == 0 && spec != MSIM_SPEC_ONE) {
-                  for (u32 i = N - 1; i >= 1; i--) {
-                    const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                    const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-                  }
-                }
-                __syncthreads();
-                u32 my_part = 0;
-                if (is_node) {
-                  if (spec == MSIM_SPEC_ONE) {
-                    const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                    my_part = lane == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-                  } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                    const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                    u32 comp = 0;
-                    for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                    my_part = ((comp >> lane) & 1) ? (all_nodes & ~comp) : comp;
-                  } else {  // majorities-ring
-                    const u32 m = N / 2 + 1;
-                    u32 pos = 0;
-                    for (u32 i = 0; i < N; i++) if (misc[i] == lane) pos = i;
-                    const u32 i0 = (pos + N - (m / 2) % N) % N;
-                    u32 vis = 0;
-                    for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                    my_part = all_nodes & ~vis;
-                  }
-                }
-                part |= my_part;
-                const u32 words = N * MSIM_MASK_WORDS;
-                u32 off = 0;
-                if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-                else {
-                  off = n_payload; n_payload += words;
-                  if (is_node) { g_pay[off + lane * 4] = part; g_pay[off + lane * 4 + 1] = 0; g_pay[off + lane * 4 + 2] = 0; g_pay[off + lane * 4 + 3] = 0; }
-                }
-                nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-              } else {  // :stop-partition -> heal! (net.clj:112-113)
-                part = 0;
-                nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-              }
-              nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-            }
+            #include "group64_nemesis.inc"
             if (gen_live && gen_next <= T && free_mask) {
               // one 64-bit draw per generated op: high word -> stagger, low word -> pick / mix / echo payload
               const u32 nfree = __popcll(free_mask);
@@ -621,33 +535,7 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
       }
     }
 
-    // ---- history rows: canonical order = nemesis rows, invokes (slot order), completions (slot order) ----
-    {
-      const u64 imask = __ballot(inv_row), cmask = __ballot(cmp_row);
-      const u32 ni = (u32)__popcll(imask);
-      const u32 nr = nem_rows + ni + (u32)__popcll(cmask);
-      if (nr) {
-        if (n_rows + nr > max_rows) { flags |= MSIM_FLAG_ROWS_OVERFLOW; break; }
-        const u32 tlo = (u32)((u64)T * 1000ull), thi = (u32)(((u64)T * 1000ull) >> 32);
-        if (NEM && nem_rows && lane == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          stage[n_rows % STAGE_ROWS] = make_uint4(tlo, thi, pk, nem_v1);
-          stage[(n_rows + 1) % STAGE_ROWS] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (inv_row) stage[(n_rows + nem_rows + (u32)__popcll(imask & lt_mask)) % STAGE_ROWS] = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row) stage[(n_rows + nem_rows + ni + (u32)__popcll(cmask & lt_mask)) % STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        const u32 new_n = n_rows + nr;
-        if ((new_n >> 6) != (n_rows >> 6)) {  // a 64-row block completed: coalesced 1 KiB append to HBM
-          __syncthreads();
-          for (u32 blk = n_rows >> 6; blk < (new_n >> 6); blk++) {
-            const u32 gi = blk * 64 + lane;
-            if (gi < max_rows) reinterpret_cast<uint4 *>(g_rows)[gi] = stage[gi % STAGE_ROWS];
-          }
-          __syncthreads();
-        }
-        n_rows = new_n;
-      }
-    }
+    #include "group64_rows.inc"
 
     // ---- cascade loop: while the scheduler is quiet at T and only plain gossip is due, every round is
     //      R3 + COMMIT + poll (no scheduler, no clients, no rows).  Same rounds the loop above would run. ----
@@ -727,3 +615,4 @@ __global__ void __launch_bounds__(64, 3) sim_kernel(const KParams p) {   // (thr
     p.meta[inst] = m;
   }
 }
+#include "group64_end.inc"

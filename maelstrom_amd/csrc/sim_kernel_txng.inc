@@ -68,60 +68,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
   u32 loss_on = 0, next_id = 0, n_rows = 0, n_payload = 0, flags = 0, rounds = 0;
   u32 n_ev = 0, ev_base = 0, id_base = 0;
 
-  auto jwrite = [&](u32 idx, u32 recv, u32 y, u32 a, u32 b, u32 src, u32 dest) {
-    if (idx < jcap) g_ev[idx] = make_uint4(T, (y & ~0x80u) | (recv << 7), a, src | (dest << 8) | ((b & 0xFFFFu) << 16));
-    else my_flags |= MSIM_FLAG_JOURNAL_OVERFLOW;
-  };
-  auto lds_push = [&](const uint4 m) {
-    if (in_n < my_cap) { my_inbox[in_n++] = m; return; }
-    if (sp_n < my_spill_cap) { my_spill[sp_n++] = m; return; }
-    my_flags |= MSIM_FLAG_INBOX_OVERFLOW;
-  };
-  // an envelope for THIS lane's endpoint arrives (net.clj:189-221)
-  auto arrive = [&](u32 id, u32 type, u32 a, u32 b, u32 src) {
-    u32 lat = 0;
-    if ((src < N || src >= LIN) && is_server) {  // neither end is a client (util.clj:7-16)
-      if (!NET_RANDOM || lat_dist == MSIM_LAT_CONSTANT) lat = lat_mean;
-      else if (lat_dist == MSIM_LAT_UNIFORM) lat = scale32(draw32(key, S_LATENCY, id), 2 * lat_mean);
-      else lat = (u32)(((u64)lat_mean * neg_ln_q16(draw32(key, S_LATENCY, id))) >> 16);
-    }
-    if (jcap) jwrite(ev_base + (id - id_base), 0, (id << 8) | type, a, b, src, lane);  // :send precedes the loss decision
-    if (NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss) return;
-    uint4 m = make_uint4(T + lat * 1000u, (id << 8) | type, a, b | (src << 24));
-    if (!have_pm) { pm = m; have_pm = true; return; }
-    if (m.x < pm.x || (m.x == pm.x && m.y < pm.y)) { const uint4 t = m; m = pm; pm = t; }
-    lds_push(m);
-  };
-  auto try_commit = [&](const uint4 e) {
-    const u32 src = e.w >> 24;
-    if (NEM && is_node && src < N && ((part >> src) & 1)) return;  // partitioned (node <-> node only; never happens in this program)
-    cm = e; has_c = true;
-    deliver_at = e.x <= T ? T : T + ((e.x - T) / 1000u) * 1000u;  // (Thread/sleep (long dt)) net.clj:236-238
-  };
-  auto poll = [&]() {
-    const bool elig = is_server || busy;   // clients are in recv! only while an RPC is outstanding (client.clj:94-95)
-    if (have_pm) {
-      have_pm = false;
-      if (elig && !has_c && (in_n | sp_n) == 0) try_commit(pm);
-      else lds_push(pm);
-    }
-    while (elig && !has_c && (in_n | sp_n) != 0) {
-      u32 best = 0; bool in_spill = false;
-      uint2 bk = make_uint2(INF, INF);
-      for (u32 i = 0; i < in_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_inbox[i]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; }
-      }
-      for (u32 i = 0; i < sp_n; i++) {
-        const uint2 kk = *reinterpret_cast<const uint2 *>(&my_spill[i]);
-        if (kk.x < bk.x || (kk.x == bk.x && kk.y < bk.y)) { bk = kk; best = i; in_spill = true; }
-      }
-      uint4 e;
-      if (in_spill) { e = my_spill[best]; sp_n--; if (best != sp_n) my_spill[best] = my_spill[sp_n]; }
-      else { e = my_inbox[best]; in_n--; if (best != in_n) my_inbox[best] = my_inbox[in_n]; }
-      try_commit(e);
-    }
-  };
+#define PAYS_LATENCY(src) (((src) < N || (src) >= LIN) && is_server)   // neither end is a client (group64_net.inc)
+#define ENDPOINT_LANES   // a lane is one endpoint: node, worker slot or service
+#define COMMIT_FLAG   // has_c says whether an envelope is committed
+#define POLL_LANE (is_server || busy)   // the lanes that take from their queue (group64_poll.inc)
+  #include "group64_net.inc"
+  #include "group64_poll.inc"
   auto visible = [&](u32 k, u32 from) -> u32 {
     if (from == V_NIL) return 0u;
     const u32 cnt = g_kvn[k];
@@ -131,56 +83,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
   };
 
   for (;;) {
-    const u64 busy_mask = __ballot(busy);
-
-    // ---- time-free phase transitions ----
-    if (!(phase == PH_MAIN && ((rate > 0 && gen_next < cutoff) || (NEM && nem_next < cutoff)))) {
-      for (bool again = true; again;) {
-        again = false;
-        switch (phase) {
-          case PH_INIT_WAIT: if (!busy_mask) { phase = PH_MAIN_START; again = true; } break;
-          case PH_MAIN_START:
-            cutoff = T + p.cfg.time_limit_ms * 1000u; gen_next = T; nem_next = T;
-            next_msg_id = 0; loss_on = 1; phase = PH_MAIN; again = true; break;
-          case PH_MAIN: {
-            const bool gl = rate > 0 && gen_next < cutoff, nl = NEM && nem_next < cutoff;
-            if (gl || nl) break;
-            if (rate == 0 && T < cutoff) break;
-            phase = PH_DRAIN; again = true;
-          } break;
-          case PH_DRAIN: if (!(busy_mask & worker_mask)) { phase = PH_DONE; again = true; } break;  // no final phase (txn_list_append.clj:142)
-          default: break;
-        }
-      }
-      if (phase == PH_DONE) break;
-    }
-    if (++rounds > ROUND_LIMIT) { flags |= MSIM_FLAG_ROUND_LIMIT; break; }
+    #include "group64_phase.inc"
 
     // ---- R0: time ----
-    const bool gen_live = rate > 0 && gen_next < cutoff;
-    const bool nem_live = NEM && nem_next < cutoff;
-    const u64 free_mask = worker_mask & ~busy_mask;
-    u32 due = INF;
-    switch (phase) {
-      case PH_INIT: due = T; break;
-      case PH_MAIN:
-        if (nem_live) due = max(nem_next, T);
-        if (gen_live && free_mask) due = min(due, max(gen_next, T));
-        if (rate == 0 && !nem_live) due = min(due, cutoff);
-        break;
-      default: break;
-    }
-    const u32 my_t = has_c ? deliver_at : INF;
-    bool timeout_round = false;
-    if (due > T && !__ballot(my_t <= T)) {
-      u32 k = my_t == INF ? INF : my_t * 2;
-      if (busy) k = min(k, timeout_at * 2 + 1);
-      u32 km = wave_min(k);
-      if (due != INF) km = min(km, due * 2);
-      if (km == INF) { flags |= MSIM_FLAG_ROUND_LIMIT; break; }
-      timeout_round = (km & 1) != 0;
-      T = max(T, km >> 1);
-    }
+    #include "group64_time.inc"
+    #include "group64_jump.inc"
 
     bool inv_row = false; u32 inv_packed = 0, inv_value = 0, inv_len = 0;
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
@@ -202,55 +109,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
         switch (phase) {
           case PH_INIT: if (is_client && slot < N) { mark = true; kind = K_INIT; } phase = PH_INIT_WAIT; break;
           case PH_MAIN: {
-            if (NEM && nem_live && nem_next <= T) {  // flip-flop start/stop (nemesis.clj:10-16 + [upstream] partition package)
-              const u32 j = nem_j++;
-              nem_rows = 2;
-              if ((j & 1) == 0) {
-                const u32 spec = scale32(draw32(key, S_NEM_SPEC, j), 4);
-                if (lane < N) misc[lane] = lane;
-                __syncthreads();
-                if (lane == 0 && spec != MSIM_SPEC_ONE) {
-                  for (u32 i = N - 1; i >= 1; i--) {
-                    const u32 kk = scale32(draw32(key, S_NEM_SHUFFLE, ((u64)j << 16) | i), i + 1);
-                    const u32 t = misc[i]; misc[i] = misc[kk]; misc[kk] = t;
-                  }
-                }
-                __syncthreads();
-                u32 my_part = 0;
-                if (is_node) {
-                  if (spec == MSIM_SPEC_ONE) {
-                    const u32 loner = scale32(draw32(key, S_NEM_PICK, j), N);
-                    my_part = lane == loner ? (all_nodes & ~(1u << loner)) : (1u << loner);
-                  } else if (spec == MSIM_SPEC_MAJORITY || spec == MSIM_SPEC_MINORITY_THIRD) {
-                    const u32 cnt = spec == MSIM_SPEC_MAJORITY ? N / 2 : (N - 1) / 3;
-                    u32 comp = 0;
-                    for (u32 i = 0; i < cnt; i++) comp |= 1u << misc[i];
-                    my_part = ((comp >> lane) & 1) ? (all_nodes & ~comp) : comp;
-                  } else {
-                    const u32 m = N / 2 + 1;
-                    u32 pos = 0;
-                    for (u32 i = 0; i < N; i++) if (misc[i] == lane) pos = i;
-                    const u32 i0 = (pos + N - (m / 2) % N) % N;
-                    u32 vis = 0;
-                    for (u32 kk = 0; kk < m; kk++) vis |= 1u << misc[(i0 + kk) % N];
-                    my_part = all_nodes & ~vis;
-                  }
-                }
-                part |= my_part;
-                const u32 words = N * MSIM_MASK_WORDS;
-                u32 off = 0;
-                if (n_payload + words > max_pay) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-                else {
-                  off = n_payload; n_payload += words;
-                  if (is_node) { g_pay[off + lane * 4] = part; g_pay[off + lane * 4 + 1] = 0; g_pay[off + lane * 4 + 2] = 0; g_pay[off + lane * 4 + 3] = 0; }
-                }
-                nem_f = MSIM_F_START_PARTITION; nem_v1 = spec; nem_v2 = off; nem_len2 = words;
-              } else {
-                part = 0;
-                nem_f = MSIM_F_STOP_PARTITION; nem_v1 = MSIM_NO_VALUE; nem_v2 = MSIM_NO_VALUE; nem_len2 = 0;
-              }
-              nem_next = T + __umulhi(draw32(key, S_NEM_STAGGER, j), p.nem_period2_us);
-            }
+            #include "group64_nemesis.inc"
             if (gen_live && gen_next <= T && free_mask) {
               const u32 nfree = (u32)__popcll(free_mask);
               const u32 kk = gen_k++;
@@ -259,29 +118,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
               const u32 pick = scale32(r_lo, nfree);
               const bool sel = is_worker && !busy && (u32)__popcll(free_mask & lt_mask) == pick;
               // the transaction ([upstream] elle list-append gen): lane 0 writes the micro-ops and owns the key pool
-              const u32 n_mops = 1 + scale32((u32)(draw64(key, S_GEN2, kk) >> 32), p.cfg.max_txn_length);
-              u32 bad = 0;
-              if (n_payload + n_mops > max_pay) bad = MSIM_FLAG_PAYLOAD_OVERFLOW;
-              else if (lane == 0) {
-                const u32 kc = p.cfg.key_count;
-                for (u32 j = 0; j < n_mops; j++) {
-                  const u64 h3 = draw64(key, S_GEN3, (u64)kk * 8 + j);
-                  const u32 x = scale32((u32)(h3 >> 32), (1u << kc) - 1) + 1;
-                  const u32 ki = 31 - (u32)__clz((int)x);
-                  const u32 k = gen[ki];
-                  if (h3 & 1) {
-                    const u32 v = gen[16 + ki];
-                    gen[16 + ki] = v + 1;
-                    g_pay[n_payload + j] = 1u | (k << 1) | (v << 16);
-                    if (v + 1 > mw) {
-                      const u32 nk = gen[32];
-                      if (nk >= p.cfg.max_values) { bad = MSIM_FLAG_VALUES_OVERFLOW; break; }
-                      gen[ki] = nk; gen[32] = nk + 1; gen[16 + ki] = 1;
-                    }
-                  } else g_pay[n_payload + j] = (k << 1) | (0xFFu << 16);
-                }
-              }
-              bad = rdlane(bad, 0);
+              #include "group64_txn_gen.inc"
               if (bad) { flags |= bad; phase = PH_DONE; break; }
               if (sel) { mark = true; kind = K_OP; m_value = n_payload | (n_mops << 24); }
               n_payload += n_mops;
@@ -472,53 +309,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
       }
     }
 
-    // ---- history rows ----
-    {
-      const u64 imask = __ballot(inv_row), cmask = __ballot(cmp_row);
-      const u32 ni = (u32)__popcll(imask);
-      const u32 nr = nem_rows + ni + (u32)__popcll(cmask);
-      if (nr) {
-        if (n_rows + nr > max_rows) { flags |= MSIM_FLAG_ROWS_OVERFLOW; break; }
-        const u32 tlo = (u32)((u64)T * 1000ull), thi = (u32)(((u64)T * 1000ull) >> 32);
-        if (NEM && nem_rows && lane == 0) {
-          const u32 pk = MSIM_T_INFO | (nem_f << 2) | (MSIM_PROCESS_NEMESIS << 12);
-          stage[n_rows % STAGE_ROWS] = make_uint4(tlo, thi, pk, nem_v1);
-          stage[(n_rows + 1) % STAGE_ROWS] = make_uint4(tlo, thi | (nem_len2 << 16), pk, nem_v2);
-        }
-        if (inv_row) stage[(n_rows + nem_rows + (u32)__popcll(imask & lt_mask)) % STAGE_ROWS] = make_uint4(tlo, thi | (inv_len << 16), inv_packed, inv_value);
-        if (cmp_row) stage[(n_rows + nem_rows + ni + (u32)__popcll(cmask & lt_mask)) % STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-        const u32 new_n = n_rows + nr;
-        if ((new_n >> 6) != (n_rows >> 6)) {
-          __syncthreads();
-          for (u32 blk = n_rows >> 6; blk < (new_n >> 6); blk++) {
-            const u32 gi = blk * 64 + lane;
-            if (gi < max_rows) reinterpret_cast<uint4 *>(g_rows)[gi] = stage[gi % STAGE_ROWS];
-          }
-          __syncthreads();
-        }
-        n_rows = new_n;
-      }
-    }
+    #include "group64_rows.inc"
   }
 
-  // ---- epilogue ----
-  __syncthreads();
-  {
-    const u32 blk = n_rows >> 6;
-    const u32 gi = blk * 64 + lane;
-    if (gi < n_rows) reinterpret_cast<uint4 *>(g_rows)[gi] = stage[gi % STAGE_ROWS];
-  }
-  const u32 t_send_cl = wave_sum(s_send_cl), t_send_sv = wave_sum(s_send_sv);
-  const u32 t_recv_cl = wave_sum(s_recv_cl), t_recv_sv = wave_sum(s_recv_sv);
-  for (u32 b = 1; b <= MSIM_FLAG_ARENA_OVERRUN; b <<= 1) if (__ballot((my_flags & b) != 0)) flags |= b;
-  if (lane == 0) {
-    msim_net_stats st;
-    st.all_send = (u64)t_send_cl + t_send_sv; st.all_recv = (u64)t_recv_cl + t_recv_sv;
-    st.clients_send = t_send_cl; st.clients_recv = t_recv_cl;
-    st.servers_send = t_send_sv; st.servers_recv = t_recv_sv;
-    p.stats[inst] = st;
-    msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
-    m.n_events = jcap ? n_ev : 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
-    p.meta[inst] = m;
-  }
+  #include "group64_stats.inc"
 }
+#include "group64_end.inc"

@@ -2,6 +2,7 @@
 // instantiate them (k_general_*.hip, k_wide_*.hip, k_raft.hip, k_svc.hip, k_txn.hip, k_mk.hip, k_dt.hip, k_kafka.hip, k_hat.hip) and for engine.hip,
 // which needs their LDS / scratch layout constants.  A template nobody instantiates costs a parse: every unit includes all of them (the
 // families share message enums and constants in include order) and compiles only its own.
+// The round machinery the kernels have in common is text included inside them, group64_*.inc (docs/KERNELS.md has who takes what).
 #ifndef MSIM_SIM_KERNELS_H
 #define MSIM_SIM_KERNELS_H
 #include <hip/hip_runtime.h>

@@ -3,13 +3,17 @@ oracle — bit for bit, on a machine without a GPU.  Test infrastructure on both
 maelstrom_amd/csrc by tools/hipemu/build_emu.py with the host compiler and loaded through MSIM_LIB in a child process; the product
 library (hipcc, gfx950) is not involved and still refuses to run without a device.  One small case per kernel layout the round touched:
 the two-clusters-per-wavefront broadcast kernel (constant and random latency), the wide kernel with the nodes' sets in LDS and its
-lone-operation path, eight clusters per wavefront for two txn-list-append nodes, the Datomic-style one (one cluster per wavefront), for txn-rw-register, echo / unique-ids, g-set / the counters the broadcast programs and kafka (one cluster per wavefront; its committed-offset lookup), the list-append check's workgroup-per-history kernel, the kafka checker's device pass."""
+lone-operation path, eight clusters per wavefront for two txn-list-append nodes, the Datomic-style one (one cluster per wavefront), for txn-rw-register, echo / unique-ids, g-set / the counters the broadcast programs and kafka (one cluster per wavefront; its committed-offset lookup), the list-append check's workgroup-per-history kernel, the kafka checker's device pass.  The same emulator run also takes the 56 generated cases of
+tests/one_cluster_cases.py (every one-cluster-per-wavefront kernel that shares csrc/group64_*.inc in each of its four instantiations: two clusters, four
+simulated seconds, about half a second each on the emulator, well inside the run's time limit)."""
 import os
 import shutil
 import subprocess
 import sys
 
 import pytest
+
+import one_cluster_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tools", "hipemu", "_build", "libmaelsim_emu.so")
@@ -60,6 +64,8 @@ CASES = [
     "{'workload':'txn-list-append','bin':'datomic','node_count':2,'concurrency':12,'rate':200,'time_limit':5,'latency':5,'nemesis':['partition'],'nemesis_interval':2,'p_loss':0.03,'flags':0x400,'n':5}",   # a full 16-lane group
     "{'workload':'lin-kv','bin':'lin-kv-proxy','proxy_service':'seq-kv','node_count':3,'rate':100,'time_limit':4,'latency':10,'n':2}",   # seq-kv: one cluster per wavefront (svc_kernel<>)
 ]
+# every one-cluster-per-wavefront kernel sharing csrc/group64_*.inc in each of its <NEM, NET_RANDOM> instantiations
+CASES += [repr(dict(kw, seed=one_cluster_cases.SEED, n=one_cluster_cases.CLUSTERS, **({'flags': fl} if fl else {}))) for _, kw, fl in one_cluster_cases.cases()]
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,7 @@ import pytest
 from maelstrom_amd import _abi as A
 from maelstrom_amd import engine as E
 import oracle_lib as O
+import one_cluster_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -442,6 +443,16 @@ def test_kafka_many_workers_parity(lib, kw):
     up to 64 request handlers in flight per node, a client's offsets and assign / poll / commit state in its own lane) against oracle/kafka_nodes.inc."""
     cfg = E.test_config("kafka", seed=41, **kw)
     _compare(cfg, 0, 5)
+
+
+@pytest.mark.parametrize("kw,dev_flags", [pytest.param(kw, fl, id=cid) for cid, kw, fl in one_cluster_cases.cases()])
+def test_one_cluster_kernels_every_instantiation_parity(lib, kw, dev_flags):
+    """Every one-cluster-per-wavefront kernel that shares csrc/group64_*.inc, in each of its four <NEM, NET_RANDOM> instantiations
+    (tests/one_cluster_cases.py: two clusters of three nodes, or two nodes with three workers each; the instantiation with both also
+    keeps the journal and gives a queue two LDS slots; raft, txn and mk with MSIM_DEV_FLAGS bit 9, without which raft4 / txn8 / mk8 run)."""
+    cfg = E.test_config(seed=one_cluster_cases.SEED, **kw)
+    ora = _compare(cfg, 0, one_cluster_cases.CLUSTERS, dev_flags=dev_flags)
+    assert (ora.meta["n_rows"] > 0).all()
 
 
 def test_deep_queues_spill_to_hbm(lib):
