@@ -73,7 +73,12 @@ static void hat_node_handle(sim_t *s, u32 node, const qent *q) {
     case M_INIT: out_send(s, node, q->src, M_INIT_OK, 0, q->b); break;
     case M_TXN: { /* :120-130 */
       u32 off0 = q->a & 0xFFFFFFu, n = q->a >> 24;
-      if (h->n_txn >= h->G || h->lamport[node] >= (1u << 21) - 1) { s->meta.flags |= MSIM_FLAG_ARENA_OVERRUN; break; }
+      if (h->n_txn >= h->G || h->lamport[node] >= (1u << 21) - 1) {
+        /* an engine capacity, mirrored while the engine runs: a kernel stops its cluster at the end of the round whose rows did not fit,
+         * this run goes on dropping rows, and what it meets in later rounds no kernel ever sees */
+        if (!s->rows_stop_round || s->rows_stop_round == s->rounds) s->meta.flags |= MSIM_FLAG_ARENA_OVERRUN;
+        break;
+      }
       u32 off = payload_alloc(s, n);
       if (off == INF) break;
       u32 g = h->n_txn++, ts = (h->lamport[node]++ << 3) | node;

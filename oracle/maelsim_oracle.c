@@ -122,6 +122,7 @@ typedef struct {
   /* scheduler */
   u32 phase, T, cutoff, gen_next, gen_k, next_value, nem_next, nem_j, sleep_until, loss_on;
   u32 rounds;
+  u32 rows_stop_round; /* the round whose rows did not all fit (0 = none): the kernels stop the cluster at the end of that round */
   /* outbox for the current round */
   outmsg *out; u32 n_out, cap_out;
   /* outputs */
@@ -200,7 +201,7 @@ static void out_send_x(sim_t *s, u32 sender, u32 src, u32 dest, u32 type, u32 a,
 static void out_send(sim_t *s, u32 src, u32 dest, u32 type, u32 a, u32 b) { out_send_x(s, src, src, dest, type, a, b, NULL); }
 
 static void add_row(sim_t *s, u32 type, u32 f, u32 err, u32 final, u32 process, u32 value, u32 len) {
-  if (s->meta.n_rows >= s->cfg.max_rows) { s->meta.flags |= MSIM_FLAG_ROWS_OVERFLOW; return; }
+  if (s->meta.n_rows >= s->cfg.max_rows) { s->meta.flags |= MSIM_FLAG_ROWS_OVERFLOW; if (!s->rows_stop_round) s->rows_stop_round = s->rounds; return; }
   msim_op *r = &s->rows[s->meta.n_rows++];
   r->time_len = ((u64)s->T * 1000ull) | ((u64)len << 48);
   r->packed = type | (f << 2) | (err << 7) | (final << 11) | (process << 12);
