@@ -2,8 +2,8 @@
 // as the reference's own runs invoke it (doc/05-datomic/01-single-node.md:257,322: one node, --concurrency 10n), in 16-lane groups.
 //
 // Same program and the same rounds as dtg_kernel<> (sim_kernel_dtg.inc; specification: oracle/dt_nodes.inc): the node's lock and its arrival-order
-// waiting queue, the persistent hash tree in lww-kv, the root pointer in lin-kv, Promise#await's 5 s — its handlers are repeated here statement for
-// statement (the node's index is its lane in the group).  What changes is the mapping, as in txng4.hip / svc4.hip (the time step, the network, the
+// waiting queue, the persistent hash tree in lww-kv, the root pointer in lin-kv, Promise#await's 5 s — its node and services are the same text,
+// dt_node.inc / dt_input.inc (the node's index is its lane in the group).  What changes is the mapping, as in txng4.hip / svc4.hip (the time step, the network, the
 // partition nemesis and the history rows are shared: group16.h, group16_*.inc): a cluster is n nodes + its worker slots + lin-kv + lww-kv <= 16 endpoints, one lane each of a 16-lane
 // group — 1 node with 10 workers is 13 — and a wavefront carries four clusters.
 //
@@ -87,12 +87,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D4_WAVE
   u32 *const curs_g = reinterpret_cast<u32 *>(smem + rp.off_curs) + grp * N * DG_WORDS;                 // [node of the group][DG_WORDS]
   u32 *const cu = curs_g + (is_node ? l : 0) * DG_WORDS;
   u32 *const my_wl = g_wl + (size_t)(is_node ? l : 0) * DT_MAXW;
-  u32 *const gpool = reinterpret_cast<u32 *>(smem + rp.off_gen) + grp * 36;                             // active[16], next_val[16], next_key
+  u32 *const gen = reinterpret_cast<u32 *>(smem + rp.off_gen) + grp * 36;                             // active[16], next_val[16], next_key
   u32 *const misc = reinterpret_cast<u32 *>(smem + rp.off_misc) + grp * GS;
 
   for (u32 i = lane; i < 4 * N * DG_WORDS; i += 64) reinterpret_cast<u32 *>(smem + rp.off_curs)[i] = 0;
-  gpool[l] = l; gpool[16 + l] = 1;
-  if (l == 0) gpool[32] = p.cfg.key_count;
+  gen[l] = l; gen[16 + l] = 1;
+  if (l == 0) gen[32] = p.cfg.key_count;
   if (real) {
     for (u32 i = l; i < mv; i += GS) { g_kvn[i] = 0; g_first[i] = DT_NONE; g_hash[i] = (unsigned char)dt_hash(i); }
     for (u32 i = l; i < N * DT_CASQ * 3u; i += GS) g_cas[i] = 0;
@@ -162,41 +162,41 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D4_WAVE
       }
       #include "group8_nemesis.inc"
       {
-        const bool gen = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
-        if (__ballot(gen)) {
+        const bool gen_now = act && phase == PH_MAIN && gen_live && gen_next <= T && free_mask != 0;
+        if (__ballot(gen_now)) {
           const u32 nfree = __popc(free_mask);
           const u32 kk = gen_k;
           const u64 h = draw64(key, S_GEN, kk);
           const u32 r_hi = (u32)(h >> 32), r_lo = (u32)h;
           const u32 pick = scale32(r_lo, nfree);
-          const bool sel = gen && is_worker && !busy && (u32)__popc(free_mask & lt) == pick;
+          const bool sel = gen_now && is_worker && !busy && (u32)__popc(free_mask & lt) == pick;
           // the transaction ([upstream] elle list-append gen): lane 0 of the group writes the micro-ops and owns the key pool
           const u32 n_mops = 1 + scale32((u32)(draw64(key, S_GEN2, kk) >> 32), p.cfg.max_txn_length);
           u32 bad = 0;
-          if (gen && n_payload + n_mops > max_pay) bad = MSIM_FLAG_PAYLOAD_OVERFLOW;
-          else if (gen && l == 0) {
+          if (gen_now && n_payload + n_mops > max_pay) bad = MSIM_FLAG_PAYLOAD_OVERFLOW;
+          else if (gen_now && l == 0) {
             const u32 kc = p.cfg.key_count;
             for (u32 j = 0; j < n_mops; j++) {
               const u64 h3 = draw64(key, S_GEN3, (u64)kk * 8 + j);
               const u32 x = scale32((u32)(h3 >> 32), (1u << kc) - 1) + 1;
               const u32 ki = 31 - (u32)__clz((int)x);
-              const u32 k = gpool[ki];
+              const u32 k = gen[ki];
               if (h3 & 1) {
-                const u32 v = gpool[16 + ki];
-                gpool[16 + ki] = v + 1;
+                const u32 v = gen[16 + ki];
+                gen[16 + ki] = v + 1;
                 g_pay[n_payload + j] = 1u | (k << 1) | (v << 16);
                 if (v + 1 > mw) {
-                  const u32 nk = gpool[32];
+                  const u32 nk = gen[32];
                   if (nk >= p.cfg.max_values) { bad = MSIM_FLAG_VALUES_OVERFLOW; break; }
-                  gpool[ki] = nk; gpool[32] = nk + 1; gpool[16 + ki] = 1;
+                  gen[ki] = nk; gen[32] = nk + 1; gen[16 + ki] = 1;
                 }
               } else g_pay[n_payload + j] = (k << 1) | (0xFFu << 16);
             }
           }
           bad = GGET(bad, 0);
-          if (gen && bad) { flags |= bad; phase = PH_DONE; alive = false; normal = false; }
+          if (gen_now && bad) { flags |= bad; phase = PH_DONE; alive = false; normal = false; }
           if (sel && !bad) { mark = true; kind = K_OP; m_value = n_payload | (n_mops << 24); }
-          if (gen && !bad) { gen_k++; n_payload += n_mops; gen_next = T + __umulhi(r_hi, p.gen_period2_us); }
+          if (gen_now && !bad) { gen_k++; n_payload += n_mops; gen_next = T + __umulhi(r_hi, p.gen_period2_us); }
         }
       }
 
@@ -237,193 +237,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D4_WAVE
       u32 n_out = 0, o_dest = 0;           // node -> service: n_out messages, all to the same service; one in registers (o1_*) or DT_MAXW writes in my_wl[]
       u32 o1_type = 0, o1_a = 0, o1_b = 0, o_wlo = 0;
       u32 o_type = 0, o_a = 0, o_b = 0, o_to = 0, need_words = 0, done_ref = 0, done_rv = 0;   // service -> node; the completed transaction's payload
-      auto rec_of = [&](u32 ptr) -> u32 * { return g_rec + ((size_t)(ptr >> 20) * TC + (ptr & 0xFFFFFu)) * DT_RW; };
-      auto is_new = [&](u32 ptr) -> bool { return (ptr >> 20) == l && (ptr & 0xFFFFFu) >= cu[DC_PSTART]; };
-      auto has_key = [&](u32 k) -> bool {   // the key is in the lineage of the working tree
-        if (g_first[k] <= cu[DC_RV]) return true;   // (DT_NONE is above every version)
-        const u32 no = cu[DC_NOWN];
-        for (u32 i = 0; i < no; i++) if (cu[DC_OWN + i] == k) return true;
-        return false;
-      };
-      auto br_index = [&](u32 w0, u32 h) -> u32 {   // branch_index (:231-247) with the split's bounds (:170-181)
-        const u32 lo = (w0 >> 8) & 0xFFu, hi = (w0 >> 16) & 0xFFu, bs = (hi - lo) / 8u;
-        for (u32 i = 0; i < 7u; i++) if (h < lo + (i + 1u) * bs) return i;
-        return 7u;
-      };
-      auto send1 = [&](u32 dest, u32 type, u32 a, u32 b) { o_dest = dest; n_out = 1; o1_type = type; o1_a = a; o1_b = b; };
       auto reply = [&](u32 type, u32 a, u32 cmsg) { rep = true; r_type = type; r_a = a; r_to = cmsg >> 24; r_b = cmsg & 0xFFFFFFu; };   // (cmsg = the client's msg_id | its endpoint << 24)
-      auto start_txn = [&](u32 cmsg, u32 ref) {   // the lock is ours: current_tree (:358-365)
-        cu[DC_STAGE] = DS_ROOT; cu[DC_CMSG] = cmsg; cu[DC_REF] = ref; cu[DC_J] = 0; cu[DC_NOWN] = 0;
-        const u32 rid = ++node_msgid; cu[DC_RPC] = rid;
-        send1(D_LIN, M_READ, 0, rid);
-        wait_until = T + DT_AWAIT_US;
-      };
-      auto unlock = [&]() {   // the next waiting transaction takes the lock (:348, :371), in arrival order
-        cu[DC_STAGE] = DS_IDLE;
-        wait_until = INF;
-        const u32 wq = cu[DG_WQN], cnt = wq & 0xFFu, head = wq >> 8;
-        if (cnt) {
-          const u32 cmsg = cu[DG_WQ + 2u * head], ref = cu[DG_WQ + 2u * head + 1u];
-          cu[DG_WQN] = (cnt - 1u) | (((head + 1u) & (DG_WAITQ - 1u)) << 8);
-          start_txn(cmsg, ref);
-        }
-      };
-      auto load = [&](u32 ptr) {   // Tree.load with a cache miss (:83-101)
-        const u32 rid = ++node_msgid;
-        cu[DC_STAGE] = DS_LOAD; cu[DC_TARGET] = ptr; cu[DC_RPC] = rid;
-        send1(D_LWW, M_READ, ptr, rid);
-        wait_until = T + DT_AWAIT_US;
-      };
-      // walks to the key's leaf; the first tree node on the way that has to be fetched, DT_NONE if the path is in memory
-      auto descend = [&](u32 k) -> u32 {
-        const u32 h = g_hash[k];
-        u32 pt = cu[DC_T];
-        for (u32 d = 0; d < DT_MAXDEPTH; d++) {
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0], w3 = __hip_atomic_load(r + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (word 3 is the one word of a record that changes after its creation, by L2 atomics: read past the L1)
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if (!is_new(pt) && !((w3 >> (2u + l)) & 1u)) return pt;   // neither created by this transaction nor loaded by this node
-          if ((w0 & 1u) == 0u) return DT_NONE;
-          const u32 ci = br_index(w0, h);
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        my_flags |= MSIM_FLAG_ARENA_OVERRUN;
-        return DT_NONE;
-      };
-      // assoc (:158-197, :256-268) along a path that is in memory (sim_kernel_dt.inc)
-      auto assoc = [&](u32 k) {
-        const u32 h = g_hash[k];
-        u32 n = 0, pt = cu[DC_T];
-        for (; n + 1u < DT_MAXDEPTH; n++) {
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0];
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if ((w0 & 1u) == 0u) break;
-          const u32 ci = br_index(w0, h);
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        const u32 *const lf = rec_of(pt);
-        const u32 lw0 = lf[0], lcount = lf[1];
-        if (lw0 & 1u) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; return; }
-        const bool has = has_key(k);
-        const u32 L = (has || lcount < 8u) ? 1u : 9u, base = next_p, ver = cu[DC_RV] + 1u;
-        if (base + L + n >= TC) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; return; }   // engine capacity
-        const u32 lo = (lw0 >> 8) & 0xFFu, hi = (lw0 >> 16) & 0xFFu;
-        auto put = [&](u32 idx, u32 w0, u32 cnt) -> u32 * { u32 *const r = g_rec + ((size_t)l * TC + idx) * DT_RW; r[0] = w0; r[1] = cnt; r[2] = ver; __hip_atomic_store(r + 3, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return r; };   // (word 3: lww-kv replica in bits 0-1, 3 = not written; bit 2 + i: node i has loaded it)
-        if (L == 1u) put(base + 1u, lw0, lcount + (has ? 0u : 1u));
-        else {   // eight leaves under a new branch: the lineage's keys of this range (and the new one) by sub-range
-          const u32 bs = (hi - lo) / 8u, nk = gpool[32];
-          u64 c_lo = 0, c_hi = 0;   // 4 x 16-bit counters each
-          for (u32 q = 0; q < nk; q++) {
-            if (q != k && !has_key(q)) continue;
-            const u32 hq = g_hash[q];
-            if (hq < lo || hq >= hi) continue;
-            const u32 ci = bs ? min((hq - lo) / bs, 7u) : 7u;
-            if (ci < 4u) c_lo += 1ull << (16u * ci); else c_hi += 1ull << (16u * (ci - 4u));
-          }
-          u32 *const br = put(base + 9u, 1u | (lo << 8) | (hi << 16), 0u);
-          for (u32 i = 0; i < 8u; i++) {
-            const u32 b_lo = lo + i * bs, b_hi = i == 7u ? hi : b_lo + bs;
-            const u32 cnt = (u32)((i < 4u ? c_lo >> (16u * i) : c_hi >> (16u * (i - 4u))) & 0xFFFFu);
-            put(base + 1u + i, (b_lo << 8) | (b_hi << 16), cnt);
-            br[4u + i] = (l << 20) | (base + 1u + i);
-          }
-        }
-        pt = cu[DC_T];
-        for (u32 i = 0; i < n; i++) {   // a copy of every branch above, pointing at the new child
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0], ci = br_index(w0, h);
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          u32 *const nr = put(base + L + (n - i), w0, 0u);
-          const u32 child_new = (l << 20) | (i + 1u == n ? base + L : base + L + (n - i - 1u));
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) nr[4u + c] = c == ci ? child_new : ch[c];
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        next_p = base + L + n;
-        cu[DC_T] = (l << 20) | next_p;
-        if (!has) { const u32 no = cu[DC_NOWN]; if (no < 8u) { cu[DC_OWN + no] = k; cu[DC_NOWN] = no + 1u; } }
-      };
-      // save! (:212-224, :291-320): the new tree nodes the final tree reaches, children before their parent (sim_kernel_dt.inc)
-      auto save = [&]() {
-        u32 *const stk = cu + DG_STK;
-        u32 sp = 1, wn = 0;
-        const u32 wlo = node_msgid + 1u;
-        stk[0] = cu[DC_T]; stk[1] = 0x100u;   // (0x100: not looked at yet)
-        while (sp) {
-          const u32 pt = stk[2u * (sp - 1u)];
-          u32 mask = stk[2u * (sp - 1u) + 1u];
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0];
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if (mask & 0x100u) {
-            mask = 0;
-            if (w0 & 1u) {
-#pragma unroll
-              for (u32 c = 0; c < 8u; c++) mask |= is_new(ch[c]) ? 1u << c : 0u;
-            }
-          }
-          if (mask) {
-            const u32 ci = (u32)__builtin_ctz(mask);
-            u32 nxt = ch[0];
-#pragma unroll
-            for (u32 c = 1; c < 8u; c++) nxt = c == ci ? ch[c] : nxt;
-            stk[2u * (sp - 1u) + 1u] = mask & (mask - 1u);
-            if (sp > DT_MAXDEPTH) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; stk[2u * (sp - 1u) + 1u] = 0; continue; }
-            stk[2u * sp] = nxt; stk[2u * sp + 1u] = 0x100u; sp++;
-            continue;
-          }
-          if (wn >= DT_MAXW) my_flags |= MSIM_FLAG_ARENA_OVERRUN; else my_wl[wn++] = pt;
-          sp--;
-        }
-        node_msgid += wn;
-        cu[DC_STAGE] = DS_SAVE; cu[DC_WLO] = wlo; cu[DC_WN] = wn; cu[DC_WOUT] = wn;
-        o_dest = D_LWW; n_out = wn; o_wlo = wlo;
-        wait_until = T + DT_AWAIT_US;   // `tree2.save!.await` (:366)
-      };
-      auto reply_txn_ok = [&]() {   // the completed transaction: its reads see the version read + its own appends
-        reply(M_TXN_OK, 0, cu[DC_CMSG]);
-        done_ref = cu[DC_REF]; done_rv = cu[DC_RV];
-        const u32 off0 = done_ref & 0xFFFFFFu, n = done_ref >> 24;
-        for (u32 j = 0; j < n; j++) {
-          const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-          need_words++;
-          if (!(w & 1u)) {
-            u32 len = visible(k, done_rv);
-            for (u32 e = 0; e < j; e++) { const u32 we = g_pay[off0 + e]; if ((we & 1u) && ((we >> 1) & 0x7FFFu) == k) len++; }
-            need_words += (len + 3u) / 4u;
-          }
-        }
-      };
-      // apply_txn (:391-415) from micro-op j on; stops at the first tree node that has to be fetched
-      auto apply = [&]() {
-        const u32 ref = cu[DC_REF], off0 = ref & 0xFFFFFFu, n = ref >> 24;
-        u32 j = cu[DC_J];
-        while (j < n) {
-          const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-          const u32 miss = descend(k);   // t[k] — for an append too (:405)
-          if (miss != DT_NONE) { cu[DC_J] = j; load(miss); return; }
-          if (w & 1u) assoc(k);
-          j++;
-        }
-        cu[DC_J] = j;
-        if (cu[DC_T] == cu[DC_P1]) { reply_txn_ok(); unlock(); return; }   // nothing appended: no write, no cas
-        save();
-      };
+      // what dt_node.inc / dt_input.inc ask of the kernel
+#define REPLY_OK(type, cmsg) reply(type, 0, cmsg)
+#define REPLY_ERROR(code, cmsg) reply(M_ERROR, code, cmsg)
+#define CLIENT_REF(qb, qsrc) ((qb) | ((qsrc) << 24))   // a client is an endpoint: it rides in the top byte of the stored msg_id
+#define NODE_IX l   // a node's index is its lane in the group
+#define DT_WAIT_RING
+      #include "dt_node.inc"
 
       const bool await_over = is_node && normal && wait_until <= T;   // a node's due timer comes before its due message
       const bool take = is_server && normal && !await_over && has_c && deliver_at <= T;
@@ -434,123 +255,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D4_WAVE
         const uint4 q = cm; has_c = false;
         const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
         if (qsrc >= N && qsrc < LIN) s_recv_cl++; else s_recv_sv++;
-        if (is_node) {
-          const u32 st = cu[DC_STAGE];
-          switch (qtype) {
-            case M_INIT:
-              if (l != 0u) { reply(M_INIT_OK, 0, qb | (qsrc << 24)); break; }
-              {   // the first node writes the initial state (:337-345): Tree.empty, then the root pointer
-                u32 *const r = g_rec;
-                r[0] = (128u << 16); r[1] = 0; r[2] = 0; __hip_atomic_store(r + 3, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const u32 rid = ++node_msgid;
-                cu[DC_STAGE] = DS_INIT_LEAF; cu[DC_CMSG] = qb | (qsrc << 24); cu[DC_RPC] = rid;
-                send1(D_LWW, M_WRITE, 0, rid);
-              } break;
-            case M_TXN:
-              if (st == DS_IDLE) start_txn(qb | (qsrc << 24), qa);
-              else { const u32 wq = cu[DG_WQN], cnt = wq & 0xFFu;
-                if (cnt == DG_WAITQ) my_flags |= MSIM_FLAG_ARENA_OVERRUN;
-                else { const u32 sl = ((wq >> 8) + cnt) & (DG_WAITQ - 1u); cu[DG_WQ + 2u * sl] = qb | (qsrc << 24); cu[DG_WQ + 2u * sl + 1u] = qa; cu[DG_WQN] = wq + 1u; } }
-              break;
-            case M_READ_OK: case M_WRITE_OK: case M_CAS_OK: case M_ERROR:
-              switch (st) {
-                case DS_INIT_LEAF:
-                  if (qb != cu[DC_RPC]) break;
-                  { const u32 rid = ++node_msgid; cu[DC_STAGE] = DS_INIT_ROOT; cu[DC_RPC] = rid; send1(D_LIN, M_WRITE, 0, rid); }
-                  break;
-                case DS_INIT_ROOT:
-                  if (qb != cu[DC_RPC]) break;
-                  cu[DC_STAGE] = DS_IDLE; reply(M_INIT_OK, 0, cu[DC_CMSG]);
-                  break;
-                case DS_ROOT:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype != M_READ_OK) { reply(M_ERROR, 14, cu[DC_CMSG]); unlock(); break; }   // "Unsure how to handle" (:364)
-                  cu[DC_P1] = qa; cu[DC_T] = qa; cu[DC_PSTART] = next_p + 1u;
-                  { const u32 *const rr = rec_of(qa); const u32 rv2 = rr[2], rw3 = __hip_atomic_load(rr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); cu[DC_RV] = rv2; if ((rw3 >> (2u + l)) & 1u) apply(); else load(qa); }
-                  break;
-                case DS_LOAD:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype == M_READ_OK) { atomicOr(rec_of(cu[DC_TARGET]) + 3, 1u << (2u + l)); apply(); }   // @@cache[ptr] = tree (:95)
-                  else load(cu[DC_TARGET]);   // "Retrying read of tree node" (:97)
-                  break;
-                case DS_SAVE:
-                  if (qb < cu[DC_WLO] || qb >= cu[DC_WLO] + cu[DC_WN]) break;
-                  { const u32 left = cu[DC_WOUT] - 1u; cu[DC_WOUT] = left;
-                    if (left == 0u) { const u32 rid = ++node_msgid; cu[DC_STAGE] = DS_CAS; cu[DC_RPC] = rid;   // advance_root! (:376-388): cas root from the pointer read to the new one
-                      { u32 *const ce = g_cas + ((size_t)l * DT_CASQ + (casn++ % DT_CASQ)) * 3u; ce[0] = rid; ce[1] = cu[DC_P1]; ce[2] = cu[DC_REF]; }
-                      send1(D_LIN, M_CAS, cu[DC_T], rid); wait_until = T + DT_AWAIT_US; } }
-                  break;
-                case DS_CAS:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype == M_CAS_OK) reply_txn_ok();
-                  else reply(M_ERROR, 30, cu[DC_CMSG]);   // txn_conflict (:385)
-                  unlock();
-                  break;
-                default: break;   // "Ignoring reply ... with no callback" (node.rb:160-162)
-              }
-              break;
-            default: break;
-          }
-        } else if (is_lin) {   // lin-kv over the key "root" (service.clj:31-61)
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          if (qtype == M_READ) {
-            if (!root_exists) { o_type = M_ERROR; o_a = 20; } else { o_type = M_READ_OK; o_a = root; }
-          } else if (qtype == M_WRITE) { root = qa; root_exists = 1u; o_type = M_WRITE_OK; o_a = 0; }
-          else {   // cas, no create_if_not_exists: self-contained (:376-388) — `from` and the transaction under the msg_id in the sender's table
-            u32 c_from = 0, c_ref = 0; bool c_hit = false;
-            { const u32 *const ce = g_cas + (size_t)qsrc * DT_CASQ * 3u;
-#pragma unroll
-              for (u32 i = 0; i < DT_CASQ; i++) { const u32 e0 = ce[3u * i], e1 = ce[3u * i + 1u], e2 = ce[3u * i + 2u]; if (e0 == qb) { c_hit = true; c_from = e1; c_ref = e2; } } }
-            if (!c_hit) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; o_type = M_ERROR; o_a = 22; }   // engine capacity: DT_CASQ outstanding cas requests per node
-            else if (!root_exists) { o_type = M_ERROR; o_a = 20; }
-            else if (root != c_from) { o_type = M_ERROR; o_a = 22; }
-            else {
-              const u32 ref = c_ref, off0 = ref & 0xFFFFFFu, n = ref >> 24, v = ++cur_v;
-              root = qa;
-              for (u32 i = 0; i < n; i++) { const u32 w = g_pay[off0 + i];
-                if (w & 1u) { const u32 k = (w >> 1) & 0x7FFFu, c = g_kvn[k]; if (g_first[k] == DT_NONE) g_first[k] = v;
-                  g_kv[k * mw + c] = ((w >> 16) & 0xFFu) | (v << 8); g_kvn[k] = c + 1u; } }
-              o_type = M_CAS_OK; o_a = 0;
-            }
-          }
-        } else {   // lww-kv (service.clj:214-243 as written): merge-source, merge-dest, then the replica that serves the request
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          svc_ctr += 2u;
-          const u32 r = scale32(draw32(key, 12u /* S_LIN */, svc_ctr++), 2);
-          u32 *const rp = rec_of(qa) + 3;   // (the replica bits; the nodes set their "loaded" bits in the same word: atomics)
-          if (qtype == M_WRITE) { atomicAnd(rp, ~3u); atomicOr(rp, r); o_type = M_WRITE_OK; o_a = qa; }
-          else if ((__hip_atomic_load(rp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 3u) == r) { o_type = M_READ_OK; o_a = qa; }
-          else { o_type = M_ERROR; o_a = 20; }
-        }
+        #include "dt_input.inc"
       }
 
       // completed transactions: payload words allocated in node order, each node writes its own
       if (__ballot(need_words != 0)) {
         const u32 incl = row_scan(need_words);
         const u32 total = GGET(incl, GS - 1u);
-        if (total) {
-          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) r_a = 0; }
-          else {
-            if (need_words) {
-              const u32 off0 = done_ref & 0xFFFFFFu, n = done_ref >> 24;
-              u32 pp = n_payload + incl - need_words;
-              r_a = pp | (need_words << 24);
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                if (w & 1u) { g_pay[pp++] = w; continue; }
-                const u32 vis = visible(k, done_rv);
-                u32 e = 0, acc = 0;
-                const u32 hdr = pp++;
-                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
-                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
-                  if ((wi & 1u) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
-                if (e & 3) g_pay[pp++] = acc;
-                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
-              }
-            }
-            n_payload += total;
-          }
-        }
+        #include "dt_reads.inc"
       }
 
       // COMMIT: ids in lane order (nodes, lin-kv, lww-kv); a node's messages in the order it emitted them: the answer to a client,

@@ -11,3 +11,16 @@
 #undef WORKERS_OF
 #undef NOTHING_COMMITTED
 #undef COMMITTED_AT
+// ... and what it told its program's fragments (dt_*.inc, mk_*.inc, hat_node.inc, kafka_*.inc, txn_lin.inc, list_append_client.inc)
+#undef CLIENT_REF
+#undef REPLY_OK
+#undef REPLY_ERROR
+#undef NODE_IX
+#undef DT_WAIT_RING
+#undef MK_NSLOTS
+#undef KF_NSLOTS
+#undef REPLY_TO
+#undef TXN_REF_OF
+#undef CRASH_STRIDE
+#undef NODE_GIVES_UP
+#undef OWN_CLIENT_DELIVER

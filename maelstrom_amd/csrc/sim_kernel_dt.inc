@@ -169,23 +169,9 @@ __global__ void __launch_bounds__(64) DT_OCC dt_kernel(const KParams p) {
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
-    auto complete = [&](u32 type, u32 err, u32 ref) {
-      busy = false;
-      if (kind != K_OP) { if (type != MSIM_T_OK) my_flags |= MSIM_FLAG_ROUND_LIMIT; return; }
-      cmp_row = true; cmp_packed = type | (MSIM_F_TXN << 2) | (err << 7) | (process << 12);
-      cmp_value = ref & 0xFFFFFFu; cmp_len = ref >> 24;
-      if (type == MSIM_T_INFO) process += N;  // crashed process; the Reusable client itself lives on
-    };
-    auto client_deliver = [&](u32 qtype, u32 qa, u32 qb) {
-      s_recv_cl++;
-      if (busy && qb == want) {
-        if (qtype == M_TXN_OK) complete(MSIM_T_OK, 0, qa);
-        else if (qtype == M_ERROR)
-          if (qa == 0u) complete(MSIM_T_INFO, MSIM_ERR_TIMEOUT, c_value);   // code 0 :timeout is not :definite? (errors.edn:2-4)
-          else complete(MSIM_T_FAIL, qa == 11 ? MSIM_ERR_TEMPORARILY_UNAVAILABLE : qa == 20 ? MSIM_ERR_KEY_DOES_NOT_EXIST : qa == 30 ? MSIM_ERR_TXN_CONFLICT : qa == 14 ? MSIM_ERR_ABORT : MSIM_ERR_PRECONDITION_FAILED, c_value);
-        else complete(MSIM_T_OK, 0, c_value);  // init_ok
-      }
-    };
+#define CRASH_STRIDE N
+#define NODE_GIVES_UP
+    #include "list_append_client.inc"
 
     if (timeout_round) {
       if (busy && timeout_at <= T) complete(MSIM_T_INFO, MSIM_ERR_NET_TIMEOUT, c_value);
@@ -244,297 +230,24 @@ __global__ void __launch_bounds__(64) DT_OCC dt_kernel(const KParams p) {
       u32 n_out = 0, o_dest = 0;           // node -> service: n_out messages, all to the same service; one in registers (o1_*) or DT_MAXW writes in my_wl[]
       u32 o1_type = 0, o1_a = 0, o1_b = 0, o_wlo = 0;
       u32 o_type = 0, o_a = 0, o_b = 0, o_to = 0, need_words = 0, done_ref = 0, done_rv = 0;   // service -> node; the completed transaction's payload
-      auto rec_of = [&](u32 ptr) -> u32 * { return g_rec + ((size_t)(ptr >> 20) * TC + (ptr & 0xFFFFFu)) * DT_RW; };
-      auto is_new = [&](u32 ptr) -> bool { return (ptr >> 20) == lane && (ptr & 0xFFFFFu) >= cu[DC_PSTART]; };
-      auto has_key = [&](u32 k) -> bool {   // the key is in the lineage of the working tree
-        if (g_first[k] <= cu[DC_RV]) return true;   // (DT_NONE is above every version)
-        const u32 no = cu[DC_NOWN];
-        for (u32 i = 0; i < no; i++) if (cu[DC_OWN + i] == k) return true;
-        return false;
-      };
-      auto br_index = [&](u32 w0, u32 h) -> u32 {   // branch_index (:231-247) with the split's bounds (:170-181)
-        const u32 lo = (w0 >> 8) & 0xFFu, hi = (w0 >> 16) & 0xFFu, bs = (hi - lo) / 8u;
-        for (u32 i = 0; i < 7u; i++) if (h < lo + (i + 1u) * bs) return i;
-        return 7u;
-      };
-      auto send1 = [&](u32 dest, u32 type, u32 a, u32 b) { o_dest = dest; n_out = 1; o1_type = type; o1_a = a; o1_b = b; };
-      auto start_txn = [&](u32 cmsg, u32 ref) {   // the lock is ours: current_tree (:358-365)
-        cu[DC_STAGE] = DS_ROOT; cu[DC_CMSG] = cmsg; cu[DC_REF] = ref; cu[DC_J] = 0; cu[DC_NOWN] = 0;
-        const u32 rid = ++node_msgid; cu[DC_RPC] = rid;
-        send1(D_LIN, M_READ, 0, rid);
-        wait_until = T + DT_AWAIT_US;
-      };
-      auto unlock = [&]() {   // the next waiting transaction takes the lock (:348, :371)
-        cu[DC_STAGE] = DS_IDLE;
-        wait_until = INF;
-        const u32 wqn = cu[DC_WQN];
-        if (wqn) {
-          const u32 cmsg = cu[DC_WQ], ref = cu[DC_WQ + 1];
-          for (u32 i = 1; i < wqn; i++) { cu[DC_WQ + 2 * (i - 1)] = cu[DC_WQ + 2 * i]; cu[DC_WQ + 2 * (i - 1) + 1] = cu[DC_WQ + 2 * i + 1]; }
-          cu[DC_WQN] = wqn - 1;
-          start_txn(cmsg, ref);
-        }
-      };
-      auto load = [&](u32 ptr) {   // Tree.load with a cache miss (:83-101)
-        const u32 rid = ++node_msgid;
-        cu[DC_STAGE] = DS_LOAD; cu[DC_TARGET] = ptr; cu[DC_RPC] = rid;
-        send1(D_LWW, M_READ, ptr, rid);
-        wait_until = T + DT_AWAIT_US;
-      };
-      // walks to the key's leaf; the first tree node on the way that has to be fetched, DT_NONE if the path is in memory.  One round trip per
-      // level: a record's kind / range, its flags word (which nodes have loaded it) and its eight children are loaded together.
-      auto descend = [&](u32 k) -> u32 {
-        const u32 h = g_hash[k];
-        u32 pt = cu[DC_T];
-        for (u32 d = 0; d < DT_MAXDEPTH; d++) {
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0], w3 = __hip_atomic_load(r + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (word 3 is the one word of a record that changes after its creation, by L2 atomics: read past the L1)
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if (!is_new(pt) && !((w3 >> (2u + lane)) & 1u)) return pt;   // neither created by this transaction nor loaded by this node
-          if ((w0 & 1u) == 0u) return DT_NONE;
-          const u32 ci = br_index(w0, h);
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        my_flags |= MSIM_FLAG_ARENA_OVERRUN;
-        return DT_NONE;
-      };
-      // assoc (:158-197, :256-268) along a path that is in memory.  New pointers go leaf first, then upwards: with n branches above a
-      // leaf level of L new nodes (1, or 8 leaves + their branch) the leaf level takes base+1 .. base+L, the branch at depth i
-      // base+L+(n-i) — known before the walk down that writes the copies.
-      auto assoc = [&](u32 k) {
-        const u32 h = g_hash[k];
-        u32 n = 0, pt = cu[DC_T];
-        for (; n + 1u < DT_MAXDEPTH; n++) {
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0];
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if ((w0 & 1u) == 0u) break;
-          const u32 ci = br_index(w0, h);
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        const u32 *const lf = rec_of(pt);
-        const u32 lw0 = lf[0], lcount = lf[1];
-        if (lw0 & 1u) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; return; }
-        const bool has = has_key(k);
-        const u32 L = (has || lcount < 8u) ? 1u : 9u, base = next_p, ver = cu[DC_RV] + 1u;
-        if (base + L + n >= TC) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; return; }   // engine capacity
-        const u32 lo = (lw0 >> 8) & 0xFFu, hi = (lw0 >> 16) & 0xFFu;
-        auto put = [&](u32 idx, u32 w0, u32 cnt) -> u32 * { u32 *const r = g_rec + ((size_t)lane * TC + idx) * DT_RW; r[0] = w0; r[1] = cnt; r[2] = ver; __hip_atomic_store(r + 3, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return r; };   // (word 3: lww-kv replica in bits 0-1, 3 = not written; bit 2 + i: node i has loaded it)
-        if (L == 1u) put(base + 1u, lw0, lcount + (has ? 0u : 1u));
-        else {   // eight leaves under a new branch: the lineage's keys of this range (and the new one) by sub-range
-          const u32 bs = (hi - lo) / 8u, nk = gen[32];
-          u64 c_lo = 0, c_hi = 0;   // 4 x 16-bit counters each
-          for (u32 q = 0; q < nk; q++) {
-            if (q != k && !has_key(q)) continue;
-            const u32 hq = g_hash[q];
-            if (hq < lo || hq >= hi) continue;
-            const u32 ci = bs ? min((hq - lo) / bs, 7u) : 7u;
-            if (ci < 4u) c_lo += 1ull << (16u * ci); else c_hi += 1ull << (16u * (ci - 4u));
-          }
-          u32 *const br = put(base + 9u, 1u | (lo << 8) | (hi << 16), 0u);
-          for (u32 i = 0; i < 8u; i++) {
-            const u32 b_lo = lo + i * bs, b_hi = i == 7u ? hi : b_lo + bs;
-            const u32 cnt = (u32)((i < 4u ? c_lo >> (16u * i) : c_hi >> (16u * (i - 4u))) & 0xFFFFu);
-            put(base + 1u + i, (b_lo << 8) | (b_hi << 16), cnt);
-            br[4u + i] = (lane << 20) | (base + 1u + i);
-          }
-        }
-        pt = cu[DC_T];
-        for (u32 i = 0; i < n; i++) {   // a copy of every branch above, pointing at the new child
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0], ci = br_index(w0, h);
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          u32 *const nr = put(base + L + (n - i), w0, 0u);
-          const u32 child_new = (lane << 20) | (i + 1u == n ? base + L : base + L + (n - i - 1u));
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) nr[4u + c] = c == ci ? child_new : ch[c];
-          pt = ch[0];
-#pragma unroll
-          for (u32 c = 1; c < 8u; c++) pt = c == ci ? ch[c] : pt;
-        }
-        next_p = base + L + n;
-        cu[DC_T] = (lane << 20) | next_p;
-        if (!has) { const u32 no = cu[DC_NOWN]; if (no < 8u) { cu[DC_OWN + no] = k; cu[DC_NOWN] = no + 1u; } }
-      };
-      // save! (:212-224, :291-320): the new tree nodes the final tree reaches, children before their parent.  A stack entry is a tree node and
-      // the mask of its new children still to visit (a branch's eight children are loaded together: one round trip per visit).
-      auto save = [&]() {
-        u32 *const stk = cu + DC_STK;
-        u32 sp = 1, wn = 0;
-        const u32 wlo = node_msgid + 1u;
-        stk[0] = cu[DC_T]; stk[1] = 0x100u;   // (0x100: not looked at yet)
-        while (sp) {
-          const u32 pt = stk[2u * (sp - 1u)];
-          u32 mask = stk[2u * (sp - 1u) + 1u];
-          const u32 *const r = rec_of(pt);
-          const u32 w0 = r[0];
-          u32 ch[8];
-#pragma unroll
-          for (u32 c = 0; c < 8u; c++) ch[c] = r[4u + c];
-          if (mask & 0x100u) {
-            mask = 0;
-            if (w0 & 1u) {
-#pragma unroll
-              for (u32 c = 0; c < 8u; c++) mask |= is_new(ch[c]) ? 1u << c : 0u;
-            }
-          }
-          if (mask) {
-            const u32 ci = (u32)__builtin_ctz(mask);
-            u32 nxt = ch[0];
-#pragma unroll
-            for (u32 c = 1; c < 8u; c++) nxt = c == ci ? ch[c] : nxt;
-            stk[2u * (sp - 1u) + 1u] = mask & (mask - 1u);
-            if (sp > DT_MAXDEPTH) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; stk[2u * (sp - 1u) + 1u] = 0; continue; }
-            stk[2u * sp] = nxt; stk[2u * sp + 1u] = 0x100u; sp++;
-            continue;
-          }
-          if (wn >= DT_MAXW) my_flags |= MSIM_FLAG_ARENA_OVERRUN; else my_wl[wn++] = pt;
-          sp--;
-        }
-        node_msgid += wn;
-        cu[DC_STAGE] = DS_SAVE; cu[DC_WLO] = wlo; cu[DC_WN] = wn; cu[DC_WOUT] = wn;
-        o_dest = D_LWW; n_out = wn; o_wlo = wlo;
-        wait_until = T + DT_AWAIT_US;   // `tree2.save!.await` (:366)
-      };
-      auto reply_txn_ok = [&]() {   // the completed transaction: its reads see the version read + its own appends
-        rep = true; r_type = M_TXN_OK; r_b = cu[DC_CMSG];
-        done_ref = cu[DC_REF]; done_rv = cu[DC_RV];
-        const u32 off0 = done_ref & 0xFFFFFFu, n = done_ref >> 24;
-        for (u32 j = 0; j < n; j++) {
-          const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-          need_words++;
-          if (!(w & 1u)) {
-            u32 len = visible(k, done_rv);
-            for (u32 e = 0; e < j; e++) { const u32 we = g_pay[off0 + e]; if ((we & 1u) && ((we >> 1) & 0x7FFFu) == k) len++; }
-            need_words += (len + 3u) / 4u;
-          }
-        }
-      };
-      // apply_txn (:391-415) from micro-op j on; stops at the first tree node that has to be fetched
-      auto apply = [&]() {
-        const u32 ref = cu[DC_REF], off0 = ref & 0xFFFFFFu, n = ref >> 24;
-        u32 j = cu[DC_J];
-        while (j < n) {
-          const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-          const u32 miss = descend(k);   // t[k] — for an append too (:405)
-          if (miss != DT_NONE) { cu[DC_J] = j; load(miss); return; }
-          if (w & 1u) assoc(k);
-          j++;
-        }
-        cu[DC_J] = j;
-        if (cu[DC_T] == cu[DC_P1]) { reply_txn_ok(); unlock(); return; }   // nothing appended: no write, no cas
-        save();
-      };
+      // what dt_node.inc / dt_input.inc ask of the kernel: the answer goes to the client in the node's own lane, a client reference is its msg_id
+#define REPLY_OK(type, cmsg) { rep = true; r_type = type; r_b = cmsg; }   // (r_a: filled in when the payload is laid out)
+#define REPLY_ERROR(code, cmsg) { rep = true; r_type = M_ERROR; r_a = code; r_b = cmsg; }
+#define CLIENT_REF(qb, qsrc) (qb)
+#define NODE_IX lane   // a node's index is its lane
+      #include "dt_node.inc"
 
       const u32 jd_mask = jcap ? (u32)__ballot(lane <= N + 1u && deliver_at <= T && !(is_node && wait_until <= T)) : 0u;
       const bool await_over = is_node && wait_until <= T;   // a node's due timer comes before its due message (DESIGN.md §2.2 R3)
       if (await_over) {   // Promise#await gave up (promise.rb:24-29): RPCError.timeout => error 0 to the client (node.rb:172), the lock is free
-        rep = true; r_type = M_ERROR; r_a = 0; r_b = cu[DC_CMSG];
+        REPLY_ERROR(0, cu[DC_CMSG]);
         unlock();
       } else if (lane <= N + 1u && deliver_at <= T) {
         const uint4 q = cm; deliver_at = INF;
         const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
         if (qsrc >= N && qsrc < LIN) s_recv_cl++; else s_recv_sv++;
         if (jcap) jwrite(n_ev + __popc(jd_mask & lt32), 1, q.y, qa, qb, qsrc, is_node ? lane : N + lane);
-        if (is_node) {
-          const u32 st = cu[DC_STAGE];
-          switch (qtype) {
-            case M_INIT:
-              if (lane != 0u) { rep = true; r_type = M_INIT_OK; r_b = qb; break; }
-              {   // the first node writes the initial state (:337-345): Tree.empty, then the root pointer
-                u32 *const r = g_rec;
-                r[0] = (128u << 16); r[1] = 0; r[2] = 0; __hip_atomic_store(r + 3, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const u32 rid = ++node_msgid;
-                cu[DC_STAGE] = DS_INIT_LEAF; cu[DC_CMSG] = qb; cu[DC_RPC] = rid;
-                send1(D_LWW, M_WRITE, 0, rid);
-              } break;
-            case M_TXN:
-              if (st == DS_IDLE) start_txn(qb, qa);
-              else { const u32 wqn = cu[DC_WQN];
-                if (wqn == DT_WAITQ) my_flags |= MSIM_FLAG_ARENA_OVERRUN;
-                else { cu[DC_WQ + 2u * wqn] = qb; cu[DC_WQ + 2u * wqn + 1u] = qa; cu[DC_WQN] = wqn + 1u; } }
-              break;
-            case M_READ_OK: case M_WRITE_OK: case M_CAS_OK: case M_ERROR:
-              switch (st) {
-                case DS_INIT_LEAF:
-                  if (qb != cu[DC_RPC]) break;
-                  { const u32 rid = ++node_msgid; cu[DC_STAGE] = DS_INIT_ROOT; cu[DC_RPC] = rid; send1(D_LIN, M_WRITE, 0, rid); }
-                  break;
-                case DS_INIT_ROOT:
-                  if (qb != cu[DC_RPC]) break;
-                  cu[DC_STAGE] = DS_IDLE; rep = true; r_type = M_INIT_OK; r_b = cu[DC_CMSG];
-                  break;
-                case DS_ROOT:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype != M_READ_OK) { rep = true; r_type = M_ERROR; r_a = 14; r_b = cu[DC_CMSG]; unlock(); break; }   // "Unsure how to handle" (:364)
-                  cu[DC_P1] = qa; cu[DC_T] = qa; cu[DC_PSTART] = next_p + 1u;
-                  { const u32 *const rr = rec_of(qa); const u32 rv2 = rr[2], rw3 = __hip_atomic_load(rr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); cu[DC_RV] = rv2; if ((rw3 >> (2u + lane)) & 1u) apply(); else load(qa); }
-                  break;
-                case DS_LOAD:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype == M_READ_OK) { atomicOr(rec_of(cu[DC_TARGET]) + 3, 1u << (2u + lane)); apply(); }   // @@cache[ptr] = tree (:95)
-                  else load(cu[DC_TARGET]);   // "Retrying read of tree node" (:97)
-                  break;
-                case DS_SAVE:
-                  if (qb < cu[DC_WLO] || qb >= cu[DC_WLO] + cu[DC_WN]) break;
-                  { const u32 left = cu[DC_WOUT] - 1u; cu[DC_WOUT] = left;
-                    if (left == 0u) { const u32 rid = ++node_msgid; cu[DC_STAGE] = DS_CAS; cu[DC_RPC] = rid;   // advance_root! (:376-388): cas root from the pointer read to the new one
-                      { u32 *const ce = g_cas + ((size_t)lane * DT_CASQ + (casn++ % DT_CASQ)) * 3u; ce[0] = rid; ce[1] = cu[DC_P1]; ce[2] = cu[DC_REF]; }
-                      send1(D_LIN, M_CAS, cu[DC_T], rid); wait_until = T + DT_AWAIT_US; } }
-                  break;
-                case DS_CAS:
-                  if (qb != cu[DC_RPC]) break;
-                  if (qtype == M_CAS_OK) reply_txn_ok();
-                  else { rep = true; r_type = M_ERROR; r_a = 30; r_b = cu[DC_CMSG]; }   // txn_conflict (:385)
-                  unlock();
-                  break;
-                default: break;   // "Ignoring reply ... with no callback" (node.rb:160-162)
-              }
-              break;
-            default: break;
-          }
-        } else if (is_lin) {   // lin-kv over the key "root" (service.clj:31-61)
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          if (qtype == M_READ) {
-            if (!root_exists) { o_type = M_ERROR; o_a = 20; } else { o_type = M_READ_OK; o_a = root; }
-          } else if (qtype == M_WRITE) { root = qa; root_exists = 1u; o_type = M_WRITE_OK; o_a = 0; }
-          else {   // cas, no create_if_not_exists.  The request is self-contained (:376-388): its `from` and its transaction come from the sender's
-            // table of cas requests under the msg_id, not from what the sender holds NOW (it may have given up on this cas and moved on)
-            u32 c_from = 0, c_ref = 0; bool c_hit = false;
-            { const u32 *const ce = g_cas + (size_t)qsrc * DT_CASQ * 3u;
-#pragma unroll
-              for (u32 i = 0; i < DT_CASQ; i++) { const u32 e0 = ce[3u * i], e1 = ce[3u * i + 1u], e2 = ce[3u * i + 2u]; if (e0 == qb) { c_hit = true; c_from = e1; c_ref = e2; } } }
-            if (!c_hit) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; o_type = M_ERROR; o_a = 22; }   // engine capacity: DT_CASQ outstanding cas requests per node
-            else if (!root_exists) { o_type = M_ERROR; o_a = 20; }
-            else if (root != c_from) { o_type = M_ERROR; o_a = 22; }
-            else {
-              const u32 ref = c_ref, off0 = ref & 0xFFFFFFu, n = ref >> 24, v = ++cur_v;
-              root = qa;
-              for (u32 i = 0; i < n; i++) { const u32 w = g_pay[off0 + i];
-                if (w & 1u) { const u32 k = (w >> 1) & 0x7FFFu, c = g_kvn[k]; if (g_first[k] == DT_NONE) g_first[k] = v;
-                  g_kv[k * mw + c] = ((w >> 16) & 0xFFu) | (v << 8); g_kvn[k] = c + 1u; } }
-              o_type = M_CAS_OK; o_a = 0;
-            }
-          }
-        } else {   // lww-kv (service.clj:214-243 as written): merge-source, merge-dest, then the replica that serves the request
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          svc_ctr += 2u;
-          const u32 r = scale32(draw32(key, 12u /* S_SVC */, svc_ctr++), 2);
-          u32 *const rp = rec_of(qa) + 3;   // (the replica bits; the nodes set their "loaded" bits in the same word: atomics)
-          if (qtype == M_WRITE) { atomicAnd(rp, ~3u); atomicOr(rp, r); o_type = M_WRITE_OK; o_a = qa; }
-          else if ((__hip_atomic_load(rp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 3u) == r) { o_type = M_READ_OK; o_a = qa; }
-          else { o_type = M_ERROR; o_a = 20; }
-        }
+        #include "dt_input.inc"
       }
       n_ev += __popc(jd_mask);
 
@@ -542,29 +255,7 @@ __global__ void __launch_bounds__(64) DT_OCC dt_kernel(const KParams p) {
       {
         const u32 incl = scan32(need_words);
         const u32 total = rdlane(incl, 31);
-        if (total) {
-          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) r_a = 0; }
-          else {
-            if (need_words) {
-              const u32 off0 = done_ref & 0xFFFFFFu, n = done_ref >> 24;
-              u32 pp = n_payload + incl - need_words;
-              r_a = pp | (need_words << 24);
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                if (w & 1u) { g_pay[pp++] = w; continue; }
-                const u32 vis = visible(k, done_rv);
-                u32 e = 0, acc = 0;
-                const u32 hdr = pp++;
-                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
-                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
-                  if ((wi & 1u) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
-                if (e & 3) g_pay[pp++] = acc;
-                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
-              }
-            }
-            n_payload += total;
-          }
-        }
+        #include "dt_reads.inc"
       }
 
       // COMMIT: ids in lane order (nodes, lin-kv, lww-kv); a node's messages in the order it emitted them: the answer to its client,

@@ -1,6 +1,7 @@
 // sim_kernel_kafkag.inc — the kafka workload (sim_kernel_kafka.inc: demo/clojure/kafka.clj over lin-kv) with SEVERAL WORKERS PER NODE
-// (`--concurrency k n`).  Included by sim_kernels.h after sim_kernel_kafka.inc, whose node, service, clients and generator it keeps statement
-// for statement, in the lane layout of sim_kernel_dtg.inc / txng / mkg / hatg: a lane is an ENDPOINT — nodes 0 .. N-1, client worker slots
+// (`--concurrency k n`).  Included by sim_kernels.h after sim_kernel_kafka.inc, whose node and service are the same text (kafka_node.inc,
+// kafka_blocks.inc, kafka_svc.inc) and whose clients and generator it repeats for a worker's lane, in the lane layout of sim_kernel_dtg.inc /
+// txng / mkg / hatg: a lane is an ENDPOINT — nodes 0 .. N-1, client worker slots
 // N .. N+CS-1 (a worker's process p talks to node p mod N), lin-kv at N+CS — every endpoint has a queue, clients poll only while an RPC is
 // outstanding, COMMIT is receiver-side.  A node has up to KFG_SLOTS request handlers in flight (with one worker per node: KF_SLOTS = 8).
 // Specification: oracle/kafka_nodes.inc, bit for bit (tests/test_parity_gpu.py::test_kafka_many_workers_parity, tests/test_hipemu_parity.py).
@@ -375,125 +376,16 @@ __global__ void __launch_bounds__(64) kafkag_kernel(const KParams p) {
         const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
         if (qsrc >= N && qsrc < SVC) s_recv_cl++; else s_recv_sv++;
         if (jcap) jwrite(n_ev + (u32)__popcll(jd_mask & lt_mask), 1, q.y, qa, qb, qsrc, lane);
-        {
-          // read the chunk of `offset` of key `k_` for handler `sl`
-          auto read_chunk = [&](u32 *sl, u32 fl, u32 k_, u32 offset) {
-            const u32 rid = ++node_msgid;
-            sl[2] = rid; sl[3] = (fl & ~(7u << 6)) | (k_ << 6); sl[5] = offset;
-            to_svc = true; o_type = M_READ; o_a = k_ | ((offset / KF_CHUNK) << 8); o_b = rid;
-          };
-          switch (qtype) {
-            case M_INIT: rep = true; rep_dest = qsrc; o_type = M_INIT_OK; o_b = qb; break;
-            case M_SEND: case M_POLL: case M_LIST_OFFSETS: case M_COMMIT_OFFSETS: {
-              u32 i = 0; while (i < KFG_SLOTS && KS_USED(my_slots[i * KSW + 3])) i++;
-              if (i == KFG_SLOTS) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; break; }
-              u32 *sl = my_slots + i * KSW;
-              sl[0] = qb | (qsrc << 24); sl[1] = 0; sl[4] = 0; sl[6] = 0; sl[7] = 0;   // (whose request it is rides with its msg_id)
-              if (qtype == M_SEND) {
-                sl[4] = (qa >> 6) << 16;
-                read_chunk(sl, KS_MAKE(KK_SEND, 1u, 0u, 0u, 0u), qa & 7u, my_cache[qa & 7u]);
-              } else if (qtype == M_POLL) {
-                const u32 nk = qa >> 24;
-                if (nk == 0) { rep = true; rep_dest = qsrc; o_type = M_POLL_OK; o_a = 0; o_b = qb; break; }   // no offsets: {:msgs {}}
-                sl[1] = qa & 0xFFFFFFu;
-                const u32 w = g_pay[qa & 0xFFFFFFu];
-                read_chunk(sl, KS_MAKE(KK_POLL, 1u, 0u, 0u, nk), w & 7u, w >> 8);
-              } else {
-                const u32 rid = ++node_msgid;
-                sl[1] = qa & 0xFFFFFFu; sl[2] = rid; sl[3] = KS_MAKE(qtype == M_LIST_OFFSETS ? KK_LIST : KK_COMMIT, 1u, 0u, 0u, qa >> 24);
-                to_svc = true; o_type = M_READ; o_a = KF_OFFSETS_KEY; o_b = rid;   // get-offsets, :141-147
-              }
-            } break;
-            case M_READ_OK: case M_CAS_OK: case M_ERROR: {
-              u32 i = 0;
-              while (i < KFG_SLOTS) { if (KS_USED(my_slots[i * KSW + 3]) && my_slots[i * KSW + 2] == qb) break; i++; }
-              if (i == KFG_SLOTS) break;  // handle-reply!: no such rpc
-              u32 *sl = my_slots + i * KSW;
-              const u32 fl = sl[3], k_ = KS_KEY(fl), off = sl[5], base = off - off % KF_CHUNK;
-              switch (KS_KIND(fl)) {
-                case KK_SEND:
-                  if (KS_STAGE(fl) == 1) {
-                    const u32 cnt = qtype == M_READ_OK ? qa : 0u;   // (exceptionally [_] [])
-                    my_cache[k_] = max(my_cache[k_], base + cnt);
-                    if (cnt >= KF_CHUNK) { my_cache[k_] = max(my_cache[k_], base + KF_CHUNK); read_chunk(sl, fl, k_, my_cache[k_]); break; }   // chunk full: recur
-                    const u32 rid = ++node_msgid;
-                    sl[2] = rid; sl[3] = (fl & ~(3u << 4)) | (2u << 4); sl[4] = (sl[4] & 0xFFFF0000u) | cnt;
-                    to_svc = true; o_type = M_CAS; o_a = k_ | ((off / KF_CHUNK) << 3) | (cnt << 9) | ((sl[4] >> 16) << 14); o_b = rid;
-                  } else {
-                    rep = true; rep_dest = sl[0] >> 24; o_b = sl[0] & 0xFFFFFFu;
-                    if (qtype == M_CAS_OK) { const u32 o = base + (sl[4] & 0xFFFFu); my_cache[k_] = max(my_cache[k_], o + 1u); o_type = M_SEND_OK; o_a = o; }
-                    else { o_type = M_ERROR; o_a = qa == 22 ? 30u : qa; }   // "cas conflict", :108-110
-                    sl[3] = 0;
-                  }
-                  break;
-                case KK_POLL: {
-                  const u32 cnt = qtype == M_READ_OK ? qa : 0u, j = KS_J(fl), nk = KS_NK(fl);
-                  my_cache[k_] = max(my_cache[k_], base + cnt);
-                  sl[6 + (j >> 2)] |= cnt << (8u * (j & 3u));
-                  if (j + 1 < nk) { const u32 w = g_pay[sl[1] + j + 1]; read_chunk(sl, (fl & ~(15u << 9)) | ((j + 1u) << 9), w & 7u, w >> 8); break; }
-                  // poll_ok: sized here, written below (payload words are handed out in node order)
-                  rep = true; rep_dest = sl[0] >> 24; o_type = M_POLL_OK; o_b = sl[0] & 0xFFFFFFu; done_slot = i;
-                  for (u32 e = 0; e < nk; e++) {
-                    const u32 w = g_pay[sl[1] + e], i0 = (w >> 8) % KF_CHUNK, c = (sl[6 + (e >> 2)] >> (8u * (e & 3u))) & 0xFFu;
-                    const u32 n = c > i0 ? c - i0 : 0u;
-                    need_words += 1u + (n + 1u) / 2u;
-                  }
-                } break;
-                case KK_LIST:
-                  rep = true; rep_dest = sl[0] >> 24; o_type = M_LIST_OFFSETS_OK; o_b = sl[0] & 0xFFFFFFu; done_slot = i;
-                  sl[4] = qtype == M_READ_OK ? qa : KF_ABSENT;   // (exceptionally [res] {})
-                  need_words = KS_NK(fl);
-                  break;
-                default:   // KK_COMMIT
-                  if (KS_STAGE(fl) == 1) {
-                    const u32 from = qtype == M_READ_OK ? qa : KF_ABSENT, rid = ++node_msgid;
-                    sl[2] = rid; sl[3] = (fl & ~(3u << 4)) | (2u << 4); sl[4] = from;
-                    to_svc = true; o_type = M_CAS; o_a = KF_OFFSETS_KEY | from | (i << 16); o_b = rid;
-                  } else {
-                    rep = true; rep_dest = sl[0] >> 24; o_b = sl[0] & 0xFFFFFFu;
-                    if (qtype == M_CAS_OK) { o_type = M_COMMIT_OFFSETS_OK; o_a = 0; } else { o_type = M_ERROR; o_a = qa == 22 ? 30u : qa; }
-                    sl[3] = 0;
-                  }
-                  break;
-              }
-            } break;
-            default: break;
-          }
-        }
+#define KF_NSLOTS KFG_SLOTS
+#define REPLY_TO(cmsg) { rep = true; rep_dest = (cmsg) >> 24; o_b = (cmsg) & 0xFFFFFFu; }
+#define CLIENT_REF(qb, qsrc) ((qb) | ((qsrc) << 24))   // a client is an endpoint: it rides in the top byte of the stored msg_id
+        #include "kafka_node.inc"
       }
       // poll_ok / list_committed_offsets_ok blocks: payload words allocated in node order, each node writes its own
       {
         const u32 incl = wave_incl_scan(need_words);
         const u32 total = rdlane(incl, 63);
-        if (total) {
-          const bool fits = n_payload + total <= max_pay;
-          if (!fits) flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
-          if (need_words) {
-            u32 *sl = my_slots + done_slot * KSW;
-            if (!fits) { rep = false; sl[3] = 0; }   // (the oracle drops the reply with the handler)
-            else {
-              const u32 fl = sl[3], nk = KS_NK(fl);
-              u32 pp = n_payload + incl - need_words;
-              o_a = pp | (need_words << 24);
-              if (KS_KIND(fl) == KK_POLL) {
-                for (u32 e = 0; e < nk; e++) {
-                  const u32 w = g_pay[sl[1] + e], k_ = w & 7u, o = w >> 8, i0 = o % KF_CHUNK, c = (sl[6 + (e >> 2)] >> (8u * (e & 3u))) & 0xFFu;
-                  const u32 n = c > i0 ? c - i0 : 0u;
-                  g_pay[pp++] = k_ | (n << 8) | (o << 16);
-                  for (u32 x = 0; x < n; x += 2) g_pay[pp++] = g_log[(size_t)k_ * cap + o + x] | (x + 1 < n ? g_log[(size_t)k_ * cap + o + x + 1] << 16 : 0u);
-                }
-              } else {
-                const u32 ver = sl[4];
-                for (u32 e = 0; e < nk; e++) {
-                  const u32 k_ = g_pay[sl[1] + e] & 7u, c = ver == KF_ABSENT ? 0u : committed_at(k_, ver);
-                  g_pay[pp++] = k_ | (c ? (((c - 1u) << 8) | 0x80000000u) : 0u);   // select-keys: only the keys the map has
-                }
-              }
-              sl[3] = 0;
-            }
-          }
-          if (fits) n_payload += total;
-        }
+        #include "kafka_blocks.inc"
       }
       __syncthreads();   // the service reads the handlers' tables (LDS) after the nodes have written them
       // the lin-kv service (service.clj:31-61 over the chunk keys and "offsets"): one request per round, after the nodes
@@ -502,40 +394,7 @@ __global__ void __launch_bounds__(64) kafkag_kernel(const KParams p) {
         const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
         s_recv_sv++;
         if (jcap) jwrite(n_ev + (u32)__popcll(jd_mask & lt_mask), 1, q.y, qa, qb, qsrc, SVC);
-        svc_rep = true; o_dest = qsrc; o_b = qb;
-        if (qtype == M_READ) {
-          if (qa & KF_OFFSETS_KEY) { if (off_exists) { o_type = M_READ_OK; o_a = off_ver; } else { o_type = M_ERROR; o_a = 20; } }
-          else { const u32 c = chunk_count(qa & 7u, qa >> 8); if (c) { o_type = M_READ_OK; o_a = c; } else { o_type = M_ERROR; o_a = 20; } }
-        } else if (qtype == M_CAS) {
-          if (qa & KF_OFFSETS_KEY) {
-            const u32 from = qa & 0xFFFFu, i = (qa >> 16) & 0x7Fu;
-            if (off_exists && from != off_ver) { o_type = M_ERROR; o_a = 22; }   // (from {} never equals a stored map: they are not empty)
-            else {
-              // the value did not change since it was read (or the key is created): to = (merge-with max from (:offsets body))
-              const u32 *sl = slots + (qsrc * KFG_SLOTS + i) * KSW;
-              u32 pp = sl[1]; const u32 end = pp + KS_NK(sl[3]), newver = off_ver + 1u; bool changed = false;
-              while (pp < end) {
-                const u32 h = g_pay[pp], k_ = h & 7u, n = (h >> 8) & 0xFFu, o = h >> 16;
-                pp += 1u + (n + 1u) / 2u;
-                if (!n) continue;   // txn-offsets: only keys something was polled from
-                const u32 hi = o + n - 1u, cur = committed_at(k_, off_ver);
-                if (cur == 0 || hi > cur - 1u) { const u32 e = nupd[k_]; g_upd[(size_t)k_ * (cap + 1) + e] = (newver << 16) | hi; nupd[k_] = e + 1u; changed = true; }
-              }
-              off_exists = 1;
-              if (changed) off_ver = newver;
-              o_type = M_CAS_OK; o_a = 0;
-            }
-          } else {
-            const u32 k_ = qa & 7u, ch = (qa >> 3) & 63u, from = (qa >> 9) & 31u, msg = qa >> 14;
-            const u32 cur = chunk_count(k_, ch);
-            if (cur != 0 && cur != from) { o_type = M_ERROR; o_a = 22; }
-            else {   // the chunk is what was read, or does not exist (create_if_not_exists, :52-55): it becomes that + [msg]
-              const u32 o = ch * KF_CHUNK + (cur ? from : 0u);
-              if (o >= cap) { my_flags |= MSIM_FLAG_VALUES_OVERFLOW; o_type = M_ERROR; o_a = 22; }
-              else { g_log[(size_t)k_ * cap + o] = msg; klen[k_] = o + 1u; o_type = M_CAS_OK; o_a = 0; }
-            }
-          }
-        } else svc_rep = false;
+        #include "kafka_svc.inc"
       }
       __syncthreads();
       n_ev += (u32)__popcll(jd_mask);

@@ -1,6 +1,6 @@
 // sim_kernel_mkg.inc — the multi-key transactional node (sim_kernel_mk.inc: demo/js/multi_key_txn.js:1-246 over lin-kv + lww-kv) with SEVERAL
-// WORKERS PER NODE (`--concurrency k n`).  Included by sim_kernels.h after sim_kernel_mk.inc, whose slot layout (SK_*), node and services it
-// keeps statement for statement, in the lane layout of sim_kernel_dtg.inc / sim_kernel_txng.inc: a lane is an ENDPOINT — nodes 0 .. N-1,
+// WORKERS PER NODE (`--concurrency k n`).  Included by sim_kernels.h after sim_kernel_mk.inc, whose slot layout (SK_*) it
+// uses and whose node and services are the same text (mk_node.inc, mk_input.inc, mk_reads.inc), in the lane layout of sim_kernel_dtg.inc / sim_kernel_txng.inc: a lane is an ENDPOINT — nodes 0 .. N-1,
 // client worker slots N .. N+CS-1 (worker t talks to node t mod N), lin-kv at N+CS, lww-kv at N+CS+1 — every endpoint has a queue, clients
 // poll only while an RPC is outstanding, COMMIT is receiver-side.  A node has up to MKG_SLOTS transactions in flight (with one worker per
 // node: MK_SLOTS = 8, mk_kernel<> / mk8_kernel<>), the first MK_SL of them in LDS.
@@ -123,23 +123,8 @@ __global__ void __launch_bounds__(64) mkg_kernel(const KParams p) {
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
-    auto complete = [&](u32 type, u32 err, u32 ref) {
-      busy = false;
-      if (kind != K_OP) { if (type != MSIM_T_OK) my_flags |= MSIM_FLAG_ROUND_LIMIT; return; }
-      cmp_row = true; cmp_packed = type | (MSIM_F_TXN << 2) | (err << 7) | (process << 12);
-      cmp_value = ref & 0xFFFFFFu; cmp_len = ref >> 24;
-      if (type == MSIM_T_INFO) process += C;  // crashed process; the Reusable client itself lives on
-    };
-    // the client's recv! consumes one envelope (client.clj:94-107)
-    auto client_deliver = [&](u32 qtype, u32 qa, u32 qb) {
-      s_recv_cl++;
-      if (busy && qb == want) {
-        if (qtype == M_TXN_OK) complete(MSIM_T_OK, 0, qa);
-        else if (qtype == M_ERROR)
-          complete(MSIM_T_FAIL, qa == 11 ? MSIM_ERR_TEMPORARILY_UNAVAILABLE : qa == 20 ? MSIM_ERR_KEY_DOES_NOT_EXIST : qa == 30 ? MSIM_ERR_TXN_CONFLICT : MSIM_ERR_PRECONDITION_FAILED, c_value);
-        else complete(MSIM_T_OK, 0, c_value);  // init_ok
-      }
-    };
+#define CRASH_STRIDE C
+    #include "list_append_client.inc"
 
     if (timeout_round) {
       if (busy && timeout_at <= T) complete(MSIM_T_INFO, MSIM_ERR_NET_TIMEOUT, c_value);
@@ -203,187 +188,17 @@ __global__ void __launch_bounds__(64) mkg_kernel(const KParams p) {
       u32 rep_dest = 0;
       u32 n_out = 0, o_dest = 0;           // node -> service: n_out messages in mout[lane][..], all to the same service
       u32 o_type = 0, o_a = 0, o_b = 0, o_to = 0, need_words = 0, done_slot = 0;
-      u32 *const my_out = mout + lane * (MK_KEYS * 3u);
-      auto out_msg = [&](u32 dest, u32 type, u32 a, u32 b) { o_dest = dest; my_out[n_out * 3u] = type; my_out[n_out * 3u + 1u] = a; my_out[n_out * 3u + 2u] = b; n_out++; };
-      // the node's thunk cache (multi_key_txn.js:17,80-106): one bit per thunk id <node>.<i>, [owner][i / 32] in the first N x TC / 32 words of the
-      // node's CC-word area
-      auto cached = [&](u32 tid) -> bool { const u32 i = tid & 0xFFFFFu; return (my_cache[(tid >> 20) * (TC >> 5) + (i >> 5)] >> (i & 31u)) & 1u; };
-      auto cache_add = [&](u32 tid) { const u32 i = tid & 0xFFFFFu; my_cache[(tid >> 20) * (TC >> 5) + (i >> 5)] |= 1u << (i & 31u); };
-      // the thunk the root of version v names for `k` (MK_NONE: the map does not have the key)
-      auto thunk_of = [&](u32 k, u32 v) -> u32 {
-        const u32 first = g_first[k], cnt = g_updn[k];   // (never entered: MK_NONE > any version)
-        if (first > v) return MK_NONE;
-        if (mw1 <= 17u) {   // the versions of the key's thunks grow along the row: count those <= v with independent loads, then one more for the id
-          u32 row[17];
-#pragma unroll
-          for (u32 i = 0; i < 17u; i++) row[i] = i < cnt ? g_upd_v[k * mw1 + i] : 0xFFFFFFFFu;
-          u32 n = 0;
-#pragma unroll
-          for (u32 i = 0; i < 17u; i++) n += (i < cnt && row[i] <= v) ? 1u : 0u;
-          return n ? g_upd_t[k * mw1 + n - 1u] : MK_NONE;
-        }
-        u32 t = MK_NONE;
-        for (u32 i = 0; i < cnt && g_upd_v[k * mw1 + i] <= v; i++) t = g_upd_t[k * mw1 + i];
-        return t;
-      };
-      auto send_cas = [&](u32 *sl, u32 si) {   // casRoot, :120-137
-        const u32 rid = ++node_msgid;
-        sl[SK_HDR] = 1u | (3u << 8); sl[SK_RPC] = rid;
-        out_msg(D_LIN, M_CAS, sl[SK_RV] | (si << 16), rid);
-      };
-      // writeThunks (:160-177): state2's keys in insertion order — the thunks read, then the keys the transaction creates
-      auto begin_writes = [&](u32 *sl, u32 si) {
-        const u32 nk = sl[SK_NK], ns = sl[SK_NSTATE];
-        u32 ord[MK_KEYS], n = 0, in_state = 0;
-        for (u32 i = 0; i < ns; i++) { const u32 j = sl[SK_SORD + i]; ord[n++] = j; in_state |= 1u << j; }
-        for (u32 i = 0; i <= MK_KEYS; i++)
-          for (u32 j = 0; j < nk; j++) if (!((in_state >> j) & 1u) && sl[SK_WR + j] && sl[SK_FA + j] == i) ord[n++] = j;
-        sl[SK_HDR] = 1u | (2u << 8); sl[SK_NNEW] = 0;
-        u32 wr_out = 0;
-        for (u32 i = 0; i < n; i++) {
-          const u32 j = ord[i];
-          if (!sl[SK_WR + j]) continue;
-          if (next_tid >= TC) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; continue; }   // engine capacity
-          const u32 tid = (lane << 20) | next_tid++;
-          cache_add(tid);
-          const u32 rid = ++node_msgid;
-          sl[SK_WRTID + j] = tid; sl[SK_WRRPC + j] = rid; wr_out++;
-          out_msg(D_LWW, M_WRITE, tid, rid);
-        }
-        sl[SK_WROUT] = wr_out;
-        if (wr_out == 0) send_cas(sl, si);
-      };
-      auto thunk_ready = [&](u32 *sl, u32 j) { const u32 ns = sl[SK_NSTATE]; sl[SK_SORD + ns] = j; sl[SK_NSTATE] = ns + 1u; sl[SK_RDRPC + j] = 0; };
-      // transact (:213-236) from the node's cached root; getState (:141-156) walks the root's keys in map order
-      auto start_attempt = [&](u32 *sl, u32 si) {
-        const u32 nk = sl[SK_NK], rv = root_v;
-        sl[SK_RV] = rv; sl[SK_HDR] = 1u | (1u << 8); sl[SK_NSTATE] = 0;
-        u32 posn[MK_KEYS], tids[MK_KEYS], rd_out = 0;
-        for (u32 j = 0; j < nk; j++) { sl[SK_RDRPC + j] = 0; const u32 k = sl[SK_KEY + j]; tids[j] = thunk_of(k, rv); posn[j] = tids[j] == MK_NONE ? MK_NONE : g_pos[k]; }
-        for (u32 done = 0;;) {   // ascending position in the root map
-          u32 best = MK_NONE, bj = 0;
-          for (u32 j = 0; j < nk; j++) if (!((done >> j) & 1u) && posn[j] < best) { best = posn[j]; bj = j; }
-          if (best == MK_NONE) break;
-          done |= 1u << bj;
-          if (cached(tids[bj])) thunk_ready(sl, bj);
-          else { const u32 rid = ++node_msgid; sl[SK_RDTID + bj] = tids[bj]; sl[SK_RDRPC + bj] = rid; rd_out++; out_msg(D_LWW, M_READ, tids[bj], rid); }
-        }
-        sl[SK_RDOUT] = rd_out;
-        if (rd_out == 0) begin_writes(sl, si);
-      };
+#define MK_NSLOTS MKG_SLOTS
+#define REPLY_TO(cmsg) { rep = true; rep_dest = (cmsg) >> 24; o_b = (cmsg) & 0xFFFFFFu; }
+#define CLIENT_REF(qb, qsrc) ((qb) | ((qsrc) << 24))   // a client is an endpoint: it rides in the top byte of the stored msg_id
+      #include "mk_node.inc"
       const u64 jd_mask = jcap ? __ballot(is_server && deliver_at <= T) : 0ull;
       if (is_server && deliver_at <= T) {
         const uint4 q = cm; deliver_at = INF;
         const u32 qsrc = q.w >> 24, qb = q.w & 0xFFFFFFu, qtype = q.y & 0xFFu, qa = q.z;
         if (qsrc >= N && qsrc < LIN) s_recv_cl++; else s_recv_sv++;
         if (jcap) jwrite(n_ev + (u32)__popcll(jd_mask & lt_mask), 1, q.y, qa, qb, qsrc, lane);
-        if (is_node) {
-          switch (qtype) {
-            case M_INIT: rep = true; rep_dest = qsrc; o_type = M_INIT_OK; o_b = qb; break;
-            case M_TXN: {
-              u32 si = 0; while (si < MKG_SLOTS && (slot_of(my_node, si)[SK_HDR] & 0xFFu)) si++;
-              if (si == MKG_SLOTS) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; break; }   // engine capacity; the reference has no bound
-              u32 *const sl = slot_of(my_node, si);
-              for (u32 i = 0; i < MKW; i++) sl[i] = 0;
-              sl[SK_HDR] = 1u; sl[SK_CMSG] = qb | (qsrc << 24); sl[SK_REF] = qa;   // (whose transaction it is rides with its msg_id)
-              const u32 off0 = qa & 0xFFFFFFu, n = qa >> 24;
-              u32 nk = 0;
-              for (u32 i = 0; i < n; i++) {   // readSet / writeSet (:180-197)
-                const u32 w = g_pay[off0 + i], k = (w >> 1) & 0x7FFFu;
-                u32 j = 0; while (j < nk && sl[SK_KEY + j] != k) j++;
-                if (j == nk) { sl[SK_KEY + j] = k; nk++; }
-                if ((w & 1u) && !sl[SK_WR + j]) { sl[SK_WR + j] = 1u; sl[SK_FA + j] = i; }
-              }
-              sl[SK_NK] = nk;
-              start_attempt(sl, si);
-            } break;
-            case M_READ_OK: case M_WRITE_OK: case M_CAS_OK: case M_ERROR: {
-              bool found = false;
-              for (u32 si = 0; si < MKG_SLOTS && !found; si++) {
-                u32 *const sl = slot_of(my_node, si);
-                const u32 hdr = sl[SK_HDR];
-                if (!(hdr & 0xFFu)) continue;
-                const u32 stage_ = (hdr >> 8) & 0xFFu, nk = sl[SK_NK];
-                if (stage_ == 1u) {
-                  for (u32 j = 0; j < nk; j++) if (qb && sl[SK_RDRPC + j] == qb) {
-                    found = true;
-                    const u32 tid = sl[SK_RDTID + j];
-                    if (qtype == M_READ_OK) { cache_add(tid); thunk_ready(sl, j); sl[SK_RDOUT]--; }
-                    else if (qa == 20u) {   // not on the replica that answered: getThunk again (:92-96), from the cache if it is there by now
-                      if (cached(tid)) { thunk_ready(sl, j); sl[SK_RDOUT]--; }
-                      else { const u32 rid = ++node_msgid; sl[SK_RDRPC + j] = rid; out_msg(D_LWW, M_READ, tid, rid); }
-                    }
-                    if (sl[SK_RDOUT] == 0) begin_writes(sl, si);
-                    break;
-                  }
-                } else if (stage_ == 2u) {
-                  for (u32 j = 0; j < nk; j++) if (qb && sl[SK_WR + j] && sl[SK_WRRPC + j] == qb) {
-                    found = true;
-                    sl[SK_WRRPC + j] = 0;
-                    if (thunk_of(sl[SK_KEY + j], sl[SK_RV]) == MK_NONE) { const u32 nn = sl[SK_NNEW]; sl[SK_NORD + nn] = j; sl[SK_NNEW] = nn + 1u; }
-                    if (--sl[SK_WROUT] == 0) send_cas(sl, si);
-                    break;
-                  }
-                } else if (sl[SK_RPC] == qb) {
-                  found = true;
-                  if (stage_ == 3u) {
-                    if (qtype == M_CAS_OK) {   // :226-229: the cached root becomes the new map, the client gets the completed transaction
-                      u32 writes = 0; for (u32 j = 0; j < nk; j++) writes |= sl[SK_WR + j];
-                      const u32 rv = sl[SK_RV];
-                      root_v = rv + (writes ? 1u : 0u);
-                      rep = true; rep_dest = sl[SK_CMSG] >> 24; o_type = M_TXN_OK; o_b = sl[SK_CMSG] & 0xFFFFFFu; done_slot = si;
-                      const u32 ref = sl[SK_REF], off0 = ref & 0xFFFFFFu, n = ref >> 24;
-                      for (u32 j = 0; j < n; j++) {
-                        const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                        need_words++;
-                        if (!(w & 1u)) {
-                          u32 len = visible(k, rv);
-                          for (u32 e = 0; e < j; e++) { const u32 we = g_pay[off0 + e]; if ((we & 1u) && ((we >> 1) & 0x7FFFu) == k) len++; }
-                          need_words += (len + 3u) / 4u;
-                        }
-                      }
-                    } else { const u32 rid = ++node_msgid; sl[SK_HDR] = 1u | (4u << 8); sl[SK_RPC] = rid; out_msg(D_LIN, M_READ, 0, rid); }   // :230-234
-                  } else {   // getRoot (:112-116)
-                    root_v = qtype == M_READ_OK ? qa : 0u;
-                    start_attempt(sl, si);
-                  }
-                }
-              }
-            } break;   // no handler under that id: ignored (node.js:152-156)
-            default: break;
-          }
-        } else if (is_lin) {   // lin-kv over the key "root" (service.clj:31-61)
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          if (qtype == M_READ) {
-            if (!root_exists) { o_type = M_ERROR; o_a = 20; } else { o_type = M_READ_OK; o_a = cur_v; }
-          } else {   // cas with create_if_not_exists
-            const u32 from = qa & 0xFFFFu, si = qa >> 16;
-            if (root_exists && cur_v != from) { o_type = M_ERROR; o_a = 22; }
-            else {
-              const u32 *const sl = slot_of(qsrc, si);
-              const u32 nk = sl[SK_NK], ref = sl[SK_REF], off0 = ref & 0xFFFFFFu, n = ref >> 24;
-              u32 writes = 0; for (u32 j = 0; j < nk; j++) writes |= sl[SK_WR + j];
-              root_exists = 1u;
-              if (writes) {
-                const u32 v = ++cur_v;
-                const u32 nn = sl[SK_NNEW];
-                for (u32 i = 0; i < nn; i++) { const u32 k = sl[SK_KEY + sl[SK_NORD + i]]; g_pos[k] = n_order++; g_first[k] = v; }
-                for (u32 j = 0; j < nk; j++) if (sl[SK_WR + j]) { const u32 k = sl[SK_KEY + j], c = g_updn[k]; g_upd_v[k * mw1 + c] = v; g_upd_t[k * mw1 + c] = sl[SK_WRTID + j]; g_updn[k] = c + 1u; }
-                for (u32 i = 0; i < n; i++) { const u32 w = g_pay[off0 + i];
-                  if (w & 1u) { const u32 k = (w >> 1) & 0x7FFFu, c = g_kvn[k]; g_kv[k * mw + c] = ((w >> 16) & 0xFFu) | (v << 8); g_kvn[k] = c + 1u; } }
-              }
-              o_type = M_CAS_OK; o_a = 0;
-            }
-          }
-        } else {   // lww-kv (service.clj:214-243 as written): merge-source, merge-dest, then the replica that serves the request
-          svc_rep = true; o_to = qsrc; o_b = qb;
-          svc_ctr += 2u;   // (merge-source and merge-dest are drawn and dropped)
-          const u32 r = scale32(draw32(key, 12u /* S_SVC */, svc_ctr++), 2), tid = qa, tn = tid >> 20, ti = tid & 0xFFFFFu;
-          unsigned char *const rp = g_rep + (size_t)tn * TC + ti;
-          if (qtype == M_WRITE) { *rp = (unsigned char)r; o_type = M_WRITE_OK; o_a = tid; }
-          else if (*rp == r) { o_type = M_READ_OK; o_a = tid; }
-          else { o_type = M_ERROR; o_a = 20; }
-        }
+        #include "mk_input.inc"
       }
       n_ev += (u32)__popcll(jd_mask);
 
@@ -391,31 +206,7 @@ __global__ void __launch_bounds__(64) mkg_kernel(const KParams p) {
       {
         const u32 incl = wave_incl_scan(need_words);
         const u32 total = rdlane(incl, 63);
-        if (total) {
-          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) { o_a = 0; slot_of(my_node, done_slot)[SK_HDR] = 0; } }
-          else {
-            if (need_words) {
-              const u32 *const sl = slot_of(my_node, done_slot);
-              const u32 ref = sl[SK_REF], off0 = ref & 0xFFFFFFu, n = ref >> 24, from = sl[SK_RV];
-              u32 pp = n_payload + incl - need_words;
-              o_a = pp | (need_words << 24);
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                if (w & 1u) { g_pay[pp++] = w; continue; }
-                const u32 vis = visible(k, from);
-                u32 e = 0, acc = 0;
-                const u32 hdr = pp++;
-                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
-                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
-                  if ((wi & 1u) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
-                if (e & 3) g_pay[pp++] = acc;
-                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
-              }
-              slot_of(my_node, done_slot)[SK_HDR] = 0;
-            }
-            n_payload += total;
-          }
-        }
+        #include "mk_reads.inc"
       }
 
       // COMMIT: ids in lane order (nodes, lin-kv, lww-kv); a node's messages in the order it emitted them; every receiver takes its own in

@@ -101,23 +101,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
-    auto complete = [&](u32 type, u32 err, u32 ref) {
-      busy = false;
-      if (kind != K_OP) { if (type != MSIM_T_OK) my_flags |= MSIM_FLAG_ROUND_LIMIT; return; }
-      cmp_row = true; cmp_packed = type | (MSIM_F_TXN << 2) | (err << 7) | (process << 12);
-      cmp_value = ref & 0xFFFFFFu; cmp_len = ref >> 24;
-      if (type == MSIM_T_INFO) process += N;  // crashed process; the Reusable client itself lives on
-    };
-    // the client's recv! consumes one envelope (client.clj:94-107)
-    auto client_deliver = [&](u32 qtype, u32 qa, u32 qb) {
-      s_recv_cl++;
-      if (busy && qb == want) {
-        if (qtype == M_TXN_OK) complete(MSIM_T_OK, 0, qa);
-        else if (qtype == M_ERROR)
-          complete(MSIM_T_FAIL, qa == 11 ? MSIM_ERR_TEMPORARILY_UNAVAILABLE : qa == 20 ? MSIM_ERR_KEY_DOES_NOT_EXIST : qa == 30 ? MSIM_ERR_TXN_CONFLICT : MSIM_ERR_PRECONDITION_FAILED, c_value);
-        else complete(MSIM_T_OK, 0, c_value);  // init_ok
-      }
-    };
+#define CRASH_STRIDE N
+    #include "list_append_client.inc"
 
     if (timeout_round) {
       if (busy && timeout_at <= T) complete(MSIM_T_INFO, MSIM_ERR_NET_TIMEOUT, c_value);
@@ -172,7 +157,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
 
       // ---- R3: one input per node, then one for the service (endpoint order) ----
       bool to_svc = false, rep = false, svc_rep = false;   // node -> service, node -> own client, service -> node
-      u32 o_type = 0, o_a = 0, o_b = 0, o_dest = 0, need_words = 0, done_slot = 0;
+      u32 rep_type = 0, rep_a = 0, rep_b = 0, o_dest = 0, need_words = 0, done_slot = 0;
       const u32 jd_mask = jcap ? (u32)__ballot(lane <= N && deliver_at <= T) : 0u;
       if (lane <= N && deliver_at <= T) {
         const uint4 q = cm; deliver_at = INF;
@@ -181,13 +166,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
         if (jcap) jwrite(n_ev + __popc(jd_mask & lt32), 1, q.y, qa, qb, qsrc, is_svc ? SVC : lane);
         if (is_node) {
           switch (qtype) {
-            case M_INIT: rep = true; o_type = M_INIT_OK; o_b = qb; break;
+            case M_INIT: rep = true; rep_type = M_INIT_OK; rep_b = qb; break;
             case M_TXN: {
               u32 i = 0; while (i < TXN_SLOTS && (my_slots[i].w >> 24)) i++;
               if (i == TXN_SLOTS) { my_flags |= MSIM_FLAG_ARENA_OVERRUN; break; }
               const u32 rid = ++node_msgid;
               my_slots[i] = make_uint4(qb, qa, rid, (1u << 16) | (1u << 24));
-              to_svc = true; o_type = M_READ; o_a = 0; o_b = rid;
+              to_svc = true; rep_type = M_READ; rep_a = 0; rep_b = rid;
             } break;
             case M_READ_OK: case M_CAS_OK: case M_ERROR: {
               u32 i = 0;
@@ -198,15 +183,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
                 u32 from;
                 if (qtype == M_READ_OK) from = qa;
                 else if (qtype == M_ERROR && qa == 20) from = V_NIL;
-                else { rep = true; o_type = M_ERROR; o_a = qa; o_b = s.x; my_slots[i] = make_uint4(0, 0, 0, 0); break; }
+                else { rep = true; rep_type = M_ERROR; rep_a = qa; rep_b = s.x; my_slots[i] = make_uint4(0, 0, 0, 0); break; }
                 const u32 rid = ++node_msgid;
                 s.z = rid; s.w = from | (2u << 16) | (1u << 24);
                 my_slots[i] = s;
-                to_svc = true; o_type = M_CAS; o_a = from | (i << 16); o_b = rid;
+                to_svc = true; rep_type = M_CAS; rep_a = from | (i << 16); rep_b = rid;
               } else {
-                rep = true; o_b = s.x;
+                rep = true; rep_b = s.x;
                 if (qtype == M_CAS_OK) {  // the completed transaction goes into the payload area (sized here, written below)
-                  o_type = M_TXN_OK; done_slot = i;
+                  rep_type = M_TXN_OK; done_slot = i;
                   const u32 off0 = s.y & 0xFFFFFFu, n = s.y >> 24, from = s.w & 0xFFFFu;
                   for (u32 j = 0; j < n; j++) {
                     const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
@@ -217,31 +202,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
                       need_words += (len + 3) / 4;
                     }
                   }
-                } else { o_type = M_ERROR; o_a = qa == 22 ? 30u : qa; my_slots[i] = make_uint4(0, 0, 0, 0); }
+                } else { rep_type = M_ERROR; rep_a = qa == 22 ? 30u : qa; my_slots[i] = make_uint4(0, 0, 0, 0); }
               }
             } break;
             default: break;
           }
         } else {  // the lin-kv service (service.clj:31-61 over the key "root")
-          svc_rep = true; o_dest = qsrc; o_b = qb;
-          if (qtype == M_READ) {
-            if (root == V_NIL) { o_type = M_ERROR; o_a = 20; } else { o_type = M_READ_OK; o_a = root; }
-          } else {  // cas with create_if_not_exists
-            const u32 from = qa & 0xFFFFu, i = qa >> 16;
-            if (root != V_NIL && root != from) { o_type = M_ERROR; o_a = 22; }
-            else {
-              const u32 base = root == V_NIL ? 0u : root;
-              const u32 ref = slots[qsrc * TXN_SLOTS + i].y, off0 = ref & 0xFFFFFFu, n = ref >> 24;
-              u32 na = 0;
-              for (u32 j = 0; j < n; j++) na += g_pay[off0 + j] & 1;
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j];
-                if (w & 1) { const u32 k = (w >> 1) & 0x7FFFu; const u32 c = g_kvn[k]; g_kv[k * mw + c] = ((w >> 16) & 0xFFu) | ((base + na) << 8); g_kvn[k] = c + 1; }
-              }
-              root = base + na;
-              o_type = M_CAS_OK; o_a = 0;
-            }
-          }
+          svc_rep = true; o_dest = qsrc; rep_b = qb;
+#define TXN_REF_OF(node, i) slots[(node) * TXN_SLOTS + (i)].y
+          #include "txn_lin.inc"
         }
       }
       n_ev += __popc(jd_mask);
@@ -250,31 +219,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
       {
         const u32 incl = scan32(need_words);
         const u32 total = rdlane(incl, 31);
-        if (total) {
-          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) { o_a = 0; my_slots[done_slot] = make_uint4(0, 0, 0, 0); } }
-          else {
-            if (need_words) {
-              const uint4 s = my_slots[done_slot];
-              const u32 off0 = s.y & 0xFFFFFFu, n = s.y >> 24, from = s.w & 0xFFFFu;
-              u32 pp = n_payload + incl - need_words;
-              o_a = pp | (need_words << 24);
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                if (w & 1) { g_pay[pp++] = w; continue; }
-                const u32 vis = visible(k, from);
-                u32 e = 0, acc = 0;
-                const u32 hdr = pp++;
-                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
-                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
-                  if ((wi & 1) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
-                if (e & 3) g_pay[pp++] = acc;
-                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
-              }
-              my_slots[done_slot] = make_uint4(0, 0, 0, 0);
-            }
-            n_payload += total;
-          }
-        }
+        #include "txn_reads.inc"
       }
 
       // COMMIT: ids in lane order (nodes, then the service)
@@ -290,20 +235,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
           u32 ts = (u32)__ballot(to_svc);
           while (ts) {
             const u32 s = (u32)__builtin_ctz(ts); ts &= ts - 1;
-            const u32 ty = rdlane(o_type, s), a = rdlane(o_a, s), b = rdlane(o_b, s), off = rdlane(my_off, s);
+            const u32 ty = rdlane(rep_type, s), a = rdlane(rep_a, s), b = rdlane(rep_b, s), off = rdlane(my_off, s);
             if (is_svc) arrive(next_id + off, ty, a, b, s, SVC);
           }
           // service -> node
           const u32 sv = (u32)__ballot(svc_rep);
           if (sv) {
-            const u32 ty = rdlane(o_type, N), a = rdlane(o_a, N), b = rdlane(o_b, N), d = rdlane(o_dest, N), off = rdlane(my_off, N);
+            const u32 ty = rdlane(rep_type, N), a = rdlane(rep_a, N), b = rdlane(rep_b, N), d = rdlane(o_dest, N), off = rdlane(my_off, N);
             if (lane == d) arrive(next_id + off, ty, a, b, SVC, d);
           }
           // node -> its own client: no latency; lost like any other message (net.clj:214)
           if (rep) {
             const u32 id = next_id + my_off;
-            if (jcap) jwrite(ev_base + my_off, 0, (id << 8) | o_type, o_a, o_b, lane, my_client);
-            if (!(NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss)) { c_arr = true; ca_y = (id << 8) | o_type; ca_a = o_a; ca_b = o_b; }
+            if (jcap) jwrite(ev_base + my_off, 0, (id << 8) | rep_type, rep_a, rep_b, lane, my_client);
+            if (!(NET_RANDOM && loss_on && p_loss && draw32(key, S_LOSS, id) < p_loss)) { c_arr = true; ca_y = (id << 8) | rep_type; ca_a = rep_a; ca_b = rep_b; }
           }
           next_id += __popc(smask);
         }

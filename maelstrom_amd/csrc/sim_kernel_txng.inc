@@ -93,13 +93,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
     bool cmp_row = false; u32 cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     u32 nem_rows = 0, nem_f = 0, nem_v1 = 0, nem_v2 = 0, nem_len2 = 0;
 
-    auto complete = [&](u32 type, u32 err, u32 ref) {
-      busy = false;
-      if (kind != K_OP) { if (type != MSIM_T_OK) my_flags |= MSIM_FLAG_ROUND_LIMIT; return; }
-      cmp_row = true; cmp_packed = type | (MSIM_F_TXN << 2) | (err << 7) | (process << 12);
-      cmp_value = ref & 0xFFFFFFu; cmp_len = ref >> 24;
-      if (type == MSIM_T_INFO) process += C;  // crashed process; the Reusable client itself lives on
-    };
+#define CRASH_STRIDE C
+#define OWN_CLIENT_DELIVER   // recv! is spelled out in R4: as a lambda it is other device code
+    #include "list_append_client.inc"
 
     if (timeout_round) {
       if (busy && timeout_at <= T) complete(MSIM_T_INFO, MSIM_ERR_NET_TIMEOUT, c_value);
@@ -213,24 +209,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
           }
         } else {  // the lin-kv service (service.clj:31-61 over the key "root")
           rep = true; rep_dest = qsrc; rep_b = qb;
-          if (qtype == M_READ) {
-            if (root == V_NIL) { rep_type = M_ERROR; rep_a = 20; } else { rep_type = M_READ_OK; rep_a = root; }
-          } else {  // cas with create_if_not_exists
-            const u32 from = qa & 0xFFFFu, i = qa >> 16;
-            if (root != V_NIL && root != from) { rep_type = M_ERROR; rep_a = 22; }
-            else {
-              const u32 base = root == V_NIL ? 0u : root;
-              const u32 ref = slots[qsrc * TG_SLOTS + i].y, off0 = ref & 0xFFFFFFu, n = ref >> 24;
-              u32 na = 0;
-              for (u32 j = 0; j < n; j++) na += g_pay[off0 + j] & 1;
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j];
-                if (w & 1) { const u32 k = (w >> 1) & 0x7FFFu; const u32 c = g_kvn[k]; g_kv[k * mw + c] = ((w >> 16) & 0xFFu) | ((base + na) << 8); g_kvn[k] = c + 1; }
-              }
-              root = base + na;
-              rep_type = M_CAS_OK; rep_a = 0;
-            }
-          }
+#define TXN_REF_OF(node, i) slots[(node) * TG_SLOTS + (i)].y
+          #include "txn_lin.inc"
         }
       }
       n_ev += (u32)__popcll(jd_mask);
@@ -239,31 +219,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) tx
       {
         const u32 incl = wave_incl_scan(need_words);
         const u32 total = rdlane(incl, 63);
-        if (total) {
-          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) { rep_a = 0; my_slots[done_slot] = make_uint4(0, 0, 0, 0); } }
-          else {
-            if (need_words) {
-              const uint4 s = my_slots[done_slot];
-              const u32 off0 = s.y & 0xFFFFFFu, n = s.y >> 24, from = s.w & 0xFFFFu;
-              u32 pp = n_payload + incl - need_words;
-              rep_a = pp | (need_words << 24);
-              for (u32 j = 0; j < n; j++) {
-                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
-                if (w & 1) { g_pay[pp++] = w; continue; }
-                const u32 vis = visible(k, from);
-                u32 e = 0, acc = 0;
-                const u32 hdr = pp++;
-                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
-                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
-                  if ((wi & 1) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
-                if (e & 3) g_pay[pp++] = acc;
-                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
-              }
-              my_slots[done_slot] = make_uint4(0, 0, 0, 0);
-            }
-            n_payload += total;
-          }
-        }
+        #include "txn_reads.inc"
       }
 
       // COMMIT: one message per server endpoint at most; ids in lane order (nodes, then the service)

@@ -2,7 +2,9 @@
 // instantiate them (k_general_*.hip, k_wide_*.hip, k_raft.hip, k_svc.hip, k_txn.hip, k_mk.hip, k_dt.hip, k_kafka.hip, k_hat.hip) and for engine.hip,
 // which needs their LDS / scratch layout constants.  A template nobody instantiates costs a parse: every unit includes all of them (the
 // families share message enums and constants in include order) and compiles only its own.
-// The round machinery the kernels have in common is text included inside them, group64_*.inc (docs/KERNELS.md has who takes what).
+// The round machinery the kernels have in common is text included inside them, group64_*.inc; so are the node programs and services that a
+// one-worker kernel and its many-worker sibling share (dt_*.inc, mk_*.inc, hat_node.inc, kafka_*.inc, txn_*.inc, list_append_client.inc;
+// dtg4.hip and txng4.hip take theirs too).  docs/KERNELS.md has who takes what and what each kernel states before the include.
 #ifndef MSIM_SIM_KERNELS_H
 #define MSIM_SIM_KERNELS_H
 #include <hip/hip_runtime.h>

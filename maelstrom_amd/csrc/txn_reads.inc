@@ -1,0 +1,28 @@
+// txn_reads.inc — the completed transactions of this round in the payload area: `incl` is the kernel's prefix sum of need_words over the
+// lanes, `total` its last value; each node writes its own (sized at cas_ok) and frees the request handler.  txn_kernel<> and txng_kernel<>;
+// txng4.hip reaches its handlers through slot_ld() / slot_st() and keeps its own.
+        if (total) {
+          if (n_payload + total > max_pay) { flags |= MSIM_FLAG_PAYLOAD_OVERFLOW; if (need_words) { rep_a = 0; my_slots[done_slot] = make_uint4(0, 0, 0, 0); } }
+          else {
+            if (need_words) {
+              const uint4 s = my_slots[done_slot];
+              const u32 off0 = s.y & 0xFFFFFFu, n = s.y >> 24, from = s.w & 0xFFFFu;
+              u32 pp = n_payload + incl - need_words;
+              rep_a = pp | (need_words << 24);
+              for (u32 j = 0; j < n; j++) {
+                const u32 w = g_pay[off0 + j], k = (w >> 1) & 0x7FFFu;
+                if (w & 1) { g_pay[pp++] = w; continue; }
+                const u32 vis = visible(k, from);
+                u32 e = 0, acc = 0;
+                const u32 hdr = pp++;
+                for (u32 i = 0; i < vis; i++) { acc |= (g_kv[k * mw + i] & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } }
+                for (u32 i = 0; i < j; i++) { const u32 wi = g_pay[off0 + i];
+                  if ((wi & 1) && ((wi >> 1) & 0x7FFFu) == k) { acc |= ((wi >> 16) & 0xFFu) << (8 * (e & 3)); if ((++e & 3) == 0) { g_pay[pp++] = acc; acc = 0; } } }
+                if (e & 3) g_pay[pp++] = acc;
+                g_pay[hdr] = (k << 1) | ((e ? e : 0xFFu) << 16);  // a key without elements reads nil
+              }
+              my_slots[done_slot] = make_uint4(0, 0, 0, 0);
+            }
+            n_payload += total;
+          }
+        }
