@@ -299,7 +299,7 @@ int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances,
  * msim_check_host_rechecks.  txn-rw-register (elle's rw-register analysis): a first device pass proves a history free of everything the
  * consistency model proscribes; a history it cannot prove valid is analysed in full by a second device pass (every edge kind, the
  * non-cycle anomalies, the cycle class: G0 / G1c / G-single / G2, -realtime), whose record is the one msim_check_rw_rows gives; only
- * shapes beyond the device capacities, duplicate writes and cyclic components of more than 256 transactions go to the host.  Blocking.
+ * shapes beyond the device capacities and duplicate writes go to the host (a cyclic component may be as large as the history).  Blocking.
  * Results via msim_check_results. */
 int msim_check(msim_ctx *ctx);
 
@@ -328,8 +328,8 @@ int msim_check_txn_batch(int device, const msim_op *rows, const uint64_t *row_of
 /* txn-rw-register: the same for the rw-register analysis under `consistency_model` (MSIM_CM_*): the device proves a history free of
  * everything the model proscribes (csrc/rw_check_dev.hip, rw_check_kernel); the others are analysed and their cycles classified by
  * rw_classify_kernel, byte for byte the record of msim_check_rw_rows; the host analysis finishes only what exceeds the device
- * capacities (values >= 64, the key / writer / transaction / edge tables, 64 open calls), histories with duplicate writes, and cyclic
- * components of more than 256 transactions; *n_host (may be null) = how many those were.  For a history the first pass proves valid,
+ * capacities (values >= 64, the key / writer / transaction / edge tables, 64 open calls) and histories with duplicate writes — a cyclic
+ * component may be as large as the history; *n_host (may be null) = how many those were.  For a history the first pass proves valid,
  * out[i] carries :valid?, the counts, the non-cycle anomalies seen (none proscribed) in error_count and the edges that pass built in
  * lost_count; its allowed cycle classes are not searched for (msim_classify_rw_batch does). */
 int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,

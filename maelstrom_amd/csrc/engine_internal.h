@@ -81,7 +81,9 @@ static inline unsigned msim_host_threads() {
 // (read once per process).  0x100 round limit x20, 0x200 one cluster per wavefront, 0x400 fail instead of falling back to it,
 // 0x800 checkers on the host cores, 0x1000 time the checkers' passes (and count their launches) on stderr and name the kernel each launch
 // took (`[layout] <kernel> <n>`), 0x2000 the checkers' HBM-table kernels / the lin-kv search's tiny pools, 0x10000 at most 7 histories per
-// launch in the chunked checker loops (txn LDS and HBM-table passes, rw, unique-ids HBM tables: a partial last chunk, first > 0).
+// launch in the chunked checker loops (txn LDS and HBM-table passes, rw, unique-ids HBM tables: a partial last chunk, first > 0).  The
+// rw-register classification (rw_check_dev.hip): 0x2000 a matrix of 16 transactions per cyclic component and larger ones to the host,
+// 0x20000 a matrix of 16 with the search in the workspace behind it, as every component beyond 256 has it.
 static inline uint32_t msim_dev_flags(const msim_ctx *ctx) {
   static const uint32_t env = []() { const char *e = std::getenv("MSIM_DEV_FLAGS"); return e ? (uint32_t)std::strtoul(e, nullptr, 0) : 0u; }();   // (decimal, 0x.. or 0..)
   return env | (ctx ? ctx->dev_flags : 0u);

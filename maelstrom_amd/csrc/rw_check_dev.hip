@@ -13,8 +13,9 @@
 //     there an acyclic graph is the only thing this pass can prove, anything else goes to the host.
 // A history it cannot prove valid — a proscribed anomaly, a cycle in the subgraph — goes to rw_classify_kernel, which builds every
 // edge kind, accumulates the non-cycle anomalies and classifies the cycles (G0 / G1c / G-single / G2, -realtime): the record of check_rw
-// byte for byte.  Only a shape beyond the capacities below, duplicate writes (check_rw's writer table is last-writer-wins in row order)
-// and a strongly connected component beyond CCAP transactions are handed to check_rw on the host.  For a history the first pass does prove
+// byte for byte.  Only a shape beyond the capacities below (values >= 64, the key / writer / transaction / edge tables, 64 open calls)
+// and duplicate writes (check_rw's writer table is last-writer-wins in row order) are handed to check_rw on the host; a strongly connected
+// component may be as large as the history (up to CCAP transactions a matrix in LDS, beyond it a search in HBM).  For a history the first pass does prove
 // valid the result carries :valid? and the counts of the host's analysis, the non-cycle anomalies it saw (none of them proscribed) and the
 // edges it built; its ALLOWED cycle classes are not searched for unless the caller asks for every history's full record
 // (msim_classify_rw_batch, msim_set_check_classify).
@@ -57,6 +58,7 @@ struct RParams {
   u32 kmax, wmax;                // keys / writer-table entries the workspace of a history holds (<= KMAX / WMAX: what the configuration can name)
   const u32 *list;               // rw_classify_kernel: the histories of this launch (block b takes list[first + b])
   u32 ccap;                      // rw_classify_kernel: transactions of one strongly connected component the reachability matrix holds (<= CCAP)
+  u32 big;                       // rw_classify_kernel: a larger component is searched in the workspace (0: it is the host's, MSIM_DEV_FLAGS bit 13)
 };
 constexpr u32 CCAP = 256u;       // 256 x 256 bits of LDS: 8 KB per history
 constexpr u32 E_WW = 1u, E_WR = 2u, E_RW = 4u, E_RT = 8u, E_TO = 0x0FFFFFFFu;   // the full graph's edges: to | kind << 28
@@ -85,13 +87,16 @@ __device__ __forceinline__ u32 r_excl_scan(u32 v, u32 lane) {
 //     reach; count it, take it out, peel again.  Every search is a queue, O(edges): the realtime edges form chains as long as the
 //     history, which a sweep to a fixpoint would walk once per link;
 //   * G-single: in a component, some rw edge u -> v whose v reaches u over ww + wr (+ realtime).  Such a path lies inside the component,
-//     so reachability is closed (Warshall, rows of bits in LDS) over the component's transactions alone — ccap of them at the most, a
-//     larger component is the host's.
+//     so reachability is closed (Warshall, rows of bits in LDS) over the component's transactions alone — ccap of them at the most.
+//     A larger component (they grow with the history: a mean of 520 transactions at five nodes and 3000 transactions) would need a matrix
+//     in HBM and s^3 / 64 word operations; the question only needs what the HEADS v of the component's rw edges reach, so those are
+//     searched 64 at a time: a 64-bit word per transaction (reach, in the workspace), bit b = "head b of this batch reaches it", pushed
+//     along the other edges inside the component from a worklist until nothing changes, then every rw edge into the batch is looked up.
 __device__ __forceinline__ void rw_classify(const RParams &p, const u32 hist, msim_check_result &res, const u32 anomalies, const u32 n, const u32 n_edges,
                                             const u32 flags, const u32 c_ok, u32 *const deg, const u32 *const off, const u32 *const adj,
-                                            const u32 *const roff, const u32 *const radj, u32 *const st, u32 *const jump, u32 *const queue) {
+                                            const u32 *const roff, const u32 *const radj, u32 *const st, u32 *const jump, u32 *const queue, u64 *const reach) {
   __shared__ u64 mat[CCAP * CCAP / 64];
-  constexpr u32 GONE = 1u, FWD = 2u, BWD = 4u;
+  constexpr u32 GONE = 1u, FWD = 2u, BWD = 4u, QUEUED = 8u;
   const u32 lane = threadIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
   auto reset = [&]() { for (u32 t = lane; t < n; t += 64) st[t] = 0; __syncthreads(); };
@@ -160,8 +165,81 @@ __device__ __forceinline__ void rw_classify(const RParams &p, const u32 hist, ms
     }
     return tail;
   };
+  // A component beyond the matrix, listed in queue[0 .. s) and marked BWD: is there a rw edge u -> v in it whose v reaches u over the other
+  // kinds of `mask`?  The worklist is a ring of s slots in `deg` (free between two peels): QUEUED keeps a transaction from being in it
+  // twice, so it never holds more than the component.  A transaction is taken (mark cleared, word read) before anything is pushed in
+  // that step, so bits that reach it afterwards queue it again.  Cost: typically about (heads / 64) x the component's edges; a transaction
+  // is taken once per time its word gained bits, at most 64 times per batch, so the bound is 64 x the edges per batch = heads x edges.
+  auto single_by_search = [&](const u32 mask, const u32 s) -> bool {
+    u32 *const wl = deg;
+    u32 heads = 0;   // the heads, numbered along the list: jump[v] = its number (NONE: no rw edge of the component enters v)
+    for (u32 base = 0; base < s; base += 64) {
+      const u32 i = base + lane;
+      bool h = false; u32 v = 0;
+      if (i < s) {
+        v = queue[i];
+        for (u32 e = roff[v]; e < roff[v + 1] && !h; e++) { const u32 x = radj[e], u = x & E_TO; h = ((x >> 28) & E_RW) && u != v && (st[u] & BWD); }
+      }
+      const u64 hm = __ballot(h);
+      if (i < s) jump[v] = h ? heads + (u32)__popcll(hm & lt) : NONE;
+      heads += (u32)__popcll(hm);
+    }
+    __syncthreads();
+    for (u32 b = 0; b * 64u < heads; b++) {
+      u32 hd = 0, cnt = 0;   // the ring: first slot taken, slots taken
+      for (u32 base = 0; base < s; base += 64) {   // the words cleared, this batch's heads seeded and queued (64 of them at the most)
+        const u32 i = base + lane;
+        bool sd = false; u32 v = 0;
+        if (i < s) {
+          v = queue[i];
+          const u32 o = jump[v];
+          sd = (o >> 6) == b;
+          reach[v] = sd ? 1ull << (o & 63u) : 0ull;
+          if (sd) st[v] |= QUEUED;
+        }
+        const u64 sm = __ballot(sd);
+        if (sd) wl[cnt + (u32)__popcll(sm & lt)] = v;
+        cnt += (u32)__popcll(sm);
+      }
+      __syncthreads();
+      while (cnt) {
+        const u32 take = min(64u, cnt);
+        const bool on = lane < take;
+        u32 v = 0; u64 rv = 0;
+        if (on) { u32 q = hd + lane; if (q >= s) q -= s; v = wl[q]; st[v] &= ~QUEUED; rv = reach[v]; }
+        hd += take; if (hd >= s) hd -= s;
+        cnt -= take;
+        __syncthreads();
+        const u32 a0 = on ? off[v] : 0u, a1 = on ? off[v + 1] : 0u;
+        for (u32 k = 0; __ballot(a0 + k < a1); k++) {
+          bool push = false; u32 wv = 0;
+          if (a0 + k < a1) {
+            const u32 x = adj[a0 + k]; wv = x & E_TO;
+            if (((x >> 28) & mask & ~E_RW) && (st[wv] & BWD) && (rv & ~reach[wv]))
+              if (rv & ~(u64)atomicOr(reinterpret_cast<unsigned long long *>(&reach[wv]), (unsigned long long)rv)) push = !(atomicOr(&st[wv], QUEUED) & QUEUED);
+          }
+          const u64 pm = __ballot(push);
+          if (push) { u32 q = hd + cnt + (u32)__popcll(pm & lt); if (q >= s) q -= s; wl[q] = wv; }   // (cnt + pushes <= s: QUEUED)
+          cnt += (u32)__popcll(pm);
+        }
+        __syncthreads();
+      }
+      bool hit = false;
+      for (u32 i = lane; i < s; i += 64) {
+        const u32 u = queue[i];
+        const u64 ru = reach[u];
+        for (u32 e = off[u]; e < off[u + 1]; e++) {
+          const u32 x = adj[e], w = x & E_TO;
+          if (((x >> 28) & E_RW) && w != u && (st[w] & BWD)) { const u32 o = jump[w]; hit |= (o >> 6) == b && ((ru >> (o & 63u)) & 1ull) != 0; }
+        }
+      }
+      if (__ballot(hit)) return true;
+      __syncthreads();
+    }
+    return false;
+  };
   // the transactions in components of more than one transaction over `mask`; want_single: is there, in one of them, a rw edge u -> v
-  // whose v reaches u without a rw edge (single)?  over: a component beyond the matrix
+  // whose v reaches u without a rw edge (single)?  over: a component beyond the matrix that is left to the host
   bool single = false, over = false;
   auto components = [&](const u32 mask, const bool want_single) -> u32 {
     reset();
@@ -191,7 +269,7 @@ __device__ __forceinline__ void rw_classify(const RParams &p, const u32 hist, ms
       const u32 s = search(roff, radj, mask, pivot, FWD, BWD);   // the queue now lists the pivot's component
       cyc += s;
       if (want_single && !single && !over) {
-        if (s > p.ccap) over = true;
+        if (s > p.ccap) { if (p.big) single = single_by_search(mask, s); else over = true; }
         else {
           const u32 W = (s + 63u) >> 6;
           for (u32 i = lane; i < s; i += 64) jump[queue[i]] = i;
@@ -286,6 +364,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   u32 *const adj = vsucc + 2 * p.wmax;       // [emax]
   // FULL only: the edges reversed (radj / roff / rcur), a transaction's state in the searches, the pivot search's pointers
   u32 *const radj = adj + p.emax, *const roff = radj + p.emax, *const rcur = roff + NM + 1, *const st = rcur + NM, *const jump = st + NM;
+  // and a 64-bit word per transaction for the search of a component beyond the matrix [NM], on an 8-byte boundary
 
   msim_check_result res;
   res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
@@ -540,7 +619,8 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   anomalies = r_or(anomalies);
 
   if constexpr (FULL) {
-    rw_classify(p, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue);
+    u64 *const reach = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(jump + NM) + 7u) & ~(uintptr_t)7u);
+    rw_classify(p, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue, reach);
     return;
   }
   // ---- F: acyclic?  Kahn's algorithm, 64 ready transactions per step ---------------------------------------------------------------------
@@ -588,7 +668,7 @@ __global__ void __launch_bounds__(64) rw_classify_kernel(const RParams p) { rw_b
 
 uint64_t rw_ws_words(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return (uint64_t)nmax * 11 + 4 + 2 * (uint64_t)kmax + 3 * (uint64_t)wmax + emax; }
 
-uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws_words(nmax, emax, kmax, wmax) + emax + 4 * (uint64_t)nmax + 4; }
+uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws_words(nmax, emax, kmax, wmax) + emax + 6 * (uint64_t)nmax + 6; }   // (reach: 2 words each, 2 to align it)
 
 // full: every history's record comes from the classification (msim_classify_rw_batch, msim_set_check_classify); otherwise only the
 // records of the histories that rw_check_kernel could not prove valid do
@@ -634,7 +714,10 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
     const u32 m = (u32)todo.size();
     const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
     rp.ws_words = rw_ws_words_full(rp.nmax, rp.emax, rp.kmax, rp.wmax);
-    rp.ccap = (msim_dev_flags(ctx) & 0x2000u) ? 16u : CCAP;   // MSIM_DEV_FLAGS bit 13: a tiny matrix, so that tests reach the host
+    // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
+    // histories reach the search
+    rp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
+    rp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
     const u32 chunk = (u32)std::min<uint64_t>({m, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
     if (int rc = reserve(list_bytes + (size_t)chunk * rp.ws_words * 4)) return rc;
     rp.list = static_cast<const u32 *>(*ws_buf);
