@@ -288,8 +288,11 @@ int msim_create(const msim_config *cfg, int device, msim_ctx **out, char *err, s
  * Outputs stay resident in HBM (see msim_device_buffers) until the next run/destroy. */
 int msim_run(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances);
 
-/* As msim_run, but only enqueues the kernel on `hip_stream` (a hipStream_t; NULL = default stream)
- * and returns; the caller synchronises the stream. */
+/* As msim_run, but only enqueues the kernel and returns.  `hip_stream` is a hipStream_t; NULL = the context's own stream (one per
+ * context, non-blocking: it does not wait for the null stream, nor the null stream for it), so that several contexts have their launches
+ * in flight together.  msim_check, msim_fetch, msim_fetch_begin and msim_last_kernel_ms work on the context's stream and wait for what
+ * was queued there: after a launch on the context's stream they may be called at once.  They do not know a caller's stream: a caller
+ * that passes its own synchronises that stream before it calls any of them. */
 int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances, void *hip_stream);
 
 /* Runs the workload checker for every instance of the last run, reading the HBM-resident histories.  On the device:

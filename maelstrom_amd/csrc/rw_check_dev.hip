@@ -776,6 +776,9 @@ int msim_check_rw_device(msim_ctx *ctx) {
   const u32 n = ctx->n_inst;
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
   MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
+  // the simulation may still be running (msim_run_async): the context's stream does not block against the null stream, so the copy of
+  // the meta below is ordered behind it here and by nothing else
+  MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<msim_inst_meta> hm(n);
   MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));

@@ -131,6 +131,9 @@ class Engine:
         self.n = n_instances
 
     def run_async(self, first_instance, n_instances, stream=None):
+        """msim_run_async: queues the launch and returns.  stream=None is the context's own stream, on which check(), fetch(),
+        fetch_begin() and kernel_ms() work: they wait for the launch and may be called at once.  They do not know a caller's stream
+        (a hipStream_t as an integer): a caller that passes its own synchronises that stream before it calls any of them."""
         self._chk(self.lib.msim_run_async(self._ctx, first_instance, n_instances, stream), "msim_run_async")
         self.n = n_instances
 

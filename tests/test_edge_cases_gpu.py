@@ -1,6 +1,6 @@
 """Edge cases of the hot path through the C-ABI, engine vs oracle (bit-exact): empty workloads, single-node clusters,
 the widest clusters one wavefront holds, far-away instance ids, capacity overflows (reported identically by both, never
-silently truncated), repeated and asynchronous runs."""
+silently truncated), repeated runs.  (Asynchronous and pipelined launches: tests/test_pipeline_gpu.py.)"""
 import ctypes as C
 
 import numpy as np

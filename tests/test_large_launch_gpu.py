@@ -143,6 +143,12 @@ def _verdicts(eng, cfg, idx):
     res = eng.check_results()
     assert len(res) == eng.n
     assert (res["valid"] == 1).all(), f"{int((res['valid'] != 1).sum())} of {eng.n} histories not valid"   # every bench shape is valid
+    _records(eng, cfg, res, idx)
+
+
+def _records(eng, cfg, res, idx):
+    """The records `res` of the fetched launch's instances `idx` against the host checker / the Python restatements (shared with
+    tests/pipeline_cases.py)."""
     wl = cfg.workload
     for i in idx:
         rows, pay = eng.raw_history(i)
