@@ -55,6 +55,10 @@
 // That instantiation is TRIMMED of vector instructions the result does not need: no body counts the delivered envelopes (servers_recv follows
 // from the arrivals and what is left undelivered when the cluster stops), a flood's set word goes to HBM once, before something can read it
 // there, and an op wave-round derives its half's offsets once (see "TRIM" in sim_kernel_duo; -DDUO_NO_TRIM compiles it out).
+// Its op wave-rounds, finally, have a body for the case that pairing has made the rule, the QUIET OP ROUND: every live half acts, from flood
+// mode, so nothing is due or queued anywhere in the wavefront; the gossip part and the exchange are left out, a lane reads off its own
+// adjacency mask whether the picked node's broadcast reaches it, and takes the envelope as the poll would have (see "QUIET OP ROUND" in
+// the op round of sim_kernel_duo; every other op wave-round keeps the superset body; -DDUO_NO_QUIET compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -69,7 +73,7 @@ __constant__ u32 duo_log2_q24[257];
 enum { DK_PLAIN = 0, DK_BCAST = 1, DK_READ = 2, DK_READ_FINAL = 3, DK_INIT = 4, DK_TOPO = 5 };  // kind of an envelope (bits 24-26)
 constexpr u32 DUO_STAGE_ROWS = 128u;
 constexpr u32 DUO_DROP_ONE = 1u << 8;   // TRIM: a lane's my_flags counts the envelopes it dropped in units of this, above the flag bits
-static_assert(DUO_DROP_ONE > MSIM_FLAG_JOURNAL_OVERFLOW, "the drop count lies above every flag");
+static_assert(DUO_DROP_ONE > MSIM_FLAG_JOURNAL_OVERFLOW && DUO_DROP_ONE == 1u << 8, "the drop count lies above every flag, from bit 8 on");
 #ifndef DUO_BAG_N
 #define DUO_BAG_N 16
 #endif
@@ -115,6 +119,13 @@ constexpr bool DUO_STRETCH_ON = true;
 constexpr bool DUO_TRIM_ON = false;
 #else
 constexpr bool DUO_TRIM_ON = true;
+#endif
+// The quiet op round of the trimmed instantiation (see "QUIET OP ROUND" in the op round of sim_kernel_duo): an op wave-round in which every
+// live half acts from flood mode takes a body of its own, without the exchange; -DDUO_NO_QUIET compiles it out for A/B runs.
+#ifdef DUO_NO_QUIET
+constexpr bool DUO_QUIET_ON = false;
+#else
+constexpr bool DUO_QUIET_ON = true;
 #endif
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
@@ -247,6 +258,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   //       request (a busy client's request is queued or held: the node completes it in the round it handles it).  The two places that clear
   //       a stopped half's queue put that number into n_rsv first, an envelope dropped at a full queue adds one (a dropped request: one, which
   //       `busy` takes off again), and servers_recv = sum(n_arr) - sum(n_rsv): what the count gave, for flagged instances too.
+  //       (QUIET: the two places add that number to the count of dropped envelopes above my_flags' flag bits instead, which the epilogue
+  //        adds to n_rsv anyway: n_rsv is then no register across the rounds, the one the op round's third body needs at 80 VGPRs)
   //   (B) the flood bodies do not store sw.  A half in flood mode holds in sw, in EVERY lane, its column's word of value next_value - 1 (word 0
   //       while next_value == 0), and writes it back with one wave-wide store at the points after which its HBM copy can be read: the head
   //       of an op round in which it acts (before the read runs and the read op's copy) and DUO_MATERIALISE.  An acting half in flood
@@ -256,6 +269,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   //       through, so that nothing of it lives across the gossip loop), and rows and payload are addressed as the wavefront's base plus a
   //       32-bit byte offset (msim_launch_duo checks that the two slabs of a wavefront stay below 4 GiB).
   constexpr bool TRIM = DUO_TRIM_ON && STRETCH;
+  constexpr bool QUIET = DUO_QUIET_ON && TRIM;                   // ... and give the op wave-round of quiescent flood halves a body of its own
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -339,6 +353,17 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // STRETCH: the four neighbours' node numbers in one register (8 bits each, ascending like nbl), for the flood bodies, and what a node
   // leaves out of its fan-out: the bit of the envelope's src, or nothing without skip-sender
   // (there the generic bodies take an envelope's constant part from it as well: kc's four registers are what the stretch needs)
+#ifdef MSIM_HIPEMU
+  // QUIET leans on the neighbour relation being SYMMETRIC (bit a of adj(b) == bit b of adj(a)), as it is for every shape topo_adj builds
+  // with at most four neighbours (grid, partial grids included, line, tree2/3/4: each edge is set from both ends); see the quiet op round
+  if (QUIET) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const u32 sy_a = bperm(nbl[k], adj);   // the adjacency mask of neighbour k (an unused slot: lane 31's, which is 0 and not looked at)
+      if ((kc[k] >> 16) != 31u && ((sy_a >> i) & 1u) == 0) __builtin_trap();
+    }
+  }
+#endif
   u32 nbp = 0;
   if (STRETCH) nbp = (kc[0] >> 16) | (kc[1] >> 8) | kc[2] | (kc[3] << 8);
 #define DUO_KC(k_) (STRETCH ? ({ u32 kc_p = nbp; MSIM_OPAQUE(kc_p); ((kc_p >> (8 * (k_))) & 31u) << 16; }) : kc[k_])   /* (computed where it is used: not hoisted into four registers again) */
@@ -736,6 +761,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u32 pf_nrun = 0;   // reads of this lane's cluster that ran ahead of their wave-round's op (read runs)
   u64 pf_pk = 0; u32 pf_npark = 0, pf_npk = 0, pf_wmax = 0, pf_nop2 = 0;   // parked gossip rounds and their cycles, the parks, the longest wait, op wave-rounds that carried two ops
   u32 pf_nst = 0, pf_nstr = 0, pf_ngg = 0; u64 pf_gg = 0;   // flood stretches, the rounds taken inside them, generic gossip rounds and their cycles
+  u32 pf_nquiet = 0;   // flood op rounds that took the quiet body (counted in pf_nfop as well)
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -1023,6 +1049,81 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #endif
         }
       }
+      // QUIET OP ROUND.  The body below is a superset: it serves a half that acts beside one in mid-flood, a half outside flood mode, halves
+      // that only gossip, and both queue representations.  Pairing has made one situation the rule: EVERY live half acts, from flood mode.
+      // By st_m such a half is quiescent, so in every lane of it in_n == 0, sp_n == 0, deliver_at == INF and busy == 0, and nothing is due in
+      // the wavefront (op_due == 0; a -DDUO_PROF build and the host-emulator build trap if any of that is false).  Then the round's gossip
+      // part has nothing to do, and the exchange would only find what every lane can read off its own registers: the one publisher of a
+      // half is the picked node of its broadcast, whose client's request fans out to all of its adj, so a lane receives exactly one envelope
+      // iff its half's op is a broadcast and bit `picked` of its OWN adj is set (the neighbour relation is symmetric, see topo_adj); the poll
+      // would take that envelope out of a queue that held nothing else: cm = value | picked << 16 (DK_PLAIN), deliver_at = T, in_n stays 0
+      // (nx means nothing while the queue is empty and is not written).  The pick, the read, the rows, the set word and the tail are the
+      // superset body's; every round, delivery and message is simulated as before, only the detour through the exchange goes.  The state is
+      // updated in place, and the path meets the superset body's only in front of the tail they share.  The tests are scalar, on masks in SGPRs;
+      // every other op wave-round (one op, a half outside flood mode, the first op behind a GENERAL body) takes the body below as it is.
+      bool quiet = false;
+      if constexpr (QUIET) quiet = fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0;
+#ifdef DUO_PROF
+      bool pf_flr = false;
+#endif
+      if (QUIET && quiet) {
+#if defined(DUO_PROF) || defined(MSIM_HIPEMU)
+        if (op_due != 0 || (opn && ((in_n | sp_n | busy) != 0 || deliver_at != INF))) __builtin_trap();   // the quiet invariant
+#endif
+        // 1. the op's draw and pick
+        u32 r_hi, r_lo; DUO_DRAW(gen_k, r_hi, r_lo);
+        const u32 picked = scale32(r_lo, N);
+        const u64 rd_m = op_m & DUO_BAL_CMP(r_lo & 1u, !=, 0u, 33);   // the halves whose op is a read, a broadcast (whole halves)
+        const u64 bc_m = op_m & ~rd_m;
+        const u64 sel_b = op_m & DUO_BAL_CMP(i, ==, picked, 32);
+        const bool sel = lane_in(sel_b);
+        const u32 val = next_value;
+        next_value += lane_in(bc_m) ? 1u : 0u;
+        gen_k += opn ? 1u : 0u;
+        gen_next = opn ? T + __umulhi(r_hi, p.gen_period2_us) : gen_next;
+        n_cl += sel ? 1u : 0u;
+        // 2. a read -> read_ok with the whole set of the picked node, copied by the cluster's lanes; the cluster publishes nothing
+        u32 cmp_value = val, cmp_len = 0;
+        if (const u64 rs_b = sel_b & rd_m) {
+          wave_lds_fence();
+          const u32 words = (next_value + 31u) >> 5;
+          const bool ok = n_payload + words <= max_pay;   // payload_alloc of the oracle
+          const u64 ok_b = rs_b & bal(ok);
+          if (lane_in(rs_b)) {
+            if (!ok) my_flags |= MSIM_FLAG_PAYLOAD_OVERFLOW;
+            cmp_value = ok ? n_payload : 0u; cmp_len = words;
+          }
+          const u64 cp_b = hm2((u32)ok_b != 0, (u32)(ok_b >> 32) != 0);   // the clusters that copy a set
+          const bool cp = lane_in(cp_b);
+          for (u32 w = i; cp_b & bal(w < words); w += 32)
+            if (cp && w < words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + picked * 4u);
+          n_payload += cp ? words : 0u;
+        }
+        // 3. the invocation and the completion row
+        if (sel) {
+          u32 r4_i = i; MSIM_OPAQUE(r4_i);   // (the rows' constant words are built here, not kept in registers across the rounds)
+          const bool is_rd = lane_in(rd_m);
+          const u64 tns = (u64)T * 1000ull;
+          const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
+          const u32 fk = is_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
+          DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (r4_i << 12), is_rd ? MSIM_NO_VALUE : val);
+          DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (cmp_len << 16), MSIM_T_OK | (fk << 2) | (r4_i << 12), cmp_value);
+        }
+        n_rows += opn ? 2u : 0u;
+        // 4. the set word of the flood to come (B): the word of value next_value - 1, or 0 where a broadcast's value opens a new word, with
+        //    the picked node's own bit
+        sw = lane_in(bc_m & DUO_BAL_CMP(val & 31u, ==, 0u, 32)) ? 0u : sw;
+        sw |= lane_in(sel_b & bc_m) ? 1u << (val & 31u) : 0u;
+        // 5. the broadcast's delivery: the picked node's neighbours hold its envelope, due in the cluster's next round
+        const bool rcv = lane_in(bc_m & DUO_BAL_CMP((adj >> picked) & 1u, !=, 0u, 33));
+        n_arr += rcv ? 1u : 0u;
+        cm = rcv ? (val | (picked << 16)) : cm;
+        deliver_at = rcv ? T : deliver_at;
+        // 6. the tail (the next block of draws, the scheduler's view) is the one below, shared with the superset body
+#ifdef DUO_PROF
+        pf_flr = true; pf_nquiet++;
+#endif
+      } else {
       // the word of the nodes' sets that the op's value falls in, fetched first: only the picked node's store at the end of the round
       // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
       u32 op_w = 0;
@@ -1092,6 +1193,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // the acting clusters are quiescent but for this op: they are in flood mode from here on (a read: with nothing in flight).  The word
       // of the op's value is every lane's set word for the flood to come (no node has handled anything in this round)
       if (fl_ok) { sw = opn ? op_w1 : sw; fl_m |= op_m; }
+#ifdef DUO_PROF
+      pf_flr = fl_round;
+#endif
+      }
       // FLOOD: a cluster that has used up its block of the generator's draws draws the next one here (once per 32 ops), where the round's
       // temporaries are dead; without flood mode its next op takes the GENERAL body, which draws it and leaves flood mode
       if (FLOOD) {
@@ -1104,12 +1209,12 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         DUO_SCHED_VIEW(hbusy_b);
         alive_v = lane_in(alive_m) ? 1u : 0u;
         if (~alive_m) {
-          if (!lane_in(alive_m)) { if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   /* what stays undelivered (A) */
+          if (!lane_in(alive_m)) { if (QUIET) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE; else if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   /* what stays undelivered (A) */
                                    deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
         }
       } else sched_at = opn ? gen_next : sched_at;
 #ifdef DUO_PROF
-      if (fl_round) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
+      if (pf_flr) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
       pf_nop2 += op_m == ~0ull ? 1u : 0u;
 #endif
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
@@ -1273,7 +1378,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     }
     alive_v = lane_in(alive_m) ? 1u : 0u;
     if (~alive_m) {
-      if (!lane_in(alive_m)) { if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   // what stays undelivered (A)
+      if (!lane_in(alive_m)) { if (QUIET) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE; else if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   // what stays undelivered (A)
                                deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
     }
     P3_MARK(7)   // [7] = the scheduler's view
@@ -1295,7 +1400,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (!RND && !DUO_DIRECT && real && g0 < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0] = stage[g0 % DUO_STAGE_ROWS];
     if (!RND && !DUO_DIRECT && real && g0 + 32u < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0 + 32u] = stage[(g0 + 32u) % DUO_STAGE_ROWS];
   }
-  if (TRIM) n_rsv += my_flags / DUO_DROP_ONE;   // (a dropped envelope is not received either)
+  // (a dropped envelope is not received either; QUIET: what a stopped half left undelivered is counted there as well, `- busy` and all, so the
+  //  field is read as a signed number: the sum over a lane is what n_rsv and the drop count gave together)
+  if (QUIET) n_rsv += (u32)((int)my_flags >> 8); else
+  if (TRIM) n_rsv += my_flags / DUO_DROP_ONE;
   const u32 sc_cl = wave_incl_scan(n_cl), sc_arr = wave_incl_scan(n_arr), sc_rsv = wave_incl_scan(n_rsv);
   const u32 lo_cl = rdlane(sc_cl, 31), lo_arr = rdlane(sc_arr, 31), lo_rsv = rdlane(sc_rsv, 31);
   const u32 t_cl = hi ? rdlane(sc_cl, 63) - lo_cl : lo_cl;
@@ -1315,14 +1423,15 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     m.n_events = 0; m.reserved[0] = 0; m.reserved[1] = 0; m.reserved[2] = 0;
 #ifdef DUO_PROF
     // GENERAL bodies | op rounds << 16, wave-rounds | the reads of both clusters that ran inside a read run << 16, their cycles / 1024
-    // (GENERAL | op << 16), all cycles / 4096 | parks << 16 (11 bits) | the longest wait of a parked half << 27 (5 bits, saturating) (tools/duo_prof_report.py)
+    // (GENERAL | op << 16: 5 bits, saturating: generic op rounds are rare) | quiet op rounds << 21 (11 bits, saturating; they are among the
+    // flood op rounds), all cycles / 4096 | parks << 16 (11 bits) | the longest wait of a parked half << 27 (5 bits, saturating) (tools/duo_prof_report.py)
     // the wavefront's upper instance: flood gossip rounds | parked gossip rounds << 16, flood op rounds | op wave-rounds with two ops << 16
     // (12 bits) | materialisations << 28 (4 bits, saturating; their cycles are part of the GENERAL bodies'), cycles / 1024 (flood gossip
     // rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | parked gossip rounds << 16)
     // with -DDUO_PROF_STRETCH as well, the lower instance carries instead of the GENERAL bodies' and op rounds' figures: flood stretches |
     // the rounds taken inside them << 16, and generic gossip rounds | their cycles / 1024 << 16 (tools/duo_prof_report.py with STRETCH=1)
     (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg;
-    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = (u32)(pf_gen >> 10) | ((u32)(pf_op >> 10) << 16);
+    if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = ((u32)(pf_gen >> 10) & 0xFFFFu) | (min((u32)(pf_op >> 10), 31u) << 16) | (min(pf_nquiet, 2047u) << 21);
                m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27);
 #ifdef DUO_PROF_STRETCH
                m.n_events = min(pf_nst, 65535u) | (min(pf_nstr, 65535u) << 16); m.reserved[1] = min(pf_ngg, 65535u) | (min((u32)(pf_gg >> 10), 65535u) << 16);

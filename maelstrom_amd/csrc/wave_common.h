@@ -109,6 +109,9 @@ __device__ __forceinline__ void forget(uint4 &v) { forget(v.x); forget(v.y); for
 __device__ __forceinline__ u32 lane_get(u32 v, u32 l) { return (u32)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)v); }
 
 // ---- topologies (broadcast.clj:40-185): adjacency mask of node a, N <= 32 -------------------------
+// The relation is SYMMETRIC for every shape: bit b of topo_adj(a) is set exactly when bit a of topo_adj(b) is (a partial grid drops an
+// edge at both of its ends, a tree's parent edge is its child edge seen from below).  The quiet op round of duo.hip reads "the picked
+// node sends to me" off the receiver's own mask and leans on this; the host-emulator build of that kernel asserts it.
 __device__ __forceinline__ u32 topo_adj(u32 topology, u32 n, u32 a) {
   u32 m = 0;
   switch (topology) {

@@ -4,6 +4,7 @@ the number of wave-rounds, how many of them were GENERAL rounds (op rounds and f
 flood bodies (flood gossip rounds, flood op rounds) and the materialisations, which the wavefront's upper instance carries; and the
 wave-rounds with an op, the ops they executed, and how many of those were reads that ran ahead of their wave-round's op (read runs); and
 the paired op rounds: parks, parked gossip rounds per park and their cycles, the longest wait, op wave-rounds that carried one op or two.
+And the quiet op rounds: how many of the flood op rounds took the body without the exchange.
 TOPOLOGY / NODES choose another shape (e.g. TOPOLOGY=line NODES=24, the long floods the wait cap is for).
 STRETCH=1: the library is a -DDUO_PROF -DDUO_PROF_STRETCH build (tools/variant_lib.sh profstretch duo.hip -DDUO_PROF -DDUO_PROF_STRETCH), whose lower
 instance carries the flood stretches, the rounds taken inside them and the generic gossip rounds with their cycles, counted directly, in place of
@@ -46,7 +47,9 @@ assert npark.max() < 2047, "this shape parks too often for the 11-bit field of t
 ctot = (ctot.astype(np.int64) & 0xFFFF).astype(np.float64)
 ev = ev.astype(np.int64); cyc = cyc.astype(np.int64)
 ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)          # GENERAL bodies, generic op rounds
-cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, (cyc >> 16).astype(np.float64) * 1024
+# (beside the generic op rounds' cycles, 5 bits that saturate: the flood op rounds that took the quiet body, 11 bits that saturate)
+cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, ((cyc >> 16) & 31).astype(np.float64) * 1024
+nquiet, cop_sat, nquiet_sat = (cyc >> 21).astype(np.float64), bool((((cyc >> 16) & 31) == 31).any()), bool(((cyc >> 21) == 2047).any())
 ctot *= 4096
 # flood gossip rounds, flood op rounds, materialisations and their cycles (a build without flood mode leaves the generic numbers there: zero them)
 flood = os.environ.get("FLOOD", "1") != "0"
@@ -84,6 +87,9 @@ print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / n
 nopw = ngen.mean() + nop_all   # wave-rounds with an op (a GENERAL body of the main phase carries one as well)
 print(f"wave-rounds with an op {nopw:.0f} per wavefront; reads executed ahead of such a round's op (read runs) {nrun.mean():.0f} per wavefront, "
       f"{nrun.mean() / max(nopw, 1):.2f} per wave-round with an op")
+if not stretch:
+    print(f"quiet op rounds (every live half acts from flood mode: the body without the exchange) {nquiet.mean():.0f}{' or more' if nquiet_sat else ''} of the {nfop.mean():.0f} flood op rounds "
+          f"per wavefront, {nfop.mean() - nquiet.mean():.0f} take the superset body" + ("; the generic op rounds' cycle field is saturated (31 x 1024 per wavefront)" if cop_sat else ""))
 nop1 = nop_all - nop2.mean()
 wmax_s = f"{wmax} or more" if wmax == 31 else str(wmax)   # (the field saturates)
 print(f"paired op rounds: parks {npark.mean():.0f} per wavefront, parked gossip rounds {npk.mean():.0f} ({npk.mean() / max(npark.mean(), 1):.2f} per park, longest wait {wmax_s}) at "

@@ -8,12 +8,15 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 CMD="python $ROOT/bench.py --steps 3 --warmup 3 --cpu-sample 0 --no-gather --no-fetch"
-rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t -- $CMD > "$OUT/trace.log" 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAVES SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SMEM -d "$OUT/pmc_sq" -o s -- $CMD > "$OUT/pmc_sq.log" 2>&1
+# every pass under a time limit of its own; a pass that fails ends the script (nothing more is started on the device behind a fault)
+LIM="timeout -k 10 ${PASS_LIMIT:-300}"
+fail() { echo "profile_headline: the $1 pass failed (exit $2)"; tail -20 "$OUT/$1.log"; exit 1; }
+$LIM rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t -- $CMD > "$OUT/trace.log" 2>&1 || fail trace $?
+$LIM rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_WAVES SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SMEM -d "$OUT/pmc_sq" -o s -- $CMD > "$OUT/pmc_sq.log" 2>&1 || fail pmc_sq $?
 if [ "${2:-}" = "full" ]; then
-  rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o f -- $CMD > "$OUT/pmc_fetch.log" 2>&1
-  rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o w -- $CMD > "$OUT/pmc_write.log" 2>&1
-  rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS -d "$OUT/pmc_cyc" -o c -- $CMD > "$OUT/pmc_cyc.log" 2>&1
+  $LIM rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o f -- $CMD > "$OUT/pmc_fetch.log" 2>&1 || fail pmc_fetch $?
+  $LIM rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o w -- $CMD > "$OUT/pmc_write.log" 2>&1 || fail pmc_write $?
+  $LIM rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_SALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS -d "$OUT/pmc_cyc" -o c -- $CMD > "$OUT/pmc_cyc.log" 2>&1 || fail pmc_cyc $?
 fi
 DBS=$(find "$OUT" -name "*_results.db" | sort)
 python $ROOT/tools/rocpd_summary.py $DBS > "$OUT/summary.txt" 2>&1
