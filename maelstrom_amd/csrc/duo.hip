@@ -59,6 +59,11 @@
 // mode, so nothing is due or queued anywhere in the wavefront; the gossip part and the exchange are left out, a lane reads off its own
 // adjacency mask whether the picked node's broadcast reaches it, and takes the envelope as the poll would have (see "QUIET OP ROUND" in
 // the op round of sim_kernel_duo; every other op wave-round keeps the superset body; -DDUO_NO_QUIET compiles it out).
+// And the round that ends a flood stretch because a half has run out of due envelopes has, in the steady state of the main phase, a path
+// of its own, the STEADY LEAVE: the tail of an op round notes per half (sd_m) that the half's next round can only be an op round's, and
+// for such a half the stretch's exit does what R0's block and the exit test would have done, and nothing else: the time jump, the round
+// count, the count-down, then the park of the dry half or the release of the parked one and the op round of both.  Everything else goes
+// through the loop's head as ever (see "STEADY LEAVE" at the exit of the flood stretch and sd_m; -DDUO_NO_STEADY compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -126,6 +131,14 @@ constexpr bool DUO_TRIM_ON = true;
 constexpr bool DUO_QUIET_ON = false;
 #else
 constexpr bool DUO_QUIET_ON = true;
+#endif
+// The steady leave of the quiet instantiation (see "STEADY LEAVE" at the exit of the flood stretch in sim_kernel_duo): the round that ends a
+// stretch because a half has run out of due envelopes parks that half or goes to the op round without a pass through R0 and the exit
+// test, when an op round has left the half in the state those would find; -DDUO_NO_STEADY compiles it out for A/B runs.
+#ifdef DUO_NO_STEADY
+constexpr bool DUO_STEADY_ON = false;
+#else
+constexpr bool DUO_STEADY_ON = true;
 #endif
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
@@ -270,6 +283,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   //       32-bit byte offset (msim_launch_duo checks that the two slabs of a wavefront stay below 4 GiB).
   constexpr bool TRIM = DUO_TRIM_ON && STRETCH;
   constexpr bool QUIET = DUO_QUIET_ON && TRIM;                   // ... and give the op wave-round of quiescent flood halves a body of its own
+  constexpr bool STEADY = DUO_STEADY_ON && QUIET;                // ... and leave a flood stretch for a park or an op round without R0 and the exit test
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -451,6 +465,23 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // wave-rounds it may still wait (counted down in every wave-round; far from 0 while nobody is parked)
   constexpr u32 PARK_IDLE = 0x7FFFFFFFu;
   u64 park_m = 0; u32 park_left = PARK_IDLE;
+  // STEADY: sd_m = the halves whose next round, once their flood has run dry, can only be an op round's (a lane mask of whole halves like
+  // fl_m).  The tail of an op round sets a half's bit, on the state that round leaves, iff the half acted, no scheduler's view ran, and
+  //   the half is in fl_m, next_value < max_values, n_rows + 2 <= max_rows, gen_k - dc_base < 32 (after the refill of the draws), and
+  //   phase == PH_MAIN, gen_next < cutoff and busy == 0 in every lane, which hold where the bit is set without a compare (see the tail):
+  // st_m's own terms (see the exit test) and what keeps the scheduler's view out of the way.  Why the bit still tells the truth when it is
+  // used, at the exit of a flood stretch, about a half with nothing due:
+  //   * phase, busy, next_value, n_rows, gen_k, dc_base, gen_next and cutoff are written by op rounds (the bit is set again at their tail,
+  //     or cleared with the scheduler's view), by GENERAL bodies (their head clears every bit) and nowhere else: no gossip body, flood or
+  //     generic, and nothing in R0 touches them.  fl_m is cleared by DUO_MATERIALISE alone, which only the GENERAL body calls;
+  //   * fg_m grows in R0's block (the round limit) and in the scheduler's view: the block clears the bits of the halves it forces or finds
+  //     stuck, the view's two callers clear all of them, and the use applies & ~fg_m again;
+  //   * a half that does not act in an op round (it is in mid-flood beside its partner's op) keeps its bit: that round's gossip part is
+  //     a gossip round to it.
+  // So for a live half with its bit set and nothing due, st_m's five compares hold, and the sixth term, nothing due and no client busy,
+  // holds by busy == 0 and the caller's own knowledge that nothing is due (a -DDUO_PROF build and the host-emulator build recompute all of
+  // it at the use and trap if it differs).
+  u64 sd_m = 0;
   // The helpers below are macros on purpose: as lambdas capturing the state by reference they left the closures (and with
   // them every captured variable) in scratch memory once the optimizer turned a select of two captured values into a select
   // of their addresses.
@@ -762,6 +793,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u64 pf_pk = 0; u32 pf_npark = 0, pf_npk = 0, pf_wmax = 0, pf_nop2 = 0;   // parked gossip rounds and their cycles, the parks, the longest wait, op wave-rounds that carried two ops
   u32 pf_nst = 0, pf_nstr = 0, pf_ngg = 0; u64 pf_gg = 0;   // flood stretches, the rounds taken inside them, generic gossip rounds and their cycles
   u32 pf_nquiet = 0;   // flood op rounds that took the quiet body (counted in pf_nfop as well)
+  u32 pf_nspark = 0, pf_nsleave = 0; u64 pf_sx = 0; bool pf_sleft = false;   // steady parks (counted in pf_npark as well), steady leaves, the cycles of both from the stretch's exit on
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -848,6 +880,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
             sched_at = stuck ? INF : sched_at;
             rounds += stuck ? 1u : 0u;
             alive_m &= ~stuck_b; fg_m &= ~stuck_b; alive_v = stuck ? 0u : alive_v;
+            if (STEADY) sd_m &= ~stuck_b;
             T = lane_in(idle_b & ~stuck_b) ? km : T;
             stuck_any = stuck_b != 0;
             due_b = bal(deliver_at <= T);
@@ -855,6 +888,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           // the round limit is looked at here and in GENERAL rounds (a stretch of pure gossip always ends in one of the two)
           // (PAIR: not for a parked half: its round is counted, its op round decided; the limit is looked at again behind its op)
           fg_m |= alive_m & bal(rounds >= round_limit) & (PAIR ? ~park_m : ~0ull);
+          if (STEADY) sd_m &= ~fg_m;
           want_m = alive_m & (fg_m | bal(sched_at <= T));
           }
         }
@@ -935,6 +969,15 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #ifdef DUO_PROF
         pf_nst++;
 #endif
+        // (STEADY: a steady park comes back to this wrapper with `continue`; every other stretch passes it once and leaves by the `break`
+        //  at its end.  THE CONVENTION BELOW IS OFF BY ONE ON PURPOSE: under STEADY the stretch's exit keeps park_left and st_more as the
+        //  loop's last park_left-- and st_more++ left them, i.e. with the NEXT round's count-down and count already taken, and the steady
+        //  leave is written on those values (park_left against 0, sl_r1 = rounds with the next round counted, round_limit < sl_r1); where it
+        //  declines it takes both back (park_left++, rounds = sl_r1 - alive_v) so that the loop's head finds what it always found, and the
+        //  -DDUO_PROF counters undo it too (pf_sn, pf_pl).  Written on the values after `park_left++; st_more--` instead, the compiler kept
+        //  wrapper and stretch as two loops and closed the inner one with s_mov + s_branch: a taken branch more on every round's back
+        //  edge (profiles/r31_isa_static.txt).  Whoever changes one of these places changes all of them.)
+        for (;;) {
         for (;;) {
           const bool st_n = lane_in(st_due);
 #if defined(DUO_PROF) || defined(MSIM_HIPEMU)
@@ -954,16 +997,79 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           pf_nwave++;
 #endif
         }
-        park_left++; st_more--;   // (the round that ends the stretch begins at the loop's head: its count-down and its count are taken there)
+        // (the round that ends the stretch begins at the loop's head: its count-down and its count are taken there; STEADY: they are what the
+        //  steady leave needs, and are taken back where it declines, so that the back edge above keeps its one value of each)
+        if (!STEADY) { park_left++; st_more--; }
 #ifdef DUO_PROF
         // one reading per stretch (one per round cost a round of this loop more than the round itself); a half is parked or released at the
         // exit test only, so a stretch is parked as a whole or not at all
-        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk += st_more + 1u; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); }
-        else { pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg += st_more + 1u; }
-        pf_nstr += st_more + 1u;
+        { const u64 pf_s1 = __builtin_readcyclecounter();   // (STEADY: the steady leave is counted from here)
+          const u32 pf_sn = st_more + (STEADY ? 0u : 1u), pf_pl = park_left + (STEADY ? 1u : 0u);   // (STEADY: the stretch's count-down and count are not taken back)
+          if (pf_parked) { pf_pk += pf_s1 - pf_it; pf_npk += pf_sn; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - pf_pl); }
+          else { pf_fg += pf_s1 - pf_it; pf_nfg += pf_sn; }
+          pf_nstr += pf_sn;
+          pf_it = pf_s1; }
 #endif
-        rounds += st_more * alive_v;
+        if (!STEADY) rounds += st_more * alive_v;
         deliver_at = lane_in(st_due) ? T : INF;
+        // STEADY LEAVE.  The round that is next begins at the loop's head, and when the stretch ended because a half has run dry (dry_m: no
+        // lane of it has something due, and it is not parked), nearly all that R0's block and the exit test do there is to find out again
+        // what the half's last op round left behind.  With both halves alive, the count-down not about to run out (the head's park_left--
+        // and its test), every dry half steady (sd_m & ~fg_m, see sd_m) and no unparked half at the round limit (ONE compare over both
+        // halves: R0's block looks at the live partner's limit too, whenever it is entered), the answers are known:
+        //   * want_m is 0 inside a stretch, so sched_at > T in both halves, and a dry half at latency 0 holds nothing (deliver_at == INF),
+        //     so the block's idle_b is dry_m, km is sched_at, which an op round's tail set to gen_next (never INF: nobody is stuck), and
+        //     T moves to it; due_b stays st_due; fg_m gets nothing from the limit; want_m becomes the dry halves and a parked one;
+        //   * rounds += alive_v, and gw_m is want_m: the flood invariant rules out a special envelope at the partner;
+        //   * st_m holds in the dry halves by sd_m, and in a parked half because nothing it looks at has changed since the test that
+        //     parked it (see PAIRED OP ROUNDS).
+        // So the head would either PARK the dry half (its partner still has envelopes due and is not parked: gw_m is one half) and come
+        // back to this loop with st_due as it is, or, with dry_m | park_m covering both halves, release the parked half and LEAVE for an
+        // op round of both (op_m = ~0, op_due = 0: the quiet body by its own test).  Exactly that is done here, and nothing else: the same
+        // time jump, round count and count-down at the same round, the same park_m, park_left and alive_v (the stretch's last park_left--
+        // and st_more++ ARE that round's count-down and count: sl_r1 is rounds with that round counted, so the limit test reads
+        // round_limit < sl_r1, and park_left is tested against 0; where the path declines both are taken back).  Everything else (a dry half
+        // that is not steady, a finished or absent partner, the count-down at 0, the limit reached) goes to the loop's head as ever,
+        // where R0's block is entered by the same test that ended the stretch and rebuilds want_m.  No round, delivery or message is
+        // skipped or batched: this removes tests.  All of it sits behind the stretch's exit; the back edge above is untouched.
+        if constexpr (STEADY) {
+          const u64 dry_m = ~park_m & hm2((u32)st_due == 0, (u32)(st_due >> 32) == 0);
+          const u32 sl_r1 = rounds + st_more * alive_v;   // the stretch's rounds and the next round's count
+          if (alive_m == ~0ull && park_left != 0u && dry_m != 0 && (dry_m & ~(sd_m & ~fg_m)) == 0 &&
+              (~park_m & DUO_BAL_CMP(round_limit, <, sl_r1, 36)) == 0) {
+#if defined(DUO_PROF) || defined(MSIM_HIPEMU)
+            {   // the steady invariant: what R0's block and the exit test would have found
+              const bool sl_dry = lane_in(dry_m), sl_op = lane_in(dry_m | park_m);
+              if (sl_op && ((in_n | sp_n | busy) != 0 || deliver_at != INF)) __builtin_trap();
+              if (sl_dry && (sched_at <= T || sched_at == INF)) __builtin_trap();
+              if (!sl_op && lane_in(st_due) && cm > 0xFFFFFFu) __builtin_trap();
+              if (sl_op && (lane_in(fg_m) || phase != PH_MAIN || next_value >= max_values || n_rows + 2u > max_rows || gen_k - dc_base >= 32u)) __builtin_trap();
+              if ((dry_m & st_due) != 0 || (park_m & st_due) != 0) __builtin_trap();
+            }
+#endif
+            T = lane_in(dry_m) ? sched_at : T;
+            rounds = sl_r1;
+#ifdef DUO_PROF
+            pf_nwave++;
+#endif
+            if ((dry_m | park_m) == ~0ull) {   // leave: both halves take their op
+              if (park_m != 0) { alive_v = 1u; park_m = 0; park_left = PARK_IDLE; }   // (the parked half's round is not counted again; both halves are alive)
+              op_m = ~0ull; op_due = 0;
+#ifdef DUO_PROF
+              pf_nsleave++; pf_sleft = true;
+#endif
+            } else {   // park: the dry half waits for its partner's flood
+              park_m = dry_m; park_left = (u32)DUO_PAIR_WAIT; alive_v = lane_in(dry_m) ? 0u : alive_v; st_more = 0;
+#ifdef DUO_PROF
+              pf_npark++; pf_nspark++; pf_parked = true; { const u64 pf_p0 = __builtin_readcyclecounter(); pf_sx += pf_p0 - pf_it; pf_it = pf_p0; }
+#endif
+              continue;
+            }
+          } else { park_left++; rounds = sl_r1 - alive_v; }
+        }
+        break;
+        }
+        if (STEADY && op_m != 0) break;   // (a steady leave: op_m is 0 wherever else this point is reached, a parking exit test included)
       } else if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
         u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
         if (!TRIM) n_rsv += due_n ? 1u : 0u;
@@ -994,7 +1100,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (!alive_m) break;
 #ifdef DUO_PROF
     const u64 pf_a = __builtin_readcyclecounter();
-    pf_exit += pf_a - pf_it;
+    if (pf_sleft) { pf_sx += pf_a - pf_it; pf_sleft = false; } else pf_exit += pf_a - pf_it;   // (a steady leave's cycles: from the stretch's exit)
 #endif
     if (LAT0 && !RND && op_m != 0) {
       // ---- an op round: the gossip round of both clusters, plus the op of each cluster in op_m.  It computes what the GENERAL body
@@ -1212,7 +1318,17 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           if (!lane_in(alive_m)) { if (QUIET) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE; else if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   /* what stays undelivered (A) */
                                    deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
         }
-      } else sched_at = opn ? gen_next : sched_at;
+        if (STEADY) sd_m = 0;
+      } else {
+        sched_at = opn ? gen_next : sched_at;
+        // STEADY: the acting halves' bits of sd_m, on the state this round leaves (see sd_m); a half that did not act keeps its bit
+        // (three of sd_m's terms need no compare here.  phase == PH_MAIN and gen_next < cutoff: this is the else branch of the test above,
+        //  which has just found both in every lane of every live half.  busy == 0: an acting half had no busy client when this op round was
+        //  chosen, by st_m's sixth term or by its bit of sd_m, and an op round leaves busy as it is; looking at it here kept it in a register
+        //  through the superset body, which sent that body's rarest path to scratch.  The emulator and -DDUO_PROF builds check all three at the use)
+        if constexpr (STEADY)
+          sd_m = (sd_m & ~op_m) | (op_m & fl_m & DUO_BAL_CMP(next_value, <, max_values, 36) & DUO_BAL_CMP(n_rows + 2u, <=, max_rows, 37) & DUO_BAL_CMP(gen_k - dc_base, <, 32u, 36));
+      }
 #ifdef DUO_PROF
       if (pf_flr) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
       pf_nop2 += op_m == ~0ull ? 1u : 0u;
@@ -1220,6 +1336,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
     DUO_MATERIALISE();
+    if (STEADY) sd_m = 0;   // (this body changes what the bits stand for, see sd_m)
     // (RUNS: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
     DUO_UPM_NOW();   // TRIM (C)
     u32 gi = i; if (RUNS) MSIM_OPAQUE(gi);
@@ -1430,9 +1547,15 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     // rounds | the leaving rounds' R0 << 16), cycles / 1024 (flood op rounds | parked gossip rounds << 16)
     // with -DDUO_PROF_STRETCH as well, the lower instance carries instead of the GENERAL bodies' and op rounds' figures: flood stretches |
     // the rounds taken inside them << 16, and generic gossip rounds | their cycles / 1024 << 16 (tools/duo_prof_report.py with STRETCH=1)
-    (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg;
+    // with -DDUO_PROF_STEADY as well, the lower instance carries instead of the GENERAL bodies' and generic op rounds' cycles and the quiet
+    // count: steady parks (11 bits, saturating; they are among the parks) | steady leaves << 11 (11 bits, saturating) | the cycles of both,
+    // from the stretch's exit on, / 4096 << 22 (10 bits, saturating) (tools/duo_prof_report.py with STEADY=1)
+    (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg; (void)pf_nspark; (void)pf_nsleave; (void)pf_sx;
     if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = ((u32)(pf_gen >> 10) & 0xFFFFu) | (min((u32)(pf_op >> 10), 31u) << 16) | (min(pf_nquiet, 2047u) << 21);
                m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27);
+#ifdef DUO_PROF_STEADY
+               m.reserved[1] = min(pf_nspark, 2047u) | (min(pf_nsleave, 2047u) << 11) | (min((u32)(pf_sx >> 12), 1023u) << 22);
+#endif
 #ifdef DUO_PROF_STRETCH
                m.n_events = min(pf_nst, 65535u) | (min(pf_nstr, 65535u) << 16); m.reserved[1] = min(pf_ngg, 65535u) | (min((u32)(pf_gg >> 10), 65535u) << 16);
 #endif

@@ -8,7 +8,16 @@ And the quiet op rounds: how many of the flood op rounds took the body without t
 TOPOLOGY / NODES choose another shape (e.g. TOPOLOGY=line NODES=24, the long floods the wait cap is for).
 STRETCH=1: the library is a -DDUO_PROF -DDUO_PROF_STRETCH build (tools/variant_lib.sh profstretch duo.hip -DDUO_PROF -DDUO_PROF_STRETCH), whose lower
 instance carries the flood stretches, the rounds taken inside them and the generic gossip rounds with their cycles, counted directly, in place of
-the GENERAL bodies' and generic op rounds' figures: the lines about those are left out, the stretch lines are printed."""
+the GENERAL bodies' and generic op rounds' figures: the lines about those are left out, the stretch lines are printed.
+STEADY=1: the library is a -DDUO_PROF -DDUO_PROF_STEADY build (tools/variant_lib.sh profsteady duo.hip -DDUO_PROF -DDUO_PROF_STEADY), whose lower
+instance carries the steady parks, the steady leaves and the cycles of both (from the stretch's exit to the re-entry of the stretch or the op
+round's head) in place of the GENERAL bodies' and generic op rounds' cycles and the quiet count: the lines that need those are left out, and the
+leaving rounds are split into fast ones (steady parks and leaves) and slow ones (through R0 and the exit test) with the cycles of each.
+How to read that split: a slow round's cycles are counted from the loop's head, so where the steady leave looked and declined, the cycles between
+the stretch's exit and the loop's head (the declined test) are in no bucket, and "slow at N cycles each" leaves them out; the fast cycles are a
+10-bit field in units of 4096 per wavefront, read at the middle of its unit (+2048 per wavefront, a bias of at most that much either way).
+The line "steady fields" says in how many wavefronts a field is saturated.  As of round 17 the -DDUO_PROF_STEADY build does not fit its SGPRs (139
+spills, v_readlane / v_writelane inside the loops: profiles/r31_round_split_after.txt), so its counts are exact and its cycles are its own spills'."""
 import os
 import sys
 
@@ -51,6 +60,12 @@ ngen, nop = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64)     
 cgen, cop = (cyc & 0xFFFF).astype(np.float64) * 1024, ((cyc >> 16) & 31).astype(np.float64) * 1024
 nquiet, cop_sat, nquiet_sat = (cyc >> 21).astype(np.float64), bool((((cyc >> 16) & 31) == 31).any()), bool(((cyc >> 21) == 2047).any())
 ctot *= 4096
+steady = os.environ.get("STEADY", "0") != "0"
+if steady:   # (the word that held cgen | cop | nquiet: steady parks, 11 bits | steady leaves, 11 bits | their cycles / 4096, 10 bits, all saturating)
+    nspark, nsleave, csx = (cyc & 0x7FF).astype(np.float64), ((cyc >> 11) & 0x7FF).astype(np.float64), (cyc >> 22).astype(np.float64) * 4096 + 2048
+    steady_sat = int(((cyc & 0x7FF) == 2047).sum() + (((cyc >> 11) & 0x7FF) == 2047).sum()), int(((cyc >> 22) == 1023).sum())   # wavefronts with a saturated count, with saturated cycles
+    print(f"steady fields: max steady parks {nspark.max():.0f}, max steady leaves {nsleave.max():.0f}, max cycles / 4096 {(cyc >> 22).max()}; saturated in {steady_sat[0]} (counts) and {steady_sat[1]} (cycles) of {len(cyc)} wavefronts")
+    cgen, cop, nquiet = cgen * 0, cop * 0, nquiet * 0
 # flood gossip rounds, flood op rounds, materialisations and their cycles (a build without flood mode leaves the generic numbers there: zero them)
 flood = os.environ.get("FLOOD", "1") != "0"
 nfg, nfop, nop2, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, (up[:, 1] >> 16) & 0xFFF, (up[:, 1] >> 28) & 0xF)]
@@ -73,12 +88,16 @@ print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kern
 nsched = ngen.mean() + nop_all
 print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.mean():.0f}), GENERAL {nsched:.0f} ({100 * nsched / nwave.mean():.1f} %): "
       f"op rounds {nop_all:.0f} ({100 * nop_all / max(nsched, 1):.1f} % of them), full GENERAL bodies {ngen.mean():.0f}")
-print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL bodies {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %), "
-      f"in generic op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
+if steady:
+    print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e})")
+else:
+    print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}); in GENERAL bodies {cgen.mean():.3e} ({100 * cgen.mean() / ctot.mean():.1f} %), "
+          f"in generic op rounds {cop.mean():.3e} ({100 * cop.mean() / ctot.mean():.1f} %)")
 ngos = nwave.mean() - nsched - nfg.mean() - npk.mean()          # generic gossip rounds: the loop's rest (a parked round in a generic body is counted as parked)
 cgos = ctot.mean() - cgen.mean() - cop.mean() - cfop.mean() - cfg_.mean() - cpk.mean() - cexit.mean()   # (without flood mode: with the leaving rounds' R0, as ever; materialisations are part of the GENERAL bodies)
-print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per generic op round ({nop.mean():.0f}) {cop.mean() / max(nop.mean(), 1):.0f}, "
-      f"per generic gossip round ({ngos:.0f}) {cgos / max(ngos, 1):.0f}")
+if not steady:
+    print(f"cycles per GENERAL body {cgen.mean() / max(ngen.mean(), 1):.0f}, per generic op round ({nop.mean():.0f}) {cop.mean() / max(nop.mean(), 1):.0f}, "
+          f"per generic gossip round ({ngos:.0f}) {cgos / max(ngos, 1):.0f}")
 nfl = nfg.mean() + nfop.mean()
 print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / nwave.mean():.1f} %): flood gossip rounds {nfg.mean():.0f} at {cfg_.mean() / max(nfg.mean(), 1):.0f} cycles "
       f"({100 * cfg_.mean() / ctot.mean():.1f} % of the cycles), flood op rounds {nfop.mean():.0f} at {cfop.mean() / max(nfop.mean(), 1):.0f} ({100 * cfop.mean() / ctot.mean():.1f} %), "
@@ -87,7 +106,13 @@ print(f"flood bodies {nfl:.0f} of {nwave.mean():.0f} wave-rounds ({100 * nfl / n
 nopw = ngen.mean() + nop_all   # wave-rounds with an op (a GENERAL body of the main phase carries one as well)
 print(f"wave-rounds with an op {nopw:.0f} per wavefront; reads executed ahead of such a round's op (read runs) {nrun.mean():.0f} per wavefront, "
       f"{nrun.mean() / max(nopw, 1):.2f} per wave-round with an op")
-if not stretch:
+if steady:
+    nleave = nsched + npark.mean()
+    nfast = nspark.mean() + nsleave.mean()
+    print(f"steady leave: steady parks {nspark.mean():.0f} of the {npark.mean():.0f} parks, steady leaves {nsleave.mean():.0f} of the {nop_all:.0f} op rounds per wavefront; of the {nleave:.0f} rounds "
+          f"that leave the gossip loop or park a half {nfast:.0f} are fast ({100 * nfast / max(nleave, 1):.1f} %) at {csx.mean() / max(nfast, 1):.0f} cycles each from the stretch's exit "
+          f"({100 * csx.mean() / ctot.mean():.1f} % of the cycles), {nleave - nfast:.0f} slow at {cexit.mean() / max(nleave - nfast, 1):.0f} each through R0 and the exit test ({100 * cexit.mean() / ctot.mean():.1f} %)")
+if not stretch and not steady:
     print(f"quiet op rounds (every live half acts from flood mode: the body without the exchange) {nquiet.mean():.0f}{' or more' if nquiet_sat else ''} of the {nfop.mean():.0f} flood op rounds "
           f"per wavefront, {nfop.mean() - nquiet.mean():.0f} take the superset body" + ("; the generic op rounds' cycle field is saturated (31 x 1024 per wavefront)" if cop_sat else ""))
 nop1 = nop_all - nop2.mean()
