@@ -122,3 +122,21 @@ def test_device_checkers_on_the_emulator_equal_the_host_checkers(emu_lib):
         run_env = dict(env, MSIM_DEV_FLAGS=flags) if flags else env
         r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + args, cwd=ROOT, env=run_env, capture_output=True, text=True, timeout=1500)
         assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+@pytest.mark.timeout(1800)
+def test_checker_fallback_levels_on_the_emulator(emu_lib):
+    """The synthetic list-append and pn-counter histories at the capacities of their device checkers (tests/test_txn_check_synthetic_gpu.py,
+    tests/test_pn_check_synthetic_gpu.py) through the emulated kernels, between guarded slabs; the modules' child processes (the runs under
+    MSIM_DEV_FLAGS) inherit MSIM_LIB and so run on the emulator too, as do those of tests/test_lin_check_gpu.py in the test above.  The
+    list-append module runs once more on a build of txn_check_dev.hip with -DTC_NO_POTENTIAL: the emulator's lanes are not in lockstep,
+    so how many sweeps the potential takes says nothing about the device; without it Kahn's queue decides every history the LDS kernel keeps."""
+    sys.path.insert(0, os.path.join(ROOT, "tools", "hipemu"))
+    import build_emu
+    nopot = build_emu.build_variant("nopotential", "txn_check_dev.hip", ["-DTC_NO_POTENTIAL"])
+    for lib, mod in ((emu_lib, "test_pn_check_synthetic_gpu.py"), (emu_lib, "test_txn_check_synthetic_gpu.py"), (nopot, "test_txn_check_synthetic_gpu.py")):
+        env = dict(os.environ, MSIM_LIB=lib, HIPEMU_DIVERGENT="1", MSIM_GUARD="3")
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", mod)],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0 and " passed" in r.stdout and "skipped" not in r.stdout, (lib, mod, r.stdout[-3000:] + r.stderr[-3000:])
+        assert "[msim guard] 0 damaged byte(s)" in r.stdout, r.stdout[-2000:]
