@@ -38,7 +38,8 @@
 //   flood op round       the same plus the op of each acting cluster, which (re-)enters flood mode with the op's value
 //   gossip / op round    the generic bodies (rings in LDS, set word re-read): some cluster is not in flood mode; they take one that is as it is
 //   GENERAL round        the full body; it first writes the queues of the clusters in flood mode out to their rings
-// (details at "FLOOD MODE" below; every round, delivery and message is still simulated: only the queue's representation differs).
+// (details at "FLOOD MODE" below; every round, delivery and message is still simulated: only the queue's representation differs; the one
+// exception is a REMEMBERED flood, see "FLOOD MEMO" at the end of this comment).
 // In that instantiation an op round also takes a RUN OF READS at once: a read leaves a quiescent cluster quiescent, so its next round is
 // its generator's next op; while the op at hand is a read and the one behind it is again an op round's, the read is executed as a cluster
 // round of its own (its rows at its own time, its payload from its own node's set, the time jump, the round count) before the wave-round's
@@ -64,6 +65,14 @@
 // for such a half the stretch's exit does what R0's block and the exit test would have done, and nothing else: the time jump, the round
 // count, the count-down, then the park of the dry half or the release of the parked one and the op round of both.  Everything else goes
 // through the loop's head as ever (see "STEADY LEAVE" at the exit of the flood stretch and sd_m; -DDUO_NO_STEADY compiles it out).
+// FLOOD MEMO.  In that instantiation, at last, a flood is simulated ONCE per origin and pair of clusters, then applied.  A quiet op round
+// takes a broadcast only from a quiescent cluster, there is no draw per message and no nemesis, so what the flood does to the cluster
+// (every node's set gains the value's bit, n_arr and rounds rise, nothing is left queued or held) is a function of the topology and the
+// picked node alone.  The wavefront records, in a table in LDS that its two clusters share, what its own simulation of the first flood from
+// an origin did, per lane, and a later broadcast from that origin by a steady half applies the record in the op round itself: the rounds,
+// deliveries and messages of that flood are not simulated again.  Two halves that come out of an op round with nothing in flight (reads,
+// replayed broadcasts) go straight to their next op round, the DIRECT WAY ON (see "FLOOD MEMO" in sim_kernel_duo; -DDUO_NO_MEMO
+// compiles all of it out, -DDUO_MEMO_VERIFY makes the emulator and -DDUO_PROF builds simulate a remembered flood and compare).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -140,6 +149,24 @@ constexpr bool DUO_STEADY_ON = false;
 #else
 constexpr bool DUO_STEADY_ON = true;
 #endif
+// The flood memo of the steady instantiation (see "FLOOD MEMO" in sim_kernel_duo): a flood from an origin the wavefront has simulated before
+// is applied from the record of that simulation, and two halves with nothing in flight go from one op round to the next directly;
+// -DDUO_NO_MEMO compiles it out for A/B runs (the kernel is then the previous one, instruction for instruction).
+// (the -DDUO_PROF_STRETCH and -DDUO_PROF_STEADY builds count the rounds of simulated floods, inside stretches and at their exits: they leave the
+//  memo out, since a remembered flood has no rounds to count; -DDUO_PROF_MEMO is the profile build of this path)
+#if defined(DUO_NO_MEMO) || defined(DUO_PROF_STRETCH) || defined(DUO_PROF_STEADY)
+constexpr bool DUO_MEMO_ON = false;
+#else
+constexpr bool DUO_MEMO_ON = true;
+#endif
+// what the kernel's MEMO is for the instantiation that has it: msim_launch_duo gives that one the table's LDS
+constexpr bool DUO_MEMO_BUILD = DUO_MEMO_ON && DUO_STEADY_ON && DUO_QUIET_ON && DUO_TRIM_ON && DUO_STRETCH_ON && DUO_PAIR_ON && DUO_PLAN_ON && DUO_FLOOD_ON;
+constexpr u32 DUO_MEMO_BYTES = 32u * 32u * 2u;   // [origin][lane] of 16 bits
+#if defined(DUO_MEMO_VERIFY) && (defined(MSIM_HIPEMU) || defined(DUO_PROF))
+constexpr bool DUO_MEMO_CHECK = true;    // a remembered flood is simulated all the same and compared with its record
+#else
+constexpr bool DUO_MEMO_CHECK = false;
+#endif
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
 // difference of two floods' lengths); one that runs out was paid for nothing and leaves them out of step.  Measured, the longer the
@@ -167,6 +194,7 @@ struct DuoParams {
   u32 off_seq;       // RND: byte offset of the arrival-sequence array (u16 per ring entry) inside a cluster's LDS region
   u32 off_log2;      // RND: byte offset of the Q24 log2 table (one per wavefront, behind both clusters)
   u32 off_dc;        // flood instantiation: byte offset of the block of 32 generator draws inside a cluster's LDS region
+  u32 off_memo;      // memo instantiation: byte offset of the wavefront's table of remembered floods (behind both clusters' regions)
 };
 
 // -ln(u), u = (r+1)/2^32, Q16, integer only: the sampler of engine.hip / the oracle over a copy of the table in LDS
@@ -219,6 +247,12 @@ __device__ __forceinline__ u64 bal(bool pred) { return __ballot(pred); }
 // the mask itself, and a per-lane use reads the lane's bit (lane_in)
 __device__ __forceinline__ u64 hm2(bool lo, bool up) { return (lo ? 0xFFFFFFFFull : 0ull) | (up ? 0xFFFFFFFF00000000ull : 0ull); }
 __device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// a value every lane holds alike, as one the compiler knows to be so (an SGPR)
+#ifdef MSIM_HIPEMU
+#define DUO_UNIFORM(x_) (x_)
+#else
+#define DUO_UNIFORM(x_) ((u32)__builtin_amdgcn_readfirstlane((int)(x_)))
+#endif
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
 
 // element idx_ of an array; BYTES32: as the base plus a 32-bit BYTE offset (the whole array is below 4 GiB), the form whose address is the
@@ -284,6 +318,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   constexpr bool TRIM = DUO_TRIM_ON && STRETCH;
   constexpr bool QUIET = DUO_QUIET_ON && TRIM;                   // ... and give the op wave-round of quiescent flood halves a body of its own
   constexpr bool STEADY = DUO_STEADY_ON && QUIET;                // ... and leave a flood stretch for a park or an op round without R0 and the exit test
+  constexpr bool MEMO = DUO_MEMO_ON && STEADY;                   // ... and simulate a flood once per origin, then apply what that simulation did
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -313,6 +348,14 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     u64 *ptr_ = my_spill;                                                                                                 \
     if (RUNS) {                                                                                                           \
       DUO_LANE_NOW(ms_l); const u32 ms_i = ms_l & 31u;                                                                    \
+      if (MEMO) {                                                                                                              \
+        /* (the memo instantiation: the wavefront's base in SGPRs and a 32-bit byte offset, like the sets; the 64-bit form below took two  \
+           registers more than the superset op round's checked append has to spare there.  The offset fits 32 bits: dp.inst_bytes, the   \
+           distance to the upper cluster's scratch, is below 2 GiB (msim_launch_duo returns MSIM_LAYOUT_DOES_NOT_FIT otherwise), and the    \
+           node's slice starts inside the instance's own spill area, node * spill_cap * 16 < 32 nodes x 65536 envelopes x 16 B = 32 MiB) */ \
+        const u32 ms_off = (DUO_INST_OF(ms_l) - blockIdx.x * 2u) * dp.inst_bytes + (ms_i < N ? ms_i : 0u) * p.spill_cap * 16u;          \
+        ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<unsigned char *>(p.scratch + (size_t)(blockIdx.x * 2u) * p.scratch_words + p.spill_off) + (size_t)ms_off); \
+      } else                                                                                                              \
       ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)DUO_INST_OF(ms_l) * p.scratch_words + p.spill_off) + \
                                      (size_t)(ms_i < N ? ms_i : 0) * p.spill_cap);                                          \
     }
@@ -482,6 +525,53 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // holds by busy == 0 and the caller's own knowledge that nothing is due (a -DDUO_PROF build and the host-emulator build recompute all of
   // it at the use and trap if it differs).
   u64 sd_m = 0;
+  // FLOOD MEMO.  mm_known = the origins whose flood this wavefront remembers (bit = node number; SGPRs, one mask for both halves: they run
+  // the same configuration), mm_rec = the halves that are recording one (a lane mask of whole halves), mm_org = the origins they record
+  // (lower half | upper half << 8).  The table in LDS holds 16 bits per origin and lane (the lane's number inside its half):
+  //   while the origin is being recorded   n_arr & 0x7F | (rounds & 0xFF) << 8, as they stood just before the op round handed out the first hop;
+  //   once it is remembered                 the rise of n_arr (<= 4: a node sends a value once) | the value's bit in sw at the end << 7 |
+  //                                         the rise of rounds << 8 (the same in every lane of the row; < 256: a flood ends within N + 2 rounds).
+  // RECORDING starts in the quiet op round, for a half that takes a broadcast from an origin not remembered (two halves with the same
+  // one: the lower records), and ends where the steady leave finds that half dry and steady (dry_m, sd_m & ~fg_m): there the half holds
+  // and queues nothing, so the rises are the whole flood's, and rounds stands at the dry point (sl_r1 less the round that is next).  A half
+  // that reaches an op round's head or a GENERAL body still recording has not come by there: the recording is dropped (mm_rec is cleared)
+  // and the origin stays unknown.  That covers every place that clears the half's bit of sd_m (the GENERAL body, and through it a
+  // materialisation, a capacity stop and a dropped envelope, which only generic code meets; the tail's view branch and R0's forced or stuck
+  // halves, which the steady leave then declines) and the round limit, which the steady leave declines as well.
+  // WHY A RECORD DOES NOT DEPEND ON THE STATE.  The quiet op round acts on quiescent halves only: nothing queued, held or awaited in any
+  // lane, and the value is fresh, so no node's set has its bit.  In this instantiation a message has no draw and no deadline, and a node
+  // forwards a value once, to its neighbours less the sender (fan_skip), whatever else its set holds.  So which node handles which
+  // envelope in which round follows from adj, fan_skip and the picked node; T stands through the flood; a flooding half is not parked, so
+  // rounds rises by one per wave-round whichever body runs it (stretch, flood, generic or the gossip part of its partner's op round).
+  // REPLAY (step 5 of the quiet op round) puts the half where its flood's dry point would: the rises are added, sw gains the bit where the
+  // record has it, in_n stays 0 and deliver_at INF.  What it does not reproduce is cm and nx (the last envelope handled, the last queue
+  // head).  Their readers behind a dry point: cm is read under `due` (deliver_at <= T) by every body and by the exit test's special-envelope
+  // term, and a dry lane has nothing due; DUO_SEEN_WORD takes an address from cm's value for the generic bodies' prefetch of sw, which a
+  // half in flood mode discards, and which is loaded again behind every change of cm once DUO_MATERIALISE has ended flood mode (cm's
+  // value is an earlier one of the cluster, its word inside the set region); nx is read while in_n != 0 alone, and an arrival at an
+  // empty queue sets it first.  n_arr and n_rsv are read by the epilogue (sums), in_n and deliver_at by the two places that stop a half
+  // (what stays undelivered: nothing, as behind the simulated flood), sw by DUO_FLOOD_WB at the next op round's head (the replayed word is
+  // the simulated one in every lane that holds a node; the other lanes' columns are never read).
+  // The replaying half is dry at once, T standing at the op's time: a simulating partner finds it as it finds a half whose flood was short
+  // (R0's block moves it to its next op, the exit test parks it).  The round limit: a replay takes place only if rounds + the longest
+  // record replayed in this wave-round + the leaving round stays below round_limit in EVERY live half.  In its own half no look at the
+  // limit during the flood could then have found anything; and the partner's limit is looked at whenever R0's block is entered, which the
+  // replaying half's dry point used to cause that many rounds into the partner's flood and now causes at once: the partner's term makes
+  // sure that neither look finds anything.  It also needs T < gen_next < cutoff, room for a value and two rows (sd_m's terms on the state
+  // this round leaves: the half's next round is an op round's) so that no op or view of the half's OWN scheduler could have met the flood
+  // in mid-run.  Its PARTNER's can: a partner that reaches the cutoff, a capacity or its round limit in the same op round forces GENERAL
+  // bodies, with DUO_MATERIALISE, on a half in mid-flood.  The record applies all the same, and the argument rests on this: the generic
+  // code simulates the same deliveries from the materialised queues (the same envelopes in the same rounds, n_arr counted at the commit), no
+  // scheduler acts on the half (its sched_at lies ahead of T until the flood has run dry), and rounds still rises by one per wave-round.
+  // The replayed half is dry in those GENERAL bodies, which then do nothing for it before its own next op.  (The -DDUO_MEMO_VERIFY trap in
+  // the GENERAL body covers a scheduler that acts on the verifying half itself, act_b, and nothing else; a GENERAL body the partner forces
+  // lets the verification run on, and the head of the half's next op round, or the GENERAL body that acts on it, compares or drops it.)
+  u32 mm_known = 0, mm_org = 0; u64 mm_rec = 0;
+  // (addressed from a lane number the optimizer cannot see through, where it is used: no register holds an address of it across the rounds)
+#define DUO_MEMO_AT(org_, l_) (reinterpret_cast<unsigned short *>(smem + dp.off_memo)[(org_) * 32u + ((l_) & 31u)])
+  // -DDUO_MEMO_VERIFY (emulator and -DDUO_PROF builds): the halves whose flood is simulated although it is remembered, their record and
+  // where n_arr and rounds stood; compared when the half next acts (the head of an op round; a GENERAL body that acts on it in mid-flood traps)
+  u64 vf_m = 0; u32 vf_e = 0, vf_n0 = 0, vf_r0 = 0, vf_bit = 0;
   // The helpers below are macros on purpose: as lambdas capturing the state by reference they left the closures (and with
   // them every captured variable) in scratch memory once the optimizer turned a select of two captured values into a select
   // of their addresses.
@@ -794,6 +884,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u32 pf_nst = 0, pf_nstr = 0, pf_ngg = 0; u64 pf_gg = 0;   // flood stretches, the rounds taken inside them, generic gossip rounds and their cycles
   u32 pf_nquiet = 0;   // flood op rounds that took the quiet body (counted in pf_nfop as well)
   u32 pf_nspark = 0, pf_nsleave = 0; u64 pf_sx = 0; bool pf_sleft = false;   // steady parks (counted in pf_npark as well), steady leaves, the cycles of both from the stretch's exit on
+  u32 pf_ndrop = 0;   // recordings dropped (the wavefront's): a half that acted, or met a GENERAL body, before the steady leave had taken its record
+  u32 pf_nrec = 0, pf_nrep = 0, pf_nbout = 0;   // floods recorded (the wavefront's), floods replayed and broadcasts taken outside the quiet body (this lane's cluster's)
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -844,11 +936,17 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     sched_at = lane_in(alive_m) ? sv_sa : INF;                                                                            \
     fg_m = alive_m & ~((rate > 0 ? bal(phase == PH_MAIN) & bal(gen_next < cutoff) : 0ull) | bal(phase == PH_SLEEP));      \
   } while (0)
+  u32 mm_direct = 0;   // MEMO: the tail of an op round has done what leads to the next one (the direct way on); a scalar
   for (;;) {
     // the halves whose scheduler wants a GENERAL round, alive & (force_general | sched_at <= T): recomputed where its parts change (after a
     // GENERAL round, at a time jump, at the round limit); a gossip round adds the halves with a special envelope due
     u64 want_m = alive_m & (fg_m | bal(sched_at <= T));
     u64 op_m = 0, op_due = 0;   // LAT0: the halves that take an op round (see below; 0: the GENERAL body runs), the due envelopes
+    // (MEMO: THE DIRECT WAY ON from the tail of an op round, see there: the next wave-round is the op round of both halves, nothing is due)
+#ifdef DUO_PROF
+    if (MEMO && mm_direct != 0) pf_it = __builtin_readcyclecounter();   // (no R0 and no exit test on the direct way: nothing goes to pf_exit)
+#endif
+    if (MEMO && mm_direct != 0) { op_m = ~0ull; mm_direct = 0; } else
     // ---- gossip rounds of both clusters, until one of them needs a GENERAL round ----
     for (;;) {
 #ifdef DUO_PROF
@@ -1047,6 +1145,24 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
               if ((dry_m & st_due) != 0 || (park_m & st_due) != 0) __builtin_trap();
             }
 #endif
+            if constexpr (MEMO) {
+              // FLOOD MEMO: a recording half is dry and steady: its flood is over, what it did becomes the record of its origin
+              if (const u64 mm_fin = mm_rec & dry_m) {
+                DUO_LANE_NOW(mf_l);
+                if (lane_in(mm_fin)) {
+                  const u32 mf_org = (mm_org >> ((mf_l >> 5) << 3)) & 31u;
+                  const u32 mf_b = DUO_MEMO_AT(mf_org, mf_l);
+                  DUO_MEMO_AT(mf_org, mf_l) = (unsigned short)(((n_arr - mf_b) & 0x7Fu) | (((sw >> ((next_value - 1u) & 31u)) & 1u) << 7) | (((sl_r1 - 1u - (mf_b >> 8)) & 0xFFu) << 8));
+                }
+                if ((u32)mm_fin) mm_known |= 1u << (mm_org & 31u);
+                if ((u32)(mm_fin >> 32)) mm_known |= 1u << ((mm_org >> 8) & 31u);
+                mm_rec &= ~mm_fin;
+                wave_lds_fence();   // (the other half may read the row in its next op round)
+#ifdef DUO_PROF
+                pf_nrec += ((u32)mm_fin ? 1u : 0u) + ((u32)(mm_fin >> 32) ? 1u : 0u);
+#endif
+              }
+            }
             T = lane_in(dry_m) ? sched_at : T;
             rounds = sl_r1;
 #ifdef DUO_PROF
@@ -1107,6 +1223,19 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       //      computes for such a cluster: every worker is free, so the pick is the node of that rank, and it is idle, so its recv! takes
       //      the request at once and the node completes it in this round (busy goes 1 -> 0 within the round) ----
       const bool opn = lane_in(op_m);
+      if constexpr (MEMO) {
+#ifdef DUO_PROF
+        pf_ndrop += ((u32)(mm_rec & op_m) ? 1u : 0u) + ((u32)((mm_rec & op_m) >> 32) ? 1u : 0u);
+#endif
+        mm_rec &= ~op_m;   // a half that acts without having come by the steady leave's record: the recording is dropped (see FLOOD MEMO)
+        if constexpr (DUO_MEMO_CHECK) {
+          if (vf_m & op_m) {   // the simulated flood against its record: the rises, the leaving round, the end state
+            if (lane_in(vf_m & op_m) && (n_arr - vf_n0 != (vf_e & 0x7Fu) || rounds - vf_r0 != (vf_e >> 8) + 1u || in_n != 0 || deliver_at != INF ||
+                                         ((sw >> vf_bit) & 1u) != ((vf_e >> 7) & 1u))) __builtin_trap();
+            vf_m &= ~op_m;
+          }
+        }
+      }
       DUO_UPM_NOW();   // (C)
       if (TRIM && (op_m & fl_m) != 0) DUO_FLOOD_WB(op_m & fl_m);   // (B): the read runs, the read op's copy read the sets from HBM
       // READ RUNS.  An acting cluster is quiescent, and a read leaves it so: the picked node copies its set to the payload, two rows
@@ -1169,6 +1298,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // every other op wave-round (one op, a half outside flood mode, the first op behind a GENERAL body) takes the body below as it is.
       bool quiet = false;
       if constexpr (QUIET) quiet = fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0;
+      u64 dw_m = 0;   // MEMO: the halves this round leaves with nothing in flight: a read, a replayed broadcast (the quiet body knows them)
 #ifdef DUO_PROF
       bool pf_flr = false;
 #endif
@@ -1221,7 +1351,45 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         sw = lane_in(bc_m & DUO_BAL_CMP(val & 31u, ==, 0u, 32)) ? 0u : sw;
         sw |= lane_in(sel_b & bc_m) ? 1u << (val & 31u) : 0u;
         // 5. the broadcast's delivery: the picked node's neighbours hold its envelope, due in the cluster's next round
-        const bool rcv = lane_in(bc_m & DUO_BAL_CMP((adj >> picked) & 1u, !=, 0u, 33));
+        //    FLOOD MEMO: unless the flood from this origin is remembered and may be replayed; then all of it is applied here
+        u64 rp_m = 0;
+        if constexpr (MEMO) {
+          const u64 kn_m = bc_m & DUO_BAL_CMP((mm_known >> picked) & 1u, !=, 0u, 33);   // whole halves: picked is the cluster's
+          const u64 cand_m = kn_m & DUO_BAL_CMP(next_value, <, max_values, 36) & DUO_BAL_CMP(n_rows + 2u, <=, max_rows, 37) &
+                             DUO_BAL_CMP(gen_next, <, cutoff, 36) & DUO_BAL_CMP(T, <, gen_next, 36);
+          if (cand_m) {
+            DUO_LANE_NOW(mr_l);
+            u32 mr_e = 0;
+            if (lane_in(cand_m)) mr_e = DUO_MEMO_AT(picked, mr_l);
+            const u32 mr_k = max(rdlane(mr_e, 0), rdlane(mr_e, 32)) >> 8;   // the longest flood replayed (a half that does not replay: 0)
+            rp_m = (alive_m & ~DUO_BAL_CMP(rounds + mr_k + 1u, <, round_limit, 36)) == 0 ? cand_m : 0ull;
+            if constexpr (DUO_MEMO_CHECK) {   // simulate it all the same; the head of the half's next op round compares
+              if (rp_m) {
+                const bool vf_on = lane_in(rp_m);
+                vf_e = vf_on ? mr_e : vf_e; vf_n0 = vf_on ? n_arr : vf_n0; vf_r0 = vf_on ? rounds : vf_r0; vf_bit = vf_on ? (val & 31u) : vf_bit;
+                vf_m |= rp_m;
+              }
+            }
+#ifdef DUO_PROF
+            pf_nrep += lane_in(rp_m) ? 1u : 0u;
+#endif
+            if constexpr (DUO_MEMO_CHECK) rp_m = 0;
+            if (rp_m) {   // (mr_e is 0 in the lanes of a half that does not replay)
+              n_arr += mr_e & 0x7Fu;
+              sw |= ((mr_e >> 7) & 1u) << (val & 31u);
+              rounds += mr_e >> 8;
+            }
+          }
+          if (const u64 un_m = bc_m & ~kn_m) {   // an origin not remembered (rare): record this flood, see FLOOD MEMO
+            const u32 ms_lo = rdlane(picked, 0), ms_up = rdlane(picked, 32);
+            const u64 ms_m = (un_m == ~0ull && ms_lo == ms_up) ? 0xFFFFFFFFull : un_m;   // (one row, one recorder)
+            DUO_LANE_NOW(ms_l);
+            if (lane_in(ms_m)) DUO_MEMO_AT(picked, ms_l) = (unsigned short)((n_arr & 0x7Fu) | ((rounds & 0xFFu) << 8));
+            mm_rec = ms_m; mm_org = ms_lo | (ms_up << 8);
+          }
+          dw_m = rd_m | rp_m;
+        }
+        const bool rcv = lane_in(bc_m & ~rp_m & DUO_BAL_CMP((adj >> picked) & 1u, !=, 0u, 33));
         n_arr += rcv ? 1u : 0u;
         cm = rcv ? (val | (picked << 16)) : cm;
         deliver_at = rcv ? T : deliver_at;
@@ -1256,6 +1424,9 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       if (!TRIM) n_rsv += due_n ? 1u : 0u;
       pub = bc ? ((STRETCH && fl_round) ? adj : (0x80000000u | (63u << 16) | val)) : pub;   // (the flood bodies publish fan-out masks)
       pub_b |= bal(bc);
+#ifdef DUO_PROF
+      pf_nbout += half_any(bc) ? 1u : 0u;
+#endif
       // a read -> read_ok with the whole set, copied by the cluster's lanes (one reader per cluster)
       u32 cmp_value = val, cmp_len = 0;
       if (const u64 rd_b = bal(sel) & bal(is_rd)) {
@@ -1333,10 +1504,36 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       if (pf_flr) { pf_fop += __builtin_readcyclecounter() - pf_a; pf_nfop++; } else { pf_op += __builtin_readcyclecounter() - pf_a; pf_nop++; }
       pf_nop2 += op_m == ~0ull ? 1u : 0u;
 #endif
+      // THE DIRECT WAY ON (FLOOD MEMO).  Both halves have come out of the quiet body with nothing in flight (dw_m: a read or a replayed
+      // broadcast each) and steady (sd_m, which the tail has just set on the state this round leaves: the view did not run, so alive_m is
+      // what it was, both halves, and nobody is parked: both acted).  The loop's head would find two dry halves: R0's block moves each T
+      // to its sched_at (gen_next, never INF and never behind T), looks at the round limit of both, the round is counted, the exit test
+      // finds st_m in both halves by sd_m and nothing due, and nobody to park: an op round of both, the quiet body by its own test.  That
+      // is what the steady leave does for two dry halves, and it is done here in its words: the same time jump and round count, the same
+      // decline at the limit (round_limit < rounds with the next round counted), and whatever is declined goes to the loop's head untouched.
+      // (park_left, far from 0 while nobody is parked, is not counted down for these rounds: it is set again before anybody looks at it)
+      if constexpr (MEMO) {
+        if (dw_m == ~0ull && sd_m == ~0ull && fg_m == 0 && DUO_BAL_CMP(round_limit, <, rounds + 1u, 36) == 0) {
+#if defined(DUO_PROF) || defined(MSIM_HIPEMU)
+          if (alive_m != ~0ull || park_m != 0 || (in_n | sp_n | busy) != 0 || deliver_at != INF || sched_at < T || sched_at == INF || phase != PH_MAIN ||
+              next_value >= max_values || n_rows + 2u > max_rows || gen_k - dc_base >= 32u) __builtin_trap();   // what R0's block and the exit test would have found
+#endif
+          T = sched_at;
+          rounds += 1u;
+          mm_direct = DUO_UNIFORM(1u);   // (op_m = ~0, op_due = 0: in front of the gossip loop, which is passed by)
+#ifdef DUO_PROF
+          pf_nwave++;
+#endif
+        }
+      }
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
     DUO_MATERIALISE();
     if (STEADY) sd_m = 0;   // (this body changes what the bits stand for, see sd_m)
+#ifdef DUO_PROF
+    if (MEMO) pf_ndrop += ((u32)mm_rec ? 1u : 0u) + ((u32)(mm_rec >> 32) ? 1u : 0u);
+#endif
+    if (MEMO) mm_rec = 0;   // (and a flood it takes part in is not recorded, see FLOOD MEMO)
     // (RUNS: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
     DUO_UPM_NOW();   // TRIM (C)
     u32 gi = i; if (RUNS) MSIM_OPAQUE(gi);
@@ -1347,6 +1544,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     u32 mark = 0, m_kind = 0, m_val = 0;
     const u64 act_b = alive_m & bal(sched_at <= T);
     const bool act = lane_in(act_b);
+    if constexpr (MEMO && DUO_MEMO_CHECK) {   // a scheduler that acts on a half whose remembered flood is still under way: a replay would have been wrong
+      if (lane_in(vf_m & act_b) && (in_n != 0 || deliver_at != INF)) __builtin_trap();
+      vf_m &= ~act_b;
+    }
     if (act_b & bal(phase != PH_MAIN)) {   // rare: db setup, topology, final reads
       if (act && phase == PH_INIT) { mark = is_node; m_kind = DK_INIT; phase = PH_INIT_WAIT; }
       else if (act && phase == PH_TOPO) { mark = is_node; m_kind = DK_TOPO; phase = PH_TOPO_WAIT; }
@@ -1367,6 +1568,9 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       m_kind = gen ? (is_rd ? DK_READ : DK_BCAST) : m_kind;
       m_val = gen && !is_rd ? next_value : m_val;
       next_value += gen && !is_rd && !ovf ? 1u : 0u;
+#ifdef DUO_PROF
+      pf_nbout += gen && !is_rd && !ovf ? 1u : 0u;
+#endif
       gen_k += gen ? 1u : 0u;
       gen_next = gen ? T + __umulhi(r_hi, p.gen_period2_us) : gen_next;
     }
@@ -1550,7 +1754,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     // with -DDUO_PROF_STEADY as well, the lower instance carries instead of the GENERAL bodies' and generic op rounds' cycles and the quiet
     // count: steady parks (11 bits, saturating; they are among the parks) | steady leaves << 11 (11 bits, saturating) | the cycles of both,
     // from the stretch's exit on, / 4096 << 22 (10 bits, saturating) (tools/duo_prof_report.py with STEADY=1)
-    (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg; (void)pf_nspark; (void)pf_nsleave; (void)pf_sx;
+    (void)pf_mat; (void)pf_nst; (void)pf_nstr; (void)pf_ngg; (void)pf_gg; (void)pf_nspark; (void)pf_nsleave; (void)pf_sx; (void)pf_nrec; (void)pf_nrep; (void)pf_nbout; (void)pf_ndrop;
     if (!hi) { m.n_events = pf_ngen | (pf_nop << 16); m.reserved[0] = pf_nwave | (pf_nrun_all << 16); m.reserved[1] = ((u32)(pf_gen >> 10) & 0xFFFFu) | (min((u32)(pf_op >> 10), 31u) << 16) | (min(pf_nquiet, 2047u) << 21);
                m.reserved[2] = ((u32)(pf_tot >> 12) & 0xFFFFu) | (min(pf_npark, 2047u) << 16) | (min(pf_wmax, 31u) << 27);
 #ifdef DUO_PROF_STEADY
@@ -1562,6 +1766,13 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
              }
     else { m.n_events = pf_nfg | (pf_npk << 16); m.reserved[0] = pf_nfop | (min(pf_nop2, 4095u) << 16) | (min(pf_nmat, 15u) << 28); m.reserved[1] = ((u32)(pf_fg >> 10) & 0xFFFFu) | ((u32)(pf_exit >> 10) << 16);
            m.reserved[2] = ((u32)(pf_fop >> 10) & 0xFFFFu) | ((u32)(pf_pk >> 10) << 16); }
+#ifdef DUO_PROF_MEMO
+    // with -DDUO_PROF_MEMO as well, BOTH instances carry in reserved[1], instead of cycles: the cluster's replayed floods (16 bits, saturating) |
+    // its broadcasts taken outside the quiet body << 16 (8 bits, saturating) | the floods the wavefront recorded << 24 (tools/duo_prof_report.py with MEMO=1);
+    // the upper instance's reserved[2] is the number of recordings the wavefront dropped
+    m.reserved[1] = min(pf_nrep, 65535u) | (min(pf_nbout, 255u) << 16) | (min(pf_nrec, 255u) << 24);
+    if (hi) m.reserved[2] = pf_ndrop;   // (the upper instance, instead of the flood op rounds' and parked rounds' cycles: the recordings the wavefront dropped)
+#endif
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }
@@ -1669,6 +1880,10 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   dp.off_dc = 0;
   if (DUO_PLAN_ON && DUO_FLOOD_ON && lat0 && deg4) { dp.off_dc = (u32)off; off += 32 * 8; dp.half_bytes = (u32)off; }
   dp.off_log2 = (u32)(2 * off);
+  // the memo instantiation's table of remembered floods, one per wavefront, behind both clusters' regions (the headline shape: 2560 + 2048
+  // bytes per wavefront, 24 wavefronts per CU as before; the fit test above is not touched: which kernel runs a configuration stays as it was)
+  const bool memo = DUO_MEMO_BUILD && lat0 && deg4;
+  dp.off_memo = memo ? (u32)(2 * off) : 0u;
   dp.deg = duo_degree(c);
   dp.echoback = c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK;
   dp.round_limit = (kp.dev_flags & 0x100u) ? 2000000u : ROUND_LIMIT;
@@ -1676,6 +1891,7 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   // limit can be made to fall anywhere, e.g. inside a run of reads (read at every launch: a test sweeps it within one process)
   if (const char *rl = std::getenv("MSIM_DUO_ROUND_LIMIT")) { const unsigned long v = std::strtoul(rl, nullptr, 0); if (v > 0 && v < ROUND_LIMIT) dp.round_limit = (u32)v; }
   size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
+  if (memo) lds += DUO_MEMO_BYTES;
   lds = std::min(lds + (size_t)DUO_LDS_PAD, (size_t)160 * 1024);
   const dim3 grid((n + 1) / 2);
   if (rnd) return deg4 ? duo_launch<false, true, true>(dp, grid, lds, st) : duo_launch<false, false, true>(dp, grid, lds, st);

@@ -17,7 +17,12 @@ How to read that split: a slow round's cycles are counted from the loop's head, 
 the stretch's exit and the loop's head (the declined test) are in no bucket, and "slow at N cycles each" leaves them out; the fast cycles are a
 10-bit field in units of 4096 per wavefront, read at the middle of its unit (+2048 per wavefront, a bias of at most that much either way).
 The line "steady fields" says in how many wavefronts a field is saturated.  As of round 17 the -DDUO_PROF_STEADY build does not fit its SGPRs (139
-spills, v_readlane / v_writelane inside the loops: profiles/r31_round_split_after.txt), so its counts are exact and its cycles are its own spills'."""
+spills, v_readlane / v_writelane inside the loops: profiles/r31_round_split_after.txt), so its counts are exact and its cycles are its own spills'.
+(Both of those builds leave the flood memo out, see DUO_MEMO_ON in csrc/duo.hip: they count the rounds of simulated floods.)
+MEMO=1: the library is a -DDUO_PROF -DDUO_PROF_MEMO build (tools/variant_lib.sh profmemo duo.hip -DDUO_PROF -DDUO_PROF_MEMO), in which BOTH instances of a
+wavefront carry, in place of the cycles of the GENERAL bodies, generic op rounds, flood gossip rounds and leaving rounds and of the quiet count:
+the floods their cluster replayed (16 bits), the broadcasts it took outside the quiet body (8 bits, saturating) and the floods the wavefront
+recorded (8 bits); the upper instance's reserved[2] is the number of recordings the wavefront dropped.  Only counts are printed: wave-rounds, op wave-rounds, flood gossip and parked rounds, parks, recorded and replayed floods."""
 import os
 import sys
 
@@ -71,6 +76,22 @@ flood = os.environ.get("FLOOD", "1") != "0"
 nfg, nfop, nop2, nmat = [x.astype(np.float64) * flood for x in (up[:, 0], up[:, 1] & 0xFFFF, (up[:, 1] >> 16) & 0xFFF, (up[:, 1] >> 28) & 0xF)]
 cfg_, cexit, cfop, cpk = [x.astype(np.float64) * 1024 * flood for x in (up[:, 2] & 0xFFFF, up[:, 2] >> 16, up[:, 3] & 0xFFFF, up[:, 3] >> 16)]
 cpk += 512 * (npk > 0)   # (the fields are truncated to 1024 cycles; it matters for this small one alone)
+if os.environ.get("MEMO", "0") != "0":
+    lo1 = cyc   # reserved[1] of the lower instances; up[:, 2] is that of the upper ones
+    nrep = ((lo1 & 0xFFFF) + (up[:, 2] & 0xFFFF)).astype(np.float64)
+    nout = (((lo1 >> 16) & 0xFF) + ((up[:, 2] >> 16) & 0xFF)).astype(np.float64)
+    nrec = (lo1 >> 24).astype(np.float64)
+    ndrop = up[:, 3].astype(np.float64)   # reserved[2] of the upper instances: recordings dropped
+    assert ((lo1 >> 24) == (up[:, 2] >> 24)).all(), "the two instances of a wavefront carry the same count of recorded floods"
+    out_sat = int((((lo1 >> 16) & 0xFF) == 255).sum() + (((up[:, 2] >> 16) & 0xFF) == 255).sum())
+    print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms (a -DDUO_PROF build: not the product's time)")
+    print(f"per wavefront: wave-rounds {nwave.mean():.0f} (cluster rounds {rounds.mean():.0f} in the lower cluster), op wave-rounds {nop.mean() + nfop.mean():.0f} "
+          f"({nfop.mean():.0f} flood op rounds, {nop.mean():.0f} generic, {nop2.mean():.0f} with two ops), full GENERAL bodies {ngen.mean():.0f}, "
+          f"flood gossip rounds {nfg.mean():.0f}, parked gossip rounds {npk.mean():.0f}, parks {npark.mean():.0f} (longest wait {wmax}), reads executed ahead in read runs {nrun.mean():.0f}")
+    print(f"flood memo, per wavefront (two clusters): floods recorded {nrec.mean():.1f} (max {nrec.max():.0f}), recordings dropped {ndrop.mean():.2f} (max {ndrop.max():.0f}), floods replayed {nrep.mean():.0f} (min {nrep.min():.0f}), "
+          f"broadcasts taken outside the quiet body {nout.mean():.1f}" + (f" (the field is saturated in {out_sat} instances)" if out_sat else ""))
+    print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}): this build's, SGPR spills and all")
+    sys.exit(0)
 stretch = os.environ.get("STRETCH", "0") != "0"
 if stretch:
     nst, nstr, ngg, cgg = (ev & 0xFFFF).astype(np.float64), (ev >> 16).astype(np.float64), (cyc & 0xFFFF).astype(np.float64), (cyc >> 16).astype(np.float64) * 1024
