@@ -448,6 +448,50 @@ typedef struct msim_availability {
 int msim_check_availability(msim_ctx *ctx, uint32_t mode, double availability, msim_availability *out, uint32_t n_out);
 int msim_check_availability_rows(const msim_op *rows, uint32_t n_rows, uint32_t mode, double availability, msim_availability *out);
 
+/* [upstream] jepsen.checker/stats with its :by-f map, as jepsen.kafka/stats-checker wraps it (core.clj:96-97), and the numbers behind
+ * jepsen.checker/perf's latency-raw / latency-quantiles / rate plots (core.clj:92) — two parts of every test's composed checker.
+ * Upstream jepsen.checker is not vendored: this comment is the contract, parity with its plots is unpinned.
+ *   Client rows are rows whose process is not MSIM_PROCESS_NEMESIS; nemesis rows are ignored throughout.
+ *   :stats  over client completion rows (:ok / :fail / :info): per distinct :f the counts and valid = ok_count > 0; the totals are the
+ *           sums; the overall valid = every :f other than MSIM_F_CRASH is valid (an empty history is valid).  An :f that only ever
+ *           appears in :invoke rows has no entry.
+ *   pairing a completion pairs with the previous client row of its worker thread (process mod concurrency) if that row is an :invoke of
+ *           the same :process — in every history an interpreter produces (a thread has one operation open, after an :info its next
+ *           process is process + concurrency) that is the latest earlier unpaired :invoke of the process.  A completion without such a
+ *           row counts in :stats, has no latency and is counted in `unpaired`; an invocation nothing pairs with in open_count.
+ *   latency latency_us = (time_ns(completion) - time_ns(invocation)) / 1000 in 64 bits (integer division), saturated at 0xFFFFFFFF.
+ *   groups  (f, completion type) over the whole history; with windows (window, f, completion type), window = min(floor(invocation
+ *           time / window_ms), n_windows - 1): every paired op lies in exactly one window.
+ *   record  count, sum_us and the quantiles 0, 0.5, 0.95, 0.99, 1 of a group's latencies: the element at index min(n - 1,
+ *           floor(n * q)) of the ascending latencies, n * q an IEEE double product (the rule of msim_check_result.stable_latency_ms).
+ *           An empty group is all zeros. */
+#define MSIM_PERF_MAX_F 4          /* most distinct client :f of any workload (kafka: send poll assign crash) */
+#define MSIM_PERF_MAX_WINDOWS 16
+typedef struct msim_latency_dist { uint32_t count; uint32_t q_us[5]; uint64_t sum_us; } msim_latency_dist;       /* 32 B */
+typedef struct msim_f_stats {
+  uint32_t f;                      /* MSIM_F_*, 0xFFFFFFFF = unused slot */
+  uint32_t valid, count, ok_count, fail_count, info_count, unpaired, reserved;
+  msim_latency_dist latency[3];    /* by completion type: ok, fail, info */
+} msim_f_stats;
+typedef struct msim_perf_result {
+  uint32_t valid, n_f, count, ok_count, fail_count, info_count, open_count;
+  uint32_t flags;                  /* bit 0: more than MSIM_PERF_MAX_F distinct :f — the history's record is not complete (by_f holds the
+                                      MSIM_PERF_MAX_F lowest; valid and the totals cover every :f) */
+  msim_f_stats by_f[MSIM_PERF_MAX_F];   /* ascending MSIM_F_*; unused slots are zero with f = 0xFFFFFFFF */
+} msim_perf_result;
+/* Every history of the last run from the HBM-resident rows (csrc/perf_check_dev.hip, one wavefront per history), on the context's
+ * stream: like msim_check it may be called straight after msim_run_async on that stream.  out[n_out >= n_instances]; `windows` (NULL
+ * or n_windows == 0: whole-history records only) receives n_instances x n_windows x MSIM_PERF_MAX_F x 3 records, the :f slots in
+ * by_f's order.  Blocking. */
+int msim_check_perf(msim_ctx *ctx, uint32_t window_ms, uint32_t n_windows, msim_perf_result *out, uint32_t n_out, msim_latency_dist *windows);
+/* One history on the host, no device: the twin the device is held to. */
+int msim_check_perf_rows(const msim_op *rows, uint32_t n_rows, uint32_t concurrency, uint32_t window_ms, uint32_t n_windows,
+                         msim_perf_result *out, msim_latency_dist *windows);
+/* `n_histories` histories given on the host in slabs (history i at rows + i * max_rows, n_rows[i] rows used: the convention of
+ * msim_check_set_full_batch) through the device kernel; max_rows < 65535 and concurrency 1..128 as for every device checker. */
+int msim_check_perf_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, uint32_t concurrency,
+                          uint32_t window_ms, uint32_t n_windows, msim_perf_result *out, msim_latency_dist *windows);
+
 /* Host-only utility: one instance's net journal in the reference's on-disk format — the bytes of a
  * `store/<test>/net-journal/<stripe>.fressian` file as maelstrom.net.journal writes it (net/journal.clj:55-141,220-239: one
  * Fressian "ev" struct per log-send! / log-recv!, "msg" structs with cached src / dest, bodies through write-body!), for the

@@ -46,8 +46,10 @@ EXPORTS = [
     "msim_selftest_wave", "msim_last_error", "msim_destroy",
     "msim_comm_unique_id", "msim_comm_init", "msim_gather", "msim_journal_fressian_rows",
     "msim_check_availability", "msim_check_availability_rows",
+    "msim_check_perf", "msim_check_perf_rows", "msim_check_perf_batch",
 ]
 AVAIL_NIL, AVAIL_TOTAL, AVAIL_FRACTION = range(3)
+PERF_MAX_F, PERF_MAX_WINDOWS = 4, 16
 COMM_ID_BYTES = 128
 
 
@@ -103,6 +105,20 @@ class Availability(C.Structure):
     _fields_ = [("valid", C.c_uint32), ("ok_fraction", C.c_float), ("ok_count", C.c_uint32), ("invoke_count", C.c_uint32)]
 
 
+class LatencyDist(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("q_us", C.c_uint32 * 5), ("sum_us", C.c_uint64)]
+
+
+class FStats(C.Structure):
+    _fields_ = [("f", C.c_uint32), ("valid", C.c_uint32), ("count", C.c_uint32), ("ok_count", C.c_uint32), ("fail_count", C.c_uint32),
+                ("info_count", C.c_uint32), ("unpaired", C.c_uint32), ("reserved", C.c_uint32), ("latency", LatencyDist * 3)]
+
+
+class PerfResult(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("n_f", C.c_uint32), ("count", C.c_uint32), ("ok_count", C.c_uint32), ("fail_count", C.c_uint32),
+                ("info_count", C.c_uint32), ("open_count", C.c_uint32), ("flags", C.c_uint32), ("by_f", FStats * PERF_MAX_F)]
+
+
 class Gathered(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("payload", C.c_void_p), ("meta", C.c_void_p), ("stats", C.c_void_p),
                 ("rows_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("meta_bytes", C.c_uint64), ("stats_bytes", C.c_uint64),
@@ -110,6 +126,7 @@ class Gathered(C.Structure):
 
 
 assert C.sizeof(Config) == 120, C.sizeof(Config)
+assert C.sizeof(LatencyDist) == 32 and C.sizeof(FStats) == 128 and C.sizeof(PerfResult) == 544
 assert C.sizeof(Op) == 16 and C.sizeof(NetStats) == 48 and C.sizeof(InstMeta) == 32 and C.sizeof(CheckResult) == 68 and C.sizeof(Event) == 16
 
 _lib = None
@@ -183,6 +200,10 @@ def load():
     lib.msim_check_availability.argtypes = [C.c_void_p, C.c_uint32, C.c_double, P(Availability), C.c_uint32]
     lib.msim_check_availability_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, P(Availability)]
     lib.msim_check_availability.restype = lib.msim_check_availability_rows.restype = C.c_int
+    lib.msim_check_perf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.msim_check_perf_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.msim_check_perf_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.msim_check_perf.restype = lib.msim_check_perf_rows.restype = lib.msim_check_perf_batch.restype = C.c_int
     lib.msim_comm_unique_id.argtypes = [C.c_char_p]
     lib.msim_comm_init.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
     lib.msim_gather.argtypes = [C.c_void_p, C.c_int, P(Gathered)]

@@ -81,6 +81,8 @@ static void free_buffers(msim_ctx *c) {
   if (c->h_journal) (void)hipHostFree(c->h_journal);
   if (c->d_check_scratch) (void)msim_dev_free(c->d_check_scratch);
   c->d_check_scratch = nullptr; c->cap_check_scratch = 0;
+  if (c->d_perf_scratch) (void)msim_dev_free(c->d_perf_scratch);
+  c->d_perf_scratch = nullptr; c->cap_perf_scratch = 0;
   if (c->d_compact) (void)msim_dev_free(c->d_compact);
   if (c->d_off) (void)msim_dev_free(c->d_off);
   if (c->d_compact2) (void)msim_dev_free(c->d_compact2);
@@ -294,6 +296,7 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
     MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check, poison, (size_t)ctx->cap_inst * sizeof(msim_check_result), st));
     if (ctx->d_journal) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_journal, poison, (size_t)ctx->cap_inst * c.journal_capacity * sizeof(msim_event), st));
     if (ctx->d_check_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check_scratch, poison, ctx->cap_check_scratch, st));
+    if (ctx->d_perf_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_perf_scratch, poison, ctx->cap_perf_scratch, st));
   }
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));   // (the launch's duration is read from these events on its own stream: msim_last_kernel_ms)
   hipError_t e;

@@ -38,6 +38,7 @@ struct msim_ctx {
   uint64_t *h_row_off = nullptr, *h_pay_off = nullptr, *h_ev_off = nullptr;  // compacted offsets per instance
   // fetch path: device-side compaction buffers + grow-only capacities (bytes) of the pinned mirrors
   void *d_check_scratch = nullptr; size_t cap_check_scratch = 0;  // checker.hip: read records per instance
+  void *d_perf_scratch = nullptr; size_t cap_perf_scratch = 0;    // perf_check_dev.hip: latency records per instance, the results behind them
   void *d_compact = nullptr; uint64_t *d_off = nullptr;
   void *d_compact2 = nullptr; uint64_t *d_off2 = nullptr; size_t cap_compact2 = 0, cap_off2 = 0;   // the payload's own pair (both compactions are queued before the first copy)
   bool fetch_pending = false;      // msim_fetch_begin has queued the copies; msim_fetch waits for them

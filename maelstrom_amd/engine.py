@@ -20,6 +20,12 @@ CHECK_DT = np.dtype([("valid", "<u4"), ("attempt_count", "<u4"), ("stable_count"
                      ("never_read_count", "<u4"), ("stale_count", "<u4"), ("duplicated_count", "<u4"),
                      ("error_count", "<u4"), ("stable_latency_ms", "<u4", (5,)), ("op_count", "<u4"),
                      ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4")])
+LATENCY_DT = np.dtype([("count", "<u4"), ("q_us", "<u4", (5,)), ("sum_us", "<u8")])
+F_STATS_DT = np.dtype([("f", "<u4"), ("valid", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
+                       ("unpaired", "<u4"), ("reserved", "<u4"), ("latency", LATENCY_DT, (3,))])
+PERF_DT = np.dtype([("valid", "<u4"), ("n_f", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
+                    ("open_count", "<u4"), ("flags", "<u4"), ("by_f", F_STATS_DT, (A.PERF_MAX_F,))])
+PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
 WORKLOADS = {"echo": A.WL_ECHO, "broadcast": A.WL_BROADCAST, "g-set": A.WL_G_SET, "lin-kv": A.WL_LIN_KV,
              "txn-list-append": A.WL_TXN_LIST_APPEND, "pn-counter": A.WL_PN_COUNTER, "g-counter": A.WL_G_COUNTER, "unique-ids": A.WL_UNIQUE_IDS,
@@ -172,6 +178,16 @@ class Engine:
         res = (A.Availability * self.n)()
         self._chk(self.lib.msim_check_availability(self._ctx, mode, a, res, self.n), "msim_check_availability")
         return [{"valid?": bool(r.valid), "ok-fraction": float(r.ok_fraction), "ok-count": r.ok_count, "invoke-count": r.invoke_count} for r in res]
+
+    def check_perf(self, window_s=None, n_windows=0):
+        """[upstream] jepsen.checker/stats with :by-f and the numbers behind jepsen.checker/perf's latency plots (core.clj:92-97) over
+        every history of the last run, on the device (msim_check_perf): one record per history as check_perf_rows gives it.  With
+        `window_s` and `n_windows` (at most 16) each record also has "windows": the latency records per time window of the invocation."""
+        window_ms, n_windows = _perf_windows(window_s, n_windows)
+        out = np.zeros(self.n, dtype=PERF_DT)
+        win = np.zeros((self.n, n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
+        self._chk(self.lib.msim_check_perf(self._ctx, window_ms, n_windows, out.ctypes.data, self.n, win.ctypes.data if n_windows else None), "msim_check_perf")
+        return [decode_perf(out[i], win[i] if n_windows else None) for i in range(self.n)]
 
     # ---- multi-GPU ensemble (include/maelsim.h "multi-GPU ensemble"; maelstrom_amd/ensemble.py) ----
     @staticmethod
@@ -628,6 +644,96 @@ def check_availability_rows(rows, availability=None):
     if rc:
         raise EngineError(f"msim_check_availability_rows: {rc}")
     return {"valid?": bool(r.valid), "ok-fraction": float(r.ok_fraction), "ok-count": r.ok_count, "invoke-count": r.invoke_count}
+
+
+def _perf_windows(window_s, n_windows):
+    n_windows = int(n_windows)
+    if n_windows < 0 or n_windows > A.PERF_MAX_WINDOWS:
+        raise EngineError(f"n_windows must be 0..{A.PERF_MAX_WINDOWS}")
+    if not n_windows:
+        return 0, 0
+    window_ms = int(round((window_s or 0) * 1000))
+    if window_ms <= 0 or window_ms >= 2**32:
+        raise EngineError("windows need a window_s of at least one millisecond")
+    return window_ms, n_windows
+
+
+def _decode_latency(d):
+    return {"count": int(d["count"]), "sum-us": int(d["sum_us"]), "quantiles-us": {q: int(v) for q, v in zip(PERF_QUANTILES, d["q_us"])}}
+
+
+def decode_perf(rec, windows=None):
+    """One msim_perf_result (a PERF_DT record; `windows` its [n_windows][slot][type] latency records) as maps: the :stats fields,
+    "open-count", "complete?" (False: more than four distinct :f, "by-f" holds the four lowest), per :f the counts, "unpaired" and
+    "latency" by completion type; "windows" = per window {:f {type latency}}."""
+    names = [F_KW.get(int(rec["by_f"][k]["f"]), int(rec["by_f"][k]["f"])) for k in range(int(rec["n_f"]))]
+    out = {"valid?": bool(rec["valid"]), "count": int(rec["count"]), "ok-count": int(rec["ok_count"]), "fail-count": int(rec["fail_count"]),
+           "info-count": int(rec["info_count"]), "open-count": int(rec["open_count"]), "complete?": not (int(rec["flags"]) & 1), "by-f": {}}
+    for k, name in enumerate(names):
+        fs = rec["by_f"][k]
+        out["by-f"][name] = {"valid?": bool(fs["valid"]), "count": int(fs["count"]), "ok-count": int(fs["ok_count"]), "fail-count": int(fs["fail_count"]),
+                             "info-count": int(fs["info_count"]), "unpaired": int(fs["unpaired"]),
+                             "latency": {TYPE_KW[t + 1]: _decode_latency(fs["latency"][t]) for t in range(3)}}
+    if windows is not None:
+        out["windows"] = [{name: {TYPE_KW[t + 1]: _decode_latency(w[k][t]) for t in range(3)} for k, name in enumerate(names)} for w in windows]
+    return out
+
+
+def stats_map(record):
+    """The reference's :stats map (doc/02-echo/index.md:369-378) of a check_perf / check_perf_rows record."""
+    keys = ("valid?", "count", "ok-count", "fail-count", "info-count")
+    m = {k: record[k] for k in keys}
+    m["by-f"] = {f: {k: fs[k] for k in keys} for f, fs in record["by-f"].items()}
+    return m
+
+
+def perf_census(records):
+    """An ensemble's per-history records (Engine.check_perf) pooled on the host, next to anomaly_census: per (:f, completion type) that
+    occurs, how many histories have it, the total count, the mean latency in us (sum of sum-us / total count) and the min, median and
+    max over those histories of each quantile."""
+    pools = {}
+    for rec in records:
+        for f, fs in rec["by-f"].items():
+            for typ, d in fs["latency"].items():
+                if d["count"]:
+                    pools.setdefault((f, typ), []).append(d)
+    census = {}
+    for key, ds in sorted(pools.items()):
+        count = sum(d["count"] for d in ds)
+        census[key] = {"histories": len(ds), "count": count, "mean-us": sum(d["sum-us"] for d in ds) / count,
+                       "quantiles-us": {q: {"min": int(min(v)), "median": float(np.median(v)), "max": int(max(v))}
+                                        for q in PERF_QUANTILES for v in [[d["quantiles-us"][q] for d in ds]]}}
+    return census
+
+
+def check_perf_rows(rows, concurrency, window_s=None, n_windows=0):
+    """:stats / :perf of one history on the host (msim_check_perf_rows): the record Engine.check_perf gives per history."""
+    window_ms, n_windows = _perf_windows(window_s, n_windows)
+    rows = np.ascontiguousarray(rows)
+    out = np.zeros(1, dtype=PERF_DT)
+    win = np.zeros((n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
+    rc = A.load().msim_check_perf_rows(rows.ctypes.data if len(rows) else None, len(rows), int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
+    if rc:
+        raise EngineError(f"msim_check_perf_rows: {rc}")
+    return decode_perf(out[0], win if n_windows else None)
+
+
+def check_perf_batch(histories, concurrency, window_s=None, n_windows=0, max_rows=None, device=0):
+    """:stats / :perf of several histories (arrays of rows) through the device kernel behind Engine.check_perf (msim_check_perf_batch);
+    `max_rows` = the slab size (default: the longest history)."""
+    window_ms, n_windows = _perf_windows(window_s, n_windows)
+    hs = [np.ascontiguousarray(h) for h in histories]
+    mr = int(max_rows) if max_rows else max(1, max(len(h) for h in hs))
+    slab = np.zeros((len(hs), mr), dtype=OP_DT)
+    for i, h in enumerate(hs):
+        slab[i, :len(h)] = h
+    nr = np.asarray([len(h) for h in hs], dtype=np.uint32)
+    out = np.zeros(len(hs), dtype=PERF_DT)
+    win = np.zeros((len(hs), n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
+    rc = A.load().msim_check_perf_batch(device, slab.ctypes.data, nr.ctypes.data, mr, len(hs), int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
+    if rc:
+        raise EngineError(f"msim_check_perf_batch: {rc}")
+    return [decode_perf(out[i], win[i] if n_windows else None) for i in range(len(hs))]
 
 
 def check_lin_kv_batch(histories, device=0):
