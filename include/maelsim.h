@@ -306,9 +306,12 @@ int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances,
  * Results via msim_check_results. */
 int msim_check(msim_ctx *ctx);
 
-/* txn-rw-register only (else MSIM_E_UNSUPPORTED): on != 0 makes the next msim_check give, for EVERY history, the full record of
- * msim_check_rw_rows — the histories the consistency model accepts name their allowed cycle classes and carry the full graph's edge and
- * cycle counts (an anomaly census of an ensemble).  Off (the default), a history the first pass proves valid keeps that pass's record. */
+/* The two transactional workloads only (else MSIM_E_UNSUPPORTED).  txn-rw-register: on != 0 makes the next msim_check give, for EVERY
+ * history, the full record of msim_check_rw_rows — the histories the consistency model accepts name their allowed cycle classes and carry
+ * the full graph's edge and cycle counts (an anomaly census of an ensemble).  Off (the default), a history the first pass proves valid
+ * keeps that pass's record.  txn-list-append: on != 0 makes msim_check analyse what the clean passes cannot prove clean on the device
+ * too (txn_classify_kernel, as msim_classify_txn_batch), judged by the context's consistency model; the records are the same either way,
+ * msim_check_host_rechecks then counts only what reached the host.  Off (the default), the host analyses those histories. */
 int msim_set_check_classify(msim_ctx *ctx, uint32_t on);
 
 /* Developer switches of a context (A/B comparisons, tracing; never needed for normal use) — the same bits the environment variable
@@ -317,7 +320,8 @@ int msim_set_check_classify(msim_ctx *ctx, uint32_t on);
 int msim_set_dev_flags(msim_ctx *ctx, uint32_t flags);
 
 /* How many histories of the last msim_check the device handed to the host (lin-kv: the search needed more than 512
- * configurations; txn-list-append: not provably clean, i.e. the host analysed and classified it; txn-rw-register: beyond the device
+ * configurations; txn-list-append: not provably clean, i.e. the host analysed and classified it — after msim_set_check_classify only
+ * what is beyond the device capacities, see msim_classify_txn_batch; txn-rw-register: beyond the device
  * capacities, see msim_check_rw_batch; else 0). */
 uint32_t msim_check_host_rechecks(const msim_ctx *ctx);
 
@@ -327,6 +331,16 @@ uint32_t msim_check_host_rechecks(const msim_ctx *ctx);
  * (strict-serializable).  out[i] is what msim_check_txn_rows gives for history i. */
 int msim_check_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                          uint32_t n_histories, msim_check_result *out);
+
+/* txn-list-append: as msim_check_txn_batch, judged under `consistency_model` (MSIM_CM_*), but a history the clean passes cannot prove
+ * clean is analysed in full on the device (csrc/txn_check_dev.hip, txn_classify_kernel): every non-cycle anomaly accumulated, the
+ * tagged edges built, the cycles classified (G0 / G1c / G-single / G2, -realtime).  out[i] is field for field what the host analysis
+ * of msim_check_txn_rows writes (valid by msim_violated_anomalies under the model).  Only a (key, element) appended more than once, a
+ * payload outside its area and histories beyond the kernel's table capacities (4096 keys, 65536 writer-table entries, 64 open calls,
+ * rows / 2 + 65 transactions and 32 edges per transaction of the batch's longest history) go to the host; *n_host (may be null) = how
+ * many those were. */
+int msim_classify_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                            uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host);
 
 /* txn-rw-register: the same for the rw-register analysis under `consistency_model` (MSIM_CM_*): the device proves a history free of
  * everything the model proscribes (csrc/rw_check_dev.hip, rw_check_kernel); the others are analysed and their cycles classified by

@@ -144,8 +144,9 @@ class Engine:
         self.n = n_instances
 
     def check(self, classify=False):
-        """msim_check.  classify=True (txn-rw-register only): every history's record is the full analysis of check_rw_history, its allowed
-        cycle classes named (msim_set_check_classify); see anomaly_census."""
+        """msim_check.  classify=True (msim_set_check_classify; the two transactional workloads only).  txn-rw-register: every history's
+        record is the full analysis of check_rw_history, its allowed cycle classes named.  txn-list-append: a history that is not provably
+        clean is analysed and its cycles classified on the device, not on the host cores (the records are the same).  See anomaly_census."""
         if classify or getattr(self, "_classify", False):
             self._chk(self.lib.msim_set_check_classify(self._ctx, 1 if classify else 0), "msim_set_check_classify")
             self._classify = bool(classify)
@@ -837,6 +838,14 @@ def classify_rw_batch(histories, consistency_model="read-committed", device=0):
     """txn-rw-register: the full analysis of every history on the device (msim_classify_rw_batch): each record is what
     check_rw_history's msim_check_rw_rows writes, the allowed cycle classes of valid histories included.  Returns (records, n_host)."""
     return check_rw_batch(histories, consistency_model, device, _entry="msim_classify_rw_batch")
+
+
+def classify_txn_batch(histories, consistency_model="strict-serializable", device=0):
+    """txn-list-append: several histories, each (rows, payload), analysed on the device whatever they hold (msim_classify_txn_batch): the
+    clean passes of check_txn_batch first, then the full analysis (every anomaly, the cycle classes) of what they cannot prove clean.
+    Each record is what check_txn_batch gives, judged under `consistency_model`; the host analysis only takes what exceeds the device
+    capacities.  Returns (CHECK_DT records, how many histories went to the host)."""
+    return check_rw_batch(histories, consistency_model, device, _entry="msim_classify_txn_batch")
 
 
 def anomaly_census(results):
