@@ -73,6 +73,9 @@
 // deliveries and messages of that flood are not simulated again.  Two halves that come out of an op round with nothing in flight (reads,
 // replayed broadcasts) go straight to their next op round, the DIRECT WAY ON (see "FLOOD MEMO" in sim_kernel_duo; -DDUO_NO_MEMO
 // compiles all of it out, -DDUO_MEMO_VERIFY makes the emulator and -DDUO_PROF builds simulate a remembered flood and compare).
+// STEADY RUN.  A remembered broadcast being as cheap as a read, the loop of the read runs takes it as a cluster round too: a half goes from
+// one block of 32 draws to the next inside the loop, and the quiet body, the tail and the head of an op wave-round are paid once per
+// block (see "STEADY RUN" at the read runs of sim_kernel_duo; -DDUO_NO_STEADY_RUN compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -167,6 +170,19 @@ constexpr bool DUO_MEMO_CHECK = true;    // a remembered flood is simulated all 
 #else
 constexpr bool DUO_MEMO_CHECK = false;
 #endif
+// The steady run of the memo instantiation (see "STEADY RUN" at the read runs of sim_kernel_duo): the loop of the read runs also takes a
+// broadcast whose flood is remembered, as a cluster round of its own, so that a half goes through a whole block of draws inside the loop;
+// -DDUO_NO_STEADY_RUN compiles it out for A/B runs (the kernel is then the previous one, instruction for instruction).  The verifying
+// build (DUO_MEMO_CHECK) takes no broadcast into a run: it simulates every remembered flood.
+// (the -DDUO_PROF builds split the op wave-rounds by the body that took them, with the cycles of each kind and the count of quiet ones:
+//  they leave the steady run out, as the -DDUO_PROF_STRETCH and -DDUO_PROF_STEADY builds leave the memo out, since it leaves a few dozen op
+//  wave-rounds per wavefront to split, one per block of draws; -DDUO_PROF_RUN is the profile build of this path)
+#if defined(DUO_NO_STEADY_RUN) || (defined(DUO_PROF) && !defined(DUO_PROF_RUN))
+constexpr bool DUO_SRUN_ON = false;
+#else
+constexpr bool DUO_SRUN_ON = true;
+#endif
+constexpr u32 DUO_SRUN_FAR = 8192u;   // more than one run can add to a cluster's rounds: 31 ops of a block x (a record of at most 255 rounds + 1)
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
 // difference of two floods' lengths); one that runs out was paid for nothing and leaves them out of step.  Measured, the longer the
@@ -319,7 +335,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   constexpr bool QUIET = DUO_QUIET_ON && TRIM;                   // ... and give the op wave-round of quiescent flood halves a body of its own
   constexpr bool STEADY = DUO_STEADY_ON && QUIET;                // ... and leave a flood stretch for a park or an op round without R0 and the exit test
   constexpr bool MEMO = DUO_MEMO_ON && STEADY;                   // ... and simulate a flood once per origin, then apply what that simulation did
-  constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                 // latency 0: a time jump goes to the scheduler's next event
+  constexpr bool SRUN = DUO_SRUN_ON && MEMO && !DUO_MEMO_CHECK;   // ... and take a remembered broadcast as a cluster round of the read runs' loop
+  constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
   // FLOOD: the cluster's rows and payload are addressed like its sets, from the wavefront's base (SGPRs: the lower cluster's) and the
@@ -886,6 +903,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u32 pf_nspark = 0, pf_nsleave = 0; u64 pf_sx = 0; bool pf_sleft = false;   // steady parks (counted in pf_npark as well), steady leaves, the cycles of both from the stretch's exit on
   u32 pf_ndrop = 0;   // recordings dropped (the wavefront's): a half that acted, or met a GENERAL body, before the steady leave had taken its record
   u32 pf_nrec = 0, pf_nrep = 0, pf_nbout = 0;   // floods recorded (the wavefront's), floods replayed and broadcasts taken outside the quiet body (this lane's cluster's)
+  u32 pf_nrunb = 0, pf_nit = 0;   // broadcasts of this lane's cluster taken in runs (counted in pf_nrep as well), iterations of the runs' loop (the wavefront's)
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -1251,6 +1269,89 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // masks its index with 31, so a lane of a half that does not act reads some draw of the block and never outside it; and the three
       // places that look at the round limit agree: a read runs ahead only while rounds < round_limit, which is exactly when R0 of the
       // cluster's next round would not force a GENERAL round (rounds >= round_limit) and the scheduler's view would not stop it (>).
+      // STEADY RUN (the memo instantiation).  A broadcast whose flood is remembered is as cheap as a read: two rows, next_value, the set word's
+      // bit and the recorded rises.  So the loop takes it as a cluster round too, and a half goes from one block of 32 draws to the next
+      // inside the loop: the quiet body, the tail, the head and the write-back (B) are paid once per block, not once per op.  A half's op
+      // at hand is taken if it is
+      //   (a) a read, under the read runs' conditions, unchanged; or
+      //   (b) a broadcast, in an op wave-round that is `quiet` at entry (fl_ok, every live half acts, all in flood mode: the replay's own
+      //       precondition; sr_m), from an origin in mm_known, whose op after it is again an op round's: its draw is in the block (k < 31),
+      //       T < next < cutoff (no op of the half's own scheduler could have met the flood in mid-run), rows for both ops, and a value
+      //       left for the op after (st_m's term: a broadcast moves next_value), and with every live half FAR from the round limit: rounds +
+      //       DUO_SRUN_FAR < round_limit, tested once per op round.  One run adds at most 31 x (255 + 1) rounds to a half, so no look at the
+      //       limit, the half's own or its partner's, could have found anything in any round the run stands for; under a low
+      //       MSIM_DUO_ROUND_LIMIT the run takes reads only and the limit is found where it always was.
+      // A broadcast's iteration does for its half what the quiet body's steps 1, 3, 4, the replay and the direct way on do: the pick, n_cl,
+      // gen_k, next_value, the two rows at T, the set word (0 where the value opens a word; the record's bit, which the picked node's own
+      // lane carries as well: its record was taken from an sw with the bit set), n_arr and rounds by the record, then T = next and the next
+      // round's count.  A half's rounds do not depend on its partner's (a parked round is the one the direct way on counts), so the two halves
+      // take their iterations independently.  gen_next and sched_at are set by the op that ends the run, in the round below, as for reads.
+      // Whatever else the op at hand is (an origin not remembered, the block's last draw, the cutoff, a capacity) ends that half's run and is
+      // the op of the round below, as before.  A recording cannot be open here: the head has dropped those of the acting halves.
+      // THE SETS.  Reads copy from HBM, and inside a run sw can be newer than HBM (sr_dirty, a scalar mask of whole halves): a read's
+      // iteration writes sw back first (it sees the bits of the broadcasts before it), a broadcast that opens a word writes the completed
+      // word back before sw is reset, and the run's end leaves nothing dirty for the round below.
+      if constexpr (SRUN) {
+        u64 sr_m = 0, sr_dirty = 0;
+        if (fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0 && (alive_m & ~DUO_BAL_CMP(rounds + DUO_SRUN_FAR, <, round_limit, 36)) == 0) sr_m = op_m;
+        for (;;) {
+          const u32 rr_k = gen_k - dc_base;
+          u32 rr_hi, rr_lo; DUO_DRAW(gen_k, rr_hi, rr_lo);
+          const u32 rr_next = T + __umulhi(rr_hi, p.gen_period2_us);
+          const u32 rr_words = (next_value + 31u) >> 5;
+          const u32 rr_node = scale32(rr_lo, N);
+          const u64 rr_rd = DUO_BAL_CMP(rr_lo & 1u, !=, 0u, 33);
+          const u64 rr_c = op_m & bal(rr_k < 31u) & bal(rr_next < cutoff) & bal(n_rows + 4u <= max_rows);
+          const u64 rr_b = rr_c & rr_rd & bal(n_payload + rr_words <= max_pay) & bal(rounds < round_limit);
+          u64 sb_b = 0;
+          if (sr_m) sb_b = sr_m & rr_c & ~rr_rd & DUO_BAL_CMP((mm_known >> rr_node) & 1u, !=, 0u, 33) & DUO_BAL_CMP(T, <, rr_next, 36) &
+                           DUO_BAL_CMP(next_value + 1u, <, max_values, 36);
+          const u64 sr_go = rr_b | sb_b;
+          if (!sr_go) break;
+          const bool rr_go = lane_in(sr_go), rr_rdn = lane_in(rr_b);
+          const bool rr_sel = rr_go && i == rr_node;
+          n_cl += rr_sel ? 1u : 0u;
+          if (const u64 sr_wb = sr_dirty & (rr_b | (sb_b & DUO_BAL_CMP(next_value & 31u, ==, 0u, 32)))) { DUO_FLOOD_WB(sr_wb); sr_dirty &= ~sr_wb; }
+          wave_lds_fence();
+          for (u32 w = i; rr_b & bal(w < rr_words); w += 32)
+            if (rr_rdn && w < rr_words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + rr_node * 4u);
+          const u32 rr_val = next_value;
+          if (rr_sel) {
+            u32 rr_i = i; MSIM_OPAQUE(rr_i);   // (the rows' constant words are built here, not kept in registers across the rounds)
+            const u64 tns = (u64)T * 1000ull;
+            const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
+            const u32 fk = rr_rdn ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
+            DUO_ROW(n_rows) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (rr_i << 12), rr_rdn ? MSIM_NO_VALUE : rr_val);
+            DUO_ROW(n_rows + 1u) = make_uint4(tlo, thi | (rr_rdn ? rr_words << 16 : 0u), MSIM_T_OK | (fk << 2) | (rr_i << 12), rr_rdn ? n_payload : rr_val);
+          }
+          n_payload += rr_rdn ? rr_words : 0u;
+          if (sb_b) {   // the remembered flood of each broadcasting half (sb_e is 0 in the other half's lanes)
+            DUO_LANE_NOW(sb_l);
+            u32 sb_e = 0;
+            if (lane_in(sb_b)) sb_e = DUO_MEMO_AT(rr_node, sb_l);
+#ifdef MSIM_HIPEMU
+            if (rr_sel && !rr_rdn && ((sb_e >> 7) & 1u) == 0) __builtin_trap();   // the picked node's own lane carries the bit
+#endif
+            sw = lane_in(sb_b & DUO_BAL_CMP(rr_val & 31u, ==, 0u, 32)) ? 0u : sw;
+            sw |= ((sb_e >> 7) & 1u) << (rr_val & 31u);
+            n_arr += sb_e & 0x7Fu;
+            rounds += sb_e >> 8;
+            next_value += lane_in(sb_b) ? 1u : 0u;
+            sr_dirty |= sb_b;
+#ifdef DUO_PROF
+            pf_nrunb += lane_in(sb_b) ? 1u : 0u; pf_nrep += lane_in(sb_b) ? 1u : 0u;
+#endif
+          }
+          n_rows += rr_go ? 2u : 0u;
+          gen_k += rr_go ? 1u : 0u;
+          T = rr_go ? rr_next : T;      // (the next round's R0: nothing is due, the scheduler acts at the generator's next op)
+          rounds += rr_go ? 1u : 0u;
+#ifdef DUO_PROF
+          pf_nrun += rr_rdn ? 1u : 0u; pf_nit++;
+#endif
+        }
+        if (sr_dirty) DUO_FLOOD_WB(sr_dirty);
+      } else
       if (RUNS) {
         for (;;) {
           const u32 rr_k = gen_k - dc_base;
@@ -1712,6 +1813,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #ifdef DUO_PROF
   const u64 pf_tot = __builtin_readcyclecounter() - pf_t0;
   const u32 pf_nrun_all = rdlane(pf_nrun, 0) + rdlane(pf_nrun, 32);
+  const u32 pf_nrunb_all = rdlane(pf_nrunb, 0) + rdlane(pf_nrunb, 32);
 #endif
 
   // ---- epilogue: the partial row block, net stats, meta ----
@@ -1773,6 +1875,12 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     m.reserved[1] = min(pf_nrep, 65535u) | (min(pf_nbout, 255u) << 16) | (min(pf_nrec, 255u) << 24);
     if (hi) m.reserved[2] = pf_ndrop;   // (the upper instance, instead of the flood op rounds' and parked rounds' cycles: the recordings the wavefront dropped)
 #endif
+#ifdef DUO_PROF_RUN
+    // with -DDUO_PROF_RUN as well, the lower instance's reserved[2] carries, instead of all cycles, the parks and the longest wait: the iterations
+    // of the runs' loop (16 bits, saturating) | the broadcasts of both clusters taken in runs << 16 (tools/duo_prof_report.py with MEMO=1 RUN=1)
+    if (!hi) m.reserved[2] = min(pf_nit, 65535u) | (min(pf_nrunb_all, 65535u) << 16);
+#endif
+    (void)pf_nrunb_all; (void)pf_nit;
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }

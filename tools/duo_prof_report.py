@@ -22,7 +22,12 @@ spills, v_readlane / v_writelane inside the loops: profiles/r31_round_split_afte
 MEMO=1: the library is a -DDUO_PROF -DDUO_PROF_MEMO build (tools/variant_lib.sh profmemo duo.hip -DDUO_PROF -DDUO_PROF_MEMO), in which BOTH instances of a
 wavefront carry, in place of the cycles of the GENERAL bodies, generic op rounds, flood gossip rounds and leaving rounds and of the quiet count:
 the floods their cluster replayed (16 bits), the broadcasts it took outside the quiet body (8 bits, saturating) and the floods the wavefront
-recorded (8 bits); the upper instance's reserved[2] is the number of recordings the wavefront dropped.  Only counts are printed: wave-rounds, op wave-rounds, flood gossip and parked rounds, parks, recorded and replayed floods."""
+recorded (8 bits); the upper instance's reserved[2] is the number of recordings the wavefront dropped.  Only counts are printed: wave-rounds, op wave-rounds, flood gossip and parked rounds, parks, recorded and replayed floods.
+MEMO=1 RUN=1: the library is a -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN build (tools/variant_lib.sh profrun duo.hip -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN), whose lower
+instance carries in reserved[2], in place of all cycles, the parks and the longest wait: the iterations of the runs' loop (16 bits) and the broadcasts of both
+clusters taken in runs (16 bits), the steady run of csrc/duo.hip; those two figures are printed, the parks and the cycles are left out.
+(Every -DDUO_PROF build WITHOUT -DDUO_PROF_RUN leaves the steady run out, see DUO_SRUN_ON in csrc/duo.hip: its figures split the op wave-rounds of the kernel
+without the run by the body that took them; the counts of the kernel as it ships are those of the RUN=1 build.)"""
 import os
 import sys
 
@@ -56,6 +61,11 @@ nrun = (nwave.astype(np.int64) >> 16).astype(np.float64)
 nwave = (nwave.astype(np.int64) & 0xFFFF).astype(np.float64)
 npk = (up[:, 0] >> 16).astype(np.float64)
 up[:, 0] &= 0xFFFF
+run = os.environ.get("RUN", "0") != "0"
+nit, nrunb = (ctot.astype(np.int64) & 0xFFFF).astype(np.float64), (ctot.astype(np.int64) >> 16).astype(np.float64)   # (RUN=1: what reserved[2] of the lower instance holds)
+if run:
+    assert max(nit.max(), nrunb.max()) < 65535, "this shape overflows the 16-bit fields of the DUO_PROF_RUN build"
+    ctot = ctot * 0
 npark, wmax = ((ctot.astype(np.int64) >> 16) & 0x7FF).astype(np.float64), int((ctot.astype(np.int64) >> 27).max())
 assert npark.max() < 2047, "this shape parks too often for the 11-bit field of the DUO_PROF build"
 ctot = (ctot.astype(np.int64) & 0xFFFF).astype(np.float64)
@@ -90,7 +100,11 @@ if os.environ.get("MEMO", "0") != "0":
           f"flood gossip rounds {nfg.mean():.0f}, parked gossip rounds {npk.mean():.0f}, parks {npark.mean():.0f} (longest wait {wmax}), reads executed ahead in read runs {nrun.mean():.0f}")
     print(f"flood memo, per wavefront (two clusters): floods recorded {nrec.mean():.1f} (max {nrec.max():.0f}), recordings dropped {ndrop.mean():.2f} (max {ndrop.max():.0f}), floods replayed {nrep.mean():.0f} (min {nrep.min():.0f}), "
           f"broadcasts taken outside the quiet body {nout.mean():.1f}" + (f" (the field is saturated in {out_sat} instances)" if out_sat else ""))
-    print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}): this build's, SGPR spills and all")
+    if run:
+        print(f"steady run, per wavefront (two clusters): iterations of the runs' loop {nit.mean():.0f}, broadcasts taken in runs {nrunb.mean():.0f} (counted among the floods replayed), "
+              f"reads taken in runs {nrun.mean():.0f}; {(nrunb.mean() + nrun.mean()) / max(nit.mean(), 1):.2f} ops per iteration (the parks and the cycles are not carried by this build)")
+    else:
+        print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}): this build's, SGPR spills and all")
     sys.exit(0)
 stretch = os.environ.get("STRETCH", "0") != "0"
 if stretch:
