@@ -306,12 +306,15 @@ int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances,
  * Results via msim_check_results. */
 int msim_check(msim_ctx *ctx);
 
-/* The two transactional workloads only (else MSIM_E_UNSUPPORTED).  txn-rw-register: on != 0 makes the next msim_check give, for EVERY
+/* The two transactional workloads and kafka only (else MSIM_E_UNSUPPORTED).  txn-rw-register: on != 0 makes the next msim_check give, for EVERY
  * history, the full record of msim_check_rw_rows — the histories the consistency model accepts name their allowed cycle classes and carry
  * the full graph's edge and cycle counts (an anomaly census of an ensemble).  Off (the default), a history the first pass proves valid
  * keeps that pass's record.  txn-list-append: on != 0 makes msim_check analyse what the clean passes cannot prove clean on the device
  * too (txn_classify_kernel, as msim_classify_txn_batch), judged by the context's consistency model; the records are the same either way,
- * msim_check_host_rechecks then counts only what reached the host.  Off (the default), the host analyses those histories. */
+ * msim_check_host_rechecks then counts only what reached the host.  Off (the default), the host analyses those histories.  kafka:
+ * on != 0 makes msim_check name the anomalies of a history the clean pass cannot prove clean on the device too (kafka_classify_kernel,
+ * as msim_classify_kafka_batch); the records are the same either way, msim_check_host_rechecks then counts only that entry's
+ * hand-overs.  Off (the default), the host checker classifies those histories. */
 int msim_set_check_classify(msim_ctx *ctx, uint32_t on);
 
 /* Developer switches of a context (A/B comparisons, tracing; never needed for normal use) — the same bits the environment variable
@@ -322,7 +325,8 @@ int msim_set_dev_flags(msim_ctx *ctx, uint32_t flags);
 /* How many histories of the last msim_check the device handed to the host (lin-kv: the search needed more than 512
  * configurations; txn-list-append: not provably clean, i.e. the host analysed and classified it — after msim_set_check_classify only
  * what is beyond the device capacities, see msim_classify_txn_batch; txn-rw-register: beyond the device
- * capacities, see msim_check_rw_batch; else 0). */
+ * capacities, see msim_check_rw_batch; kafka: not provably clean, i.e. the host checker classified it — after msim_set_check_classify
+ * only the hand-overs of msim_classify_kafka_batch; else 0). */
 uint32_t msim_check_host_rechecks(const msim_ctx *ctx);
 
 /* txn-list-append: checks `n_histories` histories given on the host — rows / payload words of history i at row_offsets[i] /
@@ -383,6 +387,22 @@ int msim_check_kafka_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *
  * msim_check_kafka_rows gives for history i. */
 int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                            uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host);
+
+/* kafka: as msim_check_kafka_batch (the same arguments, the same MSIM_E_INVALID / MSIM_E_RANGE cases), but a history the clean pass cannot
+ * prove clean is classified on the device (csrc/kafka_check_dev.hip, kafka_classify_kernel: one workgroup per history, all passes run,
+ * nothing stops at the first anomaly).  out[i] is field for field what msim_check_kafka_rows writes for history i — valid, error_count
+ * with EVERY MSIM_KAFKA_* bit present, lost_count, never_read_count, duplicated_count, attempt_count, stable_count, the four op counts —
+ * including where that record depends on the order of the rows: an offset seen with several messages keeps the LAST observation's
+ * message (the aborted-read test reads it), a message seen at several offsets has its home at the FIRST observation's offset
+ * (duplicated_count counts the distinct other offsets).  Observation order = row index, inside one :ok poll payload order.
+ * An anomaly is never a reason to hand a history to the host checker; only these are, counted in *n_host (may be null):
+ *   - a row or poll block that does not decode, an :ok send of a key >= 8, an offset or message >= 2048 (the host's MALFORMED);
+ *   - a process that returns after a later process of its worker (process mod concurrency): not one stream per worker;
+ *   - tables beyond LDS: an :ok send or a polled pair that names an offset or message >= 1152 (64-bit table cells, 128 bytes per
+ *     offset, in a CU's 160 KB).
+ * concurrency 0 or more than 64 is MSIM_E_INVALID, as there. */
+int msim_classify_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                              uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host);
 
 /* unique-ids: checks `n_histories` histories given on the host — history i in the slab rows + i * max_rows, n_rows[i] rows used —
  * with the device checker of msim_check ([upstream] jepsen.checker/unique-ids); out[i] is what msim_check_unique_rows gives. */

@@ -55,7 +55,7 @@ struct msim_ctx {
   uint32_t dev_flags = 0;           // msim_set_dev_flags: ORed with the MSIM_DEV_FLAGS of the environment (developer switches)
   uint32_t txn_big = 0;             // txn_check_dev.hip: histories of the last check whose tables did not fit LDS (HBM-table kernel)
   uint32_t lin_host_rechecks = 0;   // lin_check_dev.hip: histories of the last check the host search had to finish
-  bool check_classify = false;      // msim_set_check_classify: txn-rw-register records name the allowed cycle classes too; txn-list-append's unclean histories are analysed on the device
+  bool check_classify = false;      // msim_set_check_classify: txn-rw-register records name the allowed cycle classes too; txn-list-append's and kafka's unclean histories are analysed on the device
   std::string err;
 };
 

@@ -6,7 +6,8 @@
 // (the op counts, sends attempted / acknowledged, the unobserved writes — "there is no recency requirement", :25-28 —, :valid?);
 // anything else — an observation that disagrees with another one, a lost write, an aborted read, a process whose offsets do not
 // strictly increase or jump over a known offset, a row that does not decode, an offset or message beyond the tables — is answered
-// NEEDS_HOST and the host checker classifies it (kafka_dev_run below): never approximated.
+// NEEDS_HOST and the host checker classifies it (kafka_dev_run below): never approximated.  A caller whose histories are not clean
+// (msim_classify_kafka_batch, msim_set_check_classify) has them classified by kafka_classify_kernel instead, see there.
 //
 // Layout.  The tables of kafka_check.cpp (the key's log as observed, where each message was seen, polled / acknowledged / failed
 // flags) live in LDS, `T` entries per key (the configuration bounds offsets and messages by max-writes-per-key; a first pass over
@@ -229,6 +230,222 @@ __global__ void __launch_bounds__(NT) kafka_check_kernel(const KCParams p) {
 #undef GETBIT
 }
 
+// ---- the classification of unclean histories (msim_classify_kafka_batch, msim_set_check_classify) -------------------------------------
+// kafka_check_kernel leaves at the first anomaly; a caller whose node is buggy then pays a PCIe copy and a host check per history.
+// kafka_classify_kernel takes the histories that kernel answered NEEDS_HOST (`list`, compacted on the device) and writes the record
+// check_kafka (kafka_check.cpp) writes, field for field: every MSIM_KAFKA_* bit, the lost / unobserved / duplicate counts.  An anomaly
+// is never a reason to leave.  The host's record depends on the order of the observations in two places (observe() there): msg[k][o]
+// keeps the LAST observation's message (only the aborted-read test reads the value), where[k][m] keeps the FIRST observation's offset
+// and every later observation of m elsewhere marks ITS offset a duplicate.  So the table cells are ordered keys of 64 bits,
+//   row index (31 bits) | ordinal of the observation inside its row (17 bits: a poll's len is 16 bits of words, two pairs a word) | value (11),
+// written with an atomic max (msg, bit 63 = seen) and an atomic min (where): the order of the threads does not matter.
+//   pass 1   every observation: the two ordered cells, the polled / acknowledged / failed bits, the key's highest polled offset;
+//   pass 1'  the same observations again: m differs from the last message at (k, o) -> inconsistent-offsets (two different messages
+//            at a cell: at least one differs from the last); o differs from m's first home -> a bit of dup_at (its popcount =
+//            duplicated_count, duplicate iff non-zero);
+//   pass 1b  acknowledged and never polled: lost below the key's highest polled offset, else unobserved; polled and the last message's
+//            send failed: aborted-read;
+//   pass 2   kafka_check_kernel's walk of the worker streams, setting bits: nonmonotonic-send, (int-)nonmonotonic-poll, (int-)poll-skip
+//            (int-: the key already had a block in this poll).
+// Handed to the host checker (NEEDS_HOST, counted in n_host), and nothing else is:
+//   * a row or poll block that does not decode, an :ok send of a key >= 8, an offset or message >= OFFS: the host's MALFORMED;
+//   * a process that returns after a later process of its worker: not one stream per worker;
+//   * an observation that names an offset or message >= TC_MAX = 1152: the cells take 128 bytes per offset, (132 T + 8544) bytes in all,
+//     and a CU has 160 KB of LDS (T = 288 at the bench shape: 46 KB).
+constexpr u32 TC_MAX = 1152u;
+constexpr u64 SEEN = 1ull << 63;
+
+size_t kafka_classify_lds_bytes(u32 T) { return (size_t)KEYS * T * 16 + (4 * (size_t)KEYS * T / 32 + KEYS + 16 + CMAX * WST + NWV * STAGE) * 4; }
+
+// the histories the clean pass could not prove clean: list[0] = how many, list[1 ..] = which (in no particular order)
+__global__ void __launch_bounds__(256) kafka_todo_kernel(const msim_check_result *out, u32 n, u32 *list) {
+  const u32 i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n && out[i].valid == NEEDS_HOST) list[1u + atomicAdd(&list[0], 1u)] = i;
+}
+
+__global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, const u32 *list) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const u32 hist = list[blockIdx.x], T = p.T, KT = KEYS * T, C = p.C;
+  unsigned long long *const msg = reinterpret_cast<unsigned long long *>(smem);   // [KEYS][T] SEEN | order | the message: the max is the last observation (0: offset never seen)
+  unsigned long long *const where = msg + KT;              // [KEYS][T] by message: order | the offset: the min is the first observation (~0: never seen)
+  u32 *const polled = reinterpret_cast<u32 *>(where + KT); // [KEYS * T / 32] bits
+  u32 *const acked = polled + KT / 32;
+  u32 *const failed = acked + KT / 32;                    // by message: its send definitely failed
+  u32 *const dup_at = failed + KT / 32;                   // by offset: some message seen here has its first home elsewhere
+  u32 *const top1 = dup_at + KT / 32;                     // [KEYS] 1 + the highest polled offset
+  u32 *const hdr = top1 + KEYS;                           // [16]: [0] the host's, [1..7] as kafka_check_kernel, [8] lost, [9] duplicates, [10] MSIM_KAFKA_* bits
+  u32 *const wst = hdr + 16;                              // [CMAX][WST]
+  u32 *const stg = wst + CMAX * WST + wave * STAGE;       // this wavefront's staging area
+
+  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
+  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
+  const u32 n = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
+  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
+  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
+
+  for (u32 i = tid; i < KT; i += NT) { msg[i] = 0ull; where[i] = ~0ull; }
+  for (u32 i = tid; i < 4 * KT / 32 + KEYS + 16; i += NT) polled[i] = 0;
+  for (u32 i = tid; i < CMAX * WST; i += NT) wst[i] = EMPTY;
+  __syncthreads();
+
+#define TO_HOST() do { hdr[0] = 1u; } while (0)
+#define SETBIT(a_, i_) atomicOr(&(a_)[(i_) >> 5], 1u << ((i_) & 31u))
+#define GETBIT(a_, i_) (((a_)[(i_) >> 5] >> ((i_) & 31u)) & 1u)
+  u32 bits = 0;
+  // `ord`: row index << 17 | ordinal inside the row.  sweep 0 records the observation, sweep 1 compares it with what all of them left
+  auto observe = [&](u32 sweep, u32 k, u32 o, u32 m, u64 ord) __attribute__((always_inline)) {
+    if (o >= T || m >= T) { TO_HOST(); return; }
+    if (sweep == 0) {
+      atomicMax(&msg[k * T + o], (unsigned long long)(SEEN | (ord << 11) | m));
+      atomicMin(&where[k * T + m], (unsigned long long)((ord << 11) | o));
+    } else {
+      if ((u32)(msg[k * T + o] & 0x7FFull) != m) bits |= MSIM_KAFKA_INCONSISTENT_OFFSETS;
+      if ((u32)(where[k * T + m] & 0x7FFull) != o) SETBIT(dup_at, k * T + o);
+    }
+  };
+
+  msim_check_result res;
+  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
+  res.duplicated_count = 0; res.error_count = 0;
+  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
+  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+
+  // ---- pass 1 (sweep 0) and pass 1' (sweep 1): every observation, in any order of the threads ----
+  for (u32 sweep = 0; sweep < 2; sweep++) {
+    u32 c_inv = 0, c_ok = 0, c_fail = 0, c_info = 0, c_att = 0, c_stable = 0;
+    for (u32 idx = tid; idx < n; idx += NT) {
+      const uint4 row = r[idx];
+      const u32 type = row.z & 3u, f = (row.z >> 2) & 31u, proc = row.z >> 12;
+      if (proc == MSIM_PROCESS_NEMESIS) continue;
+      c_inv += type == MSIM_T_INVOKE; c_ok += type == MSIM_T_OK; c_fail += type == MSIM_T_FAIL; c_info += type == MSIM_T_INFO;
+      if (f == MSIM_F_SEND) {
+        const u32 k = row.w & 63u, m = (row.w >> 6) & 0x7FFu, o = row.w >> 17;
+        if (type == MSIM_T_INVOKE) c_att++;
+        else if (type == MSIM_T_OK) {
+          if (o == 0x7FFu || k >= KEYS) { TO_HOST(); continue; }
+          c_stable++;
+          observe(sweep, k, o, m, (u64)idx << 17);
+          if (sweep == 0 && o < T) SETBIT(acked, k * T + o);
+        } else if (type == MSIM_T_FAIL && sweep == 0) {
+          if (k < KEYS && m < T) SETBIT(failed, k * T + m);   // (a message beyond the tables is never the last one of a cell: such an observation is the host's)
+        }
+      } else if (f == MSIM_F_POLL && type == MSIM_T_OK) {
+        const u32 len = row.y >> 16;
+        if (len == 0) continue;
+        if ((u64)row.w + len > n_words) { TO_HOST(); continue; }
+        const u32 *const w = pay + row.w;
+        u64 ord = (u64)idx << 17;
+        for (u32 q = 0; q < len;) {
+          const u32 h = w[q++], k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
+          if (q + (cnt + 1) / 2 > len) { TO_HOST(); break; }
+          for (u32 e = 0; e < cnt; e++, ord++) {
+            const u32 m = (w[q + e / 2] >> (16 * (e & 1))) & 0xFFFFu;
+            observe(sweep, k, o0 + e, m, ord);
+            if (sweep == 0 && o0 + e < T) { SETBIT(polled, k * T + o0 + e); atomicMax(&top1[k], o0 + e + 1u); }
+          }
+          q += (cnt + 1) / 2;
+        }
+      }
+    }
+    if (sweep == 0) {
+      atomicAdd(&hdr[1], c_inv); atomicAdd(&hdr[2], c_ok); atomicAdd(&hdr[3], c_fail); atomicAdd(&hdr[4], c_info);
+      atomicAdd(&hdr[5], c_att); atomicAdd(&hdr[6], c_stable);
+    }
+    __syncthreads();
+    // does not decode, or beyond the tables: the host's (pass 2 reads only payload that decodes).  Asked after sweep 0 only: sweep 1 finds
+    // nothing sweep 0 did not, and behind its barrier pass 2 of a faster wavefront may already be writing hdr[0]
+    if (sweep == 0 && hdr[0]) { if (tid == 0) p.out[hist] = res; return; }
+  }
+
+  // ---- pass 1b: lost / unobserved writes, aborted reads, the duplicates' offsets ----
+  {
+    u32 unobs = 0, lost = 0, dups = 0;
+    for (u32 i = tid; i < KT; i += NT) {
+      const u32 k = i / T, o = i - k * T;
+      const bool pl = GETBIT(polled, i) != 0;
+      if (GETBIT(acked, i) && !pl) { if (o + 1u < top1[k]) lost++; else unobs++; }
+      if (pl) { const unsigned long long c = msg[i]; if (c != 0ull && GETBIT(failed, k * T + (u32)(c & 0x7FFull))) bits |= MSIM_KAFKA_ABORTED_READ; }
+    }
+    for (u32 i = tid; i < KT / 32; i += NT) dups += (u32)__popc(dup_at[i]);
+    if (lost) { bits |= MSIM_KAFKA_LOST_WRITE; atomicAdd(&hdr[8], lost); }
+    if (dups) { bits |= MSIM_KAFKA_DUPLICATE; atomicAdd(&hdr[9], dups); }
+    atomicAdd(&hdr[7], unobs);
+  }
+
+  // ---- pass 2: every process's own sequence of offsets per key (kafka_check_kernel's walk; lane k holds key k) ----
+  for (u32 base = 0; base < n; base += 64) {
+    const u32 idx = base + lane;
+    uint4 row = make_uint4(0, 0, 0, 0);
+    if (idx < n) row = r[idx];
+    const u32 proc_l = row.z >> 12, type_l = row.z & 3u, f_l = (row.z >> 2) & 31u;
+    const bool rel = idx < n && proc_l != MSIM_PROCESS_NEMESIS && (proc_l % C) % NWV == wave &&
+                     ((f_l == MSIM_F_ASSIGN && type_l == MSIM_T_INVOKE) || (f_l == MSIM_F_POLL && (type_l == MSIM_T_FAIL || type_l == MSIM_T_INFO)) ||
+                      (type_l == MSIM_T_OK && (f_l == MSIM_F_SEND || f_l == MSIM_F_POLL)));
+    u64 todo = __ballot(rel);
+    while (todo) {
+      const u32 j = (u32)__builtin_ctzll(todo);
+      todo &= todo - 1;
+      const u32 rz = k_rl(row.z, j), rw = k_rl(row.w, j), ry = k_rl(row.y, j);
+      const u32 type = rz & 3u, f = (rz >> 2) & 31u, proc = rz >> 12;
+      u32 *const s = wst + (proc % C) * WST;
+      const u32 cur = s[16];
+      if (cur != proc) {   // the worker's next process starts with nothing remembered; a process that RETURNS is not a worker's stream
+        if (cur != EMPTY && proc < cur) TO_HOST();
+        k_wave_fence();
+        if (lane < 16) s[lane] = EMPTY; else if (lane == 16) s[16] = proc;
+        k_wave_fence();
+      }
+      // the positions change: nothing is tracked across an assign, nor across a poll that failed or crashed (kafka_check.cpp)
+      if (type != MSIM_T_OK) { if (lane < 8) s[lane] = EMPTY; continue; }
+      if (f == MSIM_F_SEND) {
+        const u32 k = rw & 63u, o = rw >> 17;
+        if (k >= KEYS || o >= OFFS) continue;
+        if (lane == k) { const u32 last = s[8 + k]; if (last != EMPTY && o <= last) bits |= MSIM_KAFKA_NONMONOTONIC_SEND; s[8 + k] = o; }
+        continue;
+      }
+      const u32 len = ry >> 16;
+      if (len == 0) continue;
+      for (u32 q = lane; q < len && q < STAGE; q += 64) stg[q] = pay[rw + q];
+      k_wave_fence();
+      bool internal = false;   // this lane's key already had a block in this poll: what follows is judged as an internal error
+      for (u32 q = 0; q < len;) {
+        const u32 h = q < STAGE ? stg[q] : pay[rw + q];
+        q++;
+        const u32 k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
+        if (q + (cnt + 1) / 2 > len) break;
+        q += (cnt + 1) / 2;
+        if (!cnt) continue;
+        if (lane == k) {
+          const u32 lp = s[k];
+          if (lp != EMPTY) {
+            if (o0 <= lp) bits |= internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL;
+            else for (u32 o = lp + 1; o < o0; o++) if (o < T && msg[k * T + o] != 0ull) { bits |= internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP; break; }
+          }
+          s[k] = o0 + cnt - 1u;
+          internal = true;
+        }
+      }
+      k_wave_fence();   // (the staging area is rewritten by the next poll)
+    }
+  }
+  if (bits) atomicOr(&hdr[10], bits);
+  __syncthreads();
+
+  if (tid == 0) {
+    if (!hdr[0]) {
+      res.op_count = hdr[1]; res.ok_count = hdr[2]; res.fail_count = hdr[3]; res.info_count = hdr[4];
+      res.attempt_count = hdr[5]; res.stable_count = hdr[6]; res.never_read_count = hdr[7];
+      res.lost_count = hdr[8]; res.duplicated_count = hdr[9]; res.error_count = hdr[10];
+      res.valid = (flags || hdr[10]) ? 0u : ((hdr[6] == 0 && hdr[2] == 0) ? 2u : 1u);
+    }
+    p.out[hist] = res;
+  }
+#undef TO_HOST
+#undef SETBIT
+#undef GETBIT
+}
+
 // The highest offset / message value any :ok send or poll of the launch names: sizes the tables (most tests use a fraction of what
 // max-writes-per-key allows, and the LDS a history's tables take decides how many histories a CU works on at once).
 __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *bound) {
@@ -260,12 +477,15 @@ __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *
   if ((tid & 63u) == 0 && hi) atomicMax(bound, hi);
 }
 
-int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host) {
+// classify: what kafka_check_kernel cannot prove clean goes to kafka_classify_kernel first, and only what THAT hands over to the host
+int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
+                  bool classify = false) {
   const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   const auto t0 = std::chrono::steady_clock::now();
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  u32 h_bound = 0;
   {   // tables no larger than the launch's histories need (kp.T: what the configuration / the checker's own bound allows)
-    u32 *d_bound = nullptr, h_bound = 0;
+    u32 *d_bound = nullptr;
     MSIM_HIP_TRY(ctx, msim_dev_malloc(&d_bound, 4));
     hipError_t e = hipMemsetAsync(d_bound, 0, 4, st);
     if (e == hipSuccess) { hipLaunchKernelGGL(kafka_bound_kernel, dim3(n), dim3(NT), 0, st, kp, d_bound); e = hipGetLastError(); }
@@ -280,11 +500,34 @@ int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst
   if (lds > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_check_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kafka_check_kernel, dim3(n), dim3(NT), lds, st, kp);
   MSIM_HIP_TRY(ctx, hipGetLastError());
+  u32 n_unclean = 0;
+  if (classify) {   // the histories not proved clean, listed on the device, each to a workgroup of kafka_classify_kernel
+    u32 *d_list = nullptr;
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&d_list, ((size_t)n + 1) * 4));
+    hipError_t e = hipMemsetAsync(d_list, 0, 4, st);
+    if (e == hipSuccess) { hipLaunchKernelGGL(kafka_todo_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, kp.out, n, d_list); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_unclean, d_list, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && n_unclean) {
+      KCParams cp = kp;   // tables for what the launch names (the configuration's bound does not hold for an unclean history), up to what LDS holds
+      cp.T = std::min(TC_MAX, std::max(32u, (h_bound + 1u + 31u) & ~31u));
+      const size_t clds = kafka_classify_lds_bytes(cp.T);
+      if (clds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_classify_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
+      if (e == hipSuccess) { hipLaunchKernelGGL(kafka_classify_kernel, dim3(n_unclean), dim3(NT), clds, st, cp, d_list + 1); e = hipGetLastError(); }
+      if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the list is freed below)
+    }
+    (void)msim_dev_free(d_list);
+    MSIM_HIP_TRY(ctx, e);
+  }
   MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, kp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   std::vector<u32> todo;
   for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-  if (trace) std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %zu of %u histories for the host\n", lds, ms(), todo.size(), n);
+  if (trace) {
+    if (classify) std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %u of %u histories classified on the device, %zu of those for the host\n",
+                               lds, ms(), n_unclean, n, todo.size());
+    else std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %zu of %u histories for the host\n", lds, ms(), todo.size(), n);
+  }
   if (!todo.empty()) {
     std::vector<uint64_t> ro, po;
     if (kp.row_off) { ro.resize(n + 1); po.resize(n + 1);
@@ -345,7 +588,7 @@ int msim_check_kafka_device(msim_ctx *ctx) {
   kp.T = kafka_table_entries(ctx->cfg.max_writes_per_key + 8u);
   kp.C = ctx->cfg.concurrency;
   u32 redone = 0;
-  int rc = kafka_dev_run(ctx, kp, n, &hm, ctx->h_check, ctx->stream, &redone);
+  int rc = kafka_dev_run(ctx, kp, n, &hm, ctx->h_check, ctx->stream, &redone, ctx->check_classify);
   if (rc != MSIM_OK) return rc;
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
@@ -355,8 +598,8 @@ int msim_check_kafka_device(msim_ctx *ctx) {
 
 // Checks `n_histories` kafka histories given on the host (rows / payload words of history i at row_offsets[i] / payload_offsets[i]) as
 // msim_check does for the histories of a run; `concurrency` = the worker threads of the test (process mod concurrency).
-extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
-                                      uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host) {
+static int kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                       uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host, bool classify) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || concurrency == 0 || concurrency > CMAX) return MSIM_E_INVALID;
   const uint64_t tr = row_offsets[n_histories], tw = payload_offsets[n_histories];
   if (tw != 0 && !payload) return MSIM_E_INVALID;   // (as msim_check_kafka_rows: payload words announced, none given)
@@ -379,8 +622,20 @@ extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uin
     std::memset(&kp, 0, sizeof kp);
     kp.rows = d_rows; kp.payload = d_pay; kp.row_off = d_ro; kp.pay_off = d_po; kp.out = d_out;
     kp.T = OFFS; kp.C = concurrency;
-    rc = kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host);
+    rc = kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify);
   } while (false);
   for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out}) if (q) (void)msim_dev_free(q);
   return rc;
+}
+
+extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                      uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host) {
+  return kafka_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, concurrency, out, n_host, false);
+}
+
+// As msim_check_kafka_batch, but what the clean pass cannot prove clean is classified by kafka_classify_kernel: only that kernel's
+// hand-overs (its header comment) reach the host checker and are counted in *n_host.
+extern "C" int msim_classify_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                         uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host) {
+  return kafka_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, concurrency, out, n_host, true);
 }

@@ -591,8 +591,8 @@ extern "C" int msim_classify_rw_batch(int device, const msim_op *rows, const uin
 
 extern "C" int msim_set_check_classify(msim_ctx *ctx, uint32_t on) {
   if (!ctx) return MSIM_E_INVALID;
-  if (ctx->cfg.workload != MSIM_WL_TXN_RW_REGISTER && ctx->cfg.workload != MSIM_WL_TXN_LIST_APPEND) {
-    ctx->err = "msim_set_check_classify: only txn-rw-register and txn-list-append have a classification"; return MSIM_E_UNSUPPORTED;
+  if (ctx->cfg.workload != MSIM_WL_TXN_RW_REGISTER && ctx->cfg.workload != MSIM_WL_TXN_LIST_APPEND && ctx->cfg.workload != MSIM_WL_KAFKA) {
+    ctx->err = "msim_set_check_classify: only txn-rw-register, txn-list-append and kafka have a classification"; return MSIM_E_UNSUPPORTED;
   }
   ctx->check_classify = on != 0;
   return MSIM_OK;

@@ -144,9 +144,11 @@ class Engine:
         self.n = n_instances
 
     def check(self, classify=False):
-        """msim_check.  classify=True (msim_set_check_classify; the two transactional workloads only).  txn-rw-register: every history's
-        record is the full analysis of check_rw_history, its allowed cycle classes named.  txn-list-append: a history that is not provably
-        clean is analysed and its cycles classified on the device, not on the host cores (the records are the same).  See anomaly_census."""
+        """msim_check.  classify=True (msim_set_check_classify; the two transactional workloads and kafka only).  txn-rw-register: every
+        history's record is the full analysis of check_rw_history, its allowed cycle classes named.  txn-list-append: a history that is not
+        provably clean is analysed and its cycles classified on the device, not on the host cores (the records are the same).  kafka: a
+        history that is not provably clean has its anomalies named on the device, not on the host cores (the records are the same;
+        check_host_rechecks() then counts only classify_kafka_batch's hand-overs).  See anomaly_census, kafka_anomaly_census."""
         if classify or getattr(self, "_classify", False):
             self._chk(self.lib.msim_set_check_classify(self._ctx, 1 if classify else 0), "msim_set_check_classify")
             self._classify = bool(classify)
@@ -857,7 +859,7 @@ def anomaly_census(results):
 
 
 
-def check_kafka_batch(histories, concurrency, device=0):
+def check_kafka_batch(histories, concurrency, device=0, _entry="msim_check_kafka_batch"):
     """kafka: several histories, each (rows, payload), through the device pass behind Engine.check() (csrc/kafka_check_dev.hip) with the
     host checker for what it cannot prove clean (msim_check_kafka_batch); `concurrency` = the worker threads of the test.  Returns
     (CHECK_DT records, how many histories went to the host)."""
@@ -871,11 +873,27 @@ def check_kafka_batch(histories, concurrency, device=0):
         pay = np.zeros(1, dtype=np.uint32)
     out = np.zeros(len(rs), dtype=CHECK_DT)
     n_host = C.c_uint32()
-    rc = A.load().msim_check_kafka_batch(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs), concurrency,
-                                         out.ctypes.data, C.byref(n_host))
+    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs), concurrency,
+                                   out.ctypes.data, C.byref(n_host))
     if rc:
-        raise EngineError(f"msim_check_kafka_batch: {rc}")
+        raise EngineError(f"{_entry}: {rc}")
     return out, n_host.value
+
+
+def classify_kafka_batch(histories, concurrency, device=0):
+    """kafka: as check_kafka_batch, but a history the device cannot prove clean has its anomalies named on the device too
+    (msim_classify_kafka_batch, kafka_classify_kernel): every record is what check_kafka_history's msim_check_kafka_rows writes, all
+    anomaly bits and counts.  Only what does not decode, a process that returns after a later one of its worker, and offsets or messages
+    from 1152 on go to the host checker.  Returns (CHECK_DT records, how many histories went to the host).  See kafka_anomaly_census."""
+    return check_kafka_batch(histories, concurrency, device, _entry="msim_classify_kafka_batch")
+
+
+def kafka_anomaly_census(results):
+    """How many records of a kafka check (CHECK_DT) carry each anomaly of A.KAFKA_ANOMALIES (by name), and how many none ("clean")."""
+    bits = np.asarray(results["error_count"], dtype=np.uint32)
+    census = {name: int(((bits & np.uint32(b)) != 0).sum()) for b, name in A.KAFKA_ANOMALIES.items()}
+    census["clean"] = int((bits == 0).sum())
+    return census
 
 
 def journal_fressian(cfg, events, payload):
