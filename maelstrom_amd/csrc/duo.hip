@@ -76,6 +76,11 @@
 // STEADY RUN.  A remembered broadcast being as cheap as a read, the loop of the read runs takes it as a cluster round too: a half goes from
 // one block of 32 draws to the next inside the loop, and the quiet body, the tail and the head of an op wave-round are paid once per
 // block (see "STEADY RUN" at the read runs of sim_kernel_duo; -DDUO_NO_STEADY_RUN compiles it out).
+// BLOCK PLAN.  What that loop does op after op is closed-form over the block of draws, so in front of it lane k of a half plans draw k:
+// prefix sums give its op's time, value count, rows and payload offset, it tests on them what the loop tests, and the longest prefix of ops
+// that all pass is committed at once (62 rows by 31 lanes, the reads' payload written as the all-ones sets it must hold, under facts about
+// the sets that are checked per half; the loop stays the fallback for whatever the plan declines; see "BLOCK PLAN" in front of the steady
+// run's loop of sim_kernel_duo; -DDUO_NO_BLOCK_PLAN compiles it out).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
@@ -182,7 +187,17 @@ constexpr bool DUO_SRUN_ON = false;
 #else
 constexpr bool DUO_SRUN_ON = true;
 #endif
-constexpr u32 DUO_SRUN_FAR = 8192u;   // more than one run can add to a cluster's rounds: 31 ops of a block x (a record of at most 255 rounds + 1)
+// The block plan of the steady-run instantiation (see "BLOCK PLAN" in front of the steady run's loop in sim_kernel_duo): the ops of a block
+// of draws that the loop would take one after the other are taken at once, lane k planning draw k; -DDUO_NO_BLOCK_PLAN compiles it out for
+// A/B runs (the kernel is then the previous one, instruction for instruction).  The name DUO_PLAN_ON belongs to the read runs' switch above.
+// -DDUO_BLOCK_PLAN_NO_FACTS (developer / tests) treats every half's sets as not uniform: the plan is compiled in and always declines.
+#ifdef DUO_NO_BLOCK_PLAN
+constexpr bool DUO_BPLAN_ON = false;
+#else
+constexpr bool DUO_BPLAN_ON = true;
+#endif
+constexpr u32 DUO_BPLAN_BYTES = 32u * 4u;   // [origin]: what a remembered flood adds to its half's sum of n_arr | its rounds << 16
+constexpr u32 DUO_SRUN_FAR = 8192u;  // more than one run can add to a cluster's rounds: 31 ops of a block x (a record of at most 255 rounds + 1)
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
 // difference of two floods' lengths); one that runs out was paid for nothing and leaves them out of step.  Measured, the longer the
@@ -336,6 +351,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   constexpr bool STEADY = DUO_STEADY_ON && QUIET;                // ... and leave a flood stretch for a park or an op round without R0 and the exit test
   constexpr bool MEMO = DUO_MEMO_ON && STEADY;                   // ... and simulate a flood once per origin, then apply what that simulation did
   constexpr bool SRUN = DUO_SRUN_ON && MEMO && !DUO_MEMO_CHECK;   // ... and take a remembered broadcast as a cluster round of the read runs' loop
+  constexpr bool BPLAN = DUO_BPLAN_ON && SRUN;                   // ... and plan the steady ops of a block of draws across the lanes
   constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
@@ -589,6 +605,31 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // -DDUO_MEMO_VERIFY (emulator and -DDUO_PROF builds): the halves whose flood is simulated although it is remembered, their record and
   // where n_arr and rounds stood; compared when the half next acts (the head of an op round; a GENERAL body that acts on it in mid-flood traps)
   u64 vf_m = 0; u32 vf_e = 0, vf_n0 = 0, vf_r0 = 0, vf_bit = 0;
+  // BLOCK PLAN (see there): mm_full = the remembered origins whose record has the value's bit in every node lane (a subset of mm_known);
+  // bp_vw_lo / bp_vw_hi = how many leading words of the half's sets were SEEN to be all ones in every node lane when they were completed
+  // (SGPRs); DUO_BPLAN_TOT(origin) = the sum of the origin's record over the half's lanes | its rounds << 16 (LDS, behind the memo table).
+  u32 mm_full = 0, bp_vw_lo = 0, bp_vw_hi = 0;
+#define DUO_BPLAN_TOT(org_) (reinterpret_cast<u32 *>(smem + dp.off_memo + DUO_MEMO_BYTES)[(org_) & 31u])
+  // a completed word is SEEN: a quiescent flood half of seen_m_ whose next_value is a multiple of 32 holds in sw the word its last value
+  // has just completed, current in HBM; if that is the next word to count and it is all ones in all N node lanes, it is counted.  Called
+  // wherever a steady half can stand at such a point: in front of the plan, where the loop takes a broadcast that opens a word, and behind
+  // the loop (the round below may open the next word).  Two scalar tests per call unless a half stands at a boundary.
+#ifdef DUO_BLOCK_PLAN_NO_FACTS
+#define DUO_BPLAN_SEEN(seen_m_) do { } while (0)
+#else
+#define DUO_BPLAN_SEEN(seen_m_) do {                                                                                     \
+    if constexpr (BPLAN) {                                                                                                \
+      const u32 bs_v_lo = rdlane(next_value, 0), bs_v_hi = rdlane(next_value, 32);                                        \
+      const bool bs_c_lo = (u32)(seen_m_) != 0 && bs_v_lo != 0 && (bs_v_lo & 31u) == 0 && bp_vw_lo + 1u == (bs_v_lo >> 5); \
+      const bool bs_c_hi = (u32)((seen_m_) >> 32) != 0 && bs_v_hi != 0 && (bs_v_hi & 31u) == 0 && bp_vw_hi + 1u == (bs_v_hi >> 5); \
+      if (bs_c_lo | bs_c_hi) {                                                                                            \
+        const u64 bs_on = DUO_BAL_CMP(sw, ==, 0xFFFFFFFFu, 32);                                                           \
+        if (bs_c_lo && (~(u32)bs_on & all_nodes) == 0) bp_vw_lo++;                                                        \
+        if (bs_c_hi && (~(u32)(bs_on >> 32) & all_nodes) == 0) bp_vw_hi++;                                                \
+      }                                                                                                                   \
+    }                                                                                                                     \
+  } while (0)
+#endif
   // The helpers below are macros on purpose: as lambdas capturing the state by reference they left the closures (and with
   // them every captured variable) in scratch memory once the optimizer turned a select of two captured values into a select
   // of their addresses.
@@ -904,6 +945,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   u32 pf_ndrop = 0;   // recordings dropped (the wavefront's): a half that acted, or met a GENERAL body, before the steady leave had taken its record
   u32 pf_nrec = 0, pf_nrep = 0, pf_nbout = 0;   // floods recorded (the wavefront's), floods replayed and broadcasts taken outside the quiet body (this lane's cluster's)
   u32 pf_nrunb = 0, pf_nit = 0;   // broadcasts of this lane's cluster taken in runs (counted in pf_nrep as well), iterations of the runs' loop (the wavefront's)
+  u32 pf_nplan = 0, pf_nplanop = 0;   // block plans that took at least one op, the ops they took (the wavefront's; counted in pf_nrun / pf_nrunb as well: the loop's own are those less these)
   u64 pf_exit = 0;   // R0 and the exit test of the wave-rounds that leave the gossip loop (their op round or GENERAL body is counted from there on)
 #define PF_MAT_BEGIN const u64 pf_m0 = __builtin_readcyclecounter();
 #define PF_MAT_END pf_mat += __builtin_readcyclecounter() - pf_m0; pf_nmat++;
@@ -1167,10 +1209,26 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
               // FLOOD MEMO: a recording half is dry and steady: its flood is over, what it did becomes the record of its origin
               if (const u64 mm_fin = mm_rec & dry_m) {
                 DUO_LANE_NOW(mf_l);
+                u32 mf_e = 0;
                 if (lane_in(mm_fin)) {
                   const u32 mf_org = (mm_org >> ((mf_l >> 5) << 3)) & 31u;
                   const u32 mf_b = DUO_MEMO_AT(mf_org, mf_l);
-                  DUO_MEMO_AT(mf_org, mf_l) = (unsigned short)(((n_arr - mf_b) & 0x7Fu) | (((sw >> ((next_value - 1u) & 31u)) & 1u) << 7) | (((sl_r1 - 1u - (mf_b >> 8)) & 0xFFu) << 8));
+                  mf_e = ((n_arr - mf_b) & 0x7Fu) | (((sw >> ((next_value - 1u) & 31u)) & 1u) << 7) | (((sl_r1 - 1u - (mf_b >> 8)) & 0xFFu) << 8);
+                  DUO_MEMO_AT(mf_org, mf_l) = (unsigned short)mf_e;
+                }
+                if constexpr (BPLAN) {   // BLOCK PLAN: the record's sum over the half and whether every node lane has the value's bit
+                  const u32 mf_s = scan32(mf_e & 0x7Fu);
+                  const u64 mf_b7 = bal((mf_e & 0x80u) != 0);
+                  if ((u32)mm_fin) {
+                    const u32 mf_t = rdlane(mf_s, 31) | ((rdlane(mf_e, 0) >> 8) << 16);
+                    if (mf_l == 0u) DUO_BPLAN_TOT(mm_org & 31u) = mf_t;
+                    if ((~(u32)mf_b7 & all_nodes) == 0) mm_full |= 1u << (mm_org & 31u);
+                  }
+                  if ((u32)(mm_fin >> 32)) {
+                    const u32 mf_t = rdlane(mf_s, 63) | ((rdlane(mf_e, 32) >> 8) << 16);
+                    if (mf_l == 32u) DUO_BPLAN_TOT((mm_org >> 8) & 31u) = mf_t;
+                    if ((~(u32)(mf_b7 >> 32) & all_nodes) == 0) mm_full |= 1u << ((mm_org >> 8) & 31u);
+                  }
                 }
                 if ((u32)mm_fin) mm_known |= 1u << (mm_org & 31u);
                 if ((u32)(mm_fin >> 32)) mm_known |= 1u << ((mm_org >> 8) & 31u);
@@ -1294,6 +1352,143 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       if constexpr (SRUN) {
         u64 sr_m = 0, sr_dirty = 0;
         if (fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0 && (alive_m & ~DUO_BAL_CMP(rounds + DUO_SRUN_FAR, <, round_limit, 36)) == 0) sr_m = op_m;
+        // BLOCK PLAN.  What the loop below does op after op is closed-form over the block of draws: op k + 1 depends on op k through prefix
+        // sums alone (the time, the values, the rows, the payload, the rounds).  So in front of the loop lane k of a half in sr_m reads draw k
+        // of the block (k0 = gen_k - dc_base <= k < 31), scans give it its op's time, value count, row index and payload offset as they stand
+        // if every op before it is taken, and it tests on them EXACTLY what the loop tests on its op: k < 31, next < cutoff, n_rows + 4 <=
+        // max_rows; for a read the payload's room (rounds < round_limit follows from sr_m's FAR term: a block adds less than DUO_SRUN_FAR);
+        // for a broadcast an origin in mm_full, T < next and next_value + 1 < max_values.  The plan takes the longest prefix [k0, m) of ops
+        // that all pass (a ballot, its trailing ones) and commits it at once; op m and all behind it are the loop's and the round's below,
+        // on the state the loop would have left there, so every stop is found where it always was.
+        // THE SETS.  A planned read does not copy its node's set, it writes what that set must hold: inside a quiet run every node has taken
+        // every value in, so a set is all ones up to a last, partial word.  That is not assumed.  A half plans only while, checked,
+        //   * every completed word of its sets was SEEN to be all ones in all N node lanes: bp_vw_lo / bp_vw_hi count the leading words seen
+        //     so (DUO_BPLAN_SEEN), where an acting flood half stands at next_value a multiple of 32 with the completed word in sw, current in
+        //     HBM: in front of the plan, behind the loop, where the loop opens a word, and where a plan completes one in its middle; a word
+        //     completed anywhere else is counted later, one per op wave-round, from what the lanes themselves wrote back to HBM;
+        //   * sw is the same in all N node lanes (one compare against the half's first lane), so one scalar per half is every node's word;
+        //   * the origin's record has the value's bit in all N node lanes (mm_full, filled where mm_known is).
+        // A half for which one of these fails takes the loop for the block, whose result is the parent's by construction.  With them, a
+        // payload word is all ones unless it is the last word of a read whose value count is no multiple of 32; that word is the half's sw
+        // at entry (if the read's count lies in the entry word) with the bits of the block's broadcasts before the read.  Each word's value
+        // is built before it is stored, one store per word.  A word completed inside the plan is written back, all ones, before sw starts
+        // the next one, and the block's end leaves sw dirty for the loop's own write-backs (sr_dirty), as a broadcast's iteration does.
+        // THE SUMS.  n_cl and n_arr are read by the epilogue alone, as sums over the half (n_arr also by a recording, as a lane's own rise
+        // while its half simulates, which no plan falls into).  So the lane that plans an op counts its pick, and the lane that plans a
+        // broadcast adds the whole half's rise: DUO_BPLAN_TOT(origin), the record's sum over the lanes, kept beside the record (one LDS
+        // read per lane, no loop over broadcasts or origins: of per broadcast, per distinct origin and per origin at the run's end, each of
+        // which walks the block's ~15 broadcasts with a table row read per lane, this costs one read and one add per plan).
+        if constexpr (BPLAN) {
+          DUO_LANE_NOW(bp_l);
+          const u32 bp_i = bp_l & 31u;
+          const bool bp_up = bp_l >= 32u;
+          const u32 bp_v_lo = rdlane(next_value, 0), bp_v_hi = rdlane(next_value, 32);
+          const u32 bp_s_lo = rdlane(sw, 0), bp_s_hi = rdlane(sw, 32);
+          const u32 bp_sh = bp_up ? bp_s_hi : bp_s_lo;   // the half's set word: every node lane's, once checked
+          const u64 bp_un = DUO_BAL_CMP(sw, ==, bp_sh, 32);
+          bool bp_u_lo = (~(u32)bp_un & all_nodes) == 0, bp_u_hi = (~(u32)(bp_un >> 32) & all_nodes) == 0;
+#ifdef DUO_BLOCK_PLAN_NO_FACTS
+          bp_u_lo = false; bp_u_hi = false;
+#endif
+          DUO_BPLAN_SEEN(op_m & fl_m);   // (B) has written their sw back
+#ifndef DUO_BLOCK_PLAN_NO_FACTS
+          // A half whose count lags (a word was completed where nobody looked: a GENERAL body, a generic op round) catches up one word per
+          // op wave-round, from HBM: word bp_vw of an acting flood half lies below the word sw stands for, so its lanes wrote it back
+          // before sw moved on and nothing writes it again; each lane loads its own column's word, the one it stored itself.
+          if (const u64 bp_lag = op_m & fl_m & hm2(bp_vw_lo < (bp_v_lo >> 5), bp_vw_hi < (bp_v_hi >> 5))) {
+            u32 bp_lw = 0xFFFFFFFFu;
+            if (lane_in(bp_lag)) bp_lw = DUO_SET(set_lane + (bp_up ? bp_vw_hi : bp_vw_lo) * 128u);
+            const u64 bp_lon = DUO_BAL_CMP(bp_lw, ==, 0xFFFFFFFFu, 32);
+            if ((u32)bp_lag && (~(u32)bp_lon & all_nodes) == 0) bp_vw_lo++;
+            if ((u32)(bp_lag >> 32) && (~(u32)(bp_lon >> 32) & all_nodes) == 0) bp_vw_hi++;
+          }
+#endif
+          const u64 bp_m = sr_m & hm2(bp_u_lo && bp_vw_lo == (bp_v_lo >> 5), bp_u_hi && bp_vw_hi == (bp_v_hi >> 5));
+          if (bp_m) {
+            const u64 bp_d = DUO_DCL_MINE();
+            const u32 bp_lo = (u32)bp_d, bp_k0 = gen_k - dc_base;
+            const bool bp_val = lane_in(bp_m) && bp_i >= bp_k0 && bp_i < 31u;
+            const u32 bp_dt = bp_val ? __umulhi((u32)(bp_d >> 32), p.gen_period2_us) : 0u;
+            const bool bp_rd = (bp_lo & 1u) != 0;
+            const u32 bp_node = scale32(bp_lo, N);
+            const bool bp_kn = ((mm_full >> bp_node) & 1u) != 0;
+            const u32 bp_b1 = bp_val && !bp_rd ? 1u : 0u;
+            // (inclusive scans inside the half; a lane outside [k0, 31) adds nothing, so its own figures are the sums of those below it)
+            const u32 bp_next = T + scan32(bp_dt);
+            const u32 bp_T = bp_next - bp_dt;
+            const u32 bp_v = next_value + scan32(bp_b1) - bp_b1;
+            const u32 bp_w = (bp_v + 31u) >> 5;
+            const u32 bp_pw = bp_val && bp_rd ? bp_w : 0u;
+            const u32 bp_po = n_payload + scan32(bp_pw) - bp_pw;
+            u32 bp_e = 0;
+            if (bp_b1 != 0 && bp_kn) bp_e = DUO_BPLAN_TOT(bp_node);
+            const u32 bp_es = scan32(bp_e) - bp_e;
+            const u32 bp_row = n_rows + 2u * (bp_i - bp_k0);
+            const bool bp_ok = bp_val && bp_next < cutoff && bp_row + 4u <= max_rows &&
+                               (bp_rd ? bp_po + bp_w <= max_pay : (bp_kn && bp_T < bp_next && bp_v + 1u < max_values));
+            const u64 bp_okb = bal(bp_ok), bp_bcb = bal(bp_b1 != 0);
+            // per half, on the scalar unit: m, the lanes taken, their broadcasts; a word completed in mid-plan must come out all ones
+#define DUO_BP_HALF(h_, l0_, okb_, bcb_)                                                                                  \
+            const u32 bp_k_##h_ = min(rdlane(bp_k0, l0_), 31u);                                                          \
+            u32 bp_m_##h_ = (u32)__builtin_ctz(~((okb_) | ((1u << bp_k_##h_) - 1u)));                                    \
+            u32 bp_nb_##h_ = (u32)__popc((bcb_) & ((1u << bp_m_##h_) - 1u) & ~((1u << bp_k_##h_) - 1u));                 \
+            bool bp_x_##h_ = bp_nb_##h_ != 0 && (bp_v_##h_ & 31u) != 0 && ((bp_v_##h_ + bp_nb_##h_ - 1u) >> 5) != (bp_v_##h_ >> 5); \
+            if (bp_x_##h_ && (bp_s_##h_ | ~((1u << (bp_v_##h_ & 31u)) - 1u)) != 0xFFFFFFFFu) { bp_m_##h_ = bp_k_##h_; bp_nb_##h_ = 0; bp_x_##h_ = false; } \
+            const u32 bp_tk_##h_ = ((1u << bp_m_##h_) - 1u) & ~((1u << bp_k_##h_) - 1u);                                 \
+            const u32 bp_c_##h_ = bp_m_##h_ - bp_k_##h_;                                                                 \
+            const bool bp_o_##h_ = bp_nb_##h_ != 0 && ((bp_v_##h_ & 31u) == 0 || bp_x_##h_);                             \
+            const u32 bp_g_##h_ = bp_nb_##h_ == 0 ? 0u : ((2u << ((bp_v_##h_ + bp_nb_##h_ - 1u) & 31u)) - 1u) & ~(bp_o_##h_ ? 0u : (1u << (bp_v_##h_ & 31u)) - 1u);
+            DUO_BP_HALF(lo, 0, (u32)bp_okb, (u32)bp_bcb)
+            DUO_BP_HALF(hi, 32, (u32)(bp_okb >> 32), (u32)(bp_bcb >> 32))
+#undef DUO_BP_HALF
+            const u64 bp_tk = (u64)bp_tk_lo | ((u64)bp_tk_hi << 32);
+            if (bp_tk) {
+              const bool bp_t = lane_in(bp_tk);
+              if (bp_t) {   // the op's two rows, from the lane that planned it
+                const u64 tns = (u64)bp_T * 1000ull;
+                const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
+                const u32 fk = bp_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
+                DUO_ROW(bp_row) = make_uint4(tlo, thi, MSIM_T_INVOKE | (fk << 2) | (bp_node << 12), bp_rd ? MSIM_NO_VALUE : bp_v);
+                DUO_ROW(bp_row + 1u) = make_uint4(tlo, thi | (bp_rd ? bp_w << 16 : 0u), MSIM_T_OK | (fk << 2) | (bp_node << 12), bp_rd ? bp_po : bp_v);
+              }
+              n_cl += bp_t ? 1u : 0u;
+              n_arr += bp_t ? bp_e & 0xFFFFu : 0u;
+              // a word completed in mid-plan: all ones in every node lane (tested above on the half's word), written back before sw is reset
+              if (bp_x_lo | bp_x_hi) {
+                if (lane_in(hm2(bp_x_lo, bp_x_hi))) DUO_SET(set_lane + ((next_value & 0xFFE0u) << 2)) = sw | ~((1u << (next_value & 31u)) - 1u);
+                bp_vw_lo += bp_x_lo ? 1u : 0u; bp_vw_hi += bp_x_hi ? 1u : 0u;
+              }
+              // the last word of a read's payload, where its value count is no multiple of 32
+              const u32 bp_same = (bp_v >> 5) == (next_value >> 5) && (next_value & 31u) != 0 ? 0xFFFFFFFFu : 0u;
+              const u32 bp_pv = (bp_sh & bp_same) | (((1u << (bp_v & 31u)) - 1u) & ~(((1u << (next_value & 31u)) - 1u) & bp_same));
+              // the state behind op m - 1: lane m's own figures
+              const u32 bp_ma = (bp_up ? 32u + bp_m_hi : bp_m_lo) << 2, bp_c = bp_up ? bp_c_hi : bp_c_lo;
+              sw = lane_in(hm2(bp_o_lo, bp_o_hi)) ? 0u : sw;
+              sw |= bp_up ? bp_g_hi : bp_g_lo;
+              sr_dirty |= hm2(bp_nb_lo != 0, bp_nb_hi != 0);
+              T = bperm(bp_ma, bp_T);
+              next_value = bperm(bp_ma, bp_v);
+              n_payload = bperm(bp_ma, bp_po);
+              rounds += bp_c + (bperm(bp_ma, bp_es) >> 16);
+              n_rows += 2u * bp_c;
+              gen_k += bp_c;
+              // the payload: the reads of both halves side by side, every word by the lane of its position
+              for (u32 bp_r_lo = bp_tk_lo & ~(u32)bp_bcb, bp_r_hi = bp_tk_hi & ~(u32)(bp_bcb >> 32); (bp_r_lo | bp_r_hi) != 0; bp_r_lo &= bp_r_lo - 1u, bp_r_hi &= bp_r_hi - 1u) {
+                const u32 bp_ra = (bp_up ? 32u + (u32)__builtin_ctz(bp_r_hi | 0x80000000u) : (u32)__builtin_ctz(bp_r_lo | 0x80000000u)) << 2;
+                const u32 bp_xo = bperm(bp_ra, bp_po), bp_xv = bperm(bp_ra, bp_v), bp_xp = bperm(bp_ra, bp_pv);
+                const bool bp_xn = lane_in(hm2(bp_r_lo != 0, bp_r_hi != 0));
+                const u32 bp_xw = bp_xn ? (bp_xv + 31u) >> 5 : 0u;
+                const u32 bp_xl = (bp_xv & 31u) != 0 ? bp_xw - 1u : 0xFFFFFFFFu;
+                for (u32 w = bp_i; bal(w < bp_xw); w += 32)
+                  if (w < bp_xw) DUO_PAY(bp_xo + w) = w == bp_xl ? bp_xp : 0xFFFFFFFFu;
+              }
+#ifdef DUO_PROF
+              pf_nplan += (bp_c_lo ? 1u : 0u) + (bp_c_hi ? 1u : 0u); pf_nplanop += bp_c_lo + bp_c_hi;
+              { const u32 pf_b = bp_up ? bp_nb_hi : bp_nb_lo; pf_nrunb += pf_b; pf_nrep += pf_b; pf_nrun += bp_c - pf_b; }
+#endif
+            }
+          }
+        }
         for (;;) {
           const u32 rr_k = gen_k - dc_base;
           u32 rr_hi, rr_lo; DUO_DRAW(gen_k, rr_hi, rr_lo);
@@ -1312,6 +1507,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           const bool rr_sel = rr_go && i == rr_node;
           n_cl += rr_sel ? 1u : 0u;
           if (const u64 sr_wb = sr_dirty & (rr_b | (sb_b & DUO_BAL_CMP(next_value & 31u, ==, 0u, 32)))) { DUO_FLOOD_WB(sr_wb); sr_dirty &= ~sr_wb; }
+          if constexpr (BPLAN) { if (const u64 sr_open = sb_b & DUO_BAL_CMP(next_value & 31u, ==, 0u, 32)) DUO_BPLAN_SEEN(sr_open); }   // (the word is complete and current in HBM)
           wave_lds_fence();
           for (u32 w = i; rr_b & bal(w < rr_words); w += 32)
             if (rr_rdn && w < rr_words) DUO_PAY(n_payload + w) = DUO_SET(set_half + w * 128u + rr_node * 4u);
@@ -1351,6 +1547,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #endif
         }
         if (sr_dirty) DUO_FLOOD_WB(sr_dirty);
+        DUO_BPLAN_SEEN(op_m & fl_m);   // (a plan or the loop may have ended on a completed word, which the round below may leave behind)
       } else
       if (RUNS) {
         for (;;) {
@@ -1879,8 +2076,14 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     // with -DDUO_PROF_RUN as well, the lower instance's reserved[2] carries, instead of all cycles, the parks and the longest wait: the iterations
     // of the runs' loop (16 bits, saturating) | the broadcasts of both clusters taken in runs << 16 (tools/duo_prof_report.py with MEMO=1 RUN=1)
     if (!hi) m.reserved[2] = min(pf_nit, 65535u) | (min(pf_nrunb_all, 65535u) << 16);
+#ifdef DUO_PROF_PLAN
+    // with -DDUO_PROF_PLAN as well (every word of the -DDUO_PROF_RUN build is taken), the upper instance's reserved[2] carries, instead of the
+    // recordings dropped: the block plans that took an op (16 bits, saturating) | the ops they took << 16 (reads and broadcasts of both
+    // clusters; they are among the runs' reads and broadcasts, so the loop's own ops are those less these) (tools/duo_prof_report.py with PLAN=1)
+    else m.reserved[2] = min(pf_nplan, 65535u) | (min(pf_nplanop, 65535u) << 16);
 #endif
-    (void)pf_nrunb_all; (void)pf_nit;
+#endif
+    (void)pf_nrunb_all; (void)pf_nit; (void)pf_nplan; (void)pf_nplanop;
 #endif
 #if defined(DUO_PROF2) || defined(DUO_PROF3)
     if (!hi) { m.n_events = (u32)(p2[0] >> 6); m.reserved[0] = (u32)(p2[1] >> 6); m.reserved[1] = (u32)(p2[2] >> 6); m.reserved[2] = (u32)(p2[3] >> 6); }
@@ -2000,6 +2203,7 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   if (const char *rl = std::getenv("MSIM_DUO_ROUND_LIMIT")) { const unsigned long v = std::strtoul(rl, nullptr, 0); if (v > 0 && v < ROUND_LIMIT) dp.round_limit = (u32)v; }
   size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
   if (memo) lds += DUO_MEMO_BYTES;
+  if (memo && DUO_BPLAN_ON) lds += DUO_BPLAN_BYTES;   // the block plan's totals per origin, behind the table (4736 bytes per wavefront at the headline shape)
   lds = std::min(lds + (size_t)DUO_LDS_PAD, (size_t)160 * 1024);
   const dim3 grid((n + 1) / 2);
   if (rnd) return deg4 ? duo_launch<false, true, true>(dp, grid, lds, st) : duo_launch<false, false, true>(dp, grid, lds, st);

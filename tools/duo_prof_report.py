@@ -26,6 +26,9 @@ recorded (8 bits); the upper instance's reserved[2] is the number of recordings 
 MEMO=1 RUN=1: the library is a -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN build (tools/variant_lib.sh profrun duo.hip -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN), whose lower
 instance carries in reserved[2], in place of all cycles, the parks and the longest wait: the iterations of the runs' loop (16 bits) and the broadcasts of both
 clusters taken in runs (16 bits), the steady run of csrc/duo.hip; those two figures are printed, the parks and the cycles are left out.
+MEMO=1 RUN=1 PLAN=1: the library is that build with -DDUO_PROF_PLAN as well (tools/variant_lib.sh profplan duo.hip -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN -DDUO_PROF_PLAN),
+whose upper instance carries in reserved[2], in place of the recordings dropped: the block plans that took an op (16 bits) and the ops they took (16 bits), the
+block plan of csrc/duo.hip; printed with the ops the runs' loop still took (the runs' reads and broadcasts less the plans' ops).
 (Every -DDUO_PROF build WITHOUT -DDUO_PROF_RUN leaves the steady run out, see DUO_SRUN_ON in csrc/duo.hip: its figures split the op wave-rounds of the kernel
 without the run by the body that took them; the counts of the kernel as it ships are those of the RUN=1 build.)"""
 import os
@@ -92,6 +95,11 @@ if os.environ.get("MEMO", "0") != "0":
     nout = (((lo1 >> 16) & 0xFF) + ((up[:, 2] >> 16) & 0xFF)).astype(np.float64)
     nrec = (lo1 >> 24).astype(np.float64)
     ndrop = up[:, 3].astype(np.float64)   # reserved[2] of the upper instances: recordings dropped
+    plan = run and os.environ.get("PLAN", "0") != "0"
+    if plan:   # (PLAN=1: that word holds the block plans | the ops they took << 16 instead)
+        nplan, nplanop = (up[:, 3] & 0xFFFF).astype(np.float64), (up[:, 3] >> 16).astype(np.float64)
+        assert max(nplan.max(), nplanop.max()) < 65535, "this shape overflows the 16-bit fields of the DUO_PROF_PLAN build"
+        ndrop = ndrop * 0
     assert ((lo1 >> 24) == (up[:, 2] >> 24)).all(), "the two instances of a wavefront carry the same count of recorded floods"
     out_sat = int((((lo1 >> 16) & 0xFF) == 255).sum() + (((up[:, 2] >> 16) & 0xFF) == 255).sum())
     print(f"latency {kw['latency']} ms {kw['latency_dist']}, {n} instances: sim kernel {sim_ms:.3f} ms (a -DDUO_PROF build: not the product's time)")
@@ -103,6 +111,10 @@ if os.environ.get("MEMO", "0") != "0":
     if run:
         print(f"steady run, per wavefront (two clusters): iterations of the runs' loop {nit.mean():.0f}, broadcasts taken in runs {nrunb.mean():.0f} (counted among the floods replayed), "
               f"reads taken in runs {nrun.mean():.0f}; {(nrunb.mean() + nrun.mean()) / max(nit.mean(), 1):.2f} ops per iteration (the parks and the cycles are not carried by this build)")
+        if plan:
+            left = nrunb + nrun - nplanop
+            print(f"block plan, per wavefront (two clusters): plans that took an op {nplan.mean():.0f}, the ops they took {nplanop.mean():.0f} ({nplanop.mean() / max(nplan.mean(), 1):.1f} per plan; min {nplanop.min():.0f}), "
+                  f"ops the runs' loop still took {left.mean():.0f} (max {left.max():.0f}) (the recordings dropped are not carried by this build)")
     else:
         print(f"cycles per wavefront {ctot.mean():.3e} (max {ctot.max():.3e}): this build's, SGPR spills and all")
     sys.exit(0)
