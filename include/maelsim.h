@@ -417,6 +417,43 @@ int msim_check_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row
  * 2 unknown; attempt_count = keys, error_count = non-linearizable keys.  Needs no device. */
 int msim_check_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim_check_result *out);
 
+/* lin-kv, explained: what `independent/checker` + Knossos' `checker/linearizable` report per key beside the verdict — for a key that is
+ * not linearizable :op, :previous-ok and the :model values of the :configs just before that op, for a linearizable one the values of the
+ * :configs the search ends with (doc/06-raft/01-key-value.md:144-158).  One record per key of a history, ascending by key.  Every field is
+ * defined independently of how a search prunes, so the host search, the device search and an unpruned search give the same bytes:
+ *   op_row           the row of the first :ok completion of the key whose return leaves no configuration (valid == 0; else MSIM_NO_VALUE);
+ *   previous_ok_row  the largest row below op_row that is an :ok completion of the key paired with an invocation (MSIM_NO_VALUE: none);
+ *   "that moment"    valid == 0: just before the closure for op_row — the configurations are the survivors of the return at
+ *                    previous_ok_row (the initial {nil} if there is none); valid == 1: the end of the key;
+ *   n_pending        calls of the key invoked and not completed at that moment: writes and cas that never return included, calls
+ *                    completed by :fail, reads without an :ok and (valid == 0) the returning call itself not;
+ *   n_values, values the distinct register values over the configurations at that moment, the first 8 ascending (nil = 0xFF last).
+ * valid == 2 (unknown: more than 64 calls of the key open at once, as msim_check_lin_kv_rows): both rows MSIM_NO_VALUE, the rest 0.
+ * Not reported: :final-paths and :last-op (the search keeps no paths) and the number of configurations (it depends on the pruning). */
+typedef struct msim_lin_key_result {   /* 32 bytes */
+  uint32_t key;              /* 0..255 */
+  uint32_t valid;            /* 1 linearizable, 0 not, 2 unknown */
+  uint32_t op_row;
+  uint32_t previous_ok_row;
+  uint32_t n_pending;
+  uint32_t n_values;
+  uint8_t  values[8];        /* unused = 0 */
+} msim_lin_key_result;
+
+/* Host-only: msim_check_lin_kv_rows (the same *out) and the key records of the history: keys[0 .. min(*n_keys, max_keys)), *n_keys = the
+ * keys the history has; 1 <= max_keys <= 256.  Needs no device. */
+int msim_explain_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim_check_result *out, msim_lin_key_result *keys, uint32_t max_keys,
+                             uint32_t *n_keys);
+/* As msim_check_lin_kv_batch (the same histories, the same out[i]) with the key records written by the device search at every level it
+ * has (csrc/lin_check_dev.hip; a history the host search finishes has its records from there): history i's records in
+ * keys[i * max_keys ..], n_keys[i] of them (only the first max_keys are written; the slab's records beyond them are zero);
+ * *n_host (may be null) = how many histories went to the host search.  1 <= max_keys <= 256. */
+int msim_explain_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out,
+                              msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t *n_host);
+/* The same over the histories of the last run where they lie in HBM (MSIM_WL_LIN_KV only, else MSIM_E_UNSUPPORTED): keys / n_keys hold
+ * `n_out` histories (at least the run's, else MSIM_E_RANGE).  Leaves msim_check_results as msim_check would. */
+int msim_explain_lin_kv(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t n_out);
+
 /* Host-only utility behind msim_check for txn-list-append: the list-append analysis of [upstream] elle
  * (jepsen.tests.cycle.append, txn_list_append.clj:142) for the default --consistency-models strict-serializable
  * (core.clj:160-165): per-key version orders from the longest reads, ww/wr/rw + realtime dependency graph, cycle search,

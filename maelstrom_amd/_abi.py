@@ -47,6 +47,7 @@ EXPORTS = [
     "msim_comm_unique_id", "msim_comm_init", "msim_gather", "msim_journal_fressian_rows",
     "msim_check_availability", "msim_check_availability_rows",
     "msim_check_perf", "msim_check_perf_rows", "msim_check_perf_batch",
+    "msim_explain_lin_kv_rows", "msim_explain_lin_kv_batch", "msim_explain_lin_kv",
 ]
 AVAIL_NIL, AVAIL_TOTAL, AVAIL_FRACTION = range(3)
 PERF_MAX_F, PERF_MAX_WINDOWS = 4, 16
@@ -119,6 +120,11 @@ class PerfResult(C.Structure):
                 ("info_count", C.c_uint32), ("open_count", C.c_uint32), ("flags", C.c_uint32), ("by_f", FStats * PERF_MAX_F)]
 
 
+class LinKeyResult(C.Structure):
+    _fields_ = [("key", C.c_uint32), ("valid", C.c_uint32), ("op_row", C.c_uint32), ("previous_ok_row", C.c_uint32),
+                ("n_pending", C.c_uint32), ("n_values", C.c_uint32), ("values", C.c_uint8 * 8)]
+
+
 class Gathered(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("payload", C.c_void_p), ("meta", C.c_void_p), ("stats", C.c_void_p),
                 ("rows_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("meta_bytes", C.c_uint64), ("stats_bytes", C.c_uint64),
@@ -127,6 +133,7 @@ class Gathered(C.Structure):
 
 assert C.sizeof(Config) == 120, C.sizeof(Config)
 assert C.sizeof(LatencyDist) == 32 and C.sizeof(FStats) == 128 and C.sizeof(PerfResult) == 544
+assert C.sizeof(LinKeyResult) == 32
 assert C.sizeof(Op) == 16 and C.sizeof(NetStats) == 48 and C.sizeof(InstMeta) == 32 and C.sizeof(CheckResult) == 68 and C.sizeof(Event) == 16
 
 _lib = None
@@ -161,6 +168,10 @@ def load():
     lib.msim_check_host_rechecks.restype = C.c_uint32
     lib.msim_check_lin_kv_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.msim_check_lin_kv_batch.restype = C.c_int
+    lib.msim_explain_lin_kv_rows.argtypes = [C.c_void_p, C.c_uint32, P(CheckResult), C.c_void_p, C.c_uint32, P(C.c_uint32)]
+    lib.msim_explain_lin_kv_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)]
+    lib.msim_explain_lin_kv.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    lib.msim_explain_lin_kv_rows.restype = lib.msim_explain_lin_kv_batch.restype = lib.msim_explain_lin_kv.restype = C.c_int
     lib.msim_check_txn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.msim_check_txn_batch.restype = C.c_int
     lib.msim_check_unique_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

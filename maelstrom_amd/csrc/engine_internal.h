@@ -98,8 +98,9 @@ void msim_gather_free(msim_ctx *ctx);
 // checker.hip
 int msim_check_launch(msim_ctx *ctx);
 // lin_check.cpp (host search) / lin_check_dev.hip (one wavefront per history)
-int msim_check_lin_kv_host(msim_ctx *ctx);
-int msim_check_lin_kv_device(msim_ctx *ctx);
+// (keys / max_keys / n_keys: msim_explain_lin_kv's key records, a slab of max_keys per history; null / 0 / null: the plain check)
+int msim_check_lin_kv_host(msim_ctx *ctx, msim_lin_key_result *keys = nullptr, uint32_t max_keys = 0, uint32_t *n_keys = nullptr);
+int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys = nullptr, uint32_t max_keys = 0, uint32_t *n_keys = nullptr);
 // txn_check.cpp (host analysis) / txn_check_dev.hip (device: proves a list-append history clean, else hands it to the host)
 int msim_check_txn_host(msim_ctx *ctx);
 int msim_check_txn_device(msim_ctx *ctx);

@@ -68,8 +68,22 @@ inline bool step(uint32_t val, const Op &op, uint32_t *out) {
   *out = op.v2; return true;
 }
 
-// one key: rows (indices into the instance history) in order.  Returns 1 linearizable, 0 not, 2 unknown (too wide).
-int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
+// the register values of a set of configurations as msim_lin_key_result reports them (dominance and the twin symmetry only drop
+// configurations whose value another one keeps, so this set does not depend on the pruning)
+void values_of(const std::vector<Cfg> &configs, uint64_t bm[4]) {
+  bm[0] = bm[1] = bm[2] = bm[3] = 0;
+  for (const Cfg &c : configs) bm[(c.val >> 6) & 3u] |= 1ull << (c.val & 63u);
+}
+void explain_fill(msim_lin_key_result *rec, uint32_t valid, uint32_t op_row, uint32_t prev_ok, uint32_t n_pending, const uint64_t bm[4]) {
+  rec->valid = valid; rec->op_row = op_row; rec->previous_ok_row = prev_ok; rec->n_pending = n_pending; rec->n_values = 0;
+  std::memset(rec->values, 0, sizeof rec->values);
+  if (!bm) return;
+  for (uint32_t v = 0; v < 256; v++) if ((bm[v >> 6] >> (v & 63u)) & 1ull) { if (rec->n_values < 8) rec->values[rec->n_values] = (uint8_t)v; rec->n_values++; }   // (nil = 0xFF comes last)
+}
+
+// one key: rows (indices into the instance history) in order.  Returns 1 linearizable, 0 not, 2 unknown (too wide).  `rec` (may be
+// null): the key's msim_lin_key_result but for its `key`.
+int check_key(const msim_op *rows, const std::vector<uint32_t> &idx, msim_lin_key_result *rec = nullptr) {
   // pair invocations with completions by process
   std::unordered_map<uint32_t, uint32_t> open;         // process -> position in idx of its invoke
   std::vector<int> comp(idx.size(), -1);               // invoke position -> completion position
@@ -79,7 +93,7 @@ int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
     if (MSIM_OP_TYPE(r) == MSIM_T_INVOKE) open[proc] = k;
     else { auto it = open.find(proc); if (it != open.end()) { comp[it->second] = (int)k; open.erase(it); } }
   }
-  struct Ev { bool call; uint32_t id; };
+  struct Ev { bool call; uint32_t id; uint32_t at; };   // at: the event's own position in idx
   std::vector<Ev> events;
   std::vector<Op> eff(idx.size());
   std::vector<int> inv_of(idx.size(), -1);
@@ -93,9 +107,9 @@ int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
       Op o; o.f = MSIM_OP_F(r); o.v1 = (src.value >> 8) & 0xFF; o.v2 = (src.value >> 16) & 0xFF; o.ok = ok;
       o.skip = !ok && o.f == MSIM_F_READ;                                      // an unfinished read constrains nothing
       eff[k] = o;
-      events.push_back({true, k});
+      events.push_back({true, k, k});
       if (c >= 0) inv_of[c] = (int)k;
-    } else if (MSIM_OP_TYPE(r) == MSIM_T_OK && inv_of[k] >= 0) events.push_back({false, (uint32_t)inv_of[k]});
+    } else if (MSIM_OP_TYPE(r) == MSIM_T_OK && inv_of[k] >= 0) events.push_back({false, (uint32_t)inv_of[k], k});
   }
   // pending ops get slots 0..63 in a bitmask
   std::unordered_map<uint32_t, uint32_t> slot_of;
@@ -122,9 +136,13 @@ int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
     return false;
   };
   std::vector<Cfg> configs{{0, 0xFF}}, stack, out;
+  uint32_t prev_ok = MSIM_NO_VALUE;      // (explaining) the row of the last :ok completion that returned
+  uint64_t before[4];                    // (explaining) the values of the configurations a closure starts from
+  auto open_calls = [&]() { uint32_t c = 0; for (uint64_t m = pending; m; m &= m - 1) c += !eff[op_in_slot[(uint32_t)__builtin_ctzll(m)]].skip; return c; };
+  auto unknown = [&]() { if (rec) explain_fill(rec, 2, MSIM_NO_VALUE, MSIM_NO_VALUE, 0, nullptr); return 2; };
   for (const Ev &ev : events) {
     if (ev.call) {
-      if (pending == ~0ull) return 2;
+      if (pending == ~0ull) return unknown();
       const uint32_t s = (uint32_t)__builtin_ctzll(~pending);
       pending |= 1ull << s; slot_of[ev.id] = s; op_in_slot[s] = ev.id;
       if (!eff[ev.id].ok) {
@@ -141,12 +159,13 @@ int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
     const uint32_t s = slot_of[ev.id];
     const uint64_t bit = 1ull << s;
     seen.clear(); out.clear(); stack.clear();
+    if (rec) values_of(configs, before);
     for (const Cfg &c : configs) if (admit(c)) stack.push_back(c);
     size_t explored = 0;
     while (!stack.empty()) {
       const Cfg c = stack.back(); stack.pop_back();
       if (!is_minimal(c)) continue;   // superseded by a smaller configuration found later
-      if (++explored > 2000000) return 2;
+      if (++explored > 2000000) return unknown();
       if (c.lin & bit) { out.push_back({c.lin & ~bit, c.val}); continue; }
       uint64_t cand = pending & ~c.lin;
       while (cand) {
@@ -169,12 +188,16 @@ int check_key(const msim_op *rows, const std::vector<uint32_t> &idx) {
     for (const Cfg &c : out) (void)admit(c);
     for (uint32_t u : seen.used) { const Seen::Slot &g = seen.slots[u];
       for (int i = g.head; i >= 0; i = seen.pool[(size_t)i].next) if (!seen.pool[(size_t)i].dead) configs.push_back({g.base | seen.pool[(size_t)i].ib, g.val}); }
-    if (configs.empty()) return 0;
+    if (configs.empty()) { if (rec) explain_fill(rec, 0, idx[ev.at], prev_ok, open_calls(), before); return 0; }   // (the returning call has left `pending`)
+    prev_ok = idx[ev.at];
   }
+  if (rec) { values_of(configs, before); explain_fill(rec, 1, MSIM_NO_VALUE, MSIM_NO_VALUE, open_calls(), before); }
   return 1;
 }
 
-void check_instance(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res) {
+// keys / max_keys / n_keys (null / 0 / null: the plain check): the key records of msim_explain_lin_kv_rows
+void check_instance(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys = nullptr, uint32_t max_keys = 0,
+                    uint32_t *n_keys = nullptr) {
   std::memset(res, 0, sizeof *res);
   std::unordered_map<uint32_t, std::vector<uint32_t>> by_key;
   for (uint32_t i = 0; i < n_rows; i++) {
@@ -186,6 +209,17 @@ void check_instance(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_c
     if (f == MSIM_F_READ || f == MSIM_F_WRITE || f == MSIM_F_CAS) by_key[r.value & 0xFF].push_back(i);
   }
   uint32_t bad = 0, unknown = 0;
+  if (keys) {   // in ascending key order, a record each
+    std::vector<uint32_t> order;
+    for (auto &kv : by_key) order.push_back(kv.first);
+    std::sort(order.begin(), order.end());
+    for (uint32_t i = 0; i < order.size(); i++) {
+      msim_lin_key_result *rec = i < max_keys ? &keys[i] : nullptr;
+      const int v = check_key(rows, by_key[order[i]], rec); bad += v == 0; unknown += v == 2;
+      if (rec) rec->key = order[i];
+    }
+    if (n_keys) *n_keys = (uint32_t)order.size();
+  } else
   for (auto &kv : by_key) { const int v = check_key(rows, kv.second); bad += v == 0; unknown += v == 2; }
   res->attempt_count = (uint32_t)by_key.size();    // keys checked (independent/checker)
   res->error_count = bad;                          // keys whose history is not linearizable
@@ -197,6 +231,17 @@ void check_instance(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_c
 // the host search for one history (lin_check_dev.hip hands over what exceeds the device's registers)
 void msim_lin_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res) { check_instance(rows, n_rows, flags, res); }
 
+// the same with the key records (msim_explain_lin_kv_batch / msim_explain_lin_kv hand over what exceeds the device's pools)
+void msim_lin_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys, uint32_t max_keys,
+                                    uint32_t *n_keys) { check_instance(rows, n_rows, flags, res, keys, max_keys, n_keys); }
+
+// Host-only entry point: msim_check_lin_kv_rows and the key records of the history.
+extern "C" int msim_explain_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim_check_result *out, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
+  if (!rows || !out || !keys || !n_keys || max_keys < 1 || max_keys > 256) return MSIM_E_INVALID;
+  check_instance(rows, n_rows, 0, out, keys, max_keys, n_keys);
+  return MSIM_OK;
+}
+
 // Host-only entry point: checks one lin-kv history given as rows (no device involved).
 extern "C" int msim_check_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim_check_result *out) {
   if (!rows || !out) return MSIM_E_INVALID;
@@ -205,20 +250,22 @@ extern "C" int msim_check_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim
 }
 
 // Runs the lin-kv checker over the fetched histories of the last run; results to ctx->h_check and ctx->d_check.
-int msim_check_lin_kv_host(msim_ctx *ctx) {
+int msim_check_lin_kv_host(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
   const auto t0 = std::chrono::steady_clock::now();
   int rc = msim_fetch(ctx);
   if (rc != MSIM_OK) return rc;
   const uint32_t n = ctx->n_inst;
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
   MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
+  if (keys) std::memset(keys, 0, (size_t)n * max_keys * sizeof(msim_lin_key_result));   // (as the device path leaves the records a history does not have)
   unsigned nt = msim_host_threads();
   if (nt > n) nt = n;
   std::vector<std::thread> th;
   for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([ctx, n, nt, t]() {
+    th.emplace_back([ctx, n, nt, t, keys, max_keys, n_keys]() {
       for (uint32_t i = t; i < n; i += nt)
-        check_instance(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_meta[i].flags, &ctx->h_check[i]);
+        check_instance(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_meta[i].flags, &ctx->h_check[i], keys ? keys + (size_t)i * max_keys : nullptr, max_keys,
+                       n_keys ? n_keys + i : nullptr);
     });
   for (auto &x : th) x.join();
   MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));

@@ -37,6 +37,8 @@
 #include "engine_internal.h"
 
 void msim_lin_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);   // lin_check.cpp
+void msim_lin_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys, uint32_t max_keys,
+                                    uint32_t *n_keys);                                                               // lin_check.cpp
 
 namespace {
 
@@ -321,10 +323,56 @@ __device__ int pool_close(const Pool &P, u32 &n_out) {
   return KEY_OK;
 }
 
+// ---- the explaining check (msim_explain_lin_kv*): one msim_lin_key_result per finished key --------------------------------------------
+// The explaining kernels (lin_check_explain_kernel / lin_check_wg_explain_kernel: the passes' text with EXPLAIN = true) report, beside the verdict, the register values present in the configurations "at that
+// moment" (include/maelsim.h): a 256-bit presence bitmap in LDS behind P.tws (8 words; the plain instantiations do not have them),
+// filled with atomicOr from whatever holds those configurations — the registers, the pool, P.outb.  Dominance, the twin symmetry and
+// the two-survivors race of pool_admit only ever drop a configuration whose value another one keeps, so the bitmap needs no
+// minimisation pass and equals the host's.  P.ctr[14] = 1 asks every thread of the workgroup to add the pool's entries (the start
+// configurations of a closure that begins in the pool) before pool_close overwrites them.
+struct XParams { msim_lin_key_result *keys; u32 max_keys; };   // history i's records at keys[i * max_keys ..]
+struct KeyRec { u32 op_row, prev_ok, n_pending, n_values, v_lo, v_hi; };
+__device__ __forceinline__ u32 *vb_of(const Pool &P) { return P.tws + 32; }
+__device__ __forceinline__ void vb_add(u32 *vb, u32 val) { atomicOr(&vb[(val >> 5) & 7u], 1u << (val & 31u)); }
+__device__ __forceinline__ void vb_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+// (one wavefront) the bitmap := the values of the configurations in the registers
+__device__ void vb_from_regs(u32 *vb, const RegSet &S, u32 lane) {
+  if (lane < 8u) vb[lane] = 0;
+  vb_wave_sync();
+  if ((S.alive >> lane) & 1ull) vb_add(vb, S.c_val);
+  vb_wave_sync();
+}
+// (one wavefront) the bitmap as the record has it: how many values, the first 8 ascending, a byte each (nil = 0xFF is the largest)
+__device__ void vb_read(const u32 *vb, u32 lane, KeyRec &kr) {
+  const u32 w = lane < 8u ? vb[lane] : 0u;
+  kr.n_values = l_wave_sum((u32)__popc(w));
+  u64 packed = 0; u32 got = 0;
+  for (u32 i = 0; i < 8u; i++) {
+    u32 wi = rl(w, i);
+    while (wi && got < 8u) { const u32 b = (u32)__builtin_ctz(wi); wi &= wi - 1u; packed |= (u64)(i * 32u + b) << (8u * got); got++; }
+  }
+  kr.v_lo = (u32)packed; kr.v_hi = (u32)(packed >> 32);
+}
+// (lane 0) record `idx` of history `inst`: two 16-byte vector stores
+__device__ void write_key_record(const XParams &xp, u32 inst, u32 idx, u32 k, int st, const KeyRec &kr) {
+  if (idx >= xp.max_keys) return;
+  uint4 *const dst = reinterpret_cast<uint4 *>(xp.keys + (size_t)inst * xp.max_keys + idx);
+  dst[0] = make_uint4(k, st == KEY_OK ? 1u : st == KEY_BAD ? 0u : 2u, kr.op_row, kr.prev_ok);
+  dst[1] = make_uint4(kr.n_pending, kr.n_values, kr.v_lo, kr.v_hi);
+}
+
 // pool_close with a way out when the pool overflows: what it holds — configurations reached so far, a sound start for the same closure —
 // moves to a slot of the workgroup-sized HBM workspace `g` (claimed here, kept for the rest of the history) and the closure runs again.
 struct Grow { u32 *ws; u32 *claim; u32 n_slots, cap, n_heads, out_cap; };   // ws == nullptr: no such workspace (pass 1)
+template <bool EXPLAIN>
 __device__ int pool_close_grow(Pool &P, u32 &n_out, const Grow &g) {
+  if constexpr (EXPLAIN) {   // (after the command barrier, before pool_close's first: nothing has been admitted yet)
+    if (P.ctr[14]) {
+      u32 *const vb = vb_of(P);
+      const u32 pn = min(P.ctr[0], P.cap);
+      for (u32 i = threadIdx.x; i < pn; i += blockDim.x) { const u32 c = pool_ld(&P.cfg[i]); if (!(c & P_DEAD)) vb_add(vb, c >> 24); }
+    }
+  }
   int st = pool_close(P, n_out);
   if (st != KEY_TOO_WIDE || g.ws == nullptr || P.cap >= g.cap) return st;
   const u32 tid = threadIdx.x, T = blockDim.x;
@@ -350,9 +398,12 @@ __device__ int pool_close_grow(Pool &P, u32 &n_out, const Grow &g) {
 // A closure that outgrows them moves to the pool P — `acquire` provides it at the first need, false = there is none: KEY_TOO_WIDE —
 // where the whole workgroup finishes it (pass 1: the wavefront alone; pass 2: it is the FIRST of a workgroup whose other wavefronts
 // wait in pool_workers()), and the survivors come back to the registers as soon as 64 lanes hold them again.
-template <class Acquire>
-__device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Outcome outcome, u32 lane, Pool &P, Acquire acquire, const Grow &grow) {
+// EXPLAIN: `kr` = the key's record when it is finished (KEY_OK / KEY_BAD / KEY_UNKNOWN), the same in every lane.
+template <bool EXPLAIN, class Acquire>
+__device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Outcome outcome, u32 lane, Pool &P, Acquire acquire, const Grow &grow, KeyRec &kr) {
   RegSet S; S.c_lin = 0; S.c_val = 0xFFu; S.alive = 1ull;
+  u32 prev_ok = MSIM_NO_VALUE, last_n_out = 0;        // (EXPLAIN) the row of the last :ok completion that returned; the survivors in P.outb while in_pool
+  if constexpr (EXPLAIN) { kr.op_row = MSIM_NO_VALUE; kr.prev_ok = MSIM_NO_VALUE; kr.n_pending = 0; kr.n_values = 0; kr.v_lo = 0; kr.v_hi = 0; }   // (what KEY_UNKNOWN reports)
   const bool prof = P.ctr[8] != 0;   // (developer trace: ctr[9..13] = register closures, their time, pool closures, their time, entries they admitted)
   bool in_pool = false;                               // the configurations are in the pool (more than 64 survived the last call)
   u64 pending = 0, info_bits = 0;
@@ -397,6 +448,7 @@ __device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Ou
             const u64 sm = __ballot(setter);
             if (sm) { const u32 nv = rl(sval, 63u - (u32)__builtin_clzll(sm)); if (lane == a) S.c_val = nv; }
             m &= ~__ballot(mine_row && rank < nclean);
+            if constexpr (EXPLAIN) { const u64 okm = __ballot(okc); if (okm) prev_ok = base + 63u - (u32)__builtin_clzll(okm); }   // the run's highest :ok completion
           }
         }
         continue;
@@ -435,6 +487,9 @@ __device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Ou
       int st = KEY_TOO_WIDE;
       u64 ov_lin = 0; u32 ov_val = 0;
       const u64 tq0 = prof ? wall_clock64() : 0;
+      RegSet S0;                                                 // (EXPLAIN) the configurations the closure starts from
+      if constexpr (EXPLAIN) S0 = S;
+      bool in_vb = false;                                        // (EXPLAIN) their values are in the bitmap already
       if (!in_pool) st = close_regs(S, pending, info_bits, s_op, s_tw, bit, lane, ov_lin, ov_val);
       if (prof && lane == 0) { P.ctr[9]++; P.ctr[10] += (u32)(wall_clock64() - tq0); }
       if (st == KEY_TOO_WIDE) {
@@ -450,15 +505,24 @@ __device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Ou
           if ((S.alive >> lane) & 1ull) pool_admit(P, (u32)S.c_lin | (S.c_val << 24), (u32)info_bits);
           if (lane == 0) pool_admit(P, (u32)ov_lin | (ov_val << 24), (u32)info_bits);
         }
+        if constexpr (EXPLAIN) {   // the start configurations' values: from the registers' copy here, from the pool by every thread (pool_close_grow)
+          u32 *const vb = vb_of(P);
+          if (lane < 8u) vb[lane] = 0;
+          if (lane == 0) P.ctr[14] = in_pool ? 1u : 0u;
+          vb_wave_sync();
+          if (!in_pool && ((S0.alive >> lane) & 1ull)) vb_add(vb, S0.c_val);
+          in_vb = true;
+        }
         if (lane == 0) P.ctr[3] = CMD_CLOSE;
         __syncthreads();   // (the command barrier: the other wavefronts join)
         u32 n_out = 0;
         const u64 tq1 = prof ? wall_clock64() : 0;
-        st = pool_close_grow(P, n_out, grow);
+        st = pool_close_grow<EXPLAIN>(P, n_out, grow);
         if (prof && lane == 0) { P.ctr[11]++; P.ctr[12] += (u32)(wall_clock64() - tq1); P.ctr[13] += P.ctr[0]; }
         if (st == KEY_TOO_WIDE) return KEY_TOO_WIDE;
         if (st == KEY_OK) {
           in_pool = n_out > 64u;
+          if constexpr (EXPLAIN) last_n_out = n_out;
           if (!in_pool) {
             const u32 c = lane < n_out ? pool_ld(&P.outb[lane]) : 0u;
             S.c_lin = c & P_LIN; S.c_val = c >> 24; S.alive = n_out == 64u ? ~0ull : (1ull << n_out) - 1ull;
@@ -466,19 +530,42 @@ __device__ int search_key(const uint4 *r, u32 n, u32 k, u32 lo, u32 hi, const Ou
         }
       }
       pending &= ~bit;
-      if (st == KEY_BAD) return KEY_BAD;
+      if (st == KEY_BAD) {
+        if constexpr (EXPLAIN) {   // Knossos' :op, :previous-ok and the :configs before the op
+          u32 *const vb = vb_of(P);
+          if (!in_vb) vb_from_regs(vb, S0, lane);
+          kr.op_row = base + j; kr.prev_ok = prev_ok;
+          kr.n_pending = (u32)__popcll(__ballot(((pending >> lane) & 1ull) && !(s_op >> 31)));   // (the returning call has left `pending`)
+          vb_read(vb, lane, kr);
+        }
+        return KEY_BAD;
+      }
+      if constexpr (EXPLAIN) prev_ok = base + j;
     }
+  }
+  if constexpr (EXPLAIN) {   // the :configs the search ends with
+    u32 *const vb = vb_of(P);
+    if (!in_pool) vb_from_regs(vb, S, lane);
+    else {
+      if (lane < 8u) vb[lane] = 0;
+      vb_wave_sync();
+      for (u32 i = lane; i < last_n_out; i += 64u) vb_add(vb, pool_ld(&P.outb[i]) >> 24);
+      vb_wave_sync();
+    }
+    kr.n_pending = (u32)__popcll(__ballot(((pending >> lane) & 1ull) && !(s_op >> 31)));
+    vb_read(vb, lane, kr);
   }
   return KEY_OK;
 }
 
 // the other wavefronts of the workgroup: wait for the first one's closures
+template <bool EXPLAIN>
 __device__ void pool_workers(Pool &P, const Grow &grow) {
   for (;;) {
     __syncthreads();
     if (P.ctr[3] == CMD_DONE) return;
     u32 n_out;
-    (void)pool_close_grow(P, n_out, grow);
+    (void)pool_close_grow<EXPLAIN>(P, n_out, grow);
   }
 }
 
@@ -495,7 +582,8 @@ __device__ void clear_result(msim_check_result &res) {
 
 // pass 1: one wavefront per history; the configurations in its registers, the closures that outgrow them in a slot of the HBM workspace
 struct HParams { u32 *pool; u32 *claim; u32 n_slots, cap, n_heads, out_cap, trace; };   // slot = cfg[cap] next[cap] heads[n_heads] outb[out_cap] words
-__global__ void __launch_bounds__(64) lin_check_kernel(const LParams p, const HParams hp) {
+template <bool EXPLAIN>
+__device__ __forceinline__ void lin_check_pass1(const LParams &p, const HParams &hp, const XParams &xp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32 *const key_lo = reinterpret_cast<u32 *>(smem);          // [256] first row of the key
   u32 *const key_hi = key_lo + 256;                           // [256] last row of the key
@@ -531,8 +619,10 @@ __global__ void __launch_bounds__(64) lin_check_kernel(const LParams p, const HP
   for (u32 k = 0; k < 256 && paired; k++) {
     const u32 lo = key_lo[k], hi = key_hi[k];
     if (lo == 0xFFFFFFFFu) continue;
-    const int st = search_key(r, n, k, lo, hi, outcome, lane, P, acquire, no_grow);
+    KeyRec kr;
+    const int st = search_key<EXPLAIN>(r, n, k, lo, hi, outcome, lane, P, acquire, no_grow, kr);
     if (st == KEY_TOO_WIDE) { resume = k; break; }
+    if constexpr (EXPLAIN) { if (lane == 0) write_key_record(xp, inst, n_keys, k, st, kr); }   // at index "keys finished so far"
     n_keys++; n_bad += st == KEY_BAD; n_unknown += st == KEY_UNKNOWN;
   }
   if (lane == 0) {
@@ -544,12 +634,16 @@ __global__ void __launch_bounds__(64) lin_check_kernel(const LParams p, const HP
     p.out[inst] = res;
   }
 }
+// (the plain kernel keeps its name and its arguments; the explaining one is the same text with EXPLAIN)
+__global__ void __launch_bounds__(64) lin_check_kernel(const LParams p, const HParams hp) { lin_check_pass1<false>(p, hp, XParams{nullptr, 0}); }
+__global__ void __launch_bounds__(64) lin_check_explain_kernel(const LParams p, const HParams hp, const XParams xp) { lin_check_pass1<true>(p, hp, xp); }
 
 // pass 2: one workgroup per history still open, from the key it stopped at: the first wavefront walks the keys with the configurations
 // in its registers, the whole workgroup closes the calls that outgrow them in the pool — in LDS (`cap` configurations = what 160 KiB
 // hold); the handful of closures that outgrow that too move to a slot of the HBM workspace `grow`
 struct WParams { u32 cap, n_heads, out_cap, trace; Grow grow; };
-__global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, const WParams wp) {
+template <bool EXPLAIN>
+__device__ __forceinline__ void lin_check_pass2(const LParams &p, const WParams &wp, const XParams &xp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32 *const key_lo = reinterpret_cast<u32 *>(smem);
   u32 *const key_hi = key_lo + 256;
@@ -557,7 +651,7 @@ __global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, con
   Pool P;
   P.cap = wp.cap; P.n_heads = wp.n_heads; P.out_cap = wp.out_cap;
   P.ctr = key_hi + 256 + outcome_bytes(p.table_rows) / 4; P.ops = P.ctr + 16; P.tws = P.ops + 32;
-  pool_place(P, P.tws + 32);
+  pool_place(P, P.tws + 32 + (EXPLAIN ? 8 : 0));   // (EXPLAIN: the value bitmap lies in between)
   const u32 tid = threadIdx.x, lane = tid & 63u, inst = p.list[blockIdx.x];
   msim_check_result res = p.out[inst];
   if (res.valid != NEEDS_HOST || res.lost_count == RESUME_NONE) return;   // decided by an earlier pass / not the device's
@@ -571,7 +665,7 @@ __global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, con
   __syncthreads();
   if (tid == 0) P.ctr[8] = wp.trace;
   __syncthreads();
-  if (tid >= 64) { pool_workers(P, wp.grow); return; }
+  if (tid >= 64) { pool_workers<EXPLAIN>(P, wp.grow); return; }
   const u64 t_p0 = wp.trace ? wall_clock64() : 0;
   { u32 a, b, c, d; (void)pair_rows(r, n, key_lo, key_hi, outcome, lane, a, b, c, d); }   // (pass 1 paired them: it fits)
   const u32 t_pair = wp.trace ? (u32)(wall_clock64() - t_p0) : 0;
@@ -579,8 +673,10 @@ __global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, con
   for (u32 k = k0; k < 256; k++) {
     const u32 lo = key_lo[k], hi = key_hi[k];
     if (lo == 0xFFFFFFFFu) continue;
-    const int st = search_key(r, n, k, lo, hi, outcome, lane, P, []() { return true; }, wp.grow);
+    KeyRec kr;
+    const int st = search_key<EXPLAIN>(r, n, k, lo, hi, outcome, lane, P, []() { return true; }, wp.grow, kr);
     if (st == KEY_TOO_WIDE) { resume = k; break; }
+    if constexpr (EXPLAIN) { if (lane == 0) write_key_record(xp, inst, n_keys, k, st, kr); }   // behind pass 1's records: n_keys began at its count
     n_keys++; n_bad += st == KEY_BAD; n_unknown += st == KEY_UNKNOWN;
   }
   if (lane == 0) P.ctr[3] = CMD_DONE;
@@ -594,12 +690,19 @@ __global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, con
     p.out[inst] = res;
   }
 }
+__global__ void __launch_bounds__(1024) lin_check_wg_kernel(const LParams p, const WParams wp) { lin_check_pass2<false>(p, wp, XParams{nullptr, 0}); }
+__global__ void __launch_bounds__(1024) lin_check_wg_explain_kernel(const LParams p, const WParams wp, const XParams xp) { lin_check_pass2<true>(p, wp, xp); }
 
 // launches the search over `n` histories: pass 1 (a wavefront each: 64 configurations in registers, the closures beyond that in a
 // slot of an HBM workspace), then for what it left open pass 2 (a workgroup of 1024 each, the pool in LDS: the largest that fits) and
-// the host search (all host threads) for what exceeds even that
-int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any, msim_check_result *h_out, hipStream_t st, u32 *n_host) {
+// the host search (all host threads) for what exceeds even that.  xp (may be null: the plain check, the plain kernels): the explaining
+// check — the EXPLAIN kernels write the key records to xp->keys (device, zeroed here), which come to h_keys (host, the same layout)
+// once the device passes are through; a history the host search finishes has all its records rewritten there.  h_n_keys[i] = its keys.
+int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any, msim_check_result *h_out, hipStream_t st, u32 *n_host,
+                      const XParams *xp = nullptr, msim_lin_key_result *h_keys = nullptr, u32 *h_n_keys = nullptr) {
   LParams lp = lp0;
+  const size_t keys_bytes = xp ? (size_t)n * xp->max_keys * sizeof(msim_lin_key_result) : 0;
+  const XParams xp0 = xp ? *xp : XParams{nullptr, 0};
   const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   const bool tiny = (msim_dev_flags(ctx) & 0x2000u) != 0;    // developer / tests: pools small enough that every level is reached, the host search included
   const auto t0 = std::chrono::steady_clock::now();
@@ -608,7 +711,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
   lp.table_rows = max_rows_any < table_cap ? max_rows_any : table_cap;
   lp.list = nullptr;
   const size_t lds = 2048 + outcome_bytes(lp.table_rows);
-  const size_t fixed = lds + (16 + 32 + 32) * 4;   // + the pools' counters and the calls' operations
+  const size_t fixed = lds + (16 + 32 + 32 + (xp ? 8 : 0)) * 4;   // + the pools' counters and the calls' operations (+ the explaining check's value bitmap)
   HParams hp;
   hp.cap = tiny ? 66 : 2048; hp.n_heads = tiny ? 32 : 512; hp.out_cap = tiny ? 66 : 1024;
   hp.n_slots = n < 4096u ? n : 4096u;   // (a history claims one when a closure first outgrows the registers; without one it waits for pass 2)
@@ -618,7 +721,10 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
   hp.claim = hp.pool + (ws_bytes - 256) / 4;
   struct Ws { u32 *p; ~Ws() { if (p) (void)msim_dev_free(p); } } ws_guard{hp.pool};
   MSIM_HIP_TRY(ctx, hipMemsetAsync(hp.claim, 0, 4, st));
-  hipLaunchKernelGGL(lin_check_kernel, dim3(n), dim3(64), fixed, st, lp, hp);
+  if (xp) {
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(xp0.keys, 0, keys_bytes, st));
+    hipLaunchKernelGGL(lin_check_explain_kernel, dim3(n), dim3(64), fixed, st, lp, hp, xp0);
+  } else hipLaunchKernelGGL(lin_check_kernel, dim3(n), dim3(64), fixed, st, lp, hp);
   MSIM_HIP_TRY(ctx, hipGetLastError());
   MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, lp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -648,7 +754,8 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
       const uint64_t first = lp.meta ? (uint64_t)i * lp.stride : ho[i];
       std::vector<msim_op> rows(nr ? nr : 1);
       if (nr && hipMemcpy(rows.data(), lp.rows + first, (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost) != hipSuccess) { copy_err = 1; return; }
-      msim_lin_check_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k]);
+      if (xp) { u32 nk = 0; msim_lin_explain_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k], h_keys + (size_t)i * xp0.max_keys, xp0.max_keys, &nk); }
+      else msim_lin_check_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k]);
       host_done[k] = 1;
     };
     u32 *d_list = nullptr, *ws2 = nullptr;
@@ -673,9 +780,11 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
       g.ws = nullptr; g.claim = nullptr;
       e = msim_dev_malloc(&ws2, (size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap) * 4 + 256);
       if (e == hipSuccess) { g.ws = ws2; g.claim = ws2 + (size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap); e = hipMemsetAsync(g.claim, 0, 4, st); }
-      if (e == hipSuccess && l2 > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lin_check_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
+      const void *const wg = xp ? reinterpret_cast<const void *>(&lin_check_wg_explain_kernel) : reinterpret_cast<const void *>(&lin_check_wg_kernel);
+      if (e == hipSuccess && l2 > 64 * 1024) e = hipFuncSetAttribute(wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
       if (e == hipSuccess) {
-        hipLaunchKernelGGL(lin_check_wg_kernel, dim3((u32)todo.size()), dim3(1024), l2, st, lp, wp);
+        if (xp) hipLaunchKernelGGL(lin_check_wg_explain_kernel, dim3((u32)todo.size()), dim3(1024), l2, st, lp, wp, xp0);
+        else hipLaunchKernelGGL(lin_check_wg_kernel, dim3((u32)todo.size()), dim3(1024), l2, st, lp, wp);
         e = hipGetLastError();
       }
       if (trace && e == hipSuccess) {
@@ -699,6 +808,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     else std::fill(wanted.begin(), wanted.end(), 1);   // (the host can still do everything)
     const double t_dev = ms();
     if (d_list) (void)msim_dev_free(d_list);
+    if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));   // (before the host search rewrites its histories' records)
     u32 n_host_needed = 0;
     for (size_t k = 0; k < order.size(); k++) n_host_needed += wanted[k] != 0;
     if (n_host_needed) {   // what even the HBM pools could not hold (or found no slot): the host search, all host threads
@@ -727,7 +837,8 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     if (trace) { u32 slots = 0; for (size_t k = 0; k < order.size(); k++) if (wanted[k] && h2[order[k]].duplicated_count == 1u) slots++;
       std::fprintf(stderr, "[lin-check] device passes done at %.2f ms, %u histories needed the host search (%u of them: more than 23 calls pending on a key)\n", t_dev, n_host_needed, slots); }
     todo.resize(n_host_needed);
-  }
+  } else if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));
+  if (xp) for (u32 i = 0; i < n; i++) h_n_keys[i] = h_out[i].attempt_count;   // keys checked = records the history has
   if (trace) std::fprintf(stderr, "[lin-check] done at %.2f ms\n", ms());
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
@@ -736,9 +847,12 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
 }  // namespace
 
 // msim_check for lin-kv: the histories of the last run, where they lie in HBM.
-int msim_check_lin_kv_device(msim_ctx *ctx) {
+int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
+  XParams xp; xp.keys = nullptr; xp.max_keys = max_keys;
+  if (keys) MSIM_HIP_TRY(ctx, msim_dev_malloc(&xp.keys, (size_t)n * max_keys * sizeof(msim_lin_key_result)));
+  struct Slab { msim_lin_key_result *p; ~Slab() { if (p) (void)msim_dev_free(p); } } slab_guard{xp.keys};
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
   MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
   LParams lp;
@@ -746,7 +860,7 @@ int msim_check_lin_kv_device(msim_ctx *ctx) {
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   const auto t0 = std::chrono::steady_clock::now();
   u32 redone = 0;
-  int rc = lin_check_dev_run(ctx, lp, n, ctx->cfg.max_rows, ctx->h_check, ctx->stream, &redone);
+  int rc = lin_check_dev_run(ctx, lp, n, ctx->cfg.max_rows, ctx->h_check, ctx->stream, &redone, keys ? &xp : nullptr, keys, n_keys);
   if (rc != MSIM_OK) return rc;
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
@@ -756,8 +870,8 @@ int msim_check_lin_kv_device(msim_ctx *ctx) {
 
 // Checks `n_histories` lin-kv histories given on the host (history i = rows[row_offsets[i] .. row_offsets[i+1])) on device
 // `device`; out[i] as msim_check_lin_kv_rows would fill it.
-extern "C" int msim_check_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out) {
-  if (!rows || !row_offsets || !out || n_histories == 0) return MSIM_E_INVALID;
+static int lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out,
+                        msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t *n_host) {
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
   msim_ctx tmp_ctx;   // error reporting in the HIP_TRY macro; the device the host worker threads select
   tmp_ctx.device = device;
@@ -766,19 +880,44 @@ extern "C" int msim_check_lin_kv_batch(int device, const msim_op *rows, const ui
   u32 max_n = 1;
   for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0xFFFFFFFFull) return MSIM_E_RANGE; if (c > max_n) max_n = (u32)c; }
   msim_op *d_rows = nullptr; uint64_t *d_off = nullptr; msim_check_result *d_out = nullptr;
+  XParams xp; xp.keys = nullptr; xp.max_keys = max_keys;
   int rc = MSIM_E_HIP;
   do {
     if (msim_dev_malloc(&d_rows, (size_t)(total ? total : 1) * sizeof(msim_op)) != hipSuccess) break;
     if (msim_dev_malloc(&d_off, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
     if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
+    if (keys && msim_dev_malloc(&xp.keys, (size_t)n_histories * max_keys * sizeof(msim_lin_key_result)) != hipSuccess) break;
     if (total && hipMemcpy(d_rows, rows, (size_t)total * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
     if (hipMemcpy(d_off, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
     LParams lp;
     lp.rows = d_rows; lp.meta = nullptr; lp.off = d_off; lp.out = d_out; lp.stride = 0; lp.table_rows = 0; lp.list = nullptr;
-    rc = lin_check_dev_run(ctx, lp, n_histories, max_n, out, nullptr, nullptr);
+    rc = lin_check_dev_run(ctx, lp, n_histories, max_n, out, nullptr, n_host, keys ? &xp : nullptr, keys, n_keys);
   } while (false);
+  if (xp.keys) (void)msim_dev_free(xp.keys);
   if (d_rows) (void)msim_dev_free(d_rows);
   if (d_off) (void)msim_dev_free(d_off);
   if (d_out) (void)msim_dev_free(d_out);
   return rc;
+}
+
+extern "C" int msim_check_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out) {
+  if (!rows || !row_offsets || !out || n_histories == 0) return MSIM_E_INVALID;
+  return lin_kv_batch(device, rows, row_offsets, n_histories, out, nullptr, 0, nullptr, nullptr);
+}
+
+// msim_check_lin_kv_batch with the key records (the EXPLAIN kernels; include/maelsim.h msim_lin_key_result).
+extern "C" int msim_explain_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out,
+                                         msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t *n_host) {
+  if (!rows || !row_offsets || !out || !keys || !n_keys || n_histories == 0 || max_keys < 1 || max_keys > 256) return MSIM_E_INVALID;
+  return lin_kv_batch(device, rows, row_offsets, n_histories, out, keys, max_keys, n_keys, n_host);
+}
+
+// msim_check for lin-kv with the key records: the histories of the last run, where they lie in HBM.
+extern "C" int msim_explain_lin_kv(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t n_out) {
+  if (!ctx || !keys || !n_keys || max_keys < 1 || max_keys > 256) return MSIM_E_INVALID;
+  if (ctx->cfg.workload != MSIM_WL_LIN_KV) { ctx->err = "msim_explain_lin_kv: not a lin-kv context"; return MSIM_E_UNSUPPORTED; }
+  if (!ctx->ran) { ctx->err = "msim_explain_lin_kv before msim_run"; return MSIM_E_RANGE; }
+  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_lin_kv: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
+         msim_check_lin_kv_host(ctx, keys, max_keys, n_keys) : msim_check_lin_kv_device(ctx, keys, max_keys, n_keys);
 }

@@ -20,6 +20,8 @@ CHECK_DT = np.dtype([("valid", "<u4"), ("attempt_count", "<u4"), ("stable_count"
                      ("never_read_count", "<u4"), ("stale_count", "<u4"), ("duplicated_count", "<u4"),
                      ("error_count", "<u4"), ("stable_latency_ms", "<u4", (5,)), ("op_count", "<u4"),
                      ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4")])
+LIN_KEY_DT = np.dtype([("key", "<u4"), ("valid", "<u4"), ("op_row", "<u4"), ("previous_ok_row", "<u4"), ("n_pending", "<u4"), ("n_values", "<u4"),
+                       ("values", "u1", (8,))])   # msim_lin_key_result
 LATENCY_DT = np.dtype([("count", "<u4"), ("q_us", "<u4", (5,)), ("sum_us", "<u8")])
 F_STATS_DT = np.dtype([("f", "<u4"), ("valid", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
                        ("unpaired", "<u4"), ("reserved", "<u4"), ("latency", LATENCY_DT, (3,))])
@@ -153,6 +155,16 @@ class Engine:
             self._chk(self.lib.msim_set_check_classify(self._ctx, 1 if classify else 0), "msim_set_check_classify")
             self._classify = bool(classify)
         self._chk(self.lib.msim_check(self._ctx), "msim_check")
+
+    def explain_lin_kv(self, max_keys=256):
+        """lin-kv: check() that also explains (msim_explain_lin_kv): per history of the last run (CHECK_DT record — check_results() holds
+        the same afterwards —, LIN_KEY_DT records, one per key ascending: Knossos' :op / :previous-ok rows, the :configs' register values
+        and the open calls; see lin_kv_analysis), written by the device search at every level it has."""
+        keys = np.zeros((self.n, max_keys), dtype=LIN_KEY_DT)
+        nk = np.zeros(self.n, dtype=np.uint32)
+        self._chk(self.lib.msim_explain_lin_kv(self._ctx, keys.ctypes.data, max_keys, nk.ctypes.data, self.n), "msim_explain_lin_kv")
+        res = self.check_results()
+        return [(res[i], keys[i, :min(int(nk[i]), max_keys)].copy()) for i in range(self.n)]
 
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
@@ -751,6 +763,68 @@ def check_lin_kv_batch(histories, device=0):
     if rc:
         raise EngineError(f"msim_check_lin_kv_batch: {rc}")
     return out
+
+
+def explain_lin_kv_history(rows, max_keys=256):
+    """The explaining lin-kv check of one history on the host (msim_explain_lin_kv_rows) -> (CHECK_DT record, LIN_KEY_DT records, one per
+    key ascending: Knossos' :op / :previous-ok rows and the :configs' register values; include/maelsim.h msim_lin_key_result)."""
+    rows = np.ascontiguousarray(rows)
+    out = np.zeros(1, dtype=CHECK_DT)
+    keys = np.zeros(max_keys, dtype=LIN_KEY_DT)
+    n = C.c_uint32()
+    rc = A.load().msim_explain_lin_kv_rows(rows.ctypes.data, len(rows), out.ctypes.data_as(C.POINTER(A.CheckResult)), keys.ctypes.data, max_keys, C.byref(n))
+    if rc:
+        raise EngineError(f"msim_explain_lin_kv_rows: {rc}")
+    return out[0], keys[:min(n.value, max_keys)].copy()
+
+
+def explain_lin_kv_batch(histories, device=0, max_keys=256, with_n_host=False):
+    """The explaining lin-kv check of several histories (arrays of rows) with the device search (msim_explain_lin_kv_batch): per history
+    (CHECK_DT record — what check_lin_kv_batch gives —, LIN_KEY_DT records as explain_lin_kv_history gives them).  with_n_host: also how
+    many histories the host search finished."""
+    hs = [np.ascontiguousarray(h) for h in histories]
+    off = np.zeros(len(hs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(h) for h in hs])
+    rows = np.concatenate(hs) if hs else np.zeros(0, dtype=OP_DT)
+    if len(rows) == 0:
+        rows = np.zeros(1, dtype=OP_DT)
+    out = np.zeros(len(hs), dtype=CHECK_DT)
+    keys = np.zeros((len(hs), max_keys), dtype=LIN_KEY_DT)
+    nk = np.zeros(len(hs), dtype=np.uint32)
+    n_host = C.c_uint32()
+    rc = A.load().msim_explain_lin_kv_batch(device, rows.ctypes.data, off.ctypes.data, len(hs), out.ctypes.data, keys.ctypes.data, max_keys, nk.ctypes.data, C.byref(n_host))
+    if rc:
+        raise EngineError(f"msim_explain_lin_kv_batch: {rc}")
+    res = [(out[i], keys[i, :min(int(nk[i]), max_keys)].copy()) for i in range(len(hs))]
+    return (res, n_host.value) if with_n_host else res
+
+
+def lin_kv_analysis(rows, key_records, payload=None, n_nodes=0):
+    """The Jepsen-shaped result map of `independent/checker` over Knossos' `checker/linearizable` from the key records of one history
+    (pure formatting): {"valid?", "results": {k: {"linearizable": {"valid?", "op", "previous-ok", "configs": [{"model": v}, ...],
+    "pending-count"}}}, "failures": [k ...]}; op / previous-ok are the history's ops as decode_history gives them (None where the record
+    has MSIM_NO_VALUE), a model value None is nil.  Not reported: :final-paths, :last-op, the number of configurations."""
+    verdict = {1: True, 0: False, 2: "unknown"}
+    ops = []
+
+    def op_at(row):
+        if int(row) == A.NO_VALUE:
+            return None
+        if not ops:
+            ops.extend(decode_history(rows, payload if payload is not None else np.zeros(1, dtype=np.uint32), n_nodes, A.WL_LIN_KV))
+        return ops[int(row)]
+
+    results, failures = {}, []
+    for rec in key_records:
+        k, valid = int(rec["key"]), verdict[int(rec["valid"])]
+        n_shown = min(int(rec["n_values"]), 8)
+        results[k] = {"linearizable": {"valid?": valid, "op": op_at(rec["op_row"]), "previous-ok": op_at(rec["previous_ok_row"]),
+                                       "configs": [{"model": _nil(int(v))} for v in rec["values"][:n_shown]], "value-count": int(rec["n_values"]),
+                                       "pending-count": int(rec["n_pending"])}}
+        if valid is False:
+            failures.append(k)
+    valid = False if failures else ("unknown" if any(r["linearizable"]["valid?"] == "unknown" for r in results.values()) else True)
+    return {"valid?": valid, "results": results, "failures": failures}
 
 
 def check_unique_batch(histories, device=0, fn="msim_check_unique_batch"):
