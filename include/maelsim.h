@@ -292,7 +292,13 @@ int msim_run(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances);
  * context, non-blocking: it does not wait for the null stream, nor the null stream for it), so that several contexts have their launches
  * in flight together.  msim_check, msim_fetch, msim_fetch_begin and msim_last_kernel_ms work on the context's stream and wait for what
  * was queued there: after a launch on the context's stream they may be called at once.  They do not know a caller's stream: a caller
- * that passes its own synchronises that stream before it calls any of them. */
+ * that passes its own synchronises that stream before it calls any of them.
+ * A context's slabs (msim_device_buffers) are OUTPUTS.  For set-full (broadcast, g-set) and echo, a context whose caller checks its
+ * launches queues the checker straight behind the simulation kernel, at launch time, on the context's own stream (see msim_check): a
+ * caller that writes into the slabs between msim_run* and msim_check gets the check of what the simulation wrote, not of what it wrote.
+ * A launch on the context's own stream (msim_run too) overwrites the slabs of the previous run; it waits ON THE DEVICE — the host does
+ * not — for the work the null stream holds at the time of the call, so that zero-copy readers of the previous run queued there have
+ * read them first.  A reader on another stream orders itself before the next msim_run* (an event, or a synchronisation). */
 int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances, void *hip_stream);
 
 /* Runs the workload checker for every instance of the last run, reading the HBM-resident histories.  On the device:
@@ -303,7 +309,14 @@ int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n_instances,
  * consistency model proscribes; a history it cannot prove valid is analysed in full by a second device pass (every edge kind, the
  * non-cycle anomalies, the cycle class: G0 / G1c / G-single / G2, -realtime), whose record is the one msim_check_rw_rows gives; only
  * shapes beyond the device capacities and duplicate writes go to the host (a cyclic component may be as large as the history).  Blocking.
- * Results via msim_check_results. */
+ * Results via msim_check_results.
+ * Set-full and echo (one kernel over the slabs, no host work): once msim_check has checked a launch made on the context's own stream, the
+ * context is armed, and its next launches on that stream queue the checker behind the simulation kernel themselves; msim_check then
+ * only waits for it.  With several contexts in flight the check runs beside the other contexts' simulations and not while the host
+ * waits here.  Nothing of a queued check is visible before msim_check: msim_check_results refuses until then, and the check's time
+ * (msim_last_kernel_ms) is taken from its own events as before.  A second msim_check of the same run launches the kernel again.  A new
+ * run that arrives while the previous run's queued check was never taken disarms the context (one wasted check per change of habit);
+ * a launch on a caller's stream never queues one. */
 int msim_check(msim_ctx *ctx);
 
 /* The two transactional workloads and kafka only (else MSIM_E_UNSUPPORTED).  txn-rw-register: on != 0 makes the next msim_check give, for EVERY
@@ -593,7 +606,10 @@ int msim_check_results(msim_ctx *ctx, const msim_check_result **results, uint32_
 /* Device-resident output buffers of the last run, for zero-copy consumers (RCCL gather, GPU checkers).
  * rows: n_instances * max_rows msim_op; payload: n_instances * max_payload_words u32;
  * stats: n_instances msim_net_stats; meta: n_instances msim_inst_meta; check: n_instances msim_check_result;
- * journal: n_instances * journal_capacity msim_event. */
+ * journal: n_instances * journal_capacity msim_event.
+ * The slabs are outputs: the engine overwrites them with the next run.  `check` of the previous msim_check is overwritten by the next
+ * check, which an armed context (msim_check) queues behind its next simulation kernel: never earlier than that kernel's end — stats
+ * and meta are overwritten no later than that — and no longer only by the next msim_check. */
 typedef struct msim_device_buffers {
   void *rows; void *payload; void *stats; void *meta;
   void *check;                 /* n_instances msim_check_result (valid after msim_check) */

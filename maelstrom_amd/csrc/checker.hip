@@ -492,7 +492,22 @@ static hipError_t check_dispatch(CParams &cp, u32 n, hipStream_t st) {
   return hipGetLastError();
 }
 
-int msim_check_launch(msim_ctx *ctx) {
+// d_check_scratch for n histories: the read records of every instance.  Frees and allocates when it has to grow — a hipFree waits for
+// the whole device —, so run_impl calls it in front of the simulation whose check it is about to queue, never between the two.
+int msim_check_reserve(msim_ctx *ctx, uint32_t n) {
+  const size_t rec_bytes = (size_t)n * (ctx->cfg.max_rows / 2 + 1) * 3 * sizeof(u32);
+  if (ctx->cap_check_scratch < rec_bytes) {
+    if (ctx->d_check_scratch) (void)msim_dev_free(ctx->d_check_scratch);
+    ctx->d_check_scratch = nullptr; ctx->cap_check_scratch = 0;
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_check_scratch, rec_bytes));
+    ctx->cap_check_scratch = rec_bytes;
+  }
+  return MSIM_OK;
+}
+
+// Queues the checker over the slabs of the last run on `stream`, between ev2 and ev3, and returns: it never waits.  Behind the
+// simulation kernel on the same stream (run_impl) it reads what that kernel wrote; it writes d_check and d_check_scratch only.
+int msim_check_enqueue(msim_ctx *ctx, hipStream_t stream) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const msim_config &c = ctx->cfg;
   CParams cp;
@@ -500,21 +515,27 @@ int msim_check_launch(msim_ctx *ctx) {
   cp.rows = ctx->d_rows; cp.payload = ctx->d_payload; cp.meta = ctx->d_meta; cp.out = ctx->d_check;
   cp.max_rows = c.max_rows; cp.max_pay = c.max_payload_words; cp.max_values = c.max_values; cp.C = c.concurrency; cp.workload = c.workload;
   if (const char *why = check_limits(c.max_rows, c.max_values, c.concurrency)) { ctx->err = why; return MSIM_E_UNSUPPORTED; }
-  const size_t rec_bytes = (size_t)ctx->n_inst * (c.max_rows / 2 + 1) * 3 * sizeof(u32);
-  if (ctx->cap_check_scratch < rec_bytes) {
-    if (ctx->d_check_scratch) (void)msim_dev_free(ctx->d_check_scratch);
-    ctx->d_check_scratch = nullptr; ctx->cap_check_scratch = 0;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_check_scratch, rec_bytes));
-    ctx->cap_check_scratch = rec_bytes;
-  }
+  const int rc = msim_check_reserve(ctx, ctx->n_inst);   // (run_impl has sized it already where the check follows its simulation)
+  if (rc != MSIM_OK) return rc;
   cp.recs = static_cast<u32 *>(ctx->d_check_scratch);
-  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-  MSIM_HIP_TRY(ctx, check_dispatch(cp, ctx->n_inst, ctx->stream));
-  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, stream));
+  MSIM_HIP_TRY(ctx, check_dispatch(cp, ctx->n_inst, stream));
+  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, stream));
+  return MSIM_OK;
+}
+
+// The other half: waits for the queued checker and makes its records visible (msim_check_results refuses until then).
+int msim_check_wait(msim_ctx *ctx) {
+  MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   MSIM_HIP_TRY(ctx, hipEventSynchronize(ctx->ev3));
   MSIM_HIP_TRY(ctx, hipEventElapsedTime(&ctx->check_ms, ctx->ev2, ctx->ev3));
   ctx->checked = true; ctx->check_fetched = false;
   return MSIM_OK;
+}
+
+int msim_check_launch(msim_ctx *ctx) {
+  const int rc = msim_check_enqueue(ctx, ctx->stream);
+  return rc != MSIM_OK ? rc : msim_check_wait(ctx);
 }
 
 // Checks `n_histories` broadcast / g-set (set-full) or echo histories given on the host with the device checker of msim_check:

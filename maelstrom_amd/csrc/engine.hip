@@ -145,6 +145,7 @@ extern "C" int msim_create(const msim_config *cfg, int device, msim_ctx **out, c
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev1);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev2);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev3);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_null, hipEventDisableTiming);
   if (e != hipSuccess) { set_err(err, errlen, hipGetErrorString(e)); delete ctx; return MSIM_E_HIP; }
   *out = ctx;
   return MSIM_OK;
@@ -231,6 +232,12 @@ static int ensure_buffers(msim_ctx *ctx, uint32_t n) {
   return MSIM_OK;
 }
 
+// The workloads whose msim_check is one launch of checker.hip's kernel over the slabs (msim_check_launch, the final return of
+// msim_check): set-full for broadcast and g-set, and echo.  Every other checker sizes host work from a copy of the instance meta.
+static bool check_launch_route(const msim_config &c) {
+  return c.workload == MSIM_WL_ECHO || c.workload == MSIM_WL_BROADCAST || c.workload == MSIM_WL_G_SET;
+}
+
 static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, bool blocking) {
   if (!ctx) return MSIM_E_INVALID;
   if (n == 0) { ctx->err = "n_instances must be > 0"; return MSIM_E_INVALID; }
@@ -238,9 +245,21 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   // msim_fetch_begin has queued PCIe copies on the context's stream: they are over before this launch (which may sit on the caller's own
   // stream, msim_run_async) drops the claim to them — the pinned mirrors they write may be regrown by the next fetch
   if (ctx->fetch_pending) { MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); ctx->fetch_pending = false; }
+  // The check queued behind the previous launch was never taken: this caller does not check every run, so the context stops queueing
+  // checks (msim_check arms it again).  That check may still be reading the slabs on the context's stream: a launch on that stream is
+  // ordered behind it, a launch on a caller's stream waits for it here (slabs that are regrown below are freed by hipFree, which waits).
+  const bool own_stream = st == ctx->stream;
+  if (ctx->check_queued) {
+    ctx->check_queued = false; ctx->check_armed = false;
+    if (!own_stream) MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
   int rc = ensure_buffers(ctx, n);
   if (rc != MSIM_OK) return rc;
   const msim_config &c = ctx->cfg;
+  // an armed context queues the checker straight behind this simulation (below, after ev1).  Its scratch grows HERE, in front of the
+  // launch: a hipFree / hipMalloc between the two kernels would stall every context's launches.  A failure is msim_check's to report.
+  const bool queue_check = ctx->check_armed && own_stream && check_launch_route(c) && !(msim_dev_flags(ctx) & 0x40000u) &&
+                           msim_check_reserve(ctx, n) == MSIM_OK;
   KParams kp;
   std::memset(&kp, 0, sizeof kp);
   kp.cfg = c; kp.first_instance = first;
@@ -284,6 +303,17 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   const size_t lds = off;
   if (lds > 160 * 1024) { ctx->err = "cluster state exceeds the 160 KiB LDS of a CU (lower inbox_capacity / max_values)"; return MSIM_E_INVALID; }
 
+  // The slabs this launch overwrites are what a zero-copy consumer of the previous run (msim_device_buffers_get) reads — bench.py's
+  // sums are queued on the null stream and never waited for.  Since the host no longer waits in msim_check for a check that was queued
+  // ahead, it can launch while those kernels still wait for a place on the chip (measured: 3 of 5 benchmark runs then summed rows of
+  // the NEW run's net stats).  So a launch on the context's own stream waits, on the device, for what the null stream holds now; the
+  // host does not wait, and the other contexts' launches are not held.  A consumer on another stream orders itself.  The dependency
+  // across two queues costs a launch some 20 us where nothing else fills the chip (measured at --in-flight 1: 0.866 -> 0.883 ms per
+  // step); asking first whether the null stream is idle (hipStreamQuery) costs more than it saves (0.866 -> 0.904).
+  if (own_stream) {
+    MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev_null, nullptr));
+    MSIM_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_null, 0));
+  }
   // developer check for reads of memory no kernel of this launch wrote: MSIM_POISON=<byte> fills every device buffer of the context
   // with that byte before each launch (HBM comes back from hipMalloc with whatever its last owner left there); results must not depend on it
   static const int poison = []() { const char *p = std::getenv("MSIM_POISON"); return p ? (int)(std::strtoul(p, nullptr, 0) & 0xFFu) : -1; }();
@@ -353,8 +383,16 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   if (e != hipSuccess) { ctx->err = std::string("kernel launch: ") + hipGetErrorString(e); return MSIM_E_HIP; }
   ctx->n_inst = n; ctx->first_instance = first;
   ctx->fetched = false; ctx->fetch_pending = false; ctx->checked = false; ctx->check_fetched = false; ctx->ran = true;
+  ctx->ran_own_stream = own_stream;
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
   ctx->sim_ms_stale = true;   // msim_run_async: the elapsed time is taken when somebody asks for it (the launch is over by then, or is waited for)
+  // The check of this run, queued now: its inputs are complete when the simulation kernel ends and the stream orders it behind that, so
+  // it runs beside the next launches of the other contexts and not while the host waits in msim_check.  Nothing of it is visible before
+  // msim_check (`checked` stays false); if it cannot be queued, msim_check launches it, and reports why, as it always did.
+  if (queue_check) {
+    ctx->check_queued = msim_check_enqueue(ctx, st) == MSIM_OK;
+    if (ctx->check_queued && (kp.dev_flags & 0x1000u)) std::fprintf(stderr, "[check] queued %u\n", n);
+  }
   if (blocking) {
     MSIM_HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
     MSIM_HIP_TRY(ctx, hipEventElapsedTime(&ctx->sim_ms, ctx->ev0, ctx->ev1));
@@ -400,6 +438,17 @@ extern "C" int msim_check(msim_ctx *ctx) {
     return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
            msim_check_unique_host(ctx) : msim_check_unique_device(ctx);
   }
+  // set-full (broadcast, g-set) and echo: one launch of checker.hip's kernel.  run_impl has queued it behind the simulation on an armed
+  // context: then this call only waits for it.  Otherwise the kernel is launched here — also for a second msim_check of the same run —
+  // and a caller that checks a launch on the context's own stream arms the context for its next launches.
+  const uint32_t flags = msim_dev_flags(ctx);
+  if (ctx->check_queued) {
+    ctx->check_queued = false;
+    if (flags & 0x1000u) std::fprintf(stderr, "[check] taken %u\n", ctx->n_inst);
+    return msim_check_wait(ctx);
+  }
+  if (ctx->ran_own_stream && !(flags & 0x40000u)) ctx->check_armed = true;
+  if (flags & 0x1000u) std::fprintf(stderr, "[check] launched %u\n", ctx->n_inst);
   return msim_check_launch(ctx);
 }
 
@@ -666,12 +715,14 @@ extern "C" const char *msim_last_error(const msim_ctx *ctx) { return ctx ? ctx->
 extern "C" void msim_destroy(msim_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
+  if (ctx->check_queued && ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // a queued check nobody took still reads the slabs
   free_buffers(ctx);
   msim_gather_free(ctx);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
   if (ctx->ev3) (void)hipEventDestroy(ctx->ev3);
+  if (ctx->ev_null) (void)hipEventDestroy(ctx->ev_null);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -17,6 +17,7 @@ struct msim_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;   // gather.cpp's own timing events
+  hipEvent_t ev_null = nullptr;                  // run_impl: what the null stream holds when a launch is queued (the launch waits for it on the device)
   // device buffers of the last run
   uint32_t n_inst = 0, cap_inst = 0;
   uint64_t first_instance = 0;
@@ -50,6 +51,10 @@ struct msim_ctx {
   void *d_all[4] = {nullptr, nullptr, nullptr, nullptr}; size_t cap_all[4] = {0, 0, 0, 0};   // rows, payload, meta, stats of every rank (root)
   uint64_t *d_sizes = nullptr;   // world x 4 u64 for the size all-gather
   bool fetched = false, checked = false, check_fetched = false, ran = false;
+  // the set-full / echo check queued behind its simulation at launch time (engine.hip run_impl, msim_check): `ran_own_stream` the last
+  // launch is on the context's own stream; `check_armed` the caller checked such a launch, so the next one queues its check straight
+  // behind the simulation kernel; `check_queued` that check is in the queue and msim_check has not taken it yet
+  bool ran_own_stream = false, check_armed = false, check_queued = false;
   float sim_ms = 0.f, check_ms = 0.f;
   bool sim_ms_stale = false;        // the last launch was msim_run_async: sim_ms is read from ev0 / ev1 on demand
   uint32_t dev_flags = 0;           // msim_set_dev_flags: ORed with the MSIM_DEV_FLAGS of the environment (developer switches)
@@ -84,7 +89,9 @@ static inline unsigned msim_host_threads() {
 // took (`[layout] <kernel> <n>`), 0x2000 the checkers' HBM-table kernels / the lin-kv search's tiny pools, 0x10000 at most 7 histories per
 // launch in the chunked checker loops (txn LDS and HBM-table passes, rw, unique-ids HBM tables: a partial last chunk, first > 0).  The
 // rw-register classification (rw_check_dev.hip): 0x2000 a matrix of 16 transactions per cyclic component and larger ones to the host,
-// 0x20000 a matrix of 16 with the search in the workspace behind it, as every component beyond 256 has it.
+// 0x20000 a matrix of 16 with the search in the workspace behind it, as every component beyond 256 has it.  0x40000 the set-full / echo
+// check is launched where msim_check is called, never queued behind its simulation (a context under it never arms).  Under 0x1000 the
+// route of every such check is named too: `[check] queued <n>` (run_impl), `[check] taken <n>` / `[check] launched <n>` (msim_check).
 static inline uint32_t msim_dev_flags(const msim_ctx *ctx) {
   static const uint32_t env = []() { const char *e = std::getenv("MSIM_DEV_FLAGS"); return e ? (uint32_t)std::strtoul(e, nullptr, 0) : 0u; }();   // (decimal, 0x.. or 0..)
   return env | (ctx ? ctx->dev_flags : 0u);
@@ -95,7 +102,13 @@ static inline uint32_t msim_dev_flags(const msim_ctx *ctx) {
 int msim_compact_on_device(msim_ctx *ctx, uint64_t *row_units, uint64_t *pay_words);
 // gather.cpp
 void msim_gather_free(msim_ctx *ctx);
-// checker.hip
+// checker.hip: the set-full / echo checker over the context's slabs.  msim_check_reserve sizes d_check_scratch for n histories (it may
+// free and allocate: never between a simulation and the check queued behind it); msim_check_enqueue queues the kernel between ev2 and
+// ev3 on `stream` and never waits; msim_check_wait waits for ev3 and marks the run checked; msim_check_launch = enqueue on the context's
+// stream + wait
+int msim_check_reserve(msim_ctx *ctx, uint32_t n);
+int msim_check_enqueue(msim_ctx *ctx, hipStream_t stream);
+int msim_check_wait(msim_ctx *ctx);
 int msim_check_launch(msim_ctx *ctx);
 // lin_check.cpp (host search) / lin_check_dev.hip (one wavefront per history)
 // (keys / max_keys / n_keys: msim_explain_lin_kv's key records, a slab of max_keys per history; null / 0 / null: the plain check)

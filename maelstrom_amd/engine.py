@@ -141,7 +141,9 @@ class Engine:
     def run_async(self, first_instance, n_instances, stream=None):
         """msim_run_async: queues the launch and returns.  stream=None is the context's own stream, on which check(), fetch(),
         fetch_begin() and kernel_ms() work: they wait for the launch and may be called at once.  They do not know a caller's stream
-        (a hipStream_t as an integer): a caller that passes its own synchronises that stream before it calls any of them."""
+        (a hipStream_t as an integer): a caller that passes its own synchronises that stream before it calls any of them.  On a context
+        whose launches the caller checks (see check()), a launch on the context's own stream queues the set-full / echo checker behind
+        the simulation kernel at once; the slabs of device_buffers() are outputs, and what a caller writes into them is not checked."""
         self._chk(self.lib.msim_run_async(self._ctx, first_instance, n_instances, stream), "msim_run_async")
         self.n = n_instances
 
@@ -150,7 +152,11 @@ class Engine:
         history's record is the full analysis of check_rw_history, its allowed cycle classes named.  txn-list-append: a history that is not
         provably clean is analysed and its cycles classified on the device, not on the host cores (the records are the same).  kafka: a
         history that is not provably clean has its anomalies named on the device, not on the host cores (the records are the same;
-        check_host_rechecks() then counts only classify_kafka_batch's hand-overs).  See anomaly_census, kafka_anomaly_census."""
+        check_host_rechecks() then counts only classify_kafka_batch's hand-overs).  See anomaly_census, kafka_anomaly_census.
+        Set-full (broadcast, g-set) and echo: the first check() of a launch on the context's own stream arms the context; its next
+        launches queue the checker behind their simulation, and check() only waits for it (check_results() refuses until then).  A
+        second check() of the same run launches the kernel again; a run nobody checked disarms the context; developer flag 0x40000
+        keeps the checker where check() is called."""
         if classify or getattr(self, "_classify", False):
             self._chk(self.lib.msim_set_check_classify(self._ctx, 1 if classify else 0), "msim_set_check_classify")
             self._classify = bool(classify)
