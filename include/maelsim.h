@@ -498,6 +498,61 @@ uint32_t msim_violated_anomalies(uint32_t anomalies, uint32_t consistency_model)
 int msim_check_rw_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,
                        msim_check_result *out);
 
+/* The transactional verdicts, explained: a WITNESS CYCLE for the cycle class of a history's record — what elle's result map carries
+ * per cycle anomaly as :cycle (the transactions) and :steps (the kind of each dependency; doc/05-datomic/04-optimization.md:311-345).
+ * The witness is defined independently of how any search walks the graph, so the host analysis, the device kernels (the matrix path
+ * and the search of a large component) and an unpruned search give the same bytes.
+ *   Class and masks.  cls (G0 / G1c / G-single / G2) and x (MSIM_EDGE_RT or 0) are what the record's error_count names: the dependency
+ *     edges alone are tried first, the realtime edges only if that finds nothing, and the lowest class is the one named.  The mask M is
+ *     WW|x for G0, WW|WR|x for G1c, WW|WR|RW|x for G2; for G-single N = WW|WR|x and the cycle closes through one RW edge.  An edge
+ *     a -> b "in mask K" is some edge a -> b, a != b, with a kind in K; parallel edges are merged.
+ *   G0 / G1c / G2.  t0 = the smallest transaction index on a cycle over M; d(v) = the BFS distance from t0 over M; the closing
+ *     transaction u minimises (d(u), u) among the transactions with an edge u -> t0 in M and finite d; the path is walked back from
+ *     p_L = u (L = d(u)): p_(i-1) = the smallest index w with d(w) = i - 1 and an edge w -> p_i in M.  The cycle is t0 = p_0 .. p_L,
+ *     length = L + 1; `kinds` of a step = the OR of the kinds of all edges between its two transactions, intersected with M.
+ *   G-single.  v0 = the smallest index v with an RW edge u -> v (u != v) whose u is reachable from v over N; BFS from v0 over N; u0
+ *     minimises (d(u), u) among the tails u of RW edges into v0 with finite d; the walk back as above over N.  The cycle is v0 .. u0;
+ *     the steps on the path report kinds & N, the last step (u0 -> v0) exactly MSIM_EDGE_RW.
+ *   No cycle: the record is all zeros and no step is written.
+ *   Truncation: steps beyond max_steps are not written (the slab there stays zero), `length` keeps the true value — the rule max_keys
+ *     follows in msim_explain_lin_kv_batch.
+ * Not reported: the key and the values behind a step (the device edges do not carry them), and witnesses for the non-cycle anomalies. */
+enum { MSIM_EDGE_WW = 1u, MSIM_EDGE_WR = 2u, MSIM_EDGE_RW = 4u, MSIM_EDGE_RT = 8u };
+typedef struct msim_cycle_result {   /* 16 bytes, one per history */
+  uint32_t anomalies;  /* the cycle bits of the history's record: one of MSIM_ANOMALY_G0 / G1C / G_SINGLE / G2, | MSIM_ANOMALY_REALTIME; 0 = no cycle */
+  uint32_t length;     /* transactions on the witness cycle (0 = none); NOT capped by max_steps */
+  uint32_t n_steps;    /* min(length, max_steps): steps written */
+  uint32_t reserved;   /* 0 */
+} msim_cycle_result;
+typedef struct msim_cycle_step {     /* 16 bytes */
+  uint32_t txn;        /* transaction index = ordinal of its :invoke among the client txn rows the analysis counts */
+  uint32_t inv_row;    /* its :invoke row */
+  uint32_t cmp_row;    /* its completion row; MSIM_NO_VALUE = never completed */
+  uint32_t kinds;      /* MSIM_EDGE_* of the step from this transaction to the next on the cycle (the last step returns to step 0) */
+} msim_cycle_step;
+
+/* Host-only: msim_check_txn_rows / msim_check_rw_rows judged under `consistency_model` (the same *out) with the witness: *cycle and
+ * steps[0 .. cycle->n_steps); steps holds max_steps (>= 1) records, those not written are zeroed.  Need no device. */
+int msim_explain_txn_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,
+                          msim_check_result *out, msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps);
+int msim_explain_rw_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,
+                         msim_check_result *out, msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps);
+/* As msim_classify_txn_batch / msim_classify_rw_batch (the same histories, the same out[i], the same refusals, and max_steps == 0 is
+ * MSIM_E_INVALID) with the witness found on the device (csrc/cycle_classify.inc, txn_explain_kernel / rw_explain_kernel): cycles[i],
+ * and history i's steps at steps + i * max_steps.  A list-append history the clean passes prove clean has the zero record; a history
+ * the host finishes (counted in *n_host as there) has the records of the host entries above. */
+int msim_explain_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                           uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host,
+                           msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps);
+int msim_explain_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                          uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host,
+                          msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps);
+/* The same over the histories of the last run where they lie in HBM (MSIM_WL_TXN_LIST_APPEND and MSIM_WL_TXN_RW_REGISTER, else
+ * MSIM_E_UNSUPPORTED), under the context's consistency model: cycles / steps hold `n_out` histories (at least the run's, else
+ * MSIM_E_RANGE).  Leaves msim_check_results as msim_check after msim_set_check_classify(ctx, 1) would; the switch itself is not
+ * changed.  Always the device route (developer flag 0x800 does not move it to the host cores). */
+int msim_explain_txn(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, uint32_t n_out);
+
 /* Host-only utility behind msim_check for pn-counter: the checker of workload/pn_counter.clj:84-123 — every :ok read
  * marked :final? must lie in the acceptable set = sum of the :ok adds plus any subset of the :info adds, kept as merged
  * closed integer ranges.  out->valid 1/0; attempt_count = final reads, error_count = final reads outside the set,

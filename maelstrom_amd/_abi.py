@@ -48,7 +48,9 @@ EXPORTS = [
     "msim_check_availability", "msim_check_availability_rows",
     "msim_check_perf", "msim_check_perf_rows", "msim_check_perf_batch",
     "msim_explain_lin_kv_rows", "msim_explain_lin_kv_batch", "msim_explain_lin_kv",
+    "msim_explain_txn_rows", "msim_explain_rw_rows", "msim_explain_txn_batch", "msim_explain_rw_batch", "msim_explain_txn",
 ]
+EDGE_KINDS = {1: "ww", 2: "wr", 4: "rw", 8: "realtime"}   # MSIM_EDGE_*
 AVAIL_NIL, AVAIL_TOTAL, AVAIL_FRACTION = range(3)
 PERF_MAX_F, PERF_MAX_WINDOWS = 4, 16
 COMM_ID_BYTES = 128
@@ -182,6 +184,14 @@ def load():
     lib.msim_check_set_full_batch.restype = C.c_int
     lib.msim_check_rw_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.msim_check_rw_batch.restype = C.c_int
+    for fn in (lib.msim_explain_txn_rows, lib.msim_explain_rw_rows):
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, P(CheckResult), C.c_void_p, C.c_void_p, C.c_uint32]
+        fn.restype = C.c_int
+    for fn in (lib.msim_explain_txn_batch, lib.msim_explain_rw_batch):
+        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        fn.restype = C.c_int
+    lib.msim_explain_txn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    lib.msim_explain_txn.restype = C.c_int
     lib.msim_classify_rw_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.msim_classify_rw_batch.restype = C.c_int
     lib.msim_classify_txn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]

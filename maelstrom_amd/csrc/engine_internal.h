@@ -116,9 +116,10 @@ int msim_check_lin_kv_host(msim_ctx *ctx, msim_lin_key_result *keys = nullptr, u
 int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys = nullptr, uint32_t max_keys = 0, uint32_t *n_keys = nullptr);
 // txn_check.cpp (host analysis) / txn_check_dev.hip (device: proves a list-append history clean, else hands it to the host)
 int msim_check_txn_host(msim_ctx *ctx);
-int msim_check_txn_device(msim_ctx *ctx);
+// (cycles / steps / max_steps: msim_explain_txn's witness cycles, a slab of max_steps per history; null / null / 0: the plain check)
+int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0);
 // rw_check_dev.hip (device: proves a rw-register history free of what the consistency model proscribes, else hands it to the host)
-int msim_check_rw_device(msim_ctx *ctx);
+int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0);
 // kafka_check.cpp (host)
 int msim_check_kafka_host(msim_ctx *ctx);
 // kafka_check_dev.hip (device pass + host checker for what it cannot prove clean)

@@ -40,6 +40,8 @@
 
 void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
                                  msim_check_result *res);   // txn_check.cpp
+void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);   // txn_check.cpp
 
 namespace {
 
@@ -59,6 +61,7 @@ struct RParams {
   const u32 *list;               // rw_classify_kernel: the histories of this launch (block b takes list[first + b])
   u32 ccap;                      // rw_classify_kernel: transactions of one strongly connected component the reachability matrix holds (<= CCAP)
   u32 big;                       // rw_classify_kernel: a larger component is searched in the workspace (0: it is the host's, MSIM_DEV_FLAGS bit 13)
+  msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // rw_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
 };
 
 __device__ __forceinline__ u32 r_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
@@ -80,8 +83,9 @@ __device__ __forceinline__ u32 r_excl_scan(u32 v, u32 lane) {
 
 // FULL = false: the pass that proves a history free of what the model proscribes (rw_check_kernel).  FULL = true: the classification
 // (rw_classify_kernel): every edge kind whatever the model is, the non-cycle anomalies accumulated, the cycles classified — the record
-// of check_rw + finish + classify + judge (txn_check.cpp), field for field.
-template <bool FULL>
+// of check_rw + finish + classify + judge (txn_check.cpp), field for field.  EXPLAIN (rw_explain_kernel, with FULL): and the witness cycle
+// of the record's cycle class (cycle_classify.inc).
+template <bool FULL, bool EXPLAIN = false>
 __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   const u32 lane = threadIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
@@ -363,7 +367,10 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   if constexpr (FULL) {
     u64 *const reach = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(jump + NM) + 7u) & ~(uintptr_t)7u);
     const CycleParams cp = {p.out, p.cm, p.proscribed, p.ccap, p.big};
-    cycle_classify(cp, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue, reach);
+    if constexpr (EXPLAIN) {
+      const CycleWitness cw = {p.cycles, p.steps, p.max_steps, t_inv, t_cmp};
+      cycle_classify<true>(cp, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue, reach, &cw);
+    } else cycle_classify(cp, hist, res, anomalies, n, n_edges, flags, c_ok, indeg, off, adj, roff, radj, st, jump, queue, reach);
     return;
   }
   // ---- F: acyclic?  Kahn's algorithm, 64 ready transactions per step ---------------------------------------------------------------------
@@ -408,6 +415,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
 
 __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) { rw_body<false>(p, p.first + blockIdx.x); }
 __global__ void __launch_bounds__(64) rw_classify_kernel(const RParams p) { rw_body<true>(p, p.list[p.first + blockIdx.x]); }
+__global__ void __launch_bounds__(64) rw_explain_kernel(const RParams p) { rw_body<true, true>(p, p.list[p.first + blockIdx.x]); }
 
 uint64_t rw_ws_words(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return (uint64_t)nmax * 11 + 4 + 2 * (uint64_t)kmax + 3 * (uint64_t)wmax + emax; }
 
@@ -416,7 +424,13 @@ uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws
 // full: every history's record comes from the classification (msim_classify_rw_batch, msim_set_check_classify); otherwise only the
 // records of the histories that rw_check_kernel could not prove valid do
 int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-               void **ws_buf, size_t *ws_cap, bool full = false) {
+               void **ws_buf, size_t *ws_cap, bool full = false, msim_cycle_result *h_cycles = nullptr, msim_cycle_step *h_steps = nullptr) {
+  // h_cycles / h_steps (msim_explain_rw_batch, msim_explain_txn; with full): the witness cycles, found by rw_explain_kernel in rp.cycles / rp.steps
+  const bool explain = full && h_cycles != nullptr;
+  if (explain) {
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(rp.cycles, 0, (size_t)n * sizeof(msim_cycle_result), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(rp.steps, 0, (size_t)n * rp.max_steps * sizeof(msim_cycle_step), st));
+  }
   const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   const auto t0 = std::chrono::steady_clock::now();
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
@@ -469,7 +483,8 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
     u32 launches = 0;
     for (u32 first = 0; first < m; first += chunk, launches++) {
       rp.first = first;
-      hipLaunchKernelGGL(rw_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
+      if (explain) hipLaunchKernelGGL(rw_explain_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
+      else hipLaunchKernelGGL(rw_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
       MSIM_HIP_TRY(ctx, hipGetLastError());
     }
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
@@ -477,6 +492,11 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
     todo.clear();
     for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
     if (trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, ms(), todo.size());
+  }
+  if (explain) {
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, rp.cycles, (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, rp.steps, (size_t)n * rp.max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   }
   if (!todo.empty()) {
     std::vector<uint64_t> ro, po;
@@ -499,8 +519,10 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
       th.emplace_back([&, w]() {
         for (size_t k = w; k < todo.size(); k += nt) {
           const u32 i = todo[k];
-          msim_rw_check_instance_host(rows[k].data(), hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), pays[k].data(),
-                                      hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]), hmeta ? (*hmeta)[i].flags : 0u, rp.cm, &h_out[i]);
+          const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
+          if (explain) msim_txn_explain_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, rp.cm, &h_out[i], &h_cycles[i],
+                                                      h_steps + (size_t)i * rp.max_steps, rp.max_steps, true);
+          else msim_rw_check_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, rp.cm, &h_out[i]);
         }
       });
     for (auto &x : th) x.join();
@@ -514,7 +536,8 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
 }  // namespace
 
 // msim_check for txn-rw-register: the histories of the last run, where they lie in HBM.
-int msim_check_rw_device(msim_ctx *ctx) {
+// (cycles / steps / max_steps: msim_explain_txn's witness cycles with every history's full record, whatever msim_set_check_classify says)
+int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
@@ -535,8 +558,14 @@ int msim_check_rw_device(msim_ctx *ctx) {
   // histories may need — 1 MB of workspace per history was four launches of 4096 for the demo shape, each waiting for its slowest history
   rp.kmax = ctx->cfg.max_values ? ctx->cfg.max_values : 1u;
   rp.wmax = (u32)std::min<uint64_t>(WMAX, (uint64_t)rp.kmax * (ctx->cfg.max_writes_per_key + 2u));
+  struct Slabs { void *c = nullptr, *s = nullptr; ~Slabs() { if (c) (void)msim_dev_free(c); if (s) (void)msim_dev_free(s); } } slabs;
+  if (cycles) {
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.c, (size_t)n * sizeof(msim_cycle_result)));
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.s, (size_t)n * max_steps * sizeof(msim_cycle_step)));
+    rp.cycles = static_cast<msim_cycle_result *>(slabs.c); rp.steps = static_cast<msim_cycle_step *>(slabs.s); rp.max_steps = max_steps;
+  }
   u32 redone = 0;
-  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->check_classify);
+  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->check_classify || cycles, cycles, steps);
   if (rc != MSIM_OK) return rc;
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
@@ -547,7 +576,8 @@ int msim_check_rw_device(msim_ctx *ctx) {
 // Checks `n_histories` rw-register histories given on the host (rows / payload words of history i at row_offsets[i] /
 // payload_offsets[i]) as msim_check does for the histories of a run.
 static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
-                    uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool full) {
+                    uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool full,
+                    msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
   msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
@@ -556,8 +586,11 @@ static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets
   u32 max_r = 1;
   for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0x7FFFFFFFull) return MSIM_E_RANGE; if (c > max_r) max_r = (u32)c; }
   msim_op *d_rows = nullptr; u32 *d_pay = nullptr; uint64_t *d_ro = nullptr, *d_po = nullptr; msim_check_result *d_out = nullptr; void *ws = nullptr; size_t ws_cap = 0;
+  msim_cycle_result *d_cycles = nullptr; msim_cycle_step *d_steps = nullptr;
   int rc = MSIM_E_HIP;
   do {
+    if (cycles && (msim_dev_malloc(&d_cycles, (size_t)n_histories * sizeof(msim_cycle_result)) != hipSuccess ||
+                   msim_dev_malloc(&d_steps, (size_t)n_histories * max_steps * sizeof(msim_cycle_step)) != hipSuccess)) break;
     if (msim_dev_malloc(&d_rows, (size_t)(tr ? tr : 1) * sizeof(msim_op)) != hipSuccess) break;
     if (msim_dev_malloc(&d_pay, (size_t)(tw ? tw : 1) * 4) != hipSuccess) break;
     if (msim_dev_malloc(&d_ro, (size_t)(n_histories + 1) * 8) != hipSuccess || msim_dev_malloc(&d_po, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
@@ -571,9 +604,10 @@ static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets
     rp.rows = d_rows; rp.payload = d_pay; rp.row_off = d_ro; rp.pay_off = d_po; rp.out = d_out;
     rp.nmax = max_r / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
      rp.proscribed = msim_proscribed_anomalies(consistency_model);
-    rc = rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, &ws, &ws_cap, full);
+    rp.cycles = d_cycles; rp.steps = d_steps; rp.max_steps = max_steps;
+    rc = rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, &ws, &ws_cap, full, cycles, steps);
   } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, ws}) if (q) (void)msim_dev_free(q);
+  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, (void *)d_cycles, (void *)d_steps, ws}) if (q) (void)msim_dev_free(q);
   return rc;
 }
 
@@ -587,6 +621,14 @@ extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64
 extern "C" int msim_classify_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                                       uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host) {
   return rw_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true);
+}
+
+// msim_classify_rw_batch with the witness cycles (rw_explain_kernel; include/maelsim.h msim_cycle_result).
+extern "C" int msim_explain_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                     uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host,
+                                     msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+  if (!cycles || !steps || max_steps == 0) return MSIM_E_INVALID;
+  return rw_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true, cycles, steps, max_steps);
 }
 
 extern "C" int msim_set_check_classify(msim_ctx *ctx, uint32_t on) {

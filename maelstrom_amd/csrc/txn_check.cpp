@@ -187,8 +187,73 @@ uint32_t judge(uint32_t anomalies, uint32_t cm) {
   return anomalies & msim_proscribed_anomalies(cm);
 }
 
+// The witness cycle of include/maelsim.h (msim_cycle_result / msim_cycle_step) for the cycle bits `dep` that finish() decided, straight
+// from the definition: a component search for t0 (or a search per candidate head for v0), one BFS, the walk back over the reversed edges.
+struct Witness { msim_cycle_result *cycle; msim_cycle_step *steps; uint32_t max_steps; };
+void witness(Scratch &S, uint32_t n, uint32_t dep, const Witness &W) {
+  const uint8_t x = (dep & MSIM_ANOMALY_REALTIME) ? E_RT : 0;
+  const bool single = (dep & MSIM_ANOMALY_G_SINGLE) != 0;
+  const uint8_t M = (uint8_t)(((dep & MSIM_ANOMALY_G0) ? E_WW : (dep & MSIM_ANOMALY_G2) ? E_WW | E_WR | E_RW : E_WW | E_WR) | x);   // (G-single: N)
+  std::vector<uint32_t> roff(n + 1, 0), d(n), q;
+  for (const Edge &e : S.adj) roff[e.to + 1]++;
+  for (uint32_t v = 0; v < n; v++) roff[v + 1] += roff[v];
+  std::vector<Edge> radj(S.adj.size());
+  { std::vector<uint32_t> pos(roff.begin(), roff.end() - 1); for (const Edge &e : S.adj) radj[pos[e.to]++] = e; }
+  const uint32_t INF = 0xFFFFFFFFu;
+  auto bfs = [&](uint32_t src) {
+    std::fill(d.begin(), d.end(), INF); q.clear(); q.push_back(src); d[src] = 0;
+    for (size_t h = 0; h < q.size(); h++) {
+      const uint32_t v = q[h];
+      for (uint32_t k = S.adj_off[v]; k < S.adj_off[v + 1]; k++) { const Edge &e = S.adj[k]; if ((e.kind & M) && d[e.to] == INF) { d[e.to] = d[v] + 1; q.push_back(e.to); } }
+    }
+  };
+  // the closing transaction: the tail u of an edge of `close` into `head` with the smallest (d(u), u)
+  auto closing = [&](uint32_t head, uint8_t close) -> uint32_t {
+    uint32_t u = INF;
+    for (uint32_t k = roff[head]; k < roff[head + 1]; k++) {
+      const Edge &e = radj[k];
+      if (!(e.kind & close) || d[e.from] == INF) continue;
+      if (u == INF || d[e.from] < d[u] || (d[e.from] == d[u] && e.from < u)) u = e.from;
+    }
+    return u;
+  };
+  uint32_t head = INF, u = INF;
+  if (!single) {
+    (void)scc(S, n, M);
+    std::vector<uint32_t> size(n, 0);
+    for (uint32_t v = 0; v < n; v++) size[(size_t)S.comp[v]]++;
+    for (uint32_t v = 0; v < n && head == INF; v++) if (size[(size_t)S.comp[v]] > 1) head = v;
+    if (head == INF) return;
+    bfs(head); u = closing(head, M);
+  } else {
+    for (uint32_t v = 0; v < n && head == INF; v++) {
+      bool cand = false;
+      for (uint32_t k = roff[v]; k < roff[v + 1] && !cand; k++) cand = (radj[k].kind & E_RW) != 0;
+      if (!cand) continue;
+      bfs(v); u = closing(v, E_RW);
+      if (u != INF) head = v;
+    }
+  }
+  if (head == INF || u == INF) return;
+  const uint32_t L = d[u];
+  W.cycle->anomalies = dep; W.cycle->length = L + 1; W.cycle->n_steps = std::min(L + 1, W.max_steps);
+  auto kinds = [&](uint32_t a, uint32_t b2, uint8_t mask) { uint32_t k2 = 0; for (uint32_t k = S.adj_off[a]; k < S.adj_off[a + 1]; k++) if (S.adj[k].to == b2) k2 |= S.adj[k].kind; return k2 & mask; };
+  uint32_t at = u, next = head;
+  for (uint32_t i = L + 1; i-- > 0;) {   // position i holds p_i; `next` is p_(i+1) (the head behind p_L)
+    if (i < W.max_steps) {
+      msim_cycle_step &s = W.steps[i];
+      s.txn = at; s.inv_row = (uint32_t)S.txns[at].inv; s.cmp_row = S.txns[at].cmp < 0 ? MSIM_NO_VALUE : (uint32_t)S.txns[at].cmp;
+      s.kinds = (single && i == L) ? (uint32_t)E_RW : kinds(at, next, M);
+    }
+    if (i == 0) break;
+    uint32_t w = INF;
+    for (uint32_t k = roff[at]; k < roff[at + 1]; k++) { const Edge &e = radj[k]; if ((e.kind & M) && d[e.from] == i - 1 && e.from < w) w = e.from; }
+    next = at; at = w;
+  }
+}
+
 // realtime edges, adjacency, cycle classification, verdict
-void finish(Scratch &S, uint32_t anomalies, uint32_t flags, uint32_t cm, msim_check_result *out) {
+void finish(Scratch &S, uint32_t anomalies, uint32_t flags, uint32_t cm, msim_check_result *out, const Witness *W = nullptr) {
   const uint32_t n = (uint32_t)S.txns.size();
   auto add = [&](uint32_t a, uint32_t b2, uint8_t kind) { if (a != b2) S.edges.push_back(Edge{a, b2, kind}); };
   for (uint32_t t = 0; t < n; t++) if (S.txns[t].type != MSIM_T_FAIL) for (uint32_t k = 0; k < S.txns[t].n_rt; k++) add(S.rt[S.txns[t].rt0 + k], t, E_RT);
@@ -206,6 +271,7 @@ void finish(Scratch &S, uint32_t anomalies, uint32_t flags, uint32_t cm, msim_ch
     uint32_t dep = classify(S, n, false, &cyc);
     if (!dep) { const uint32_t with_rt = classify(S, n, true, &cyc); if (with_rt) dep = with_rt | MSIM_ANOMALY_REALTIME; }
     anomalies |= dep;
+    if (W && dep) witness(S, n, dep, *W);
   }
 
   out->lost_count = (uint32_t)S.edges.size(); out->stale_count = cyc; out->error_count = anomalies;
@@ -213,7 +279,8 @@ void finish(Scratch &S, uint32_t anomalies, uint32_t flags, uint32_t cm, msim_ch
 }
 
 // ---- list-append -------------------------------------------------------------------------------------------------------
-void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out) {
+void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out,
+                   const Witness *W = nullptr) {
   uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, false, out), max_key = 0;
   const uint32_t n = (uint32_t)S.txns.size();
   uint32_t max_val = 0;
@@ -314,7 +381,7 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
       if (m.len < lm.len) { const int w = S.writer[kv(m.key, ord[m.len])]; if (w >= 0 && S.txns[(size_t)w].type != MSIM_T_FAIL) add(t, (uint32_t)w, E_RW); }
     }
   }
-  finish(S, anomalies, flags, cm, out);
+  finish(S, anomalies, flags, cm, out, W);
 }
 
 // ---- rw-register -------------------------------------------------------------------------------------------------------
@@ -328,7 +395,8 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
 //     reads must agree with the transaction's own earlier micro-ops (internal); G1a / G1b as for list-append.
 // Returns false (out->valid = 2, unknown) when a register value is >= 64: the version graphs below hold 64 versions per key
 // (the engine's generator stops at max-writes-per-key <= 63; externally produced histories may not).
-bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out) {
+bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out,
+              const Witness *W = nullptr) {
   uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, true, out), max_key = 0;
   const uint32_t n = (uint32_t)S.txns.size();
   uint32_t max_val = 0;
@@ -431,7 +499,7 @@ bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *
       }
     }
   }
-  finish(S, anomalies, flags, cm, out);
+  finish(S, anomalies, flags, cm, out, W);
   return true;
 }
 
@@ -447,6 +515,35 @@ void msim_txn_check_instance_host(const msim_op *rows, uint32_t n_rows, const ui
 void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res) {
   thread_local Scratch S;
   (void)check_rw(S, rows, n_rows, payload, n_words, flags, cm, res);
+}
+
+// the same with the witness cycle (the explain kernels hand over what they cannot finish); cycle / steps[0 .. max_steps) are cleared first
+void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw) {
+  thread_local Scratch S;
+  std::memset(cycle, 0, sizeof *cycle); std::memset(steps, 0, (size_t)max_steps * sizeof *steps);
+  const Witness W = {cycle, steps, max_steps};
+  if (rw) (void)check_rw(S, rows, n_rows, payload, n_words, flags, cm, res, &W);
+  else check_history(S, rows, n_rows, payload, n_words, flags, cm, res, &W);
+}
+
+extern "C" int msim_explain_txn_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,
+                                     msim_check_result *out, msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps) {
+  if (!rows || !out || (!payload && n_words) || consistency_model > MSIM_CM_READ_UNCOMMITTED || !cycle || !steps || max_steps == 0) return MSIM_E_INVALID;
+  Scratch S;
+  std::memset(cycle, 0, sizeof *cycle); std::memset(steps, 0, (size_t)max_steps * sizeof *steps);
+  const Witness W = {cycle, steps, max_steps};
+  check_history(S, rows, n_rows, payload, n_words, 0, consistency_model, out, &W);
+  return MSIM_OK;
+}
+
+extern "C" int msim_explain_rw_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,
+                                    msim_check_result *out, msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps) {
+  if (!rows || !out || (!payload && n_words) || consistency_model > MSIM_CM_READ_UNCOMMITTED || !cycle || !steps || max_steps == 0) return MSIM_E_INVALID;
+  Scratch S;
+  std::memset(cycle, 0, sizeof *cycle); std::memset(steps, 0, (size_t)max_steps * sizeof *steps);
+  const Witness W = {cycle, steps, max_steps};
+  return check_rw(S, rows, n_rows, payload, n_words, 0, consistency_model, out, &W) ? MSIM_OK : MSIM_E_INVALID;
 }
 
 extern "C" int msim_check_txn_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, msim_check_result *out) {

@@ -39,6 +39,8 @@
 
 void msim_txn_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
                                   msim_check_result *res);   // txn_check.cpp
+void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);   // txn_check.cpp
 
 namespace {
 
@@ -58,6 +60,7 @@ struct TParams {
   const u32 *list;               // (not null: the launch's histories are list[first + blockIdx.x])
   u32 lds_bytes;                 // txn_check_lds_kernel: dynamic LDS of a wavefront
   u32 cm, proscribed, ccap, big; // txn_classify_kernel: the model and what it proscribes; cycle_classify.inc's matrix and search (CycleParams)
+  msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // txn_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
 };
 
 __device__ __forceinline__ u32 t_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
@@ -892,251 +895,19 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
 __device__ __forceinline__ u32 t_or(u32 v) { for (int o = 32; o; o >>= 1) v |= (u32)__shfl_xor((int)v, o); return v; }
 
 __global__ void __launch_bounds__(64) txn_classify_kernel(const TParams p) {
-  const u32 lane = threadIdx.x, hist = p.list[p.first + blockIdx.x];
-  const u64 lt = (1ull << lane) - 1ull;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n_rows = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
-  const u32 NM = p.nmax;
-  u32 *const ws = p.ws + (u64)blockIdx.x * p.ws_words;   // (ws_words is even and the workspace 256-byte aligned: the 64-bit tables come first)
-  u64 *const long64 = reinterpret_cast<u64 *>(ws);            // [KMAX] (len + 1) << 40 | inverted transaction << 16 | inverted micro-op
-  u64 *const reach = long64 + KMAX;                           // [NM] cycle_classify's search of a component beyond the matrix
-  u32 *const t_cmp = reinterpret_cast<u32 *>(reach + NM), *const t_off = t_cmp + NM, *const t_lt = t_off + NM;   // t_lt: words | type << 16
-  u32 *const t_first = t_lt + NM;            // transactions invoked before this one's completion row (= index of the first one after it)
-  u32 *const sm = t_first + NM;              // [NM + 1] suffix minimum of the :ok completions ...
-  u32 *const smf = sm + NM + 1;              // [NM + 1] ... and t_first of the transaction that attains it
-  u32 *const deg = smf + NM + 1, *const off = deg + NM;   // off [NM + 1]: out-degrees, then CSR offsets
-  u32 *const cur = off + NM + 1, *const queue = cur + NM;
-  u32 *const roff = queue + NM, *const rcur = roff + NM + 1, *const st = rcur + NM, *const jump = st + NM;   // roff [NM + 1]: in-degrees, then offsets
-  u32 *const longest = jump + NM;            // [KMAX] (len + 1) << 24 | first payload word of the list
-  u32 *const writer = longest + KMAX;        // [WMAX]
-  u32 *const adj = writer + WMAX, *const radj = adj + p.emax;   // [emax] each
-
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
-#define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
-  if (n_words >= (1u << 24) || NM > 0xFFFFFFu) TO_HOST();
-
-  // ---- A: transactions (txn_check_kernel's pairing) ---------------------------------------------------------------------------------
-  u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0;
-  {
-    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // lane = one open call (o_len: words of its request)
-    for (u32 base = 0; base < n_rows; base += 64) {
-      const u32 idx = base + lane;
-      uint4 row = make_uint4(0, 0, 0, 0);
-      if (idx < n_rows) row = r[idx];
-      const u32 type = row.z & 3u, f = (row.z >> 2) & 31u, proc = row.z >> 12, len = row.y >> 16, woff = row.w;
-      const bool is = idx < n_rows && proc != MSIM_PROCESS_NEMESIS && f == MSIM_F_TXN;
-      if (__ballot(is && (u64)woff + len > n_words)) { bad = true; break; }
-      const bool inv = is && type == MSIM_T_INVOKE;
-      const u64 im = __ballot(inv);
-      const u32 my_t = n + (u32)__popcll(im & lt);
-      if (n + (u32)__popcll(im) > NM) { bad = true; break; }
-      if (inv) { t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); t_first[my_t] = 0; }   // never completed = indeterminate
-      u64 m = __ballot(is);
-      while (m) {
-        const u32 j = (u32)__builtin_ctzll(m); m &= m - 1;
-        const u32 z = t_rl(row.z, j);
-        const u32 jt = z & 3u, jp = z >> 12;
-        const u64 hit = __ballot(o_used && o_proc == jp);
-        if (jt == MSIM_T_INVOKE) {
-          u32 s;
-          if (hit) s = (u32)__builtin_ctzll(hit);
-          else { const u64 used = __ballot(o_used); if (used == ~0ull) { bad = true; break; } s = (u32)__builtin_ctzll(~used); }
-          const u32 tj = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-          const u32 jl = t_rl(row.y, j) >> 16;
-          if (lane == s) { o_used = true; o_proc = jp; o_txn = tj; o_len = jl; }
-        } else if (hit) {
-          const u32 s = (u32)__builtin_ctzll(hit);
-          const u32 id = t_rl(o_txn, s), ilen = t_rl(o_len, s);
-          if (lane == s) o_used = false;
-          if (lane == j) {
-            t_cmp[id] = idx; t_first[id] = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-            if (jt == MSIM_T_OK) { t_off[id] = woff; t_lt[id] = len | (MSIM_T_OK << 16); }   // the completed form replaces the requested one
-            else t_lt[id] = ilen | (jt << 16);
-          }
-          c_ok += jt == MSIM_T_OK; c_fail += jt == MSIM_T_FAIL; c_info += jt == MSIM_T_INFO;
-        }
-      }
-      if (bad) break;
-      n += (u32)__popcll(im);
-    }
-    if (bad) TO_HOST();
-  }
-  __syncthreads();
-  res.op_count = n; res.attempt_count = n; res.ok_count = c_ok; res.stable_count = c_ok; res.fail_count = c_fail; res.info_count = c_info;
-#define TYPE(t_) (t_lt[t_] >> 16)
-
-  // ---- B: ranges, and the tables cleared ------------------------------------------------------------------------------------------
-  u32 max_key = 0, max_val = 0, anomalies = 0; bool bad = false;
-  for (u32 t = lane; t < n; t += 64) {
-    const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-    for (u32 i = 0; i < wn;) { const Mop m = next_mop(w, wn, i); bad |= m.bad; max_key = max(max_key, m.key); if (m.f) max_val = max(max_val, m.val); }
-  }
-  max_key = t_max(max_key); max_val = t_max(max_val);
-  const u32 stride = max_val + 1u;
-  if (__ballot(bad) || max_key >= KMAX || (u64)(max_key + 1u) * stride > WMAX) TO_HOST();
-  for (u32 k = lane; k <= max_key; k += 64) { longest[k] = 0; long64[k] = 0; }
-  for (u32 k = lane; k < (max_key + 1u) * stride; k += 64) writer[k] = NONE;
-  for (u32 t = lane; t <= n; t += 64) { off[t] = 0; roff[t] = 0; if (t < n) { cur[t] = 0; rcur[t] = 0; } }
-  __syncthreads();
-
-  // ---- C: writers (every transaction, whatever became of it) -------------------------------------------------------------------------
-  for (u32 t = lane; t < n; t += 64) {
-    const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-    for (u32 i = 0; i < wn;) { const Mop m = next_mop(w, wn, i); if (m.f && atomicCAS(&writer[m.key * stride + m.val], NONE, t) != NONE) bad = true; }
-  }
-  __syncthreads();
-  if (__ballot(bad)) TO_HOST();   // a (key, element) appended twice: the host's table is last-writer-wins in row order
-#define WRITER(k_, el_) ((el_) < stride ? writer[(k_) * stride + (el_)] : NONE)
-
-  // ---- D: the reads of :ok transactions ------------------------------------------------------------------------------------------------
-  for (u32 t = lane; t < n; t += 64) {
-    if (TYPE(t) != MSIM_T_OK) continue;
-    const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-    u32 k = 0;
-    for (u32 i = 0; i < wn; k++) {
-      const Mop m = next_mop(w, wn, i);
-      if (m.f) continue;
-      { u64 s0 = 0, s1 = 0, s2 = 0, s3 = 0;   // duplicates
-        for (u32 e = 0; e < m.len; e++) {
-          const u32 x = elem(m.list, e); const u64 b = 1ull << (x & 63u); const u32 q = x >> 6;
-          const u64 s = q == 0 ? s0 : q == 1 ? s1 : q == 2 ? s2 : s3;
-          if (s & b) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;
-          s0 |= q == 0 ? b : 0; s1 |= q == 1 ? b : 0; s2 |= q == 2 ? b : 0; s3 |= q == 3 ? b : 0;
-        } }
-      { int prev = -1; Mop pm = m; u32 e_i = 0, e_k = 0;   // internal consistency: what the transaction's own earlier micro-ops imply for this read
-        for (e_i = 0, e_k = 0; e_k < k; e_k++) { const Mop q = next_mop(w, wn, e_i); if (!q.f && q.key == m.key) { prev = (int)e_k; pm = q; } }
-        const u32 e0 = prev < 0 ? 0u : (u32)prev + 1u;
-        u32 n_app = 0;
-        for (e_i = 0, e_k = 0; e_k < k; e_k++) { const Mop q = next_mop(w, wn, e_i); if (e_k >= e0 && q.f && q.key == m.key) n_app++; }
-        bool ok = true; u32 at = 0;
-        if (prev >= 0) { ok = m.len == pm.len + n_app; if (ok) for (u32 e = 0; e < pm.len; e++) ok &= elem(m.list, e) == elem(pm.list, e); at = pm.len; }
-        else { ok = m.len >= n_app; at = m.len - n_app; }
-        if (ok) { u32 a = 0; for (e_i = 0, e_k = 0; e_k < k; e_k++) { const Mop q = next_mop(w, wn, e_i); if (e_k >= e0 && q.f && q.key == m.key) { if (elem(m.list, at + a) != q.val) ok = false; a++; } } }
-        if (!ok) anomalies |= MSIM_ANOMALY_INTERNAL; }
-      u32 ext = m.len;   // the externally visible part: without the transaction's own appends at the tail
-      while (ext > 0 && WRITER(m.key, elem(m.list, ext - 1)) == t) ext--;
-      for (u32 e = 0; e < ext; e++) { const u32 wr = WRITER(m.key, elem(m.list, e)); if (wr == NONE || TYPE(wr) == MSIM_T_FAIL) anomalies |= MSIM_ANOMALY_G1A; }
-      if (ext > 0) {   // G1b: the last visible element must be its writer's last append to the key
-        const u32 last = elem(m.list, ext - 1), wr = WRITER(m.key, last);
-        if (wr != NONE && wr != t) {
-          const u32 *w2 = pay + t_off[wr]; const u32 wn2 = t_lt[wr] & 0xFFFFu; u32 fin = NONE;
-          for (u32 i2 = 0; i2 < wn2;) { const Mop q = next_mop(w2, wn2, i2); if (q.f && q.key == m.key) fin = q.val; }
-          if (fin != last) anomalies |= MSIM_ANOMALY_G1B;
-        }
-      }
-      // the key's longest read; among equals the first in (transaction, micro-op) order
-      atomicMax(reinterpret_cast<unsigned long long *>(&long64[m.key]),
-                (unsigned long long)(((u64)(m.len + 1u) << 40) | ((u64)(0xFFFFFFu - t) << 16) | (u64)(0xFFFFu - (k & 0xFFFFu))));
-    }
-  }
-  __syncthreads();
-  for (u32 key = lane; key <= max_key; key += 64) {   // the winner's list (lane = key)
-    const u64 L = long64[key];
-    if (!L) continue;
-    const u32 t = 0xFFFFFFu - (u32)((L >> 16) & 0xFFFFFFu), k = 0xFFFFu - (u32)(L & 0xFFFFu);
-    const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-    u32 i = 0; Mop m = next_mop(w, wn, i);
-    for (u32 e_k = 0; e_k < k && i < wn; e_k++) m = next_mop(w, wn, i);
-    longest[key] = ((m.len + 1u) << 24) | (u32)(m.list - pay);
-  }
-
-  // realtime order in closed form: sm[j] = earliest :ok completion among transactions j .. n-1 (smf[j]: how many transactions were
-  // invoked before that completion)
-  {
-    u64 carry = ~0ull;
-    for (int b = (int)((n + 63u) / 64u) - 1; b >= 0; b--) {
-      const u32 t = (u32)b * 64u + lane;
-      u64 v = (t < n && TYPE(t) == MSIM_T_OK) ? (((u64)t_cmp[t] << 32) | t_first[t]) : ~0ull;
-      for (int o = 1; o < 64; o <<= 1) {
-        const u32 ylo = (u32)__shfl_down((int)(u32)v, o), yhi = (u32)__shfl_down((int)(u32)(v >> 32), o);
-        const u64 y = ((u64)yhi << 32) | ylo;
-        if (lane + (u32)o < 64u) v = min(v, y);
-      }
-      v = min(v, carry);
-      if (t < n) { sm[t] = (u32)(v >> 32); smf[t] = (u32)v; }
-      carry = ((u64)t_rl((u32)(v >> 32), 0) << 32) | t_rl((u32)v, 0);
-    }
-    if (lane == 0) { sm[n] = NONE; smf[n] = n; }
-  }
-  __syncthreads();
-
-  // ---- E: edges: pass 0 counts degrees, pass 1 fills the CSR and its reverse ------------------------------------------------------------
-  u32 n_edges = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    u32 my_edges = 0;
-#define ADD(a_, b_, kind_) do { const u32 ea = (a_), eb = (b_); if (ea != eb) { if (pass == 0) { atomicAdd(&off[ea], 1u); atomicAdd(&roff[eb], 1u); my_edges++; } \
-      else { adj[off[ea] + atomicAdd(&cur[ea], 1u)] = eb | ((kind_) << 28); radj[roff[eb] + atomicAdd(&rcur[eb], 1u)] = ea | ((kind_) << 28); } } } while (0)
-    for (u32 key = lane; key <= max_key; key += 64) {   // ww along each key's version order (lane = key)
-      const u32 L = longest[key];
-      if (L == 0) continue;
-      const u32 len = (L >> 24) - 1u; const u32 *ord = pay + (L & 0xFFFFFFu);
-      for (u32 i = 0; i + 1 < len; i++) {
-        const u32 a = WRITER(key, elem(ord, i)), b = WRITER(key, elem(ord, i + 1));
-        if (a == NONE || b == NONE) continue;
-        const bool fa = TYPE(a) == MSIM_T_FAIL, fb = TYPE(b) == MSIM_T_FAIL;
-        if (fa && !fb) anomalies |= MSIM_ANOMALY_DIRTY_UPDATE;
-        if (!fa && !fb) ADD(a, b, E_WW);
-      }
-    }
-    for (u32 t = lane; t < n; t += 64) {   // wr / rw per read of an :ok transaction; its realtime successors
-      if (TYPE(t) != MSIM_T_OK) continue;
-      const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-      for (u32 i = 0; i < wn;) {
-        const Mop m = next_mop(w, wn, i);
-        if (m.f) continue;
-        const u32 L = longest[m.key];
-        if (L == 0) continue;   // (an :ok read always left one)
-        const u32 llen = (L >> 24) - 1u; const u32 *ord = pay + (L & 0xFFFFFFu);
-        bool pre = m.len <= llen;
-        if (pre) for (u32 e = 0; e < m.len; e++) pre &= elem(m.list, e) == elem(ord, e);
-        if (!pre) { anomalies |= MSIM_ANOMALY_INCOMPATIBLE_ORDER; continue; }
-        u32 ext = m.len;
-        while (ext > 0 && WRITER(m.key, elem(m.list, ext - 1)) == t) ext--;
-        if (ext > 0) { const u32 wr = WRITER(m.key, elem(m.list, ext - 1)); if (wr != NONE && TYPE(wr) != MSIM_T_FAIL) ADD(wr, t, E_WR); }
-        if (m.len < llen) { const u32 wr = WRITER(m.key, elem(ord, m.len)); if (wr != NONE && TYPE(wr) != MSIM_T_FAIL) ADD(t, wr, E_RW); }   // anti-dependency
-      }
-      const u32 first = t_first[t];                          // the transactions invoked after t completed start here ...
-      const u32 last = sm[first] == NONE ? n : smf[first];   // ... and end where the first of them to complete :ok did
-      for (u32 v = first; v < last; v++) if (TYPE(v) != MSIM_T_FAIL) ADD(t, v, E_RT);
-    }
-#undef ADD
-    __syncthreads();
-    if (pass == 0) {
-      n_edges = t_sum(my_edges);
-      if (n_edges > p.emax) TO_HOST();
-      for (int which = 0; which < 2; which++) {   // out-degrees / in-degrees -> offsets (exclusive prefix sums, 64 at a time)
-        u32 *const o = which ? roff : off;
-        u32 carry = 0;
-        for (u32 base = 0; base <= n; base += 64) {
-          const u32 t = base + lane;
-          const u32 d = t < n ? o[t] : 0u;
-          const u32 ex = t_excl_scan(d, lane);
-          if (t <= n) o[t] = carry + ex;
-          carry += t_sum(d);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  anomalies = t_or(anomalies);
-  const CycleParams cp = {p.out, p.cm, p.proscribed, p.ccap, p.big};
-  cycle_classify(cp, hist, res, anomalies, n, n_edges, flags, c_ok, deg, off, adj, roff, radj, st, jump, queue, reach);
-#undef TO_HOST
-#undef WRITER
-#undef TYPE
+  constexpr bool EXPLAIN = false;
+#include "txn_classify_body.inc"
+}
+__global__ void __launch_bounds__(64) txn_explain_kernel(const TParams p) {
+  constexpr bool EXPLAIN = true;
+#include "txn_classify_body.inc"
 }
 
 // words of workspace per history: the tables of txn_check_kernel / the per-transaction words of txn_check_lds_kernel
 uint64_t ws_words_for(u32 nmax, u32 emax) { return (uint64_t)nmax * 11 + 4 + KMAX + WMAX + emax; }
 uint64_t ws_words_lds(u32 nmax) { return (uint64_t)nmax * 6 + 8; }
 uint64_t ws_words_classify(u32 nmax, u32 emax) { return ((uint64_t)nmax * 16 + 4 + 3 * KMAX + WMAX + 2 * (uint64_t)emax + 1) & ~1ull; }   // txn_classify_kernel (even: 64-bit tables)
+uint64_t ws_words_explain(u32 nmax, u32 emax) { return ((uint64_t)nmax * 17 + 4 + 3 * KMAX + WMAX + 2 * (uint64_t)emax + 1) & ~1ull; }    // txn_explain_kernel: and t_inv
 
 // LDS of a workgroup of txn_check_lds_kernel: what a history of `nmax` transactions over `keys` keys with elements below `stride`
 // needs with 4.5 dependency edges per transaction, at most 78 KiB (two workgroups per CU)
@@ -1158,7 +929,13 @@ int grow_ws(msim_ctx *ctx, void **ws_buf, size_t *ws_cap, size_t need) {
 // classify: what the two passes cannot prove clean goes to txn_classify_kernel, and only what that one hands on to the host
 // (msim_classify_txn_batch, msim_set_check_classify); otherwise to the host at once
 int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-                void **ws_buf, size_t *ws_cap, bool classify = false) {
+                void **ws_buf, size_t *ws_cap, bool classify = false, msim_cycle_result *h_cycles = nullptr, msim_cycle_step *h_steps = nullptr) {
+  // h_cycles / h_steps (msim_explain_txn*; with classify): the witness cycles, found by txn_explain_kernel in tp.cycles / tp.steps
+  const bool explain = classify && h_cycles != nullptr;
+  if (explain) {   // a history the clean passes prove clean keeps the zero record
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(tp.cycles, 0, (size_t)n * sizeof(msim_cycle_result), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(tp.steps, 0, (size_t)n * tp.max_steps * sizeof(msim_cycle_step), st));
+  }
   const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   // Which kernel takes the first pass: the one with its tables in LDS, a workgroup of sixteen wavefronts per history.  Measured on cfg5,
   // 32768 histories (profiles/r03b_cfg5_txn_check_*, r03k_cfg5_txn_check.txt, r03x_txn_check.txt): tables in an HBM workspace, one
@@ -1225,7 +1002,7 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     const u32 m = (u32)todo.size();
     const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
     tp.emax *= 2;   // (a clean history has few edges per transaction; one without isolation has more)
-    tp.ws_words = ws_words_classify(tp.nmax, tp.emax);
+    tp.ws_words = explain ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
     tp.cm = cm; tp.proscribed = msim_proscribed_anomalies(cm);
     // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
     // histories reach the search (as for rw_classify_kernel)
@@ -1239,7 +1016,8 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     u32 launches = 0;
     for (u32 first = 0; first < m; first += chunk, launches++) {
       tp.first = first;
-      hipLaunchKernelGGL(txn_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, tp);
+      if (explain) hipLaunchKernelGGL(txn_explain_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, tp);
+      else hipLaunchKernelGGL(txn_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, tp);
       MSIM_HIP_TRY(ctx, hipGetLastError());
     }
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
@@ -1247,6 +1025,11 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     todo.clear();
     for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST || h_out[i].valid == NEEDS_HBM) todo.push_back(i);
     if (trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, ms(), todo.size());
+  }
+  if (explain) {
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, tp.cycles, (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, tp.steps, (size_t)n * tp.max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   }
   if (!todo.empty()) {
     std::vector<uint64_t> ro, po;
@@ -1269,8 +1052,10 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
       th.emplace_back([&, w]() {
         for (size_t k = w; k < todo.size(); k += nt) {
           const u32 i = todo[k];
-          msim_txn_check_instance_host(rows[k].data(), hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), pays[k].data(),
-                                       hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]), hmeta ? (*hmeta)[i].flags : 0u, cm, &h_out[i]);
+          const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
+          if (explain) msim_txn_explain_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, cm, &h_out[i], &h_cycles[i],
+                                                      h_steps + (size_t)i * tp.max_steps, tp.max_steps, false);
+          else msim_txn_check_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, cm, &h_out[i]);
         }
       });
     for (auto &x : th) x.join();
@@ -1284,7 +1069,9 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
 }  // namespace
 
 // msim_check for txn-list-append: the histories of the last run, where they lie in HBM.
-int msim_check_txn_device(msim_ctx *ctx) {
+// (cycles / steps / max_steps: msim_explain_txn's witness cycles, a slab of max_steps per history, with the full analysis on the device
+// whatever msim_set_check_classify says; null / null / 0: the plain check)
+int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
@@ -1300,9 +1087,17 @@ int msim_check_txn_device(msim_ctx *ctx) {
   tp.max_rows = ctx->cfg.max_rows; tp.max_pay = ctx->cfg.max_payload_words;
   tp.nmax = ctx->cfg.max_rows / 2 + 1; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
   tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
+  tp.cycles = nullptr; tp.steps = nullptr; tp.max_steps = max_steps;
   tp.lds_bytes = lds_bytes_for(tp.nmax, ctx->cfg.max_values, ctx->cfg.max_writes_per_key + 1);
+  struct Slabs { void *c = nullptr, *s = nullptr; ~Slabs() { if (c) (void)msim_dev_free(c); if (s) (void)msim_dev_free(s); } } slabs;
+  if (cycles) {
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.c, (size_t)n * sizeof(msim_cycle_result)));
+    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.s, (size_t)n * max_steps * sizeof(msim_cycle_step)));
+    tp.cycles = static_cast<msim_cycle_result *>(slabs.c); tp.steps = static_cast<msim_cycle_step *>(slabs.s);
+  }
   u32 redone = 0;
-  int rc = txn_dev_run(ctx, tp, n, ctx->cfg.consistency_model, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->check_classify);
+  int rc = txn_dev_run(ctx, tp, n, ctx->cfg.consistency_model, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
+                       ctx->check_classify || cycles, cycles, steps);
   if (rc != MSIM_OK) return rc;
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
@@ -1313,7 +1108,8 @@ int msim_check_txn_device(msim_ctx *ctx) {
 // Checks `n_histories` list-append histories given on the host (rows / payload words of history i at row_offsets[i] /
 // payload_offsets[i]) with the device pass of msim_check on HIP device `device`; out[i] as msim_check_txn_rows would fill it.
 static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
-                     uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool classify) {
+                     uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool classify,
+                     msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
   msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
@@ -1322,12 +1118,15 @@ static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offset
   u32 max_r = 1;
   for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0x7FFFFFFFull) return MSIM_E_RANGE; if (c > max_r) max_r = (u32)c; }
   msim_op *d_rows = nullptr; u32 *d_pay = nullptr; uint64_t *d_ro = nullptr, *d_po = nullptr; msim_check_result *d_out = nullptr; void *ws = nullptr; size_t ws_cap = 0;
+  msim_cycle_result *d_cycles = nullptr; msim_cycle_step *d_steps = nullptr;
   int rc = MSIM_E_HIP;
   do {
     if (msim_dev_malloc(&d_rows, (size_t)(tr ? tr : 1) * sizeof(msim_op)) != hipSuccess) break;
     if (msim_dev_malloc(&d_pay, (size_t)(tw ? tw : 1) * 4) != hipSuccess) break;
     if (msim_dev_malloc(&d_ro, (size_t)(n_histories + 1) * 8) != hipSuccess || msim_dev_malloc(&d_po, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
     if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
+    if (cycles && (msim_dev_malloc(&d_cycles, (size_t)n_histories * sizeof(msim_cycle_result)) != hipSuccess ||
+                   msim_dev_malloc(&d_steps, (size_t)n_histories * max_steps * sizeof(msim_cycle_step)) != hipSuccess)) break;
     if (tr && hipMemcpy(d_rows, rows, (size_t)tr * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
     if (tw && hipMemcpy(d_pay, payload, (size_t)tw * 4, hipMemcpyHostToDevice) != hipSuccess) break;
     if (hipMemcpy(d_ro, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
@@ -1336,10 +1135,11 @@ static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offset
     tp.rows = d_rows; tp.payload = d_pay; tp.meta = nullptr; tp.row_off = d_ro; tp.pay_off = d_po; tp.out = d_out;
     tp.max_rows = 0; tp.max_pay = 0; tp.nmax = max_r / 2 + 65; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
   tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
+    tp.cycles = d_cycles; tp.steps = d_steps; tp.max_steps = max_steps;
     tp.lds_bytes = lds_bytes_for(tp.nmax, std::min<u32>(KMAX, tp.nmax * 2 + 16), 17);
-    rc = txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, &ws, &ws_cap, classify);
+    rc = txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, &ws, &ws_cap, classify, cycles, steps);
   } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, ws}) if (q) (void)msim_dev_free(q);
+  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, (void *)d_cycles, (void *)d_steps, ws}) if (q) (void)msim_dev_free(q);
   return rc;
 }
 
@@ -1353,4 +1153,21 @@ extern "C" int msim_check_txn_batch(int device, const msim_op *rows, const uint6
 extern "C" int msim_classify_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                                        uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host) {
   return txn_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true);
+}
+
+// msim_classify_txn_batch with the witness cycles (txn_explain_kernel; include/maelsim.h msim_cycle_result).
+extern "C" int msim_explain_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                      uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host,
+                                      msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+  if (!cycles || !steps || max_steps == 0) return MSIM_E_INVALID;
+  return txn_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true, cycles, steps, max_steps);
+}
+
+extern "C" int msim_explain_txn(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, uint32_t n_out) {
+  if (!ctx || !cycles || !steps || max_steps == 0) return MSIM_E_INVALID;
+  const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
+  if (!rw && ctx->cfg.workload != MSIM_WL_TXN_LIST_APPEND) { ctx->err = "msim_explain_txn: not a txn-list-append or txn-rw-register context"; return MSIM_E_UNSUPPORTED; }
+  if (!ctx->ran) { ctx->err = "msim_explain_txn before msim_run"; return MSIM_E_RANGE; }
+  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_txn: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  return rw ? msim_check_rw_device(ctx, cycles, steps, max_steps) : msim_check_txn_device(ctx, cycles, steps, max_steps);
 }

@@ -22,6 +22,8 @@ CHECK_DT = np.dtype([("valid", "<u4"), ("attempt_count", "<u4"), ("stable_count"
                      ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4")])
 LIN_KEY_DT = np.dtype([("key", "<u4"), ("valid", "<u4"), ("op_row", "<u4"), ("previous_ok_row", "<u4"), ("n_pending", "<u4"), ("n_values", "<u4"),
                        ("values", "u1", (8,))])   # msim_lin_key_result
+CYCLE_DT = np.dtype([("anomalies", "<u4"), ("length", "<u4"), ("n_steps", "<u4"), ("reserved", "<u4")])        # msim_cycle_result
+CYCLE_STEP_DT = np.dtype([("txn", "<u4"), ("inv_row", "<u4"), ("cmp_row", "<u4"), ("kinds", "<u4")])          # msim_cycle_step
 LATENCY_DT = np.dtype([("count", "<u4"), ("q_us", "<u4", (5,)), ("sum_us", "<u8")])
 F_STATS_DT = np.dtype([("f", "<u4"), ("valid", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
                        ("unpaired", "<u4"), ("reserved", "<u4"), ("latency", LATENCY_DT, (3,))])
@@ -171,6 +173,16 @@ class Engine:
         self._chk(self.lib.msim_explain_lin_kv(self._ctx, keys.ctypes.data, max_keys, nk.ctypes.data, self.n), "msim_explain_lin_kv")
         res = self.check_results()
         return [(res[i], keys[i, :min(int(nk[i]), max_keys)].copy()) for i in range(self.n)]
+
+    def explain_txn(self, max_steps=64):
+        """txn-list-append / txn-rw-register: check(classify=True) that also explains (msim_explain_txn): per history of the last run
+        (CHECK_DT record — check_results() holds the same afterwards —, CYCLE_DT record, CYCLE_STEP_DT steps: the witness cycle of the
+        record's cycle class as include/maelsim.h defines it; see txn_cycle_analysis), found on the device."""
+        cycles = np.zeros(self.n, dtype=CYCLE_DT)
+        steps = np.zeros((self.n, max_steps), dtype=CYCLE_STEP_DT)
+        self._chk(self.lib.msim_explain_txn(self._ctx, cycles.ctypes.data, steps.ctypes.data, max_steps, self.n), "msim_explain_txn")
+        res = self.check_results()
+        return [(res[i], cycles[i], steps[i, :int(cycles[i]["n_steps"])].copy()) for i in range(self.n)]
 
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
@@ -928,6 +940,79 @@ def classify_txn_batch(histories, consistency_model="strict-serializable", devic
     Each record is what check_txn_batch gives, judged under `consistency_model`; the host analysis only takes what exceeds the device
     capacities.  Returns (CHECK_DT records, how many histories went to the host)."""
     return check_rw_batch(histories, consistency_model, device, _entry="msim_classify_txn_batch")
+
+
+def explain_txn_history(rows, payload, consistency_model="strict-serializable", max_steps=64, _entry="msim_explain_txn_rows"):
+    """The host list-append analysis of one history with the witness cycle of its cycle class (msim_explain_txn_rows; include/maelsim.h
+    msim_cycle_result) -> (CHECK_DT record, CYCLE_DT record, CYCLE_STEP_DT steps, the first min(length, max_steps) of the cycle)."""
+    rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    out = np.zeros(1, dtype=CHECK_DT)
+    cycle = np.zeros(1, dtype=CYCLE_DT)
+    steps = np.zeros(max_steps, dtype=CYCLE_STEP_DT)
+    rc = getattr(A.load(), _entry)(rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), CONSISTENCY_MODELS[consistency_model],
+                                   out.ctypes.data_as(C.POINTER(A.CheckResult)), cycle.ctypes.data, steps.ctypes.data, max_steps)
+    if rc:
+        raise EngineError(f"{_entry}: {rc}")
+    return out[0], cycle[0], steps[:int(cycle[0]["n_steps"])].copy()
+
+
+def explain_rw_history(rows, payload, consistency_model="strict-serializable", max_steps=64):
+    """The same for one rw-register history (msim_explain_rw_rows)."""
+    return explain_txn_history(rows, payload, consistency_model, max_steps, _entry="msim_explain_rw_rows")
+
+
+def explain_txn_batch(histories, consistency_model="strict-serializable", device=0, max_steps=64, _entry="msim_explain_txn_batch"):
+    """txn-list-append: classify_txn_batch with the witness cycles found on the device (msim_explain_txn_batch).  Returns (CHECK_DT
+    records, CYCLE_DT records, a list of CYCLE_STEP_DT arrays — the steps written per history —, how many histories went to the host).
+    The whole zero-padded slab of steps is the returned list's `.slab` ((histories, max_steps))."""
+    rs = [np.ascontiguousarray(h[0]) for h in histories]
+    ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
+    ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
+    po = np.zeros(len(ps) + 1, dtype=np.uint64); po[1:] = np.cumsum([len(x) for x in ps])
+    rows = np.concatenate(rs) if rs else np.zeros(0, dtype=OP_DT)
+    pay = np.concatenate(ps) if ps else np.zeros(0, dtype=np.uint32)
+    if len(pay) == 0:
+        pay = np.zeros(1, dtype=np.uint32)
+    out = np.zeros(len(rs), dtype=CHECK_DT)
+    cycles = np.zeros(len(rs), dtype=CYCLE_DT)
+    slab = np.zeros((len(rs), max_steps), dtype=CYCLE_STEP_DT)
+    n_host = C.c_uint32()
+    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs),
+                                   CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host), cycles.ctypes.data, slab.ctypes.data, max_steps)
+    if rc:
+        raise EngineError(f"{_entry}: {rc}")
+    steps = _StepLists(slab[i, :int(cycles[i]["n_steps"])].copy() for i in range(len(rs)))
+    steps.slab = slab
+    return out, cycles, steps, n_host.value
+
+
+class _StepLists(list):
+    """explain_txn_batch's list of step arrays; `.slab` is the whole zero-padded array the entry wrote"""
+
+
+def explain_rw_batch(histories, consistency_model="read-committed", device=0, max_steps=64):
+    """txn-rw-register: classify_rw_batch with the witness cycles found on the device (msim_explain_rw_batch); as explain_txn_batch."""
+    return explain_txn_batch(histories, consistency_model, device, max_steps, _entry="msim_explain_rw_batch")
+
+
+def txn_cycle_analysis(rows, payload, cycle, steps, n_nodes=0, rw=False):
+    """elle's :anomalies map for the witness cycle of one history (pure formatting): {"anomalies": {"G-single-realtime": [{"cycle":
+    [ops ...], "steps": [{"type": "rw"}, ...]}]}} — the cycle's ops are the transactions' completions as decode_history gives them (the
+    invocation where one never completed), a step's type the strongest-first name of its kinds ("ww", "wr", "rw", "realtime"; "types"
+    lists all of them where parallel edges were merged).  No cycle: {"anomalies": {}}.  A witness longer than the steps given is
+    marked "truncated": its true length.  Not reported: the :key / :value of a step, witnesses of the non-cycle anomalies."""
+    bits = int(cycle["anomalies"])
+    if not bits:
+        return {"anomalies": {}}
+    name = next(n for b, n in A.ANOMALIES.items() if bits & b & 0x39) + ("-realtime" if bits & 512 else "")
+    ops = decode_history(rows, payload, n_nodes, A.WL_TXN_RW_REGISTER if rw else A.WL_TXN_LIST_APPEND)
+    entry = {"cycle": [ops[int(s["inv_row"] if int(s["cmp_row"]) == A.NO_VALUE else s["cmp_row"])] for s in steps],
+             "steps": [dict({"type": next(n for b, n in A.EDGE_KINDS.items() if int(s["kinds"]) & b)},
+                            **({"types": [n for b, n in A.EDGE_KINDS.items() if int(s["kinds"]) & b]} if bin(int(s["kinds"])).count("1") > 1 else {}))
+                       for s in steps]}
+    if int(cycle["length"]) > len(steps):
+        entry["truncated"] = int(cycle["length"])
+    return {"anomalies": {name: [entry]}}
 
 
 def anomaly_census(results):
