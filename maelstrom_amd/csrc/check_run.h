@@ -1,0 +1,210 @@
+// check_run.h — the host side the device checkers share (lin / txn / rw / kafka / pn / unique / perf _check_dev.hip): device buffers
+// that free themselves, the grow-only workspace, a caller's histories uploaded, the chunked launch loop, the hand-off of what the
+// device leaves to the host checkers, the frame of msim_check_*_device.  Host only: nothing here is seen by a kernel.  A new checker
+// mode supplies its kernel launch and its host callable; docs/KERNELS.md, "the host side of the device checkers".
+#ifndef MSIM_CHECK_RUN_H
+#define MSIM_CHECK_RUN_H
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "engine_internal.h"
+
+// A device allocation of msim_dev_malloc that is freed with its owner (move-only).
+class DevBuf {
+  void *p_ = nullptr;
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+  ~DevBuf() { reset(); }
+  void reset() { if (p_) (void)msim_dev_free(p_); p_ = nullptr; }
+  hipError_t alloc(size_t bytes) { reset(); return msim_dev_malloc(&p_, bytes); }
+  // room for `bytes` (at least one row's) with src's `bytes` copied there
+  hipError_t upload(const void *src, size_t bytes) {
+    const hipError_t e = alloc(bytes ? bytes : sizeof(msim_op));
+    return e == hipSuccess && bytes ? hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) : e;
+  }
+  template <typename T> T *get() const { return static_cast<T *>(p_); }
+  void **addr() { return &p_; }   // for grow_ws
+};
+
+// the grow-only workspace: *buf holds at least `need` bytes afterwards (what it held before is not kept)
+static inline int grow_ws(msim_ctx *ctx, void **buf, size_t *cap, size_t need) {
+  if (*cap >= need) return MSIM_OK;
+  if (*buf) (void)msim_dev_free(*buf);
+  *buf = nullptr; *cap = 0;
+  MSIM_HIP_TRY(ctx, msim_dev_malloc(buf, need));
+  *cap = need;
+  return MSIM_OK;
+}
+
+// a batch entry's stand-in for the context of a run: only for error text (and the device lin-kv's host workers select)
+struct BatchCtx : msim_ctx { explicit BatchCtx(int dev) { device = dev; } };
+
+// A caller's histories in the offsets layout, on the device: rows (payload words) of history i at row_offsets[i] (payload_offsets[i]).
+struct OffsetsBatch {
+  DevBuf rows, pay, row_off, pay_off;
+  u32 longest = 1;   // rows of the longest history (at least 1)
+  // MSIM_E_RANGE: a history of more than `limit` rows (`pay_limit` payload words; 0: not looked at).  payload_offsets null: rows only.
+  int upload(msim_ctx *ctx, const msim_op *h_rows, const uint64_t *row_offsets, const u32 *payload, const uint64_t *payload_offsets, u32 n,
+             uint64_t limit, uint64_t pay_limit = 0) {
+    for (u32 i = 0; i < n; i++) {
+      const uint64_t c = row_offsets[i + 1] - row_offsets[i];
+      if (c > limit || (pay_limit && payload_offsets[i + 1] - payload_offsets[i] > pay_limit)) return MSIM_E_RANGE;
+      if (c > longest) longest = (u32)c;
+    }
+    MSIM_HIP_TRY(ctx, rows.upload(h_rows, (size_t)row_offsets[n] * sizeof(msim_op)));
+    MSIM_HIP_TRY(ctx, row_off.upload(row_offsets, (size_t)(n + 1) * 8));
+    if (!payload_offsets) return MSIM_OK;
+    MSIM_HIP_TRY(ctx, pay.upload(payload, payload ? (size_t)payload_offsets[n] * 4 : 0));
+    MSIM_HIP_TRY(ctx, pay_off.upload(payload_offsets, (size_t)(n + 1) * 8));
+    return MSIM_OK;
+  }
+};
+
+// A caller's histories in the slab layout, on the device: history i in rows + i * max_rows, n_rows[i] of them used; the
+// msim_inst_meta records of a run made up for them.
+struct SlabBatch {
+  DevBuf rows, meta;
+  int upload(msim_ctx *ctx, const msim_op *h_rows, const u32 *n_rows, u32 max_rows, u32 n) {   // MSIM_E_RANGE: n_rows[i] > max_rows
+    std::vector<msim_inst_meta> hm(n);
+    for (u32 i = 0; i < n; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
+    MSIM_HIP_TRY(ctx, rows.upload(h_rows, (size_t)n * max_rows * sizeof(msim_op)));
+    MSIM_HIP_TRY(ctx, meta.upload(hm.data(), (size_t)n * sizeof(msim_inst_meta)));
+    return MSIM_OK;
+  }
+};
+
+// histories per launch: as many as `budget` bytes of workspace hold at `bytes_per_history`; MSIM_DEV_FLAGS bit 16 (0x10000): at most 7,
+// so that small batches reach the chunk loops (a partial last chunk, first > 0)
+static inline u32 chunk_for(u32 n, uint64_t bytes_per_history, uint64_t budget, uint32_t flags) {
+  return (u32)std::min<uint64_t>({n, (flags & 0x10000u) ? 7 : ~0ull, std::max<uint64_t>(1, budget / bytes_per_history)});
+}
+
+// launch(first, count) for every chunk of n, until one fails (*err); returns the launches made
+template <class F> static inline u32 for_chunks(u32 n, u32 chunk, hipError_t *err, F launch) {
+  u32 launches = 0;
+  *err = hipSuccess;
+  for (u32 first = 0; first < n && *err == hipSuccess; first += chunk, launches++) { launch(first, std::min(chunk, n - first)); *err = hipGetLastError(); }
+  return launches;
+}
+
+// the histories whose record says pred(valid): what the next pass (or the host) still has to do
+template <class P> static inline std::vector<u32> needs(const msim_check_result *h_out, u32 n, P pred) {
+  std::vector<u32> todo;
+  for (u32 i = 0; i < n; i++) if (pred(h_out[i].valid)) todo.push_back(i);
+  return todo;
+}
+
+// developer: the passes' times on stderr (MSIM_DEV_FLAGS bit 12)
+struct PassTimer {
+  const bool trace;
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  explicit PassTimer(const msim_ctx *ctx) : trace((msim_dev_flags(ctx) & 0x1000u) != 0) {}
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Where n histories lie on the device: the slabs of a run with the meta records on the host (hmeta), or a caller's offsets.
+struct HistorySource {
+  const msim_op *rows; const u32 *payload;   // payload null: rows only
+  const std::vector<msim_inst_meta> *hmeta; u32 max_rows, max_pay;
+  const uint64_t *row_off, *pay_off;
+};
+// (of a checker's *Params: they name these alike)
+template <class P> static inline HistorySource source_of(const P &p, const std::vector<msim_inst_meta> *hmeta) {
+  return HistorySource{p.rows, p.payload, hmeta, p.max_rows, p.max_pay, p.row_off, p.pay_off};
+}
+
+// The hand-off: the rows and payload words of the histories `todo` come to the host, analyse(rows, n_rows, payload, n_words, flags, i)
+// — which writes h_out[i] — runs on up to msim_host_threads() threads, the finished records go back to d_out + i.
+template <class F>
+static inline int hand_off(msim_ctx *ctx, const HistorySource &s, u32 n, const std::vector<u32> &todo, const msim_check_result *h_out, msim_check_result *d_out, F analyse) {
+  if (todo.empty()) return MSIM_OK;
+  std::vector<uint64_t> ro, po;
+  if (!s.hmeta) {
+    ro.resize(n + 1); po.resize(n + 1);
+    MSIM_HIP_TRY(ctx, hipMemcpy(ro.data(), s.row_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+    if (s.payload) MSIM_HIP_TRY(ctx, hipMemcpy(po.data(), s.pay_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  auto n_rows = [&](u32 i) { return s.hmeta ? (*s.hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]); };
+  auto n_words = [&](u32 i) { return !s.payload ? 0u : s.hmeta ? (*s.hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]); };
+  std::vector<std::vector<msim_op>> rows(todo.size());
+  std::vector<std::vector<u32>> pays(todo.size());
+  for (size_t k = 0; k < todo.size(); k++) {
+    const u32 i = todo[k], nr = n_rows(i), nw = n_words(i);
+    rows[k].resize(nr ? nr : 1); pays[k].resize(nw ? nw : 1);
+    if (nr) MSIM_HIP_TRY(ctx, hipMemcpy(rows[k].data(), s.rows + (s.hmeta ? (uint64_t)i * s.max_rows : ro[i]), (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost));
+    if (nw) MSIM_HIP_TRY(ctx, hipMemcpy(pays[k].data(), s.payload + (s.hmeta ? (uint64_t)i * s.max_pay : po[i]), (size_t)nw * 4, hipMemcpyDeviceToHost));
+  }
+  unsigned nt = msim_host_threads();
+  if (nt > todo.size()) nt = (unsigned)todo.size();
+  std::vector<std::thread> th;
+  for (unsigned w = 0; w < nt; w++)
+    th.emplace_back([&, w]() {
+      for (size_t k = w; k < todo.size(); k += nt) {
+        const u32 i = todo[k];
+        analyse(rows[k].data(), n_rows(i), pays[k].data(), n_words(i), s.hmeta ? (*s.hmeta)[i].flags : 0u, i);
+      }
+    });
+  for (auto &x : th) x.join();
+  for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(d_out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
+  return MSIM_OK;
+}
+
+// The witness cycles of an explaining rw / txn check: the two device slabs (a cycle record, max_steps steps per history), cleared on the
+// stream before the passes and copied to the caller's arrays behind them.
+struct WitnessSlabs {
+  DevBuf c, s;
+  u32 n = 0, max_steps = 0;
+  msim_cycle_result *h_cycles = nullptr; msim_cycle_step *h_steps = nullptr;
+  int alloc(msim_ctx *ctx, u32 n_, u32 max_steps_, msim_cycle_result *cycles, msim_cycle_step *steps) {
+    n = n_; max_steps = max_steps_; h_cycles = cycles; h_steps = steps;
+    MSIM_HIP_TRY(ctx, c.alloc((size_t)n * sizeof(msim_cycle_result)));
+    MSIM_HIP_TRY(ctx, s.alloc((size_t)n * max_steps * sizeof(msim_cycle_step)));
+    return MSIM_OK;
+  }
+  template <class P> void bind(P &p) const { p.cycles = c.get<msim_cycle_result>(); p.steps = s.get<msim_cycle_step>(); p.max_steps = max_steps; }
+  int clear(msim_ctx *ctx, hipStream_t st) {
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(c.get<void>(), 0, (size_t)n * sizeof(msim_cycle_result), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(s.get<void>(), 0, (size_t)n * max_steps * sizeof(msim_cycle_step), st));
+    return MSIM_OK;
+  }
+  int fetch(msim_ctx *ctx, hipStream_t st) {
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, c.get<void>(), (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, s.get<void>(), (size_t)n * max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return MSIM_OK;
+  }
+};
+
+// how rw_dev_run / txn_dev_run go beyond the clean passes: `full` the classification on the device; with `witness` its EXPLAIN kernel
+struct CycleMode {
+  bool full = false;
+  WitnessSlabs *witness = nullptr;
+};
+
+// The frame of msim_check_{rw,txn,kafka,pn}_device.  begin_check: the pinned records of the run anew; with `hm`, the meta records on the
+// host — behind the context's stream: the simulation may still be running (msim_run_async), the context's stream does not block against
+// the null stream, so the copy of the meta is ordered behind it here and by nothing else.  Returns in *t0 where check_ms starts.
+static inline int begin_check(msim_ctx *ctx, std::chrono::steady_clock::time_point *t0, std::vector<msim_inst_meta> *hm) {
+  const u32 n = ctx->n_inst;
+  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
+  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
+  if (hm) MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *t0 = std::chrono::steady_clock::now();
+  if (hm) { hm->resize(n); MSIM_HIP_TRY(ctx, hipMemcpy(hm->data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost)); }
+  return MSIM_OK;
+}
+static inline void finish_check(msim_ctx *ctx, std::chrono::steady_clock::time_point t0, u32 redone) {
+  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->lin_host_rechecks = redone;
+  ctx->checked = true; ctx->check_fetched = true;
+}
+
+#endif

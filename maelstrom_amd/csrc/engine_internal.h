@@ -1,4 +1,6 @@
-// engine_internal.h — private to libmaelsim (engine.hip, checker.hip).
+// engine_internal.h — private to libmaelsim: engine.hip and the simulation kernels' units (through sim_kernels.h / wave_common.h),
+// checker.hip, the host checkers (lin_check.cpp, txn_check.cpp, kafka_check.cpp, pn_check.cpp), the device checkers (through
+// check_run.h), gather.cpp, guard.cpp.
 #ifndef MSIM_ENGINE_INTERNAL_H
 #define MSIM_ENGINE_INTERNAL_H
 

@@ -25,13 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out);   // kafka_check.cpp
 
@@ -480,19 +478,17 @@ __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *
 // classify: what kafka_check_kernel cannot prove clean goes to kafka_classify_kernel first, and only what THAT hands over to the host
 int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
                   bool classify = false) {
-  const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  const PassTimer tm(ctx);
   u32 h_bound = 0;
   {   // tables no larger than the launch's histories need (kp.T: what the configuration / the checker's own bound allows)
-    u32 *d_bound = nullptr;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&d_bound, 4));
-    hipError_t e = hipMemsetAsync(d_bound, 0, 4, st);
-    if (e == hipSuccess) { hipLaunchKernelGGL(kafka_bound_kernel, dim3(n), dim3(NT), 0, st, kp, d_bound); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_bound, d_bound, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)msim_dev_free(d_bound);
-    MSIM_HIP_TRY(ctx, e);
+    DevBuf bound;
+    MSIM_HIP_TRY(ctx, bound.alloc(4));
+    u32 *const d_bound = bound.get<u32>();
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(d_bound, 0, 4, st));
+    hipLaunchKernelGGL(kafka_bound_kernel, dim3(n), dim3(NT), 0, st, kp, d_bound);
+    MSIM_HIP_TRY(ctx, hipGetLastError());
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(&h_bound, d_bound, 4, hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
     const u32 t = ((h_bound + 1u + 31u) & ~31u);
     if (t < kp.T) kp.T = t < 32u ? 32u : t;
   }
@@ -502,60 +498,38 @@ int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst
   MSIM_HIP_TRY(ctx, hipGetLastError());
   u32 n_unclean = 0;
   if (classify) {   // the histories not proved clean, listed on the device, each to a workgroup of kafka_classify_kernel
-    u32 *d_list = nullptr;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&d_list, ((size_t)n + 1) * 4));
-    hipError_t e = hipMemsetAsync(d_list, 0, 4, st);
-    if (e == hipSuccess) { hipLaunchKernelGGL(kafka_todo_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, kp.out, n, d_list); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(&n_unclean, d_list, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && n_unclean) {
+    DevBuf list;
+    MSIM_HIP_TRY(ctx, list.alloc(((size_t)n + 1) * 4));
+    u32 *const d_list = list.get<u32>();
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(d_list, 0, 4, st));
+    hipLaunchKernelGGL(kafka_todo_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, kp.out, n, d_list);
+    MSIM_HIP_TRY(ctx, hipGetLastError());
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(&n_unclean, d_list, 4, hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (n_unclean) {
       KCParams cp = kp;   // tables for what the launch names (the configuration's bound does not hold for an unclean history), up to what LDS holds
       cp.T = std::min(TC_MAX, std::max(32u, (h_bound + 1u + 31u) & ~31u));
       const size_t clds = kafka_classify_lds_bytes(cp.T);
-      if (clds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_classify_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
-      if (e == hipSuccess) { hipLaunchKernelGGL(kafka_classify_kernel, dim3(n_unclean), dim3(NT), clds, st, cp, d_list + 1); e = hipGetLastError(); }
-      if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the list is freed below)
+      if (clds > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_classify_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
+      hipLaunchKernelGGL(kafka_classify_kernel, dim3(n_unclean), dim3(NT), clds, st, cp, d_list + 1);
+      MSIM_HIP_TRY(ctx, hipGetLastError());
+      MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));   // (the list is freed with this block)
     }
-    (void)msim_dev_free(d_list);
-    MSIM_HIP_TRY(ctx, e);
   }
   MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, kp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::vector<u32> todo;
-  for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-  if (trace) {
+  const std::vector<u32> todo = needs(h_out, n, [](u32 valid) { return valid == NEEDS_HOST; });
+  if (tm.trace) {
     if (classify) std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %u of %u histories classified on the device, %zu of those for the host\n",
-                               lds, ms(), n_unclean, n, todo.size());
-    else std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %zu of %u histories for the host\n", lds, ms(), todo.size(), n);
+                               lds, tm.ms(), n_unclean, n, todo.size());
+    else std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %zu of %u histories for the host\n", lds, tm.ms(), todo.size(), n);
   }
   if (!todo.empty()) {
-    std::vector<uint64_t> ro, po;
-    if (kp.row_off) { ro.resize(n + 1); po.resize(n + 1);
-      MSIM_HIP_TRY(ctx, hipMemcpy(ro.data(), kp.row_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
-      MSIM_HIP_TRY(ctx, hipMemcpy(po.data(), kp.pay_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost)); }
-    std::vector<std::vector<msim_op>> rows(todo.size());
-    std::vector<std::vector<u32>> pays(todo.size());
-    for (size_t k = 0; k < todo.size(); k++) {
-      const u32 i = todo[k];
-      const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
-      rows[k].resize(nr ? nr : 1); pays[k].resize(nw ? nw : 1);
-      if (nr) MSIM_HIP_TRY(ctx, hipMemcpy(rows[k].data(), kp.rows + (hmeta ? (uint64_t)i * kp.max_rows : ro[i]), (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost));
-      if (nw) MSIM_HIP_TRY(ctx, hipMemcpy(pays[k].data(), kp.payload + (hmeta ? (uint64_t)i * kp.max_pay : po[i]), (size_t)nw * 4, hipMemcpyDeviceToHost));
-    }
-    unsigned nt = msim_host_threads();
-    if (nt > todo.size()) nt = (unsigned)todo.size();
-    std::vector<std::thread> th;
-    for (unsigned w = 0; w < nt; w++)
-      th.emplace_back([&, w]() {
-        for (size_t k = w; k < todo.size(); k += nt) {
-          const u32 i = todo[k];
-          msim_kafka_check_instance_host(rows[k].data(), hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), pays[k].data(),
-                                         hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]), hmeta ? (*hmeta)[i].flags : 0u, &h_out[i]);
-        }
-      });
-    for (auto &x : th) x.join();
-    for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(kp.out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
-    if (trace) std::fprintf(stderr, "[kafka-check] host checker on those: done at %.2f ms\n", ms());
+    const int rc = hand_off(ctx, source_of(kp, hmeta), n, todo, h_out, kp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
+      msim_kafka_check_instance_host(rows, nr, pay, nw, flags, &h_out[i]);
+    });
+    if (rc != MSIM_OK) return rc;
+    if (tm.trace) std::fprintf(stderr, "[kafka-check] host checker on those: done at %.2f ms\n", tm.ms());
   }
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
@@ -571,14 +545,9 @@ int msim_check_kafka_device(msim_ctx *ctx) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
   if (ctx->cfg.concurrency == 0 || ctx->cfg.concurrency > CMAX) return msim_check_kafka_host(ctx);
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  // the simulation may still be running (msim_run_async): the context's stream does not block against the null stream, so the copy of
-  // the meta below is ordered behind it here and by nothing else
-  MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<msim_inst_meta> hm(n);
-  MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));
+  std::chrono::steady_clock::time_point t0;
+  std::vector<msim_inst_meta> hm;
+  if (int rc = begin_check(ctx, &t0, &hm)) return rc;
   KCParams kp;
   std::memset(&kp, 0, sizeof kp);
   kp.rows = ctx->d_rows; kp.payload = ctx->d_payload; kp.meta = ctx->d_meta; kp.out = ctx->d_check;
@@ -590,9 +559,7 @@ int msim_check_kafka_device(msim_ctx *ctx) {
   u32 redone = 0;
   int rc = kafka_dev_run(ctx, kp, n, &hm, ctx->h_check, ctx->stream, &redone, ctx->check_classify);
   if (rc != MSIM_OK) return rc;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->lin_host_rechecks = redone;
-  ctx->checked = true; ctx->check_fetched = true;
+  finish_check(ctx, t0, redone);
   return MSIM_OK;
 }
 
@@ -601,31 +568,19 @@ int msim_check_kafka_device(msim_ctx *ctx) {
 static int kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                        uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host, bool classify) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || concurrency == 0 || concurrency > CMAX) return MSIM_E_INVALID;
-  const uint64_t tr = row_offsets[n_histories], tw = payload_offsets[n_histories];
-  if (tw != 0 && !payload) return MSIM_E_INVALID;   // (as msim_check_kafka_rows: payload words announced, none given)
+  if (payload_offsets[n_histories] != 0 && !payload) return MSIM_E_INVALID;   // (as msim_check_kafka_rows: payload words announced, none given)
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
-  tmp_ctx.device = device;
-  for (u32 i = 0; i < n_histories; i++) if (row_offsets[i + 1] - row_offsets[i] > 0x7FFFFFFFull || payload_offsets[i + 1] - payload_offsets[i] > 0x7FFFFFFFull) return MSIM_E_RANGE;
-  msim_op *d_rows = nullptr; u32 *d_pay = nullptr; uint64_t *d_ro = nullptr, *d_po = nullptr; msim_check_result *d_out = nullptr;
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)(tr ? tr : 1) * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_pay, (size_t)(tw ? tw : 1) * 4) != hipSuccess) break;
-    if (msim_dev_malloc(&d_ro, (size_t)(n_histories + 1) * 8) != hipSuccess || msim_dev_malloc(&d_po, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (tr && hipMemcpy(d_rows, rows, (size_t)tr * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (tw && payload && hipMemcpy(d_pay, payload, (size_t)tw * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_ro, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_po, payload_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    KCParams kp;
-    std::memset(&kp, 0, sizeof kp);
-    kp.rows = d_rows; kp.payload = d_pay; kp.row_off = d_ro; kp.pay_off = d_po; kp.out = d_out;
-    kp.T = OFFS; kp.C = concurrency;
-    rc = kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify);
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out}) if (q) (void)msim_dev_free(q);
-  return rc;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  OffsetsBatch b;
+  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull, 0x7FFFFFFFull)) return rc;
+  DevBuf d_out;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  KCParams kp;
+  std::memset(&kp, 0, sizeof kp);
+  kp.rows = b.rows.get<msim_op>(); kp.payload = b.pay.get<u32>(); kp.row_off = b.row_off.get<uint64_t>(); kp.pay_off = b.pay_off.get<uint64_t>();
+  kp.out = d_out.get<msim_check_result>();
+  kp.T = OFFS; kp.C = concurrency;
+  return kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify);
 }
 
 extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,

@@ -34,7 +34,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 void msim_lin_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);   // lin_check.cpp
 void msim_lin_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys, uint32_t max_keys,
@@ -703,10 +703,9 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
   LParams lp = lp0;
   const size_t keys_bytes = xp ? (size_t)n * xp->max_keys * sizeof(msim_lin_key_result) : 0;
   const XParams xp0 = xp ? *xp : XParams{nullptr, 0};
-  const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
   const bool tiny = (msim_dev_flags(ctx) & 0x2000u) != 0;    // developer / tests: pools small enough that every level is reached, the host search included
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  const PassTimer tm(ctx);
+  const bool trace = tm.trace;
   const u32 table_cap = 24u * 1024u;   // rows (51 KiB of LDS)
   lp.table_rows = max_rows_any < table_cap ? max_rows_any : table_cap;
   lp.list = nullptr;
@@ -717,9 +716,10 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
   hp.n_slots = n < 4096u ? n : 4096u;   // (a history claims one when a closure first outgrows the registers; without one it waits for pass 2)
   hp.pool = nullptr; hp.claim = nullptr; hp.trace = trace ? 1u : 0u;
   const size_t ws_bytes = (size_t)hp.n_slots * pool_words(hp.cap, hp.n_heads, hp.out_cap) * 4 + 256;
-  MSIM_HIP_TRY(ctx, msim_dev_malloc(&hp.pool, ws_bytes));
+  DevBuf ws;
+  MSIM_HIP_TRY(ctx, ws.alloc(ws_bytes));
+  hp.pool = ws.get<u32>();
   hp.claim = hp.pool + (ws_bytes - 256) / 4;
-  struct Ws { u32 *p; ~Ws() { if (p) (void)msim_dev_free(p); } } ws_guard{hp.pool};
   MSIM_HIP_TRY(ctx, hipMemsetAsync(hp.claim, 0, 4, st));
   if (xp) {
     MSIM_HIP_TRY(ctx, hipMemsetAsync(xp0.keys, 0, keys_bytes, st));
@@ -734,7 +734,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     { std::vector<u32> us, pc, ad, pt; for (u32 i = 0; i < n; i++) { us.push_back(h_out[i].never_read_count); pc.push_back(h_out[i].stable_latency_ms[3]); pt.push_back(h_out[i].stable_latency_ms[4]); ad.push_back(h_out[i].stable_count); }
       auto q = [&](std::vector<u32> &v, const char *nm) { std::sort(v.begin(), v.end()); std::fprintf(stderr, "[lin-check]   pass 1 %s per history: median %u, 90%% %u, 95%% %u, 97%% %u, 99%% %u, max %u\n", nm, v[v.size() / 2], v[v.size() * 9 / 10], v[v.size() * 95 / 100], v[v.size() * 97 / 100], v[v.size() * 99 / 100], v.back()); };
       q(us, "microseconds"); q(pc, "pool closures"); q(pt, "microseconds in pool closures"); q(ad, "pool entries admitted"); }
-    std::fprintf(stderr, "[lin-check] pass 1 (registers + HBM pools of %u configurations, %zu MB of workspace): %.2f ms, %u histories claimed a pool, %zu of %u still open\n", hp.cap, ws_bytes >> 20, ms(), claimed, todo.size(), n); }
+    std::fprintf(stderr, "[lin-check] pass 1 (registers + HBM pools of %u configurations, %zu MB of workspace): %.2f ms, %u histories claimed a pool, %zu of %u still open\n", hp.cap, ws_bytes >> 20, tm.ms(), claimed, todo.size(), n); }
   if (!todo.empty()) {
     std::vector<msim_inst_meta> hm;
     std::vector<uint64_t> ho;
@@ -758,11 +758,11 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
       else msim_lin_check_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k]);
       host_done[k] = 1;
     };
-    u32 *d_list = nullptr, *ws2 = nullptr;
-    hipError_t e = msim_dev_malloc(&d_list, todo.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_list, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, st);
+    DevBuf list, grow;   // (an error of the device passes is no early return: the host can still do everything)
+    hipError_t e = list.alloc(todo.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(list.get<u32>(), todo.data(), todo.size() * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-      lp.list = d_list;
+      lp.list = list.get<u32>();
       // pass 2: what 160 KiB of LDS hold beside the pairing table
       WParams wp;
       wp.trace = trace ? 1u : 0u;
@@ -778,8 +778,8 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
       g.cap = tiny ? 80u : 262144u; g.n_heads = tiny ? 64u : 65536u; g.out_cap = tiny ? 80u : 65536u;
       g.n_slots = (u32)std::min<size_t>(todo.size(), tiny ? 2 : 64);
       g.ws = nullptr; g.claim = nullptr;
-      e = msim_dev_malloc(&ws2, (size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap) * 4 + 256);
-      if (e == hipSuccess) { g.ws = ws2; g.claim = ws2 + (size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap); e = hipMemsetAsync(g.claim, 0, 4, st); }
+      e = grow.alloc((size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap) * 4 + 256);
+      if (e == hipSuccess) { g.ws = grow.get<u32>(); g.claim = g.ws + (size_t)g.n_slots * pool_words(g.cap, g.n_heads, g.out_cap); e = hipMemsetAsync(g.claim, 0, 4, st); }
       const void *const wg = xp ? reinterpret_cast<const void *>(&lin_check_wg_explain_kernel) : reinterpret_cast<const void *>(&lin_check_wg_kernel);
       if (e == hipSuccess && l2 > 64 * 1024) e = hipFuncSetAttribute(wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
       if (e == hipSuccess) {
@@ -795,19 +795,19 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
         for (u32 i : todo) { left += h2[i].valid == NEEDS_HOST; us.push_back(h2[i].never_read_count); for (int q = 0; q < 5; q++) a[q] += h2[i].stable_latency_ms[q]; a[5] += h2[i].stable_count; }
         std::sort(us.begin(), us.end());
         u32 grown = 0; (void)hipMemcpy(&grown, g.claim, 4, hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "[lin-check] pass 2 (pool of %u configurations, %zu B of LDS; %u histories moved on to an HBM pool of %u) done at %.2f ms, %zu histories still open\n", wp.cap, l2, grown, g.cap, ms(), left);
+        std::fprintf(stderr, "[lin-check] pass 2 (pool of %u configurations, %zu B of LDS; %u histories moved on to an HBM pool of %u) done at %.2f ms, %zu histories still open\n", wp.cap, l2, grown, g.cap, tm.ms(), left);
         std::fprintf(stderr, "[lin-check]   sums: pairing %.0f us; %.0f register closures %.0f us; %.0f pool closures %.0f us, %.0f entries admitted\n", a[0], a[1], a[2], a[3], a[4], a[5]);
         std::fprintf(stderr, "[lin-check]   microseconds per workgroup: median %u, 90%% %u, max %u\n", us[us.size() / 2], us[us.size() * 9 / 10], us.back());
       }
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h2.data(), lp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (ws2) (void)msim_dev_free(ws2);
+    grow.reset();
     wanted.assign(order.size(), 0);
     if (e == hipSuccess) for (size_t k = 0; k < order.size(); k++) wanted[k] = h2[order[k]].valid == NEEDS_HOST;
     else std::fill(wanted.begin(), wanted.end(), 1);   // (the host can still do everything)
-    const double t_dev = ms();
-    if (d_list) (void)msim_dev_free(d_list);
+    const double t_dev = tm.ms();
+    list.reset();
     if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));   // (before the host search rewrites its histories' records)
     u32 n_host_needed = 0;
     for (size_t k = 0; k < order.size(); k++) n_host_needed += wanted[k] != 0;
@@ -839,7 +839,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     todo.resize(n_host_needed);
   } else if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));
   if (xp) for (u32 i = 0; i < n; i++) h_n_keys[i] = h_out[i].attempt_count;   // keys checked = records the history has
-  if (trace) std::fprintf(stderr, "[lin-check] done at %.2f ms\n", ms());
+  if (trace) std::fprintf(stderr, "[lin-check] done at %.2f ms\n", tm.ms());
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
 }
@@ -850,9 +850,9 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
 int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
-  XParams xp; xp.keys = nullptr; xp.max_keys = max_keys;
-  if (keys) MSIM_HIP_TRY(ctx, msim_dev_malloc(&xp.keys, (size_t)n * max_keys * sizeof(msim_lin_key_result)));
-  struct Slab { msim_lin_key_result *p; ~Slab() { if (p) (void)msim_dev_free(p); } } slab_guard{xp.keys};
+  DevBuf slab;
+  if (keys) MSIM_HIP_TRY(ctx, slab.alloc((size_t)n * max_keys * sizeof(msim_lin_key_result)));
+  const XParams xp{slab.get<msim_lin_key_result>(), max_keys};
   if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
   MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
   LParams lp;
@@ -862,9 +862,7 @@ int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t 
   u32 redone = 0;
   int rc = lin_check_dev_run(ctx, lp, n, ctx->cfg.max_rows, ctx->h_check, ctx->stream, &redone, keys ? &xp : nullptr, keys, n_keys);
   if (rc != MSIM_OK) return rc;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->lin_host_rechecks = redone;
-  ctx->checked = true; ctx->check_fetched = true;
+  finish_check(ctx, t0, redone);
   return MSIM_OK;
 }
 
@@ -873,31 +871,16 @@ int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t 
 static int lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out,
                         msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t *n_host) {
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx;   // error reporting in the HIP_TRY macro; the device the host worker threads select
-  tmp_ctx.device = device;
-  msim_ctx *ctx = &tmp_ctx;
-  const uint64_t total = row_offsets[n_histories];
-  u32 max_n = 1;
-  for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0xFFFFFFFFull) return MSIM_E_RANGE; if (c > max_n) max_n = (u32)c; }
-  msim_op *d_rows = nullptr; uint64_t *d_off = nullptr; msim_check_result *d_out = nullptr;
-  XParams xp; xp.keys = nullptr; xp.max_keys = max_keys;
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)(total ? total : 1) * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_off, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (keys && msim_dev_malloc(&xp.keys, (size_t)n_histories * max_keys * sizeof(msim_lin_key_result)) != hipSuccess) break;
-    if (total && hipMemcpy(d_rows, rows, (size_t)total * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_off, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    LParams lp;
-    lp.rows = d_rows; lp.meta = nullptr; lp.off = d_off; lp.out = d_out; lp.stride = 0; lp.table_rows = 0; lp.list = nullptr;
-    rc = lin_check_dev_run(ctx, lp, n_histories, max_n, out, nullptr, n_host, keys ? &xp : nullptr, keys, n_keys);
-  } while (false);
-  if (xp.keys) (void)msim_dev_free(xp.keys);
-  if (d_rows) (void)msim_dev_free(d_rows);
-  if (d_off) (void)msim_dev_free(d_off);
-  if (d_out) (void)msim_dev_free(d_out);
-  return rc;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  OffsetsBatch b;
+  if (int rc = b.upload(ctx, rows, row_offsets, nullptr, nullptr, n_histories, 0xFFFFFFFFull)) return rc;
+  DevBuf d_out, slab;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  if (keys) MSIM_HIP_TRY(ctx, slab.alloc((size_t)n_histories * max_keys * sizeof(msim_lin_key_result)));
+  const XParams xp{slab.get<msim_lin_key_result>(), max_keys};
+  LParams lp;
+  lp.rows = b.rows.get<msim_op>(); lp.meta = nullptr; lp.off = b.row_off.get<uint64_t>(); lp.out = d_out.get<msim_check_result>(); lp.stride = 0; lp.table_rows = 0; lp.list = nullptr;
+  return lin_check_dev_run(ctx, lp, n_histories, b.longest, out, nullptr, n_host, keys ? &xp : nullptr, keys, n_keys);
 }
 
 extern "C" int msim_check_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out) {

@@ -25,7 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -338,12 +338,7 @@ extern "C" int msim_check_perf(msim_ctx *ctx, uint32_t window_ms, uint32_t n_win
   // one cached block: the records of pass 1, the results, the window records
   const size_t rec_bytes = perf_align((size_t)n * std::max(1u, pp.max_rows / 2) * sizeof(uint2)), out_bytes = perf_align((size_t)n * sizeof(msim_perf_result));
   const size_t win_bytes = (size_t)n * W * SLOTS * sizeof(msim_latency_dist), need = rec_bytes + out_bytes + win_bytes;
-  if (ctx->cap_perf_scratch < need) {
-    if (ctx->d_perf_scratch) (void)msim_dev_free(ctx->d_perf_scratch);
-    ctx->d_perf_scratch = nullptr; ctx->cap_perf_scratch = 0;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_perf_scratch, need));
-    ctx->cap_perf_scratch = need;
-  }
+  if (int rc = grow_ws(ctx, &ctx->d_perf_scratch, &ctx->cap_perf_scratch, need)) return rc;
   unsigned char *const base = static_cast<unsigned char *>(ctx->d_perf_scratch);
   pp.rows = ctx->d_rows; pp.meta = ctx->d_meta; pp.recs = reinterpret_cast<uint2 *>(base);
   pp.out = reinterpret_cast<msim_perf_result *>(base + rec_bytes);
@@ -371,30 +366,23 @@ extern "C" int msim_check_perf_batch(int device, const msim_op *rows, const uint
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0 || perf_args(window_ms, n_windows, windows)) return MSIM_E_INVALID;
   if (perf_limits(max_rows, concurrency)) return MSIM_E_UNSUPPORTED;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  std::vector<msim_inst_meta> hm(n_histories);
-  for (u32 i = 0; i < n_histories; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  SlabBatch b;
+  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
   const u32 W = windows ? n_windows : 0;
   PParams pp;
   std::memset(&pp, 0, sizeof pp);
   pp.max_rows = max_rows; pp.C = concurrency; pp.W = W; pp.window_ns = (u64)window_ms * 1000000ull;
-  msim_op *d_rows = nullptr; msim_inst_meta *d_meta = nullptr; msim_perf_result *d_out = nullptr; msim_latency_dist *d_win = nullptr; uint2 *d_rec = nullptr;
-  const size_t row_bytes = (size_t)n_histories * max_rows * sizeof(msim_op), win_bytes = (size_t)n_histories * W * SLOTS * sizeof(msim_latency_dist);
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, row_bytes) != hipSuccess) break;
-    if (msim_dev_malloc(&d_meta, (size_t)n_histories * sizeof(msim_inst_meta)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_perf_result)) != hipSuccess) break;
-    if (W && msim_dev_malloc(&d_win, win_bytes) != hipSuccess) break;
-    if (msim_dev_malloc(&d_rec, (size_t)n_histories * std::max(1u, max_rows / 2) * sizeof(uint2)) != hipSuccess) break;
-    if (hipMemcpy(d_rows, rows, row_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_meta, hm.data(), (size_t)n_histories * sizeof(msim_inst_meta), hipMemcpyHostToDevice) != hipSuccess) break;
-    pp.rows = d_rows; pp.meta = d_meta; pp.out = d_out; pp.win = d_win; pp.recs = d_rec;
-    if (perf_dispatch(pp, n_histories, nullptr) != hipSuccess) break;
-    if (hipDeviceSynchronize() != hipSuccess) break;
-    if (hipMemcpy(out, d_out, (size_t)n_histories * sizeof(msim_perf_result), hipMemcpyDeviceToHost) != hipSuccess) break;
-    if (W && hipMemcpy(windows, d_win, win_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = MSIM_OK;
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_meta, (void *)d_out, (void *)d_win, (void *)d_rec}) if (q) (void)msim_dev_free(q);
-  return rc;
+  const size_t win_bytes = (size_t)n_histories * W * SLOTS * sizeof(msim_latency_dist);
+  DevBuf d_out, d_win, d_rec;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_perf_result)));
+  if (W) MSIM_HIP_TRY(ctx, d_win.alloc(win_bytes));
+  MSIM_HIP_TRY(ctx, d_rec.alloc((size_t)n_histories * std::max(1u, max_rows / 2) * sizeof(uint2)));
+  pp.rows = b.rows.get<msim_op>(); pp.meta = b.meta.get<msim_inst_meta>();
+  pp.out = d_out.get<msim_perf_result>(); pp.win = d_win.get<msim_latency_dist>(); pp.recs = d_rec.get<uint2>();
+  MSIM_HIP_TRY(ctx, perf_dispatch(pp, n_histories, nullptr));
+  MSIM_HIP_TRY(ctx, hipDeviceSynchronize());
+  MSIM_HIP_TRY(ctx, hipMemcpy(out, pp.out, (size_t)n_histories * sizeof(msim_perf_result), hipMemcpyDeviceToHost));
+  if (W) MSIM_HIP_TRY(ctx, hipMemcpy(windows, pp.win, win_bytes, hipMemcpyDeviceToHost));
+  return MSIM_OK;
 }

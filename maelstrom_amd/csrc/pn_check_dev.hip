@@ -9,13 +9,9 @@
 // (pn_check.cpp) — same result either way.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cstring>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 void msim_pn_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);   // pn_check.cpp
 
@@ -127,18 +123,13 @@ static int pn_dev_run(msim_ctx *ctx, const msim_op *d_rows, const msim_inst_meta
   MSIM_HIP_TRY(ctx, hipGetLastError());
   MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::vector<u32> todo;
-  for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
+  const std::vector<u32> todo = needs(h_out, n, [](u32 valid) { return valid == NEEDS_HOST; });
   if (!todo.empty()) {   // wider than the bitmap: the host checker
     std::vector<msim_inst_meta> hm(n);
     MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));
-    std::vector<msim_op> rows;
-    for (u32 i : todo) {
-      rows.resize(hm[i].n_rows ? hm[i].n_rows : 1);
-      if (hm[i].n_rows) MSIM_HIP_TRY(ctx, hipMemcpy(rows.data(), d_rows + (size_t)i * max_rows, (size_t)hm[i].n_rows * sizeof(msim_op), hipMemcpyDeviceToHost));
-      msim_pn_check_instance_host(rows.data(), hm[i].n_rows, hm[i].flags, &h_out[i]);
-      MSIM_HIP_TRY(ctx, hipMemcpy(d_out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
-    }
+    const int rc = hand_off(ctx, HistorySource{d_rows, nullptr, &hm, max_rows, 0, nullptr, nullptr}, n, todo, h_out, d_out,
+                            [&](const msim_op *rows, u32 nr, const u32 *, u32, u32 flags, u32 i) { msim_pn_check_instance_host(rows, nr, flags, &h_out[i]); });
+    if (rc != MSIM_OK) return rc;
   }
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
@@ -147,16 +138,12 @@ static int pn_dev_run(msim_ctx *ctx, const msim_op *d_rows, const msim_inst_meta
 // msim_check for pn-counter / g-counter: the histories of the last run, where they lie in HBM.
 int msim_check_pn_device(msim_ctx *ctx) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const u32 n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  const auto t0 = std::chrono::steady_clock::now();
+  std::chrono::steady_clock::time_point t0;
+  if (int rc = begin_check(ctx, &t0, nullptr)) return rc;   // (no meta here: pn_dev_run fetches it behind the kernel, for the host checker only)
   u32 redone = 0;
-  int rc = pn_dev_run(ctx, ctx->d_rows, ctx->d_meta, ctx->d_check, ctx->cfg.max_rows, n, ctx->h_check, ctx->stream, &redone);
+  int rc = pn_dev_run(ctx, ctx->d_rows, ctx->d_meta, ctx->d_check, ctx->cfg.max_rows, ctx->n_inst, ctx->h_check, ctx->stream, &redone);
   if (rc != MSIM_OK) return rc;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->lin_host_rechecks = redone;
-  ctx->checked = true; ctx->check_fetched = true;
+  finish_check(ctx, t0, redone);
   return MSIM_OK;
 }
 
@@ -165,20 +152,10 @@ int msim_check_pn_device(msim_ctx *ctx) {
 extern "C" int msim_check_pn_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
-  tmp_ctx.device = device;
-  std::vector<msim_inst_meta> hm(n_histories);
-  for (u32 i = 0; i < n_histories; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
-  msim_op *d_rows = nullptr; msim_inst_meta *d_meta = nullptr; msim_check_result *d_out = nullptr;
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)n_histories * max_rows * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_meta, (size_t)n_histories * sizeof(msim_inst_meta)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (hipMemcpy(d_rows, rows, (size_t)n_histories * max_rows * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_meta, hm.data(), (size_t)n_histories * sizeof(msim_inst_meta), hipMemcpyHostToDevice) != hipSuccess) break;
-    rc = pn_dev_run(ctx, d_rows, d_meta, d_out, max_rows, n_histories, out, nullptr, nullptr);
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_meta, (void *)d_out}) if (q) (void)msim_dev_free(q);
-  return rc;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  SlabBatch b;
+  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
+  DevBuf d_out;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  return pn_dev_run(ctx, b.rows.get<msim_op>(), b.meta.get<msim_inst_meta>(), d_out.get<msim_check_result>(), max_rows, n_histories, out, nullptr, nullptr);
 }

@@ -30,13 +30,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
                                  msim_check_result *res);   // txn_check.cpp
@@ -424,49 +422,32 @@ uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws
 // full: every history's record comes from the classification (msim_classify_rw_batch, msim_set_check_classify); otherwise only the
 // records of the histories that rw_check_kernel could not prove valid do
 int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-               void **ws_buf, size_t *ws_cap, bool full = false, msim_cycle_result *h_cycles = nullptr, msim_cycle_step *h_steps = nullptr) {
-  // h_cycles / h_steps (msim_explain_rw_batch, msim_explain_txn; with full): the witness cycles, found by rw_explain_kernel in rp.cycles / rp.steps
-  const bool explain = full && h_cycles != nullptr;
-  if (explain) {
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(rp.cycles, 0, (size_t)n * sizeof(msim_cycle_result), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(rp.steps, 0, (size_t)n * rp.max_steps * sizeof(msim_cycle_step), st));
-  }
-  const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+               void **ws_buf, size_t *ws_cap, const CycleMode mode = {}) {
+  // mode.witness (msim_explain_rw_batch, msim_explain_txn; with full): the witness cycles, found by rw_explain_kernel in rp.cycles / rp.steps
+  WitnessSlabs *const wit = mode.full ? mode.witness : nullptr;
+  if (wit) { wit->bind(rp); if (int rc = wit->clear(ctx, st)) return rc; }
+  const PassTimer tm(ctx);
   if (rp.kmax == 0 || rp.kmax > KMAX) rp.kmax = KMAX;
   if (rp.wmax == 0 || rp.wmax > WMAX) rp.wmax = WMAX;
   rp.ws_words = rw_ws_words(rp.nmax, rp.emax, rp.kmax, rp.wmax);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold
-  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;   // MSIM_DEV_FLAGS bit 16: at most 7 histories per launch
-  auto reserve = [&](size_t need) -> int {
-    if (*ws_cap < need) {
-      if (*ws_buf) (void)msim_dev_free(*ws_buf);
-      *ws_buf = nullptr; *ws_cap = 0;
-      MSIM_HIP_TRY(ctx, msim_dev_malloc(ws_buf, need));
-      *ws_cap = need;
-    }
-    return MSIM_OK;
-  };
+  const auto for_host = [](u32 valid) { return valid == NEEDS_HOST; };
   std::vector<u32> todo;
-  if (!full) {
-    const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
-    if (int rc = reserve((size_t)chunk * rp.ws_words * 4)) return rc;
+  hipError_t e;
+  if (!mode.full) {
+    const u32 chunk = chunk_for(n, rp.ws_words * 4, budget, msim_dev_flags(ctx));
+    if (int rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * rp.ws_words * 4)) return rc;
     rp.ws = static_cast<u32 *>(*ws_buf);
-    u32 launches = 0;
-    for (u32 first = 0; first < n; first += chunk, launches++) {
+    const u32 launches = for_chunks(n, chunk, &e, [&](u32 first, u32 count) {
       rp.first = first;
-      hipLaunchKernelGGL(rw_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, rp);
-      MSIM_HIP_TRY(ctx, hipGetLastError());
-    }
+      hipLaunchKernelGGL(rw_check_kernel, dim3(count), dim3(64), 0, st, rp);
+    });
+    MSIM_HIP_TRY(ctx, e);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-    if (trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories not proved valid\n", launches, ms(), todo.size(), n);
-  } else {
-    todo.resize(n);
-    for (u32 i = 0; i < n; i++) todo[i] = i;
-  }
+    todo = needs(h_out, n, for_host);
+    if (tm.trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories not proved valid\n", launches, tm.ms(), todo.size(), n);
+  } else todo = needs(h_out, n, [](u32) { return true; });
   if (!todo.empty()) {   // the classification, over the list of histories that need it: the list first in the workspace, then a slice per block
     const u32 m = (u32)todo.size();
     const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
@@ -475,59 +456,30 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
     // histories reach the search
     rp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     rp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    const u32 chunk = (u32)std::min<uint64_t>({m, max_chunk, std::max<uint64_t>(1, budget / (rp.ws_words * 4))});
-    if (int rc = reserve(list_bytes + (size_t)chunk * rp.ws_words * 4)) return rc;
+    const u32 chunk = chunk_for(m, rp.ws_words * 4, budget, msim_dev_flags(ctx));
+    if (int rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * rp.ws_words * 4)) return rc;
     rp.list = static_cast<const u32 *>(*ws_buf);
     rp.ws = reinterpret_cast<u32 *>(static_cast<char *>(*ws_buf) + list_bytes);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    u32 launches = 0;
-    for (u32 first = 0; first < m; first += chunk, launches++) {
+    const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) {
       rp.first = first;
-      if (explain) hipLaunchKernelGGL(rw_explain_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
-      else hipLaunchKernelGGL(rw_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, rp);
-      MSIM_HIP_TRY(ctx, hipGetLastError());
-    }
+      if (wit) hipLaunchKernelGGL(rw_explain_kernel, dim3(count), dim3(64), 0, st, rp);
+      else hipLaunchKernelGGL(rw_classify_kernel, dim3(count), dim3(64), 0, st, rp);
+    });
+    MSIM_HIP_TRY(ctx, e);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    todo.clear();
-    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST) todo.push_back(i);
-    if (trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, ms(), todo.size());
+    todo = needs(h_out, n, for_host);
+    if (tm.trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, tm.ms(), todo.size());
   }
-  if (explain) {
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, rp.cycles, (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, rp.steps, (size_t)n * rp.max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
+  if (wit) if (int rc = wit->fetch(ctx, st)) return rc;
   if (!todo.empty()) {
-    std::vector<uint64_t> ro, po;
-    if (rp.row_off) { ro.resize(n + 1); po.resize(n + 1);
-      MSIM_HIP_TRY(ctx, hipMemcpy(ro.data(), rp.row_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
-      MSIM_HIP_TRY(ctx, hipMemcpy(po.data(), rp.pay_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost)); }
-    std::vector<std::vector<msim_op>> rows(todo.size());
-    std::vector<std::vector<u32>> pays(todo.size());
-    for (size_t k = 0; k < todo.size(); k++) {
-      const u32 i = todo[k];
-      const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
-      rows[k].resize(nr ? nr : 1); pays[k].resize(nw ? nw : 1);
-      if (nr) MSIM_HIP_TRY(ctx, hipMemcpy(rows[k].data(), rp.rows + (hmeta ? (uint64_t)i * rp.max_rows : ro[i]), (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost));
-      if (nw) MSIM_HIP_TRY(ctx, hipMemcpy(pays[k].data(), rp.payload + (hmeta ? (uint64_t)i * rp.max_pay : po[i]), (size_t)nw * 4, hipMemcpyDeviceToHost));
-    }
-    unsigned nt = msim_host_threads();
-    if (nt > todo.size()) nt = (unsigned)todo.size();
-    std::vector<std::thread> th;
-    for (unsigned w = 0; w < nt; w++)
-      th.emplace_back([&, w]() {
-        for (size_t k = w; k < todo.size(); k += nt) {
-          const u32 i = todo[k];
-          const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
-          if (explain) msim_txn_explain_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, rp.cm, &h_out[i], &h_cycles[i],
-                                                      h_steps + (size_t)i * rp.max_steps, rp.max_steps, true);
-          else msim_rw_check_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, rp.cm, &h_out[i]);
-        }
-      });
-    for (auto &x : th) x.join();
-    for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(rp.out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
-    if (trace) std::fprintf(stderr, "[rw-check] host analysis of those: done at %.2f ms\n", ms());
+    const int rc = hand_off(ctx, source_of(rp, hmeta), n, todo, h_out, rp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
+      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], &wit->h_cycles[i], wit->h_steps + (size_t)i * rp.max_steps, rp.max_steps, true);
+      else msim_rw_check_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i]);
+    });
+    if (rc != MSIM_OK) return rc;
+    if (tm.trace) std::fprintf(stderr, "[rw-check] host analysis of those: done at %.2f ms\n", tm.ms());
   }
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
@@ -540,14 +492,9 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
 int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  // the simulation may still be running (msim_run_async): the context's stream does not block against the null stream, so the copy of
-  // the meta below is ordered behind it here and by nothing else
-  MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<msim_inst_meta> hm(n);
-  MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));
+  std::chrono::steady_clock::time_point t0;
+  std::vector<msim_inst_meta> hm;
+  if (int rc = begin_check(ctx, &t0, &hm)) return rc;
   RParams rp;
   std::memset(&rp, 0, sizeof rp);
   rp.rows = ctx->d_rows; rp.payload = ctx->d_payload; rp.meta = ctx->d_meta; rp.out = ctx->d_check;
@@ -558,18 +505,13 @@ int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_st
   // histories may need — 1 MB of workspace per history was four launches of 4096 for the demo shape, each waiting for its slowest history
   rp.kmax = ctx->cfg.max_values ? ctx->cfg.max_values : 1u;
   rp.wmax = (u32)std::min<uint64_t>(WMAX, (uint64_t)rp.kmax * (ctx->cfg.max_writes_per_key + 2u));
-  struct Slabs { void *c = nullptr, *s = nullptr; ~Slabs() { if (c) (void)msim_dev_free(c); if (s) (void)msim_dev_free(s); } } slabs;
-  if (cycles) {
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.c, (size_t)n * sizeof(msim_cycle_result)));
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.s, (size_t)n * max_steps * sizeof(msim_cycle_step)));
-    rp.cycles = static_cast<msim_cycle_result *>(slabs.c); rp.steps = static_cast<msim_cycle_step *>(slabs.s); rp.max_steps = max_steps;
-  }
+  WitnessSlabs wit;
+  if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
   u32 redone = 0;
-  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->check_classify || cycles, cycles, steps);
+  int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
+                      CycleMode{ctx->check_classify || cycles, cycles ? &wit : nullptr});
   if (rc != MSIM_OK) return rc;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->lin_host_rechecks = redone;
-  ctx->checked = true; ctx->check_fetched = true;
+  finish_check(ctx, t0, redone);
   return MSIM_OK;
 }
 
@@ -580,35 +522,20 @@ static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets
                     msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
-  tmp_ctx.device = device;
-  const uint64_t tr = row_offsets[n_histories], tw = payload_offsets[n_histories];
-  u32 max_r = 1;
-  for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0x7FFFFFFFull) return MSIM_E_RANGE; if (c > max_r) max_r = (u32)c; }
-  msim_op *d_rows = nullptr; u32 *d_pay = nullptr; uint64_t *d_ro = nullptr, *d_po = nullptr; msim_check_result *d_out = nullptr; void *ws = nullptr; size_t ws_cap = 0;
-  msim_cycle_result *d_cycles = nullptr; msim_cycle_step *d_steps = nullptr;
-  int rc = MSIM_E_HIP;
-  do {
-    if (cycles && (msim_dev_malloc(&d_cycles, (size_t)n_histories * sizeof(msim_cycle_result)) != hipSuccess ||
-                   msim_dev_malloc(&d_steps, (size_t)n_histories * max_steps * sizeof(msim_cycle_step)) != hipSuccess)) break;
-    if (msim_dev_malloc(&d_rows, (size_t)(tr ? tr : 1) * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_pay, (size_t)(tw ? tw : 1) * 4) != hipSuccess) break;
-    if (msim_dev_malloc(&d_ro, (size_t)(n_histories + 1) * 8) != hipSuccess || msim_dev_malloc(&d_po, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (tr && hipMemcpy(d_rows, rows, (size_t)tr * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (tw && hipMemcpy(d_pay, payload, (size_t)tw * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_ro, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_po, payload_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    RParams rp;
-    std::memset(&rp, 0, sizeof rp);
-    rp.rows = d_rows; rp.payload = d_pay; rp.row_off = d_ro; rp.pay_off = d_po; rp.out = d_out;
-    rp.nmax = max_r / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
-     rp.proscribed = msim_proscribed_anomalies(consistency_model);
-    rp.cycles = d_cycles; rp.steps = d_steps; rp.max_steps = max_steps;
-    rc = rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, &ws, &ws_cap, full, cycles, steps);
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, (void *)d_cycles, (void *)d_steps, ws}) if (q) (void)msim_dev_free(q);
-  return rc;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  OffsetsBatch b;
+  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
+  DevBuf d_out, ws; size_t ws_cap = 0;
+  WitnessSlabs wit;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
+  RParams rp;
+  std::memset(&rp, 0, sizeof rp);
+  rp.rows = b.rows.get<msim_op>(); rp.payload = b.pay.get<u32>(); rp.row_off = b.row_off.get<uint64_t>(); rp.pay_off = b.pay_off.get<uint64_t>();
+  rp.out = d_out.get<msim_check_result>();
+  rp.nmax = b.longest / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
+  rp.proscribed = msim_proscribed_anomalies(consistency_model);
+  return rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{full, cycles ? &wit : nullptr});
 }
 
 extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,

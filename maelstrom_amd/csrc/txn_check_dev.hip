@@ -28,14 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 void msim_txn_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
                                   msim_check_result *res);   // txn_check.cpp
@@ -917,26 +915,13 @@ u32 lds_bytes_for(u32 nmax, u32 keys, u32 stride) {
   return (u32)std::min<uint64_t>(78 * 1024, std::max<uint64_t>(8 * 1024, (need + 255) & ~255ull));
 }
 
-int grow_ws(msim_ctx *ctx, void **ws_buf, size_t *ws_cap, size_t need) {
-  if (*ws_cap >= need) return MSIM_OK;
-  if (*ws_buf) (void)msim_dev_free(*ws_buf);
-  *ws_buf = nullptr; *ws_cap = 0;
-  MSIM_HIP_TRY(ctx, msim_dev_malloc(ws_buf, need));
-  *ws_cap = need;
-  return MSIM_OK;
-}
-
-// classify: what the two passes cannot prove clean goes to txn_classify_kernel, and only what that one hands on to the host
+// mode.full: what the two passes cannot prove clean goes to txn_classify_kernel, and only what that one hands on to the host
 // (msim_classify_txn_batch, msim_set_check_classify); otherwise to the host at once
 int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-                void **ws_buf, size_t *ws_cap, bool classify = false, msim_cycle_result *h_cycles = nullptr, msim_cycle_step *h_steps = nullptr) {
-  // h_cycles / h_steps (msim_explain_txn*; with classify): the witness cycles, found by txn_explain_kernel in tp.cycles / tp.steps
-  const bool explain = classify && h_cycles != nullptr;
-  if (explain) {   // a history the clean passes prove clean keeps the zero record
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(tp.cycles, 0, (size_t)n * sizeof(msim_cycle_result), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(tp.steps, 0, (size_t)n * tp.max_steps * sizeof(msim_cycle_step), st));
-  }
-  const bool trace = (msim_dev_flags(ctx) & 0x1000u) != 0;   // developer: time the passes
+                void **ws_buf, size_t *ws_cap, const CycleMode mode = {}) {
+  // mode.witness (msim_explain_txn*; with full): the witness cycles, found by txn_explain_kernel in tp.cycles / tp.steps
+  WitnessSlabs *const wit = mode.full ? mode.witness : nullptr;
+  if (wit) { wit->bind(tp); if (int rc = wit->clear(ctx, st)) return rc; }   // a history the clean passes prove clean keeps the zero record
   // Which kernel takes the first pass: the one with its tables in LDS, a workgroup of sixteen wavefronts per history.  Measured on cfg5,
   // 32768 histories (profiles/r03b_cfg5_txn_check_*, r03k_cfg5_txn_check.txt, r03x_txn_check.txt): tables in an HBM workspace, one
   // wavefront per history: 82 GB of HBM traffic, 130 ms (64 histories in flight per CU); tables in LDS (78 KiB: two histories per CU),
@@ -946,121 +931,84 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
   // for histories whose tables do not fit); MSIM_TXN_WG = threads per history (64 .. 1024, the default: 66 ms; 512: 75 ms).
   const bool hbm_only = (msim_dev_flags(ctx) & 0x2000u) != 0;
   static const u32 wg_threads = []() { const char *e = std::getenv("MSIM_TXN_WG"); u32 v = e ? (u32)std::atoi(e) : 1024u; v = (v / 64u) * 64u; return v < 64u ? 64u : v > 1024u ? 1024u : v; }();
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  const PassTimer tm(ctx);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold (every one of them has its own slice)
-  // MSIM_DEV_FLAGS bit 16 (0x10000): at most 7 histories per launch, so that small batches reach the chunk loops (a partial last chunk, first > 0)
-  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;
+  const auto for_host = [](u32 valid) { return valid == NEEDS_HOST || valid == NEEDS_HBM; };
   int rc;
+  hipError_t e;
   std::vector<u32> big;   // histories for txn_check_kernel
   if (!hbm_only) {
     // pass 1: tables in LDS
     tp.ws_words = ws_words_lds(tp.nmax); tp.list = nullptr;
-    const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / (tp.ws_words * 4))});
+    const u32 chunk = chunk_for(n, tp.ws_words * 4, budget, msim_dev_flags(ctx));
     if ((rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
     tp.ws = static_cast<u32 *>(*ws_buf);
     if (tp.lds_bytes > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(txn_check_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds_bytes));
-    u32 launches = 0;
-    for (u32 first = 0; first < n; first += chunk, launches++) {
+    const u32 launches = for_chunks(n, chunk, &e, [&](u32 first, u32 count) {
       tp.first = first;
-      hipLaunchKernelGGL(txn_check_lds_kernel, dim3(std::min(chunk, n - first)), dim3(wg_threads), tp.lds_bytes, st, tp);
-      MSIM_HIP_TRY(ctx, hipGetLastError());
-    }
+      hipLaunchKernelGGL(txn_check_lds_kernel, dim3(count), dim3(wg_threads), tp.lds_bytes, st, tp);
+    });
+    MSIM_HIP_TRY(ctx, e);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HBM) big.push_back(i);
-    if (trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup, %u launches): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, launches, ms(), big.size(), n);
-  } else { big.resize(n); for (u32 i = 0; i < n; i++) big[i] = i; }
+    big = needs(h_out, n, [](u32 valid) { return valid == NEEDS_HBM; });
+    if (tm.trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup, %u launches): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, launches, tm.ms(), big.size(), n);
+  } else big = needs(h_out, n, [](u32) { return true; });
   if (!big.empty()) {
     // pass 2: the histories whose tables do not fit LDS, tables in an HBM workspace
-    u32 *d_list = nullptr;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&d_list, big.size() * 4));
-    MSIM_HIP_TRY(ctx, hipMemcpy(d_list, big.data(), big.size() * 4, hipMemcpyHostToDevice));
-    tp.ws_words = ws_words_for(tp.nmax, tp.emax); tp.list = d_list;
+    DevBuf d_list;
+    MSIM_HIP_TRY(ctx, d_list.upload(big.data(), big.size() * 4));
+    tp.ws_words = ws_words_for(tp.nmax, tp.emax); tp.list = d_list.get<u32>();
     const u32 nb = (u32)big.size();
-    const u32 chunk = (u32)std::min<uint64_t>({nb, max_chunk, std::max<uint64_t>(1, budget / (tp.ws_words * 4))});
-    rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4);
-    u32 launches = 0;
-    if (rc == MSIM_OK) {
-      tp.ws = static_cast<u32 *>(*ws_buf);
-      for (u32 first = 0; first < nb; first += chunk, launches++) {
-        tp.first = first;
-        hipLaunchKernelGGL(txn_check_kernel, dim3(std::min(chunk, nb - first)), dim3(64), 0, st, tp);
-        if (hipGetLastError() != hipSuccess) { rc = MSIM_E_HIP; ctx->err = "txn_check_kernel launch"; break; }
-      }
-    }
-    if (rc == MSIM_OK && (hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { rc = MSIM_E_HIP; ctx->err = "txn check: copy of the results"; }
-    (void)msim_dev_free(d_list);
-    if (rc != MSIM_OK) return rc;
-    if (trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories (%u launches): done at %.2f ms\n", nb, launches, ms());
+    const u32 chunk = chunk_for(nb, tp.ws_words * 4, budget, msim_dev_flags(ctx));
+    if ((rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
+    tp.ws = static_cast<u32 *>(*ws_buf);
+    const u32 launches = for_chunks(nb, chunk, &e, [&](u32 first, u32 count) {
+      tp.first = first;
+      hipLaunchKernelGGL(txn_check_kernel, dim3(count), dim3(64), 0, st, tp);
+    });
+    MSIM_HIP_TRY(ctx, e);
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (tm.trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories (%u launches): done at %.2f ms\n", nb, launches, tm.ms());
   }
   if (ctx) ctx->txn_big = (u32)big.size();
-  std::vector<u32> todo;
-  for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST || h_out[i].valid == NEEDS_HBM) todo.push_back(i);
-  if (trace) std::fprintf(stderr, "[txn-check] device passes: %.2f ms, %zu of %u histories for the host\n", ms(), todo.size(), n);
-  if (classify && !todo.empty()) {   // the full analysis on the device: the list of histories first in the workspace, then a slice per block
+  std::vector<u32> todo = needs(h_out, n, for_host);
+  if (tm.trace) std::fprintf(stderr, "[txn-check] device passes: %.2f ms, %zu of %u histories for the host\n", tm.ms(), todo.size(), n);
+  if (mode.full && !todo.empty()) {   // the full analysis on the device: the list of histories first in the workspace, then a slice per block
     const u32 m = (u32)todo.size();
     const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
     tp.emax *= 2;   // (a clean history has few edges per transaction; one without isolation has more)
-    tp.ws_words = explain ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
+    tp.ws_words = wit ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
     tp.cm = cm; tp.proscribed = msim_proscribed_anomalies(cm);
     // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
     // histories reach the search (as for rw_classify_kernel)
     tp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     tp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    const u32 chunk = (u32)std::min<uint64_t>({m, max_chunk, std::max<uint64_t>(1, budget / (tp.ws_words * 4))});
+    const u32 chunk = chunk_for(m, tp.ws_words * 4, budget, msim_dev_flags(ctx));
     if ((rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
     tp.list = static_cast<const u32 *>(*ws_buf);
     tp.ws = reinterpret_cast<u32 *>(static_cast<char *>(*ws_buf) + list_bytes);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    u32 launches = 0;
-    for (u32 first = 0; first < m; first += chunk, launches++) {
+    const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) {
       tp.first = first;
-      if (explain) hipLaunchKernelGGL(txn_explain_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, tp);
-      else hipLaunchKernelGGL(txn_classify_kernel, dim3(std::min(chunk, m - first)), dim3(64), 0, st, tp);
-      MSIM_HIP_TRY(ctx, hipGetLastError());
-    }
+      if (wit) hipLaunchKernelGGL(txn_explain_kernel, dim3(count), dim3(64), 0, st, tp);
+      else hipLaunchKernelGGL(txn_classify_kernel, dim3(count), dim3(64), 0, st, tp);
+    });
+    MSIM_HIP_TRY(ctx, e);
     MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    todo.clear();
-    for (u32 i = 0; i < n; i++) if (h_out[i].valid == NEEDS_HOST || h_out[i].valid == NEEDS_HBM) todo.push_back(i);
-    if (trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, ms(), todo.size());
+    todo = needs(h_out, n, for_host);
+    if (tm.trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, tm.ms(), todo.size());
   }
-  if (explain) {
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, tp.cycles, (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, tp.steps, (size_t)n * tp.max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
+  if (wit && (rc = wit->fetch(ctx, st)) != MSIM_OK) return rc;
   if (!todo.empty()) {
-    std::vector<uint64_t> ro, po;
-    if (tp.row_off) { ro.resize(n + 1); po.resize(n + 1);
-      MSIM_HIP_TRY(ctx, hipMemcpy(ro.data(), tp.row_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost));
-      MSIM_HIP_TRY(ctx, hipMemcpy(po.data(), tp.pay_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost)); }
-    std::vector<std::vector<msim_op>> rows(todo.size());
-    std::vector<std::vector<u32>> pays(todo.size());
-    for (size_t k = 0; k < todo.size(); k++) {
-      const u32 i = todo[k];
-      const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
-      rows[k].resize(nr ? nr : 1); pays[k].resize(nw ? nw : 1);
-      if (nr) MSIM_HIP_TRY(ctx, hipMemcpy(rows[k].data(), tp.rows + (hmeta ? (uint64_t)i * tp.max_rows : ro[i]), (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost));
-      if (nw) MSIM_HIP_TRY(ctx, hipMemcpy(pays[k].data(), tp.payload + (hmeta ? (uint64_t)i * tp.max_pay : po[i]), (size_t)nw * 4, hipMemcpyDeviceToHost));
-    }
-    unsigned nt = msim_host_threads();
-    if (nt > todo.size()) nt = (unsigned)todo.size();
-    std::vector<std::thread> th;
-    for (unsigned w = 0; w < nt; w++)
-      th.emplace_back([&, w]() {
-        for (size_t k = w; k < todo.size(); k += nt) {
-          const u32 i = todo[k];
-          const u32 nr = hmeta ? (*hmeta)[i].n_rows : (u32)(ro[i + 1] - ro[i]), nw = hmeta ? (*hmeta)[i].n_payload_words : (u32)(po[i + 1] - po[i]);
-          if (explain) msim_txn_explain_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, cm, &h_out[i], &h_cycles[i],
-                                                      h_steps + (size_t)i * tp.max_steps, tp.max_steps, false);
-          else msim_txn_check_instance_host(rows[k].data(), nr, pays[k].data(), nw, hmeta ? (*hmeta)[i].flags : 0u, cm, &h_out[i]);
-        }
-      });
-    for (auto &x : th) x.join();
-    for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(tp.out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
-    if (trace) std::fprintf(stderr, "[txn-check] host analysis of those: done at %.2f ms\n", ms());
+    rc = hand_off(ctx, source_of(tp, hmeta), n, todo, h_out, tp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
+      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], &wit->h_cycles[i], wit->h_steps + (size_t)i * tp.max_steps, tp.max_steps, false);
+      else msim_txn_check_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i]);
+    });
+    if (rc != MSIM_OK) return rc;
+    if (tm.trace) std::fprintf(stderr, "[txn-check] host analysis of those: done at %.2f ms\n", tm.ms());
   }
   if (n_host) *n_host = (u32)todo.size();
   return MSIM_OK;
@@ -1074,14 +1022,9 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
 int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  // the simulation may still be running (msim_run_async): the context's stream does not block against the null stream, so the copy of
-  // the meta below is ordered behind it here and by nothing else
-  MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<msim_inst_meta> hm(n);
-  MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));
+  std::chrono::steady_clock::time_point t0;
+  std::vector<msim_inst_meta> hm;
+  if (int rc = begin_check(ctx, &t0, &hm)) return rc;
   TParams tp;
   tp.rows = ctx->d_rows; tp.payload = ctx->d_payload; tp.meta = ctx->d_meta; tp.row_off = nullptr; tp.pay_off = nullptr; tp.out = ctx->d_check;
   tp.max_rows = ctx->cfg.max_rows; tp.max_pay = ctx->cfg.max_payload_words;
@@ -1089,19 +1032,13 @@ int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_s
   tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
   tp.cycles = nullptr; tp.steps = nullptr; tp.max_steps = max_steps;
   tp.lds_bytes = lds_bytes_for(tp.nmax, ctx->cfg.max_values, ctx->cfg.max_writes_per_key + 1);
-  struct Slabs { void *c = nullptr, *s = nullptr; ~Slabs() { if (c) (void)msim_dev_free(c); if (s) (void)msim_dev_free(s); } } slabs;
-  if (cycles) {
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.c, (size_t)n * sizeof(msim_cycle_result)));
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(&slabs.s, (size_t)n * max_steps * sizeof(msim_cycle_step)));
-    tp.cycles = static_cast<msim_cycle_result *>(slabs.c); tp.steps = static_cast<msim_cycle_step *>(slabs.s);
-  }
+  WitnessSlabs wit;
+  if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
   u32 redone = 0;
   int rc = txn_dev_run(ctx, tp, n, ctx->cfg.consistency_model, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
-                       ctx->check_classify || cycles, cycles, steps);
+                       CycleMode{ctx->check_classify || cycles, cycles ? &wit : nullptr});
   if (rc != MSIM_OK) return rc;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->lin_host_rechecks = redone;
-  ctx->checked = true; ctx->check_fetched = true;
+  finish_check(ctx, t0, redone);
   return MSIM_OK;
 }
 
@@ -1112,35 +1049,21 @@ static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offset
                      msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
-  tmp_ctx.device = device;
-  const uint64_t tr = row_offsets[n_histories], tw = payload_offsets[n_histories];
-  u32 max_r = 1;
-  for (u32 i = 0; i < n_histories; i++) { const uint64_t c = row_offsets[i + 1] - row_offsets[i]; if (c > 0x7FFFFFFFull) return MSIM_E_RANGE; if (c > max_r) max_r = (u32)c; }
-  msim_op *d_rows = nullptr; u32 *d_pay = nullptr; uint64_t *d_ro = nullptr, *d_po = nullptr; msim_check_result *d_out = nullptr; void *ws = nullptr; size_t ws_cap = 0;
-  msim_cycle_result *d_cycles = nullptr; msim_cycle_step *d_steps = nullptr;
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)(tr ? tr : 1) * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_pay, (size_t)(tw ? tw : 1) * 4) != hipSuccess) break;
-    if (msim_dev_malloc(&d_ro, (size_t)(n_histories + 1) * 8) != hipSuccess || msim_dev_malloc(&d_po, (size_t)(n_histories + 1) * 8) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (cycles && (msim_dev_malloc(&d_cycles, (size_t)n_histories * sizeof(msim_cycle_result)) != hipSuccess ||
-                   msim_dev_malloc(&d_steps, (size_t)n_histories * max_steps * sizeof(msim_cycle_step)) != hipSuccess)) break;
-    if (tr && hipMemcpy(d_rows, rows, (size_t)tr * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (tw && hipMemcpy(d_pay, payload, (size_t)tw * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_ro, row_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_po, payload_offsets, (size_t)(n_histories + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-    TParams tp;
-    tp.rows = d_rows; tp.payload = d_pay; tp.meta = nullptr; tp.row_off = d_ro; tp.pay_off = d_po; tp.out = d_out;
-    tp.max_rows = 0; tp.max_pay = 0; tp.nmax = max_r / 2 + 65; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  OffsetsBatch b;
+  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
+  DevBuf d_out, ws; size_t ws_cap = 0;
+  WitnessSlabs wit;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
+  TParams tp;
+  tp.rows = b.rows.get<msim_op>(); tp.payload = b.pay.get<u32>(); tp.meta = nullptr; tp.row_off = b.row_off.get<uint64_t>(); tp.pay_off = b.pay_off.get<uint64_t>();
+  tp.out = d_out.get<msim_check_result>();
+  tp.max_rows = 0; tp.max_pay = 0; tp.nmax = b.longest / 2 + 65; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
   tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
-    tp.cycles = d_cycles; tp.steps = d_steps; tp.max_steps = max_steps;
-    tp.lds_bytes = lds_bytes_for(tp.nmax, std::min<u32>(KMAX, tp.nmax * 2 + 16), 17);
-    rc = txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, &ws, &ws_cap, classify, cycles, steps);
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_ro, (void *)d_po, (void *)d_out, (void *)d_cycles, (void *)d_steps, ws}) if (q) (void)msim_dev_free(q);
-  return rc;
+  tp.cycles = nullptr; tp.steps = nullptr; tp.max_steps = max_steps;
+  tp.lds_bytes = lds_bytes_for(tp.nmax, std::min<u32>(KMAX, tp.nmax * 2 + 16), 17);
+  return txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{classify, cycles ? &wit : nullptr});
 }
 
 extern "C" int msim_check_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,

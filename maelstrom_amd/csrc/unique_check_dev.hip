@@ -8,11 +8,9 @@
 // the HBM tables cost 256 KiB of initialisation and scattered compare-and-swaps per history (25 ms per 16384 histories of the demo shape).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstring>
-#include <vector>
+#include <cstdio>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -159,23 +157,15 @@ static int unique_dev_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *w
   }
   u32 slots = 64; while (slots < (paired ? up.max_rows : 2 * up.max_rows)) slots <<= 1;   // >= 2 x the ids a history can acknowledge
   up.table_slots = slots;
-  const uint64_t budget = 4ull << 30;
-  const uint64_t max_chunk = (msim_dev_flags(ctx) & 0x10000u) ? 7 : ~0ull;   // MSIM_DEV_FLAGS bit 16: at most 7 histories per launch
-  const u32 chunk = (u32)std::min<uint64_t>({n, max_chunk, std::max<uint64_t>(1, budget / ((uint64_t)slots * 8))});
-  const size_t need = (size_t)chunk * slots * 8;
-  if (*ws_cap < need) {
-    if (*ws) (void)msim_dev_free(*ws);
-    *ws = nullptr; *ws_cap = 0;
-    MSIM_HIP_TRY(ctx, msim_dev_malloc(ws, need));
-    *ws_cap = need;
-  }
+  const u32 chunk = chunk_for(n, (uint64_t)slots * 8, 4ull << 30, msim_dev_flags(ctx));
+  if (int rc = grow_ws(ctx, ws, ws_cap, (size_t)chunk * slots * 8)) return rc;
   up.ws = static_cast<uint2 *>(*ws);
-  u32 launches = 0;
-  for (u32 first = 0; first < n; first += chunk, launches++) {
+  hipError_t e;
+  const u32 launches = for_chunks(n, chunk, &e, [&](u32 first, u32 count) {
     up.first = first;
-    hipLaunchKernelGGL(unique_check_kernel, dim3(std::min(chunk, n - first)), dim3(64), 0, st, up);
-    MSIM_HIP_TRY(ctx, hipGetLastError());
-  }
+    hipLaunchKernelGGL(unique_check_kernel, dim3(count), dim3(64), 0, st, up);
+  });
+  MSIM_HIP_TRY(ctx, e);
   if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[unique-check] HBM tables (%u slots) over %u histories (%u launches)\n", slots, n, launches);   // developer trace bit
   return MSIM_OK;
 }
@@ -200,24 +190,15 @@ int msim_check_unique_device(msim_ctx *ctx) {
 extern "C" int msim_check_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0) return MSIM_E_INVALID;
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  msim_ctx tmp_ctx; msim_ctx *ctx = &tmp_ctx;   // only for error text
-  tmp_ctx.device = device;
-  std::vector<msim_inst_meta> hm(n_histories);
-  for (u32 i = 0; i < n_histories; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
-  msim_op *d_rows = nullptr; msim_inst_meta *d_meta = nullptr; msim_check_result *d_out = nullptr; void *ws = nullptr; size_t ws_cap = 0;
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)n_histories * max_rows * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_meta, (size_t)n_histories * sizeof(msim_inst_meta)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (hipMemcpy(d_rows, rows, (size_t)n_histories * max_rows * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_meta, hm.data(), (size_t)n_histories * sizeof(msim_inst_meta), hipMemcpyHostToDevice) != hipSuccess) break;
-    UParams up;
-    up.rows = d_rows; up.meta = d_meta; up.out = d_out; up.max_rows = max_rows; up.ws = nullptr; up.table_slots = 0; up.first = 0;
-    rc = unique_dev_run(ctx, up, n_histories, &ws, &ws_cap, nullptr, false);
-    if (rc != MSIM_OK) break;
-    rc = hipMemcpy(out, d_out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost) == hipSuccess ? MSIM_OK : MSIM_E_HIP;
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_meta, (void *)d_out, ws}) if (q) (void)msim_dev_free(q);
-  return rc;
+  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
+  SlabBatch b;
+  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
+  DevBuf d_out, ws; size_t ws_cap = 0;
+  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  UParams up;
+  up.rows = b.rows.get<msim_op>(); up.meta = b.meta.get<msim_inst_meta>(); up.out = d_out.get<msim_check_result>();
+  up.max_rows = max_rows; up.ws = nullptr; up.table_slots = 0; up.first = 0;
+  if (int rc = unique_dev_run(ctx, up, n_histories, ws.addr(), &ws_cap, nullptr, false)) return rc;
+  MSIM_HIP_TRY(ctx, hipMemcpy(out, up.out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost));
+  return MSIM_OK;
 }
