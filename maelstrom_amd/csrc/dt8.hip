@@ -21,7 +21,6 @@
 #include <cstdio>
 
 #include "group8.h"
-#include "layout_thresholds.h"
 
 namespace {
 
@@ -1130,7 +1129,6 @@ uint64_t msim_dt8_extra_scratch_words(const msim_config &c) {
 
 hipError_t msim_launch_dt8(const KParams &kp, uint32_t n, hipStream_t st) {
   const msim_config &c = kp.cfg;
-  if (n < MSIM_DT8_MIN_CLUSTERS && !(kp.dev_flags & 0x400u)) return MSIM_LAYOUT_DOES_NOT_FIT;   // the kernel is latency-bound: below the measured crossover one cluster per wavefront is faster
   M8Params tp;
   tp.k = kp; tp.n_inst = n;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;

@@ -19,7 +19,6 @@
 
 #include "sim_kernels.h"
 #include "group16.h"
-#include "layout_thresholds.h"
 
 namespace {
 
@@ -345,7 +344,6 @@ uint64_t msim_dtg4_extra_scratch_words(const msim_config &c) {
 
 hipError_t msim_launch_dtg4(const KParams &kp, uint32_t n, hipStream_t st) {
   const msim_config &c = kp.cfg;
-  if (n < (kp.N == 1 ? MSIM_DTG4_MIN_CLUSTERS : MSIM_DTG4_MIN_CLUSTERS / 2u) && !(kp.dev_flags & 0x400u)) return MSIM_LAYOUT_DOES_NOT_FIT;   // (two nodes and more: even from 8192 on, profiles/r06f_dtg4_threshold_sweep.jsonl)
   D4Params rp;
   rp.k = kp; rp.n_inst = n;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;

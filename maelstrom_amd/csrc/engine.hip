@@ -20,19 +20,18 @@
 //
 // This file holds the host runtime and msim_run's choice of a kernel.  The one-cluster-per-wavefront kernels (sim_kernel*.inc, collected by
 // sim_kernels.h) are instantiated by the k_*.hip units; denser layouts live in
-// their own translation units and are taken where a configuration and the batch fit them (DESIGN.md §4.1b has the table): duo.hip (two
+// their own translation units and are taken where a configuration and the batch fit them (launch_plan.h has the table): duo.hip (two
 // broadcast clusters per wavefront, the headline), raft4.hip (four), txn8.hip / mk8.hip / hat8.hip / uid8.hip / crdt8.hip / bcast8.hip
 // (eight: the transactional programs, echo / unique-ids, the CRDTs, the broadcast programs at tutorial sizes).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
-
 #include "sim_kernels.h"   // the layout constants of the kernels; this unit instantiates none of them (the k_*.hip units do)
+#include "launch_plan.h"   // the packed layouts, the node programs, msim_plan_launch
 
 // Reference (shuffle) versions, used only by the self-test to validate the DPP encodings on hardware.
 __device__ u32 wave_min_ref(u32 v) { for (int o = 32; o; o >>= 1) v = min(v, (u32)__shfl_xor((int)v, o)); return v; }
@@ -52,7 +51,6 @@ __global__ void wave_selftest_kernel(const u32 *in, u32 *out) {
   bad |= lane_get(v, (lane * 7 + 3) & 63) != (u32)__shfl((int)v, (int)((lane * 7 + 3) & 63));
   out[blockIdx.x * 64 + lane] = bad;
 }
-
 
 // =====================================================================================================
 // Host runtime
@@ -153,74 +151,23 @@ extern "C" int msim_create(const msim_config *cfg, int device, msim_ctx **out, c
 
 // multi-key transactional node: thunk ids a node may hand out (every attempt of a transaction writes its keys again: x4 for the
 // retries) and the slots of its thunk cache (what it wrote + what it read: twice that, load factor 1/2)
-static uint32_t mk_tcap(const msim_config &c) {
+uint32_t msim_mk_tcap(const msim_config &c) {
   const double ops = (double)c.rate_mhz * (double)c.time_limit_ms / 1e6 * 1.125 + 64.0;
   uint32_t t = 64; while (t < 4.0 * ops * c.max_txn_length / c.n_nodes + 64.0) t <<= 1;
   return t;
 }
-static uint32_t mk_ccap(const msim_config &c) { return 4 * mk_tcap(c); }
+uint32_t msim_mk_ccap(const msim_config &c) { return 4 * msim_mk_tcap(c); }
 
-// per-instance scratch = [protocol scratch][spill area: n_nodes x spill_capacity envelopes]
-static uint32_t raft_log_cap(const msim_config &c) {  // every client op is appended at most once, by the leader that takes it
+uint32_t msim_raft_log_cap(const msim_config &c) {  // every client op is appended at most once, by the leader that takes it
   const double expected = (double)c.rate_mhz * (double)c.time_limit_ms / 1e6;
   return (uint32_t)(expected + expected / 8.0) + 64 + 8;
 }
-static uint64_t proto_scratch_words(const msim_config &c) {
-  uint64_t w = 4;
-  if (c.node_program == MSIM_NODE_RAFT) w = (uint64_t)c.n_nodes * raft_log_cap(c) * 2 + (uint64_t)c.n_nodes * R_ARENA_WORDS;
-  if (c.node_program == MSIM_NODE_BCAST_ACK_RETRY) w = (uint64_t)c.n_nodes * c.max_values * 3;
-  // batched gossip: the nodes' u16 arrival logs, then 16 bytes per (node, peer) link (sim_kernel_general.inc g_log / g_link)
-  if (c.node_program == MSIM_NODE_BCAST_BATCH) w = (uint64_t)c.n_nodes * (c.max_values / 2) + (uint64_t)c.n_nodes * c.n_nodes * 4;
-  if (c.node_program == MSIM_NODE_TXN_SINGLE_KEY) w = (uint64_t)c.max_values * (c.max_writes_per_key + 1);  // elements + counts per key
-  if (c.node_program == MSIM_NODE_TXN_MULTI_KEY)   // elements, counts, map position, entry version, thunk counts, thunk versions + ids, the nodes' caches, the replica bytes
-    w = (uint64_t)c.max_values * (c.max_writes_per_key + 4 + 2 * (c.max_writes_per_key + 1)) + (uint64_t)c.n_nodes * mk_ccap(c) + (uint64_t)c.n_nodes * mk_tcap(c) / 4 + 4 +
-        (uint64_t)c.n_nodes * ((c.concurrency > c.n_nodes ? MKG_SLOTS : MK_SLOTS) - MK_SL) * mk_slot_words(8);   // + the transaction slots that are not in LDS (several workers per node: mkg_kernel<> has MKG_SLOTS)
-  if (c.node_program == MSIM_NODE_TXN_DATOMIC) w = dt_scratch_words(c);   // elements, counts, first versions, key hashes, the tree nodes, the nodes' caches, a round's write lists
-  if (c.node_program == MSIM_NODE_KAFKA) w = (uint64_t)KF_KEYS * (2 * (c.max_writes_per_key + 1) + 1);   // the logs + the committed-offset lists of the keys
-  if (c.node_program == MSIM_NODE_TXN_RW_HAT) {  // registers per node + txn table + pending masks (bytes) + replicate lists
-    const uint64_t G = c.max_rows / 2;
-    w = (uint64_t)c.n_nodes * c.max_values + 2 * G + ((uint64_t)c.n_nodes * G + 3) / 4 + c.replication_words;
-  }
-  if (c.node_program == MSIM_NODE_G_SET || c.node_program == MSIM_NODE_PN_COUNTER) {
-    const uint64_t total_ms = (uint64_t)c.time_limit_ms + c.quiesce_ms + 2ull * c.client_timeout_ms;
-    const uint64_t ticks = total_ms / 5000 + 3;
-    w = ticks * c.n_nodes * (c.max_values / 32);
-    // wide clusters: + the union of every tick's snapshots (wide_union_off: what a node that received all of a tick merges in one go) + the nodes' sets
-    if (c.n_nodes > 32) w = ((w + ticks * (c.max_values / 32) + 3) & ~3ull) + (c.node_program == MSIM_NODE_G_SET ? wide_sparse_words(ticks, c.max_values / 32) : 0) + (((uint64_t)c.n_nodes * (c.max_values / 32) + 3) & ~3ull);   // (+ the ticks' frequent elements and rare holders: sim_kernel_wide.inc SPARSE)
-  }
-  const bool bcast_ff = c.node_program == MSIM_NODE_BCAST_FF || c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK;
-  const bool bcast_rpc = c.node_program == MSIM_NODE_BCAST_ACK_RETRY || c.node_program == MSIM_NODE_BCAST_RPC_ALL;
-  if (bcast_ff && c.n_nodes > 32) w = 4 + (((uint64_t)c.n_nodes * (c.max_values / 32) + 3) & ~3ull);  // wide clusters: the nodes' sets
-  // wide clusters, acknowledged gossip: 128-bit unacked masks per (node, value), the retry FIFO, the nodes' sets
-  if (bcast_rpc && c.n_nodes > 32) w = (uint64_t)c.n_nodes * c.max_values * 6 + (((uint64_t)c.n_nodes * (c.max_values / 32) + 3) & ~3ull);
-  return (w + 3) & ~3ull;  // keep the spill area 16-byte aligned
-}
-static uint64_t scratch_words(const msim_config &c) {
-  const uint64_t queues = c.n_nodes + (c.node_program == MSIM_NODE_KAFKA || c.node_program == MSIM_NODE_TXN_SINGLE_KEY || c.node_program == MSIM_NODE_LIN_KV_PROXY || c.node_program == MSIM_NODE_TSO_IDS ? 1 : c.node_program == MSIM_NODE_TXN_MULTI_KEY || c.node_program == MSIM_NODE_TXN_DATOMIC ? 2 : 0);  // + the services
-  uint64_t w = proto_scratch_words(c) + queues * c.spill_capacity * 4;
-  if (c.node_program == MSIM_NODE_LIN_KV_PROXY || c.node_program == MSIM_NODE_TSO_IDS) w += (uint64_t)(c.concurrency > c.n_nodes ? c.concurrency : c.n_nodes) * (R_CLIENT_CAP - PX_CL) * 4;   // svc_kernel<>: the clients' inboxes beyond PX_CL envelopes
-  if (msim_raft4_eligible(c)) w += msim_raft4_extra_scratch_words(c);   // raft4.hip keeps fewer envelopes in LDS
-  if (msim_svc4_eligible(c)) w += msim_svc4_extra_scratch_words(c);     // svc4.hip likewise
-  if (msim_txng4_eligible(c)) w += msim_txng4_extra_scratch_words(c);   // txng4.hip likewise
-  if (msim_dtg4_eligible(c)) w += msim_dtg4_extra_scratch_words(c);     // dtg4.hip likewise
-  if (msim_txn8_eligible(c)) w += msim_txn8_extra_scratch_words(c);     // txn8.hip likewise
-  if (msim_mk8_eligible(c)) w += msim_mk8_extra_scratch_words(c);       // mk8.hip likewise
-  if (msim_dt8_eligible(c)) w += msim_dt8_extra_scratch_words(c);       // dt8.hip likewise (+ the nodes' save stacks)
-  if (msim_hat8_eligible(c)) w += msim_hat8_extra_scratch_words(c);     // hat8.hip likewise
-  if (msim_kafka8_eligible(c)) w += msim_kafka8_extra_scratch_words(c); // kafka8.hip likewise
-  if (msim_uid8_eligible(c)) w += msim_uid8_extra_scratch_words(c);     // uid8.hip likewise
-  if (msim_crdt8_eligible(c)) w += msim_crdt8_extra_scratch_words(c);   // crdt8.hip likewise
-  if (msim_bcast8_eligible(c)) w += msim_bcast8_extra_scratch_words(c); // bcast8.hip likewise
-  // duo.hip: the nodes' sets, last and on a 128-byte boundary of the instance's scratch (the total stays a multiple of 32 words)
-  if (msim_duo_eligible(c)) w = ((w + 31) & ~31ull) + msim_duo_extra_scratch_words(c);
-  return w;
-}
 
-static int ensure_buffers(msim_ctx *ctx, uint32_t n) {
+static int ensure_buffers(msim_ctx *ctx, uint32_t n, const LaunchPlan &plan) {
   if (n <= ctx->cap_inst) return MSIM_OK;
   free_buffers(ctx);
   const msim_config &c = ctx->cfg;
-  ctx->scratch_words_per_inst = scratch_words(c);
+  ctx->scratch_words_per_inst = plan.kp.scratch_words;
   MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_rows, (size_t)n * c.max_rows * sizeof(msim_op)));
   MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_payload, (size_t)n * c.max_payload_words * 4));
   MSIM_HIP_TRY(ctx, msim_dev_malloc(&ctx->d_stats, (size_t)n * sizeof(msim_net_stats)));
@@ -232,10 +179,54 @@ static int ensure_buffers(msim_ctx *ctx, uint32_t n) {
   return MSIM_OK;
 }
 
-// The workloads whose msim_check is one launch of checker.hip's kernel over the slabs (msim_check_launch, the final return of
-// msim_check): set-full for broadcast and g-set, and echo.  Every other checker sizes host work from a copy of the instance meta.
-static bool check_launch_route(const msim_config &c) {
-  return c.workload == MSIM_WL_ECHO || c.workload == MSIM_WL_BROADCAST || c.workload == MSIM_WL_G_SET;
+// The workloads with a checker on the host cores and one on the device (the others: set-full / echo, msim_check below).
+struct WorkloadCheck { uint32_t workload; int (*host)(msim_ctx *); int (*device)(msim_ctx *); bool host_rechecks; };   // (host_rechecks: the device pass hands histories it cannot decide to the host, counted in lin_host_rechecks)
+static const WorkloadCheck *workload_check(uint32_t workload) {
+  static const WorkloadCheck table[] = {
+    {MSIM_WL_LIN_KV, [](msim_ctx *x) { return msim_check_lin_kv_host(x); }, [](msim_ctx *x) { return msim_check_lin_kv_device(x); }, true},
+    {MSIM_WL_TXN_LIST_APPEND, msim_check_txn_host, [](msim_ctx *x) { return msim_check_txn_device(x); }, true},
+    {MSIM_WL_TXN_RW_REGISTER, msim_check_txn_host, [](msim_ctx *x) { return msim_check_rw_device(x); }, true},
+    {MSIM_WL_KAFKA, msim_check_kafka_host, msim_check_kafka_device, true},
+    {MSIM_WL_PN_COUNTER, msim_check_pn_host, msim_check_pn_device, true},
+    {MSIM_WL_G_COUNTER, msim_check_pn_host, msim_check_pn_device, true},
+    {MSIM_WL_UNIQUE_IDS, msim_check_unique_host, msim_check_unique_device, false},
+  };
+  for (const WorkloadCheck &w : table) if (w.workload == workload) return &w;
+  return nullptr;
+}
+
+static int poison_buffers(msim_ctx *ctx, hipStream_t st) {
+  const msim_config &c = ctx->cfg;
+  // developer check for reads of memory no kernel of this launch wrote: MSIM_POISON=<byte> fills every device buffer of the context
+  // with that byte before each launch (HBM comes back from hipMalloc with whatever its last owner left there); results must not depend on it
+  static const int poison = []() { const char *p = std::getenv("MSIM_POISON"); return p ? (int)(std::strtoul(p, nullptr, 0) & 0xFFu) : -1; }();
+  if (poison >= 0) {
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_rows, poison, (size_t)ctx->cap_inst * c.max_rows * sizeof(msim_op), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_payload, poison, (size_t)ctx->cap_inst * c.max_payload_words * 4, st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, poison, (size_t)ctx->cap_inst * sizeof(msim_net_stats), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_meta, poison, (size_t)ctx->cap_inst * sizeof(msim_inst_meta), st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_scratch, poison, (size_t)ctx->cap_inst * ctx->scratch_words_per_inst * 4, st));
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check, poison, (size_t)ctx->cap_inst * sizeof(msim_check_result), st));
+    if (ctx->d_journal) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_journal, poison, (size_t)ctx->cap_inst * c.journal_capacity * sizeof(msim_event), st));
+    if (ctx->d_check_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check_scratch, poison, ctx->cap_check_scratch, st));
+    if (ctx->d_perf_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_perf_scratch, poison, ctx->cap_perf_scratch, st));
+  }
+  return MSIM_OK;
+}
+
+// Queues the simulation kernel of a launch: several clusters per wavefront where a packed layout takes this configuration and this batch
+// (launch_plan.h), else one.  *e = what the launch answered, *kname = the kernel that took it.
+static int launch_simulation(msim_ctx *ctx, const KParams &kp, const LaunchPlan &plan, uint32_t n, hipStream_t st, hipError_t *e, const char **kname) {
+  bool duo_required = false;
+  *e = msim_launch_packed(kp, n, st, kname, &duo_required);
+  if (duo_required) { ctx->err = "MSIM_DEV_FLAGS bit 10: the two-clusters-per-wavefront layout was required but this cluster state does not fit it"; return MSIM_E_UNSUPPORTED; }
+  if (*e == MSIM_LAYOUT_DOES_NOT_FIT && (kp.dev_flags & 0x400u) && kp.cfg.node_program == MSIM_NODE_RAFT) { ctx->err = "MSIM_DEV_FLAGS bit 10: the four-clusters-per-wavefront Raft layout was required but does not apply"; return MSIM_E_UNSUPPORTED; }
+  if (*e == MSIM_LAYOUT_DOES_NOT_FIT) {   // not eligible, below the floor, or the cluster state does not fit the dense layout: one cluster per wavefront (k_*.hip)
+    const Launcher1 &l = msim_one_cluster_launcher(*plan.program, kp.cfg);
+    *e = l.fn(kp, n, plan.lds, st);
+    if (*e != MSIM_LAYOUT_DOES_NOT_FIT) *kname = l.name;
+  }
+  return MSIM_OK;
 }
 
 static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, bool blocking) {
@@ -253,56 +244,21 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
     ctx->check_queued = false; ctx->check_armed = false;
     if (!own_stream) MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  int rc = ensure_buffers(ctx, n);
-  if (rc != MSIM_OK) return rc;
   const msim_config &c = ctx->cfg;
+  const uint32_t flags = msim_dev_flags(ctx);
+  const LaunchPlan plan = msim_plan_launch(c, flags);
+  if (plan.rc != MSIM_OK) { ctx->err = plan.err; return plan.rc; }   // (a configuration that cannot be launched allocates nothing)
+  int rc = ensure_buffers(ctx, n, plan);
+  if (rc != MSIM_OK) return rc;
   // an armed context queues the checker straight behind this simulation (below, after ev1).  Its scratch grows HERE, in front of the
   // launch: a hipFree / hipMalloc between the two kernels would stall every context's launches.  A failure is msim_check's to report.
-  const bool queue_check = ctx->check_armed && own_stream && check_launch_route(c) && !(msim_dev_flags(ctx) & 0x40000u) &&
+  // (the workloads without a row in workload_check: msim_check is one launch of checker.hip's kernel over the slabs)
+  const bool queue_check = ctx->check_armed && own_stream && !workload_check(c.workload) && !(flags & 0x40000u) &&
                            msim_check_reserve(ctx, n) == MSIM_OK;
-  KParams kp;
-  std::memset(&kp, 0, sizeof kp);
-  kp.cfg = c; kp.first_instance = first;
+  KParams kp = plan.kp;   // + what belongs to this launch
+  kp.first_instance = first;
   kp.rows = ctx->d_rows; kp.payload = ctx->d_payload; kp.stats = ctx->d_stats; kp.meta = ctx->d_meta;
-  kp.scratch = ctx->d_scratch; kp.scratch_words = ctx->scratch_words_per_inst;
-  kp.journal = reinterpret_cast<uint4 *>(ctx->d_journal);
-  kp.N = c.n_nodes; kp.C = c.concurrency; kp.CS = c.concurrency > c.n_nodes ? c.concurrency : c.n_nodes;
-  kp.W = c.max_values / 32;
-  kp.cap_node = c.inbox_capacity; kp.spill_cap = c.spill_capacity; kp.spill_off = proto_scratch_words(c);
-  const uint64_t period_us = 1000000000ull / (c.rate_mhz ? c.rate_mhz : 1);
-  if (2 * period_us > 0xFFFFFFFFull || 2000ull * c.nemesis_interval_ms > 0xFFFFFFFFull) { ctx->err = "rate too low / nemesis interval too long for u32 microseconds"; return MSIM_E_INVALID; }
-  kp.gen_period2_us = (u32)(2 * period_us);
-  kp.nem_period2_us = (u32)(2000ull * c.nemesis_interval_ms);
-  const bool is_raft = c.node_program == MSIM_NODE_RAFT;
-  kp.raft_log_cap = is_raft ? raft_log_cap(c) : 0;
-  kp.dev_flags = msim_dev_flags(ctx);
-  const bool wide = c.n_nodes > 32;
-  const bool wide_setl = wide_sets_in_lds(c, kp.dev_flags);   // (no row staging in that layout)
-  const bool wide_crdt = wide && (c.node_program == MSIM_NODE_G_SET || c.node_program == MSIM_NODE_PN_COUNTER);   // (rows unstaged: sim_kernel_wide.inc ROWS_DIRECT)
-  size_t off = (wide_setl || wide_crdt) ? 0 : (wide ? WIDE_STAGE_ROWS : STAGE_ROWS) * 16;
-  const bool is_txn = c.node_program == MSIM_NODE_TXN_SINGLE_KEY, is_px = c.node_program == MSIM_NODE_LIN_KV_PROXY || c.node_program == MSIM_NODE_TSO_IDS;
-  const bool is_hat = c.node_program == MSIM_NODE_TXN_RW_HAT, is_mk = c.node_program == MSIM_NODE_TXN_MULTI_KEY, is_kf = c.node_program == MSIM_NODE_KAFKA, is_dt = c.node_program == MSIM_NODE_TXN_DATOMIC;
-  kp.mk_tcap = is_mk ? mk_tcap(c) : is_dt ? dt_tcap(c) : 0; kp.mk_ccap = is_mk ? mk_ccap(c) : 0;
-  kp.off_inbox = (u32)off;
-  const bool dt_many = (is_dt || is_mk) && c.concurrency > c.n_nodes;   // dtg_kernel<> / mkg_kernel<>: a lane per endpoint, a client inbox per worker slot
-  const bool txn_many = (is_txn || is_kf) && c.concurrency > c.n_nodes; // txng_kernel<> / kafkag_kernel<>: likewise
-  off += (is_mk || is_dt) ? ((size_t)(kp.N + 2) * kp.cap_node + (size_t)(dt_many ? kp.CS : kp.N) * T_CLIENT_CAP) * 16 : is_hat ? ((size_t)kp.N * kp.cap_node + (size_t)kp.CS * T_CLIENT_CAP) * 16   /* (hatg_kernel<>: an inbox per worker slot; CS == N otherwise) */ : is_px ? ((size_t)(kp.N + 1) * kp.cap_node + (size_t)kp.CS * PX_CL) * 16 : (is_txn || is_kf) ? ((size_t)(kp.N + 1) * kp.cap_node + (size_t)(txn_many ? kp.CS : kp.N) * T_CLIENT_CAP) * 16
-                : ((size_t)kp.N * kp.cap_node + (size_t)kp.CS * (is_raft ? R_CLIENT_CAP : CLIENT_INBOX_CAP)) * 16 + wide_client_bytes(c);   // (wide: + the pairs' client state)
-  kp.off_seen = (u32)off;
-  off += is_mk ? ((size_t)kp.N * MK_SL * mk_slot_words(mk_keys_for(c)) + (size_t)kp.N * mk_keys_for(c) * 3 + 36) * 4   // transactions in flight (the first MK_SL per node), a round's messages per node, the generator's key pool
-       : is_dt ? ((size_t)kp.N * (dt_many ? DG_WORDS : DC_WORDS) + 36) * 4   // the nodes' transactions (lock holder, waiting queue, save stack), the generator's key pool
-       : is_hat ? 36 * 4   // the generator's key pool
-       : is_px ? (size_t)kp.N * PX_SLOTS * 8 + ((c.node_program == MSIM_NODE_LIN_KV_PROXY && c.proxy_service == MSIM_SVC_SEQ_KV) ? 34 : 2) * 256 + 64 * 4   // callbacks per node + service states (seq-kv: + its ring of 32) + seq-kv indices
-       : is_txn ? (size_t)kp.N * (txn_many ? TG_SLOTS : TXN_SLOTS) * 16 + 36 * 4   // transactions in flight per node + the generator's key pool
-       : is_kf ? ((size_t)kp.N * (txn_many ? KFG_SLOTS : KF_SLOTS) * KSW + (size_t)kp.N * KF_KEYS + (size_t)(txn_many ? kp.CS : kp.N) * KF_KEYS + 36 + 2 * KF_KEYS) * 4   // request handlers, offset caches, client offsets (per worker slot), key pool, lin-kv lengths
-       : is_raft ? (size_t)kp.N * 256 + (size_t)kp.N * kp.N * 3 * 4   // KV state + next/match index + append_entries refs
-       : wide ? (wide_setl ? (size_t)kp.N * kp.W * 4 : 0) + wide_pending_bytes(c)   // the sets of a wide cluster live in HBM scratch unless they fit LDS (wide_sets_in_lds); + the CRDTs' delivered-but-unmerged replicates
-                 : (size_t)kp.N * kp.W * 4;
-  off = (off + 15) & ~(size_t)15;
-  kp.off_misc = (u32)off; if (c.nemesis_mask) off += (wide ? 128 : 64) * 4;  // shuffle scratch, only the partition nemesis needs it
-  const size_t lds = off;
-  if (lds > 160 * 1024) { ctx->err = "cluster state exceeds the 160 KiB LDS of a CU (lower inbox_capacity / max_values)"; return MSIM_E_INVALID; }
-
+  kp.scratch = ctx->d_scratch; kp.journal = reinterpret_cast<uint4 *>(ctx->d_journal);
   // The slabs this launch overwrites are what a zero-copy consumer of the previous run (msim_device_buffers_get) reads — bench.py's
   // sums are queued on the null stream and never waited for.  Since the host no longer waits in msim_check for a check that was queued
   // ahead, it can launch while those kernels still wait for a place on the chip (measured: 3 of 5 benchmark runs then summed rows of
@@ -314,71 +270,11 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
     MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev_null, nullptr));
     MSIM_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_null, 0));
   }
-  // developer check for reads of memory no kernel of this launch wrote: MSIM_POISON=<byte> fills every device buffer of the context
-  // with that byte before each launch (HBM comes back from hipMalloc with whatever its last owner left there); results must not depend on it
-  static const int poison = []() { const char *p = std::getenv("MSIM_POISON"); return p ? (int)(std::strtoul(p, nullptr, 0) & 0xFFu) : -1; }();
-  if (poison >= 0) {
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_rows, poison, (size_t)ctx->cap_inst * c.max_rows * sizeof(msim_op), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_payload, poison, (size_t)ctx->cap_inst * c.max_payload_words * 4, st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, poison, (size_t)ctx->cap_inst * sizeof(msim_net_stats), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_meta, poison, (size_t)ctx->cap_inst * sizeof(msim_inst_meta), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_scratch, poison, (size_t)ctx->cap_inst * ctx->scratch_words_per_inst * 4, st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check, poison, (size_t)ctx->cap_inst * sizeof(msim_check_result), st));
-    if (ctx->d_journal) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_journal, poison, (size_t)ctx->cap_inst * c.journal_capacity * sizeof(msim_event), st));
-    if (ctx->d_check_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_check_scratch, poison, ctx->cap_check_scratch, st));
-    if (ctx->d_perf_scratch) MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_perf_scratch, poison, ctx->cap_perf_scratch, st));
-  }
+  if ((rc = poison_buffers(ctx, st)) != MSIM_OK) return rc;
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));   // (the launch's duration is read from these events on its own stream: msim_last_kernel_ms)
-  hipError_t e;
   const char *kname = "?";   // the kernel this launch took: named on stderr under MSIM_DEV_FLAGS bit 12
-  auto took = [&](hipError_t r, const char *k) { if (r != MSIM_LAYOUT_DOES_NOT_FIT) kname = k; return r; };
-  // the headline layout: two clusters per wavefront (duo.hip); MSIM_DEV_FLAGS bit 9 keeps the one-cluster kernels
-  e = MSIM_LAYOUT_DOES_NOT_FIT;
-  if (msim_duo_eligible(c) && !(kp.dev_flags & 0x200u) && !((kp.dev_flags & 0x8000u) && msim_bcast8_eligible(c))) {   // (bit 15: small clusters eight per wavefront instead)
-    e = took(msim_launch_duo(kp, n, st), "duo");
-    if (e == MSIM_LAYOUT_DOES_NOT_FIT && (kp.dev_flags & 0x400u)) { ctx->err = "MSIM_DEV_FLAGS bit 10: the two-clusters-per-wavefront layout was required but this cluster state does not fit it"; return MSIM_E_UNSUPPORTED; }
-  }
-  // the broadcast programs at the tutorial's cluster sizes: eight clusters per wavefront (bcast8.hip) where the headline layout does not apply
-  if (e == MSIM_LAYOUT_DOES_NOT_FIT && msim_bcast8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_bcast8(kp, n, st), "bcast8");
-  // Raft: four clusters per wavefront (raft4.hip) when a cluster fits a 16-lane group
-  if (msim_raft4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_raft4(kp, n, st), "raft4");
-  // the lin-kv proxy over lin-kv / lww-kv: four clusters per wavefront (svc4.hip) for large batches when a cluster and its service fit a 16-lane group
-  if (msim_svc4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_svc4(kp, n, st), c.node_program == MSIM_NODE_TSO_IDS ? "svc4<TSO>" : "svc4");
-  // txn-list-append, single-root node with several workers per node: four clusters per wavefront (txng4.hip) for large batches when nodes + workers + lin-kv fit a 16-lane group
-  if (msim_txng4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_txng4(kp, n, st), "txng4");
-  // the Datomic-style node with several workers per node: four clusters per wavefront (dtg4.hip) for large batches when nodes + workers + the two services fit a 16-lane group
-  if (msim_dtg4_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_dtg4(kp, n, st), "dtg4");
-  // txn-list-append: eight clusters per wavefront (txn8.hip) when a cluster fits an 8-lane group
-  if (msim_txn8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_txn8(kp, n, st), "txn8");
-  // the canonical txn-list-append node: eight clusters per wavefront (mk8.hip) when a cluster fits an 8-lane group
-  if (msim_mk8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_mk8(kp, n, st), "mk8");
-  // the Datomic-style txn-list-append node: eight clusters per wavefront (dt8.hip) when a cluster fits an 8-lane group
-  if (msim_dt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_dt8(kp, n, st), "dt8");
-  // txn-rw-register over the highly-available-transactions node: eight clusters per wavefront (hat8.hip)
-  if (msim_hat8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_hat8(kp, n, st), "hat8");
-  // kafka: eight clusters per wavefront (kafka8.hip) for large batches
-  if (msim_kafka8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_kafka8(kp, n, st), "kafka8");
-  // echo / unique-ids (flake ids): eight clusters per wavefront (uid8.hip) for large batches of small clusters
-  if (msim_uid8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_uid8(kp, n, st), "uid8");
-  // g-set / pn-counter / g-counter: eight clusters per wavefront (crdt8.hip) for large batches of small clusters
-  if (msim_crdt8_eligible(c) && !(kp.dev_flags & 0x200u)) e = took(msim_launch_crdt8(kp, n, st), "crdt8");
-  if (e == MSIM_LAYOUT_DOES_NOT_FIT && (kp.dev_flags & 0x400u) && is_raft) { ctx->err = "MSIM_DEV_FLAGS bit 10: the four-clusters-per-wavefront Raft layout was required but does not apply"; return MSIM_E_UNSUPPORTED; }
-  if (e == MSIM_LAYOUT_DOES_NOT_FIT) switch (c.node_program) {   // not eligible, or the cluster state does not fit the dense layout: one cluster per wavefront (k_*.hip)
-    case MSIM_NODE_ECHO: case MSIM_NODE_FLAKE_IDS: e = took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
-    case MSIM_NODE_G_SET: e = wide ? took(msim_launch_wide_gset(kp, n, lds, st), "wide_gset") : took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
-    case MSIM_NODE_PN_COUNTER: e = wide ? took(msim_launch_wide_pn(kp, n, lds, st), "wide_pn") : took(msim_launch_general_a(kp, n, lds, st), "general_a"); break;
-    case MSIM_NODE_BCAST_FF: case MSIM_NODE_BCAST_FF_ECHOBACK: e = wide ? took(msim_launch_wide_bcast(kp, n, lds, st), "wide_bcast") : took(msim_launch_general_b(kp, n, lds, st), "general_b"); break;
-    case MSIM_NODE_BCAST_ACK_RETRY: case MSIM_NODE_BCAST_RPC_ALL: e = wide ? took(msim_launch_wide_ack(kp, n, lds, st), "wide_ack") : took(msim_launch_general_c(kp, n, lds, st), "general_c"); break;
-    case MSIM_NODE_BCAST_BATCH: e = took(msim_launch_general_d(kp, n, lds, st), "general_d"); break;
-    case MSIM_NODE_RAFT: e = took(msim_launch_raft1(kp, n, lds, st), "raft1"); break;
-    case MSIM_NODE_LIN_KV_PROXY: case MSIM_NODE_TSO_IDS: e = took(msim_launch_svc1(kp, n, lds, st), "svc1"); break;   // (lin-tso ids: the proxy's layout with the timestamp oracle on the service lane)
-    case MSIM_NODE_TXN_SINGLE_KEY: e = txn_many ? took(msim_launch_txng(kp, n, lds, st), "txng") : took(msim_launch_txn1(kp, n, lds, st), "txn1"); break;
-    case MSIM_NODE_TXN_MULTI_KEY: e = dt_many ? took(msim_launch_mkg(kp, n, lds, st), "mkg") : took(msim_launch_mk1(kp, n, lds, st), "mk1"); break;
-    case MSIM_NODE_TXN_DATOMIC: e = dt_many ? took(msim_launch_dtg(kp, n, lds, st), "dtg") : took(msim_launch_dt1(kp, n, lds, st), "dt1"); break;
-    case MSIM_NODE_KAFKA: e = txn_many ? took(msim_launch_kafkag(kp, n, lds, st), "kafkag") : took(msim_launch_kafka1(kp, n, lds, st), "kafka1"); break;
-    case MSIM_NODE_TXN_RW_HAT: e = c.concurrency > c.n_nodes ? took(msim_launch_hatg(kp, n, lds, st), "hatg") : took(msim_launch_hat1(kp, n, lds, st), "hat1"); break;
-    default: ctx->err = "node program not built into this engine"; return MSIM_E_UNSUPPORTED;
-  }
+  hipError_t e;
+  if ((rc = launch_simulation(ctx, kp, plan, n, st, &e, &kname)) != MSIM_OK) return rc;
   if (kp.dev_flags & 0x1000u) std::fprintf(stderr, "[layout] %s %u\n", kname, n);   // developer / tests: which kernel this launch took
   if (e != hipSuccess) { ctx->err = std::string("kernel launch: ") + hipGetErrorString(e); return MSIM_E_HIP; }
   ctx->n_inst = n; ctx->first_instance = first;
@@ -414,30 +310,8 @@ extern "C" int msim_run_async(msim_ctx *ctx, uint64_t first_instance, uint32_t n
 extern "C" int msim_check(msim_ctx *ctx) {
   if (!ctx) return MSIM_E_INVALID;
   if (!ctx->ran) { ctx->err = "msim_check before msim_run"; return MSIM_E_RANGE; }
-  if (ctx->cfg.workload == MSIM_WL_LIN_KV) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_lin_kv_host(ctx) : msim_check_lin_kv_device(ctx);
-  }
-  if (ctx->cfg.workload == MSIM_WL_TXN_LIST_APPEND) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_txn_host(ctx) : msim_check_txn_device(ctx);
-  }
-  if (ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_txn_host(ctx) : msim_check_rw_device(ctx);
-  }
-  if (ctx->cfg.workload == MSIM_WL_KAFKA) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_kafka_host(ctx) : msim_check_kafka_device(ctx);
-  }
-  if (ctx->cfg.workload == MSIM_WL_PN_COUNTER || ctx->cfg.workload == MSIM_WL_G_COUNTER) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_pn_host(ctx) : msim_check_pn_device(ctx);
-  }
-  if (ctx->cfg.workload == MSIM_WL_UNIQUE_IDS) {
-    return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
-           msim_check_unique_host(ctx) : msim_check_unique_device(ctx);
-  }
+  if (const WorkloadCheck *wc = workload_check(ctx->cfg.workload))
+    return (msim_dev_flags(ctx) & 0x800u) ? wc->host(ctx) : wc->device(ctx);   // bit 11: keep the check on the host cores
   // set-full (broadcast, g-set) and echo: one launch of checker.hip's kernel.  run_impl has queued it behind the simulation on an armed
   // context: then this call only waits for it.  Otherwise the kernel is launched here — also for a second msim_check of the same run —
   // and a caller that checks a launch on the context's own stream arms the context for its next launches.
@@ -659,7 +533,10 @@ extern "C" int msim_set_dev_flags(msim_ctx *ctx, uint32_t flags) {
   return MSIM_OK;
 }
 
-extern "C" uint32_t msim_check_host_rechecks(const msim_ctx *ctx) { return ctx && ctx->checked && (ctx->cfg.workload == MSIM_WL_LIN_KV || ctx->cfg.workload == MSIM_WL_TXN_LIST_APPEND || ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER || ctx->cfg.workload == MSIM_WL_PN_COUNTER || ctx->cfg.workload == MSIM_WL_G_COUNTER || ctx->cfg.workload == MSIM_WL_KAFKA) ? ctx->lin_host_rechecks : 0u; }
+extern "C" uint32_t msim_check_host_rechecks(const msim_ctx *ctx) {
+  const WorkloadCheck *wc = ctx && ctx->checked ? workload_check(ctx->cfg.workload) : nullptr;
+  return wc && wc->host_rechecks ? ctx->lin_host_rechecks : 0u;
+}
 
 extern "C" int msim_check_results(msim_ctx *ctx, const msim_check_result **results, uint32_t *n) {
   if (!ctx) return MSIM_E_INVALID;

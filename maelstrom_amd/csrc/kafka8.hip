@@ -23,7 +23,6 @@
 #include <cstdio>
 
 #include "group8.h"
-#include "layout_thresholds.h"
 
 namespace {
 
@@ -672,7 +671,6 @@ uint64_t msim_kafka8_extra_scratch_words(const msim_config &c) {
 
 hipError_t msim_launch_kafka8(const KParams &kp, uint32_t n, hipStream_t st) {
   const msim_config &c = kp.cfg;
-  if (n < MSIM_KAFKA8_MIN_CLUSTERS && !(kp.dev_flags & 0x400u)) return MSIM_LAYOUT_DOES_NOT_FIT;
   K8Params up;
   up.k = kp; up.n_inst = n;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;

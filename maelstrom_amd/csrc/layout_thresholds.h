@@ -1,6 +1,6 @@
-// layout_thresholds.h — the launch sizes from which the eight-clusters-per-wavefront layouts are taken instead of one cluster per
-// wavefront (msim_launch_*8 return MSIM_LAYOUT_DOES_NOT_FIT below them and msim_run falls back; MSIM_DEV_FLAGS bit 10 forces the
-// packed layout whatever the launch).  The packed kernels are latency-bound — a wavefront's run takes a fixed time whatever the batch —
+// layout_thresholds.h — the launch sizes from which the packed layouts (eight or four clusters per wavefront) are taken instead of one
+// cluster per wavefront: the min_clusters column of the table in launch_plan.h, whose loop skips a row below its floor so that msim_run
+// falls back (MSIM_DEV_FLAGS bit 10 takes the packed layout whatever the launch).  The packed kernels are latency-bound — a wavefront's run takes a fixed time whatever the batch —
 // so they win from the batch size on where the one-cluster kernels have filled the chip.  Each number is a crossover MEASURED on one
 // MI355X (256 CUs); on another part they are the first thing to re-measure.
 //
@@ -25,4 +25,14 @@
 #define MSIM_SVC4_MIN_CLUSTERS 4096u
 #define MSIM_TXNG4_MIN_CLUSTERS 8192u
 #define MSIM_DTG4_MIN_CLUSTERS 16384u
+
+#include "../../include/maelsim.h"
+// hat8: a small batch is better off with one cluster per wavefront: eight per wavefront are an eighth of the wavefronts, a wavefront's
+// run is a chain of dependent round trips (the longer the more nodes a cluster has), and below ~1024 wavefronts — one per SIMD — nothing
+// hides it.  Measured crossovers (profiles/r03ae_hat8.txt; both kernels with the wavefront-wide list passes): 2 nodes 8192 clusters (37.8
+// against 44.9 ms; 16384: 44.5 / 85.7), 3 nodes between 8192 and 16384 (63 / 53, 75 / 103), 5 nodes near 16384 (112 / 128; 8192:
+// 97 / 68).  So: 6400 / 9600 / 16000 clusters of 2 / 3 / 5 nodes.
+static inline uint32_t msim_hat8_min_clusters(const msim_config &c) { return MSIM_HAT8_MIN_CLUSTERS_PER_NODE * c.n_nodes; }
+// dtg4: two nodes and more are even from 8192 on (profiles/r06f_dtg4_threshold_sweep.jsonl)
+static inline uint32_t msim_dtg4_min_clusters(const msim_config &c) { return c.n_nodes == 1 ? MSIM_DTG4_MIN_CLUSTERS : MSIM_DTG4_MIN_CLUSTERS / 2u; }
 #endif

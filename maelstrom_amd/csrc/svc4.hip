@@ -24,7 +24,6 @@
 
 #include "wave_common.h"
 #include "group16.h"
-#include "layout_thresholds.h"
 
 namespace {
 
@@ -336,7 +335,6 @@ static void svc4_launch(const S4Params &rp, bool nem, bool rnd, dim3 grid, size_
 
 hipError_t msim_launch_svc4(const KParams &kp, uint32_t n, hipStream_t st) {
   const msim_config &c = kp.cfg;
-  if (n < MSIM_SVC4_MIN_CLUSTERS && !(kp.dev_flags & 0x400u)) return MSIM_LAYOUT_DOES_NOT_FIT;
   S4Params rp;
   rp.k = kp; rp.n_inst = n;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;

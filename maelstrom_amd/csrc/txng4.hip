@@ -20,7 +20,6 @@
 
 #include "wave_common.h"
 #include "group16.h"
-#include "layout_thresholds.h"
 
 namespace {
 
@@ -383,7 +382,6 @@ uint64_t msim_txng4_extra_scratch_words(const msim_config &c) {
 
 hipError_t msim_launch_txng4(const KParams &kp, uint32_t n, hipStream_t st) {
   const msim_config &c = kp.cfg;
-  if (n < MSIM_TXNG4_MIN_CLUSTERS && !(kp.dev_flags & 0x400u)) return MSIM_LAYOUT_DOES_NOT_FIT;
   G4Params rp;
   rp.k = kp; rp.n_inst = n;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;
