@@ -553,6 +553,64 @@ int msim_explain_rw_batch(int device, const msim_op *rows, const uint64_t *row_o
  * changed.  Always the device route (developer flag 0x800 does not move it to the host cores). */
 int msim_explain_txn(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, uint32_t n_out);
 
+/* The set-full verdicts (broadcast, g-set), explained: WHICH elements are lost, never read or stale, and the ops that say so — the rest
+ * of [upstream] jepsen.checker/set-full's result map (doc/03-broadcast/01-broadcast.md:423-437, :564-577): :lost, :never-read, :stale,
+ * :worst-stale and :lost-latencies.  Defined here without reference to how they are found: the host entry, the device kernel
+ * (csrc/set_full_body.inc behind set_explain_kernel) and a plain walk over the ops give the same bytes.
+ *   Per element (one per :add / :broadcast invocation, numbered 0, 1, 2 .. in invocation order), over the client ops:
+ *     known         the first (by :index) :ok completion of its add or :ok read holding it;
+ *     last-present  the latest-invoked :ok read holding it; last-absent the latest-invoked :ok read, completed after the add's
+ *                   invocation, lacking it — both named by the read's INVOKE row;
+ *     stable <=> last-present and index(last-absent, -1) < index(last-present); lost <=> known and last-absent and
+ *     index(last-present, -1) < index(last-absent) and index(known) < index(last-absent); never-read otherwise;
+ *     :stable-latency = long(nanos->ms(max(0, (time(last-absent) + 1 | 0 without one) - time(known)))); stale <=> stable with latency > 0;
+ *     :lost-latency [upstream, unpinned: jepsen's source is not vendored, this comment is the contract] =
+ *                     long(nanos->ms(max(0, (time(last-present) + 1 | 0 without one) - time(known)))).
+ *   Segments.  A history's slab of max_elements records holds the lost elements, then the never-read ones, then the stale ones, each
+ *     segment in ascending element order ((sort (map :element ...))).
+ *   Truncation.  Segments that do not fit are filled in that order, each later one with the room left: n_lost = min(lost, max_elements),
+ *     n_never_read = min(never-read, max_elements - n_lost), n_stale likewise, truncated = 1 if a record is missing (the true counts are
+ *     the msim_check_result's).  max_elements = 0 is legal: the header only.  Records beyond the written counts are zero.
+ *   worst_stale.  The up to eight stale elements of largest latency, descending; among equal latencies the LARGER element first — what
+ *     (->> stale (sort-by :stable-latency) reverse (take 8)) yields over elements in ascending order.  jepsen's own order among ties
+ *     follows its map's iteration order, so the tie order is this library's choice.
+ *   lost_latency_ms.  Quantiles 0, .5, .95, .99, 1 of the lost latencies by the rule of :stable-latencies (sorted[min(n-1, floor(n*q))]);
+ *     all 0 when nothing is lost.
+ *   :duplicated is always {}: a read is a bitmap, no element can be held twice (duplicated_count = 0). */
+enum { MSIM_SET_STABLE = 0, MSIM_SET_LOST = 1, MSIM_SET_NEVER_READ = 2 };
+typedef struct msim_set_element {          /* 24 bytes: jepsen's per-element result map */
+  uint32_t element;
+  uint32_t outcome;                        /* MSIM_SET_* */
+  uint32_t latency_ms;                     /* :stable-latency (stable) / :lost-latency (lost); MSIM_NO_VALUE for never-read */
+  uint32_t known_row;                      /* row of :known; MSIM_NO_VALUE = nil */
+  uint32_t last_present_row;               /* INVOKE row of :last-present; MSIM_NO_VALUE = nil */
+  uint32_t last_absent_row;                /* INVOKE row of :last-absent; MSIM_NO_VALUE = nil */
+} msim_set_element;
+typedef struct msim_set_explain {          /* 232 bytes, one per history */
+  uint32_t n_lost, n_never_read, n_stale;  /* records WRITTEN to the three segments of the history's slab, in this order */
+  uint32_t truncated;                      /* 1: the slab was too short for all of them */
+  uint32_t n_worst_stale;                  /* 0..8 */
+  uint32_t lost_latency_ms[5];
+  msim_set_element worst_stale[8];         /* those beyond n_worst_stale are zero */
+} msim_set_explain;
+
+/* Host-only: one broadcast / g-set history (rows, payload words as msim_check_set_full_batch takes them) by the plain walk
+ * (csrc/set_check.cpp): *out is the whole record of the device checker (counts, quantiles, op_count, :stats), *hdr and elements[0 ..
+ * max_elements) as above (elements may be NULL when max_elements is 0).  MSIM_WL_ECHO and every other workload: MSIM_E_UNSUPPORTED.
+ * Needs no device. */
+int msim_explain_set_full_rows(uint32_t workload, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words,
+                               msim_check_result *out, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements);
+/* As msim_check_set_full_batch (the same slabs, the same out[i], the same limits) with the explanation written on the device: hdr[i],
+ * and history i's records at elements + i * max_elements.  MSIM_WL_ECHO: MSIM_E_UNSUPPORTED. */
+int msim_explain_set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
+                                const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories,
+                                msim_check_result *out, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements);
+/* The same over the histories of the last run where they lie in HBM (MSIM_WL_BROADCAST and MSIM_WL_G_SET, else MSIM_E_UNSUPPORTED):
+ * hdr / elements hold `n_out` histories (at least the run's, else MSIM_E_RANGE).  Towards the context it is msim_check: a check queued
+ * behind the simulation is taken and waited for, the context is armed as msim_check arms it, and msim_check_results holds the records
+ * msim_check writes. */
+int msim_explain_set_full(msim_ctx *ctx, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements, uint32_t n_out);
+
 /* Host-only utility behind msim_check for pn-counter: the checker of workload/pn_counter.clj:84-123 — every :ok read
  * marked :final? must lie in the acceptable set = sum of the :ok adds plus any subset of the :info adds, kept as merged
  * closed integer ranges.  out->valid 1/0; attempt_count = final reads, error_count = final reads outside the set,

@@ -49,7 +49,10 @@ EXPORTS = [
     "msim_check_perf", "msim_check_perf_rows", "msim_check_perf_batch",
     "msim_explain_lin_kv_rows", "msim_explain_lin_kv_batch", "msim_explain_lin_kv",
     "msim_explain_txn_rows", "msim_explain_rw_rows", "msim_explain_txn_batch", "msim_explain_rw_batch", "msim_explain_txn",
+    "msim_explain_set_full_rows", "msim_explain_set_full_batch", "msim_explain_set_full",
 ]
+SET_STABLE, SET_LOST, SET_NEVER_READ = range(3)   # MSIM_SET_*
+SET_OUTCOMES = {SET_STABLE: "stable", SET_LOST: "lost", SET_NEVER_READ: "never-read"}
 EDGE_KINDS = {1: "ww", 2: "wr", 4: "rw", 8: "realtime"}   # MSIM_EDGE_*
 AVAIL_NIL, AVAIL_TOTAL, AVAIL_FRACTION = range(3)
 PERF_MAX_F, PERF_MAX_WINDOWS = 4, 16
@@ -192,6 +195,12 @@ def load():
         fn.restype = C.c_int
     lib.msim_explain_txn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     lib.msim_explain_txn.restype = C.c_int
+    if hasattr(lib, "msim_explain_set_full"):   # (MSIM_LIB may name an older build: tools/set_explain_ab.py times the parent's check_kernel; calling a missing entry still raises)
+        lib.msim_explain_set_full_rows.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(CheckResult), C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.msim_explain_set_full_batch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.msim_explain_set_full.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.msim_explain_set_full_rows.restype = lib.msim_explain_set_full_batch.restype = lib.msim_explain_set_full.restype = C.c_int
     lib.msim_classify_rw_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.msim_classify_rw_batch.restype = C.c_int
     lib.msim_classify_txn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]

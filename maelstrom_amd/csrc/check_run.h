@@ -183,6 +183,33 @@ struct WitnessSlabs {
   }
 };
 
+// The explanation of an explaining set-full check: the two device slabs (a header, max_elements element records per history), cleared on
+// the stream before the kernel and copied to the caller's arrays behind it.
+struct SetExplainSlabs {
+  DevBuf h, e;
+  u32 n = 0, max_elements = 0;
+  msim_set_explain *h_hdr = nullptr; msim_set_element *h_elements = nullptr;
+  size_t el_bytes() const { return (size_t)n * max_elements * sizeof(msim_set_element); }
+  int alloc(msim_ctx *ctx, u32 n_, u32 max_elements_, msim_set_explain *hdr, msim_set_element *elements) {
+    n = n_; max_elements = max_elements_; h_hdr = hdr; h_elements = elements;
+    MSIM_HIP_TRY(ctx, h.alloc((size_t)n * sizeof(msim_set_explain)));
+    MSIM_HIP_TRY(ctx, e.alloc(std::max(el_bytes(), sizeof(msim_set_element))));
+    return MSIM_OK;
+  }
+  template <class X> void bind(X &x) const { x.hdr = h.get<msim_set_explain>(); x.elements = e.get<msim_set_element>(); x.max_elements = max_elements; }
+  int clear(msim_ctx *ctx, hipStream_t st) {
+    MSIM_HIP_TRY(ctx, hipMemsetAsync(h.get<void>(), 0, (size_t)n * sizeof(msim_set_explain), st));
+    if (el_bytes()) MSIM_HIP_TRY(ctx, hipMemsetAsync(e.get<void>(), 0, el_bytes(), st));
+    return MSIM_OK;
+  }
+  int fetch(msim_ctx *ctx, hipStream_t st) {
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_hdr, h.get<void>(), (size_t)n * sizeof(msim_set_explain), hipMemcpyDeviceToHost, st));
+    if (el_bytes()) MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_elements, e.get<void>(), el_bytes(), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return MSIM_OK;
+  }
+};
+
 // how rw_dev_run / txn_dev_run go beyond the clean passes: `full` the classification on the device; with `witness` its EXPLAIN kernel
 struct CycleMode {
   bool full = false;

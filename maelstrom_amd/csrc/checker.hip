@@ -33,6 +33,7 @@
 #include <cstring>
 #include <vector>
 
+#include "check_run.h"
 #include "engine_internal.h"
 
 #define NONE 0xFFFFu      /* per-element row index: none */
@@ -48,6 +49,13 @@ struct CParams {
   u32 max_rows, max_pay, max_values, C, workload, max_reads;
   u32 off_valid, off_tbl;   // LDS offsets (bytes): the valid bitmap, the per-thread tables
   float rcp_C;
+};
+// what set_explain_kernel writes beside p.out (msim_explain_set_full*; include/maelsim.h msim_set_explain): check_kernel has an empty one
+struct SetExplainOut {
+  msim_set_explain *hdr;        // one per history
+  msim_set_element *elements;   // per history: max_elements records, zeroed by the host
+  u32 max_elements;
+  u32 off_lat;                  // LDS offset (bytes) of the two latency arrays: the u16 row indices stay where they are
 };
 
 #ifdef MSIM_HIPEMU
@@ -93,380 +101,24 @@ __device__ __forceinline__ void c_lds_fence() {
 __device__ __forceinline__ u32 c_wave_max(u32 v) { return c_rdlane(c_wave_incl_max(v), 63); }
 
 __global__ void __launch_bounds__(64) check_kernel(const CParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char csmem[];
-  typedef unsigned short u16;
-  u16 *const known = reinterpret_cast<u16 *>(csmem);
-  u16 *const lp_idx = known + p.max_values;
-  u16 *const la_idx = lp_idx + p.max_values;
-  u32 *const lat = reinterpret_cast<u32 *>(csmem);  // reused after the walk: stable latency per element (needs 4 B each)
-  u32 *const valid = reinterpret_cast<u32 *>(csmem + p.off_valid);  // bitmap over invocation ranks: read completed :ok
-  u32 *const slot = reinterpret_cast<u32 *>(csmem + p.off_tbl);     // [C] the worker thread's pending invocation: row | rank << 16 (echo: row)
-  u32 *const first = slot + p.C;                                     // [C] ds_min target: (round, lane) of the thread's earliest pending row
-  u32 *const slotv = first + p.C;                                    // [C] echo: the :value of the thread's last invocation
-
-  const u32 lane = threadIdx.x, inst = blockIdx.x;
-  const msim_inst_meta meta = p.meta[inst];
-  const uint4 *const rows = reinterpret_cast<const uint4 *>(p.rows + (size_t)inst * p.max_rows);
-  const u32 *const pay = p.payload + (size_t)inst * p.max_pay;
-  u32 *const rec = p.recs + (size_t)inst * p.max_reads * 3;
-  const u32 n_rows = meta.n_rows, C = p.C;
-  const bool setfull = p.workload != MSIM_WL_ECHO;
-  const u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;   // lanes below this one
-
-  for (u32 i = lane; i < p.max_values; i += 64) { known[i] = NONE; lp_idx[i] = NONE; la_idx[i] = NONE; }
-  for (u32 i = lane; i < (p.max_reads + 31) / 32 + 2; i += 64) valid[i] = 0;
-  for (u32 i = lane; i < C; i += 64) { slot[i] = NONE32; first[i] = 0xFFFFFFFFu; slotv[i] = 0; }
-  __syncthreads();
-
-  u32 v_cur = 0, n_ri = 0, errors = 0;
-#ifdef CK_PROF   // developer build (tools/check_prof_report.py): cycles of pass 1 / pass 2 / the rest in stable_latency_ms[0..2], pairing rounds in [3], reads in [4]
-  const u64 ck_t0 = __builtin_readcyclecounter(); u64 ck_t1 = 0, ck_t2 = 0; u32 ck_rounds = 0;
-#endif
-  u32 cnt_lo = 0, cnt_hi = 0;    // per lane: rows of type :invoke | :ok << 16, :fail | :info << 16 (summed over the wavefront at the end)
-  u32 round_key = 0x3FFFFFFu;    // decreases with every pairing round: a later round's ds_min beats whatever an earlier one left
-
-  // ---- pass 1 ----
-  // Four chunks of rows (4 KiB) are in flight: with one, a chunk's 150 instructions waited out an HBM round trip each time (round 6: pass 1 took
-  // 1.7e5 cycles per history, 2700 per chunk).  The buffers keep their registers — a rotation by moves would wait for the load just issued —
-  // and the loads are unconditional (past the end: the last row again; every use of a row is behind `lane < cnt`).
-  auto ldrow = [&](u32 b) -> uint4 { return rows[min(b + lane, n_rows ? n_rows - 1 : 0u)]; };
-  auto rowchunk = [&](const u32 base, const uint4 r) {
-    const u32 cnt = min(64u, n_rows - base);
-    const u32 my_type = r.z & 3, my_f = (r.z >> 2) & 31, my_proc = r.z >> 12, idx = base + lane;
-    const bool live = lane < cnt && my_proc != MSIM_PROCESS_NEMESIS;  // (r/filter (comp number? :process))
-    const bool add_like = my_f == MSIM_F_ADD || my_f == MSIM_F_BROADCAST;
-    if (live) { const u32 one = 1u << ((my_type & 1) * 16); if (my_type & 2) cnt_hi += one; else cnt_lo += one; }
-    // add :ok -> known (first of add-ok / first containing read, by :index): order-free as a minimum; one add per element
-    if (live && add_like && my_type == MSIM_T_OK && r.w < p.max_values && known[r.w] > idx) known[r.w] = (u16)idx;
-    const u64 add_inv = __ballot(live && add_like && my_type == MSIM_T_INVOKE);  // elements come into existence
-    const u32 v_here = v_cur + (u32)__popcll(add_inv & lt);                      // elements existing at this row
-    v_cur += (u32)__popcll(add_inv);  // values are handed out 0,1,2,... in invoke order
-    const bool is_r = live && my_f == (setfull ? MSIM_F_READ : MSIM_F_ECHO);
-    const u64 ri = __ballot(is_r && my_type == MSIM_T_INVOKE);
-    const u32 rank = n_ri + (u32)__popcll(ri & lt);                                // invocation order of the reads
-    n_ri += (u32)__popcll(ri);
-    // what a read :ok leaves behind: its record at the rank of its invocation `sv` = row | rank << 16
-    auto record = [&](u32 sv) {
-      const u32 rk = sv >> 16;
-      if (rk < p.max_reads) {
-        u32 *q = rec + (size_t)rk * 3;
-        q[0] = r.w | ((r.y >> 16) << 24); q[1] = (sv & 0xFFFFu) | (v_here << 16); q[2] = idx;
-        atomicOr(&valid[rk >> 5], 1u << (rk & 31));
-      }
-    };
-    // A completion that directly follows its invocation (all but a few: the rows of one operation are only separated when another
-    // worker thread's row falls between them) is settled from the lane below; the pair never touches the thread's table entry.
-    // (Same PROCESS, which is the same worker thread for the two rows of one operation; the invocation's rank is this lane's count of the
-    //  invocations below it, less one.  Rows reach the lane above by DPP: the packed word, and for echo the value.)
-    const u32 below_z = c_dpp<0x138, 0xF, true>(r.z);   // wave_shr:1
-    const u32 below_v = setfull ? 0u : c_dpp<0x138, 0xF, true>(r.w);
-    const bool adj = is_r && my_type != MSIM_T_INVOKE && lane > 0 && (below_z & 3) == MSIM_T_INVOKE && ((below_z ^ r.z) & 0xFFFFF07Cu) == 0;
-    const u64 adj_m = __ballot(adj);
-    if (adj) {
-      if (setfull) { if (my_type == MSIM_T_OK) record((idx - 1) | ((rank - 1) << 16)); }
-      // echo.clj:44-63: every :invoke whose completion is not an :ok carrying the same :echo is an error — a :fail, an
-      // :info (its :value is the request string, (:echo "...") = nil) and an invocation that never completes included
-      else if (my_type != MSIM_T_OK || below_v != r.w) errors++;
-    }
-    bool pend = is_r && !adj && !((adj_m >> 1 >> lane) & 1);
-    u64 pm = __ballot(pend);
-    // worker thread = process mod C ([upstream] jepsen's interpreter): one float multiply and a correction instead of a division
-    u32 tt = 0;
-    if (pm && pend) {
-      const u32 qd = (u32)((float)my_proc * p.rcp_C);
-      int rem = (int)(my_proc - qd * C);
-      if (rem < 0) rem += (int)C;
-      if (rem >= (int)C) rem -= (int)C;
-      tt = (u32)rem;
-    }
-    while (pm) {   // rounds: the earliest pending read row of every worker thread acts on the thread's table entry
-      const u32 key = (round_key << 6) | lane;
-      if (pend) atomicMin(&first[tt], key);
-      c_lds_fence();   // (one wavefront: LDS is in order; __syncthreads would also wait for the rows in flight)
-      if (pend && first[tt] == key) {
-        pend = false;
-        const u32 s = slot[tt];
-        if (my_type == MSIM_T_INVOKE) {
-          slot[tt] = setfull ? (idx | (rank << 16)) : idx;
-          if (!setfull) slotv[tt] = r.w;
-        } else {
-          slot[tt] = NONE32;
-          if (setfull) { if (my_type == MSIM_T_OK && s != NONE32) record(s); }
-          else if (my_type != MSIM_T_OK || slotv[tt] != r.w) errors++;
-        }
-      }
-      round_key--;
-      c_lds_fence();   // (one wavefront: LDS is in order; __syncthreads would also wait for the rows in flight)
-      pm = __ballot(pend);
-#ifdef CK_PROF
-      ck_rounds++;
-#endif
-    }
-  };
-  if (n_rows) {
-    uint4 q0 = ldrow(0), q1 = ldrow(64), q2 = ldrow(128), q3 = ldrow(192);
-    for (u32 base = 0; base < n_rows; base += 256) {
-      rowchunk(base, q0); q0 = ldrow(base + 256);
-      if (base + 64 >= n_rows) break;
-      rowchunk(base + 64, q1); q1 = ldrow(base + 320);
-      if (base + 128 >= n_rows) break;
-      rowchunk(base + 128, q2); q2 = ldrow(base + 384);
-      if (base + 192 >= n_rows) break;
-      rowchunk(base + 192, q3); q3 = ldrow(base + 448);
-    }
-  }
-  if (!setfull) { for (u32 i = lane; i < C; i += 64) errors += slot[i] != NONE32 ? 1u : 0u; }   // invocations left without a completion
-  errors = c_wave_sum(errors);
-  cnt_lo = c_wave_sum(cnt_lo & 0xFFFFu) | (c_wave_sum(cnt_lo >> 16) << 16);   // (at most 65534 rows: every count fits 16 bits)
-  cnt_hi = c_wave_sum(cnt_hi & 0xFFFFu) | (c_wave_sum(cnt_hi >> 16) << 16);
-  const u32 op_count = cnt_lo & 0xFFFFu, n_ok = cnt_lo >> 16, n_fail = cnt_hi & 0xFFFFu, n_info = cnt_hi >> 16;
-  __threadfence_block();
-  __syncthreads();
-  if (n_ri > p.max_reads) n_ri = p.max_reads;
-#ifdef CK_PROF
-  ck_t1 = __builtin_readcyclecounter();
-#endif
-
-  // ---- pass 2: ONE sweep over the :ok reads in invocation order, 64 reads at a time, LANE r = READ r of the chunk ----------------------------
-  // Per element three reductions over the reads (§ header): last-present = the LAST read that has it, last-absent = the LAST read that lacks
-  // it while it exists, known = the smallest :ok index among the reads that have it.  Rounds 3-6 swept with lane w = word w of ONE read's
-  // bitmap at a time: a read cost ~140 issued instructions whatever it changed (its rank, three readlanes, the load, the masks, three bit
-  // loops), half the lanes idle (17 words on average).  Now a lane holds its OWN read's bitmap (16-byte loads at the read's own address, three
-  // in flight) and the wavefront walks the words 0 .. max words of the chunk; for word w
-  //   last-present: the highest lane with a bit decides ALL its bits at once (one 32-lane store, lane b = element 32w + b); what is left
-  //     (bits some lower lane has and that one has not: only at the frontier of the elements still spreading) takes the next-highest lane with
-  //     one of them, and so on.  Later chunks overwrite: the last chunk's last read wins.  last-absent likewise over ~word & existing
-  //     (nothing to do for words whose elements every read of the chunk holds);
-  //   known: the FIRST lane that has a not-yet-seen element gives its :ok index (lowest lane first, all its new bits at once) — right unless a
-  //     read invoked later completed earlier; such a read has an :ok index below the maximum of the reads before it, so every lane of which
-  //     that is true (`nm`: rare) takes the minimum over ALL its bits — which is always allowed, `known` being a minimum over containing reads.
-  // Element 32w + b is always written by lane b: no cross-lane ordering in LDS.
-  {
-    const u32 sub = lane & 31u;
-    uint4 tiny = make_uint4(0, 0, 0, 0);   // a payload slab of less than four words, whole
-    if (p.max_pay < 4) { if (p.max_pay > 0) tiny.x = pay[0]; if (p.max_pay > 1) tiny.y = pay[1]; if (p.max_pay > 2) tiny.z = pay[2]; }
-    u32 unkv = 0xFFFFFFFFu;          // lane j: the elements of word j no read has contained yet
-    u64 unk_any = ~0ull;             // wave-uniform: the lanes of unkv that are not zero
-    u32 pend = NONE;                 // lane j: word j was SETTLED in the last chunk that had it (below) — last-present of its 32 elements, not yet written
-    u32 ok_carry = 0;                // the largest :ok index of the chunks before
-    auto chunk_mask = [&](u32 cb) -> u64 {
-      if (cb >= n_ri) return 0ull;
-      const u32 cn = min(64u, n_ri - cb);
-      return ((u64)valid[cb / 32 + 1] << 32 | valid[cb / 32]) & (cn >= 64 ? ~0ull : ((1ull << cn) - 1));
-    };
-    // the records of the next chunk are requested while this one is swept
-    u32 nx = 0, ny = 0, nz = 0;
-    u64 nmask = chunk_mask(0);
-    if ((nmask >> lane) & 1) { const u32 *q = rec + (size_t)lane * 3; nx = q[0]; ny = q[1]; nz = q[2]; }
-    for (u32 cb = 0; cb < n_ri; cb += 64) {
-      const u64 vmask = nmask;
-      const u32 rx = nx, ry = ny, rz = nz;   // {payload ref | words << 24, invoke index | elements existing at completion << 16, :ok index}; 0 for a rank without an :ok
-      nmask = chunk_mask(cb + 64);
-      nx = ny = nz = 0;
-      if ((nmask >> lane) & 1) { const u32 *q = rec + (size_t)(cb + 64 + lane) * 3; nx = q[0]; ny = q[1]; nz = q[2]; }
-      if (!vmask) continue;
-      const u32 ref = rx & 0xFFFFFFu, nw = rx >> 24, inv = ry & 0xFFFFu, v_here = ry >> 16, ok = rz;
-      // four words of this lane's bitmap from word 4g on: ONE unconditional 16-byte load (a lane with nothing there reads the slab's first
-      // words and ignores them: no branch around the load, so the loads in flight stay countable).  A bitmap that ends in the slab's last
-      // three words — one instance in thousands — reads the slab's last four words and shifts.  (A slab of less than four words holds no bitmap
-      // worth the name: it is read once, before the sweep.)
-      auto ld = [&](u32 g) -> uint4 {
-        const u32 at = ref + 4 * g;
-        const bool in = 4 * g < nw;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (p.max_pay >= 4) {
-          const u32 last4 = p.max_pay - 4;
-          const ck_u32x4 q = *reinterpret_cast<const ck_u32x4 *>(pay + (in ? min(at, last4) : 0u));   // (16 bytes at a 4-byte boundary)
-          v = in ? make_uint4(q.x, q.y, q.z, q.w) : make_uint4(0, 0, 0, 0);   // (a lane without a word in this group — a rank without a record among them — holds zeros)
-          if (__ballot(in && at > last4)) {
-            const u32 sh = in && at > last4 ? at - last4 : 0u;
-            if (sh == 1) v = make_uint4(v.y, v.z, v.w, 0); else if (sh == 2) v = make_uint4(v.z, v.w, 0, 0); else if (sh >= 3) v = make_uint4(sh == 3 ? v.w : 0u, 0, 0, 0);
-          }
-        } else if (in) {   // (no load here: a load on this path would make the loads in flight uncountable for the path that matters)
-          auto tw = [&](u32 i) { return i == 0 ? tiny.x : (i == 1 ? tiny.y : (i == 2 ? tiny.z : 0u)); };
-          v = make_uint4(tw(at), tw(at + 1), tw(at + 2), 0);
-        }
-        return v;
-      };
-      uint4 b0 = ld(0), b1 = ld(1), b2 = ld(2), b3 = ld(3);
-      const u32 maxw = min(64u, c_wave_max(max(nw, (v_here + 31) >> 5)));   // (a bitmap may be shorter than the elements that exist: they are absent)
-      // lanes whose :ok index is below the largest of the reads before them: inclusive prefix maximum, then the lane below's
-      const u32 pm = c_wave_incl_max(ok);
-      u32 before = (u32)__shfl_up((int)pm, 1);
-      before = max(lane ? before : 0u, ok_carry);
-      const u64 nm_mask = __ballot(((vmask >> lane) & 1) && ok < before);
-      ok_carry = max(ok_carry, c_rdlane(pm, 63));
-      const u32 inv_top = c_rdlane(inv, 63u - (u32)__builtin_clzll(vmask));
-      const u32 minw = ~c_wave_max(((vmask >> lane) & 1) ? ~nw : 0u);   // every read of the chunk has at least this many words
-      // one word of the 64 bitmaps.  What the loops decide for element 32w + b collects in lane b's registers; LDS is touched once per word and kind
-      auto word = [&](const u32 w, const u32 raw) {
-        u32 W = raw;
-        if (w >= minw) W = w < nw ? raw : 0u;   // (wave-uniform test: below minw every read of the chunk has the word, and a lane without a read holds zeros)
-        u32 unk_w = (unk_any >> w) & 1 ? c_rdlane(unkv, w) : 0u;
-        // A SETTLED word — every read of the chunk holds all 32 elements, all of them seen before, no overtaker among the reads: most words,
-        // the elements behind the frontier — changes one thing: last-present = the chunk's last read, for all 32.  That is noted in `pend`
-        // and written when a chunk finds the word unsettled, or at the end.
-        if (__ballot(W == 0xFFFFFFFFu) == vmask && unk_w == 0 && nm_mask == 0) { if (lane == w) pend = inv_top; return; }
-        const u32 e = 32 * w + sub;
-        const bool e_ok = lane < 32 && e < p.max_values;
-        const u32 pw = c_rdlane(pend, w);
-        if (pw != NONE) { if (e_ok) lp_idx[e] = (u16)pw; if (lane == w) pend = NONE; }
-        const int d = (int)v_here - (int)(32 * w);
-        const u32 ex = d >= 32 ? 0xFFFFFFFFu : (d <= 0 ? 0u : ((1u << d) - 1));  // elements that exist at this read
-        const u32 A = ~W & ex;
-        u64 m = __ballot(W != 0);
-        const u64 holders = m;
-        if (m) {   // last-present
-          u32 rem = 0xFFFFFFFFu, got = 0;
-          do {
-            const u32 L = 63u - (u32)__builtin_clzll(m);
-            const u32 bits = c_rdlane(W, L) & rem, iv = c_rdlane(inv, L);
-            got = ((bits >> sub) & 1) ? iv : got;
-            rem &= ~bits;
-            m = __ballot((W & rem) != 0);
-          } while (m);
-          if (e_ok && !((rem >> sub) & 1)) lp_idx[e] = (u16)got;
-        }
-        m = __ballot(A != 0);
-        if (m) {   // last-absent
-          u32 rem = 0xFFFFFFFFu, got = 0;
-          do {
-            const u32 L = 63u - (u32)__builtin_clzll(m);
-            const u32 bits = c_rdlane(A, L) & rem, iv = c_rdlane(inv, L);
-            got = ((bits >> sub) & 1) ? iv : got;
-            rem &= ~bits;
-            m = __ballot((A & rem) != 0);
-          } while (m);
-          if (e_ok && !((rem >> sub) & 1)) la_idx[e] = (u16)got;
-        }
-        if (unk_w) {   // known: the first read that holds a not-yet-seen element gives its :ok index.  Every lane takes the bits NO LOWER lane
-          const u32 nw_bits = W & unk_w;   // holds (a prefix OR across the lanes) and writes them itself: as many turns as ONE read has new elements
-          if (__ballot(nw_bits != 0)) {
-            const u32 below = c_wave_excl_or(nw_bits);
-            u32 mine = nw_bits & ~below;
-            while (mine) {
-              const u32 x = 32 * w + (u32)__builtin_ctz(mine); mine &= mine - 1;
-              if (x < p.max_values && known[x] > ok) known[x] = (u16)ok;
-            }
-            c_lds_fence();   // (the elements of word w are lane b's again below)
-            unk_w &= ~(c_rdlane(below, 63) | c_rdlane(nw_bits, 63));   // everything some lane holds
-            if (lane == w) unkv = unk_w;
-            unk_any = __ballot(unkv != 0);
-          }
-        }
-        u32 kmin = NONE;
-        bool any = false;   // wave-uniform
-        m = nm_mask & holders;
-        if (m) {   // ... and the reads that overtook an earlier one
-          any = true;
-          do {
-            const u32 L = (u32)__builtin_ctzll(m); m &= m - 1;
-            const u32 bits = c_rdlane(W, L), okl = c_rdlane(ok, L);
-            kmin = ((bits >> sub) & 1) ? min(kmin, okl) : kmin;
-          } while (m);
-        }
-        if (any && e_ok && known[e] > kmin) known[e] = (u16)kmin;
-      };
-      auto group = [&](const u32 g, const uint4 &c) {
-        // four settled words at once (most groups: everything well behind the frontier)
-        if (4 * g + 3 < minw && nm_mask == 0 && ((unk_any >> (4 * g)) & 0xFu) == 0 && __ballot((c.x & c.y & c.z & c.w) == 0xFFFFFFFFu) == vmask) {
-          if ((lane >> 2) == g) pend = inv_top;
-          return;
-        }
-        word(4 * g, c.x);
-        if (4 * g + 1 < maxw) word(4 * g + 1, c.y);
-        if (4 * g + 2 < maxw) word(4 * g + 2, c.z);
-        if (4 * g + 3 < maxw) word(4 * g + 3, c.w);
-      };
-      // four 16-byte loads per lane in flight; the buffers keep their registers (a rotation by moves would wait for the load just issued)
-      const u32 ng = (maxw + 3) >> 2;
-      for (u32 g = 0; g < ng; g += 4) {
-        group(g, b0); if (g + 1 >= ng) break; b0 = ld(g + 4);
-        group(g + 1, b1); if (g + 2 >= ng) break; b1 = ld(g + 5);
-        group(g + 2, b2); if (g + 3 >= ng) break; b2 = ld(g + 6);
-        group(g + 3, b3); b3 = ld(g + 7);
-      }
-    }
-    for (u64 m = __ballot(pend != NONE); m; m &= m - 1) {   // the words that were settled to the end
-      const u32 w = (u32)__builtin_ctzll(m), pw = c_rdlane(pend, w), e = 32 * w + sub;
-      if (lane < 32 && e < p.max_values) lp_idx[e] = (u16)pw;
-    }
-  }
-  __syncthreads();
-
-#ifdef CK_PROF
-  ck_t2 = __builtin_readcyclecounter();
-#endif
-  // ---- per-element outcomes (each lane owns elements e = lane, lane+64, ...; at most 32 per lane) ----
-  u32 c_stable = 0, c_lost = 0, c_never = 0, c_stale = 0;
-  u32 my_lat[32];  // statically indexed (unrolled): stays in VGPRs
-#pragma unroll
-  for (u32 k = 0; k < 32; k++) {
-    const u32 e = lane + 64 * k;
-    u32 l = NOLAT;
-    if (e < v_cur) {
-      const u32 kn = known[e], lp = lp_idx[e], la = la_idx[e];
-      const bool stable = lp != NONE && (la == NONE || la < lp);
-      const bool lost = kn != NONE && la != NONE && (lp == NONE || lp < la) && kn < la;
-      if (stable) {
-        l = 0;
-        if (la != NONE) {
-          const uint4 ra = rows[la], rk = rows[kn];
-          const u64 ta = (((u64)(ra.y & 0xFFFF) << 32) | ra.x) + 1, tk = ((u64)(rk.y & 0xFFFF) << 32) | rk.x;
-          if (ta > tk) l = (u32)((ta - tk) / 1000000ull);
-        }
-        c_stable++; if (l > 0) c_stale++;
-      } else if (lost) c_lost++; else c_never++;
-    }
-    my_lat[k] = l;
-  }
-  __syncthreads();  // everyone has read the u16 arrays: the same LDS now holds the latencies
-#pragma unroll
-  for (u32 k = 0; k < 32; k++) { const u32 e = lane + 64 * k; if (e < v_cur) lat[e] = my_lat[k]; }
-  __syncthreads();
-  const u32 n_stable = c_wave_sum(c_stable), n_lost = c_wave_sum(c_lost), n_never = c_wave_sum(c_never), n_stale = c_wave_sum(c_stale);
-
-  // ---- quantiles of the stable latencies: idx-th smallest by bisection on the value ----
-  u32 q[5] = {0, 0, 0, 0, 0};
-  if (n_stable) {
-    u32 lmax = 0;  // the search range is [0, largest stable latency]
-    for (u32 e = lane; e < v_cur; e += 64) { const u32 l = lat[e]; if (l != NOLAT) lmax = max(lmax, l); }
-    for (int o = 32; o; o >>= 1) lmax = max(lmax, (u32)__shfl_xor((int)lmax, o));
-    const double pts[5] = {0.0, 0.5, 0.95, 0.99, 1.0};
-    for (int qi = 0; qi < 5; qi++) {
-      const u32 want = min(n_stable - 1, (u32)floor((double)n_stable * pts[qi]));
-      u32 lo = 0, hi = lmax;  // smallest v with count(lat <= v) > want
-      while (lo < hi) {
-        const u32 mid = lo + (hi - lo) / 2;
-        u32 c = 0;
-        for (u32 e = lane; e < v_cur; e += 64) { const u32 l = lat[e]; c += (l != NOLAT && l <= mid) ? 1u : 0u; }
-        if (c_wave_sum(c) > want) hi = mid; else lo = mid + 1;
-      }
-      q[qi] = lo;
-    }
-  }
-
-  if (lane == 0) {
-    msim_check_result o;
-    o.attempt_count = v_cur; o.stable_count = n_stable; o.lost_count = n_lost; o.never_read_count = n_never;
-    o.stale_count = n_stale; o.duplicated_count = 0; o.error_count = errors;
-    for (int i = 0; i < 5; i++) o.stable_latency_ms[i] = q[i];
-#ifdef CK_PROF
-    o.stable_latency_ms[0] = (u32)(ck_t1 - ck_t0); o.stable_latency_ms[1] = (u32)(ck_t2 - ck_t1); o.stable_latency_ms[2] = (u32)(__builtin_readcyclecounter() - ck_t2); o.stable_latency_ms[3] = ck_rounds; o.stable_latency_ms[4] = n_ri;
-#endif
-    o.op_count = op_count; o.ok_count = n_ok; o.fail_count = n_fail; o.info_count = n_info;
-    if (meta.flags) o.valid = 0;
-    else if (!setfull) o.valid = errors == 0 ? 1 : 0;
-    else o.valid = n_lost ? 0u : (n_stable == 0 ? 2u : 1u);
-    p.out[inst] = o;
-  }
+  constexpr bool EXPLAIN = false;
+  const SetExplainOut x = SetExplainOut();
+#include "set_full_body.inc"
+}
+// The same check with its explanation (msim_explain_set_full*): the lost / never-read / stale elements, the eight stalest, the lost
+// latencies.  Set-full only (the entries refuse echo).
+__global__ void __launch_bounds__(64) set_explain_kernel(const CParams p, const SetExplainOut x) {
+  constexpr bool EXPLAIN = true;
+#include "set_full_body.inc"
 }
 
 // LDS of one wavefront: three u16 indices per element (reused as one u32 latency per element), the valid bitmap over the read
-// ranks (read one word past the last chunk), the per-thread tables slot / first / slotv
-static size_t check_lds_layout(CParams &cp) {
+// ranks (read one word past the last chunk), the per-thread tables slot / first / slotv.  set_explain_kernel (off_lat given) keeps the
+// indices and has two u32 latencies per element behind them.
+static size_t check_lds_layout(CParams &cp, u32 *off_lat = nullptr) {
   size_t lds = (size_t)cp.max_values * 3 * 2 < (size_t)cp.max_values * 4 ? (size_t)cp.max_values * 4 : (size_t)cp.max_values * 3 * 2;
   lds = (lds + 3) & ~(size_t)3;
+  if (off_lat) { lds = ((size_t)cp.max_values * 3 * 2 + 3) & ~(size_t)3; *off_lat = (u32)lds; lds += (size_t)cp.max_values * 2 * 4; }
   cp.off_valid = (u32)lds;
   lds += ((size_t)(cp.max_reads + 31) / 32 + 2) * 4;
   cp.off_tbl = (u32)lds;
@@ -489,6 +141,18 @@ static hipError_t check_dispatch(CParams &cp, u32 n, hipStream_t st) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(check_kernel, dim3(n), dim3(64), lds, st, cp);
+  return hipGetLastError();
+}
+// the same for set_explain_kernel, which also writes x's header and element slabs (cleared by the caller)
+static hipError_t set_explain_dispatch(CParams &cp, SetExplainOut &x, u32 n, hipStream_t st) {
+  cp.max_reads = cp.max_rows / 2 + 1;
+  cp.rcp_C = 1.0f / (float)cp.C;
+  const size_t lds = check_lds_layout(cp, &x.off_lat);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&set_explain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(set_explain_kernel, dim3(n), dim3(64), lds, st, cp, x);
   return hipGetLastError();
 }
 
@@ -540,8 +204,10 @@ int msim_check_launch(msim_ctx *ctx) {
 
 // Checks `n_histories` broadcast / g-set (set-full) or echo histories given on the host with the device checker of msim_check:
 // history i lies in the slabs rows + i * max_rows (n_rows[i] rows used) and payload + i * max_payload_words.
-extern "C" int msim_check_set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
-                                         const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out) {
+// (xs: msim_explain_set_full_batch's slabs — set_explain_kernel in place of check_kernel, on the same upload)
+static int set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
+                          const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out,
+                          SetExplainSlabs *xs) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0 || (!payload && max_payload_words)) return MSIM_E_INVALID;
   if (workload != MSIM_WL_ECHO && workload != MSIM_WL_BROADCAST && workload != MSIM_WL_G_SET) return MSIM_E_INVALID;
   if (check_limits(max_rows, max_values, concurrency)) return MSIM_E_UNSUPPORTED;
@@ -564,13 +230,79 @@ extern "C" int msim_check_set_full_batch(int device, uint32_t workload, uint32_t
     if (max_payload_words && hipMemcpy(d_pay, payload, pay_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
     if (hipMemcpy(d_meta, hm.data(), (size_t)n_histories * sizeof(msim_inst_meta), hipMemcpyHostToDevice) != hipSuccess) break;
     cp.rows = d_rows; cp.payload = d_pay; cp.meta = d_meta; cp.out = d_out; cp.recs = d_rec;
-    if (check_dispatch(cp, n_histories, nullptr) != hipSuccess) break;
+    if (xs) {
+      BatchCtx bc(device);
+      SetExplainOut x;
+      std::memset(&x, 0, sizeof x);
+      if (xs->clear(&bc, nullptr) != MSIM_OK) break;
+      xs->bind(x);
+      if (set_explain_dispatch(cp, x, n_histories, nullptr) != hipSuccess) break;
+      if (xs->fetch(&bc, nullptr) != MSIM_OK) break;
+    } else if (check_dispatch(cp, n_histories, nullptr) != hipSuccess) break;
     if (hipDeviceSynchronize() != hipSuccess) break;
     if (hipMemcpy(out, d_out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost) != hipSuccess) break;
     rc = MSIM_OK;
   } while (false);
   for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_meta, (void *)d_out, (void *)d_rec}) if (q) (void)msim_dev_free(q);
   return rc;
+}
+extern "C" int msim_check_set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
+                                         const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out) {
+  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out, nullptr);
+}
+
+// The explaining set-full check (include/maelsim.h msim_set_explain) of a caller's histories: msim_check_set_full_batch's upload and
+// records, with set_explain_kernel's header and element records per history.
+extern "C" int msim_explain_set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
+                                           const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories,
+                                           msim_check_result *out, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements) {
+  if (!hdr || (!elements && max_elements) || n_histories == 0) return MSIM_E_INVALID;
+  if (workload != MSIM_WL_BROADCAST && workload != MSIM_WL_G_SET) return MSIM_E_UNSUPPORTED;
+  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
+  BatchCtx bc(device);
+  SetExplainSlabs xs;
+  const int rc = xs.alloc(&bc, n_histories, max_elements, hdr, elements);
+  if (rc != MSIM_OK) return rc;
+  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out, &xs);
+}
+
+// ... and of the last run where it lies in HBM.  Towards the context this is msim_check (engine.hip): a check queued behind the
+// simulation is taken and waited for, a launch on the context's own stream arms the context; then the explaining kernel runs over the
+// same slabs on the context's stream and leaves in d_check the records check_kernel writes.
+extern "C" int msim_explain_set_full(msim_ctx *ctx, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements, uint32_t n_out) {
+  if (!ctx || !hdr || (!elements && max_elements)) return MSIM_E_INVALID;
+  const msim_config &c = ctx->cfg;
+  if (c.workload != MSIM_WL_BROADCAST && c.workload != MSIM_WL_G_SET) { ctx->err = "msim_explain_set_full: not a broadcast or g-set context"; return MSIM_E_UNSUPPORTED; }
+  if (!ctx->ran) { ctx->err = "msim_explain_set_full before msim_run"; return MSIM_E_RANGE; }
+  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_set_full: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (const char *why = check_limits(c.max_rows, c.max_values, c.concurrency)) { ctx->err = why; return MSIM_E_UNSUPPORTED; }
+  MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t flags = msim_dev_flags(ctx);
+  if (ctx->check_queued) {
+    ctx->check_queued = false;
+    if (flags & 0x1000u) std::fprintf(stderr, "[check] taken %u\n", ctx->n_inst);
+    const int rc = msim_check_wait(ctx);
+    if (rc != MSIM_OK) return rc;
+  } else if (ctx->ran_own_stream && !(flags & 0x40000u)) ctx->check_armed = true;
+  if (flags & 0x1000u) std::fprintf(stderr, "[check] explain %u\n", ctx->n_inst);
+  SetExplainSlabs xs;
+  int rc = xs.alloc(ctx, ctx->n_inst, max_elements, hdr, elements);
+  if (rc != MSIM_OK) return rc;
+  if ((rc = msim_check_reserve(ctx, ctx->n_inst)) != MSIM_OK) return rc;
+  CParams cp;
+  std::memset(&cp, 0, sizeof cp);
+  cp.rows = ctx->d_rows; cp.payload = ctx->d_payload; cp.meta = ctx->d_meta; cp.out = ctx->d_check;
+  cp.max_rows = c.max_rows; cp.max_pay = c.max_payload_words; cp.max_values = c.max_values; cp.C = c.concurrency; cp.workload = c.workload;
+  cp.recs = static_cast<u32 *>(ctx->d_check_scratch);
+  SetExplainOut x;
+  std::memset(&x, 0, sizeof x);
+  if ((rc = xs.clear(ctx, ctx->stream)) != MSIM_OK) return rc;
+  xs.bind(x);
+  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  MSIM_HIP_TRY(ctx, set_explain_dispatch(cp, x, ctx->n_inst, ctx->stream));
+  MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+  if ((rc = xs.fetch(ctx, ctx->stream)) != MSIM_OK) return rc;
+  return msim_check_wait(ctx);
 }
 
 // ---- maelstrom.checker/availability-checker (checker.clj:6-39) ---------------------------------------------------------

@@ -24,6 +24,9 @@ LIN_KEY_DT = np.dtype([("key", "<u4"), ("valid", "<u4"), ("op_row", "<u4"), ("pr
                        ("values", "u1", (8,))])   # msim_lin_key_result
 CYCLE_DT = np.dtype([("anomalies", "<u4"), ("length", "<u4"), ("n_steps", "<u4"), ("reserved", "<u4")])        # msim_cycle_result
 CYCLE_STEP_DT = np.dtype([("txn", "<u4"), ("inv_row", "<u4"), ("cmp_row", "<u4"), ("kinds", "<u4")])          # msim_cycle_step
+SET_ELEMENT_DT = np.dtype([(n, "<u4") for n in ("element", "outcome", "latency_ms", "known_row", "last_present_row", "last_absent_row")])   # msim_set_element
+SET_EXPLAIN_DT = np.dtype([("n_lost", "<u4"), ("n_never_read", "<u4"), ("n_stale", "<u4"), ("truncated", "<u4"), ("n_worst_stale", "<u4"),
+                           ("lost_latency_ms", "<u4", (5,)), ("worst_stale", SET_ELEMENT_DT, (8,))])   # msim_set_explain
 LATENCY_DT = np.dtype([("count", "<u4"), ("q_us", "<u4", (5,)), ("sum_us", "<u8")])
 F_STATS_DT = np.dtype([("f", "<u4"), ("valid", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
                        ("unpaired", "<u4"), ("reserved", "<u4"), ("latency", LATENCY_DT, (3,))])
@@ -183,6 +186,17 @@ class Engine:
         self._chk(self.lib.msim_explain_txn(self._ctx, cycles.ctypes.data, steps.ctypes.data, max_steps, self.n), "msim_explain_txn")
         res = self.check_results()
         return [(res[i], cycles[i], steps[i, :int(cycles[i]["n_steps"])].copy()) for i in range(self.n)]
+
+    def explain_set_full(self, max_elements=256):
+        """broadcast / g-set: check() that also explains (msim_explain_set_full): per history of the last run (CHECK_DT record —
+        check_results() holds the same afterwards —, SET_EXPLAIN_DT header, SET_ELEMENT_DT records: the lost, the never-read and the
+        stale elements, in this order, each kind ascending, with the rows of their :known / :last-present / :last-absent ops; see
+        set_full_analysis), compacted on the device.  A history with more of them than max_elements has header["truncated"] set."""
+        hdr = np.zeros(max(self.n, 1), dtype=SET_EXPLAIN_DT)
+        els = np.zeros((max(self.n, 1), max(max_elements, 1)), dtype=SET_ELEMENT_DT)
+        self._chk(self.lib.msim_explain_set_full(self._ctx, hdr.ctypes.data, els.ctypes.data, max_elements, self.n), "msim_explain_set_full")
+        res = self.check_results()
+        return [(res[i], hdr[i], els[i, :_n_set_records(hdr[i])].copy()) for i in range(self.n)]
 
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
@@ -864,6 +878,21 @@ def check_unique_batch(histories, device=0, fn="msim_check_unique_batch"):
 def check_set_full_batch(histories, concurrency, workload=A.WL_BROADCAST, max_values=None, device=0):
     """broadcast / g-set (set-full) or echo: several histories — (rows, payload words) pairs — through the device checker behind
     Engine.check() (msim_check_set_full_batch)."""
+    rows, nr, pay, max_values = _set_full_slabs(histories, max_values)
+    out = np.zeros(len(nr), dtype=CHECK_DT)
+    rc = A.load().msim_check_set_full_batch(device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
+                                            max_values, len(nr), out.ctypes.data)
+    if rc:
+        raise EngineError(f"msim_check_set_full_batch: {rc}")
+    return out
+
+
+def _n_set_records(hdr):
+    return int(hdr["n_lost"]) + int(hdr["n_never_read"]) + int(hdr["n_stale"])
+
+
+def _set_full_slabs(histories, max_values):
+    """(rows, n_rows, payload, max_values) of check_set_full_batch's call"""
     hs = [(np.ascontiguousarray(r), np.ascontiguousarray(p, dtype=np.uint32)) for r, p in histories]
     mr = max(1, max(len(r) for r, _ in hs))
     mp = max(1, max(len(p) for _, p in hs))
@@ -877,11 +906,77 @@ def check_set_full_batch(histories, concurrency, workload=A.WL_BROADCAST, max_va
         f = (rows["packed"] >> 2) & 31
         adds = (((f == A.F_ADD) | (f == A.F_BROADCAST)) & ((rows["packed"] & 3) == 0)).sum(axis=1).max() if len(hs) else 0
         max_values = max(32, (int(adds) + 31) // 32 * 32)
-    out = np.zeros(len(hs), dtype=CHECK_DT)
-    rc = A.load().msim_check_set_full_batch(device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, mr, pay.ctypes.data, mp, max_values, len(hs), out.ctypes.data)
+    return rows, nr, pay, max_values
+
+
+def explain_set_full_history(rows, payload, workload=A.WL_BROADCAST, max_elements=256):
+    """The explaining set-full check of one broadcast / g-set history on the host (msim_explain_set_full_rows; needs no device) ->
+    (CHECK_DT record, SET_EXPLAIN_DT header, SET_ELEMENT_DT records: the lost, never-read and stale elements as include/maelsim.h
+    msim_set_explain lays them out).  The whole zero-padded slab of max_elements records is the returned array's `.base`."""
+    rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    out = np.zeros(1, dtype=CHECK_DT)
+    hdr = np.zeros(1, dtype=SET_EXPLAIN_DT)
+    slab = np.zeros(max(max_elements, 1), dtype=SET_ELEMENT_DT)
+    rc = A.load().msim_explain_set_full_rows(workload, rows.ctypes.data, len(rows), payload.ctypes.data, len(payload),
+                                             out.ctypes.data_as(C.POINTER(A.CheckResult)), hdr.ctypes.data, slab.ctypes.data, max_elements)
     if rc:
-        raise EngineError(f"msim_check_set_full_batch: {rc}")
-    return out
+        raise EngineError(f"msim_explain_set_full_rows: {rc}")
+    return out[0], hdr[0], slab[:_n_set_records(hdr[0])]
+
+
+def explain_set_full_batch(histories, concurrency, workload=A.WL_BROADCAST, max_values=None, device=0, max_elements=256):
+    """broadcast / g-set: check_set_full_batch with the explanation written on the device (msim_explain_set_full_batch).  Returns
+    (CHECK_DT records, SET_EXPLAIN_DT headers, a list of SET_ELEMENT_DT arrays — the records written per history); the whole zero-padded
+    slab is the returned list's `.slab` ((histories, max_elements))."""
+    rows, nr, pay, max_values = _set_full_slabs(histories, max_values)
+    n = len(nr)
+    out = np.zeros(n, dtype=CHECK_DT)
+    hdr = np.zeros(n, dtype=SET_EXPLAIN_DT)
+    slab = np.zeros((n, max(max_elements, 1)), dtype=SET_ELEMENT_DT)
+    rc = A.load().msim_explain_set_full_batch(device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
+                                              max_values, n, out.ctypes.data, hdr.ctypes.data, slab.ctypes.data, max_elements)
+    if rc:
+        raise EngineError(f"msim_explain_set_full_batch: {rc}")
+    els = _StepLists(slab[i, :_n_set_records(hdr[i])].copy() for i in range(n))
+    els.slab = slab[:, :max_elements]
+    return out, hdr, els
+
+
+def set_full_analysis(record, header, elements, rows=None, payload=None, n_nodes=0, workload=A.WL_BROADCAST):
+    """The Jepsen-shaped result map of `checker/set-full` (doc/03-broadcast/01-broadcast.md:564-577) from one history's record, header
+    and element records (pure formatting): valid?, the five counts, lost / never-read / stale (element lists), worst-stale (a list of
+    {element, outcome, stable-latency, known, last-absent}), stable-latencies / lost-latencies ({0 .5 .95 .99 1}; only where the class
+    has members), duplicated-count, duplicated.  With `rows`, known / last-absent are the ops as decode_history gives them, else row
+    indices (None = nil).  A truncated header gives the lists as far as they were written, and "truncated": True."""
+    ops = []
+
+    def op_at(row):
+        if int(row) == A.NO_VALUE:
+            return None
+        if rows is None:
+            return int(row)
+        if not ops:
+            ops.extend(decode_history(rows, payload if payload is not None else np.zeros(1, dtype=np.uint32), n_nodes, workload))
+        return ops[int(row)]
+
+    nl, nn = int(header["n_lost"]), int(header["n_never_read"])
+    pts = PERF_QUANTILES
+    res = {"valid?": {1: True, 0: False, 2: "unknown"}[int(record["valid"])],
+           "attempt-count": int(record["attempt_count"]), "stable-count": int(record["stable_count"]), "lost-count": int(record["lost_count"]),
+           "lost": [int(e["element"]) for e in elements[:nl]],
+           "never-read-count": int(record["never_read_count"]), "never-read": [int(e["element"]) for e in elements[nl:nl + nn]],
+           "stale-count": int(record["stale_count"]), "stale": [int(e["element"]) for e in elements[nl + nn:]],
+           "worst-stale": [{"element": int(e["element"]), "outcome": A.SET_OUTCOMES[int(e["outcome"])], "stable-latency": int(e["latency_ms"]),
+                            "known": op_at(e["known_row"]), "last-absent": op_at(e["last_absent_row"])}
+                           for e in header["worst_stale"][:int(header["n_worst_stale"])]],
+           "duplicated-count": int(record["duplicated_count"]), "duplicated": {}}
+    if int(record["stable_count"]):
+        res["stable-latencies"] = {q: int(v) for q, v in zip(pts, record["stable_latency_ms"])}
+    if int(record["lost_count"]):
+        res["lost-latencies"] = {q: int(v) for q, v in zip(pts, header["lost_latency_ms"])}
+    if int(header["truncated"]):
+        res["truncated"] = True
+    return res
 
 
 def check_pn_batch(histories, device=0):
