@@ -1,7 +1,8 @@
 // check_run.h — the host side the device checkers share (lin / txn / rw / kafka / pn / unique / perf _check_dev.hip): device buffers
 // that free themselves, the grow-only workspace, a caller's histories uploaded, the chunked launch loop, the hand-off of what the
-// device leaves to the host checkers, the frame of msim_check_*_device.  Host only: nothing here is seen by a kernel.  A new checker
-// mode supplies its kernel launch and its host callable; docs/KERNELS.md, "the host side of the device checkers".
+// device leaves to the host checkers, the frame of msim_check_*_device.  Host only: nothing here is seen by a kernel (the device side
+// is check_dev.h).  A new checker mode supplies its kernel launch and its host callable; docs/KERNELS.md, "the host side of the device
+// checkers".
 #ifndef MSIM_CHECK_RUN_H
 #define MSIM_CHECK_RUN_H
 
@@ -120,6 +121,20 @@ struct HistorySource {
 template <class P> static inline HistorySource source_of(const P &p, const std::vector<msim_inst_meta> *hmeta) {
   return HistorySource{p.rows, p.payload, hmeta, p.max_rows, p.max_pay, p.row_off, p.pay_off};
 }
+
+// The host checkers on one history, on the calling thread: what a hand-off's `analyse` calls (lin_check.cpp, txn_check.cpp,
+// kafka_check.cpp, pn_check.cpp).
+void msim_lin_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);
+void msim_lin_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys, uint32_t max_keys,
+                                    uint32_t *n_keys);
+void msim_txn_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
+                                  msim_check_result *res);
+void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
+                                 msim_check_result *res);
+void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);
+void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out);
+void msim_pn_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);
 
 // The hand-off: the rows and payload words of the histories `todo` come to the host, analyse(rows, n_rows, payload, n_words, flags, i)
 // — which writes h_out[i] — runs on up to msim_host_threads() threads, the finished records go back to d_out + i.

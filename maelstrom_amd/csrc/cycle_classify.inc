@@ -1,6 +1,6 @@
 // cycle_classify.inc — the classification of one history's dependency cycles, shared by the two transactional checkers on the
 // device: rw_classify_kernel (rw_check_dev.hip, txn-rw-register) and txn_classify_kernel (txn_check_dev.hip, txn-list-append).  Included
-// inside the including unit's unnamed namespace, after its `NONE`; one wavefront per history (blockDim.x == 64).  The front end builds
+// inside the including unit's unnamed namespace, after its `NONE` and check_dev.h (the wv_* helpers); one wavefront per history (blockDim.x == 64).  The front end builds
 // the tagged edges (to | kind << 28) as a CSR and its reverse in its workspace; what this file reads beside them is CycleParams.
 struct CycleParams {
   msim_check_result *out;
@@ -13,8 +13,6 @@ struct CycleWitness {
   msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // history i's steps at steps + i * max_steps
   const u32 *t_inv, *t_cmp;                                           // a transaction's :invoke row and completion row (NONE: never completed)
 };
-__device__ __forceinline__ u32 cw_min(u32 v) { for (int o = 32; o; o >>= 1) v = min(v, (u32)__shfl_xor((int)v, o)); return v; }
-__device__ __forceinline__ u32 cw_or(u32 v) { for (int o = 32; o; o >>= 1) v |= (u32)__shfl_xor((int)v, o); return v; }
 __device__ __forceinline__ u64 cw_min64(u64 v) {
   for (int o = 32; o; o >>= 1) { const u32 lo = (u32)__shfl_xor((int)(u32)v, o), hi = (u32)__shfl_xor((int)(u32)(v >> 32), o); v = min(v, ((u64)hi << 32) | lo); }
   return v;
@@ -206,7 +204,7 @@ __device__ __forceinline__ void cycle_classify(const CycleParams &p, const u32 h
           }
         }
       }
-      if (__ballot(hit)) { if constexpr (EXPLAIN) return cw_min(hv); else return 0u; }
+      if (__ballot(hit)) { if constexpr (EXPLAIN) return wv_min(hv); else return 0u; }
       __syncthreads();
     }
     return NONE;
@@ -242,7 +240,7 @@ __device__ __forceinline__ void cycle_classify(const CycleParams &p, const u32 h
       (void)search(off, adj, mask, pivot, 0u, FWD);
       const u32 s = search(roff, radj, mask, pivot, FWD, BWD);   // the queue now lists the pivot's component
       cyc += s;
-      if constexpr (EXPLAIN) { u32 m = NONE; for (u32 i = lane; i < s; i += 64) m = min(m, queue[i]); cmin = min(cmin, cw_min(m)); }
+      if constexpr (EXPLAIN) { u32 m = NONE; for (u32 i = lane; i < s; i += 64) m = min(m, queue[i]); cmin = min(cmin, wv_min(m)); }
       if (want_single && (EXPLAIN || !single) && !over) {
         if (s > p.ccap) {
           if (p.big) { const u32 h = single_by_search(mask, s); if constexpr (EXPLAIN) { single |= h != NONE; shead = min(shead, h); } else single = h != NONE; }
@@ -278,7 +276,7 @@ __device__ __forceinline__ void cycle_classify(const CycleParams &p, const u32 h
               }
             }
           }
-          if (__ballot(hit)) { single = true; if constexpr (EXPLAIN) shead = min(shead, cw_min(hv)); }
+          if (__ballot(hit)) { single = true; if constexpr (EXPLAIN) shead = min(shead, wv_min(hv)); }
         }
       }
       for (u32 i = lane; i < s; i += 64) st[queue[i]] = GONE;
@@ -337,12 +335,12 @@ __device__ __forceinline__ void cycle_classify(const CycleParams &p, const u32 h
     for (u32 i = L;; i--) {
       u32 kk = 0;
       for (u32 e = roff[cur] + lane; e < roff[cur + 1]; e += 64) { const u32 xe = radj[e]; if ((xe & E_TO) == src) kk |= xe >> 28; }
-      kk = (sg && i == L) ? E_RW : (cw_or(kk) & K);
+      kk = (sg && i == L) ? E_RW : (wv_or(kk) & K);
       if (lane == 0 && i < cw->max_steps) { msim_cycle_step sp; sp.txn = src; sp.inv_row = cw->t_inv[src]; sp.cmp_row = cw->t_cmp[src]; sp.kinds = kk; steps[i] = sp; }
       if (i == 0) break;
       u32 pw = NONE;   // the smallest predecessor one level up
       for (u32 e = roff[src] + lane; e < roff[src + 1]; e += 64) { const u32 xe = radj[e], f = xe & E_TO; if (((xe >> 28) & K) && d[f] == i - 1u) pw = min(pw, f); }
-      pw = cw_min(pw);
+      pw = wv_min(pw);
       if (pw == NONE) return;   // (there is one: the distance came along such an edge)
       cur = src; src = pw;
     }

@@ -7,7 +7,8 @@
 // anything else — an observation that disagrees with another one, a lost write, an aborted read, a process whose offsets do not
 // strictly increase or jump over a known offset, a row that does not decode, an offset or message beyond the tables — is answered
 // NEEDS_HOST and the host checker classifies it (kafka_dev_run below): never approximated.  A caller whose histories are not clean
-// (msim_classify_kafka_batch, msim_set_check_classify) has them classified by kafka_classify_kernel instead, see there.
+// (msim_classify_kafka_batch, msim_set_check_classify) has them classified by kafka_classify_kernel instead, see there.  The two kernels
+// are the two instantiations of one body, kafka_body<CLASSIFY>.
 //
 // Layout.  The tables of kafka_check.cpp (the key's log as observed, where each message was seen, polled / acknowledged / failed
 // flags) live in LDS, `T` entries per key (the configuration bounds offsets and messages by max-writes-per-key; a first pass over
@@ -27,11 +28,11 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "check_run.h"
-
-void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out);   // kafka_check.cpp
+#include "check_dev.h"
 
 namespace {
 
@@ -53,180 +54,13 @@ struct KCParams {
   u32 C;      // worker threads: process p belongs to worker p mod C
 };
 
-__device__ __forceinline__ u32 k_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ void k_wave_fence() {   // orders the LDS traffic of ONE wavefront across its lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// A poll's payload is a sequence of blocks: a header word (key, count, first offset), then the messages of offsets o0, o0 + 1, ...,
+// two a word.  A block whose words run past the row's len does not decode.
+struct PollBlock { u32 k, cnt, o0, words; };
+__device__ __forceinline__ PollBlock poll_block(u32 h) { const u32 cnt = (h >> 8) & 0xFFu; return PollBlock{h & 7u, cnt, h >> 16, (cnt + 1) / 2}; }
+__device__ __forceinline__ u32 block_msg(const u32 *w, u32 e) { return (w[e / 2] >> (16 * (e & 1))) & 0xFFFFu; }   // w: the block's first message word
 
 size_t kafka_lds_bytes(u32 T) { return ((size_t)KEYS * T * 2 + 3 * (size_t)KEYS * T / 32 + KEYS + 16 + CMAX * WST + NWV * STAGE) * 4; }
-
-__global__ void __launch_bounds__(NT) kafka_check_kernel(const KCParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const u32 hist = blockIdx.x, T = p.T, KT = KEYS * T, C = p.C;
-  u32 *const msg = reinterpret_cast<u32 *>(smem);          // [KEYS][T] the key's log as observed (EMPTY: offset never seen)
-  u32 *const where = msg + KT;                            // [KEYS][T] message -> 1 + the offset it was seen at
-  u32 *const polled = where + KT;                         // [KEYS * T / 32] bits
-  u32 *const acked = polled + KT / 32;
-  u32 *const failed = acked + KT / 32;                    // by message: its send definitely failed
-  u32 *const top1 = failed + KT / 32;                     // [KEYS] 1 + the highest polled offset
-  u32 *const hdr = top1 + KEYS;                           // [16]: [0] not provably clean, [1..] counters
-  u32 *const wst = hdr + 16;                              // [CMAX][WST]
-  u32 *const stg = wst + CMAX * WST + wave * STAGE;       // this wavefront's staging area
-
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
-
-  for (u32 i = tid; i < KT; i += NT) { msg[i] = EMPTY; where[i] = 0; }
-  for (u32 i = tid; i < 3 * KT / 32 + KEYS + 16; i += NT) polled[i] = 0;
-  for (u32 i = tid; i < CMAX * WST; i += NT) wst[i] = EMPTY;
-  __syncthreads();
-
-#define TO_HOST() do { hdr[0] = 1u; } while (0)
-#define SETBIT(a_, i_) atomicOr(&(a_)[(i_) >> 5], 1u << ((i_) & 31u))
-#define GETBIT(a_, i_) (((a_)[(i_) >> 5] >> ((i_) & 31u)) & 1u)
-  // every observation of (key, offset, message) must agree with every other one (inconsistent offsets, duplicates: the host's)
-  auto observe = [&](u32 k, u32 o, u32 m) __attribute__((always_inline)) {
-    if (k >= KEYS || o >= T || m >= T) { TO_HOST(); return; }
-    const u32 was = atomicCAS(&msg[k * T + o], EMPTY, m);
-    if (was != EMPTY && was != m) TO_HOST();
-    const u32 home = atomicCAS(&where[k * T + m], 0u, o + 1u);
-    if (home != 0u && home != o + 1u) TO_HOST();
-  };
-
-  // ---- pass 1: what exists, what was acknowledged, what was polled, which sends failed ----
-  u32 c_inv = 0, c_ok = 0, c_fail = 0, c_info = 0, c_att = 0, c_stable = 0;
-  for (u32 idx = tid; idx < n; idx += NT) {
-    const uint4 row = r[idx];
-    const u32 type = row.z & 3u, f = (row.z >> 2) & 31u, proc = row.z >> 12;
-    if (proc == MSIM_PROCESS_NEMESIS) continue;
-    c_inv += type == MSIM_T_INVOKE; c_ok += type == MSIM_T_OK; c_fail += type == MSIM_T_FAIL; c_info += type == MSIM_T_INFO;
-    if (f == MSIM_F_SEND) {
-      const u32 k = row.w & 63u, m = (row.w >> 6) & 0x7FFu, o = row.w >> 17;
-      if (type == MSIM_T_INVOKE) c_att++;
-      else if (type == MSIM_T_OK) {
-        if (o == 0x7FFu || k >= KEYS) { TO_HOST(); continue; }
-        c_stable++;
-        observe(k, o, m);
-        if (o < T) SETBIT(acked, k * T + o);
-      } else if (type == MSIM_T_FAIL) {
-        if (k < KEYS && m < T) SETBIT(failed, k * T + m); else if (k < KEYS && m < OFFS) TO_HOST();
-      }
-    } else if (f == MSIM_F_POLL && type == MSIM_T_OK) {
-      const u32 len = row.y >> 16;
-      if (len == 0) continue;
-      if ((u64)row.w + len > n_words) { TO_HOST(); continue; }
-      const u32 *const w = pay + row.w;
-      for (u32 q = 0; q < len;) {
-        const u32 h = w[q++], k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
-        if (q + (cnt + 1) / 2 > len) { TO_HOST(); break; }
-        for (u32 e = 0; e < cnt; e++) {
-          const u32 m = (w[q + e / 2] >> (16 * (e & 1))) & 0xFFFFu;
-          observe(k, o0 + e, m);
-          if (o0 + e < T) { SETBIT(polled, k * T + o0 + e); atomicMax(&top1[k], o0 + e + 1u); }
-        }
-        q += (cnt + 1) / 2;
-      }
-    }
-  }
-  atomicAdd(&hdr[1], c_inv); atomicAdd(&hdr[2], c_ok); atomicAdd(&hdr[3], c_fail); atomicAdd(&hdr[4], c_info);
-  atomicAdd(&hdr[5], c_att); atomicAdd(&hdr[6], c_stable);
-  __syncthreads();
-
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
-#define LEAVE_IF_DECIDED() do { if (hdr[0]) { if (tid == 0) p.out[hist] = res; return; } } while (0)
-  LEAVE_IF_DECIDED();
-
-  // ---- pass 1b: lost / unobserved writes, aborted reads ----
-  {
-    u32 unobs = 0;
-    for (u32 i = tid; i < KT; i += NT) {
-      const u32 k = i / T, o = i - k * T;
-      const bool pl = GETBIT(polled, i) != 0;
-      if (GETBIT(acked, i) && !pl) { if (o + 1u < top1[k]) TO_HOST(); else unobs++; }
-      if (pl) { const u32 m = msg[i]; if (m != EMPTY && GETBIT(failed, k * T + m)) TO_HOST(); }
-    }
-    atomicAdd(&hdr[7], unobs);
-  }
-
-  // ---- pass 2: every process's own sequence of offsets per key ----
-  for (u32 base = 0; base < n; base += 64) {
-    const u32 idx = base + lane;
-    uint4 row = make_uint4(0, 0, 0, 0);
-    if (idx < n) row = r[idx];
-    const u32 proc_l = row.z >> 12, type_l = row.z & 3u, f_l = (row.z >> 2) & 31u;
-    const bool rel = idx < n && proc_l != MSIM_PROCESS_NEMESIS && (proc_l % C) % NWV == wave &&
-                     ((f_l == MSIM_F_ASSIGN && type_l == MSIM_T_INVOKE) || (f_l == MSIM_F_POLL && (type_l == MSIM_T_FAIL || type_l == MSIM_T_INFO)) ||
-                      (type_l == MSIM_T_OK && (f_l == MSIM_F_SEND || f_l == MSIM_F_POLL)));
-    u64 todo = __ballot(rel);
-    while (todo) {
-      const u32 j = (u32)__builtin_ctzll(todo);
-      todo &= todo - 1;
-      const u32 rz = k_rl(row.z, j), rw = k_rl(row.w, j), ry = k_rl(row.y, j);
-      const u32 type = rz & 3u, f = (rz >> 2) & 31u, proc = rz >> 12;
-      u32 *const s = wst + (proc % C) * WST;
-      const u32 cur = s[16];
-      if (cur != proc) {   // the worker's next process starts with nothing remembered; a process that RETURNS is not a worker's stream
-        if (cur != EMPTY && proc < cur) TO_HOST();
-        k_wave_fence();
-        if (lane < 16) s[lane] = EMPTY; else if (lane == 16) s[16] = proc;
-        k_wave_fence();
-      }
-      // the positions change: nothing is tracked across an assign, nor across a poll that failed or crashed (kafka_check.cpp)
-      if (type != MSIM_T_OK) { if (lane < 8) s[lane] = EMPTY; continue; }
-      if (f == MSIM_F_SEND) {
-        const u32 k = rw & 63u, o = rw >> 17;
-        if (k >= KEYS || o >= OFFS) continue;
-        if (lane == k) { const u32 last = s[8 + k]; if (last != EMPTY && o <= last) TO_HOST(); s[8 + k] = o; }
-        continue;
-      }
-      const u32 len = ry >> 16;
-      if (len == 0) continue;
-      for (u32 q = lane; q < len && q < STAGE; q += 64) stg[q] = pay[rw + q];
-      k_wave_fence();
-      for (u32 q = 0; q < len;) {
-        const u32 h = q < STAGE ? stg[q] : pay[rw + q];
-        q++;
-        const u32 k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
-        if (q + (cnt + 1) / 2 > len) break;
-        q += (cnt + 1) / 2;
-        if (!cnt) continue;
-        // a block holds one run o0, o0 + 1, ...: it must start above the worker's last offset of the key and skip nothing known
-        if (lane == k) {
-          const u32 lp = s[k];
-          if (lp != EMPTY) {
-            if (o0 <= lp) TO_HOST();
-            else for (u32 o = lp + 1; o < o0; o++) if (o < T && msg[k * T + o] != EMPTY) { TO_HOST(); break; }
-          }
-          s[k] = o0 + cnt - 1u;
-        }
-      }
-      k_wave_fence();   // (the staging area is rewritten by the next poll)
-    }
-  }
-  __syncthreads();
-  LEAVE_IF_DECIDED();
-
-  if (tid == 0) {
-    res.op_count = hdr[1]; res.ok_count = hdr[2]; res.fail_count = hdr[3]; res.info_count = hdr[4];
-    res.attempt_count = hdr[5]; res.stable_count = hdr[6]; res.never_read_count = hdr[7];
-    res.valid = flags ? 0u : ((hdr[6] == 0 && hdr[2] == 0) ? 2u : 1u);
-    p.out[hist] = res;
-  }
-#undef LEAVE_IF_DECIDED
-#undef TO_HOST
-#undef SETBIT
-#undef GETBIT
-}
 
 // ---- the classification of unclean histories (msim_classify_kafka_batch, msim_set_check_classify) -------------------------------------
 // kafka_check_kernel leaves at the first anomaly; a caller whose node is buggy then pays a PCIe copy and a host check per history.
@@ -243,8 +77,8 @@ __global__ void __launch_bounds__(NT) kafka_check_kernel(const KCParams p) {
 //            duplicated_count, duplicate iff non-zero);
 //   pass 1b  acknowledged and never polled: lost below the key's highest polled offset, else unobserved; polled and the last message's
 //            send failed: aborted-read;
-//   pass 2   kafka_check_kernel's walk of the worker streams, setting bits: nonmonotonic-send, (int-)nonmonotonic-poll, (int-)poll-skip
-//            (int-: the key already had a block in this poll).
+//   pass 2   the walk of the worker streams, setting bits: nonmonotonic-send, (int-)nonmonotonic-poll, (int-)poll-skip (int-: the key
+//            already had a block in this poll).
 // Handed to the host checker (NEEDS_HOST, counted in n_host), and nothing else is:
 //   * a row or poll block that does not decode, an :ok send of a key >= 8, an offset or message >= OFFS: the host's MALFORMED;
 //   * a process that returns after a later process of its worker: not one stream per worker;
@@ -255,35 +89,33 @@ constexpr u64 SEEN = 1ull << 63;
 
 size_t kafka_classify_lds_bytes(u32 T) { return (size_t)KEYS * T * 16 + (4 * (size_t)KEYS * T / 32 + KEYS + 16 + CMAX * WST + NWV * STAGE) * 4; }
 
-// the histories the clean pass could not prove clean: list[0] = how many, list[1 ..] = which (in no particular order)
-__global__ void __launch_bounds__(256) kafka_todo_kernel(const msim_check_result *out, u32 n, u32 *list) {
-  const u32 i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n && out[i].valid == NEEDS_HOST) list[1u + atomicAdd(&list[0], 1u)] = i;
-}
-
-__global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, const u32 *list) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// The one body of kafka_check_kernel (CLASSIFY = false: the first finding decides, the history is the host's) and kafka_classify_kernel
+// (CLASSIFY = true: every finding is a bit or a count of the record).  The row loop, pass 1b's scan and pass 2's walk are the same; what
+// a mode does with an observation and with a finding stands behind the switch.  `smem`: kafka_lds_bytes / kafka_classify_lds_bytes.
+template <bool CLASSIFY>
+__device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, unsigned char *const smem) {
+  using Cell = std::conditional_t<CLASSIFY, unsigned long long, u32>;
+  constexpr Cell UNSEEN = CLASSIFY ? 0u : EMPTY;          // msg of an offset never seen
+  constexpr u32 BITMAPS = CLASSIFY ? 4u : 3u;
   const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const u32 hist = list[blockIdx.x], T = p.T, KT = KEYS * T, C = p.C;
-  unsigned long long *const msg = reinterpret_cast<unsigned long long *>(smem);   // [KEYS][T] SEEN | order | the message: the max is the last observation (0: offset never seen)
-  unsigned long long *const where = msg + KT;              // [KEYS][T] by message: order | the offset: the min is the first observation (~0: never seen)
-  u32 *const polled = reinterpret_cast<u32 *>(where + KT); // [KEYS * T / 32] bits
+  const u32 T = p.T, KT = KEYS * T, C = p.C;
+  // [KEYS][T] the key's log as observed.  Clean: the message (EMPTY: offset never seen).  CLASSIFY: SEEN | order | the message: the
+  // max is the last observation (0: offset never seen)
+  Cell *const msg = reinterpret_cast<Cell *>(smem);
+  // [KEYS][T] by message.  Clean: 1 + the offset it was seen at.  CLASSIFY: order | the offset: the min is the first observation (~0: never seen)
+  Cell *const where = msg + KT;
+  u32 *const polled = reinterpret_cast<u32 *>(where + KT);   // [KEYS * T / 32] bits
   u32 *const acked = polled + KT / 32;
   u32 *const failed = acked + KT / 32;                    // by message: its send definitely failed
-  u32 *const dup_at = failed + KT / 32;                   // by offset: some message seen here has its first home elsewhere
-  u32 *const top1 = dup_at + KT / 32;                     // [KEYS] 1 + the highest polled offset
-  u32 *const hdr = top1 + KEYS;                           // [16]: [0] the host's, [1..7] as kafka_check_kernel, [8] lost, [9] duplicates, [10] MSIM_KAFKA_* bits
+  u32 *const dup_at = failed + KT / 32;                   // CLASSIFY only, by offset: some message seen here has its first home elsewhere
+  u32 *const top1 = polled + BITMAPS * (KT / 32);         // [KEYS] 1 + the highest polled offset
+  u32 *const hdr = top1 + KEYS;                           // [16]: [0] the host's, [1..7] counters; CLASSIFY: [8] lost, [9] duplicates, [10] MSIM_KAFKA_* bits
   u32 *const wst = hdr + 16;                              // [CMAX][WST]
   u32 *const stg = wst + CMAX * WST + wave * STAGE;       // this wavefront's staging area
+  HIST_VIEW(p, hist);
 
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
-
-  for (u32 i = tid; i < KT; i += NT) { msg[i] = 0ull; where[i] = ~0ull; }
-  for (u32 i = tid; i < 4 * KT / 32 + KEYS + 16; i += NT) polled[i] = 0;
+  for (u32 i = tid; i < KT; i += NT) { msg[i] = UNSEEN; where[i] = CLASSIFY ? ~(Cell)0 : (Cell)0; }
+  for (u32 i = tid; i < BITMAPS * KT / 32 + KEYS + 16; i += NT) polled[i] = 0;
   for (u32 i = tid; i < CMAX * WST; i += NT) wst[i] = EMPTY;
   __syncthreads();
 
@@ -291,10 +123,18 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
 #define SETBIT(a_, i_) atomicOr(&(a_)[(i_) >> 5], 1u << ((i_) & 31u))
 #define GETBIT(a_, i_) (((a_)[(i_) >> 5] >> ((i_) & 31u)) & 1u)
   u32 bits = 0;
-  // `ord`: row index << 17 | ordinal inside the row.  sweep 0 records the observation, sweep 1 compares it with what all of them left
+  // an anomaly: the clean pass proves nothing about such a history, the classification names it
+  auto finding = [&](u32 bit) __attribute__((always_inline)) { if constexpr (CLASSIFY) bits |= bit; else TO_HOST(); };
+  // Clean: every observation of (key, offset, message) must agree with every other one (inconsistent offsets, duplicates: the host's).
+  // CLASSIFY, `ord` = row index << 17 | ordinal inside the row: sweep 0 records the observation, sweep 1 compares it with what all of them left
   auto observe = [&](u32 sweep, u32 k, u32 o, u32 m, u64 ord) __attribute__((always_inline)) {
-    if (o >= T || m >= T) { TO_HOST(); return; }
-    if (sweep == 0) {
+    if (k >= KEYS || o >= T || m >= T) { TO_HOST(); return; }
+    if constexpr (!CLASSIFY) {
+      const u32 was = atomicCAS(&msg[k * T + o], EMPTY, m);
+      if (was != EMPTY && was != m) TO_HOST();
+      const u32 home = atomicCAS(&where[k * T + m], 0u, o + 1u);
+      if (home != 0u && home != o + 1u) TO_HOST();
+    } else if (sweep == 0) {
       atomicMax(&msg[k * T + o], (unsigned long long)(SEEN | (ord << 11) | m));
       atomicMin(&where[k * T + m], (unsigned long long)((ord << 11) | o));
     } else {
@@ -303,16 +143,12 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
     }
   };
 
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+  BLANK_RESULT(res, NEEDS_HOST);
 
-  // ---- pass 1 (sweep 0) and pass 1' (sweep 1): every observation, in any order of the threads ----
-  for (u32 sweep = 0; sweep < 2; sweep++) {
+  // ---- pass 1 (sweep 0): what exists, what was acknowledged, what was polled, which sends failed; CLASSIFY: and pass 1' (sweep 1) ----
+  for (u32 sweep = 0; sweep < (CLASSIFY ? 2u : 1u); sweep++) {
     u32 c_inv = 0, c_ok = 0, c_fail = 0, c_info = 0, c_att = 0, c_stable = 0;
-    for (u32 idx = tid; idx < n; idx += NT) {
+    for (u32 idx = tid; idx < n_rows; idx += NT) {
       const uint4 row = r[idx];
       const u32 type = row.z & 3u, f = (row.z >> 2) & 31u, proc = row.z >> 12;
       if (proc == MSIM_PROCESS_NEMESIS) continue;
@@ -326,7 +162,9 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
           observe(sweep, k, o, m, (u64)idx << 17);
           if (sweep == 0 && o < T) SETBIT(acked, k * T + o);
         } else if (type == MSIM_T_FAIL && sweep == 0) {
-          if (k < KEYS && m < T) SETBIT(failed, k * T + m);   // (a message beyond the tables is never the last one of a cell: such an observation is the host's)
+          if (k < KEYS && m < T) SETBIT(failed, k * T + m);
+          // (CLASSIFY: a message beyond the tables is never the last one of a cell: such an observation is the host's)
+          else if constexpr (!CLASSIFY) { if (k < KEYS && m < OFFS) TO_HOST(); }
         }
       } else if (f == MSIM_F_POLL && type == MSIM_T_OK) {
         const u32 len = row.y >> 16;
@@ -335,14 +173,13 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
         const u32 *const w = pay + row.w;
         u64 ord = (u64)idx << 17;
         for (u32 q = 0; q < len;) {
-          const u32 h = w[q++], k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
-          if (q + (cnt + 1) / 2 > len) { TO_HOST(); break; }
-          for (u32 e = 0; e < cnt; e++, ord++) {
-            const u32 m = (w[q + e / 2] >> (16 * (e & 1))) & 0xFFFFu;
-            observe(sweep, k, o0 + e, m, ord);
-            if (sweep == 0 && o0 + e < T) { SETBIT(polled, k * T + o0 + e); atomicMax(&top1[k], o0 + e + 1u); }
+          const PollBlock b = poll_block(w[q++]);
+          if (q + b.words > len) { TO_HOST(); break; }
+          for (u32 e = 0; e < b.cnt; e++, ord++) {
+            observe(sweep, b.k, b.o0 + e, block_msg(w + q, e), ord);
+            if (sweep == 0 && b.o0 + e < T) { SETBIT(polled, b.k * T + b.o0 + e); atomicMax(&top1[b.k], b.o0 + e + 1u); }
           }
-          q += (cnt + 1) / 2;
+          q += b.words;
         }
       }
     }
@@ -351,91 +188,94 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
       atomicAdd(&hdr[5], c_att); atomicAdd(&hdr[6], c_stable);
     }
     __syncthreads();
-    // does not decode, or beyond the tables: the host's (pass 2 reads only payload that decodes).  Asked after sweep 0 only: sweep 1 finds
-    // nothing sweep 0 did not, and behind its barrier pass 2 of a faster wavefront may already be writing hdr[0]
+    // does not decode, or beyond the tables (clean: or any disagreement): the host's (pass 2 reads only payload that decodes).  Asked after
+    // sweep 0 only: sweep 1 finds nothing sweep 0 did not, and behind its barrier pass 2 of a faster wavefront may already be writing hdr[0]
     if (sweep == 0 && hdr[0]) { if (tid == 0) p.out[hist] = res; return; }
   }
 
-  // ---- pass 1b: lost / unobserved writes, aborted reads, the duplicates' offsets ----
+  // ---- pass 1b: lost / unobserved writes, aborted reads; CLASSIFY: the duplicates' offsets ----
   {
-    u32 unobs = 0, lost = 0, dups = 0;
+    u32 unobs = 0, lost = 0;
     for (u32 i = tid; i < KT; i += NT) {
       const u32 k = i / T, o = i - k * T;
       const bool pl = GETBIT(polled, i) != 0;
-      if (GETBIT(acked, i) && !pl) { if (o + 1u < top1[k]) lost++; else unobs++; }
-      if (pl) { const unsigned long long c = msg[i]; if (c != 0ull && GETBIT(failed, k * T + (u32)(c & 0x7FFull))) bits |= MSIM_KAFKA_ABORTED_READ; }
+      if (GETBIT(acked, i) && !pl) { if (o + 1u < top1[k]) { lost++; finding(MSIM_KAFKA_LOST_WRITE); } else unobs++; }
+      if (pl) { const Cell c = msg[i]; if (c != UNSEEN && GETBIT(failed, k * T + (CLASSIFY ? (u32)(c & 0x7FFull) : (u32)c))) finding(MSIM_KAFKA_ABORTED_READ); }
     }
-    for (u32 i = tid; i < KT / 32; i += NT) dups += (u32)__popc(dup_at[i]);
-    if (lost) { bits |= MSIM_KAFKA_LOST_WRITE; atomicAdd(&hdr[8], lost); }
-    if (dups) { bits |= MSIM_KAFKA_DUPLICATE; atomicAdd(&hdr[9], dups); }
+    if constexpr (CLASSIFY) {
+      u32 dups = 0;
+      for (u32 i = tid; i < KT / 32; i += NT) dups += (u32)__popc(dup_at[i]);
+      if (lost) atomicAdd(&hdr[8], lost);
+      if (dups) { bits |= MSIM_KAFKA_DUPLICATE; atomicAdd(&hdr[9], dups); }
+    }
     atomicAdd(&hdr[7], unobs);
   }
 
-  // ---- pass 2: every process's own sequence of offsets per key (kafka_check_kernel's walk; lane k holds key k) ----
-  for (u32 base = 0; base < n; base += 64) {
+  // ---- pass 2: every process's own sequence of offsets per key (lane k holds key k) ----
+  for (u32 base = 0; base < n_rows; base += 64) {
     const u32 idx = base + lane;
     uint4 row = make_uint4(0, 0, 0, 0);
-    if (idx < n) row = r[idx];
+    if (idx < n_rows) row = r[idx];
     const u32 proc_l = row.z >> 12, type_l = row.z & 3u, f_l = (row.z >> 2) & 31u;
-    const bool rel = idx < n && proc_l != MSIM_PROCESS_NEMESIS && (proc_l % C) % NWV == wave &&
+    const bool rel = idx < n_rows && proc_l != MSIM_PROCESS_NEMESIS && (proc_l % C) % NWV == wave &&
                      ((f_l == MSIM_F_ASSIGN && type_l == MSIM_T_INVOKE) || (f_l == MSIM_F_POLL && (type_l == MSIM_T_FAIL || type_l == MSIM_T_INFO)) ||
                       (type_l == MSIM_T_OK && (f_l == MSIM_F_SEND || f_l == MSIM_F_POLL)));
     u64 todo = __ballot(rel);
     while (todo) {
       const u32 j = (u32)__builtin_ctzll(todo);
       todo &= todo - 1;
-      const u32 rz = k_rl(row.z, j), rw = k_rl(row.w, j), ry = k_rl(row.y, j);
+      const u32 rz = wv_rl(row.z, j), rw = wv_rl(row.w, j), ry = wv_rl(row.y, j);
       const u32 type = rz & 3u, f = (rz >> 2) & 31u, proc = rz >> 12;
       u32 *const s = wst + (proc % C) * WST;
       const u32 cur = s[16];
       if (cur != proc) {   // the worker's next process starts with nothing remembered; a process that RETURNS is not a worker's stream
         if (cur != EMPTY && proc < cur) TO_HOST();
-        k_wave_fence();
+        wv_fence();
         if (lane < 16) s[lane] = EMPTY; else if (lane == 16) s[16] = proc;
-        k_wave_fence();
+        wv_fence();
       }
       // the positions change: nothing is tracked across an assign, nor across a poll that failed or crashed (kafka_check.cpp)
       if (type != MSIM_T_OK) { if (lane < 8) s[lane] = EMPTY; continue; }
       if (f == MSIM_F_SEND) {
         const u32 k = rw & 63u, o = rw >> 17;
         if (k >= KEYS || o >= OFFS) continue;
-        if (lane == k) { const u32 last = s[8 + k]; if (last != EMPTY && o <= last) bits |= MSIM_KAFKA_NONMONOTONIC_SEND; s[8 + k] = o; }
+        if (lane == k) { const u32 last = s[8 + k]; if (last != EMPTY && o <= last) finding(MSIM_KAFKA_NONMONOTONIC_SEND); s[8 + k] = o; }
         continue;
       }
       const u32 len = ry >> 16;
       if (len == 0) continue;
       for (u32 q = lane; q < len && q < STAGE; q += 64) stg[q] = pay[rw + q];
-      k_wave_fence();
+      wv_fence();
       bool internal = false;   // this lane's key already had a block in this poll: what follows is judged as an internal error
       for (u32 q = 0; q < len;) {
-        const u32 h = q < STAGE ? stg[q] : pay[rw + q];
+        const PollBlock b = poll_block(q < STAGE ? stg[q] : pay[rw + q]);
         q++;
-        const u32 k = h & 7u, cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
-        if (q + (cnt + 1) / 2 > len) break;
-        q += (cnt + 1) / 2;
-        if (!cnt) continue;
-        if (lane == k) {
-          const u32 lp = s[k];
+        if (q + b.words > len) break;
+        q += b.words;
+        if (!b.cnt) continue;
+        // a block holds one run o0, o0 + 1, ...: it must start above the worker's last offset of the key and skip nothing known
+        if (lane == b.k) {
+          const u32 lp = s[b.k];
           if (lp != EMPTY) {
-            if (o0 <= lp) bits |= internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL;
-            else for (u32 o = lp + 1; o < o0; o++) if (o < T && msg[k * T + o] != 0ull) { bits |= internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP; break; }
+            if (b.o0 <= lp) finding(internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL);
+            else for (u32 o = lp + 1; o < b.o0; o++) if (o < T && msg[b.k * T + o] != UNSEEN) { finding(internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP); break; }
           }
-          s[k] = o0 + cnt - 1u;
+          s[b.k] = b.o0 + b.cnt - 1u;
           internal = true;
         }
       }
-      k_wave_fence();   // (the staging area is rewritten by the next poll)
+      wv_fence();   // (the staging area is rewritten by the next poll)
     }
   }
-  if (bits) atomicOr(&hdr[10], bits);
+  if constexpr (CLASSIFY) { if (bits) atomicOr(&hdr[10], bits); }
   __syncthreads();
 
   if (tid == 0) {
     if (!hdr[0]) {
       res.op_count = hdr[1]; res.ok_count = hdr[2]; res.fail_count = hdr[3]; res.info_count = hdr[4];
       res.attempt_count = hdr[5]; res.stable_count = hdr[6]; res.never_read_count = hdr[7];
-      res.lost_count = hdr[8]; res.duplicated_count = hdr[9]; res.error_count = hdr[10];
-      res.valid = (flags || hdr[10]) ? 0u : ((hdr[6] == 0 && hdr[2] == 0) ? 2u : 1u);
+      if constexpr (CLASSIFY) { res.lost_count = hdr[8]; res.duplicated_count = hdr[9]; res.error_count = hdr[10]; }
+      res.valid = (flags || (CLASSIFY && hdr[10])) ? 0u : ((hdr[6] == 0 && hdr[2] == 0) ? 2u : 1u);
     }
     p.out[hist] = res;
   }
@@ -444,16 +284,29 @@ __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, co
 #undef GETBIT
 }
 
+__global__ void __launch_bounds__(NT) kafka_check_kernel(const KCParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  kafka_body<false>(p, blockIdx.x, smem);
+}
+
+// the histories the clean pass could not prove clean: list[0] = how many, list[1 ..] = which (in no particular order)
+__global__ void __launch_bounds__(256) kafka_todo_kernel(const msim_check_result *out, u32 n, u32 *list) {
+  const u32 i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n && out[i].valid == NEEDS_HOST) list[1u + atomicAdd(&list[0], 1u)] = i;
+}
+
+__global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, const u32 *list) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  kafka_body<true>(p, list[blockIdx.x], smem);
+}
+
 // The highest offset / message value any :ok send or poll of the launch names: sizes the tables (most tests use a fraction of what
 // max-writes-per-key allows, and the LDS a history's tables take decides how many histories a CU works on at once).
 __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *bound) {
-  const u32 tid = threadIdx.x, hist = blockIdx.x;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
+  const u32 tid = threadIdx.x;
+  HIST_VIEW(p, blockIdx.x);
   u32 hi = 0;
-  for (u32 idx = tid; idx < n; idx += NT) {
+  for (u32 idx = tid; idx < n_rows; idx += NT) {
     const uint4 row = r[idx];
     const u32 type = row.z & 3u, f = (row.z >> 2) & 31u;
     if ((row.z >> 12) == MSIM_PROCESS_NEMESIS || type == MSIM_T_INVOKE) continue;
@@ -463,15 +316,15 @@ __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *
       if (len == 0 || (u64)row.w + len > n_words) continue;
       const u32 *const w = pay + row.w;
       for (u32 q = 0; q < len;) {
-        const u32 h = w[q++], cnt = (h >> 8) & 0xFFu, o0 = h >> 16;
-        if (q + (cnt + 1) / 2 > len) break;
-        if (cnt) hi = max(hi, o0 + cnt - 1u);
-        for (u32 e = 0; e < cnt; e++) hi = max(hi, (w[q + e / 2] >> (16 * (e & 1))) & 0xFFFFu);
-        q += (cnt + 1) / 2;
+        const PollBlock b = poll_block(w[q++]);
+        if (q + b.words > len) break;
+        if (b.cnt) hi = max(hi, b.o0 + b.cnt - 1u);
+        for (u32 e = 0; e < b.cnt; e++) hi = max(hi, block_msg(w + q, e));
+        q += b.words;
       }
     }
   }
-  for (int o = 32; o; o >>= 1) hi = max(hi, (u32)__shfl_xor((int)hi, o));
+  hi = wv_max(hi);
   if ((tid & 63u) == 0 && hi) atomicMax(bound, hi);
 }
 

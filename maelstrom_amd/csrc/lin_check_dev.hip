@@ -36,10 +36,6 @@
 
 #include "check_run.h"
 
-void msim_lin_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);   // lin_check.cpp
-void msim_lin_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_lin_key_result *keys, uint32_t max_keys,
-                                    uint32_t *n_keys);                                                               // lin_check.cpp
-
 namespace {
 
 constexpr u32 NEEDS_HOST = 3u;          // msim_check_result.valid while a history awaits the host search

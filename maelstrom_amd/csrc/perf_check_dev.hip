@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "check_run.h"
+#include "check_dev.h"
 
 namespace {
 
@@ -43,15 +44,6 @@ struct PParams {
   u32 off_hist, off_end, off_cnt, off_unp, off_lm, off_tbl;   // LDS offsets in words; the sorted latencies lie at 0
 };
 
-__device__ __forceinline__ u32 p_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
-__device__ __forceinline__ u32 p_min(u32 v) { for (int o = 32; o; o >>= 1) v = min(v, (u32)__shfl_xor((int)v, o)); return v; }
-__device__ __forceinline__ u32 p_max(u32 v) { for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor((int)v, o)); return v; }
-// orders this wavefront's LDS traffic across its lanes (LDS operations of one wavefront execute in order: the compiler must not move them)
-__device__ __forceinline__ void p_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ u32 p_kth_bit(u32 mask, u32 k) { for (; k; k--) mask &= mask - 1; return (u32)__ffs((int)mask) - 1u; }
 
 // count, sum and the five quantiles of the latencies s[a .. b): by the 64 lanes together (WAVE: every lane calls, lane 0 writes) or by the
@@ -62,9 +54,9 @@ __device__ __forceinline__ void p_select(const u32 *s, u32 a, u32 b, u32 lane, m
   u32 mn = 0xFFFFFFFFu, mx = 0; u64 sum = 0;
   for (u32 e = first; e < b; e += step) { const u32 v = s[e]; mn = min(mn, v); mx = max(mx, v); sum += v; }
   if (WAVE) {
-    mn = p_min(mn); mx = p_max(mx);
-    const u32 lo = p_sum((u32)sum & 0xFFFFu), mid = p_sum(((u32)sum >> 16) & 0xFFFFu);   // (64 x 16 bits fit a word)
-    const u32 hi = p_sum((u32)(sum >> 32) & 0xFFFFu), top = p_sum((u32)(sum >> 48));
+    mn = wv_min(mn); mx = wv_max(mx);
+    const u32 lo = wv_sum((u32)sum & 0xFFFFu), mid = wv_sum(((u32)sum >> 16) & 0xFFFFu);   // (64 x 16 bits fit a word)
+    const u32 hi = wv_sum((u32)(sum >> 32) & 0xFFFFu), top = wv_sum((u32)(sum >> 48));
     sum = (u64)lo + ((u64)mid << 16) + ((u64)hi << 32) + ((u64)top << 48);
   }
   msim_latency_dist o;
@@ -78,7 +70,7 @@ __device__ __forceinline__ void p_select(const u32 *s, u32 a, u32 b, u32 lane, m
       const u32 mid = lo + (hi - lo) / 2;
       u32 c = 0;
       for (u32 e = first; e < b; e += step) c += s[e] <= mid ? 1u : 0u;
-      if (WAVE) c = p_sum(c);
+      if (WAVE) c = wv_sum(c);
       if (c > want) hi = mid; else lo = mid + 1;
     }
     return lo;
@@ -125,7 +117,7 @@ __global__ void __launch_bounds__(64) perf_check_kernel(const PParams p) {
     n_inv += live && type == MSIM_T_INVOKE ? 1u : 0u;
     if (comp) atomicAdd(&cnt[f * NT + type - 1], 1u);
     if (live) atomicOr(&lm[2 * slot + (lane >> 5)], 1u << (lane & 31u));
-    p_lds_fence();
+    wv_fence();
     // the previous row of the worker thread: the nearest lane below with the same thread, else what the chunks before left in the table
     const u64 m = live ? ((u64)lm[2 * slot] | ((u64)lm[2 * slot + 1] << 32)) : 0ull;
     const u64 below = m & lt;
@@ -134,7 +126,7 @@ __global__ void __launch_bounds__(64) perf_check_kernel(const PParams p) {
     const u32 pl = below ? 63u - (u32)__clzll((long long)below) : lane;
     const u32 sx = (u32)__shfl((int)r.x, (int)pl), sy = (u32)__shfl((int)r.y, (int)pl), sz = (u32)__shfl((int)r.z, (int)pl);
     if (comp && below) { px = sx; py = sy; pz = sz; }
-    p_lds_fence();
+    wv_fence();
     if (live && !((m >> lane) >> 1)) {   // the thread's last row of this chunk stays behind; its lane mask is cleared for the next chunk
       tbl[3 * slot] = r.x; tbl[3 * slot + 1] = r.y; tbl[3 * slot + 2] = r.z;
       lm[2 * slot] = 0; lm[2 * slot + 1] = 0;
@@ -182,7 +174,7 @@ __global__ void __launch_bounds__(64) perf_check_kernel(const PParams p) {
   const bool has = c_ok + c_fail + c_info > 0;
   const u32 fmask = (u32)__ballot(has);
   const u32 invalid = (u32)__ballot(has && c_ok == 0 && lane != MSIM_F_CRASH);
-  const u32 t_ok = p_sum(c_ok), t_fail = p_sum(c_fail), t_info = p_sum(c_info), t_inv = p_sum(n_inv);
+  const u32 t_ok = wv_sum(c_ok), t_fail = wv_sum(c_fail), t_info = wv_sum(c_info), t_inv = wv_sum(n_inv);
   const u32 n_dist = (u32)__popc(fmask), n_f = min(n_dist, (u32)MSIM_PERF_MAX_F);
   msim_perf_result *const o = p.out + inst;
   if (lane == 0) {

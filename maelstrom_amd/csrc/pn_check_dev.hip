@@ -12,8 +12,7 @@
 #include <vector>
 
 #include "check_run.h"
-
-void msim_pn_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);   // pn_check.cpp
+#include "check_dev.h"
 
 namespace {
 
@@ -22,7 +21,6 @@ constexpr u32 MAX_INFO = 1024u;
 
 typedef long long s64;
 
-__device__ __forceinline__ u32 p_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
 __device__ __forceinline__ s64 p_sum64(s64 v) {
   for (int o = 32; o; o >>= 1) { const u32 lo = (u32)__shfl_xor((int)(u32)v, o), hi = (u32)__shfl_xor((int)(u32)((u64)v >> 32), o); v += (s64)(((u64)hi << 32) | lo); }
   return v;
@@ -64,11 +62,9 @@ __global__ void __launch_bounds__(64) pn_check_kernel(const msim_op *rows_all, c
   }
   __syncthreads();
   definite = p_sum64(definite); neg = p_sum64(neg); pos = p_sum64(pos);
-  c_inv = p_sum(c_inv); c_ok = p_sum(c_ok); c_fail = p_sum(c_fail); c_info = p_sum(c_info);
+  c_inv = wv_sum(c_inv); c_ok = wv_sum(c_ok); c_fail = wv_sum(c_fail); c_info = wv_sum(c_info);
   const u32 n_info = n_info_s;
-  msim_check_result o;
-  o.valid = NEEDS_HOST; o.attempt_count = 0; o.stable_count = 0; o.lost_count = 0; o.never_read_count = 0; o.stale_count = 0; o.duplicated_count = 0; o.error_count = 0;
-  for (int i = 0; i < 5; i++) o.stable_latency_ms[i] = 0;
+  BLANK_RESULT(o, NEEDS_HOST);
   o.op_count = c_inv; o.ok_count = c_ok; o.fail_count = c_fail; o.info_count = c_info;
   if (n_info > MAX_INFO || pos - neg >= 4096) { if (lane == 0) out[hist] = o; return; }
 
@@ -93,7 +89,7 @@ __global__ void __launch_bounds__(64) pn_check_kernel(const msim_op *rows_all, c
   bits[lane] = B;
   __syncthreads();
   // ranges = maximal runs of ones
-  { const u64 prev_top = p_get64(B, (int)lane - 1) >> 63; o.stable_count = p_sum((u32)__popcll(B & ~((B << 1) | prev_top))); }
+  { const u64 prev_top = p_get64(B, (int)lane - 1) >> 63; o.stable_count = wv_sum((u32)__popcll(B & ~((B << 1) | prev_top))); }
   // final reads that completed :ok must lie in the set
   u32 attempts = 0, errors = 0;
   for (u32 base = 0; base < n; base += 64) {
@@ -106,7 +102,7 @@ __global__ void __launch_bounds__(64) pn_check_kernel(const msim_op *rows_all, c
     const bool ok = rel >= 0 && rel < 4096 && ((bits[(u32)rel >> 6] >> ((u32)rel & 63u)) & 1ull);
     errors += ok ? 0u : 1u;
   }
-  attempts = p_sum(attempts); errors = p_sum(errors);
+  attempts = wv_sum(attempts); errors = wv_sum(errors);
   if (lane == 0) {
     o.attempt_count = attempts; o.error_count = errors;
     o.valid = flags ? 0u : (errors == 0 ? 1u : 0u);

@@ -21,12 +21,12 @@
 // (msim_classify_rw_batch, msim_set_check_classify).
 //
 // Steps (lane = transaction unless said otherwise), tables in an HBM workspace as in txn_check_kernel:
-//   A  rows -> transactions, completions paired by process (the walk of txn_check_kernel);
+//   A  rows -> transactions, completions paired by process (txn_pairing.inc, shared with the list-append kernels);
 //   B  key / value ranges; C  writer table (key, value) -> transaction by compare-and-swap, versions seen per key;
 //   D  per :ok transaction: internal consistency, G1a / G1b, wr edges, "writes follow reads" version edges (64-bit sets by atomics);
 //   E  per key (lane = key): nil precedes every version; a cyclic version order is found by peeling the versions without predecessor;
 //      ww edges along the version order; rw edges from the external reads (stronger models only);
-//   F  Kahn's algorithm over the edges built;  G (rw_classify_kernel only)  the cycle classes: cycle_classify.inc.
+//   F  Kahn's algorithm over the edges built (txn_kahn.inc; the realtime order: txn_realtime.inc);  G (rw_classify_kernel only)  the cycle classes: cycle_classify.inc.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,11 +35,7 @@
 #include <vector>
 
 #include "check_run.h"
-
-void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
-                                 msim_check_result *res);   // txn_check.cpp
-void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
-                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);   // txn_check.cpp
+#include "check_dev.h"
 
 namespace {
 
@@ -62,15 +58,6 @@ struct RParams {
   msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // rw_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
 };
 
-__device__ __forceinline__ u32 r_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ u32 r_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
-__device__ __forceinline__ u32 r_max(u32 v) { for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor((int)v, o)); return v; }
-__device__ __forceinline__ u32 r_or(u32 v) { for (int o = 32; o; o >>= 1) v |= (u32)__shfl_xor((int)v, o); return v; }
-__device__ __forceinline__ u32 r_excl_scan(u32 v, u32 lane) {
-  u32 x = v;
-  for (int o = 1; o < 64; o <<= 1) { const u32 y = (u32)__shfl_up((int)x, o); if (lane >= (u32)o) x += y; }
-  return x - v;
-}
 // one micro-op = one payload word: f (1 = write), key, value (0xFF: a read of nil)
 #define M_F(w_) ((w_) & 1u)
 #define M_KEY(w_) (((w_) >> 1) & 0x7FFFu)
@@ -87,11 +74,7 @@ template <bool FULL, bool EXPLAIN = false>
 __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   const u32 lane = threadIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n_rows = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
+  HIST_VIEW(p, hist);
   const u32 NM = p.nmax;
   const bool strong = FULL || p.cm <= MSIM_CM_SNAPSHOT_ISOLATION;            // every edge kind counts
   const bool want_rt = FULL || p.cm == MSIM_CM_STRICT_SERIALIZABLE;
@@ -110,18 +93,14 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   u32 *const radj = adj + p.emax, *const roff = radj + p.emax, *const rcur = roff + NM + 1, *const st = rcur + NM, *const jump = st + NM;
   // and a 64-bit word per transaction for the search of a component beyond the matrix [NM], on an 8-byte boundary
 
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+  BLANK_RESULT(res, NEEDS_HOST);
 #define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
   if (n_words >= (1u << 24)) TO_HOST();
 
-  // ---- A: transactions (txn_check_kernel's pairing) ---------------------------------------------------------------------------------
+  // ---- A: transactions ---------------------------------------------------------------------------------------------------------
   u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0, anomalies = 0;
   {
-    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // lane = one open call (o_len: words of its request)
+    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // txn_pairing.inc's open calls
     for (u32 base = 0; base < n_rows; base += 64) {
       const u32 idx = base + lane;
       uint4 row = make_uint4(0, 0, 0, 0);
@@ -136,31 +115,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
       const u32 my_t = n + (u32)__popcll(im & lt);
       if (n + (u32)__popcll(im) > NM) { bad = true; break; }
       if (inv) { t_inv[my_t] = idx; t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); t_first[my_t] = 0; }   // never completed = indeterminate
-      u64 m = __ballot(is);
-      while (m) {
-        const u32 j = (u32)__builtin_ctzll(m); m &= m - 1;
-        const u32 z = r_rl(row.z, j);
-        const u32 jt = z & 3u, jp = z >> 12;
-        const u64 hit = __ballot(o_used && o_proc == jp);
-        if (jt == MSIM_T_INVOKE) {
-          u32 s;
-          if (hit) s = (u32)__builtin_ctzll(hit);
-          else { const u64 used = __ballot(o_used); if (used == ~0ull) { bad = true; break; } s = (u32)__builtin_ctzll(~used); }
-          const u32 tj = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-          const u32 jl = r_rl(row.y, j) >> 16;
-          if (lane == s) { o_used = true; o_proc = jp; o_txn = tj; o_len = jl; }
-        } else if (hit) {
-          const u32 s = (u32)__builtin_ctzll(hit);
-          const u32 id = r_rl(o_txn, s), ilen = r_rl(o_len, s);
-          if (lane == s) o_used = false;
-          if (lane == j) {
-            t_cmp[id] = idx; t_first[id] = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-            if (jt == MSIM_T_OK) { t_off[id] = woff; t_lt[id] = len | (MSIM_T_OK << 16); }   // the completed form replaces the requested one
-            else t_lt[id] = ilen | (jt << 16);
-          }
-          c_ok += jt == MSIM_T_OK; c_fail += jt == MSIM_T_FAIL; c_info += jt == MSIM_T_INFO;
-        }
-      }
+#include "txn_pairing.inc"
       if (bad) break;
       n += (u32)__popcll(im);
     }
@@ -175,7 +130,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
     const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
     for (u32 i = 0; i < wn; i++) { const u32 x = w[i]; max_key = max(max_key, M_KEY(x)); if (M_VAL(x) != 0xFFu) max_val = max(max_val, M_VAL(x)); }
   }
-  max_key = r_max(max_key); max_val = r_max(max_val);
+  max_key = wv_max(max_key); max_val = wv_max(max_val);
   const u32 stride = max_val + 1u;
   if (max_val >= 64u || max_key >= p.kmax || (u64)(max_key + 1u) * stride > p.wmax) TO_HOST();   // (check_rw answers :unknown for values >= 64)
   for (u32 k = lane; k <= max_key; k += 64) { vseen[2 * k] = 0; vseen[2 * k + 1] = 0; }
@@ -209,21 +164,8 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
 
   // ---- D/E: edges: pass 0 counts degrees (and finds the non-cycle anomalies), pass 1 fills the CSR ----------------------------------------
   u32 n_edges = 0;
-  if (want_rt) {   // realtime order in closed form (txn_check_kernel): sm[j] = earliest :ok completion among transactions j .. n-1
-    u64 carry = ~0ull;
-    for (int b = (int)((n + 63u) / 64u) - 1; b >= 0; b--) {
-      const u32 t = (u32)b * 64u + lane;
-      u64 v = (t < n && TYPE(t) == MSIM_T_OK) ? (((u64)t_cmp[t] << 32) | t_first[t]) : ~0ull;
-      for (int o = 1; o < 64; o <<= 1) {
-        const u32 ylo = (u32)__shfl_down((int)(u32)v, o), yhi = (u32)__shfl_down((int)(u32)(v >> 32), o);
-        const u64 y = ((u64)yhi << 32) | ylo;
-        if (lane + (u32)o < 64u) v = min(v, y);
-      }
-      v = min(v, carry);
-      if (t < n) { sm[t] = (u32)(v >> 32); smf[t] = (u32)v; }
-      carry = ((u64)r_rl((u32)(v >> 32), 0) << 32) | r_rl((u32)v, 0);
-    }
-    if (lane == 0) { sm[n] = NONE; smf[n] = n; }
+  if (want_rt) {   // the realtime order in closed form
+#include "txn_realtime.inc"
     __syncthreads();
   }
   for (int pass = 0; pass < 2; pass++) {
@@ -337,30 +279,30 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
 #undef ADD
     __syncthreads();
     if (pass == 0) {
-      n_edges = r_sum(my_edges);
+      n_edges = wv_sum(my_edges);
       if (n_edges > p.emax) TO_HOST();
       u32 carry = 0;   // out-degrees -> CSR offsets (exclusive prefix sums, 64 at a time)
       for (u32 base = 0; base <= n; base += 64) {
         const u32 t = base + lane;
         const u32 d = t < n ? off[t] : 0u;
-        const u32 ex = r_excl_scan(d, lane);
+        const u32 ex = wv_excl_scan(d, lane);
         if (t <= n) off[t] = carry + ex;
-        carry += r_sum(d);
+        carry += wv_sum(d);
       }
       if constexpr (FULL) {   // in-degrees -> offsets of the reversed edges
         carry = 0;
         for (u32 base = 0; base <= n; base += 64) {
           const u32 t = base + lane;
           const u32 d = t < n ? indeg[t] : 0u;
-          const u32 ex = r_excl_scan(d, lane);
+          const u32 ex = wv_excl_scan(d, lane);
           if (t <= n) roff[t] = carry + ex;
-          carry += r_sum(d);
+          carry += wv_sum(d);
         }
       }
       __syncthreads();
     }
   }
-  anomalies = r_or(anomalies);
+  anomalies = wv_or(anomalies);
 
   if constexpr (FULL) {
     u64 *const reach = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(jump + NM) + 7u) & ~(uintptr_t)7u);
@@ -372,32 +314,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
     return;
   }
   // ---- F: acyclic?  Kahn's algorithm, 64 ready transactions per step ---------------------------------------------------------------------
-  u32 tail = 0;
-  for (u32 base = 0; base < n; base += 64) {
-    const u32 t = base + lane;
-    const bool z = t < n && indeg[t] == 0;
-    const u64 zm = __ballot(z);
-    if (z) queue[tail + (u32)__popcll(zm & lt)] = t;
-    tail += (u32)__popcll(zm);
-  }
-  __syncthreads();
-  u32 head = 0;
-  while (head < tail) {
-    const u32 snap = tail;
-    const u32 cnt = min(64u, snap - head);
-    const bool on = lane < cnt;
-    const u32 v = on ? queue[head + lane] : 0u;
-    const u32 a0 = on ? off[v] : 0u, a1 = on ? off[v + 1] : 0u;
-    for (u32 k = 0; __ballot(a0 + k < a1); k++) {
-      bool push = false; u32 wv = 0;
-      if (a0 + k < a1) { wv = adj[a0 + k]; push = atomicSub(&indeg[wv], 1u) == 1u; }
-      const u64 pm = __ballot(push);
-      if (push) queue[tail + (u32)__popcll(pm & lt)] = wv;
-      tail += (u32)__popcll(pm);
-    }
-    head += cnt;
-    __syncthreads();
-  }
+#include "txn_kahn.inc"
   if (tail != n) TO_HOST();   // a cycle over edge kinds the model proscribes cycles of (or, for the stronger models, any cycle): the host classifies it
 
   if (lane == 0) {

@@ -15,7 +15,7 @@
 //
 // Data-parallel restatement of the host's steps (lane = transaction unless said otherwise):
 //   A  rows -> transactions: invocations numbered by prefix sums; completions paired by process through a table of open calls
-//      in lane registers (the one serial walk);
+//      in lane registers (the one serial walk: txn_pairing.inc);
 //   B  key / element ranges; C  writer table (key, element) -> transaction by compare-and-swap (a second writer = duplicate);
 //   D  per :ok read: duplicates (256-bit set in registers), internal consistency against the transaction's own earlier micro-ops,
 //      G1a / G1b through the writer table, the key's longest read by atomic max;
@@ -25,6 +25,8 @@
 //      index range read off two prefix counts taken while pairing and a suffix minimum (the host walks the history and edits a
 //      frontier list);
 //   F  acyclicity by Kahn's algorithm: 64 ready transactions per step, in-degrees by atomics, the ready queue by ballots.
+// The walk of A, the closed form of E (txn_realtime.inc) and F (txn_kahn.inc) are text includes shared with rw_check_dev.hip; the history
+// prologue, the blank record and the wavefront helpers (wv_*) are check_dev.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,11 +36,7 @@
 #include <vector>
 
 #include "check_run.h"
-
-void msim_txn_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm,
-                                  msim_check_result *res);   // txn_check.cpp
-void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
-                                    msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);   // txn_check.cpp
+#include "check_dev.h"
 
 namespace {
 
@@ -61,14 +59,6 @@ struct TParams {
   msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // txn_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
 };
 
-__device__ __forceinline__ u32 t_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ u32 t_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
-__device__ __forceinline__ u32 t_max(u32 v) { for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor((int)v, o)); return v; }
-__device__ __forceinline__ u32 t_excl_scan(u32 v, u32 lane) {   // exclusive prefix sum over the wavefront
-  u32 x = v;
-  for (int o = 1; o < 64; o <<= 1) { const u32 y = (u32)__shfl_up((int)x, o); if (lane >= (u32)o) x += y; }
-  return x - v;
-}
 __device__ __forceinline__ u32 elem(const u32 *lw, u32 e) { return (lw[e >> 2] >> (8u * (e & 3u))) & 0xFFu; }
 
 // one micro-op of a transaction's payload words w[0 .. n): header, then the list of a read
@@ -85,11 +75,7 @@ __device__ __forceinline__ Mop next_mop(const u32 *w, u32 n, u32 &i) {
 __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
   const u32 lane = threadIdx.x, hist = p.list ? p.list[p.first + blockIdx.x] : p.first + blockIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n_rows = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
+  HIST_VIEW(p, hist);
   const u32 NM = p.nmax;
   u32 *const ws = p.ws + (u64)blockIdx.x * p.ws_words;
   u32 *const t_inv = ws, *const t_cmp = t_inv + NM, *const t_off = t_cmp + NM, *const t_lt = t_off + NM;   // t_lt: words | type << 16
@@ -102,11 +88,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
   u32 *const writer = longest + KMAX;        // [WMAX]
   u32 *const adj = writer + WMAX;            // [emax]
 
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+  BLANK_RESULT(res, NEEDS_HOST);
 #define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
 #ifdef TC_PROF   // developer build: cycles per phase in the result's unused fields
   u64 tc_prev = __builtin_readcyclecounter(); u32 tc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -119,7 +101,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
   // ---- A: transactions ---------------------------------------------------------------------------------------------------------
   u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0;
   {
-    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // lane = one open call (o_len: words of its request)
+    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // txn_pairing.inc's open calls
     for (u32 base = 0; base < n_rows; base += 64) {
       const u32 idx = base + lane;
       uint4 row = make_uint4(0, 0, 0, 0);
@@ -132,31 +114,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
       const u32 my_t = n + (u32)__popcll(im & lt);
       if (n + (u32)__popcll(im) > NM) { bad = true; break; }
       if (inv) { t_inv[my_t] = idx; t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); }   // never completed = indeterminate
-      u64 m = __ballot(is);
-      while (m) {
-        const u32 j = (u32)__builtin_ctzll(m); m &= m - 1;
-        const u32 z = t_rl(row.z, j);
-        const u32 jt = z & 3u, jp = z >> 12;
-        const u64 hit = __ballot(o_used && o_proc == jp);
-        if (jt == MSIM_T_INVOKE) {
-          u32 s;
-          if (hit) s = (u32)__builtin_ctzll(hit);
-          else { const u64 used = __ballot(o_used); if (used == ~0ull) { bad = true; break; } s = (u32)__builtin_ctzll(~used); }
-          const u32 tj = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-          const u32 jl = t_rl(row.y, j) >> 16;
-          if (lane == s) { o_used = true; o_proc = jp; o_txn = tj; o_len = jl; }
-        } else if (hit) {
-          const u32 s = (u32)__builtin_ctzll(hit);
-          const u32 id = t_rl(o_txn, s), ilen = t_rl(o_len, s);
-          if (lane == s) o_used = false;
-          if (lane == j) {
-            t_cmp[id] = idx; t_first[id] = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-            if (jt == MSIM_T_OK) { t_off[id] = woff; t_lt[id] = len | (MSIM_T_OK << 16); }   // the completed form replaces the requested one
-            else t_lt[id] = ilen | (jt << 16);
-          }
-          c_ok += jt == MSIM_T_OK; c_fail += jt == MSIM_T_FAIL; c_info += jt == MSIM_T_INFO;
-        }
-      }
+#include "txn_pairing.inc"
       if (bad) break;
       n += (u32)__popcll(im);
     }
@@ -172,7 +130,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
     const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
     for (u32 i = 0; i < wn;) { const Mop m = next_mop(w, wn, i); bad |= m.bad; max_key = max(max_key, m.key); if (m.f) max_val = max(max_val, m.val); }
   }
-  max_key = t_max(max_key); max_val = t_max(max_val);
+  max_key = wv_max(max_key); max_val = wv_max(max_val);
   const u32 stride = max_val + 1u;
   if (__ballot(bad) || max_key >= KMAX || (u64)(max_key + 1u) * stride > WMAX) TO_HOST();
   for (u32 k = lane; k <= max_key; k += 64) longest[k] = 0;
@@ -237,24 +195,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
   if (__ballot(bad)) TO_HOST();
 
   TC_MARK(3)
-  // realtime order in closed form: sm[j] = earliest :ok completion among transactions j .. n-1 (smf[j]: how many transactions were
-  // invoked before that completion)
-  {
-    u64 carry = ~0ull;
-    for (int b = (int)((n + 63u) / 64u) - 1; b >= 0; b--) {
-      const u32 t = (u32)b * 64u + lane;
-      u64 v = (t < n && (t_lt[t] >> 16) == MSIM_T_OK) ? (((u64)t_cmp[t] << 32) | t_first[t]) : ~0ull;
-      for (int o = 1; o < 64; o <<= 1) {
-        const u32 ylo = (u32)__shfl_down((int)(u32)v, o), yhi = (u32)__shfl_down((int)(u32)(v >> 32), o);
-        const u64 y = ((u64)yhi << 32) | ylo;
-        if (lane + (u32)o < 64u) v = min(v, y);
-      }
-      v = min(v, carry);
-      if (t < n) { sm[t] = (u32)(v >> 32); smf[t] = (u32)v; }
-      carry = ((u64)t_rl((u32)(v >> 32), 0) << 32) | t_rl((u32)v, 0);
-    }
-    if (lane == 0) { sm[n] = NONE; smf[n] = n; }
-  }
+#include "txn_realtime.inc"
   __syncthreads();
 
   TC_MARK(4)
@@ -302,16 +243,16 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
     __syncthreads();
     if (__ballot(bad)) TO_HOST();
     if (pass == 0) {
-      n_edges = t_sum(my_edges);
+      n_edges = wv_sum(my_edges);
       if (n_edges > p.emax) TO_HOST();
       // out-degrees -> CSR offsets (exclusive prefix sums, 64 at a time)
       u32 carry = 0;
       for (u32 base = 0; base <= n; base += 64) {
         const u32 t = base + lane;
         const u32 d = t < n ? off[t] : 0u;
-        const u32 ex = t_excl_scan(d, lane);
+        const u32 ex = wv_excl_scan(d, lane);
         if (t <= n) off[t] = carry + ex;
-        carry += t_sum(d);
+        carry += wv_sum(d);
       }
       __syncthreads();
     }
@@ -319,32 +260,7 @@ __global__ void __launch_bounds__(64) txn_check_kernel(const TParams p) {
 
   TC_MARK(5)
   // ---- F: acyclic?  Kahn's algorithm, 64 ready transactions per step -------------------------------------------------------------------------
-  u32 tail = 0;
-  for (u32 base = 0; base < n; base += 64) {
-    const u32 t = base + lane;
-    const bool z = t < n && indeg[t] == 0;
-    const u64 zm = __ballot(z);
-    if (z) queue[tail + (u32)__popcll(zm & lt)] = t;
-    tail += (u32)__popcll(zm);
-  }
-  __syncthreads();
-  u32 head = 0;
-  while (head < tail) {
-    const u32 snap = tail;
-    const u32 cnt = min(64u, snap - head);
-    const bool on = lane < cnt;
-    const u32 v = on ? queue[head + lane] : 0u;
-    const u32 a0 = on ? off[v] : 0u, a1 = on ? off[v + 1] : 0u;
-    for (u32 k = 0; __ballot(a0 + k < a1); k++) {
-      bool push = false; u32 wv = 0;
-      if (a0 + k < a1) { wv = adj[a0 + k]; push = atomicSub(&indeg[wv], 1u) == 1u; }
-      const u64 pm = __ballot(push);
-      if (push) queue[tail + (u32)__popcll(pm & lt)] = wv;
-      tail += (u32)__popcll(pm);
-    }
-    head += cnt;
-    __syncthreads();
-  }
+#include "txn_kahn.inc"
   TC_MARK(6)
   if (tail != n) TO_HOST();   // a cycle: the host finds and classifies it
 
@@ -388,11 +304,6 @@ __device__ __forceinline__ u32 h16_get(const u32 *w, u32 i) { return (w[i >> 1] 
 // minimum, the CSR prefix sums, Kahn's queue) stay on wavefront 0 while the others wait at the next barrier.  smem[0 .. 64) is the
 // workgroup's header: [0] verdict so far (0 go on, 1 tables do not fit -> txn_check_kernel, 2 not provably clean -> host), [1] n,
 // [2..4] ok / fail / info counts, [5] max key, [6] max element, [7] edges, [8] dependency edges.
-__device__ __forceinline__ void t_wave_fence() {   // orders the LDS / workspace traffic of ONE wavefront across its lanes (no s_barrier)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Two workgroups of sixteen wavefronts share a CU only at EIGHT wavefronts per SIMD: <= 64 vector and <= 96 scalar registers (the compiler's own choice,
 // 106 scalar registers, allowed seven — the second workgroup waited for the first to END: 252 histories in flight, not 512; tools/txn_check_prof_report.py).
@@ -404,11 +315,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
   const u32 tid = threadIdx.x, NT = blockDim.x, lane = tid & 63u, wave = tid >> 6;
   const u32 hist = p.list ? p.list[p.first + blockIdx.x] : p.first + blockIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n_rows = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
+  HIST_VIEW(p, hist);
   const u32 NM = p.nmax;
   u32 *const ws = p.ws + (u64)blockIdx.x * p.ws_words;
   u32 *const t_cmp = ws, *const t_off = t_cmp + NM, *const t_lt = t_off + NM;   // t_lt: words | type << 16
@@ -418,11 +325,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
   u32 *const hdr = reinterpret_cast<u32 *>(smem);
   unsigned char *const tab = smem + 64;
 
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+  BLANK_RESULT(res, NEEDS_HOST);
   // every thread of the workgroup sees the same verdict behind a barrier and leaves with it
 #define VERDICT(v_) atomicMax(&hdr[0], (u32)(v_))
 #define LEAVE_IF_DECIDED() do { __syncthreads(); const u32 vd_ = hdr[0]; if (vd_) { if (tid == 0) { res.valid = vd_ == 1u ? NEEDS_HBM : NEEDS_HOST; p.out[hist] = res; } return; } } while (0)
@@ -471,13 +374,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
       u64 rem = __ballot(is);
       while (rem) {
         const u32 j = (u32)__builtin_ctzll(rem);
-        const u32 pj = t_rl(proc, j);
+        const u32 pj = wv_rl(proc, j);
         const u64 same = __ballot(is && proc == pj);
         rem &= ~same;
         const u64 below = same & lt;
         if (is && proc == pj && below) pl = 63u - (u32)__builtin_clzll(below);
         const u32 last = 63u - (u32)__builtin_clzll(same);
-        const u32 info = (t_rl(inv ? 1u : 0u, last) << 31) | (t_rl(rank, last) << 16) | t_rl(len, last);
+        const u32 info = (wv_rl(inv ? 1u : 0u, last) << 31) | (wv_rl(rank, last) << 16) | wv_rl(len, last);
         if (np < TC_PROCS) { if (lane == 0) { blk_list[((size_t)b * TC_PROCS + np) * 2u] = pj; blk_list[((size_t)b * TC_PROCS + np) * 2u + 1u] = info; } }
         else bad = max(bad, 2u);
         np++;
@@ -493,7 +396,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
     for (u32 base = 0; base <= NB; base += 64) {
       const u32 b = base + lane;
       const u32 d = b < NB ? blk_base[b] : 0u;
-      const u32 ex = t_excl_scan(d, lane), tot = t_sum(d);
+      const u32 ex = wv_excl_scan(d, lane), tot = wv_sum(d);
       if (b <= NB) blk_base[b] = carry + ex;
       carry += tot;
     }
@@ -567,7 +470,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
       const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
       for (u32 i = 0; i < wn;) { const Mop m = next_mop(w, wn, i); bad |= m.bad; max_key = max(max_key, m.key); if (m.f) max_val = max(max_val, m.val); }
     }
-    max_key = t_max(max_key); max_val = t_max(max_val);
+    max_key = wv_max(max_key); max_val = wv_max(max_val);
     if (lane == 0) { atomicMax(&hdr[5], max_key); atomicMax(&hdr[6], max_val); }
     if (bad) VERDICT(2);
   }
@@ -653,23 +556,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
   if (bad) VERDICT(2);
 
   TL_MARK(3)
-  // realtime order in closed form (see txn_check_kernel): wavefront 0, beside the other wavefronts' share of pass D
-  if (wave == 0) {
-    u64 carry = ~0ull;
-    for (int b = (int)((n + 63u) / 64u) - 1; b >= 0; b--) {
-      const u32 t = (u32)b * 64u + lane;
-      u64 v = (t < n && (t_lt[t] >> 16) == MSIM_T_OK) ? (((u64)t_cmp[t] << 32) | t_first[t]) : ~0ull;
-      for (int o = 1; o < 64; o <<= 1) {
-        const u32 ylo = (u32)__shfl_down((int)(u32)v, o), yhi = (u32)__shfl_down((int)(u32)(v >> 32), o);
-        const u64 y = ((u64)yhi << 32) | ylo;
-        if (lane + (u32)o < 64u) v = min(v, y);
-      }
-      v = min(v, carry);
-      if (t < n) { sm[t] = (u32)(v >> 32); smf[t] = (u32)v; }
-      carry = ((u64)t_rl((u32)(v >> 32), 0) << 32) | t_rl((u32)v, 0);
-    }
-    if (lane == 0) { sm[n] = NONE; smf[n] = n; }
-  }
+  // realtime order in closed form (txn_realtime.inc): wavefront 0, beside the other wavefronts' share of pass D
+  if (wave == 0)
+#include "txn_realtime.inc"
   LEAVE_IF_DECIDED();
   TL_MARK(4)
 
@@ -719,7 +608,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
 #undef ADD
     if (bad) VERDICT(2);
     if (pass == 0) {
-      my_edges = t_sum(my_edges); my_dep = t_sum(my_dep);
+      my_edges = wv_sum(my_edges); my_dep = wv_sum(my_dep);
       if (lane == 0) { atomicAdd(&hdr[7], my_edges); atomicAdd(&hdr[8], my_dep); }
     }
     LEAVE_IF_DECIDED();
@@ -734,14 +623,14 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
         for (u32 base = 0; base <= n; base += 64) {
           const u32 t = base + lane;
           const u32 d = t < n ? h16_get(l_off, t) : 0u;
-          const u32 ex = t_excl_scan(d, lane);
-          const u32 tot = t_sum(d);
-          t_wave_fence();
+          const u32 ex = wv_excl_scan(d, lane);
+          const u32 tot = wv_sum(d);
+          wv_fence();
           // two lanes share a word: the even one writes both halves
           const u32 mine = carry + ex, next = (u32)__shfl_down((int)mine, 1);
           if (t <= n && !(t & 1u)) l_off[t >> 1] = mine | ((lane < 63u && t + 1u <= n ? next : 0u) << 16);
           carry += tot;
-          t_wave_fence();
+          wv_fence();
         }
       }
       __syncthreads();
@@ -818,7 +707,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
     if (z) l_queue[tail + (u32)__popcll(zm & lt)] = (unsigned short)t;
     tail += (u32)__popcll(zm);
   }
-  t_wave_fence();
+  wv_fence();
   // A step takes up to 64 ready transactions; the graph is deep and narrow (the realtime order: a ready set is about as wide as the
   // clients' concurrency), so the wavefront's lanes are split among the ready ones — G lanes each, a power of two — and a transaction's
   // successors are taken G at a time: a step is one or two turns of the loop below instead of one per successor (78 % of a history's
@@ -841,7 +730,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
       tail += (u32)__popcll(pm);
     }
     head += cnt;
-    t_wave_fence();
+    wv_fence();
   }
   if (lane == 0) {
     if (tail == n) {   // (else a cycle: the host finds and classifies it — res.valid is still NEEDS_HOST)
@@ -889,8 +778,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
 // run), more edges than 32 nmax — twice txn_check_kernel's, every other capacity is that kernel's.  A strongly connected component may
 // be as large as the history (MSIM_DEV_FLAGS 0x20000: a matrix of 16 and the search behind it; 0x2000: a matrix of 16 and no search).
 #include "cycle_classify.inc"
-
-__device__ __forceinline__ u32 t_or(u32 v) { for (int o = 32; o; o >>= 1) v |= (u32)__shfl_xor((int)v, o); return v; }
 
 __global__ void __launch_bounds__(64) txn_classify_kernel(const TParams p) {
   constexpr bool EXPLAIN = false;

@@ -5,11 +5,7 @@
 // own: as a function it compiled txn_classify_kernel to other code than it had (61 for 63 vector registers, 65 more instructions).
   const u32 lane = threadIdx.x, hist = p.list[p.first + blockIdx.x];
   const u64 lt = (1ull << lane) - 1ull;
-  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (p.row_off ? p.row_off[hist] : (u64)hist * p.max_rows);
-  const u32 *const pay = p.payload + (p.pay_off ? p.pay_off[hist] : (u64)hist * p.max_pay);
-  const u32 n_rows = p.meta ? p.meta[hist].n_rows : (u32)(p.row_off[hist + 1] - p.row_off[hist]);
-  const u32 n_words = p.meta ? p.meta[hist].n_payload_words : (u32)(p.pay_off[hist + 1] - p.pay_off[hist]);
-  const u32 flags = p.meta ? p.meta[hist].flags : 0u;
+  HIST_VIEW(p, hist);
   const u32 NM = p.nmax;
   u32 *const ws = p.ws + (u64)blockIdx.x * p.ws_words;   // (ws_words is even and the workspace 256-byte aligned: the 64-bit tables come first)
   u64 *const long64 = reinterpret_cast<u64 *>(ws);            // [KMAX] (len + 1) << 40 | inverted transaction << 16 | inverted micro-op
@@ -26,18 +22,14 @@
   u32 *const adj = writer + WMAX, *const radj = adj + p.emax;   // [emax] each
   [[maybe_unused]] u32 *const t_inv = radj + p.emax;          // [NM] EXPLAIN only
 
-  msim_check_result res;
-  res.valid = NEEDS_HOST; res.attempt_count = 0; res.stable_count = 0; res.lost_count = 0; res.never_read_count = 0; res.stale_count = 0;
-  res.duplicated_count = 0; res.error_count = 0;
-  for (int i = 0; i < 5; i++) res.stable_latency_ms[i] = 0;
-  res.op_count = 0; res.ok_count = 0; res.fail_count = 0; res.info_count = 0;
+  BLANK_RESULT(res, NEEDS_HOST);
 #define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
   if (n_words >= (1u << 24) || NM > 0xFFFFFFu) TO_HOST();
 
-  // ---- A: transactions (txn_check_kernel's pairing) ---------------------------------------------------------------------------------
+  // ---- A: transactions ---------------------------------------------------------------------------------------------------------
   u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0;
   {
-    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // lane = one open call (o_len: words of its request)
+    bool o_used = false; u32 o_proc = 0, o_txn = 0, o_len = 0; bool bad = false;   // txn_pairing.inc's open calls
     for (u32 base = 0; base < n_rows; base += 64) {
       const u32 idx = base + lane;
       uint4 row = make_uint4(0, 0, 0, 0);
@@ -50,31 +42,7 @@
       const u32 my_t = n + (u32)__popcll(im & lt);
       if (n + (u32)__popcll(im) > NM) { bad = true; break; }
       if (inv) { t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); t_first[my_t] = 0; if constexpr (EXPLAIN) t_inv[my_t] = idx; }   // never completed = indeterminate
-      u64 m = __ballot(is);
-      while (m) {
-        const u32 j = (u32)__builtin_ctzll(m); m &= m - 1;
-        const u32 z = t_rl(row.z, j);
-        const u32 jt = z & 3u, jp = z >> 12;
-        const u64 hit = __ballot(o_used && o_proc == jp);
-        if (jt == MSIM_T_INVOKE) {
-          u32 s;
-          if (hit) s = (u32)__builtin_ctzll(hit);
-          else { const u64 used = __ballot(o_used); if (used == ~0ull) { bad = true; break; } s = (u32)__builtin_ctzll(~used); }
-          const u32 tj = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-          const u32 jl = t_rl(row.y, j) >> 16;
-          if (lane == s) { o_used = true; o_proc = jp; o_txn = tj; o_len = jl; }
-        } else if (hit) {
-          const u32 s = (u32)__builtin_ctzll(hit);
-          const u32 id = t_rl(o_txn, s), ilen = t_rl(o_len, s);
-          if (lane == s) o_used = false;
-          if (lane == j) {
-            t_cmp[id] = idx; t_first[id] = n + (u32)__popcll(im & ((1ull << j) - 1ull));
-            if (jt == MSIM_T_OK) { t_off[id] = woff; t_lt[id] = len | (MSIM_T_OK << 16); }   // the completed form replaces the requested one
-            else t_lt[id] = ilen | (jt << 16);
-          }
-          c_ok += jt == MSIM_T_OK; c_fail += jt == MSIM_T_FAIL; c_info += jt == MSIM_T_INFO;
-        }
-      }
+#include "txn_pairing.inc"
       if (bad) break;
       n += (u32)__popcll(im);
     }
@@ -90,7 +58,7 @@
     const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
     for (u32 i = 0; i < wn;) { const Mop m = next_mop(w, wn, i); bad |= m.bad; max_key = max(max_key, m.key); if (m.f) max_val = max(max_val, m.val); }
   }
-  max_key = t_max(max_key); max_val = t_max(max_val);
+  max_key = wv_max(max_key); max_val = wv_max(max_val);
   const u32 stride = max_val + 1u;
   if (__ballot(bad) || max_key >= KMAX || (u64)(max_key + 1u) * stride > WMAX) TO_HOST();
   for (u32 k = lane; k <= max_key; k += 64) { longest[k] = 0; long64[k] = 0; }
@@ -159,24 +127,7 @@
     longest[key] = ((m.len + 1u) << 24) | (u32)(m.list - pay);
   }
 
-  // realtime order in closed form: sm[j] = earliest :ok completion among transactions j .. n-1 (smf[j]: how many transactions were
-  // invoked before that completion)
-  {
-    u64 carry = ~0ull;
-    for (int b = (int)((n + 63u) / 64u) - 1; b >= 0; b--) {
-      const u32 t = (u32)b * 64u + lane;
-      u64 v = (t < n && TYPE(t) == MSIM_T_OK) ? (((u64)t_cmp[t] << 32) | t_first[t]) : ~0ull;
-      for (int o = 1; o < 64; o <<= 1) {
-        const u32 ylo = (u32)__shfl_down((int)(u32)v, o), yhi = (u32)__shfl_down((int)(u32)(v >> 32), o);
-        const u64 y = ((u64)yhi << 32) | ylo;
-        if (lane + (u32)o < 64u) v = min(v, y);
-      }
-      v = min(v, carry);
-      if (t < n) { sm[t] = (u32)(v >> 32); smf[t] = (u32)v; }
-      carry = ((u64)t_rl((u32)(v >> 32), 0) << 32) | t_rl((u32)v, 0);
-    }
-    if (lane == 0) { sm[n] = NONE; smf[n] = n; }
-  }
+#include "txn_realtime.inc"
   __syncthreads();
 
   // ---- E: edges: pass 0 counts degrees, pass 1 fills the CSR and its reverse ------------------------------------------------------------
@@ -221,7 +172,7 @@
 #undef ADD
     __syncthreads();
     if (pass == 0) {
-      n_edges = t_sum(my_edges);
+      n_edges = wv_sum(my_edges);
       if (n_edges > p.emax) TO_HOST();
       for (int which = 0; which < 2; which++) {   // out-degrees / in-degrees -> offsets (exclusive prefix sums, 64 at a time)
         u32 *const o = which ? roff : off;
@@ -229,15 +180,15 @@
         for (u32 base = 0; base <= n; base += 64) {
           const u32 t = base + lane;
           const u32 d = t < n ? o[t] : 0u;
-          const u32 ex = t_excl_scan(d, lane);
+          const u32 ex = wv_excl_scan(d, lane);
           if (t <= n) o[t] = carry + ex;
-          carry += t_sum(d);
+          carry += wv_sum(d);
         }
       }
       __syncthreads();
     }
   }
-  anomalies = t_or(anomalies);
+  anomalies = wv_or(anomalies);
   const CycleParams cp = {p.out, p.cm, p.proscribed, p.ccap, p.big};
   if constexpr (EXPLAIN) {
     const CycleWitness cw = {p.cycles, p.steps, p.max_steps, t_inv, t_cmp};

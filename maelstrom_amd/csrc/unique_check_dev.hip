@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "check_run.h"
+#include "check_dev.h"
 
 namespace {
 
@@ -21,10 +22,6 @@ struct UParams {
   uint2 *ws;             // table_slots {id, count} per history of the launch
   u32 max_rows, table_slots /* power of two >= 2 x the ids of a history */, first;
 };
-
-__device__ __forceinline__ u32 u_sum(u32 v) { for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o); return v; }
-__device__ __forceinline__ u32 u_min(u32 v) { for (int o = 32; o; o >>= 1) v = min(v, (u32)__shfl_xor((int)v, o)); return v; }
-__device__ __forceinline__ u32 u_max(u32 v) { for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor((int)v, o)); return v; }
 
 __global__ void __launch_bounds__(64) unique_check_kernel(const UParams p) {
   const u32 lane = threadIdx.x, hist = p.first + blockIdx.x;
@@ -60,10 +57,10 @@ __global__ void __launch_bounds__(64) unique_check_kernel(const UParams p) {
   __syncthreads();
   u32 dups = 0;
   for (u32 i = lane; i < p.table_slots; i += 64) dups += tab[i].y >= 2u ? 1u : 0u;
-  dups = u_sum(dups); n_empty_id = u_sum(n_empty_id); n_ids = u_sum(n_ids);
+  dups = wv_sum(dups); n_empty_id = wv_sum(n_empty_id); n_ids = wv_sum(n_ids);
   if (n_empty_id >= 2) dups++;
-  c_inv = u_sum(c_inv); c_ok = u_sum(c_ok); c_fail = u_sum(c_fail); c_info = u_sum(c_info); c_att = u_sum(c_att);
-  lo = u_min(lo); hi = u_max(hi);
+  c_inv = wv_sum(c_inv); c_ok = wv_sum(c_ok); c_fail = wv_sum(c_fail); c_info = wv_sum(c_info); c_att = wv_sum(c_att);
+  lo = wv_min(lo); hi = wv_max(hi);
   if (lane == 0) {
     msim_check_result o;
     o.valid = flags ? 0u : (dups == 0 ? 1u : 0u);
