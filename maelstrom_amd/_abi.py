@@ -39,18 +39,6 @@ ANOMALIES = {1: "G0", 2: "G1a", 4: "G1b", 8: "G1c", 16: "G-single", 32: "G2", 64
              256: "incompatible-order", 512: "realtime", 1024: "dirty-update", 2048: "cyclic-versions"}
 MASK_WORDS = 4
 
-EXPORTS = [
-    "msim_abi_version", "msim_device_count", "msim_config_defaults", "msim_config_finalize", "msim_create",
-    "msim_run", "msim_run_async", "msim_check", "msim_check_host_rechecks", "msim_set_dev_flags", "msim_check_lin_kv_batch", "msim_check_txn_batch", "msim_check_unique_batch", "msim_check_pn_batch", "msim_check_set_full_batch", "msim_check_rw_batch", "msim_classify_rw_batch", "msim_classify_txn_batch", "msim_set_check_classify", "msim_check_kafka_rows", "msim_check_kafka_batch", "msim_classify_kafka_batch", "msim_check_lin_kv_rows", "msim_check_txn_rows", "msim_check_rw_rows", "msim_proscribed_anomalies", "msim_violated_anomalies", "msim_check_pn_rows", "msim_check_unique_rows", "msim_history_edn_rows", "msim_fetch", "msim_fetch_begin", "msim_history", "msim_net_stats_get", "msim_journal", "msim_meta",
-    "msim_check_results", "msim_device_buffers_get", "msim_last_kernel_ms", "msim_get_config",
-    "msim_selftest_wave", "msim_last_error", "msim_destroy",
-    "msim_comm_unique_id", "msim_comm_init", "msim_gather", "msim_journal_fressian_rows",
-    "msim_check_availability", "msim_check_availability_rows",
-    "msim_check_perf", "msim_check_perf_rows", "msim_check_perf_batch",
-    "msim_explain_lin_kv_rows", "msim_explain_lin_kv_batch", "msim_explain_lin_kv",
-    "msim_explain_txn_rows", "msim_explain_rw_rows", "msim_explain_txn_batch", "msim_explain_rw_batch", "msim_explain_txn",
-    "msim_explain_set_full_rows", "msim_explain_set_full_batch", "msim_explain_set_full",
-]
 SET_STABLE, SET_LOST, SET_NEVER_READ = range(3)   # MSIM_SET_*
 SET_OUTCOMES = {SET_STABLE: "stable", SET_LOST: "lost", SET_NEVER_READ: "never-read"}
 EDGE_KINDS = {1: "ww", 2: "wr", 4: "rw", 8: "realtime"}   # MSIM_EDGE_*
@@ -135,17 +123,117 @@ class Gathered(C.Structure):
                 ("rows_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("meta_bytes", C.c_uint64), ("stats_bytes", C.c_uint64),
                 ("bytes_received", C.c_uint64), ("n_instances", C.c_uint32), ("world", C.c_uint32), ("rank", C.c_uint32), ("ms", C.c_float)]
 
+class CycleResult(C.Structure):
+    _fields_ = [("anomalies", C.c_uint32), ("length", C.c_uint32), ("n_steps", C.c_uint32), ("reserved", C.c_uint32)]
 
-assert C.sizeof(Config) == 120, C.sizeof(Config)
-assert C.sizeof(LatencyDist) == 32 and C.sizeof(FStats) == 128 and C.sizeof(PerfResult) == 544
-assert C.sizeof(LinKeyResult) == 32
-assert C.sizeof(Op) == 16 and C.sizeof(NetStats) == 48 and C.sizeof(InstMeta) == 32 and C.sizeof(CheckResult) == 68 and C.sizeof(Event) == 16
+
+class CycleStep(C.Structure):
+    _fields_ = [("txn", C.c_uint32), ("inv_row", C.c_uint32), ("cmp_row", C.c_uint32), ("kinds", C.c_uint32)]
+
+
+class SetElement(C.Structure):
+    _fields_ = [("element", C.c_uint32), ("outcome", C.c_uint32), ("latency_ms", C.c_uint32), ("known_row", C.c_uint32),
+                ("last_present_row", C.c_uint32), ("last_absent_row", C.c_uint32)]
+
+
+class SetExplain(C.Structure):
+    _fields_ = [("n_lost", C.c_uint32), ("n_never_read", C.c_uint32), ("n_stale", C.c_uint32), ("truncated", C.c_uint32),
+                ("n_worst_stale", C.c_uint32), ("lost_latency_ms", C.c_uint32 * 5), ("worst_stale", SetElement * 8)]
+
+
+# The one table of records: the header's struct name -> its Structure, field names and order as in include/maelsim.h.  engine.py derives
+# the numpy dtypes from these (np.dtype(Structure)); tests/test_abi_tables.py compiles a probe against the header and compares every
+# size and offset with both.
+RECORDS = {
+    "msim_config": Config, "msim_op": Op, "msim_net_stats": NetStats, "msim_event": Event, "msim_inst_meta": InstMeta,
+    "msim_check_result": CheckResult, "msim_lin_key_result": LinKeyResult, "msim_cycle_result": CycleResult, "msim_cycle_step": CycleStep,
+    "msim_set_element": SetElement, "msim_set_explain": SetExplain, "msim_availability": Availability, "msim_latency_dist": LatencyDist,
+    "msim_f_stats": FStats, "msim_perf_result": PerfResult, "msim_device_buffers": DeviceBuffers, "msim_gathered": Gathered,
+}
+
+# The one table of prototypes: entry -> (restype, argtypes), every entry include/maelsim.h declares, in its order.  A pointer the callers
+# fill from a numpy array is a void pointer, so that an array's address (`.ctypes.data`, a plain int) is what every call site passes;
+# tests/test_abi_tables.py holds arity, parameter classes and return classes to the header's declarations.
+_P, _i, _u32, _u64, _sz, _f64, _f32, _vp, _s = C.POINTER, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_double, C.c_float, C.c_void_p, C.c_char_p
+_res = _P(CheckResult)
+_offsets_args = (_i, _vp, _vp, _vp, _vp, _u32)   # device, rows, row_offsets, payload, payload_offsets, n_histories
+_classify = (_i, _offsets_args + (_u32, _vp, _vp))   # ... consistency_model / concurrency, out, n_host
+_slab = (_i, (_i, _vp, _vp, _u32, _u32, _vp))   # device, rows, n_rows, max_rows, n_histories, out
+_explain_rows = (_i, (_vp, _u32, _vp, _u32, _u32, _res, _vp, _vp, _u32))
+_explain_batch = (_i, _offsets_args + (_u32, _vp, _vp, _vp, _vp, _u32))
+_set_full_args = (_i, _u32, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp)
+PROTOTYPES = {
+    "msim_abi_version": (_u32, ()),
+    "msim_device_count": (_i, ()),
+    "msim_config_defaults": (_i, (_P(Config), _u32, _u32)),
+    "msim_config_finalize": (_i, (_P(Config), _s, _sz)),
+    "msim_create": (_i, (_P(Config), _i, _P(_vp), _s, _sz)),
+    "msim_run": (_i, (_vp, _u64, _u32)),
+    "msim_run_async": (_i, (_vp, _u64, _u32, _vp)),
+    "msim_check": (_i, (_vp,)),
+    "msim_set_check_classify": (_i, (_vp, _u32)),
+    "msim_set_dev_flags": (_i, (_vp, _u32)),
+    "msim_check_host_rechecks": (_u32, (_vp,)),
+    "msim_check_txn_batch": (_i, _offsets_args + (_vp,)),
+    "msim_classify_txn_batch": _classify,
+    "msim_check_rw_batch": _classify,
+    "msim_classify_rw_batch": _classify,
+    "msim_check_pn_batch": _slab,
+    "msim_check_set_full_batch": (_i, _set_full_args),
+    "msim_check_kafka_rows": (_i, (_vp, _u32, _vp, _u32, _res)),
+    "msim_check_kafka_batch": _classify,
+    "msim_classify_kafka_batch": _classify,
+    "msim_check_unique_batch": _slab,
+    "msim_check_lin_kv_batch": (_i, (_i, _vp, _vp, _u32, _vp)),
+    "msim_check_lin_kv_rows": (_i, (_vp, _u32, _res)),
+    "msim_explain_lin_kv_rows": (_i, (_vp, _u32, _res, _vp, _u32, _P(_u32))),
+    "msim_explain_lin_kv_batch": (_i, (_i, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _P(_u32))),
+    "msim_explain_lin_kv": (_i, (_vp, _vp, _u32, _vp, _u32)),
+    "msim_check_txn_rows": (_i, (_vp, _u32, _vp, _u32, _vp)),
+    "msim_proscribed_anomalies": (_u32, (_u32,)),
+    "msim_violated_anomalies": (_u32, (_u32, _u32)),
+    "msim_check_rw_rows": (_i, (_vp, _u32, _vp, _u32, _u32, _vp)),
+    "msim_explain_txn_rows": _explain_rows,
+    "msim_explain_rw_rows": _explain_rows,
+    "msim_explain_txn_batch": _explain_batch,
+    "msim_explain_rw_batch": _explain_batch,
+    "msim_explain_txn": (_i, (_vp, _vp, _vp, _u32, _u32)),
+    "msim_explain_set_full_rows": (_i, (_u32, _vp, _u32, _vp, _u32, _res, _vp, _vp, _u32)),
+    "msim_explain_set_full_batch": (_i, _set_full_args + (_vp, _vp, _u32)),
+    "msim_explain_set_full": (_i, (_vp, _vp, _vp, _u32, _u32)),
+    "msim_check_unique_rows": (_i, (_vp, _u32, _vp)),
+    "msim_check_pn_rows": (_i, (_vp, _u32, _vp, _vp, _u32, _vp)),
+    "msim_history_edn_rows": (_i, (_P(Config), _vp, _u32, _vp, _u32, _s, _sz, _P(_sz))),
+    "msim_check_availability": (_i, (_vp, _u32, _f64, _P(Availability), _u32)),
+    "msim_check_availability_rows": (_i, (_vp, _u32, _u32, _f64, _P(Availability))),
+    "msim_check_perf": (_i, (_vp, _u32, _u32, _vp, _u32, _vp)),
+    "msim_check_perf_rows": (_i, (_vp, _u32, _u32, _u32, _u32, _vp, _vp)),
+    "msim_check_perf_batch": (_i, (_i, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp)),
+    "msim_journal_fressian_rows": (_i, (_P(Config), _vp, _u32, _vp, _u32, _vp, _sz, _P(_sz))),
+    "msim_fetch": (_i, (_vp,)),
+    "msim_fetch_begin": (_i, (_vp,)),
+    "msim_history": (_i, (_vp, _u32, _P(_P(Op)), _P(_u32), _P(_P(_u32)), _P(_u32))),
+    "msim_net_stats_get": (_i, (_vp, _u32, _P(NetStats))),
+    "msim_journal": (_i, (_vp, _u32, _P(_P(Event)), _P(_u32))),
+    "msim_meta": (_i, (_vp, _u32, _P(InstMeta))),
+    "msim_check_results": (_i, (_vp, _P(_P(CheckResult)), _P(_u32))),
+    "msim_device_buffers_get": (_i, (_vp, _P(DeviceBuffers))),
+    "msim_comm_unique_id": (_i, (_s,)),
+    "msim_comm_init": (_i, (_vp, _s, _i, _i)),
+    "msim_gather": (_i, (_vp, _i, _P(Gathered))),
+    "msim_last_kernel_ms": (_i, (_vp, _P(_f32), _P(_f32))),
+    "msim_get_config": (_i, (_vp, _P(Config))),
+    "msim_selftest_wave": (_i, (_i,)),
+    "msim_last_error": (_s, (_vp,)),
+    "msim_destroy": (None, (_vp,)),
+}
+EXPORTS = list(PROTOTYPES)
 
 _lib = None
 
 
 def load():
-    """Loads libmaelsim.so (built in-tree by maelstrom_amd.build / __graft_entry__.build)."""
+    """Loads libmaelsim.so (built in-tree by maelstrom_amd.build / __graft_entry__.build) and gives every entry its prototype."""
     global _lib
     if _lib is not None:
         return _lib
@@ -153,99 +241,9 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -m maelstrom_amd.build` (hipcc, gfx950). "
                            "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    P = C.POINTER
-    lib.msim_abi_version.restype = C.c_uint32
-    lib.msim_device_count.restype = C.c_int
-    lib.msim_config_defaults.argtypes = [P(Config), C.c_uint32, C.c_uint32]
-    lib.msim_config_finalize.argtypes = [P(Config), C.c_char_p, C.c_size_t]
-    lib.msim_create.argtypes = [P(Config), C.c_int, P(C.c_void_p), C.c_char_p, C.c_size_t]
-    lib.msim_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
-    lib.msim_run_async.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
-    lib.msim_check.argtypes = [C.c_void_p]
-    lib.msim_fetch.argtypes = [C.c_void_p]
-    lib.msim_fetch_begin.argtypes = [C.c_void_p]
-    lib.msim_fetch_begin.restype = C.c_int
-    lib.msim_check_lin_kv_rows.argtypes = [C.c_void_p, C.c_uint32, P(CheckResult)]
-    lib.msim_check_lin_kv_rows.restype = C.c_int
-    lib.msim_set_dev_flags.argtypes = [C.c_void_p, C.c_uint32]
-    lib.msim_set_dev_flags.restype = C.c_int
-    lib.msim_check_host_rechecks.argtypes = [C.c_void_p]
-    lib.msim_check_host_rechecks.restype = C.c_uint32
-    lib.msim_check_lin_kv_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.msim_check_lin_kv_batch.restype = C.c_int
-    lib.msim_explain_lin_kv_rows.argtypes = [C.c_void_p, C.c_uint32, P(CheckResult), C.c_void_p, C.c_uint32, P(C.c_uint32)]
-    lib.msim_explain_lin_kv_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_uint32)]
-    lib.msim_explain_lin_kv.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
-    lib.msim_explain_lin_kv_rows.restype = lib.msim_explain_lin_kv_batch.restype = lib.msim_explain_lin_kv.restype = C.c_int
-    lib.msim_check_txn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.msim_check_txn_batch.restype = C.c_int
-    lib.msim_check_unique_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    lib.msim_check_unique_batch.restype = C.c_int
-    lib.msim_check_pn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    lib.msim_check_pn_batch.restype = C.c_int
-    lib.msim_check_set_full_batch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    lib.msim_check_set_full_batch.restype = C.c_int
-    lib.msim_check_rw_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_check_rw_batch.restype = C.c_int
-    for fn in (lib.msim_explain_txn_rows, lib.msim_explain_rw_rows):
-        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, P(CheckResult), C.c_void_p, C.c_void_p, C.c_uint32]
-        fn.restype = C.c_int
-    for fn in (lib.msim_explain_txn_batch, lib.msim_explain_rw_batch):
-        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        fn.restype = C.c_int
-    lib.msim_explain_txn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-    lib.msim_explain_txn.restype = C.c_int
-    if hasattr(lib, "msim_explain_set_full"):   # (MSIM_LIB may name an older build: tools/set_explain_ab.py times the parent's check_kernel; calling a missing entry still raises)
-        lib.msim_explain_set_full_rows.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(CheckResult), C.c_void_p, C.c_void_p, C.c_uint32]
-        lib.msim_explain_set_full_batch.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        lib.msim_explain_set_full.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        lib.msim_explain_set_full_rows.restype = lib.msim_explain_set_full_batch.restype = lib.msim_explain_set_full.restype = C.c_int
-    lib.msim_classify_rw_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_classify_rw_batch.restype = C.c_int
-    lib.msim_classify_txn_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_classify_txn_batch.restype = C.c_int
-    lib.msim_set_check_classify.argtypes = [C.c_void_p, C.c_uint32]
-    lib.msim_set_check_classify.restype = C.c_int
-    lib.msim_check_kafka_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_check_kafka_batch.restype = C.c_int
-    lib.msim_classify_kafka_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_classify_kafka_batch.restype = C.c_int
-    lib.msim_check_kafka_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, P(CheckResult)]
-    lib.msim_check_kafka_rows.restype = C.c_int
-    lib.msim_history_edn_rows.argtypes = [P(Config), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, P(C.c_size_t)]
-    lib.msim_history_edn_rows.restype = C.c_int
-    lib.msim_history.argtypes = [C.c_void_p, C.c_uint32, P(P(Op)), P(C.c_uint32), P(P(C.c_uint32)), P(C.c_uint32)]
-    lib.msim_net_stats_get.argtypes = [C.c_void_p, C.c_uint32, P(NetStats)]
-    lib.msim_meta.argtypes = [C.c_void_p, C.c_uint32, P(InstMeta)]
-    lib.msim_journal.argtypes = [C.c_void_p, C.c_uint32, P(P(Event)), P(C.c_uint32)]
-    lib.msim_check_results.argtypes = [C.c_void_p, P(P(CheckResult)), P(C.c_uint32)]
-    lib.msim_device_buffers_get.argtypes = [C.c_void_p, P(DeviceBuffers)]
-    lib.msim_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float)]
-    lib.msim_get_config.argtypes = [C.c_void_p, P(Config)]
-    lib.msim_last_error.argtypes = [C.c_void_p]
-    lib.msim_last_error.restype = C.c_char_p
-    lib.msim_selftest_wave.argtypes = [C.c_int]
-    lib.msim_selftest_wave.restype = C.c_int
-    lib.msim_destroy.argtypes = [C.c_void_p]
-    lib.msim_destroy.restype = None
-    lib.msim_journal_fressian_rows.argtypes = [P(Config), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, P(C.c_size_t)]
-    lib.msim_journal_fressian_rows.restype = C.c_int
-    lib.msim_check_availability.argtypes = [C.c_void_p, C.c_uint32, C.c_double, P(Availability), C.c_uint32]
-    lib.msim_check_availability_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, P(Availability)]
-    lib.msim_check_availability.restype = lib.msim_check_availability_rows.restype = C.c_int
-    lib.msim_check_perf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.msim_check_perf_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_check_perf_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.msim_check_perf.restype = lib.msim_check_perf_rows.restype = lib.msim_check_perf_batch.restype = C.c_int
-    lib.msim_comm_unique_id.argtypes = [C.c_char_p]
-    lib.msim_comm_init.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
-    lib.msim_gather.argtypes = [C.c_void_p, C.c_int, P(Gathered)]
-    for name in ("msim_comm_unique_id", "msim_comm_init", "msim_gather"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("msim_config_defaults", "msim_config_finalize", "msim_create", "msim_run", "msim_run_async",
-                 "msim_check", "msim_fetch", "msim_fetch_begin", "msim_history", "msim_net_stats_get", "msim_journal", "msim_meta", "msim_check_results",
-                 "msim_device_buffers_get", "msim_last_kernel_ms", "msim_get_config"):
-        getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)   # MSIM_LIB may name an older build (the A/B tools under tools/ time the parent's): an entry it lacks is skipped, and calling it still raises
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib

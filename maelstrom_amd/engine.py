@@ -12,26 +12,12 @@ import numpy as np
 
 from . import _abi as A
 
-OP_DT = np.dtype([("time_len", "<u8"), ("packed", "<u4"), ("value", "<u4")])
-STATS_DT = np.dtype([(n, "<u8") for n in ("all_send", "all_recv", "clients_send", "clients_recv", "servers_send", "servers_recv")])
+# The records as numpy dtypes, derived from _abi's Structures (A.RECORDS; tests/test_abi_tables.py holds both to the header).
+(OP_DT, STATS_DT, EVENT_DT, CHECK_DT, LIN_KEY_DT, CYCLE_DT, CYCLE_STEP_DT, SET_ELEMENT_DT, SET_EXPLAIN_DT, LATENCY_DT, F_STATS_DT, PERF_DT) = (
+    np.dtype(s) for s in (A.Op, A.NetStats, A.Event, A.CheckResult, A.LinKeyResult, A.CycleResult, A.CycleStep, A.SetElement, A.SetExplain,
+                          A.LatencyDist, A.FStats, A.PerfResult))
+# msim_inst_meta stays written out: its callers know the header's reserved[3] as three words r0, r1, r2 (the oracle's dtype has the same).
 META_DT = np.dtype([(n, "<u4") for n in ("n_rows", "n_payload_words", "flags", "n_rounds", "n_events", "r0", "r1", "r2")])
-EVENT_DT = np.dtype([(n, "<u4") for n in ("time_us", "msg", "a", "route")])
-CHECK_DT = np.dtype([("valid", "<u4"), ("attempt_count", "<u4"), ("stable_count", "<u4"), ("lost_count", "<u4"),
-                     ("never_read_count", "<u4"), ("stale_count", "<u4"), ("duplicated_count", "<u4"),
-                     ("error_count", "<u4"), ("stable_latency_ms", "<u4", (5,)), ("op_count", "<u4"),
-                     ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4")])
-LIN_KEY_DT = np.dtype([("key", "<u4"), ("valid", "<u4"), ("op_row", "<u4"), ("previous_ok_row", "<u4"), ("n_pending", "<u4"), ("n_values", "<u4"),
-                       ("values", "u1", (8,))])   # msim_lin_key_result
-CYCLE_DT = np.dtype([("anomalies", "<u4"), ("length", "<u4"), ("n_steps", "<u4"), ("reserved", "<u4")])        # msim_cycle_result
-CYCLE_STEP_DT = np.dtype([("txn", "<u4"), ("inv_row", "<u4"), ("cmp_row", "<u4"), ("kinds", "<u4")])          # msim_cycle_step
-SET_ELEMENT_DT = np.dtype([(n, "<u4") for n in ("element", "outcome", "latency_ms", "known_row", "last_present_row", "last_absent_row")])   # msim_set_element
-SET_EXPLAIN_DT = np.dtype([("n_lost", "<u4"), ("n_never_read", "<u4"), ("n_stale", "<u4"), ("truncated", "<u4"), ("n_worst_stale", "<u4"),
-                           ("lost_latency_ms", "<u4", (5,)), ("worst_stale", SET_ELEMENT_DT, (8,))])   # msim_set_explain
-LATENCY_DT = np.dtype([("count", "<u4"), ("q_us", "<u4", (5,)), ("sum_us", "<u8")])
-F_STATS_DT = np.dtype([("f", "<u4"), ("valid", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
-                       ("unpaired", "<u4"), ("reserved", "<u4"), ("latency", LATENCY_DT, (3,))])
-PERF_DT = np.dtype([("valid", "<u4"), ("n_f", "<u4"), ("count", "<u4"), ("ok_count", "<u4"), ("fail_count", "<u4"), ("info_count", "<u4"),
-                    ("open_count", "<u4"), ("flags", "<u4"), ("by_f", F_STATS_DT, (A.PERF_MAX_F,))])
 PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
 WORKLOADS = {"echo": A.WL_ECHO, "broadcast": A.WL_BROADCAST, "g-set": A.WL_G_SET, "lin-kv": A.WL_LIN_KV,
@@ -66,6 +52,49 @@ class EngineError(RuntimeError):
     pass
 
 
+def _call(entry, *args):
+    """One entry of the library without a context: a code other than MSIM_OK raises "<entry>: <code>" (Engine._chk is its twin with a
+    context, whose message carries msim_last_error).  Arrays go in as their addresses (`.ctypes.data`): every entry has its prototype."""
+    rc = getattr(A.load(), entry)(*args)
+    if rc:
+        raise EngineError(f"{entry}: {rc}")
+
+
+def _concatenated(arrays, dtype):
+    off = np.zeros(len(arrays) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(a) for a in arrays])
+    return (np.concatenate(arrays) if arrays else np.zeros(0, dtype=dtype)), off
+
+
+def _offsets_form(histories, payload=True):
+    """The "offsets" form of a batch entry's input: the histories' rows concatenated and their n + 1 uint64 row offsets; with `payload`
+    (the histories are (rows, payload words) pairs) the same for the payload, where no word at all becomes one zero word.
+    -> (rows, row_offsets[, payload, payload_offsets]).  No rows at all stay no rows: explain_lin_kv_batch alone pads them."""
+    if not payload:
+        return _concatenated([np.ascontiguousarray(h) for h in histories], OP_DT)
+    rows, ro = _concatenated([np.ascontiguousarray(h[0]) for h in histories], OP_DT)
+    pay, po = _concatenated([np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories], np.uint32)
+    return rows, ro, (pay if len(pay) else np.zeros(1, dtype=np.uint32)), po
+
+
+def _padded(arrays, dtype, width=None):
+    width = int(width) if width else max(1, max(len(a) for a in arrays))
+    slab = np.zeros((len(arrays), width), dtype=dtype)
+    for i, a in enumerate(arrays):
+        slab[i, :len(a)] = a
+    return slab, np.asarray([len(a) for a in arrays], dtype=np.uint32)
+
+
+def _slab_form(histories, payload=False, max_rows=None):
+    """The "slab" form of a batch entry's input: history i zero-padded in row i of a (histories, max_rows) array, and n_rows; with
+    `payload` (the histories are (rows, payload words) pairs) the payload slab likewise.  The widths are the longest history's, at least
+    1, so an empty list of histories raises, as max() does (not with `max_rows` given).  -> (rows, n_rows[, payload])."""
+    if not payload:
+        return _padded([np.ascontiguousarray(h) for h in histories], OP_DT, max_rows)
+    rows, nr = _padded([np.ascontiguousarray(r) for r, _ in histories], OP_DT, max_rows)
+    return rows, nr, _padded([np.ascontiguousarray(p, dtype=np.uint32) for _, p in histories], np.uint32)[0]
+
+
 def test_config(workload="broadcast", bin=None, node_count=5, concurrency=None, rate=5.0, time_limit=60.0,
                 latency=0, latency_dist="constant", topology="grid", nemesis=(), nemesis_interval=10.0,
                 p_loss=0.0, seed=0, **capacities):
@@ -73,9 +102,7 @@ def test_config(workload="broadcast", bin=None, node_count=5, concurrency=None, 
     program (NODE_PROGRAMS) instead of an executable; `p_loss` is the net's :p-loss (net.clj:100,122)."""
     lib = A.load()
     cfg = A.Config()
-    rc = lib.msim_config_defaults(C.byref(cfg), WORKLOADS[workload], int(node_count))
-    if rc:
-        raise EngineError(f"msim_config_defaults: {rc}")
+    _call("msim_config_defaults", C.byref(cfg), WORKLOADS[workload], int(node_count))
     if bin is not None:
         cfg.node_program = NODE_PROGRAMS[bin]
     if concurrency is not None:
@@ -444,12 +471,9 @@ def encode_kafka_history(ops):
 
 def check_kafka_history(rows, payload):
     """The kafka checker (msim_check_kafka_rows) on one history -> dict."""
-    lib = A.load()
     res = A.CheckResult()
     rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
-    rc = lib.msim_check_kafka_rows(rows.ctypes.data_as(C.c_void_p), len(rows), payload.ctypes.data_as(C.c_void_p), len(payload), C.byref(res))
-    if rc:
-        raise EngineError(f"msim_check_kafka_rows: {rc}")
+    _call("msim_check_kafka_rows", rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), C.byref(res))
     return {"valid?": {1: True, 0: False, 2: "unknown"}[res.valid], "anomalies": sorted(n for b, n in A.KAFKA_ANOMALIES.items() if res.error_count & b),
             "send-count": res.attempt_count, "acked-count": res.stable_count, "lost-count": res.lost_count, "unobserved-count": res.never_read_count,
             "duplicate-count": res.duplicated_count, "ok-count": res.ok_count, "fail-count": res.fail_count, "info-count": res.info_count}
@@ -502,44 +526,33 @@ def encode_txn_history(ops, rw=False):
     return rows, np.asarray(payload, dtype=np.uint32)
 
 
-def check_txn_history(rows, payload):
-    """The host list-append checker (msim_check_txn_rows) on one history -> dict with :valid? and the anomaly names."""
-    lib = A.load()
+def _check_txn_rows(entry, rows, payload, *model):
     res = A.CheckResult()
     rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
-    rc = lib.msim_check_txn_rows(rows.ctypes.data_as(C.c_void_p), len(rows), payload.ctypes.data_as(C.c_void_p), len(payload), C.byref(res))
-    if rc:
-        raise EngineError(f"msim_check_txn_rows: {rc}")
+    _call(entry, rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), *model, C.byref(res))
     return {"valid?": {1: True, 0: False, 2: "unknown"}[res.valid], "anomalies": sorted(n for b, n in A.ANOMALIES.items() if res.error_count & b),
             "txn-count": res.attempt_count, "ok-count": res.ok_count, "fail-count": res.fail_count, "info-count": res.info_count,
             "edge-count": res.lost_count, "cycle-txns": res.stale_count, "anomaly-bits": res.error_count}
+
+
+def check_txn_history(rows, payload):
+    """The host list-append checker (msim_check_txn_rows) on one history -> dict with :valid? and the anomaly names."""
+    return _check_txn_rows("msim_check_txn_rows", rows, payload)
 
 
 def check_rw_history(rows, payload, consistency_model="strict-serializable"):
     """The host rw-register checker (msim_check_rw_rows) on one history -> dict like check_txn_history."""
-    lib = A.load()
-    res = A.CheckResult()
-    rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
-    rc = lib.msim_check_rw_rows(rows.ctypes.data_as(C.c_void_p), len(rows), payload.ctypes.data_as(C.c_void_p), len(payload),
-                                CONSISTENCY_MODELS[consistency_model], C.byref(res))
-    if rc:
-        raise EngineError(f"msim_check_rw_rows: {rc}")
-    return {"valid?": {1: True, 0: False, 2: "unknown"}[res.valid], "anomalies": sorted(n for b, n in A.ANOMALIES.items() if res.error_count & b),
-            "txn-count": res.attempt_count, "ok-count": res.ok_count, "fail-count": res.fail_count, "info-count": res.info_count,
-            "edge-count": res.lost_count, "cycle-txns": res.stale_count, "anomaly-bits": res.error_count}
+    return _check_txn_rows("msim_check_rw_rows", rows, payload, CONSISTENCY_MODELS[consistency_model])
 
 
 def check_pn_history(rows):
     """The host pn-counter checker (msim_check_pn_rows) on one history -> the reference's result map (pn_counter.clj:120-123
     minus the op maps of :errors)."""
-    lib = A.load()
     res = A.CheckResult()
     rows = np.ascontiguousarray(rows)
     ranges = (C.c_int64 * 512)()
     n = C.c_uint32()
-    rc = lib.msim_check_pn_rows(rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(res), ranges, 256, C.byref(n))
-    if rc:
-        raise EngineError(f"msim_check_pn_rows: {rc}")
+    _call("msim_check_pn_rows", rows.ctypes.data, len(rows), C.byref(res), ranges, 256, C.byref(n))
     finals = [int(np.int32(np.uint32(v))) for v, p in zip(rows["value"], rows["packed"]) if (p >> 11) & 1 and (p & 3) == A.T_OK and (p >> 12) != A.PROCESS_NEMESIS]
     return {"valid?": bool(res.valid), "error-count": res.error_count, "final-reads": finals,
             "acceptable": [[ranges[2 * i], ranges[2 * i + 1]] for i in range(min(n.value, 256))]}
@@ -608,9 +621,7 @@ def check_lin_kv_history(rows):
     """The per-key linearizability check (msim_check_lin_kv_rows, host search) on one history -> dict."""
     res = A.CheckResult()
     rows = np.ascontiguousarray(rows)
-    rc = A.load().msim_check_lin_kv_rows(rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(res))
-    if rc:
-        raise EngineError(f"msim_check_lin_kv_rows: {rc}")
+    _call("msim_check_lin_kv_rows", rows.ctypes.data, len(rows), C.byref(res))
     return {"valid?": {1: True, 0: False, 2: "unknown"}[res.valid], "key-count": res.attempt_count, "invalid-keys": res.error_count}
 
 
@@ -687,9 +698,7 @@ def check_availability_rows(rows, availability=None):
     mode, a = _availability_mode(availability)
     r = A.Availability()
     rows = np.ascontiguousarray(rows)
-    rc = A.load().msim_check_availability_rows(rows.ctypes.data, len(rows), mode, a, C.byref(r))
-    if rc:
-        raise EngineError(f"msim_check_availability_rows: {rc}")
+    _call("msim_check_availability_rows", rows.ctypes.data, len(rows), mode, a, C.byref(r))
     return {"valid?": bool(r.valid), "ok-fraction": float(r.ok_fraction), "ok-count": r.ok_count, "invoke-count": r.invoke_count}
 
 
@@ -759,9 +768,7 @@ def check_perf_rows(rows, concurrency, window_s=None, n_windows=0):
     rows = np.ascontiguousarray(rows)
     out = np.zeros(1, dtype=PERF_DT)
     win = np.zeros((n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
-    rc = A.load().msim_check_perf_rows(rows.ctypes.data if len(rows) else None, len(rows), int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
-    if rc:
-        raise EngineError(f"msim_check_perf_rows: {rc}")
+    _call("msim_check_perf_rows", rows.ctypes.data if len(rows) else None, len(rows), int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
     return decode_perf(out[0], win if n_windows else None)
 
 
@@ -769,31 +776,20 @@ def check_perf_batch(histories, concurrency, window_s=None, n_windows=0, max_row
     """:stats / :perf of several histories (arrays of rows) through the device kernel behind Engine.check_perf (msim_check_perf_batch);
     `max_rows` = the slab size (default: the longest history)."""
     window_ms, n_windows = _perf_windows(window_s, n_windows)
-    hs = [np.ascontiguousarray(h) for h in histories]
-    mr = int(max_rows) if max_rows else max(1, max(len(h) for h in hs))
-    slab = np.zeros((len(hs), mr), dtype=OP_DT)
-    for i, h in enumerate(hs):
-        slab[i, :len(h)] = h
-    nr = np.asarray([len(h) for h in hs], dtype=np.uint32)
-    out = np.zeros(len(hs), dtype=PERF_DT)
-    win = np.zeros((len(hs), n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
-    rc = A.load().msim_check_perf_batch(device, slab.ctypes.data, nr.ctypes.data, mr, len(hs), int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
-    if rc:
-        raise EngineError(f"msim_check_perf_batch: {rc}")
-    return [decode_perf(out[i], win[i] if n_windows else None) for i in range(len(hs))]
+    slab, nr = _slab_form(histories, max_rows=max_rows)
+    n = len(nr)
+    out = np.zeros(n, dtype=PERF_DT)
+    win = np.zeros((n, n_windows, A.PERF_MAX_F, 3), dtype=LATENCY_DT)
+    _call("msim_check_perf_batch", device, slab.ctypes.data, nr.ctypes.data, slab.shape[1], n, int(concurrency), window_ms, n_windows, out.ctypes.data, win.ctypes.data if n_windows else None)
+    return [decode_perf(out[i], win[i] if n_windows else None) for i in range(n)]
 
 
 def check_lin_kv_batch(histories, device=0):
     """lin-kv: per-key linearizability of several histories (each an array of rows) with the device search behind Engine.check()
     (msim_check_lin_kv_batch).  Returns the CHECK_DT records, one per history."""
-    hs = [np.ascontiguousarray(h) for h in histories]
-    off = np.zeros(len(hs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(h) for h in hs])
-    rows = np.concatenate(hs) if hs else np.zeros(0, dtype=hs[0].dtype if hs else np.uint8)
-    out = np.zeros(len(hs), dtype=CHECK_DT)
-    rc = A.load().msim_check_lin_kv_batch(device, rows.ctypes.data, off.ctypes.data, len(hs), out.ctypes.data)
-    if rc:
-        raise EngineError(f"msim_check_lin_kv_batch: {rc}")
+    rows, off = _offsets_form(histories, payload=False)   # histories without a single row go in as no rows; explain_lin_kv_batch pads them
+    out = np.zeros(len(off) - 1, dtype=CHECK_DT)
+    _call("msim_check_lin_kv_batch", device, rows.ctypes.data, off.ctypes.data, len(out), out.ctypes.data)
     return out
 
 
@@ -804,9 +800,7 @@ def explain_lin_kv_history(rows, max_keys=256):
     out = np.zeros(1, dtype=CHECK_DT)
     keys = np.zeros(max_keys, dtype=LIN_KEY_DT)
     n = C.c_uint32()
-    rc = A.load().msim_explain_lin_kv_rows(rows.ctypes.data, len(rows), out.ctypes.data_as(C.POINTER(A.CheckResult)), keys.ctypes.data, max_keys, C.byref(n))
-    if rc:
-        raise EngineError(f"msim_explain_lin_kv_rows: {rc}")
+    _call("msim_explain_lin_kv_rows", rows.ctypes.data, len(rows), out.ctypes.data_as(C.POINTER(A.CheckResult)), keys.ctypes.data, max_keys, C.byref(n))
     return out[0], keys[:min(n.value, max_keys)].copy()
 
 
@@ -814,20 +808,16 @@ def explain_lin_kv_batch(histories, device=0, max_keys=256, with_n_host=False):
     """The explaining lin-kv check of several histories (arrays of rows) with the device search (msim_explain_lin_kv_batch): per history
     (CHECK_DT record — what check_lin_kv_batch gives —, LIN_KEY_DT records as explain_lin_kv_history gives them).  with_n_host: also how
     many histories the host search finished."""
-    hs = [np.ascontiguousarray(h) for h in histories]
-    off = np.zeros(len(hs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(h) for h in hs])
-    rows = np.concatenate(hs) if hs else np.zeros(0, dtype=OP_DT)
-    if len(rows) == 0:
+    rows, off = _offsets_form(histories, payload=False)
+    if len(rows) == 0:   # unlike check_lin_kv_batch, which hands no rows in as they are: one zero row
         rows = np.zeros(1, dtype=OP_DT)
-    out = np.zeros(len(hs), dtype=CHECK_DT)
-    keys = np.zeros((len(hs), max_keys), dtype=LIN_KEY_DT)
-    nk = np.zeros(len(hs), dtype=np.uint32)
+    n = len(off) - 1
+    out = np.zeros(n, dtype=CHECK_DT)
+    keys = np.zeros((n, max_keys), dtype=LIN_KEY_DT)
+    nk = np.zeros(n, dtype=np.uint32)
     n_host = C.c_uint32()
-    rc = A.load().msim_explain_lin_kv_batch(device, rows.ctypes.data, off.ctypes.data, len(hs), out.ctypes.data, keys.ctypes.data, max_keys, nk.ctypes.data, C.byref(n_host))
-    if rc:
-        raise EngineError(f"msim_explain_lin_kv_batch: {rc}")
-    res = [(out[i], keys[i, :min(int(nk[i]), max_keys)].copy()) for i in range(len(hs))]
+    _call("msim_explain_lin_kv_batch", device, rows.ctypes.data, off.ctypes.data, n, out.ctypes.data, keys.ctypes.data, max_keys, nk.ctypes.data, C.byref(n_host))
+    res = [(out[i], keys[i, :min(int(nk[i]), max_keys)].copy()) for i in range(n)]
     return (res, n_host.value) if with_n_host else res
 
 
@@ -862,16 +852,9 @@ def lin_kv_analysis(rows, key_records, payload=None, n_nodes=0):
 def check_unique_batch(histories, device=0, fn="msim_check_unique_batch"):
     """unique-ids (or, with fn="msim_check_pn_batch", pn-counter / g-counter): several histories (arrays of rows) through the device
     checker behind Engine.check()."""
-    hs = [np.ascontiguousarray(h) for h in histories]
-    mr = max(1, max(len(h) for h in hs))
-    slab = np.zeros((len(hs), mr), dtype=OP_DT)
-    for i, h in enumerate(hs):
-        slab[i, :len(h)] = h
-    nr = np.asarray([len(h) for h in hs], dtype=np.uint32)
-    out = np.zeros(len(hs), dtype=CHECK_DT)
-    rc = getattr(A.load(), fn)(device, slab.ctypes.data, nr.ctypes.data, mr, len(hs), out.ctypes.data)
-    if rc:
-        raise EngineError(f"{fn}: {rc}")
+    slab, nr = _slab_form(histories)
+    out = np.zeros(len(nr), dtype=CHECK_DT)
+    _call(fn, device, slab.ctypes.data, nr.ctypes.data, slab.shape[1], len(nr), out.ctypes.data)
     return out
 
 
@@ -880,10 +863,8 @@ def check_set_full_batch(histories, concurrency, workload=A.WL_BROADCAST, max_va
     Engine.check() (msim_check_set_full_batch)."""
     rows, nr, pay, max_values = _set_full_slabs(histories, max_values)
     out = np.zeros(len(nr), dtype=CHECK_DT)
-    rc = A.load().msim_check_set_full_batch(device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
-                                            max_values, len(nr), out.ctypes.data)
-    if rc:
-        raise EngineError(f"msim_check_set_full_batch: {rc}")
+    _call("msim_check_set_full_batch", device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
+          max_values, len(nr), out.ctypes.data)
     return out
 
 
@@ -893,18 +874,10 @@ def _n_set_records(hdr):
 
 def _set_full_slabs(histories, max_values):
     """(rows, n_rows, payload, max_values) of check_set_full_batch's call"""
-    hs = [(np.ascontiguousarray(r), np.ascontiguousarray(p, dtype=np.uint32)) for r, p in histories]
-    mr = max(1, max(len(r) for r, _ in hs))
-    mp = max(1, max(len(p) for _, p in hs))
-    rows = np.zeros((len(hs), mr), dtype=OP_DT)
-    pay = np.zeros((len(hs), mp), dtype=np.uint32)
-    for i, (r, p) in enumerate(hs):
-        rows[i, :len(r)] = r
-        pay[i, :len(p)] = p
-    nr = np.asarray([len(r) for r, _ in hs], dtype=np.uint32)
+    rows, nr, pay = _slab_form(histories, payload=True)
     if max_values is None:   # every add / broadcast invocation creates one element
         f = (rows["packed"] >> 2) & 31
-        adds = (((f == A.F_ADD) | (f == A.F_BROADCAST)) & ((rows["packed"] & 3) == 0)).sum(axis=1).max() if len(hs) else 0
+        adds = (((f == A.F_ADD) | (f == A.F_BROADCAST)) & ((rows["packed"] & 3) == 0)).sum(axis=1).max()
         max_values = max(32, (int(adds) + 31) // 32 * 32)
     return rows, nr, pay, max_values
 
@@ -917,10 +890,8 @@ def explain_set_full_history(rows, payload, workload=A.WL_BROADCAST, max_element
     out = np.zeros(1, dtype=CHECK_DT)
     hdr = np.zeros(1, dtype=SET_EXPLAIN_DT)
     slab = np.zeros(max(max_elements, 1), dtype=SET_ELEMENT_DT)
-    rc = A.load().msim_explain_set_full_rows(workload, rows.ctypes.data, len(rows), payload.ctypes.data, len(payload),
-                                             out.ctypes.data_as(C.POINTER(A.CheckResult)), hdr.ctypes.data, slab.ctypes.data, max_elements)
-    if rc:
-        raise EngineError(f"msim_explain_set_full_rows: {rc}")
+    _call("msim_explain_set_full_rows", workload, rows.ctypes.data, len(rows), payload.ctypes.data, len(payload),
+          out.ctypes.data_as(C.POINTER(A.CheckResult)), hdr.ctypes.data, slab.ctypes.data, max_elements)
     return out[0], hdr[0], slab[:_n_set_records(hdr[0])]
 
 
@@ -933,10 +904,8 @@ def explain_set_full_batch(histories, concurrency, workload=A.WL_BROADCAST, max_
     out = np.zeros(n, dtype=CHECK_DT)
     hdr = np.zeros(n, dtype=SET_EXPLAIN_DT)
     slab = np.zeros((n, max(max_elements, 1)), dtype=SET_ELEMENT_DT)
-    rc = A.load().msim_explain_set_full_batch(device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
-                                              max_values, n, out.ctypes.data, hdr.ctypes.data, slab.ctypes.data, max_elements)
-    if rc:
-        raise EngineError(f"msim_explain_set_full_batch: {rc}")
+    _call("msim_explain_set_full_batch", device, workload, concurrency, rows.ctypes.data, nr.ctypes.data, rows.shape[1], pay.ctypes.data, pay.shape[1],
+          max_values, n, out.ctypes.data, hdr.ctypes.data, slab.ctypes.data, max_elements)
     els = _StepLists(slab[i, :_n_set_records(hdr[i])].copy() for i in range(n))
     els.slab = slab[:, :max_elements]
     return out, hdr, els
@@ -987,40 +956,26 @@ def check_pn_batch(histories, device=0):
 def check_txn_batch(histories, device=0):
     """txn-list-append: several histories, each (rows, payload), through the device pass behind Engine.check() with the host analysis
     for what it cannot prove clean (msim_check_txn_batch).  Returns the CHECK_DT records, one per history."""
-    rs = [np.ascontiguousarray(h[0]) for h in histories]
-    ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
-    ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
-    po = np.zeros(len(ps) + 1, dtype=np.uint64); po[1:] = np.cumsum([len(x) for x in ps])
-    rows = np.concatenate(rs) if rs else np.zeros(0, dtype=OP_DT)
-    pay = np.concatenate(ps) if ps else np.zeros(0, dtype=np.uint32)
-    if len(pay) == 0:
-        pay = np.zeros(1, dtype=np.uint32)
-    out = np.zeros(len(rs), dtype=CHECK_DT)
-    rc = A.load().msim_check_txn_batch(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs), out.ctypes.data)
-    if rc:
-        raise EngineError(f"msim_check_txn_batch: {rc}")
+    rows, ro, pay, po = _offsets_form(histories)
+    out = np.zeros(len(ro) - 1, dtype=CHECK_DT)
+    _call("msim_check_txn_batch", device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(out), out.ctypes.data)
     return out
+
+
+def _check_offsets_batch(entry, histories, device, word):
+    """The entries (device, offsets form, n_histories, one word — a consistency model or the concurrency —, out, n_host)"""
+    rows, ro, pay, po = _offsets_form(histories)
+    out = np.zeros(len(ro) - 1, dtype=CHECK_DT)
+    n_host = C.c_uint32()
+    _call(entry, device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(out), word, out.ctypes.data, C.byref(n_host))
+    return out, n_host.value
 
 
 def check_rw_batch(histories, consistency_model="read-committed", device=0, _entry="msim_check_rw_batch"):
     """txn-rw-register: several histories, each (rows, payload), through the device passes behind Engine.check(): one proves a history
     free of what the model proscribes, the other analyses and classifies the rest (msim_check_rw_batch); the host analysis only takes
     what exceeds the device capacities.  Returns (CHECK_DT records, how many histories went to the host)."""
-    rs = [np.ascontiguousarray(h[0]) for h in histories]
-    ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
-    ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
-    po = np.zeros(len(ps) + 1, dtype=np.uint64); po[1:] = np.cumsum([len(x) for x in ps])
-    rows = np.concatenate(rs) if rs else np.zeros(0, dtype=OP_DT)
-    pay = np.concatenate(ps) if ps else np.zeros(0, dtype=np.uint32)
-    if len(pay) == 0:
-        pay = np.zeros(1, dtype=np.uint32)
-    out = np.zeros(len(rs), dtype=CHECK_DT)
-    n_host = C.c_uint32()
-    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs),
-                                   CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host))
-    if rc:
-        raise EngineError(f"{_entry}: {rc}")
-    return out, n_host.value
+    return _check_offsets_batch(_entry, histories, device, CONSISTENCY_MODELS[consistency_model])
 
 
 def classify_rw_batch(histories, consistency_model="read-committed", device=0):
@@ -1044,10 +999,8 @@ def explain_txn_history(rows, payload, consistency_model="strict-serializable", 
     out = np.zeros(1, dtype=CHECK_DT)
     cycle = np.zeros(1, dtype=CYCLE_DT)
     steps = np.zeros(max_steps, dtype=CYCLE_STEP_DT)
-    rc = getattr(A.load(), _entry)(rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), CONSISTENCY_MODELS[consistency_model],
-                                   out.ctypes.data_as(C.POINTER(A.CheckResult)), cycle.ctypes.data, steps.ctypes.data, max_steps)
-    if rc:
-        raise EngineError(f"{_entry}: {rc}")
+    _call(_entry, rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), CONSISTENCY_MODELS[consistency_model],
+          out.ctypes.data_as(C.POINTER(A.CheckResult)), cycle.ctypes.data, steps.ctypes.data, max_steps)
     return out[0], cycle[0], steps[:int(cycle[0]["n_steps"])].copy()
 
 
@@ -1060,23 +1013,15 @@ def explain_txn_batch(histories, consistency_model="strict-serializable", device
     """txn-list-append: classify_txn_batch with the witness cycles found on the device (msim_explain_txn_batch).  Returns (CHECK_DT
     records, CYCLE_DT records, a list of CYCLE_STEP_DT arrays — the steps written per history —, how many histories went to the host).
     The whole zero-padded slab of steps is the returned list's `.slab` ((histories, max_steps))."""
-    rs = [np.ascontiguousarray(h[0]) for h in histories]
-    ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
-    ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
-    po = np.zeros(len(ps) + 1, dtype=np.uint64); po[1:] = np.cumsum([len(x) for x in ps])
-    rows = np.concatenate(rs) if rs else np.zeros(0, dtype=OP_DT)
-    pay = np.concatenate(ps) if ps else np.zeros(0, dtype=np.uint32)
-    if len(pay) == 0:
-        pay = np.zeros(1, dtype=np.uint32)
-    out = np.zeros(len(rs), dtype=CHECK_DT)
-    cycles = np.zeros(len(rs), dtype=CYCLE_DT)
-    slab = np.zeros((len(rs), max_steps), dtype=CYCLE_STEP_DT)
+    rows, ro, pay, po = _offsets_form(histories)
+    n = len(ro) - 1
+    out = np.zeros(n, dtype=CHECK_DT)
+    cycles = np.zeros(n, dtype=CYCLE_DT)
+    slab = np.zeros((n, max_steps), dtype=CYCLE_STEP_DT)
     n_host = C.c_uint32()
-    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs),
-                                   CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host), cycles.ctypes.data, slab.ctypes.data, max_steps)
-    if rc:
-        raise EngineError(f"{_entry}: {rc}")
-    steps = _StepLists(slab[i, :int(cycles[i]["n_steps"])].copy() for i in range(len(rs)))
+    _call(_entry, device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, n,
+          CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host), cycles.ctypes.data, slab.ctypes.data, max_steps)
+    steps = _StepLists(slab[i, :int(cycles[i]["n_steps"])].copy() for i in range(n))
     steps.slab = slab
     return out, cycles, steps, n_host.value
 
@@ -1123,21 +1068,7 @@ def check_kafka_batch(histories, concurrency, device=0, _entry="msim_check_kafka
     """kafka: several histories, each (rows, payload), through the device pass behind Engine.check() (csrc/kafka_check_dev.hip) with the
     host checker for what it cannot prove clean (msim_check_kafka_batch); `concurrency` = the worker threads of the test.  Returns
     (CHECK_DT records, how many histories went to the host)."""
-    rs = [np.ascontiguousarray(h[0]) for h in histories]
-    ps = [np.ascontiguousarray(h[1], dtype=np.uint32) for h in histories]
-    ro = np.zeros(len(rs) + 1, dtype=np.uint64); ro[1:] = np.cumsum([len(x) for x in rs])
-    po = np.zeros(len(ps) + 1, dtype=np.uint64); po[1:] = np.cumsum([len(x) for x in ps])
-    rows = np.concatenate(rs) if rs else np.zeros(0, dtype=OP_DT)
-    pay = np.concatenate(ps) if ps else np.zeros(0, dtype=np.uint32)
-    if len(pay) == 0:
-        pay = np.zeros(1, dtype=np.uint32)
-    out = np.zeros(len(rs), dtype=CHECK_DT)
-    n_host = C.c_uint32()
-    rc = getattr(A.load(), _entry)(device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, len(rs), concurrency,
-                                   out.ctypes.data, C.byref(n_host))
-    if rc:
-        raise EngineError(f"{_entry}: {rc}")
-    return out, n_host.value
+    return _check_offsets_batch(_entry, histories, device, concurrency)
 
 
 def classify_kafka_batch(histories, concurrency, device=0):
@@ -1159,34 +1090,24 @@ def kafka_anomaly_census(results):
 def journal_fressian(cfg, events, payload):
     """One instance's net journal as the bytes of a net-journal/<stripe>.fressian file (msim_journal_fressian_rows, csrc/fressian.cpp):
     what maelstrom.net.journal writes (journal.clj:55-141) and maelstrom.net.checker / net.viz read."""
-    lib = A.load()
     ev = np.ascontiguousarray(events)
     pay = np.ascontiguousarray(payload, dtype=np.uint32)
     args = (C.byref(cfg), ev.ctypes.data, len(ev), pay.ctypes.data, len(pay))
     need = C.c_size_t()
-    rc = lib.msim_journal_fressian_rows(*args, None, 0, C.byref(need))
-    if rc:
-        raise EngineError(f"msim_journal_fressian_rows: {rc}")
+    _call("msim_journal_fressian_rows", *args, None, 0, C.byref(need))
     buf = (C.c_ubyte * max(need.value, 1))()
-    rc = lib.msim_journal_fressian_rows(*args, buf, need.value, None)
-    if rc:
-        raise EngineError(f"msim_journal_fressian_rows: {rc}")
+    _call("msim_journal_fressian_rows", *args, buf, need.value, None)
     return bytes(buf[: need.value])
 
 
 def history_edn_native(cfg, rows, payload):
     """history.edn text of one history straight from the binary rows (msim_history_edn_rows, csrc/edn.cpp)."""
-    lib = A.load()
     rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
     need = C.c_size_t()
-    args = (C.byref(cfg), rows.ctypes.data_as(C.c_void_p), len(rows), payload.ctypes.data_as(C.c_void_p), len(payload))
-    rc = lib.msim_history_edn_rows(*args, None, 0, C.byref(need))
-    if rc:
-        raise EngineError(f"msim_history_edn_rows: {rc}")
+    args = (C.byref(cfg), rows.ctypes.data, len(rows), payload.ctypes.data, len(payload))
+    _call("msim_history_edn_rows", *args, None, 0, C.byref(need))
     buf = C.create_string_buffer(need.value)
-    rc = lib.msim_history_edn_rows(*args, buf, need.value, None)
-    if rc:
-        raise EngineError(f"msim_history_edn_rows: {rc}")
+    _call("msim_history_edn_rows", *args, buf, need.value, None)
     return buf.value.decode()
 
 
