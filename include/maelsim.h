@@ -417,6 +417,42 @@ int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_
 int msim_classify_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                               uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host);
 
+/* kafka: the explanation of a verdict — a witness for every anomaly, what jepsen's kafka checker prints beside the anomaly's name (the
+ * one the reference shows is workload/kafka.clj:42-60, {:key :delta :skipped :ops}).  Defined over the history alone, not by how it is found.
+ *   Vocabulary (that of msim_check_kafka_rows' checker, csrc/kafka_check.cpp).  An observation is every :ok send and every pair of every
+ *     :ok poll (key < 8, offset and message < 2048), ordered by (row index, ordinal inside the row's payload).  last(k,o) is the message
+ *     of the last observation at (k,o); home(k,m) the offset of the first observation of m in key k; top(k) the highest polled offset of
+ *     k.  lp is what the checker's last_poll[k] of the process held when a block was judged (the last offset of the process's previous
+ *     block of k; forgotten across an :assign and a poll that did not complete :ok), ls the same for last_send[k].
+ *   One finding per:
+ *     lost-write            (k,o) acknowledged, never polled, o < top(k): offset = o, row_a = the lowest :ok send row acknowledging (k,o)
+ *                           (the writer), value = that send's message, other = top(k), row_b = the lowest :ok poll row holding (k, top(k));
+ *     inconsistent-offsets  (k,o) observed with two or more different messages: offset = o, value = last(k,o), row_b = the row of that
+ *                           last observation, row_a / other = the row / message of the first observation at (k,o) whose message differs
+ *                           from value;
+ *     duplicate             (k,o) where some observation's message has its home elsewhere (count[7] = duplicated_count): offset = o,
+ *                           value / row_b = the message / row of the first such observation at (k,o), other = home(k, value), row_a = the
+ *                           row of the first observation of value;
+ *     aborted-read          (k,o) polled and the send of last(k,o) failed: offset = o, value = last(k,o), row_a = the lowest :fail send
+ *                           row of (k, value), row_b = the lowest :ok poll row holding a pair at (k,o), other = 0;
+ *     nonmonotonic-send     an :ok send row with o <= ls: offset = o, value = its message, other = ls, row_b = this row, row_a = the row
+ *                           of the :ok send that left ls;
+ *     nonmonotonic-poll, int-nonmonotonic-poll
+ *                           a block with o0 <= lp: offset = o0, value = the block's first message, other = lp, row_b = the poll's row,
+ *                           row_a = the row of the poll whose block left lp (int-: the same row);
+ *     poll-skip, int-poll-skip
+ *                           a block with o0 > lp + 1 and an observed offset strictly between: offset = o0, other = lp (:delta = offset -
+ *                           other), value = how many offsets strictly between were observed (the length of :skipped), row_a / row_b as
+ *                           for the nonmonotonic polls;
+ *     malformed             no finding; count[9] = 1 where the checker sets the bit.
+ *     Unobserved writes stay a count (never_read_count), as in jepsen.
+ *   Order.  A history's findings ascend by (anomaly, key, offset, value, other, row_a, row_b); findings equal under it are the same bytes.
+ *   Truncation.  The first max_findings in that order are written, truncated = 1 if one is missing; count[] is always the true number.
+ *     max_findings = 0 is legal: the header only.  Records beyond n_findings are zero.
+ *   Invariants.  count[i] > 0 iff bit i of the record's error_count is set; count[0] = lost_count; count[7] = duplicated_count. */
+/* The two records (msim_kafka_finding, 32 bytes; msim_kafka_explain, 48 bytes, one per history) and the three entries
+ * (msim_explain_kafka_rows, msim_explain_kafka_batch, msim_explain_kafka): maelsim_kafka_explain.h, included below. */
+
 /* unique-ids: checks `n_histories` histories given on the host — history i in the slab rows + i * max_rows, n_rows[i] rows used —
  * with the device checker of msim_check ([upstream] jepsen.checker/unique-ids); out[i] is what msim_check_unique_rows gives. */
 int msim_check_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out);
@@ -773,6 +809,8 @@ int msim_selftest_wave(int device);
 
 const char *msim_last_error(const msim_ctx *ctx);
 void msim_destroy(msim_ctx *ctx);
+
+#include "maelsim_kafka_explain.h"   /* kafka: the explained verdicts (the contract: above msim_check_unique_batch) */
 
 #ifdef __cplusplus
 }

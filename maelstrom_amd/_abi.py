@@ -45,6 +45,9 @@ EDGE_KINDS = {1: "ww", 2: "wr", 4: "rw", 8: "realtime"}   # MSIM_EDGE_*
 AVAIL_NIL, AVAIL_TOTAL, AVAIL_FRACTION = range(3)
 PERF_MAX_F, PERF_MAX_WINDOWS = 4, 16
 COMM_ID_BYTES = 128
+# kafka_explain_kernel's capacities (csrc/kafka_check_dev.hip): an observation that names an offset or message from KAFKA_EXPLAIN_TABLE_BOUND
+# on, and a history of more than KAFKA_EXPLAIN_MAX_FINDINGS findings, are explained by the host walk
+KAFKA_EXPLAIN_TABLE_BOUND, KAFKA_EXPLAIN_MAX_FINDINGS = 384, 1024
 
 
 class Config(C.Structure):
@@ -141,6 +144,15 @@ class SetExplain(C.Structure):
                 ("n_worst_stale", C.c_uint32), ("lost_latency_ms", C.c_uint32 * 5), ("worst_stale", SetElement * 8)]
 
 
+class KafkaFinding(C.Structure):
+    _fields_ = [("anomaly", C.c_uint32), ("key", C.c_uint32), ("offset", C.c_uint32), ("value", C.c_uint32), ("other", C.c_uint32),
+                ("row_a", C.c_uint32), ("row_b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KafkaExplain(C.Structure):
+    _fields_ = [("n_findings", C.c_uint32), ("truncated", C.c_uint32), ("count", C.c_uint32 * 10)]
+
+
 # The one table of records: the header's struct name -> its Structure, field names and order as in include/maelsim.h.  engine.py derives
 # the numpy dtypes from these (np.dtype(Structure)); tests/test_abi_tables.py compiles a probe against the header and compares every
 # size and offset with both.
@@ -229,6 +241,16 @@ PROTOTYPES = {
 }
 EXPORTS = list(PROTOTYPES)
 
+# The same two tables for include/maelsim_kafka_explain.h (maelsim.h includes it): the explained kafka verdicts.  They stand beside
+# RECORDS / PROTOTYPES, not in them, because those are held to maelsim.h's own text, declaration for declaration
+# (tests/test_abi_tables.py); tests/test_kafka_explain.py holds these to their header the same way.
+KAFKA_EXPLAIN_RECORDS = {"msim_kafka_finding": KafkaFinding, "msim_kafka_explain": KafkaExplain}
+KAFKA_EXPLAIN_PROTOTYPES = {
+    "msim_explain_kafka_rows": (_i, (_vp, _u32, _vp, _u32, _res, _vp, _vp, _u32)),
+    "msim_explain_kafka_batch": (_i, _offsets_args + (_u32, _vp, _vp, _vp, _u32, _vp)),
+    "msim_explain_kafka": (_i, (_vp, _vp, _vp, _u32, _u32)),
+}
+
 _lib = None
 
 
@@ -241,7 +263,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -m maelstrom_amd.build` (hipcc, gfx950). "
                            "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES}.items():
         fn = getattr(lib, name, None)   # MSIM_LIB may name an older build (the A/B tools under tools/ time the parent's): an entry it lacks is skipped, and calling it still raises
         if fn is not None:
             fn.restype, fn.argtypes = restype, list(argtypes)

@@ -134,6 +134,8 @@ void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uin
 void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
                                     msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);
 void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out);
+void msim_kafka_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out,
+                                      msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings);
 void msim_pn_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);
 
 // The hand-off: the rows and payload words of the histories `todo` come to the host, analyse(rows, n_rows, payload, n_words, flags, i)

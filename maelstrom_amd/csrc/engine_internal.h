@@ -124,6 +124,7 @@ int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles = nullptr, ms
 int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0);
 // kafka_check.cpp (host)
 int msim_check_kafka_host(msim_ctx *ctx);
+int msim_explain_kafka_host(msim_ctx *ctx, msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings);   // (hdr null: msim_check_kafka_host)
 // kafka_check_dev.hip (device pass + host checker for what it cannot prove clean)
 int msim_check_kafka_device(msim_ctx *ctx);
 // unique_check_dev.hip, pn_check_dev.hip

@@ -18,8 +18,11 @@
 // out: valid = 1 iff none of the errors above (2 = :unknown when nothing was acknowledged and nothing polled), attempt_count = sends
 // invoked, stable_count = sends acknowledged, lost_count = lost writes, never_read_count = unobserved, duplicated_count = duplicates,
 // error_count = MSIM_KAFKA_* bits, op / ok / fail / info counts as everywhere.
+// msim_explain_kafka_rows is the same walk handed an `Explain`: wherever it sets a bit it also records the witness — key, offsets, the
+// rows of the two ops — that include/maelsim.h defines ("kafka: the explanation of a verdict"); the verdict does not depend on it.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <thread>
@@ -39,7 +42,36 @@ struct Tables {
   uint8_t dup_at[KEYS][OFFS];          // offset already counted as a duplicate's second home
 };
 
-struct Proc { uint32_t process; bool open; int32_t last_poll[KEYS], last_send[KEYS]; };
+struct Proc { uint32_t process; bool open; int32_t last_poll[KEYS], last_send[KEYS]; uint32_t poll_row[KEYS], send_row[KEYS]; };
+
+// What the explanation keeps beside the tables (msim_explain_kafka_rows; include/maelsim.h, "kafka: the explanation of a verdict"): the
+// rows behind the cells, and the findings of the walk as it judges them.  check_kafka fills it where it is given one, and decides nothing
+// by it.
+constexpr uint32_t NOROW = MSIM_NO_VALUE;
+struct Explain {
+  struct Cell { uint32_t first_row, first_msg, alt_row, alt_msg, last_row; };   // per (key, offset): the first observation, the first one with another message, the last
+  std::vector<Cell> at;                       // [KEYS * OFFS]
+  std::vector<uint32_t> home_row;             // [KEYS * OFFS] by message: the row of its first observation
+  std::vector<uint32_t> dup_row, dup_msg;     // [KEYS * OFFS] by offset: the first observation whose home is elsewhere
+  std::vector<uint32_t> ack_row, poll_row, fail_row;   // the lowest :ok send row / :ok poll row of (key, offset), :fail send row of (key, message)
+  std::vector<msim_kafka_finding> found;
+  Explain() : at(KEYS * OFFS, Cell{NOROW, 0, NOROW, 0, NOROW}), home_row(KEYS * OFFS, NOROW), dup_row(KEYS * OFFS, NOROW), dup_msg(KEYS * OFFS, 0),
+              ack_row(KEYS * OFFS, NOROW), poll_row(KEYS * OFFS, NOROW), fail_row(KEYS * OFFS, NOROW) {}
+  void add(uint32_t anomaly, uint32_t key, uint32_t offset, uint32_t value, uint32_t other, uint32_t row_a, uint32_t row_b) {
+    found.push_back(msim_kafka_finding{anomaly, key, offset, value, other, row_a, row_b, 0u});
+  }
+};
+
+// the observation observe() is about to take (before it: where[k][m] still says whether m was seen)
+void note(Explain &x, const Tables &t, uint32_t k, uint32_t o, uint32_t m, uint32_t row) {
+  if (k >= KEYS || o >= OFFS || m >= OFFS) return;
+  if (!t.where[k][m]) x.home_row[k * OFFS + m] = row;
+  else if (t.where[k][m] != o + 1 && x.dup_row[k * OFFS + o] == NOROW) { x.dup_row[k * OFFS + o] = row; x.dup_msg[k * OFFS + o] = m; }
+  Explain::Cell &c = x.at[k * OFFS + o];
+  if (c.first_row == NOROW) { c.first_row = row; c.first_msg = m; }
+  else if (c.alt_row == NOROW && m != c.first_msg) { c.alt_row = row; c.alt_msg = m; }
+  c.last_row = row;
+}
 
 void observe(Tables &t, uint32_t k, uint32_t o, uint32_t m, uint32_t &bits, uint32_t &dups) {
   if (k >= KEYS || o >= OFFS || m >= OFFS) { bits |= MSIM_KAFKA_MALFORMED; return; }
@@ -55,7 +87,8 @@ bool known_between(const Tables &t, uint32_t k, int32_t a, int32_t b) {
   return false;
 }
 
-void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out, Tables &t) {
+void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out, Tables &t,
+                 Explain *x = nullptr) {
   std::memset(out, 0, sizeof *out);
   std::memset(t.msg, 0xFF, sizeof t.msg);
   std::memset(t.polled, 0, sizeof t.polled); std::memset(t.acked, 0, sizeof t.acked);
@@ -75,9 +108,10 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
       else if (type == MSIM_T_OK) {
         if (o == 0x7FFu || k >= KEYS) { bits |= MSIM_KAFKA_MALFORMED; continue; }
         out->stable_count++;
+        if (x) note(*x, t, k, o, m, i);
         observe(t, k, o, m, bits, dups);
-        if (k < KEYS && o < OFFS) t.acked[k][o] = 1;
-      } else if (type == MSIM_T_FAIL && k < KEYS && m < OFFS) t.failed[k][m] = 1;
+        if (k < KEYS && o < OFFS) { t.acked[k][o] = 1; if (x && x->ack_row[k * OFFS + o] == NOROW) x->ack_row[k * OFFS + o] = i; }
+      } else if (type == MSIM_T_FAIL && k < KEYS && m < OFFS) { t.failed[k][m] = 1; if (x && x->fail_row[k * OFFS + m] == NOROW) x->fail_row[k * OFFS + m] = i; }
     } else if (f == MSIM_F_POLL && type == MSIM_T_OK) {
       const uint32_t len = MSIM_OP_LEN(r);
       if (len == 0) continue;
@@ -88,8 +122,9 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
         if (p + (n + 1) / 2 > len) { bits |= MSIM_KAFKA_MALFORMED; break; }
         for (uint32_t e = 0; e < n; e++) {
           const uint32_t m = (w[p + e / 2] >> (16 * (e & 1))) & 0xFFFFu;
+          if (x) note(*x, t, k, o0 + e, m, i);
           observe(t, k, o0 + e, m, bits, dups);
-          if (o0 + e < OFFS) t.polled[k][o0 + e] = 1;
+          if (o0 + e < OFFS) { t.polled[k][o0 + e] = 1; if (x && x->poll_row[k * OFFS + o0 + e] == NOROW) x->poll_row[k * OFFS + o0 + e] = i; }
         }
         p += (n + 1) / 2;
       }
@@ -103,6 +138,18 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
     for (uint32_t o = 0; o < OFFS; o++) {
       if (t.acked[k][o] && !t.polled[k][o]) { if ((int32_t)o < top) { out->lost_count++; bits |= MSIM_KAFKA_LOST_WRITE; } else out->never_read_count++; }
       if (t.polled[k][o] && t.msg[k][o] != NOMSG && t.failed[k][t.msg[k][o]]) bits |= MSIM_KAFKA_ABORTED_READ;
+      if (!x) continue;
+      const uint32_t i = k * OFFS + o;
+      if (t.acked[k][o] && !t.polled[k][o] && (int32_t)o < top)
+        x->add(MSIM_KAFKA_LOST_WRITE, k, o, (rows[x->ack_row[i]].value >> 6) & 0x7FFu, (uint32_t)top, x->ack_row[i], x->poll_row[k * OFFS + (uint32_t)top]);
+      const Explain::Cell &c = x->at[i];
+      if (c.alt_row != NOROW) {   // two different messages: the first observation that differs from the last one is the first one, or the first other one
+        const bool first = c.first_msg != t.msg[k][o];
+        x->add(MSIM_KAFKA_INCONSISTENT_OFFSETS, k, o, t.msg[k][o], first ? c.first_msg : c.alt_msg, first ? c.first_row : c.alt_row, c.last_row);
+      }
+      if (t.dup_at[k][o]) { const uint32_t m = x->dup_msg[i]; x->add(MSIM_KAFKA_DUPLICATE, k, o, m, t.where[k][m] - 1u, x->home_row[k * OFFS + m], x->dup_row[i]); }
+      if (t.polled[k][o] && t.msg[k][o] != NOMSG && t.failed[k][t.msg[k][o]])
+        x->add(MSIM_KAFKA_ABORTED_READ, k, o, t.msg[k][o], 0u, x->fail_row[k * OFFS + t.msg[k][o]], x->poll_row[i]);
     }
   }
 
@@ -111,7 +158,7 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
   auto proc_of = [&](uint32_t process) -> Proc & {
     for (Proc &p : procs) if (p.process == process) return p;
     Proc p; p.process = process; p.open = true;
-    for (uint32_t k = 0; k < KEYS; k++) { p.last_poll[k] = -1; p.last_send[k] = -1; }
+    for (uint32_t k = 0; k < KEYS; k++) { p.last_poll[k] = -1; p.last_send[k] = -1; p.poll_row[k] = NOROW; p.send_row[k] = NOROW; }
     procs.push_back(p);
     return procs.back();
   };
@@ -131,8 +178,11 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
       const uint32_t k = r.value & 63u, o = r.value >> 17;
       if (k >= KEYS || o >= OFFS) continue;
       Proc &p = proc_of(process);
-      if (p.last_send[k] >= 0 && (int32_t)o <= p.last_send[k]) bits |= MSIM_KAFKA_NONMONOTONIC_SEND;
-      p.last_send[k] = (int32_t)o;
+      if (p.last_send[k] >= 0 && (int32_t)o <= p.last_send[k]) {
+        bits |= MSIM_KAFKA_NONMONOTONIC_SEND;
+        if (x) x->add(MSIM_KAFKA_NONMONOTONIC_SEND, k, o, (r.value >> 6) & 0x7FFu, (uint32_t)p.last_send[k], p.send_row[k], i);
+      }
+      p.last_send[k] = (int32_t)o; p.send_row[k] = i;
     } else if (f == MSIM_F_POLL) {
       const uint32_t len = MSIM_OP_LEN(r);
       if (len == 0 || (uint64_t)r.value + len > n_words) continue;
@@ -142,16 +192,26 @@ void check_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, 
       for (uint32_t q = 0; q < len;) {
         const uint32_t h = w[q++], k = h & 7u, n = (h >> 8) & 0xFFu, o0 = h >> 16;
         if (q + (n + 1) / 2 > len) break;
+        const uint32_t m0 = n ? w[q] & 0xFFFFu : 0u;   // the block's first message
         q += (n + 1) / 2;
         if (!n) continue;
         // a block holds one run o0, o0 + 1, ...: a key's pairs that do not continue the run start another block of the same key
         const int32_t first = (int32_t)o0, last = (int32_t)(o0 + n - 1);
         const bool internal = (in_this_poll >> k) & 1u;
         if (p.last_poll[k] >= 0) {
-          if (first <= p.last_poll[k]) bits |= internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL;
-          else if (first > p.last_poll[k] + 1 && known_between(t, k, p.last_poll[k], first)) bits |= internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP;
+          if (first <= p.last_poll[k]) {
+            bits |= internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL;
+            if (x) x->add(internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL, k, o0, m0, (uint32_t)p.last_poll[k], p.poll_row[k], i);
+          } else if (first > p.last_poll[k] + 1 && known_between(t, k, p.last_poll[k], first)) {
+            bits |= internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP;
+            if (x) {
+              uint32_t skipped = 0;
+              for (int32_t o = p.last_poll[k] + 1; o < first; o++) skipped += (uint32_t)o < OFFS && t.msg[k][o] != NOMSG;
+              x->add(internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP, k, o0, skipped, (uint32_t)p.last_poll[k], p.poll_row[k], i);
+            }
+          }
         }
-        p.last_poll[k] = last; in_this_poll |= 1u << k;
+        p.last_poll[k] = last; p.poll_row[k] = i; in_this_poll |= 1u << k;
       }
     }
   }
@@ -171,6 +231,38 @@ void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const 
   check_kafka(rows, n_rows, payload, n_words, flags, out, t[0]);
 }
 
+// The findings of one history in the contract's order, cut to max_findings (include/maelsim.h, "kafka: the explanation of a verdict").
+static void explain_kafka(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out,
+                          msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings) {
+  std::vector<Tables> t(1);
+  Explain x;
+  check_kafka(rows, n_rows, payload, n_words, flags, out, t[0], &x);
+  std::memset(hdr, 0, sizeof *hdr);
+  if (max_findings) std::memset(findings, 0, (size_t)max_findings * sizeof *findings);
+  for (const msim_kafka_finding &f : x.found) hdr->count[__builtin_ctz(f.anomaly)]++;
+  hdr->count[9] = (out->error_count & MSIM_KAFKA_MALFORMED) ? 1u : 0u;
+  std::sort(x.found.begin(), x.found.end(), [](const msim_kafka_finding &a, const msim_kafka_finding &b) {
+    const uint32_t u[7] = {a.anomaly, a.key, a.offset, a.value, a.other, a.row_a, a.row_b}, v[7] = {b.anomaly, b.key, b.offset, b.value, b.other, b.row_a, b.row_b};
+    return std::lexicographical_compare(u, u + 7, v, v + 7);
+  });
+  hdr->n_findings = (uint32_t)std::min<size_t>(x.found.size(), max_findings);
+  hdr->truncated = x.found.size() > max_findings ? 1u : 0u;
+  std::copy(x.found.begin(), x.found.begin() + hdr->n_findings, findings);
+}
+
+// one history on the calling thread, explained (kafka_check_dev.hip: what kafka_explain_kernel hands over)
+void msim_kafka_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out,
+                                      msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings) {
+  explain_kafka(rows, n_rows, payload, n_words, flags, out, hdr, findings, max_findings);
+}
+
+extern "C" int msim_explain_kafka_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, msim_check_result *out,
+                                       msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings) {
+  if ((!rows && n_rows) || !out || (!payload && n_words) || !hdr || (!findings && max_findings)) return MSIM_E_INVALID;
+  explain_kafka(rows, n_rows, payload, n_words, 0, out, hdr, findings, max_findings);
+  return MSIM_OK;
+}
+
 extern "C" int msim_check_kafka_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, msim_check_result *out) {
   if ((!rows && n_rows) || !out || (!payload && n_words)) return MSIM_E_INVALID;
   std::vector<Tables> t(1);
@@ -178,7 +270,8 @@ extern "C" int msim_check_kafka_rows(const msim_op *rows, uint32_t n_rows, const
   return MSIM_OK;
 }
 
-int msim_check_kafka_host(msim_ctx *ctx) {
+// (hdr: msim_explain_kafka's arrays — every history explained by the walk; null: msim_check)
+int msim_explain_kafka_host(msim_ctx *ctx, msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings) {
   const auto t0 = std::chrono::steady_clock::now();
   int rc = msim_fetch(ctx);
   if (rc != MSIM_OK) return rc;
@@ -189,11 +282,15 @@ int msim_check_kafka_host(msim_ctx *ctx) {
   if (nt > n) nt = n;
   std::vector<std::thread> th;
   for (unsigned w = 0; w < nt; w++)
-    th.emplace_back([ctx, n, nt, w]() {
+    th.emplace_back([=]() {
       std::vector<Tables> t(1);
-      for (uint32_t i = w; i < n; i += nt)
-        check_kafka(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_payload + ctx->h_pay_off[i], ctx->h_meta[i].n_payload_words,
-                    ctx->h_meta[i].flags, &ctx->h_check[i], t[0]);
+      for (uint32_t i = w; i < n; i += nt) {
+        const msim_op *rows = ctx->h_rows + ctx->h_row_off[i];
+        const uint32_t *pay = ctx->h_payload + ctx->h_pay_off[i];
+        const msim_inst_meta &m = ctx->h_meta[i];
+        if (hdr) explain_kafka(rows, m.n_rows, pay, m.n_payload_words, m.flags, &ctx->h_check[i], &hdr[i], findings + (size_t)i * max_findings, max_findings);
+        else check_kafka(rows, m.n_rows, pay, m.n_payload_words, m.flags, &ctx->h_check[i], t[0]);
+      }
     });
   for (auto &x : th) x.join();
   MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
@@ -201,3 +298,5 @@ int msim_check_kafka_host(msim_ctx *ctx) {
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return MSIM_OK;
 }
+
+int msim_check_kafka_host(msim_ctx *ctx) { return msim_explain_kafka_host(ctx, nullptr, nullptr, 0); }

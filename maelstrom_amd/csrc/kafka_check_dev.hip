@@ -8,7 +8,8 @@
 // strictly increase or jump over a known offset, a row that does not decode, an offset or message beyond the tables — is answered
 // NEEDS_HOST and the host checker classifies it (kafka_dev_run below): never approximated.  A caller whose histories are not clean
 // (msim_classify_kafka_batch, msim_set_check_classify) has them classified by kafka_classify_kernel instead, see there.  The two kernels
-// are the two instantiations of one body, kafka_body<CLASSIFY>.
+// are two instantiations of one body, kafka_body<MODE>; the third, kafka_explain_kernel, is the classification that keeps WHERE it set a
+// bit (msim_explain_kafka_batch, msim_explain_kafka), see there.
 //
 // Layout.  The tables of kafka_check.cpp (the key's log as observed, where each message was seen, polled / acknowledged / failed
 // flags) live in LDS, `T` entries per key (the configuration bounds offsets and messages by max-writes-per-key; a first pass over
@@ -89,14 +90,60 @@ constexpr u64 SEEN = 1ull << 63;
 
 size_t kafka_classify_lds_bytes(u32 T) { return (size_t)KEYS * T * 16 + (4 * (size_t)KEYS * T / 32 + KEYS + 16 + CMAX * WST + NWV * STAGE) * 4; }
 
-// The one body of kafka_check_kernel (CLASSIFY = false: the first finding decides, the history is the host's) and kafka_classify_kernel
-// (CLASSIFY = true: every finding is a bit or a count of the record).  The row loop, pass 1b's scan and pass 2's walk are the same; what
-// a mode does with an observation and with a finding stands behind the switch.  `smem`: kafka_lds_bytes / kafka_classify_lds_bytes.
-template <bool CLASSIFY>
-__device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, unsigned char *const smem) {
+// ---- the explanation of unclean histories (msim_explain_kafka_batch, msim_explain_kafka; include/maelsim.h, "kafka: the explanation of a
+// verdict") ----------------------------------------------------------------------------------------------------------------------------
+// kafka_explain_kernel is the classification (the same passes, the same record) that emits a finding wherever a bit is set:
+//   pass 1   also keeps, per (key, offset), the lowest :ok send row and the lowest :ok poll row, per (key, message) the lowest :fail send
+//            row (atomic minima of the row index);
+//   pass 1'  also keeps, per (key, offset), the first observation whose message differs from the last one's and the first one whose
+//            message has its home elsewhere (atomic minima of order << 11 | message, the cells' idiom), and marks the offset inconsistent;
+//   pass 1b  one finding per lost offset, inconsistent offset, duplicate's other home and aborted read, read off those cells;
+//   pass 2   a worker's state also holds the row that left each last polled / sent offset (WSTX = WST + 16 words), a skip counts the known
+//            offsets it jumps over; one finding per nonmonotonic send, per block that does not advance, per block that skips.
+// A finding is appended to the history's slab of the workspace in HBM (an atomic counter: wavefronts interleave).  Behind pass 2 the tables
+// are dead: the workgroup writes the record, gathers the findings into LDS, sorts them by the contract's key (a bitonic network over the
+// 512 threads, the slab padded with all-ones records to a power of two) and writes the first max_findings with the header.
+// Capacities — a history beyond either is handed to the host walk (NEEDS_HOST, counted in n_host), as for the classification's reasons:
+//   * TX_MAX = 384: an observation that names an offset or message from there on.  The explaining cells take (44 + 5/8) bytes per (key,
+//     offset) — 357 per offset —, 149792 bytes in all at 384 of a CU's 163840 (T = 288 at the bench shape: 115520);
+//   * FX_MAX = 1024 findings: what the sort holds (32 KB of the LDS the tables occupied; the smallest launch takes that much).
+constexpr u32 TX_MAX = 384u, FX_MAX = 1024u;
+constexpr u32 WSTX = WST + 16u;   // + the rows behind the last polled offset x 8, the last sent offset x 8
+constexpr u32 HDRX = 32u;         // the explaining header: [11] findings emitted, [16 .. 25] findings per anomaly
+
+struct KXOut {   // what kafka_explain_kernel writes beside p.out
+  msim_kafka_explain *hdr; msim_kafka_finding *findings; u32 max_findings;
+  uint4 *ws;     // FX_MAX findings (two uint4 each) per launched workgroup
+};
+
+size_t kafka_explain_lds_bytes(u32 T) {
+  const size_t tables = (size_t)KEYS * T * (32 + 12) + (5 * (size_t)KEYS * T / 32 + KEYS + HDRX + CMAX * WSTX + NWV * STAGE) * 4;
+  return std::max(tables, (size_t)FX_MAX * sizeof(msim_kafka_finding));
+}
+
+// ascending by (anomaly, key, offset, value, other, row_a, row_b, reserved): a = (a0, a1) before b
+__device__ __forceinline__ bool finding_before(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
+  if (a0.x != b0.x) return a0.x < b0.x;
+  if (a0.y != b0.y) return a0.y < b0.y;
+  if (a0.z != b0.z) return a0.z < b0.z;
+  if (a0.w != b0.w) return a0.w < b0.w;
+  if (a1.x != b1.x) return a1.x < b1.x;
+  if (a1.y != b1.y) return a1.y < b1.y;
+  if (a1.z != b1.z) return a1.z < b1.z;
+  return a1.w < b1.w;
+}
+
+// The one body of kafka_check_kernel (MODE 0: the first finding decides, the history is the host's), kafka_classify_kernel (MODE 1,
+// CLASSIFY: every finding is a bit or a count of the record) and kafka_explain_kernel (MODE 2, CLASSIFY and EXPLAIN: and a record of
+// `x`, through slab `slot` of the workspace).  The row loop, pass 1b's scan and pass 2's walk are the same; what a mode does with an
+// observation and with a finding stands behind the switches.  `smem`: kafka_lds_bytes / kafka_classify_lds_bytes / kafka_explain_lds_bytes.
+template <int MODE>
+__device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, unsigned char *const smem, const KXOut &x = KXOut{}, const u32 slot = 0) {
+  constexpr bool CLASSIFY = MODE >= 1, EXPLAIN = MODE == 2;
   using Cell = std::conditional_t<CLASSIFY, unsigned long long, u32>;
   constexpr Cell UNSEEN = CLASSIFY ? 0u : EMPTY;          // msg of an offset never seen
-  constexpr u32 BITMAPS = CLASSIFY ? 4u : 3u;
+  constexpr u32 BITMAPS = EXPLAIN ? 5u : CLASSIFY ? 4u : 3u;
+  constexpr u32 WS = EXPLAIN ? WSTX : WST, HDRW = EXPLAIN ? HDRX : 16u;
   const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const u32 T = p.T, KT = KEYS * T, C = p.C;
   // [KEYS][T] the key's log as observed.  Clean: the message (EMPTY: offset never seen).  CLASSIFY: SEEN | order | the message: the
@@ -104,19 +151,29 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
   Cell *const msg = reinterpret_cast<Cell *>(smem);
   // [KEYS][T] by message.  Clean: 1 + the offset it was seen at.  CLASSIFY: order | the offset: the min is the first observation (~0: never seen)
   Cell *const where = msg + KT;
-  u32 *const polled = reinterpret_cast<u32 *>(where + KT);   // [KEYS * T / 32] bits
+  // EXPLAIN, [KEYS][T] by offset, order | the message, minima (~0: none): the first observation that differs from the last one's message,
+  // the first one whose message has its home elsewhere
+  [[maybe_unused]] Cell *const fdiff = where + KT;
+  [[maybe_unused]] Cell *const fdup = fdiff + KT;
+  u32 *const polled = reinterpret_cast<u32 *>(where + (EXPLAIN ? 3u : 1u) * KT);   // [KEYS * T / 32] bits
   u32 *const acked = polled + KT / 32;
   u32 *const failed = acked + KT / 32;                    // by message: its send definitely failed
   u32 *const dup_at = failed + KT / 32;                   // CLASSIFY only, by offset: some message seen here has its first home elsewhere
+  [[maybe_unused]] u32 *const incons = dup_at + KT / 32;  // EXPLAIN only, by offset: seen with two different messages
   u32 *const top1 = polled + BITMAPS * (KT / 32);         // [KEYS] 1 + the highest polled offset
-  u32 *const hdr = top1 + KEYS;                           // [16]: [0] the host's, [1..7] counters; CLASSIFY: [8] lost, [9] duplicates, [10] MSIM_KAFKA_* bits
-  u32 *const wst = hdr + 16;                              // [CMAX][WST]
-  u32 *const stg = wst + CMAX * WST + wave * STAGE;       // this wavefront's staging area
+  u32 *const hdr = top1 + KEYS;                           // [HDRW]: [0] the host's, [1..7] counters; CLASSIFY: [8] lost, [9] duplicates, [10] MSIM_KAFKA_* bits
+  u32 *const wst = hdr + HDRW;                            // [CMAX][WS]
+  u32 *const stg = wst + CMAX * WS + wave * STAGE;        // this wavefront's staging area
+  // EXPLAIN, [KEYS][T] each, minima of the row index (EMPTY: none): the :ok sends of (key, offset), the :ok polls of it, the :fail sends of (key, message)
+  [[maybe_unused]] u32 *const fack = wst + CMAX * WS + NWV * STAGE;
+  [[maybe_unused]] u32 *const fpoll = fack + KT;
+  [[maybe_unused]] u32 *const ffail = fpoll + KT;
   HIST_VIEW(p, hist);
 
   for (u32 i = tid; i < KT; i += NT) { msg[i] = UNSEEN; where[i] = CLASSIFY ? ~(Cell)0 : (Cell)0; }
-  for (u32 i = tid; i < BITMAPS * KT / 32 + KEYS + 16; i += NT) polled[i] = 0;
-  for (u32 i = tid; i < CMAX * WST; i += NT) wst[i] = EMPTY;
+  if constexpr (EXPLAIN) for (u32 i = tid; i < KT; i += NT) { fdiff[i] = ~(Cell)0; fdup[i] = ~(Cell)0; fack[i] = EMPTY; fpoll[i] = EMPTY; ffail[i] = EMPTY; }
+  for (u32 i = tid; i < BITMAPS * KT / 32 + KEYS + HDRW; i += NT) polled[i] = 0;
+  for (u32 i = tid; i < CMAX * WS; i += NT) wst[i] = EMPTY;
   __syncthreads();
 
 #define TO_HOST() do { hdr[0] = 1u; } while (0)
@@ -125,6 +182,16 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
   u32 bits = 0;
   // an anomaly: the clean pass proves nothing about such a history, the classification names it
   auto finding = [&](u32 bit) __attribute__((always_inline)) { if constexpr (CLASSIFY) bits |= bit; else TO_HOST(); };
+  // EXPLAIN: the finding itself, appended to the workspace slab (more than the sort holds: the host's)
+  [[maybe_unused]] auto emit = [&](u32 bit, u32 key, u32 offset, u32 value, u32 other, u32 row_a, u32 row_b) __attribute__((always_inline)) {
+    atomicAdd(&hdr[16u + (u32)__builtin_ctz(bit)], 1u);
+    const u32 at = atomicAdd(&hdr[11], 1u);
+    if (at >= FX_MAX) { TO_HOST(); return; }
+    uint4 *const w = x.ws + ((size_t)slot * FX_MAX + at) * 2u;
+    w[0] = make_uint4(bit, key, offset, value);
+    w[1] = make_uint4(other, row_a, row_b, 0u);
+  };
+  [[maybe_unused]] auto row_of = [](u64 cell) __attribute__((always_inline)) { return (u32)(cell >> 28) & 0x7FFFFFFFu; };   // of SEEN | order << 11 | value
   // Clean: every observation of (key, offset, message) must agree with every other one (inconsistent offsets, duplicates: the host's).
   // CLASSIFY, `ord` = row index << 17 | ordinal inside the row: sweep 0 records the observation, sweep 1 compares it with what all of them left
   auto observe = [&](u32 sweep, u32 k, u32 o, u32 m, u64 ord) __attribute__((always_inline)) {
@@ -138,8 +205,14 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
       atomicMax(&msg[k * T + o], (unsigned long long)(SEEN | (ord << 11) | m));
       atomicMin(&where[k * T + m], (unsigned long long)((ord << 11) | o));
     } else {
-      if ((u32)(msg[k * T + o] & 0x7FFull) != m) bits |= MSIM_KAFKA_INCONSISTENT_OFFSETS;
-      if ((u32)(where[k * T + m] & 0x7FFull) != o) SETBIT(dup_at, k * T + o);
+      if ((u32)(msg[k * T + o] & 0x7FFull) != m) {
+        bits |= MSIM_KAFKA_INCONSISTENT_OFFSETS;
+        if constexpr (EXPLAIN) { SETBIT(incons, k * T + o); atomicMin(&fdiff[k * T + o], (unsigned long long)((ord << 11) | m)); }
+      }
+      if ((u32)(where[k * T + m] & 0x7FFull) != o) {
+        SETBIT(dup_at, k * T + o);
+        if constexpr (EXPLAIN) atomicMin(&fdup[k * T + o], (unsigned long long)((ord << 11) | m));
+      }
     }
   };
 
@@ -160,9 +233,9 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
           if (o == 0x7FFu || k >= KEYS) { TO_HOST(); continue; }
           c_stable++;
           observe(sweep, k, o, m, (u64)idx << 17);
-          if (sweep == 0 && o < T) SETBIT(acked, k * T + o);
+          if (sweep == 0 && o < T) { SETBIT(acked, k * T + o); if constexpr (EXPLAIN) atomicMin(&fack[k * T + o], idx); }
         } else if (type == MSIM_T_FAIL && sweep == 0) {
-          if (k < KEYS && m < T) SETBIT(failed, k * T + m);
+          if (k < KEYS && m < T) { SETBIT(failed, k * T + m); if constexpr (EXPLAIN) atomicMin(&ffail[k * T + m], idx); }
           // (CLASSIFY: a message beyond the tables is never the last one of a cell: such an observation is the host's)
           else if constexpr (!CLASSIFY) { if (k < KEYS && m < OFFS) TO_HOST(); }
         }
@@ -177,7 +250,10 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
           if (q + b.words > len) { TO_HOST(); break; }
           for (u32 e = 0; e < b.cnt; e++, ord++) {
             observe(sweep, b.k, b.o0 + e, block_msg(w + q, e), ord);
-            if (sweep == 0 && b.o0 + e < T) { SETBIT(polled, b.k * T + b.o0 + e); atomicMax(&top1[b.k], b.o0 + e + 1u); }
+            if (sweep == 0 && b.o0 + e < T) {
+              SETBIT(polled, b.k * T + b.o0 + e); atomicMax(&top1[b.k], b.o0 + e + 1u);
+              if constexpr (EXPLAIN) atomicMin(&fpoll[b.k * T + b.o0 + e], idx);
+            }
           }
           q += b.words;
         }
@@ -201,6 +277,20 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
       const bool pl = GETBIT(polled, i) != 0;
       if (GETBIT(acked, i) && !pl) { if (o + 1u < top1[k]) { lost++; finding(MSIM_KAFKA_LOST_WRITE); } else unobs++; }
       if (pl) { const Cell c = msg[i]; if (c != UNSEEN && GETBIT(failed, k * T + (CLASSIFY ? (u32)(c & 0x7FFull) : (u32)c))) finding(MSIM_KAFKA_ABORTED_READ); }
+      if constexpr (EXPLAIN) {
+        const u64 last = msg[i];
+        const u32 lm = (u32)(last & 0x7FFull);
+        if (GETBIT(acked, i) && !pl && o + 1u < top1[k]) {
+          const u32 top = top1[k] - 1u, writer = fack[i];
+          emit(MSIM_KAFKA_LOST_WRITE, k, o, (r[writer].w >> 6) & 0x7FFu, top, writer, fpoll[k * T + top]);
+        }
+        if (GETBIT(incons, i)) { const u64 d = fdiff[i]; emit(MSIM_KAFKA_INCONSISTENT_OFFSETS, k, o, lm, (u32)(d & 0x7FFull), row_of(d), row_of(last)); }
+        if (GETBIT(dup_at, i)) {
+          const u64 d = fdup[i], home = where[k * T + (u32)(d & 0x7FFull)];
+          emit(MSIM_KAFKA_DUPLICATE, k, o, (u32)(d & 0x7FFull), (u32)(home & 0x7FFull), row_of(home), row_of(d));
+        }
+        if (pl && last != UNSEEN && GETBIT(failed, k * T + lm)) emit(MSIM_KAFKA_ABORTED_READ, k, o, lm, 0u, ffail[k * T + lm], fpoll[i]);
+      }
     }
     if constexpr (CLASSIFY) {
       u32 dups = 0;
@@ -226,7 +316,7 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
       todo &= todo - 1;
       const u32 rz = wv_rl(row.z, j), rw = wv_rl(row.w, j), ry = wv_rl(row.y, j);
       const u32 type = rz & 3u, f = (rz >> 2) & 31u, proc = rz >> 12;
-      u32 *const s = wst + (proc % C) * WST;
+      u32 *const s = wst + (proc % C) * WS;   // EXPLAIN: [17 + k] / [25 + k] the row that left s[k] / s[8 + k]
       const u32 cur = s[16];
       if (cur != proc) {   // the worker's next process starts with nothing remembered; a process that RETURNS is not a worker's stream
         if (cur != EMPTY && proc < cur) TO_HOST();
@@ -239,7 +329,15 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
       if (f == MSIM_F_SEND) {
         const u32 k = rw & 63u, o = rw >> 17;
         if (k >= KEYS || o >= OFFS) continue;
-        if (lane == k) { const u32 last = s[8 + k]; if (last != EMPTY && o <= last) finding(MSIM_KAFKA_NONMONOTONIC_SEND); s[8 + k] = o; }
+        if (lane == k) {
+          const u32 last = s[8 + k];
+          if (last != EMPTY && o <= last) {
+            finding(MSIM_KAFKA_NONMONOTONIC_SEND);
+            if constexpr (EXPLAIN) emit(MSIM_KAFKA_NONMONOTONIC_SEND, k, o, (rw >> 6) & 0x7FFu, last, s[25 + k], base + j);
+          }
+          s[8 + k] = o;
+          if constexpr (EXPLAIN) s[25 + k] = base + j;
+        }
         continue;
       }
       const u32 len = ry >> 16;
@@ -251,16 +349,34 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
         const PollBlock b = poll_block(q < STAGE ? stg[q] : pay[rw + q]);
         q++;
         if (q + b.words > len) break;
+        [[maybe_unused]] const u32 q0 = q;   // the block's first message word
         q += b.words;
         if (!b.cnt) continue;
         // a block holds one run o0, o0 + 1, ...: it must start above the worker's last offset of the key and skip nothing known
         if (lane == b.k) {
           const u32 lp = s[b.k];
-          if (lp != EMPTY) {
-            if (b.o0 <= lp) finding(internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL);
-            else for (u32 o = lp + 1; o < b.o0; o++) if (o < T && msg[b.k * T + o] != UNSEEN) { finding(internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP); break; }
+          if constexpr (!EXPLAIN) {
+            if (lp != EMPTY) {
+              if (b.o0 <= lp) finding(internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL);
+              else for (u32 o = lp + 1; o < b.o0; o++) if (o < T && msg[b.k * T + o] != UNSEEN) { finding(internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP); break; }
+            }
+          } else if (lp != EMPTY) {
+            if (b.o0 <= lp) {
+              const u32 bit = internal ? MSIM_KAFKA_INT_NONMONOTONIC_POLL : MSIM_KAFKA_NONMONOTONIC_POLL;
+              finding(bit);
+              emit(bit, b.k, b.o0, (q0 < STAGE ? stg[q0] : pay[rw + q0]) & 0xFFFFu, lp, s[17 + b.k], base + j);
+            } else {
+              u32 skipped = 0;   // the known offsets strictly between (the offsets beyond the tables were never observed)
+              for (u32 o = lp + 1; o < b.o0 && o < T; o++) skipped += msg[b.k * T + o] != UNSEEN;
+              if (skipped) {
+                const u32 bit = internal ? MSIM_KAFKA_INT_POLL_SKIP : MSIM_KAFKA_POLL_SKIP;
+                finding(bit);
+                emit(bit, b.k, b.o0, skipped, lp, s[17 + b.k], base + j);
+              }
+            }
           }
           s[b.k] = b.o0 + b.cnt - 1u;
+          if constexpr (EXPLAIN) s[17 + b.k] = base + j;
           internal = true;
         }
       }
@@ -279,6 +395,39 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
     }
     p.out[hist] = res;
   }
+  if constexpr (EXPLAIN) {
+    // the tables and the header are dead behind this barrier: the findings come from the workspace into LDS, are sorted there and written
+    const u32 handed = hdr[0], n_found = hdr[11], n_kind = tid < 10u ? hdr[16u + tid] : 0u;
+    __syncthreads();
+    if (handed) return;   // (the record says NEEDS_HOST: the host walk writes this history's header and findings)
+    u32 n2 = 1;
+    while (n2 < n_found) n2 <<= 1;   // (n_found <= FX_MAX, else handed)
+    uint4 *const srt = reinterpret_cast<uint4 *>(smem);
+    const uint4 *const w = x.ws + (size_t)slot * FX_MAX * 2u;
+    for (u32 i = tid; i < n2; i += NT) {
+      const bool real = i < n_found;
+      srt[2 * i] = real ? w[2 * i] : make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
+      srt[2 * i + 1] = real ? w[2 * i + 1] : make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
+    }
+    __syncthreads();
+    for (u32 k = 2; k <= n2; k <<= 1)
+      for (u32 j = k >> 1; j; j >>= 1) {
+        for (u32 i = tid; i < n2; i += NT) {
+          const u32 l = i ^ j;
+          if (l > i) {
+            const uint4 a0 = srt[2 * i], a1 = srt[2 * i + 1], b0 = srt[2 * l], b1 = srt[2 * l + 1];
+            if (finding_before(b0, b1, a0, a1) == ((i & k) == 0)) { srt[2 * i] = b0; srt[2 * i + 1] = b1; srt[2 * l] = a0; srt[2 * l + 1] = a1; }
+          }
+        }
+        __syncthreads();
+      }
+    const u32 n_out = min(n_found, x.max_findings);
+    uint4 *const dst = reinterpret_cast<uint4 *>(x.findings + (size_t)hist * x.max_findings);
+    for (u32 i = tid; i < 2u * n_out; i += NT) dst[i] = srt[i];
+    u32 *const xh = reinterpret_cast<u32 *>(x.hdr + hist);
+    if (tid < 10u) xh[2u + tid] = n_kind;   // (count[9]: a history that does not decode is the host's)
+    if (tid == 0) { xh[0] = n_out; xh[1] = n_found > x.max_findings ? 1u : 0u; }
+  }
 #undef TO_HOST
 #undef SETBIT
 #undef GETBIT
@@ -286,7 +435,7 @@ __device__ __forceinline__ void kafka_body(const KCParams &p, const u32 hist, un
 
 __global__ void __launch_bounds__(NT) kafka_check_kernel(const KCParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  kafka_body<false>(p, blockIdx.x, smem);
+  kafka_body<0>(p, blockIdx.x, smem);
 }
 
 // the histories the clean pass could not prove clean: list[0] = how many, list[1 ..] = which (in no particular order)
@@ -297,7 +446,12 @@ __global__ void __launch_bounds__(256) kafka_todo_kernel(const msim_check_result
 
 __global__ void __launch_bounds__(NT) kafka_classify_kernel(const KCParams p, const u32 *list) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  kafka_body<true>(p, list[blockIdx.x], smem);
+  kafka_body<1>(p, list[blockIdx.x], smem);
+}
+
+__global__ void __launch_bounds__(NT) kafka_explain_kernel(const KCParams p, const u32 *list, const KXOut x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  kafka_body<2>(p, list[blockIdx.x], smem, x, blockIdx.x);
 }
 
 // The highest offset / message value any :ok send or poll of the launch names: sizes the tables (most tests use a fraction of what
@@ -328,9 +482,14 @@ __global__ void __launch_bounds__(NT) kafka_bound_kernel(const KCParams p, u32 *
   if ((tid & 63u) == 0 && hi) atomicMax(bound, hi);
 }
 
-// classify: what kafka_check_kernel cannot prove clean goes to kafka_classify_kernel first, and only what THAT hands over to the host
+// the caller's arrays of an explaining run: a header per history, max_findings records per history
+struct KafkaExplainRun { msim_kafka_explain *hdr; msim_kafka_finding *findings; u32 max_findings; };
+
+// classify: what kafka_check_kernel cannot prove clean goes to kafka_classify_kernel first, and only what THAT hands over to the host.
+// xr: to kafka_explain_kernel instead, which also writes its findings; what it hands over is explained by the host walk.  A launch whose
+// histories are all proved clean runs the two kernels of the plain check and nothing else.
 int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-                  bool classify = false) {
+                  bool classify = false, const KafkaExplainRun *xr = nullptr) {
   const PassTimer tm(ctx);
   u32 h_bound = 0;
   {   // tables no larger than the launch's histories need (kp.T: what the configuration / the checker's own bound allows)
@@ -350,7 +509,41 @@ int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst
   hipLaunchKernelGGL(kafka_check_kernel, dim3(n), dim3(NT), lds, st, kp);
   MSIM_HIP_TRY(ctx, hipGetLastError());
   u32 n_unclean = 0;
-  if (classify) {   // the histories not proved clean, listed on the device, each to a workgroup of kafka_classify_kernel
+  if (xr) {
+    std::memset(xr->hdr, 0, (size_t)n * sizeof(msim_kafka_explain));
+    const size_t f_bytes = (size_t)n * xr->max_findings * sizeof(msim_kafka_finding);
+    if (f_bytes) std::memset(xr->findings, 0, f_bytes);
+    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, kp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    n_unclean = (u32)needs(h_out, n, [](u32 valid) { return valid == NEEDS_HOST; }).size();
+    if (n_unclean) {
+      DevBuf list, d_hdr, d_find, ws;
+      const u32 chunk = chunk_for(n_unclean, (uint64_t)FX_MAX * sizeof(msim_kafka_finding), 64ull << 20, msim_dev_flags(ctx));
+      MSIM_HIP_TRY(ctx, list.alloc(((size_t)n + 1) * 4));
+      MSIM_HIP_TRY(ctx, d_hdr.alloc((size_t)n * sizeof(msim_kafka_explain)));
+      MSIM_HIP_TRY(ctx, d_find.alloc(std::max(f_bytes, sizeof(msim_kafka_finding))));
+      MSIM_HIP_TRY(ctx, ws.alloc((size_t)chunk * FX_MAX * sizeof(msim_kafka_finding)));
+      u32 *const d_list = list.get<u32>();
+      MSIM_HIP_TRY(ctx, hipMemsetAsync(d_list, 0, 4, st));
+      MSIM_HIP_TRY(ctx, hipMemsetAsync(d_hdr.get<void>(), 0, (size_t)n * sizeof(msim_kafka_explain), st));
+      if (f_bytes) MSIM_HIP_TRY(ctx, hipMemsetAsync(d_find.get<void>(), 0, f_bytes, st));
+      hipLaunchKernelGGL(kafka_todo_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, kp.out, n, d_list);
+      MSIM_HIP_TRY(ctx, hipGetLastError());
+      KCParams cp = kp;   // tables for what the launch names, up to what LDS holds beside the explaining cells
+      cp.T = std::min(TX_MAX, std::max(32u, (h_bound + 1u + 31u) & ~31u));
+      const size_t xlds = kafka_explain_lds_bytes(cp.T);
+      if (xlds > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_explain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+      const KXOut x{d_hdr.get<msim_kafka_explain>(), d_find.get<msim_kafka_finding>(), xr->max_findings, ws.get<uint4>()};
+      hipError_t err;
+      for_chunks(n_unclean, chunk, &err, [&](u32 first, u32 count) {   // (one workspace: the chunks follow one another on the stream)
+        hipLaunchKernelGGL(kafka_explain_kernel, dim3(count), dim3(NT), xlds, st, cp, d_list + 1 + first, x);
+      });
+      MSIM_HIP_TRY(ctx, err);
+      MSIM_HIP_TRY(ctx, hipMemcpyAsync(xr->hdr, d_hdr.get<void>(), (size_t)n * sizeof(msim_kafka_explain), hipMemcpyDeviceToHost, st));
+      if (f_bytes) MSIM_HIP_TRY(ctx, hipMemcpyAsync(xr->findings, d_find.get<void>(), f_bytes, hipMemcpyDeviceToHost, st));
+      MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));   // (the buffers are freed with this block)
+    }
+  } else if (classify) {   // the histories not proved clean, listed on the device, each to a workgroup of kafka_classify_kernel
     DevBuf list;
     MSIM_HIP_TRY(ctx, list.alloc(((size_t)n + 1) * 4));
     u32 *const d_list = list.get<u32>();
@@ -373,13 +566,14 @@ int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   const std::vector<u32> todo = needs(h_out, n, [](u32 valid) { return valid == NEEDS_HOST; });
   if (tm.trace) {
-    if (classify) std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %u of %u histories classified on the device, %zu of those for the host\n",
-                               lds, tm.ms(), n_unclean, n, todo.size());
+    if (classify || xr) std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %u of %u histories %s on the device, %zu of those for the host\n",
+                                     lds, tm.ms(), n_unclean, n, xr ? "explained" : "classified", todo.size());
     else std::fprintf(stderr, "[kafka-check] device pass (%zu B of LDS per history): %.2f ms, %zu of %u histories for the host\n", lds, tm.ms(), todo.size(), n);
   }
   if (!todo.empty()) {
     const int rc = hand_off(ctx, source_of(kp, hmeta), n, todo, h_out, kp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
-      msim_kafka_check_instance_host(rows, nr, pay, nw, flags, &h_out[i]);
+      if (xr) msim_kafka_explain_instance_host(rows, nr, pay, nw, flags, &h_out[i], &xr->hdr[i], xr->findings + (size_t)i * xr->max_findings, xr->max_findings);
+      else msim_kafka_check_instance_host(rows, nr, pay, nw, flags, &h_out[i]);
     });
     if (rc != MSIM_OK) return rc;
     if (tm.trace) std::fprintf(stderr, "[kafka-check] host checker on those: done at %.2f ms\n", tm.ms());
@@ -393,11 +587,11 @@ u32 kafka_table_entries(u32 bound) { const u32 t = (bound + 31u) & ~31u; return 
 
 }  // namespace
 
-// msim_check for kafka: the histories of the last run, where they lie in HBM.
-int msim_check_kafka_device(msim_ctx *ctx) {
+// msim_check for kafka: the histories of the last run, where they lie in HBM (xr: msim_explain_kafka's arrays).
+static int kafka_device(msim_ctx *ctx, const KafkaExplainRun *xr) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
-  if (ctx->cfg.concurrency == 0 || ctx->cfg.concurrency > CMAX) return msim_check_kafka_host(ctx);
+  if (ctx->cfg.concurrency == 0 || ctx->cfg.concurrency > CMAX) return xr ? msim_explain_kafka_host(ctx, xr->hdr, xr->findings, xr->max_findings) : msim_check_kafka_host(ctx);
   std::chrono::steady_clock::time_point t0;
   std::vector<msim_inst_meta> hm;
   if (int rc = begin_check(ctx, &t0, &hm)) return rc;
@@ -410,16 +604,29 @@ int msim_check_kafka_device(msim_ctx *ctx) {
   kp.T = kafka_table_entries(ctx->cfg.max_writes_per_key + 8u);
   kp.C = ctx->cfg.concurrency;
   u32 redone = 0;
-  int rc = kafka_dev_run(ctx, kp, n, &hm, ctx->h_check, ctx->stream, &redone, ctx->check_classify);
+  int rc = kafka_dev_run(ctx, kp, n, &hm, ctx->h_check, ctx->stream, &redone, ctx->check_classify, xr);
   if (rc != MSIM_OK) return rc;
   finish_check(ctx, t0, redone);
   return MSIM_OK;
+}
+int msim_check_kafka_device(msim_ctx *ctx) { return kafka_device(ctx, nullptr); }
+
+// msim_check that also explains.  Towards the context it is msim_check: the records, check_ms and the count of hand-overs are left as
+// msim_check leaves them; where msim_check keeps to the host cores (a concurrency beyond 64, developer flag 0x800) the walk explains.
+extern "C" int msim_explain_kafka(msim_ctx *ctx, msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings, uint32_t n_out) {
+  if (!ctx || !hdr || (!findings && max_findings)) return MSIM_E_INVALID;
+  if (ctx->cfg.workload != MSIM_WL_KAFKA) { ctx->err = "msim_explain_kafka: not a kafka context"; return MSIM_E_UNSUPPORTED; }
+  if (!ctx->ran) { ctx->err = "msim_explain_kafka before msim_run"; return MSIM_E_RANGE; }
+  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_kafka: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (msim_dev_flags(ctx) & 0x800u) return msim_explain_kafka_host(ctx, hdr, findings, max_findings);
+  const KafkaExplainRun xr{hdr, findings, max_findings};
+  return kafka_device(ctx, &xr);
 }
 
 // Checks `n_histories` kafka histories given on the host (rows / payload words of history i at row_offsets[i] / payload_offsets[i]) as
 // msim_check does for the histories of a run; `concurrency` = the worker threads of the test (process mod concurrency).
 static int kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
-                       uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host, bool classify) {
+                       uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host, bool classify, const KafkaExplainRun *xr = nullptr) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || concurrency == 0 || concurrency > CMAX) return MSIM_E_INVALID;
   if (payload_offsets[n_histories] != 0 && !payload) return MSIM_E_INVALID;   // (as msim_check_kafka_rows: payload words announced, none given)
   if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
@@ -433,7 +640,7 @@ static int kafka_batch(int device, const msim_op *rows, const uint64_t *row_offs
   kp.rows = b.rows.get<msim_op>(); kp.payload = b.pay.get<u32>(); kp.row_off = b.row_off.get<uint64_t>(); kp.pay_off = b.pay_off.get<uint64_t>();
   kp.out = d_out.get<msim_check_result>();
   kp.T = OFFS; kp.C = concurrency;
-  return kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify);
+  return kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify, xr);
 }
 
 extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
@@ -446,4 +653,15 @@ extern "C" int msim_check_kafka_batch(int device, const msim_op *rows, const uin
 extern "C" int msim_classify_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                                          uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host) {
   return kafka_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, concurrency, out, n_host, true);
+}
+
+// As msim_classify_kafka_batch, with kafka_explain_kernel in place of kafka_classify_kernel: hdr[i] and history i's findings at
+// findings + i * max_findings (include/maelsim.h, "kafka: the explanation of a verdict"); that kernel's hand-overs (its header comment)
+// are explained by the host walk and counted in *n_host.
+extern "C" int msim_explain_kafka_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
+                                        uint32_t n_histories, uint32_t concurrency, msim_check_result *out, msim_kafka_explain *hdr,
+                                        msim_kafka_finding *findings, uint32_t max_findings, uint32_t *n_host) {
+  if (!hdr || (!findings && max_findings)) return MSIM_E_INVALID;
+  const KafkaExplainRun xr{hdr, findings, max_findings};
+  return kafka_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, concurrency, out, n_host, true, &xr);
 }

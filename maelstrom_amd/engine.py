@@ -17,6 +17,7 @@ from . import _abi as A
     np.dtype(s) for s in (A.Op, A.NetStats, A.Event, A.CheckResult, A.LinKeyResult, A.CycleResult, A.CycleStep, A.SetElement, A.SetExplain,
                           A.LatencyDist, A.FStats, A.PerfResult))
 # msim_inst_meta stays written out: its callers know the header's reserved[3] as three words r0, r1, r2 (the oracle's dtype has the same).
+KAFKA_FINDING_DT, KAFKA_EXPLAIN_DT = np.dtype(A.KafkaFinding), np.dtype(A.KafkaExplain)   # (A.KAFKA_EXPLAIN_RECORDS)
 META_DT = np.dtype([(n, "<u4") for n in ("n_rows", "n_payload_words", "flags", "n_rounds", "n_events", "r0", "r1", "r2")])
 PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
@@ -224,6 +225,17 @@ class Engine:
         self._chk(self.lib.msim_explain_set_full(self._ctx, hdr.ctypes.data, els.ctypes.data, max_elements, self.n), "msim_explain_set_full")
         res = self.check_results()
         return [(res[i], hdr[i], els[i, :_n_set_records(hdr[i])].copy()) for i in range(self.n)]
+
+    def explain_kafka(self, max_findings=64):
+        """kafka: check(classify=True) that also explains (msim_explain_kafka): per history of the last run (CHECK_DT record —
+        check_results() holds the same afterwards —, KAFKA_EXPLAIN_DT header, KAFKA_FINDING_DT records: one witness per anomaly in the
+        order include/maelsim.h defines; see kafka_findings), found on the device.  A history with more findings than max_findings has
+        header["truncated"] set; header["count"] is always the true number per anomaly."""
+        hdr = np.zeros(max(self.n, 1), dtype=KAFKA_EXPLAIN_DT)
+        fs = np.zeros((max(self.n, 1), max(max_findings, 1)), dtype=KAFKA_FINDING_DT)
+        self._chk(self.lib.msim_explain_kafka(self._ctx, hdr.ctypes.data, fs.ctypes.data, max_findings, self.n), "msim_explain_kafka")
+        res = self.check_results()
+        return [(res[i], hdr[i], fs[i, :int(hdr[i]["n_findings"])].copy()) for i in range(self.n)]
 
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
@@ -1077,6 +1089,56 @@ def classify_kafka_batch(histories, concurrency, device=0):
     anomaly bits and counts.  Only what does not decode, a process that returns after a later one of its worker, and offsets or messages
     from 1152 on go to the host checker.  Returns (CHECK_DT records, how many histories went to the host).  See kafka_anomaly_census."""
     return check_kafka_batch(histories, concurrency, device, _entry="msim_classify_kafka_batch")
+
+
+def explain_kafka_history(rows, payload, max_findings=64):
+    """The explaining kafka check of one history on the host (msim_explain_kafka_rows; needs no device) -> (CHECK_DT record — what
+    msim_check_kafka_rows writes —, KAFKA_EXPLAIN_DT header, KAFKA_FINDING_DT records: one witness per anomaly as include/maelsim.h
+    defines them, in its order).  The whole zero-padded slab of max_findings records is the returned array's `.base`."""
+    rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    out = np.zeros(1, dtype=CHECK_DT)
+    hdr = np.zeros(1, dtype=KAFKA_EXPLAIN_DT)
+    slab = np.zeros(max(max_findings, 1), dtype=KAFKA_FINDING_DT)
+    _call("msim_explain_kafka_rows", rows.ctypes.data, len(rows), payload.ctypes.data, len(payload), out.ctypes.data_as(C.POINTER(A.CheckResult)),
+          hdr.ctypes.data, slab.ctypes.data, max_findings)
+    return out[0], hdr[0], slab[:int(hdr[0]["n_findings"])]
+
+
+def explain_kafka_batch(histories, concurrency, device=0, max_findings=64):
+    """kafka: classify_kafka_batch with the explanation written on the device (msim_explain_kafka_batch, kafka_explain_kernel).  Returns
+    (CHECK_DT records, KAFKA_EXPLAIN_DT headers, a list of KAFKA_FINDING_DT arrays — the records written per history, whose `.slab` is
+    the whole zero-padded (histories, max_findings) array —, how many histories went to the host walk: the three cases of
+    classify_kafka_batch, offsets or messages from A.KAFKA_EXPLAIN_TABLE_BOUND on, more than A.KAFKA_EXPLAIN_MAX_FINDINGS findings)."""
+    rows, ro, pay, po = _offsets_form(histories)
+    n = len(ro) - 1
+    out = np.zeros(n, dtype=CHECK_DT)
+    hdr = np.zeros(n, dtype=KAFKA_EXPLAIN_DT)
+    slab = np.zeros((n, max(max_findings, 1)), dtype=KAFKA_FINDING_DT)
+    n_host = C.c_uint32()
+    _call("msim_explain_kafka_batch", device, rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, n, concurrency, out.ctypes.data,
+          hdr.ctypes.data, slab.ctypes.data, max_findings, C.byref(n_host))
+    fs = _StepLists(slab[i, :int(hdr[i]["n_findings"])].copy() for i in range(n))
+    fs.slab = slab[:, :max_findings]
+    return out, hdr, fs, n_host.value
+
+
+def kafka_findings(hdr, findings):
+    """One history's findings named (pure formatting): a list of {"anomaly": its name in A.KAFKA_ANOMALIES, "key", "offset", "value",
+    "other", "row-a", "row-b" (None = none)}; the polls' skips and nonmonotonic steps also carry jepsen's "delta" = offset - other, a
+    skip its "skipped-count" = value (workload/kafka.clj:42-60).  A truncated header ends the list with {"truncated": the true counts by name}."""
+    out = []
+    for f in findings:
+        bit = int(f["anomaly"])
+        d = {"anomaly": A.KAFKA_ANOMALIES[bit], "key": int(f["key"]), "offset": int(f["offset"]), "value": int(f["value"]), "other": int(f["other"]),
+             "row-a": None if int(f["row_a"]) == A.NO_VALUE else int(f["row_a"]), "row-b": None if int(f["row_b"]) == A.NO_VALUE else int(f["row_b"])}
+        if bit & (2 | 8 | 16 | 32):
+            d["delta"] = d["offset"] - d["other"]
+        if bit & (8 | 32):
+            d["skipped-count"] = d["value"]
+        out.append(d)
+    if int(hdr["truncated"]):
+        out.append({"truncated": {name: int(hdr["count"][b.bit_length() - 1]) for b, name in A.KAFKA_ANOMALIES.items() if int(hdr["count"][b.bit_length() - 1])}})
+    return out
 
 
 def kafka_anomaly_census(results):
