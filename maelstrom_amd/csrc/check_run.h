@@ -1,8 +1,9 @@
-// check_run.h — the host side the device checkers share (lin / txn / rw / kafka / pn / unique / perf _check_dev.hip): device buffers
-// that free themselves, the grow-only workspace, a caller's histories uploaded, the chunked launch loop, the hand-off of what the
-// device leaves to the host checkers, the frame of msim_check_*_device.  Host only: nothing here is seen by a kernel (the device side
-// is check_dev.h).  A new checker mode supplies its kernel launch and its host callable; docs/KERNELS.md, "the host side of the device
-// checkers".
+// check_run.h — the host side the checkers share (checker.hip, lin / txn / rw / kafka / pn / unique / perf _check_dev.hip, and the host
+// checkers lin / txn / kafka / pn _check.cpp): device buffers that free themselves, the grow-only workspace, a caller's histories
+// uploaded and the frame of a batch entry, the chunked pass, the slabs of an explanation, the hand-off of what the device leaves to the
+// host checkers, the checker on the host cores, the frames of msim_check_*_device and msim_explain_*.  Host only: nothing here is seen
+// by a kernel (the device side is check_dev.h).  A new checker mode supplies its kernel launch and its host callable; docs/KERNELS.md,
+// "the host side of the device checkers".
 #ifndef MSIM_CHECK_RUN_H
 #define MSIM_CHECK_RUN_H
 
@@ -70,15 +71,39 @@ struct OffsetsBatch {
 };
 
 // A caller's histories in the slab layout, on the device: history i in rows + i * max_rows, n_rows[i] of them used; the
-// msim_inst_meta records of a run made up for them.
+// msim_inst_meta records of a run made up for them.  With max_pay, the payload words alike: history i's in payload + i * max_pay.
 struct SlabBatch {
-  DevBuf rows, meta;
+  DevBuf rows, meta, pay;
   int upload(msim_ctx *ctx, const msim_op *h_rows, const u32 *n_rows, u32 max_rows, u32 n) {   // MSIM_E_RANGE: n_rows[i] > max_rows
     std::vector<msim_inst_meta> hm(n);
     for (u32 i = 0; i < n; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
     MSIM_HIP_TRY(ctx, rows.upload(h_rows, (size_t)n * max_rows * sizeof(msim_op)));
     MSIM_HIP_TRY(ctx, meta.upload(hm.data(), (size_t)n * sizeof(msim_inst_meta)));
     return MSIM_OK;
+  }
+  int upload_payload(msim_ctx *ctx, const u32 *payload, u32 max_pay, u32 n) {   // (max_pay 0: an allocation all the same, the kernels are handed a pointer)
+    MSIM_HIP_TRY(ctx, pay.upload(payload, (size_t)n * max_pay * 4));
+    return MSIM_OK;
+  }
+};
+
+// The frame of a batch entry, behind its argument checks: the stand-in context, the caller's histories on the device (B: OffsetsBatch
+// or SlabBatch; begin passes B::upload its arguments) and the slab of n records of `rec_bytes` the kernels write.
+template <class B> struct BatchFrame {
+  BatchCtx ctx;
+  B b;
+  DevBuf d_out;
+  explicit BatchFrame(int device) : ctx(device) {}
+  template <class... A> int begin(u32 n, size_t rec_bytes, const A &...upload_args) {
+    if (hipSetDevice(ctx.device) != hipSuccess) return MSIM_E_HIP;
+    if (int rc = b.upload(&ctx, upload_args...)) return rc;
+    MSIM_HIP_TRY(&ctx, d_out.alloc((size_t)n * rec_bytes));
+    return MSIM_OK;
+  }
+  // (of a checker's *Params over an OffsetsBatch with payload: they name these alike)
+  template <class P> void bind(P &p) const {
+    p.rows = b.rows.template get<msim_op>(); p.payload = b.pay.template get<u32>(); p.row_off = b.row_off.template get<uint64_t>(); p.pay_off = b.pay_off.template get<uint64_t>();
+    p.out = d_out.get<msim_check_result>();
   }
 };
 
@@ -174,72 +199,83 @@ static inline int hand_off(msim_ctx *ctx, const HistorySource &s, u32 n, const s
   return MSIM_OK;
 }
 
-// The witness cycles of an explaining rw / txn check: the two device slabs (a cycle record, max_steps steps per history), cleared on the
-// stream before the passes and copied to the caller's arrays behind them.
-struct WitnessSlabs {
-  DevBuf c, s;
-  u32 n = 0, max_steps = 0;
-  msim_cycle_result *h_cycles = nullptr; msim_cycle_step *h_steps = nullptr;
-  int alloc(msim_ctx *ctx, u32 n_, u32 max_steps_, msim_cycle_result *cycles, msim_cycle_step *steps) {
-    n = n_; max_steps = max_steps_; h_cycles = cycles; h_steps = steps;
-    MSIM_HIP_TRY(ctx, c.alloc((size_t)n * sizeof(msim_cycle_result)));
-    MSIM_HIP_TRY(ctx, s.alloc((size_t)n * max_steps * sizeof(msim_cycle_step)));
+// The explanation of an explaining check: an optional header record per history (Hdr; void: records only, lin-kv's keys) and max_k
+// records per history (Rec) in two device slabs, cleared on the stream before the kernels that fill them and copied to the caller's
+// arrays behind them.  A max_k of 0 keeps one record allocated (the kernels are handed a pointer) and neither clears nor copies it.
+template <class T> struct SizeOr0 { static constexpr size_t value = sizeof(T); };
+template <> struct SizeOr0<void> { static constexpr size_t value = 0; };
+template <class Hdr, class Rec> struct ExplainSlabs {
+  static constexpr size_t hdr_size = SizeOr0<Hdr>::value;
+  DevBuf h, r;
+  u32 n = 0, max_k = 0;
+  Hdr *h_hdr = nullptr; Rec *h_rec = nullptr;   // the caller's arrays
+  size_t hdr_bytes() const { return (size_t)n * hdr_size; }
+  size_t rec_bytes() const { return (size_t)n * max_k * sizeof(Rec); }
+  int alloc(msim_ctx *ctx, u32 n_, u32 max_k_, Hdr *hdr, Rec *rec) {
+    n = n_; max_k = max_k_; h_hdr = hdr; h_rec = rec;
+    if (hdr_bytes()) MSIM_HIP_TRY(ctx, h.alloc(hdr_bytes()));
+    MSIM_HIP_TRY(ctx, r.alloc(std::max(rec_bytes(), sizeof(Rec))));
     return MSIM_OK;
   }
-  template <class P> void bind(P &p) const { p.cycles = c.get<msim_cycle_result>(); p.steps = s.get<msim_cycle_step>(); p.max_steps = max_steps; }
+  Hdr *hdr() const { return h.get<Hdr>(); }   // on the device
+  Rec *rec() const { return r.get<Rec>(); }
+  Hdr *hdr(u32 i) const { return h_hdr + i; }   // history i's, in the caller's arrays
+  Rec *rec(u32 i) const { return h_rec + (size_t)i * max_k; }
   int clear(msim_ctx *ctx, hipStream_t st) {
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(c.get<void>(), 0, (size_t)n * sizeof(msim_cycle_result), st));
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(s.get<void>(), 0, (size_t)n * max_steps * sizeof(msim_cycle_step), st));
+    if (hdr_bytes()) MSIM_HIP_TRY(ctx, hipMemsetAsync(h.get<void>(), 0, hdr_bytes(), st));
+    if (rec_bytes()) MSIM_HIP_TRY(ctx, hipMemsetAsync(r.get<void>(), 0, rec_bytes(), st));
     return MSIM_OK;
   }
   int fetch(msim_ctx *ctx, hipStream_t st) {
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_cycles, c.get<void>(), (size_t)n * sizeof(msim_cycle_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_steps, s.get<void>(), (size_t)n * max_steps * sizeof(msim_cycle_step), hipMemcpyDeviceToHost, st));
+    if (hdr_bytes()) MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_hdr, h.get<void>(), hdr_bytes(), hipMemcpyDeviceToHost, st));
+    if (rec_bytes()) MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_rec, r.get<void>(), rec_bytes(), hipMemcpyDeviceToHost, st));
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
     return MSIM_OK;
   }
 };
 
-// The explanation of an explaining set-full check: the two device slabs (a header, max_elements element records per history), cleared on
-// the stream before the kernel and copied to the caller's arrays behind it.
-struct SetExplainSlabs {
-  DevBuf h, e;
-  u32 n = 0, max_elements = 0;
-  msim_set_explain *h_hdr = nullptr; msim_set_element *h_elements = nullptr;
-  size_t el_bytes() const { return (size_t)n * max_elements * sizeof(msim_set_element); }
-  int alloc(msim_ctx *ctx, u32 n_, u32 max_elements_, msim_set_explain *hdr, msim_set_element *elements) {
-    n = n_; max_elements = max_elements_; h_hdr = hdr; h_elements = elements;
-    MSIM_HIP_TRY(ctx, h.alloc((size_t)n * sizeof(msim_set_explain)));
-    MSIM_HIP_TRY(ctx, e.alloc(std::max(el_bytes(), sizeof(msim_set_element))));
-    return MSIM_OK;
-  }
-  template <class X> void bind(X &x) const { x.hdr = h.get<msim_set_explain>(); x.elements = e.get<msim_set_element>(); x.max_elements = max_elements; }
-  int clear(msim_ctx *ctx, hipStream_t st) {
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(h.get<void>(), 0, (size_t)n * sizeof(msim_set_explain), st));
-    if (el_bytes()) MSIM_HIP_TRY(ctx, hipMemsetAsync(e.get<void>(), 0, el_bytes(), st));
-    return MSIM_OK;
-  }
-  int fetch(msim_ctx *ctx, hipStream_t st) {
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_hdr, h.get<void>(), (size_t)n * sizeof(msim_set_explain), hipMemcpyDeviceToHost, st));
-    if (el_bytes()) MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_elements, e.get<void>(), el_bytes(), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MSIM_OK;
-  }
-};
+// the witness cycles of an explaining rw / txn check: a cycle record, max_steps steps per history
+typedef ExplainSlabs<msim_cycle_result, msim_cycle_step> CycleSlabs;
+template <class P> static inline void bind_cycles(P &p, const CycleSlabs &w) { p.cycles = w.hdr(); p.steps = w.rec(); p.max_steps = w.max_k; }
 
 // how rw_dev_run / txn_dev_run go beyond the clean passes: `full` the classification on the device; with `witness` its EXPLAIN kernel
 struct CycleMode {
   bool full = false;
-  WitnessSlabs *witness = nullptr;
+  CycleSlabs *witness = nullptr;
 };
+
+// One chunked pass over `m` histories — all of the launch, or those `list` names (m of them: the list goes to the device in front of the
+// workspace, rounded to 256 bytes) —, each with `bytes_per_history` of the grow-only workspace, as many per launch as `budget` holds:
+// launch(d_list, ws, first, count) for every chunk, then the n records of the launch to h_out, waited for.  Returns the launches made,
+// or an error (< 0).
+template <class F>
+static inline int chunked_pass(msim_ctx *ctx, u32 m, uint64_t bytes_per_history, uint64_t budget, const std::vector<u32> *list, void **ws_buf, size_t *ws_cap, F launch,
+                               const msim_check_result *d_out, msim_check_result *h_out, u32 n, hipStream_t st) {
+  const size_t list_bytes = list ? ((size_t)m * 4 + 255) & ~(size_t)255 : 0;
+  const u32 chunk = chunk_for(m, bytes_per_history, budget, msim_dev_flags(ctx));
+  if (int rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * bytes_per_history)) return rc;
+  if (list) MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, list->data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+  const u32 *const d_list = list ? static_cast<const u32 *>(*ws_buf) : nullptr;
+  void *const ws = static_cast<char *>(*ws_buf) + list_bytes;
+  hipError_t e;
+  const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) { launch(d_list, ws, first, count); });
+  MSIM_HIP_TRY(ctx, e);
+  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+  MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+  return (int)launches;
+}
 
 // The frame of msim_check_{rw,txn,kafka,pn}_device.  begin_check: the pinned records of the run anew; with `hm`, the meta records on the
 // host — behind the context's stream: the simulation may still be running (msim_run_async), the context's stream does not block against
 // the null stream, so the copy of the meta is ordered behind it here and by nothing else.  Returns in *t0 where check_ms starts.
+static inline int renew_h_check(msim_ctx *ctx) {
+  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
+  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)ctx->n_inst * sizeof(msim_check_result)));
+  return MSIM_OK;
+}
 static inline int begin_check(msim_ctx *ctx, std::chrono::steady_clock::time_point *t0, std::vector<msim_inst_meta> *hm) {
   const u32 n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
+  if (int rc = renew_h_check(ctx)) return rc;
   if (hm) MSIM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   *t0 = std::chrono::steady_clock::now();
   if (hm) { hm->resize(n); MSIM_HIP_TRY(ctx, hipMemcpy(hm->data(), ctx->d_meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost)); }
@@ -249,6 +285,49 @@ static inline void finish_check(msim_ctx *ctx, std::chrono::steady_clock::time_p
   ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->lin_host_rechecks = redone;
   ctx->checked = true; ctx->check_fetched = true;
+}
+
+// The checker on the host cores (msim_check under developer flag 0x800, and where a device checker does not take a configuration): the
+// histories of the last run fetched, analyse(state, i, rows, n_rows, payload, n_words, flags, &h_check[i]) for every history i on up to
+// msim_host_threads() threads that stride over them — `state` one make_state() per thread, made on the calling thread before the first
+// starts —, the records to d_check.  check_ms is all of it, the fetch included; lin_host_rechecks is the caller's.  times (may be null):
+// the fetch, the threads' work, their number.
+struct HostRunTimes { float fetch_ms = 0.f, work_ms = 0.f; unsigned threads = 0; };
+template <class M, class A> static inline int host_check_run(msim_ctx *ctx, M make_state, A analyse, HostRunTimes *times = nullptr) {
+  typedef std::chrono::duration<float, std::milli> ms;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = msim_fetch(ctx)) return rc;
+  const auto t1 = std::chrono::steady_clock::now();
+  const u32 n = ctx->n_inst;
+  if (int rc = renew_h_check(ctx)) return rc;
+  const unsigned nt = std::min<unsigned>(msim_host_threads(), n);
+  std::vector<decltype(make_state())> states;
+  for (unsigned t = 0; t < nt; t++) states.push_back(make_state());
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; t++)
+    th.emplace_back([&, t]() {
+      auto state = std::move(states[t]);   // (on this thread's stack: the threads' states do not share cache lines)
+      for (u32 i = t; i < n; i += nt) {
+        const msim_inst_meta &m = ctx->h_meta[i];
+        analyse(state, i,ctx->h_rows + ctx->h_row_off[i], m.n_rows, ctx->h_payload + ctx->h_pay_off[i], m.n_payload_words, m.flags, &ctx->h_check[i]);
+      }
+    });
+  for (auto &x : th) x.join();
+  const auto t2 = std::chrono::steady_clock::now();
+  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
+  ctx->checked = true; ctx->check_fetched = true;
+  ctx->check_ms = ms(std::chrono::steady_clock::now() - t0).count();
+  if (times) *times = HostRunTimes{ms(t1 - t0).count(), ms(t2 - t1).count(), nt};
+  return MSIM_OK;
+}
+
+// What the msim_explain_* entries of a run refuse alike, in this order: a context of another workload (`what`: "a lin-kv", ...), nothing
+// run yet, output arrays shorter than the run.  (Their null arguments differ and stay with each.)
+static inline int explain_refusal(msim_ctx *ctx, const char *entry, bool workload_ok, const char *what, u32 n_out) {
+  if (!workload_ok) { ctx->err = std::string(entry) + ": not " + what + " context"; return MSIM_E_UNSUPPORTED; }
+  if (!ctx->ran) { ctx->err = std::string(entry) + " before msim_run"; return MSIM_E_RANGE; }
+  if (n_out < ctx->n_inst) { ctx->err = std::string(entry) + ": output arrays shorter than the run"; return MSIM_E_RANGE; }
+  return MSIM_OK;
 }
 
 #endif

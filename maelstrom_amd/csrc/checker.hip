@@ -112,10 +112,12 @@ __global__ void __launch_bounds__(64) set_explain_kernel(const CParams p, const 
 #include "set_full_body.inc"
 }
 
-// LDS of one wavefront: three u16 indices per element (reused as one u32 latency per element), the valid bitmap over the read
-// ranks (read one word past the last chunk), the per-thread tables slot / first / slotv.  set_explain_kernel (off_lat given) keeps the
-// indices and has two u32 latencies per element behind them.
-static size_t check_lds_layout(CParams &cp, u32 *off_lat = nullptr) {
+// The launch's derived parameters and the LDS of one wavefront: three u16 indices per element (reused as one u32 latency per element),
+// the valid bitmap over the read ranks (read one word past the last chunk), the per-thread tables slot / first / slotv.
+// set_explain_kernel (off_lat given) keeps the indices and has two u32 latencies per element behind them.
+static size_t check_layout(CParams &cp, u32 *off_lat = nullptr) {
+  cp.max_reads = cp.max_rows / 2 + 1;  // every :ok read has its own :invoke row
+  cp.rcp_C = 1.0f / (float)cp.C;
   size_t lds = (size_t)cp.max_values * 3 * 2 < (size_t)cp.max_values * 4 ? (size_t)cp.max_values * 4 : (size_t)cp.max_values * 3 * 2;
   lds = (lds + 3) & ~(size_t)3;
   if (off_lat) { lds = ((size_t)cp.max_values * 3 * 2 + 3) & ~(size_t)3; *off_lat = (u32)lds; lds += (size_t)cp.max_values * 2 * 4; }
@@ -131,29 +133,36 @@ static const char *check_limits(u32 max_rows, u32 max_values, u32 concurrency) {
   return nullptr;
 }
 
-// one wavefront per history over n slabs; the caller owns the buffers and the stream
-static hipError_t check_dispatch(CParams &cp, u32 n, hipStream_t st) {
-  cp.max_reads = cp.max_rows / 2 + 1;  // every :ok read has its own :invoke row
-  cp.rcp_C = 1.0f / (float)cp.C;
-  const size_t lds = check_lds_layout(cp);
+// `kernel` (check_kernel over cp; set_explain_kernel over cp and x, whose header and element slabs the caller has cleared) with `lds`
+// bytes of check_layout, one wavefront per history over n slabs; the caller owns the buffers and the stream
+template <class K, class... A> static hipError_t check_dispatch(K kernel, size_t lds, u32 n, hipStream_t st, const A &...args) {
   if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&check_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(check_kernel, dim3(n), dim3(64), lds, st, cp);
+  hipLaunchKernelGGL(kernel, dim3(n), dim3(64), lds, st, args...);
   return hipGetLastError();
 }
-// the same for set_explain_kernel, which also writes x's header and element slabs (cleared by the caller)
-static hipError_t set_explain_dispatch(CParams &cp, SetExplainOut &x, u32 n, hipStream_t st) {
-  cp.max_reads = cp.max_rows / 2 + 1;
-  cp.rcp_C = 1.0f / (float)cp.C;
-  const size_t lds = check_lds_layout(cp, &x.off_lat);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&set_explain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(set_explain_kernel, dim3(n), dim3(64), lds, st, cp, x);
-  return hipGetLastError();
+
+// the parameters of a check over n slabs as a configuration lays them out (the slabs themselves, out and recs: the caller's)
+static CParams check_params(u32 workload, u32 concurrency, u32 max_rows, u32 max_pay, u32 max_values) {
+  CParams cp;
+  std::memset(&cp, 0, sizeof cp);
+  cp.max_rows = max_rows; cp.max_pay = max_pay; cp.max_values = max_values; cp.C = concurrency; cp.workload = workload;
+  return cp;
+}
+static CParams check_params(const msim_ctx *ctx) {
+  const msim_config &c = ctx->cfg;
+  CParams cp = check_params(c.workload, c.concurrency, c.max_rows, c.max_payload_words, c.max_values);
+  cp.rows = ctx->d_rows; cp.payload = ctx->d_payload; cp.meta = ctx->d_meta; cp.out = ctx->d_check;
+  return cp;
+}
+typedef ExplainSlabs<msim_set_explain, msim_set_element> SetSlabs;   // a header, max_elements element records per history
+static SetExplainOut set_explain_out(const SetSlabs &xs) {
+  SetExplainOut x;
+  std::memset(&x, 0, sizeof x);
+  x.hdr = xs.hdr(); x.elements = xs.rec(); x.max_elements = xs.max_k;
+  return x;
 }
 
 // d_check_scratch for n histories: the read records of every instance.  Frees and allocates when it has to grow — a hipFree waits for
@@ -174,16 +183,14 @@ int msim_check_reserve(msim_ctx *ctx, uint32_t n) {
 int msim_check_enqueue(msim_ctx *ctx, hipStream_t stream) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const msim_config &c = ctx->cfg;
-  CParams cp;
-  std::memset(&cp, 0, sizeof cp);
-  cp.rows = ctx->d_rows; cp.payload = ctx->d_payload; cp.meta = ctx->d_meta; cp.out = ctx->d_check;
-  cp.max_rows = c.max_rows; cp.max_pay = c.max_payload_words; cp.max_values = c.max_values; cp.C = c.concurrency; cp.workload = c.workload;
+  CParams cp = check_params(ctx);
   if (const char *why = check_limits(c.max_rows, c.max_values, c.concurrency)) { ctx->err = why; return MSIM_E_UNSUPPORTED; }
   const int rc = msim_check_reserve(ctx, ctx->n_inst);   // (run_impl has sized it already where the check follows its simulation)
   if (rc != MSIM_OK) return rc;
   cp.recs = static_cast<u32 *>(ctx->d_check_scratch);
+  const size_t lds = check_layout(cp);
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, stream));
-  MSIM_HIP_TRY(ctx, check_dispatch(cp, ctx->n_inst, stream));
+  MSIM_HIP_TRY(ctx, check_dispatch(check_kernel, lds, ctx->n_inst, stream, cp));
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, stream));
   return MSIM_OK;
 }
@@ -197,6 +204,21 @@ int msim_check_wait(msim_ctx *ctx) {
   return MSIM_OK;
 }
 
+// What msim_check and msim_explain_set_full do first: the check run_impl queued behind the simulation is taken and waited for (1: its
+// records are in d_check; < 0: the wait failed); with nothing queued (0) a launch on the context's own stream arms the context, so that
+// its next launches queue theirs.
+int msim_check_take_or_arm(msim_ctx *ctx) {
+  const uint32_t flags = msim_dev_flags(ctx);
+  if (ctx->check_queued) {
+    ctx->check_queued = false;
+    if (flags & 0x1000u) std::fprintf(stderr, "[check] taken %u\n", ctx->n_inst);
+    const int rc = msim_check_wait(ctx);
+    return rc != MSIM_OK ? rc : 1;
+  }
+  if (ctx->ran_own_stream && !(flags & 0x40000u)) ctx->check_armed = true;
+  return 0;
+}
+
 int msim_check_launch(msim_ctx *ctx) {
   const int rc = msim_check_enqueue(ctx, ctx->stream);
   return rc != MSIM_OK ? rc : msim_check_wait(ctx);
@@ -204,51 +226,36 @@ int msim_check_launch(msim_ctx *ctx) {
 
 // Checks `n_histories` broadcast / g-set (set-full) or echo histories given on the host with the device checker of msim_check:
 // history i lies in the slabs rows + i * max_rows (n_rows[i] rows used) and payload + i * max_payload_words.
-// (xs: msim_explain_set_full_batch's slabs — set_explain_kernel in place of check_kernel, on the same upload)
+// (hdr: msim_explain_set_full_batch's arrays — set_explain_kernel in place of check_kernel, on the same upload)
 static int set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
                           const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out,
-                          SetExplainSlabs *xs) {
+                          msim_set_explain *hdr = nullptr, msim_set_element *elements = nullptr, uint32_t max_elements = 0) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0 || (!payload && max_payload_words)) return MSIM_E_INVALID;
   if (workload != MSIM_WL_ECHO && workload != MSIM_WL_BROADCAST && workload != MSIM_WL_G_SET) return MSIM_E_INVALID;
   if (check_limits(max_rows, max_values, concurrency)) return MSIM_E_UNSUPPORTED;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  std::vector<msim_inst_meta> hm(n_histories);
-  for (u32 i = 0; i < n_histories; i++) { std::memset(&hm[i], 0, sizeof hm[i]); if (n_rows[i] > max_rows) return MSIM_E_RANGE; hm[i].n_rows = n_rows[i]; }
-  CParams cp;
-  std::memset(&cp, 0, sizeof cp);
-  cp.max_rows = max_rows; cp.max_pay = max_payload_words; cp.max_values = max_values; cp.C = concurrency; cp.workload = workload;
-  msim_op *d_rows = nullptr; u32 *d_pay = nullptr; msim_inst_meta *d_meta = nullptr; msim_check_result *d_out = nullptr; u32 *d_rec = nullptr;
-  const size_t pay_bytes = (size_t)n_histories * (max_payload_words ? max_payload_words : 1) * sizeof(u32);
-  int rc = MSIM_E_HIP;
-  do {
-    if (msim_dev_malloc(&d_rows, (size_t)n_histories * max_rows * sizeof(msim_op)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_pay, pay_bytes) != hipSuccess) break;
-    if (msim_dev_malloc(&d_meta, (size_t)n_histories * sizeof(msim_inst_meta)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_out, (size_t)n_histories * sizeof(msim_check_result)) != hipSuccess) break;
-    if (msim_dev_malloc(&d_rec, (size_t)n_histories * (max_rows / 2 + 1) * 3 * sizeof(u32)) != hipSuccess) break;
-    if (hipMemcpy(d_rows, rows, (size_t)n_histories * max_rows * sizeof(msim_op), hipMemcpyHostToDevice) != hipSuccess) break;
-    if (max_payload_words && hipMemcpy(d_pay, payload, pay_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-    if (hipMemcpy(d_meta, hm.data(), (size_t)n_histories * sizeof(msim_inst_meta), hipMemcpyHostToDevice) != hipSuccess) break;
-    cp.rows = d_rows; cp.payload = d_pay; cp.meta = d_meta; cp.out = d_out; cp.recs = d_rec;
-    if (xs) {
-      BatchCtx bc(device);
-      SetExplainOut x;
-      std::memset(&x, 0, sizeof x);
-      if (xs->clear(&bc, nullptr) != MSIM_OK) break;
-      xs->bind(x);
-      if (set_explain_dispatch(cp, x, n_histories, nullptr) != hipSuccess) break;
-      if (xs->fetch(&bc, nullptr) != MSIM_OK) break;
-    } else if (check_dispatch(cp, n_histories, nullptr) != hipSuccess) break;
-    if (hipDeviceSynchronize() != hipSuccess) break;
-    if (hipMemcpy(out, d_out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost) != hipSuccess) break;
-    rc = MSIM_OK;
-  } while (false);
-  for (void *q : {(void *)d_rows, (void *)d_pay, (void *)d_meta, (void *)d_out, (void *)d_rec}) if (q) (void)msim_dev_free(q);
-  return rc;
+  BatchFrame<SlabBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, n_rows, max_rows, n_histories)) return rc;
+  if (int rc = f.b.upload_payload(ctx, payload, max_payload_words, n_histories)) return rc;
+  SetSlabs xs;
+  if (hdr) if (int rc = xs.alloc(ctx, n_histories, max_elements, hdr, elements)) return rc;
+  DevBuf d_rec;
+  MSIM_HIP_TRY(ctx, d_rec.alloc((size_t)n_histories * (max_rows / 2 + 1) * 3 * sizeof(u32)));
+  CParams cp = check_params(workload, concurrency, max_rows, max_payload_words, max_values);
+  cp.rows = f.b.rows.get<msim_op>(); cp.payload = f.b.pay.get<u32>(); cp.meta = f.b.meta.get<msim_inst_meta>(); cp.out = f.d_out.get<msim_check_result>(); cp.recs = d_rec.get<u32>();
+  if (hdr) {
+    SetExplainOut x = set_explain_out(xs);
+    if (int rc = xs.clear(ctx, nullptr)) return rc;
+    const size_t lds = check_layout(cp, &x.off_lat);
+    MSIM_HIP_TRY(ctx, check_dispatch(set_explain_kernel, lds, n_histories, nullptr, cp, x));
+    if (int rc = xs.fetch(ctx, nullptr)) return rc;
+  } else MSIM_HIP_TRY(ctx, check_dispatch(check_kernel, check_layout(cp), n_histories, nullptr, cp));
+  MSIM_HIP_TRY(ctx, hipDeviceSynchronize());
+  MSIM_HIP_TRY(ctx, hipMemcpy(out, cp.out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost));
+  return MSIM_OK;
 }
 extern "C" int msim_check_set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
                                          const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out) {
-  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out, nullptr);
+  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out);
 }
 
 // The explaining set-full check (include/maelsim.h msim_set_explain) of a caller's histories: msim_check_set_full_batch's upload and
@@ -258,12 +265,7 @@ extern "C" int msim_explain_set_full_batch(int device, uint32_t workload, uint32
                                            msim_check_result *out, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements) {
   if (!hdr || (!elements && max_elements) || n_histories == 0) return MSIM_E_INVALID;
   if (workload != MSIM_WL_BROADCAST && workload != MSIM_WL_G_SET) return MSIM_E_UNSUPPORTED;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx bc(device);
-  SetExplainSlabs xs;
-  const int rc = xs.alloc(&bc, n_histories, max_elements, hdr, elements);
-  if (rc != MSIM_OK) return rc;
-  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out, &xs);
+  return set_full_batch(device, workload, concurrency, rows, n_rows, max_rows, payload, max_payload_words, max_values, n_histories, out, hdr, elements, max_elements);
 }
 
 // ... and of the last run where it lies in HBM.  Towards the context this is msim_check (engine.hip): a check queued behind the
@@ -272,34 +274,22 @@ extern "C" int msim_explain_set_full_batch(int device, uint32_t workload, uint32
 extern "C" int msim_explain_set_full(msim_ctx *ctx, msim_set_explain *hdr, msim_set_element *elements, uint32_t max_elements, uint32_t n_out) {
   if (!ctx || !hdr || (!elements && max_elements)) return MSIM_E_INVALID;
   const msim_config &c = ctx->cfg;
-  if (c.workload != MSIM_WL_BROADCAST && c.workload != MSIM_WL_G_SET) { ctx->err = "msim_explain_set_full: not a broadcast or g-set context"; return MSIM_E_UNSUPPORTED; }
-  if (!ctx->ran) { ctx->err = "msim_explain_set_full before msim_run"; return MSIM_E_RANGE; }
-  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_set_full: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (int rc = explain_refusal(ctx, "msim_explain_set_full", c.workload == MSIM_WL_BROADCAST || c.workload == MSIM_WL_G_SET, "a broadcast or g-set", n_out)) return rc;
   if (const char *why = check_limits(c.max_rows, c.max_values, c.concurrency)) { ctx->err = why; return MSIM_E_UNSUPPORTED; }
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const uint32_t flags = msim_dev_flags(ctx);
-  if (ctx->check_queued) {
-    ctx->check_queued = false;
-    if (flags & 0x1000u) std::fprintf(stderr, "[check] taken %u\n", ctx->n_inst);
-    const int rc = msim_check_wait(ctx);
-    if (rc != MSIM_OK) return rc;
-  } else if (ctx->ran_own_stream && !(flags & 0x40000u)) ctx->check_armed = true;
-  if (flags & 0x1000u) std::fprintf(stderr, "[check] explain %u\n", ctx->n_inst);
-  SetExplainSlabs xs;
-  int rc = xs.alloc(ctx, ctx->n_inst, max_elements, hdr, elements);
-  if (rc != MSIM_OK) return rc;
+  int rc = msim_check_take_or_arm(ctx);
+  if (rc < 0) return rc;
+  if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[check] explain %u\n", ctx->n_inst);
+  SetSlabs xs;
+  if ((rc = xs.alloc(ctx, ctx->n_inst, max_elements, hdr, elements)) != MSIM_OK) return rc;
   if ((rc = msim_check_reserve(ctx, ctx->n_inst)) != MSIM_OK) return rc;
-  CParams cp;
-  std::memset(&cp, 0, sizeof cp);
-  cp.rows = ctx->d_rows; cp.payload = ctx->d_payload; cp.meta = ctx->d_meta; cp.out = ctx->d_check;
-  cp.max_rows = c.max_rows; cp.max_pay = c.max_payload_words; cp.max_values = c.max_values; cp.C = c.concurrency; cp.workload = c.workload;
+  CParams cp = check_params(ctx);
   cp.recs = static_cast<u32 *>(ctx->d_check_scratch);
-  SetExplainOut x;
-  std::memset(&x, 0, sizeof x);
+  SetExplainOut x = set_explain_out(xs);
   if ((rc = xs.clear(ctx, ctx->stream)) != MSIM_OK) return rc;
-  xs.bind(x);
+  const size_t lds = check_layout(cp, &x.off_lat);
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-  MSIM_HIP_TRY(ctx, set_explain_dispatch(cp, x, ctx->n_inst, ctx->stream));
+  MSIM_HIP_TRY(ctx, check_dispatch(set_explain_kernel, lds, ctx->n_inst, ctx->stream, cp, x));
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, ctx->stream));
   if ((rc = xs.fetch(ctx, ctx->stream)) != MSIM_OK) return rc;
   return msim_check_wait(ctx);

@@ -315,14 +315,8 @@ extern "C" int msim_check(msim_ctx *ctx) {
   // set-full (broadcast, g-set) and echo: one launch of checker.hip's kernel.  run_impl has queued it behind the simulation on an armed
   // context: then this call only waits for it.  Otherwise the kernel is launched here — also for a second msim_check of the same run —
   // and a caller that checks a launch on the context's own stream arms the context for its next launches.
-  const uint32_t flags = msim_dev_flags(ctx);
-  if (ctx->check_queued) {
-    ctx->check_queued = false;
-    if (flags & 0x1000u) std::fprintf(stderr, "[check] taken %u\n", ctx->n_inst);
-    return msim_check_wait(ctx);
-  }
-  if (ctx->ran_own_stream && !(flags & 0x40000u)) ctx->check_armed = true;
-  if (flags & 0x1000u) std::fprintf(stderr, "[check] launched %u\n", ctx->n_inst);
+  if (const int took = msim_check_take_or_arm(ctx)) return took < 0 ? took : MSIM_OK;
+  if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[check] launched %u\n", ctx->n_inst);
   return msim_check_launch(ctx);
 }
 

@@ -1,5 +1,5 @@
 // engine_internal.h — private to libmaelsim: engine.hip and the simulation kernels' units (through sim_kernels.h / wave_common.h),
-// checker.hip, the host checkers (lin_check.cpp, txn_check.cpp, kafka_check.cpp, pn_check.cpp), the device checkers (through
+// the checkers — checker.hip, the device checkers and the host checkers lin_check.cpp, txn_check.cpp, kafka_check.cpp, pn_check.cpp — (through
 // check_run.h), gather.cpp, guard.cpp.
 #ifndef MSIM_ENGINE_INTERNAL_H
 #define MSIM_ENGINE_INTERNAL_H
@@ -107,10 +107,11 @@ void msim_gather_free(msim_ctx *ctx);
 // checker.hip: the set-full / echo checker over the context's slabs.  msim_check_reserve sizes d_check_scratch for n histories (it may
 // free and allocate: never between a simulation and the check queued behind it); msim_check_enqueue queues the kernel between ev2 and
 // ev3 on `stream` and never waits; msim_check_wait waits for ev3 and marks the run checked; msim_check_launch = enqueue on the context's
-// stream + wait
+// stream + wait; msim_check_take_or_arm: 1 a queued check taken and waited for, 0 none queued (the context armed where it may be), < 0 an error
 int msim_check_reserve(msim_ctx *ctx, uint32_t n);
 int msim_check_enqueue(msim_ctx *ctx, hipStream_t stream);
 int msim_check_wait(msim_ctx *ctx);
+int msim_check_take_or_arm(msim_ctx *ctx);
 int msim_check_launch(msim_ctx *ctx);
 // lin_check.cpp (host search) / lin_check_dev.hip (one wavefront per history)
 // (keys / max_keys / n_keys: msim_explain_lin_kv's key records, a slab of max_keys per history; null / 0 / null: the plain check)

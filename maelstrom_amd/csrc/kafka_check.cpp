@@ -23,12 +23,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -272,31 +270,11 @@ extern "C" int msim_check_kafka_rows(const msim_op *rows, uint32_t n_rows, const
 
 // (hdr: msim_explain_kafka's arrays — every history explained by the walk; null: msim_check)
 int msim_explain_kafka_host(msim_ctx *ctx, msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings) {
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = msim_fetch(ctx);
-  if (rc != MSIM_OK) return rc;
-  const uint32_t n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  unsigned nt = msim_host_threads();
-  if (nt > n) nt = n;
-  std::vector<std::thread> th;
-  for (unsigned w = 0; w < nt; w++)
-    th.emplace_back([=]() {
-      std::vector<Tables> t(1);
-      for (uint32_t i = w; i < n; i += nt) {
-        const msim_op *rows = ctx->h_rows + ctx->h_row_off[i];
-        const uint32_t *pay = ctx->h_payload + ctx->h_pay_off[i];
-        const msim_inst_meta &m = ctx->h_meta[i];
-        if (hdr) explain_kafka(rows, m.n_rows, pay, m.n_payload_words, m.flags, &ctx->h_check[i], &hdr[i], findings + (size_t)i * max_findings, max_findings);
-        else check_kafka(rows, m.n_rows, pay, m.n_payload_words, m.flags, &ctx->h_check[i], t[0]);
-      }
-    });
-  for (auto &x : th) x.join();
-  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
-  ctx->checked = true; ctx->check_fetched = true;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return MSIM_OK;
+  return host_check_run(ctx, []() { return std::vector<Tables>(1); }, [=](std::vector<Tables> &t, uint32_t i, const msim_op *rows, uint32_t n_rows, const uint32_t *pay, uint32_t n_words,
+                                                                          uint32_t flags, msim_check_result *res) {
+    if (hdr) explain_kafka(rows, n_rows, pay, n_words, flags, res, &hdr[i], findings + (size_t)i * max_findings, max_findings);
+    else check_kafka(rows, n_rows, pay, n_words, flags, res, t[0]);
+  });
 }
 
 int msim_check_kafka_host(msim_ctx *ctx) { return msim_explain_kafka_host(ctx, nullptr, nullptr, 0); }

@@ -517,31 +517,28 @@ int kafka_dev_run(msim_ctx *ctx, KCParams kp, u32 n, const std::vector<msim_inst
     MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
     n_unclean = (u32)needs(h_out, n, [](u32 valid) { return valid == NEEDS_HOST; }).size();
     if (n_unclean) {
-      DevBuf list, d_hdr, d_find, ws;
+      DevBuf list, ws;
+      ExplainSlabs<msim_kafka_explain, msim_kafka_finding> xs;   // (on the device only now that some history is unclean)
       const u32 chunk = chunk_for(n_unclean, (uint64_t)FX_MAX * sizeof(msim_kafka_finding), 64ull << 20, msim_dev_flags(ctx));
       MSIM_HIP_TRY(ctx, list.alloc(((size_t)n + 1) * 4));
-      MSIM_HIP_TRY(ctx, d_hdr.alloc((size_t)n * sizeof(msim_kafka_explain)));
-      MSIM_HIP_TRY(ctx, d_find.alloc(std::max(f_bytes, sizeof(msim_kafka_finding))));
+      if (int rc = xs.alloc(ctx, n, xr->max_findings, xr->hdr, xr->findings)) return rc;
       MSIM_HIP_TRY(ctx, ws.alloc((size_t)chunk * FX_MAX * sizeof(msim_kafka_finding)));
       u32 *const d_list = list.get<u32>();
       MSIM_HIP_TRY(ctx, hipMemsetAsync(d_list, 0, 4, st));
-      MSIM_HIP_TRY(ctx, hipMemsetAsync(d_hdr.get<void>(), 0, (size_t)n * sizeof(msim_kafka_explain), st));
-      if (f_bytes) MSIM_HIP_TRY(ctx, hipMemsetAsync(d_find.get<void>(), 0, f_bytes, st));
+      if (int rc = xs.clear(ctx, st)) return rc;
       hipLaunchKernelGGL(kafka_todo_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, kp.out, n, d_list);
       MSIM_HIP_TRY(ctx, hipGetLastError());
       KCParams cp = kp;   // tables for what the launch names, up to what LDS holds beside the explaining cells
       cp.T = std::min(TX_MAX, std::max(32u, (h_bound + 1u + 31u) & ~31u));
       const size_t xlds = kafka_explain_lds_bytes(cp.T);
       if (xlds > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&kafka_explain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-      const KXOut x{d_hdr.get<msim_kafka_explain>(), d_find.get<msim_kafka_finding>(), xr->max_findings, ws.get<uint4>()};
+      const KXOut x{xs.hdr(), xs.rec(), xr->max_findings, ws.get<uint4>()};
       hipError_t err;
       for_chunks(n_unclean, chunk, &err, [&](u32 first, u32 count) {   // (one workspace: the chunks follow one another on the stream)
         hipLaunchKernelGGL(kafka_explain_kernel, dim3(count), dim3(NT), xlds, st, cp, d_list + 1 + first, x);
       });
       MSIM_HIP_TRY(ctx, err);
-      MSIM_HIP_TRY(ctx, hipMemcpyAsync(xr->hdr, d_hdr.get<void>(), (size_t)n * sizeof(msim_kafka_explain), hipMemcpyDeviceToHost, st));
-      if (f_bytes) MSIM_HIP_TRY(ctx, hipMemcpyAsync(xr->findings, d_find.get<void>(), f_bytes, hipMemcpyDeviceToHost, st));
-      MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));   // (the buffers are freed with this block)
+      if (int rc = xs.fetch(ctx, st)) return rc;   // (waits: the buffers are freed with this block)
     }
   } else if (classify) {   // the histories not proved clean, listed on the device, each to a workgroup of kafka_classify_kernel
     DevBuf list;
@@ -615,9 +612,7 @@ int msim_check_kafka_device(msim_ctx *ctx) { return kafka_device(ctx, nullptr); 
 // msim_check leaves them; where msim_check keeps to the host cores (a concurrency beyond 64, developer flag 0x800) the walk explains.
 extern "C" int msim_explain_kafka(msim_ctx *ctx, msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings, uint32_t n_out) {
   if (!ctx || !hdr || (!findings && max_findings)) return MSIM_E_INVALID;
-  if (ctx->cfg.workload != MSIM_WL_KAFKA) { ctx->err = "msim_explain_kafka: not a kafka context"; return MSIM_E_UNSUPPORTED; }
-  if (!ctx->ran) { ctx->err = "msim_explain_kafka before msim_run"; return MSIM_E_RANGE; }
-  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_kafka: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (int rc = explain_refusal(ctx, "msim_explain_kafka", ctx->cfg.workload == MSIM_WL_KAFKA, "a kafka", n_out)) return rc;
   if (msim_dev_flags(ctx) & 0x800u) return msim_explain_kafka_host(ctx, hdr, findings, max_findings);
   const KafkaExplainRun xr{hdr, findings, max_findings};
   return kafka_device(ctx, &xr);
@@ -629,16 +624,11 @@ static int kafka_batch(int device, const msim_op *rows, const uint64_t *row_offs
                        uint32_t n_histories, uint32_t concurrency, msim_check_result *out, uint32_t *n_host, bool classify, const KafkaExplainRun *xr = nullptr) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || concurrency == 0 || concurrency > CMAX) return MSIM_E_INVALID;
   if (payload_offsets[n_histories] != 0 && !payload) return MSIM_E_INVALID;   // (as msim_check_kafka_rows: payload words announced, none given)
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  OffsetsBatch b;
-  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull, 0x7FFFFFFFull)) return rc;
-  DevBuf d_out;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull, 0x7FFFFFFFull)) return rc;
   KCParams kp;
   std::memset(&kp, 0, sizeof kp);
-  kp.rows = b.rows.get<msim_op>(); kp.payload = b.pay.get<u32>(); kp.row_off = b.row_off.get<uint64_t>(); kp.pay_off = b.pay_off.get<uint64_t>();
-  kp.out = d_out.get<msim_check_result>();
+  f.bind(kp);
   kp.T = OFFS; kp.C = concurrency;
   return kafka_dev_run(ctx, kp, n_histories, nullptr, out, nullptr, n_host, classify, xr);
 }

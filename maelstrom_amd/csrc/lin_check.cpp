@@ -10,14 +10,12 @@
 // thread per slice of instances.  msim_check runs the device version (lin_check_dev.hip, one wavefront per history) and
 // comes here only for histories that exceed it; MSIM_DEV_FLAGS bit 11 keeps everything on the host.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -251,25 +249,10 @@ extern "C" int msim_check_lin_kv_rows(const msim_op *rows, uint32_t n_rows, msim
 
 // Runs the lin-kv checker over the fetched histories of the last run; results to ctx->h_check and ctx->d_check.
 int msim_check_lin_kv_host(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = msim_fetch(ctx);
-  if (rc != MSIM_OK) return rc;
-  const uint32_t n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  if (keys) std::memset(keys, 0, (size_t)n * max_keys * sizeof(msim_lin_key_result));   // (as the device path leaves the records a history does not have)
-  unsigned nt = msim_host_threads();
-  if (nt > n) nt = n;
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([ctx, n, nt, t, keys, max_keys, n_keys]() {
-      for (uint32_t i = t; i < n; i += nt)
-        check_instance(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_meta[i].flags, &ctx->h_check[i], keys ? keys + (size_t)i * max_keys : nullptr, max_keys,
-                       n_keys ? n_keys + i : nullptr);
-    });
-  for (auto &x : th) x.join();
-  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
-  ctx->checked = true; ctx->check_fetched = true; ctx->lin_host_rechecks = n;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return MSIM_OK;
+  if (keys) std::memset(keys, 0, (size_t)ctx->n_inst * max_keys * sizeof(msim_lin_key_result));   // (as the device path leaves the records a history does not have)
+  const int rc = host_check_run(ctx, []() { return 0; }, [=](int, uint32_t i, const msim_op *rows, uint32_t n_rows, const uint32_t *, uint32_t, uint32_t flags, msim_check_result *res) {
+    check_instance(rows, n_rows, flags, res, keys ? keys + (size_t)i * max_keys : nullptr, max_keys, n_keys ? n_keys + i : nullptr);
+  });
+  if (rc == MSIM_OK) ctx->lin_host_rechecks = ctx->n_inst;
+  return rc;
 }

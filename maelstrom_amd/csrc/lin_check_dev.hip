@@ -691,14 +691,15 @@ __global__ void __launch_bounds__(1024) lin_check_wg_explain_kernel(const LParam
 
 // launches the search over `n` histories: pass 1 (a wavefront each: 64 configurations in registers, the closures beyond that in a
 // slot of an HBM workspace), then for what it left open pass 2 (a workgroup of 1024 each, the pool in LDS: the largest that fits) and
-// the host search (all host threads) for what exceeds even that.  xp (may be null: the plain check, the plain kernels): the explaining
-// check — the EXPLAIN kernels write the key records to xp->keys (device, zeroed here), which come to h_keys (host, the same layout)
+// the host search (all host threads) for what exceeds even that.  xs (may be null: the plain check, the plain kernels): the explaining
+// check — the EXPLAIN kernels write the key records to xs's device slab (zeroed here), which come to the caller's array (the same layout)
 // once the device passes are through; a history the host search finishes has all its records rewritten there.  h_n_keys[i] = its keys.
+typedef ExplainSlabs<void, msim_lin_key_result> KeySlabs;   // max_keys records per history, no header
 int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any, msim_check_result *h_out, hipStream_t st, u32 *n_host,
-                      const XParams *xp = nullptr, msim_lin_key_result *h_keys = nullptr, u32 *h_n_keys = nullptr) {
+                      KeySlabs *xs = nullptr, u32 *h_n_keys = nullptr) {
   LParams lp = lp0;
-  const size_t keys_bytes = xp ? (size_t)n * xp->max_keys * sizeof(msim_lin_key_result) : 0;
-  const XParams xp0 = xp ? *xp : XParams{nullptr, 0};
+  const bool xp = xs != nullptr;
+  const XParams xp0 = xs ? XParams{xs->rec(), xs->max_k} : XParams{nullptr, 0};
   const bool tiny = (msim_dev_flags(ctx) & 0x2000u) != 0;    // developer / tests: pools small enough that every level is reached, the host search included
   const PassTimer tm(ctx);
   const bool trace = tm.trace;
@@ -718,7 +719,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
   hp.claim = hp.pool + (ws_bytes - 256) / 4;
   MSIM_HIP_TRY(ctx, hipMemsetAsync(hp.claim, 0, 4, st));
   if (xp) {
-    MSIM_HIP_TRY(ctx, hipMemsetAsync(xp0.keys, 0, keys_bytes, st));
+    if (int rc = xs->clear(ctx, st)) return rc;
     hipLaunchKernelGGL(lin_check_explain_kernel, dim3(n), dim3(64), fixed, st, lp, hp, xp0);
   } else hipLaunchKernelGGL(lin_check_kernel, dim3(n), dim3(64), fixed, st, lp, hp);
   MSIM_HIP_TRY(ctx, hipGetLastError());
@@ -750,7 +751,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
       const uint64_t first = lp.meta ? (uint64_t)i * lp.stride : ho[i];
       std::vector<msim_op> rows(nr ? nr : 1);
       if (nr && hipMemcpy(rows.data(), lp.rows + first, (size_t)nr * sizeof(msim_op), hipMemcpyDeviceToHost) != hipSuccess) { copy_err = 1; return; }
-      if (xp) { u32 nk = 0; msim_lin_explain_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k], h_keys + (size_t)i * xp0.max_keys, xp0.max_keys, &nk); }
+      if (xp) { u32 nk = 0; msim_lin_explain_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k], xs->rec(i), xp0.max_keys, &nk); }
       else msim_lin_check_instance_host(rows.data(), nr, lp.meta ? hm[i].flags : 0u, &hh[k]);
       host_done[k] = 1;
     };
@@ -804,7 +805,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     else std::fill(wanted.begin(), wanted.end(), 1);   // (the host can still do everything)
     const double t_dev = tm.ms();
     list.reset();
-    if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));   // (before the host search rewrites its histories' records)
+    if (xs) if (int rc = xs->fetch(ctx, st)) return rc;   // (before the host search rewrites its histories' records)
     u32 n_host_needed = 0;
     for (size_t k = 0; k < order.size(); k++) n_host_needed += wanted[k] != 0;
     if (n_host_needed) {   // what even the HBM pools could not hold (or found no slot): the host search, all host threads
@@ -833,7 +834,7 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
     if (trace) { u32 slots = 0; for (size_t k = 0; k < order.size(); k++) if (wanted[k] && h2[order[k]].duplicated_count == 1u) slots++;
       std::fprintf(stderr, "[lin-check] device passes done at %.2f ms, %u histories needed the host search (%u of them: more than 23 calls pending on a key)\n", t_dev, n_host_needed, slots); }
     todo.resize(n_host_needed);
-  } else if (xp) MSIM_HIP_TRY(ctx, hipMemcpy(h_keys, xp0.keys, keys_bytes, hipMemcpyDeviceToHost));
+  } else if (xs) { if (int rc = xs->fetch(ctx, st)) return rc; }
   if (xp) for (u32 i = 0; i < n; i++) h_n_keys[i] = h_out[i].attempt_count;   // keys checked = records the history has
   if (trace) std::fprintf(stderr, "[lin-check] done at %.2f ms\n", tm.ms());
   if (n_host) *n_host = (u32)todo.size();
@@ -846,17 +847,16 @@ int lin_check_dev_run(msim_ctx *ctx, const LParams &lp0, u32 n, u32 max_rows_any
 int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
-  DevBuf slab;
-  if (keys) MSIM_HIP_TRY(ctx, slab.alloc((size_t)n * max_keys * sizeof(msim_lin_key_result)));
-  const XParams xp{slab.get<msim_lin_key_result>(), max_keys};
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
+  KeySlabs xs;
+  if (keys) if (int rc = xs.alloc(ctx, n, max_keys, nullptr, keys)) return rc;
+  std::chrono::steady_clock::time_point t0;
+  if (int rc = begin_check(ctx, &t0, nullptr)) return rc;   // (no meta here: the host stage fetches it for what the device passes leave open)
   LParams lp;
-  lp.rows = ctx->d_rows; lp.meta = ctx->d_meta; lp.off = nullptr; lp.out = ctx->d_check; lp.stride = ctx->cfg.max_rows; lp.table_rows = 0; lp.list = nullptr;
+  std::memset(&lp, 0, sizeof lp);
+  lp.rows = ctx->d_rows; lp.meta = ctx->d_meta; lp.out = ctx->d_check; lp.stride = ctx->cfg.max_rows;
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-  const auto t0 = std::chrono::steady_clock::now();
   u32 redone = 0;
-  int rc = lin_check_dev_run(ctx, lp, n, ctx->cfg.max_rows, ctx->h_check, ctx->stream, &redone, keys ? &xp : nullptr, keys, n_keys);
+  int rc = lin_check_dev_run(ctx, lp, n, ctx->cfg.max_rows, ctx->h_check, ctx->stream, &redone, keys ? &xs : nullptr, n_keys);
   if (rc != MSIM_OK) return rc;
   finish_check(ctx, t0, redone);
   return MSIM_OK;
@@ -866,17 +866,14 @@ int msim_check_lin_kv_device(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t 
 // `device`; out[i] as msim_check_lin_kv_rows would fill it.
 static int lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out,
                         msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t *n_host) {
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  OffsetsBatch b;
-  if (int rc = b.upload(ctx, rows, row_offsets, nullptr, nullptr, n_histories, 0xFFFFFFFFull)) return rc;
-  DevBuf d_out, slab;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
-  if (keys) MSIM_HIP_TRY(ctx, slab.alloc((size_t)n_histories * max_keys * sizeof(msim_lin_key_result)));
-  const XParams xp{slab.get<msim_lin_key_result>(), max_keys};
+  BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, nullptr, nullptr, n_histories, 0xFFFFFFFFull)) return rc;
+  KeySlabs xs;
+  if (keys) if (int rc = xs.alloc(ctx, n_histories, max_keys, nullptr, keys)) return rc;
   LParams lp;
-  lp.rows = b.rows.get<msim_op>(); lp.meta = nullptr; lp.off = b.row_off.get<uint64_t>(); lp.out = d_out.get<msim_check_result>(); lp.stride = 0; lp.table_rows = 0; lp.list = nullptr;
-  return lin_check_dev_run(ctx, lp, n_histories, b.longest, out, nullptr, n_host, keys ? &xp : nullptr, keys, n_keys);
+  std::memset(&lp, 0, sizeof lp);
+  lp.rows = f.b.rows.get<msim_op>(); lp.off = f.b.row_off.get<uint64_t>(); lp.out = f.d_out.get<msim_check_result>();
+  return lin_check_dev_run(ctx, lp, n_histories, f.b.longest, out, nullptr, n_host, keys ? &xs : nullptr, n_keys);
 }
 
 extern "C" int msim_check_lin_kv_batch(int device, const msim_op *rows, const uint64_t *row_offsets, uint32_t n_histories, msim_check_result *out) {
@@ -894,9 +891,7 @@ extern "C" int msim_explain_lin_kv_batch(int device, const msim_op *rows, const 
 // msim_check for lin-kv with the key records: the histories of the last run, where they lie in HBM.
 extern "C" int msim_explain_lin_kv(msim_ctx *ctx, msim_lin_key_result *keys, uint32_t max_keys, uint32_t *n_keys, uint32_t n_out) {
   if (!ctx || !keys || !n_keys || max_keys < 1 || max_keys > 256) return MSIM_E_INVALID;
-  if (ctx->cfg.workload != MSIM_WL_LIN_KV) { ctx->err = "msim_explain_lin_kv: not a lin-kv context"; return MSIM_E_UNSUPPORTED; }
-  if (!ctx->ran) { ctx->err = "msim_explain_lin_kv before msim_run"; return MSIM_E_RANGE; }
-  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_lin_kv: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (int rc = explain_refusal(ctx, "msim_explain_lin_kv", ctx->cfg.workload == MSIM_WL_LIN_KV, "a lin-kv", n_out)) return rc;
   return (msim_dev_flags(ctx) & 0x800u) ?   // bit 11: keep the check on the host cores
          msim_check_lin_kv_host(ctx, keys, max_keys, n_keys) : msim_check_lin_kv_device(ctx, keys, max_keys, n_keys);
 }

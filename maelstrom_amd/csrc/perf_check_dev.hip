@@ -357,21 +357,18 @@ extern "C" int msim_check_perf_batch(int device, const msim_op *rows, const uint
                                      uint32_t window_ms, uint32_t n_windows, msim_perf_result *out, msim_latency_dist *windows) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0 || perf_args(window_ms, n_windows, windows)) return MSIM_E_INVALID;
   if (perf_limits(max_rows, concurrency)) return MSIM_E_UNSUPPORTED;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  SlabBatch b;
-  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
+  BatchFrame<SlabBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_perf_result), rows, n_rows, max_rows, n_histories)) return rc;
   const u32 W = windows ? n_windows : 0;
   PParams pp;
   std::memset(&pp, 0, sizeof pp);
   pp.max_rows = max_rows; pp.C = concurrency; pp.W = W; pp.window_ns = (u64)window_ms * 1000000ull;
   const size_t win_bytes = (size_t)n_histories * W * SLOTS * sizeof(msim_latency_dist);
-  DevBuf d_out, d_win, d_rec;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_perf_result)));
+  DevBuf d_win, d_rec;
   if (W) MSIM_HIP_TRY(ctx, d_win.alloc(win_bytes));
   MSIM_HIP_TRY(ctx, d_rec.alloc((size_t)n_histories * std::max(1u, max_rows / 2) * sizeof(uint2)));
-  pp.rows = b.rows.get<msim_op>(); pp.meta = b.meta.get<msim_inst_meta>();
-  pp.out = d_out.get<msim_perf_result>(); pp.win = d_win.get<msim_latency_dist>(); pp.recs = d_rec.get<uint2>();
+  pp.rows = f.b.rows.get<msim_op>(); pp.meta = f.b.meta.get<msim_inst_meta>();
+  pp.out = f.d_out.get<msim_perf_result>(); pp.win = d_win.get<msim_latency_dist>(); pp.recs = d_rec.get<uint2>();
   MSIM_HIP_TRY(ctx, perf_dispatch(pp, n_histories, nullptr));
   MSIM_HIP_TRY(ctx, hipDeviceSynchronize());
   MSIM_HIP_TRY(ctx, hipMemcpy(out, pp.out, (size_t)n_histories * sizeof(msim_perf_result), hipMemcpyDeviceToHost));

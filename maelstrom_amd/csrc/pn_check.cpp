@@ -8,13 +8,11 @@
 // marked :final? that completed :ok must lie in it.  Pinned by the reference's own vectors (test/maelstrom/workload/
 // pn_counter_test.clj:10-36) in tests/test_pn_counter.py.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <thread>
 #include <utility>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -98,26 +96,8 @@ extern "C" int msim_check_unique_rows(const msim_op *rows, uint32_t n_rows, msim
 }
 
 int msim_check_unique_host(msim_ctx *ctx) {
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = msim_fetch(ctx);
-  if (rc != MSIM_OK) return rc;
-  const uint32_t n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  unsigned nt = msim_host_threads();
-  if (nt > n) nt = n;
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([ctx, n, nt, t]() {
-      std::vector<uint32_t> ids;
-      for (uint32_t i = t; i < n; i += nt)
-        check_unique(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_meta[i].flags, &ctx->h_check[i], ids);
-    });
-  for (auto &x : th) x.join();
-  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
-  ctx->checked = true; ctx->check_fetched = true;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return MSIM_OK;
+  return host_check_run(ctx, []() { return std::vector<uint32_t>(); }, [](std::vector<uint32_t> &ids, uint32_t, const msim_op *rows, uint32_t n_rows, const uint32_t *, uint32_t, uint32_t flags,
+                                                                          msim_check_result *res) { check_unique(rows, n_rows, flags, res, ids); });
 }
 
 extern "C" int msim_check_pn_rows(const msim_op *rows, uint32_t n_rows, msim_check_result *out, int64_t *ranges, uint32_t cap, uint32_t *n_ranges) {
@@ -130,24 +110,7 @@ extern "C" int msim_check_pn_rows(const msim_op *rows, uint32_t n_rows, msim_che
 }
 
 int msim_check_pn_host(msim_ctx *ctx) {
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = msim_fetch(ctx);
-  if (rc != MSIM_OK) return rc;
-  const uint32_t n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  unsigned nt = msim_host_threads();
-  if (nt > n) nt = n;
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++)
-    th.emplace_back([ctx, n, nt, t]() {
-      Ranges acc;
-      for (uint32_t i = t; i < n; i += nt)
-        check_history(ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_meta[i].flags, &ctx->h_check[i], acc);
-    });
-  for (auto &x : th) x.join();
-  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
-  ctx->checked = true; ctx->check_fetched = true;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return MSIM_OK;
+  return host_check_run(ctx, []() { return Ranges(); }, [](Ranges &acc, uint32_t, const msim_op *rows, uint32_t n_rows, const uint32_t *, uint32_t, uint32_t flags, msim_check_result *res) {
+    check_history(rows, n_rows, flags, res, acc);
+  });
 }

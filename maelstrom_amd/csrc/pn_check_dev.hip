@@ -147,11 +147,7 @@ int msim_check_pn_device(msim_ctx *ctx) {
 // rows + i * max_rows, n_rows[i] of them used), with the device checker of msim_check; out[i] as msim_check_pn_rows would fill it.
 extern "C" int msim_check_pn_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0) return MSIM_E_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  SlabBatch b;
-  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
-  DevBuf d_out;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
-  return pn_dev_run(ctx, b.rows.get<msim_op>(), b.meta.get<msim_inst_meta>(), d_out.get<msim_check_result>(), max_rows, n_histories, out, nullptr, nullptr);
+  BatchFrame<SlabBatch> f(device);
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, n_rows, max_rows, n_histories)) return rc;
+  return pn_dev_run(&f.ctx, f.b.rows.get<msim_op>(), f.b.meta.get<msim_inst_meta>(), f.d_out.get<msim_check_result>(), max_rows, n_histories, out, nullptr, nullptr);
 }

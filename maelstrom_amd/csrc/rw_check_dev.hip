@@ -341,58 +341,43 @@ uint64_t rw_ws_words_full(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return rw_ws
 int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
                void **ws_buf, size_t *ws_cap, const CycleMode mode = {}) {
   // mode.witness (msim_explain_rw_batch, msim_explain_txn; with full): the witness cycles, found by rw_explain_kernel in rp.cycles / rp.steps
-  WitnessSlabs *const wit = mode.full ? mode.witness : nullptr;
-  if (wit) { wit->bind(rp); if (int rc = wit->clear(ctx, st)) return rc; }
+  CycleSlabs *const wit = mode.full ? mode.witness : nullptr;
+  if (wit) { bind_cycles(rp, *wit); if (int rc = wit->clear(ctx, st)) return rc; }
   const PassTimer tm(ctx);
   if (rp.kmax == 0 || rp.kmax > KMAX) rp.kmax = KMAX;
   if (rp.wmax == 0 || rp.wmax > WMAX) rp.wmax = WMAX;
   rp.ws_words = rw_ws_words(rp.nmax, rp.emax, rp.kmax, rp.wmax);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold
   const auto for_host = [](u32 valid) { return valid == NEEDS_HOST; };
+  // one pass of `kernel` over m histories (those of `list`, or all): chunked_pass with rp.ws_words of workspace each
+  const auto pass = [&](u32 m, const std::vector<u32> *list, auto kernel) {
+    return chunked_pass(ctx, m, rp.ws_words * 4, budget, list, ws_buf, ws_cap, [&](const u32 *d_list, void *ws, u32 first, u32 count) {
+      rp.list = d_list; rp.ws = static_cast<u32 *>(ws); rp.first = first;
+      hipLaunchKernelGGL(kernel, dim3(count), dim3(64), 0, st, rp);
+    }, rp.out, h_out, n, st);
+  };
   std::vector<u32> todo;
-  hipError_t e;
+  int rc;
   if (!mode.full) {
-    const u32 chunk = chunk_for(n, rp.ws_words * 4, budget, msim_dev_flags(ctx));
-    if (int rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * rp.ws_words * 4)) return rc;
-    rp.ws = static_cast<u32 *>(*ws_buf);
-    const u32 launches = for_chunks(n, chunk, &e, [&](u32 first, u32 count) {
-      rp.first = first;
-      hipLaunchKernelGGL(rw_check_kernel, dim3(count), dim3(64), 0, st, rp);
-    });
-    MSIM_HIP_TRY(ctx, e);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = pass(n, nullptr, rw_check_kernel)) < 0) return rc;
     todo = needs(h_out, n, for_host);
-    if (tm.trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories not proved valid\n", launches, tm.ms(), todo.size(), n);
+    if (tm.trace) std::fprintf(stderr, "[rw-check] device pass (%u launches): %.2f ms, %zu of %u histories not proved valid\n", (u32)rc, tm.ms(), todo.size(), n);
   } else todo = needs(h_out, n, [](u32) { return true; });
-  if (!todo.empty()) {   // the classification, over the list of histories that need it: the list first in the workspace, then a slice per block
+  if (!todo.empty()) {   // the classification, over the list of histories that need it
     const u32 m = (u32)todo.size();
-    const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
     rp.ws_words = rw_ws_words_full(rp.nmax, rp.emax, rp.kmax, rp.wmax);
     // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
     // histories reach the search
     rp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     rp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    const u32 chunk = chunk_for(m, rp.ws_words * 4, budget, msim_dev_flags(ctx));
-    if (int rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * rp.ws_words * 4)) return rc;
-    rp.list = static_cast<const u32 *>(*ws_buf);
-    rp.ws = reinterpret_cast<u32 *>(static_cast<char *>(*ws_buf) + list_bytes);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) {
-      rp.first = first;
-      if (wit) hipLaunchKernelGGL(rw_explain_kernel, dim3(count), dim3(64), 0, st, rp);
-      else hipLaunchKernelGGL(rw_classify_kernel, dim3(count), dim3(64), 0, st, rp);
-    });
-    MSIM_HIP_TRY(ctx, e);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, rp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = wit ? pass(m, &todo, rw_explain_kernel) : pass(m, &todo, rw_classify_kernel)) < 0) return rc;
     todo = needs(h_out, n, for_host);
-    if (tm.trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, tm.ms(), todo.size());
+    if (tm.trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, (u32)rc, tm.ms(), todo.size());
   }
-  if (wit) if (int rc = wit->fetch(ctx, st)) return rc;
+  if (wit && (rc = wit->fetch(ctx, st)) != MSIM_OK) return rc;
   if (!todo.empty()) {
-    const int rc = hand_off(ctx, source_of(rp, hmeta), n, todo, h_out, rp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
-      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], &wit->h_cycles[i], wit->h_steps + (size_t)i * rp.max_steps, rp.max_steps, true);
+    rc = hand_off(ctx, source_of(rp, hmeta), n, todo, h_out, rp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
+      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], wit->hdr(i), wit->rec(i), rp.max_steps, true);
       else msim_rw_check_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i]);
     });
     if (rc != MSIM_OK) return rc;
@@ -422,7 +407,7 @@ int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_st
   // histories may need — 1 MB of workspace per history was four launches of 4096 for the demo shape, each waiting for its slowest history
   rp.kmax = ctx->cfg.max_values ? ctx->cfg.max_values : 1u;
   rp.wmax = (u32)std::min<uint64_t>(WMAX, (uint64_t)rp.kmax * (ctx->cfg.max_writes_per_key + 2u));
-  WitnessSlabs wit;
+  CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
   u32 redone = 0;
   int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
@@ -438,19 +423,15 @@ static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets
                     uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool full,
                     msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  OffsetsBatch b;
-  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
-  DevBuf d_out, ws; size_t ws_cap = 0;
-  WitnessSlabs wit;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
+  DevBuf ws; size_t ws_cap = 0;
+  CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
   RParams rp;
   std::memset(&rp, 0, sizeof rp);
-  rp.rows = b.rows.get<msim_op>(); rp.payload = b.pay.get<u32>(); rp.row_off = b.row_off.get<uint64_t>(); rp.pay_off = b.pay_off.get<uint64_t>();
-  rp.out = d_out.get<msim_check_result>();
-  rp.nmax = b.longest / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
+  f.bind(rp);
+  rp.nmax = f.b.longest / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
   rp.proscribed = msim_proscribed_anomalies(consistency_model);
   return rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{full, cycles ? &wit : nullptr});
 }

@@ -19,15 +19,13 @@
 // Host code: the graph is pointer-chasing over a few thousand transactions per history — threads over histories here,
 // the simulation itself stays on the GPU.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <thread>
 #include <vector>
 
-#include "engine_internal.h"
+#include "check_run.h"
 
 namespace {
 
@@ -581,37 +579,18 @@ static std::vector<Scratch *> &scratch_pool(unsigned nt) {
 static std::mutex g_check_mutex;
 
 int msim_check_txn_host(msim_ctx *ctx) {
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = msim_fetch(ctx);
+  const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
+  const uint32_t cm = ctx->cfg.consistency_model;
+  std::unique_lock<std::mutex> lock(g_check_mutex, std::defer_lock);   // taken with the first thread's Scratch (behind the fetch), held until the records are back
+  unsigned taken = 0;
+  HostRunTimes tm;
+  const int rc = host_check_run(ctx, [&]() { if (!taken) lock.lock(); taken++; return scratch_pool(taken)[taken - 1]; },
+                                [=](Scratch *S, uint32_t, const msim_op *rows, uint32_t n_rows, const uint32_t *pay, uint32_t n_words, uint32_t flags, msim_check_result *res) {
+    if (rw) (void)check_rw(*S, rows, n_rows, pay, n_words, flags, cm, res);
+    else check_history(*S, rows, n_rows, pay, n_words, flags, cm, res);
+  }, &tm);
   if (rc != MSIM_OK) return rc;
-  const auto t1 = std::chrono::steady_clock::now();
-  const uint32_t n = ctx->n_inst;
-  if (ctx->h_check) { (void)hipHostFree(ctx->h_check); ctx->h_check = nullptr; }
-  MSIM_HIP_TRY(ctx, hipHostMalloc(&ctx->h_check, (size_t)n * sizeof(msim_check_result)));
-  unsigned nt = msim_host_threads();
-  if (nt > n) nt = n;
-  {
-    std::lock_guard<std::mutex> lock(g_check_mutex);
-    std::vector<Scratch *> &pool = scratch_pool(nt);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++)
-      th.emplace_back([ctx, n, nt, t, &pool]() {
-        Scratch &S = *pool[t];
-        const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
-        for (uint32_t i = t; i < n; i += nt)
-          if (rw) (void)check_rw(S, ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_payload + ctx->h_pay_off[i],
-                                 ctx->h_meta[i].n_payload_words, ctx->h_meta[i].flags, ctx->cfg.consistency_model, &ctx->h_check[i]);
-          else check_history(S, ctx->h_rows + ctx->h_row_off[i], ctx->h_meta[i].n_rows, ctx->h_payload + ctx->h_pay_off[i],
-                             ctx->h_meta[i].n_payload_words, ctx->h_meta[i].flags, ctx->cfg.consistency_model, &ctx->h_check[i]);
-      });
-    for (auto &x : th) x.join();
-  }
-  const auto t2 = std::chrono::steady_clock::now();
-  MSIM_HIP_TRY(ctx, hipMemcpy(ctx->d_check, ctx->h_check, (size_t)n * sizeof(msim_check_result), hipMemcpyHostToDevice));
-  ctx->checked = true; ctx->check_fetched = true;
-  ctx->check_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   static const char *timing = std::getenv("MSIM_TIMING");  // developer knob: where the host check spends its time
-  if (timing) std::fprintf(stderr, "[msim] txn check: fetch %.1f ms, %u threads x graph work %.1f ms, total %.1f ms\n",
-                           std::chrono::duration<float, std::milli>(t1 - t0).count(), nt, std::chrono::duration<float, std::milli>(t2 - t1).count(), ctx->check_ms);
+  if (timing) std::fprintf(stderr, "[msim] txn check: fetch %.1f ms, %u threads x graph work %.1f ms, total %.1f ms\n", tm.fetch_ms, tm.threads, tm.work_ms, ctx->check_ms);
   return MSIM_OK;
 }

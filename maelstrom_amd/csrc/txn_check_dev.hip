@@ -807,8 +807,8 @@ u32 lds_bytes_for(u32 nmax, u32 keys, u32 stride) {
 int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim_inst_meta> *hmeta, msim_check_result *h_out, hipStream_t st, u32 *n_host,
                 void **ws_buf, size_t *ws_cap, const CycleMode mode = {}) {
   // mode.witness (msim_explain_txn*; with full): the witness cycles, found by txn_explain_kernel in tp.cycles / tp.steps
-  WitnessSlabs *const wit = mode.full ? mode.witness : nullptr;
-  if (wit) { wit->bind(tp); if (int rc = wit->clear(ctx, st)) return rc; }   // a history the clean passes prove clean keeps the zero record
+  CycleSlabs *const wit = mode.full ? mode.witness : nullptr;
+  if (wit) { bind_cycles(tp, *wit); if (int rc = wit->clear(ctx, st)) return rc; }   // a history the clean passes prove clean keeps the zero record
   // Which kernel takes the first pass: the one with its tables in LDS, a workgroup of sixteen wavefronts per history.  Measured on cfg5,
   // 32768 histories (profiles/r03b_cfg5_txn_check_*, r03k_cfg5_txn_check.txt, r03x_txn_check.txt): tables in an HBM workspace, one
   // wavefront per history: 82 GB of HBM traffic, 130 ms (64 histories in flight per CU); tables in LDS (78 KiB: two histories per CU),
@@ -821,50 +821,34 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
   const PassTimer tm(ctx);
   const uint64_t budget = 6ull << 30;   // as many histories per launch as a few GB of workspace hold (every one of them has its own slice)
   const auto for_host = [](u32 valid) { return valid == NEEDS_HOST || valid == NEEDS_HBM; };
+  // one pass of `kernel` over m histories (those of `list`, or all): chunked_pass with tp.ws_words of workspace each
+  const auto pass = [&](u32 m, const std::vector<u32> *list, auto kernel, u32 threads, u32 lds) {
+    return chunked_pass(ctx, m, tp.ws_words * 4, budget, list, ws_buf, ws_cap, [&](const u32 *d_list, void *ws, u32 first, u32 count) {
+      tp.list = d_list; tp.ws = static_cast<u32 *>(ws); tp.first = first;
+      hipLaunchKernelGGL(kernel, dim3(count), dim3(threads), lds, st, tp);
+    }, tp.out, h_out, n, st);
+  };
   int rc;
-  hipError_t e;
   std::vector<u32> big;   // histories for txn_check_kernel
   if (!hbm_only) {
     // pass 1: tables in LDS
-    tp.ws_words = ws_words_lds(tp.nmax); tp.list = nullptr;
-    const u32 chunk = chunk_for(n, tp.ws_words * 4, budget, msim_dev_flags(ctx));
-    if ((rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
-    tp.ws = static_cast<u32 *>(*ws_buf);
+    tp.ws_words = ws_words_lds(tp.nmax);
     if (tp.lds_bytes > 64 * 1024) MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(txn_check_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds_bytes));
-    const u32 launches = for_chunks(n, chunk, &e, [&](u32 first, u32 count) {
-      tp.first = first;
-      hipLaunchKernelGGL(txn_check_lds_kernel, dim3(count), dim3(wg_threads), tp.lds_bytes, st, tp);
-    });
-    MSIM_HIP_TRY(ctx, e);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = pass(n, nullptr, txn_check_lds_kernel, wg_threads, tp.lds_bytes)) < 0) return rc;
     big = needs(h_out, n, [](u32 valid) { return valid == NEEDS_HBM; });
-    if (tm.trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup, %u launches): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, launches, tm.ms(), big.size(), n);
+    if (tm.trace) std::fprintf(stderr, "[txn-check] LDS pass (%u B per workgroup, %u launches): %.2f ms, %zu of %u histories do not fit\n", tp.lds_bytes, (u32)rc, tm.ms(), big.size(), n);
   } else big = needs(h_out, n, [](u32) { return true; });
   if (!big.empty()) {
     // pass 2: the histories whose tables do not fit LDS, tables in an HBM workspace
-    DevBuf d_list;
-    MSIM_HIP_TRY(ctx, d_list.upload(big.data(), big.size() * 4));
-    tp.ws_words = ws_words_for(tp.nmax, tp.emax); tp.list = d_list.get<u32>();
-    const u32 nb = (u32)big.size();
-    const u32 chunk = chunk_for(nb, tp.ws_words * 4, budget, msim_dev_flags(ctx));
-    if ((rc = grow_ws(ctx, ws_buf, ws_cap, (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
-    tp.ws = static_cast<u32 *>(*ws_buf);
-    const u32 launches = for_chunks(nb, chunk, &e, [&](u32 first, u32 count) {
-      tp.first = first;
-      hipLaunchKernelGGL(txn_check_kernel, dim3(count), dim3(64), 0, st, tp);
-    });
-    MSIM_HIP_TRY(ctx, e);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (tm.trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories (%u launches): done at %.2f ms\n", nb, launches, tm.ms());
+    tp.ws_words = ws_words_for(tp.nmax, tp.emax);
+    if ((rc = pass((u32)big.size(), &big, txn_check_kernel, 64, 0)) < 0) return rc;
+    if (tm.trace) std::fprintf(stderr, "[txn-check] HBM-table pass over %u histories (%u launches): done at %.2f ms\n", (u32)big.size(), (u32)rc, tm.ms());
   }
   if (ctx) ctx->txn_big = (u32)big.size();
   std::vector<u32> todo = needs(h_out, n, for_host);
   if (tm.trace) std::fprintf(stderr, "[txn-check] device passes: %.2f ms, %zu of %u histories for the host\n", tm.ms(), todo.size(), n);
-  if (mode.full && !todo.empty()) {   // the full analysis on the device: the list of histories first in the workspace, then a slice per block
+  if (mode.full && !todo.empty()) {   // the full analysis on the device, over the list of histories that need it
     const u32 m = (u32)todo.size();
-    const size_t list_bytes = ((size_t)m * 4 + 255) & ~(size_t)255;
     tp.emax *= 2;   // (a clean history has few edges per transaction; one without isolation has more)
     tp.ws_words = wit ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
     tp.cm = cm; tp.proscribed = msim_proscribed_anomalies(cm);
@@ -872,26 +856,14 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
     // histories reach the search (as for rw_classify_kernel)
     tp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     tp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    const u32 chunk = chunk_for(m, tp.ws_words * 4, budget, msim_dev_flags(ctx));
-    if ((rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * tp.ws_words * 4)) != MSIM_OK) return rc;
-    tp.list = static_cast<const u32 *>(*ws_buf);
-    tp.ws = reinterpret_cast<u32 *>(static_cast<char *>(*ws_buf) + list_bytes);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(*ws_buf, todo.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-    const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) {
-      tp.first = first;
-      if (wit) hipLaunchKernelGGL(txn_explain_kernel, dim3(count), dim3(64), 0, st, tp);
-      else hipLaunchKernelGGL(txn_classify_kernel, dim3(count), dim3(64), 0, st, tp);
-    });
-    MSIM_HIP_TRY(ctx, e);
-    MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, tp.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
-    MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = wit ? pass(m, &todo, txn_explain_kernel, 64, 0) : pass(m, &todo, txn_classify_kernel, 64, 0)) < 0) return rc;
     todo = needs(h_out, n, for_host);
-    if (tm.trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, launches, tm.ms(), todo.size());
+    if (tm.trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, (u32)rc, tm.ms(), todo.size());
   }
   if (wit && (rc = wit->fetch(ctx, st)) != MSIM_OK) return rc;
   if (!todo.empty()) {
     rc = hand_off(ctx, source_of(tp, hmeta), n, todo, h_out, tp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
-      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], &wit->h_cycles[i], wit->h_steps + (size_t)i * tp.max_steps, tp.max_steps, false);
+      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], wit->hdr(i), wit->rec(i), tp.max_steps, false);
       else msim_txn_check_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i]);
     });
     if (rc != MSIM_OK) return rc;
@@ -913,13 +885,12 @@ int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_s
   std::vector<msim_inst_meta> hm;
   if (int rc = begin_check(ctx, &t0, &hm)) return rc;
   TParams tp;
-  tp.rows = ctx->d_rows; tp.payload = ctx->d_payload; tp.meta = ctx->d_meta; tp.row_off = nullptr; tp.pay_off = nullptr; tp.out = ctx->d_check;
+  std::memset(&tp, 0, sizeof tp);
+  tp.rows = ctx->d_rows; tp.payload = ctx->d_payload; tp.meta = ctx->d_meta; tp.out = ctx->d_check;
   tp.max_rows = ctx->cfg.max_rows; tp.max_pay = ctx->cfg.max_payload_words;
-  tp.nmax = ctx->cfg.max_rows / 2 + 1; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
-  tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
-  tp.cycles = nullptr; tp.steps = nullptr; tp.max_steps = max_steps;
+  tp.nmax = ctx->cfg.max_rows / 2 + 1; tp.emax = tp.nmax * 16; tp.max_steps = max_steps;
   tp.lds_bytes = lds_bytes_for(tp.nmax, ctx->cfg.max_values, ctx->cfg.max_writes_per_key + 1);
-  WitnessSlabs wit;
+  CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
   u32 redone = 0;
   int rc = txn_dev_run(ctx, tp, n, ctx->cfg.consistency_model, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
@@ -935,20 +906,15 @@ static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offset
                      uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool classify,
                      msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  OffsetsBatch b;
-  if (int rc = b.upload(ctx, rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
-  DevBuf d_out, ws; size_t ws_cap = 0;
-  WitnessSlabs wit;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
+  DevBuf ws; size_t ws_cap = 0;
+  CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
   TParams tp;
-  tp.rows = b.rows.get<msim_op>(); tp.payload = b.pay.get<u32>(); tp.meta = nullptr; tp.row_off = b.row_off.get<uint64_t>(); tp.pay_off = b.pay_off.get<uint64_t>();
-  tp.out = d_out.get<msim_check_result>();
-  tp.max_rows = 0; tp.max_pay = 0; tp.nmax = b.longest / 2 + 65; tp.emax = tp.nmax * 16; tp.first = 0; tp.ws = nullptr; tp.ws_words = 0; tp.list = nullptr;
-  tp.cm = 0; tp.proscribed = 0; tp.ccap = 0; tp.big = 0;
-  tp.cycles = nullptr; tp.steps = nullptr; tp.max_steps = max_steps;
+  std::memset(&tp, 0, sizeof tp);
+  f.bind(tp);
+  tp.nmax = f.b.longest / 2 + 65; tp.emax = tp.nmax * 16; tp.max_steps = max_steps;
   tp.lds_bytes = lds_bytes_for(tp.nmax, std::min<u32>(KMAX, tp.nmax * 2 + 16), 17);
   return txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{classify, cycles ? &wit : nullptr});
 }
@@ -976,8 +942,6 @@ extern "C" int msim_explain_txn_batch(int device, const msim_op *rows, const uin
 extern "C" int msim_explain_txn(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, uint32_t n_out) {
   if (!ctx || !cycles || !steps || max_steps == 0) return MSIM_E_INVALID;
   const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
-  if (!rw && ctx->cfg.workload != MSIM_WL_TXN_LIST_APPEND) { ctx->err = "msim_explain_txn: not a txn-list-append or txn-rw-register context"; return MSIM_E_UNSUPPORTED; }
-  if (!ctx->ran) { ctx->err = "msim_explain_txn before msim_run"; return MSIM_E_RANGE; }
-  if (n_out < ctx->n_inst) { ctx->err = "msim_explain_txn: output arrays shorter than the run"; return MSIM_E_RANGE; }
+  if (int rc = explain_refusal(ctx, "msim_explain_txn", rw || ctx->cfg.workload == MSIM_WL_TXN_LIST_APPEND, "a txn-list-append or txn-rw-register", n_out)) return rc;
   return rw ? msim_check_rw_device(ctx, cycles, steps, max_steps) : msim_check_txn_device(ctx, cycles, steps, max_steps);
 }

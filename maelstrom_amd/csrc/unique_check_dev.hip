@@ -171,7 +171,8 @@ static int unique_dev_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *w
 int msim_check_unique_device(msim_ctx *ctx) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   UParams up;
-  up.rows = ctx->d_rows; up.meta = ctx->d_meta; up.out = ctx->d_check; up.max_rows = ctx->cfg.max_rows; up.ws = nullptr; up.table_slots = 0; up.first = 0;
+  std::memset(&up, 0, sizeof up);
+  up.rows = ctx->d_rows; up.meta = ctx->d_meta; up.out = ctx->d_check; up.max_rows = ctx->cfg.max_rows;
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   int rc = unique_dev_run(ctx, up, ctx->n_inst, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->stream, true);
   if (rc != MSIM_OK) return rc;
@@ -186,15 +187,12 @@ int msim_check_unique_device(msim_ctx *ctx) {
 // n_rows[i] of them used), with the device checker of msim_check; out[i] as msim_check_unique_rows would fill it.
 extern "C" int msim_check_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0) return MSIM_E_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return MSIM_E_HIP;
-  BatchCtx tmp_ctx(device); msim_ctx *ctx = &tmp_ctx;
-  SlabBatch b;
-  if (int rc = b.upload(ctx, rows, n_rows, max_rows, n_histories)) return rc;
-  DevBuf d_out, ws; size_t ws_cap = 0;
-  MSIM_HIP_TRY(ctx, d_out.alloc((size_t)n_histories * sizeof(msim_check_result)));
+  BatchFrame<SlabBatch> f(device); msim_ctx *ctx = &f.ctx;
+  if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, n_rows, max_rows, n_histories)) return rc;
+  DevBuf ws; size_t ws_cap = 0;
   UParams up;
-  up.rows = b.rows.get<msim_op>(); up.meta = b.meta.get<msim_inst_meta>(); up.out = d_out.get<msim_check_result>();
-  up.max_rows = max_rows; up.ws = nullptr; up.table_slots = 0; up.first = 0;
+  std::memset(&up, 0, sizeof up);
+  up.rows = f.b.rows.get<msim_op>(); up.meta = f.b.meta.get<msim_inst_meta>(); up.out = f.d_out.get<msim_check_result>(); up.max_rows = max_rows;
   if (int rc = unique_dev_run(ctx, up, n_histories, ws.addr(), &ws_cap, nullptr, false)) return rc;
   MSIM_HIP_TRY(ctx, hipMemcpy(out, up.out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost));
   return MSIM_OK;

@@ -2,7 +2,8 @@
 // the checker units (tools/check_batch_asan.py compiles those units and this file with -fsanitize=address,undefined and runs it): what
 // the host side of the checkers (csrc/check_run.h) allocates, it frees — LeakSanitizer at exit — and nothing reads or writes beside an
 // allocation.  The batch of each entry is the five histories of tests/test_check_batch_edges_gpu.py: [no rows, one the device hands to
-// the host, no rows, rows without payload words, no rows].  Developer tool; prints one line per entry, exits 0 when every entry returned
+// the host, no rows, rows without payload words, no rows]; the explaining kafka and set-full entries have a history whose records the
+// explaining kernel writes among the five.  Developer tool; prints one line per entry, exits 0 when every entry returned
 // MSIM_OK.
 #include <cstdio>
 #include <cstring>
@@ -48,12 +49,15 @@ struct Offsets {   // the offsets layout of a batch
   }
 };
 
-struct Slabs {   // the slab layout of a batch
-  std::vector<msim_op> rows; std::vector<uint32_t> n_rows; uint32_t max_rows = 1;
+struct Slabs {   // the slab layout of a batch (the payload words alike, for the set-full entries)
+  std::vector<msim_op> rows; std::vector<uint32_t> n_rows, pay; uint32_t max_rows = 1, max_pay = 1;
   explicit Slabs(const std::vector<History> &hs) {
-    for (const History &h : hs) if (h.rows.size() > max_rows) max_rows = (uint32_t)h.rows.size();
-    rows.resize(hs.size() * max_rows);
-    for (size_t i = 0; i < hs.size(); i++) { n_rows.push_back((uint32_t)hs[i].rows.size()); std::copy(hs[i].rows.begin(), hs[i].rows.end(), rows.begin() + i * max_rows); }
+    for (const History &h : hs) { if (h.rows.size() > max_rows) max_rows = (uint32_t)h.rows.size(); if (h.pay.size() > max_pay) max_pay = (uint32_t)h.pay.size(); }
+    rows.resize(hs.size() * max_rows); pay.resize(hs.size() * max_pay);
+    for (size_t i = 0; i < hs.size(); i++) {
+      n_rows.push_back((uint32_t)hs[i].rows.size());
+      std::copy(hs[i].rows.begin(), hs[i].rows.end(), rows.begin() + i * max_rows); std::copy(hs[i].pay.begin(), hs[i].pay.end(), pay.begin() + i * max_pay);
+    }
   }
 };
 
@@ -97,6 +101,30 @@ int main() {
     const Offsets b({none, far, none, sends, none});
     report("msim_check_kafka_batch", msim_check_kafka_batch(0, b.rows.data(), b.ro.data(), b.pay.data(), b.po.data(), N, 3, out.data(), &n_host), out, &n_host);
     report("msim_classify_kafka_batch", msim_classify_kafka_batch(0, b.rows.data(), b.ro.data(), b.pay.data(), b.po.data(), N, 3, out.data(), &n_host), out, &n_host);
+    // the explanation: offset 3 acknowledged twice, with two messages, is the explaining kernel's (it writes findings); `far` stays the host walk's
+    History twice;
+    for (uint32_t m : {5u, 6u}) { twice.rows.push_back(row(twice.rows.size(), MSIM_T_INVOKE, MSIM_F_SEND, 0, 1u | (m << 6) | (0x7FFu << 17))); twice.rows.push_back(row(twice.rows.size(), MSIM_T_OK, MSIM_F_SEND, 0, 1u | (m << 6) | (3u << 17))); }
+    const Offsets x({none, far, none, twice, none});
+    std::vector<msim_kafka_explain> hdr(N);
+    std::vector<msim_kafka_finding> findings(N * STEPS);
+    report("msim_explain_kafka_batch", msim_explain_kafka_batch(0, x.rows.data(), x.ro.data(), x.pay.data(), x.po.data(), N, 3, out.data(), hdr.data(), findings.data(), STEPS, &n_host), out, &n_host);
+    std::printf("%-28s findings %u %u (truncated %u %u)\n", "", hdr[1].n_findings, hdr[3].n_findings, hdr[1].truncated, hdr[3].truncated);
+    failures += hdr[3].n_findings == 0;
+  }
+  {   // set-full (g-set): element 1 is read once and then missing from a later read (lost), element 2 is never read; adds alone
+    History lost, adds;
+    auto op = [&](History &h, uint32_t type, uint32_t f, uint32_t p, uint32_t v, uint32_t len = 0) { h.rows.push_back(row(h.rows.size(), type, f, p, v, len)); };
+    for (uint32_t e = 0; e < 3; e++) { op(lost, MSIM_T_INVOKE, MSIM_F_ADD, e, e); op(lost, MSIM_T_OK, MSIM_F_ADD, e, e); }
+    for (uint32_t bits : {3u, 1u}) { op(lost, MSIM_T_INVOKE, MSIM_F_READ, 0, 0xFFFFFFFFu); op(lost, MSIM_T_OK, MSIM_F_READ, 0, (uint32_t)lost.pay.size(), 1); lost.pay.push_back(bits); }
+    for (uint32_t e = 0; e < 2; e++) { op(adds, MSIM_T_INVOKE, MSIM_F_ADD, e, e); op(adds, MSIM_T_OK, MSIM_F_ADD, e, e); }
+    const Slabs b({none, lost, none, adds, none});
+    std::vector<msim_set_explain> hdr(N);
+    std::vector<msim_set_element> elements(N * STEPS);
+    report("msim_check_set_full_batch", msim_check_set_full_batch(0, MSIM_WL_G_SET, 3, b.rows.data(), b.n_rows.data(), b.max_rows, b.pay.data(), b.max_pay, 32, N, out.data()), out);
+    report("msim_explain_set_full_batch", msim_explain_set_full_batch(0, MSIM_WL_G_SET, 3, b.rows.data(), b.n_rows.data(), b.max_rows, b.pay.data(), b.max_pay, 32, N, out.data(),
+                                                                       hdr.data(), elements.data(), STEPS), out);
+    std::printf("%-28s lost %u, never read %u, stale %u\n", "", hdr[1].n_lost, hdr[1].n_never_read, hdr[1].n_stale);
+    failures += hdr[1].n_lost + hdr[1].n_never_read + hdr[1].n_stale == 0;
   }
   {   // lin-kv: key 0 holds 1, nine writes overlap, a read of a value nobody wrote; a stale read
     History wide, stale;

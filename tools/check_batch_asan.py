@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools", "hipemu"))
 import build_emu as B   # noqa: E402
 
-SANITIZED = ["lin_check_dev.hip", "txn_check_dev.hip", "rw_check_dev.hip", "kafka_check_dev.hip", "pn_check_dev.hip", "unique_check_dev.hip", "perf_check_dev.hip",
+SANITIZED = ["checker.hip", "set_check.cpp", "lin_check_dev.hip", "txn_check_dev.hip", "rw_check_dev.hip", "kafka_check_dev.hip", "pn_check_dev.hip", "unique_check_dev.hip", "perf_check_dev.hip",
              "lin_check.cpp", "txn_check.cpp", "kafka_check.cpp", "pn_check.cpp", "guard.cpp"]
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-O1"]
 
