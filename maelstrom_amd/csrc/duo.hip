@@ -197,6 +197,24 @@ constexpr bool DUO_BPLAN_ON = false;
 constexpr bool DUO_BPLAN_ON = true;
 #endif
 constexpr u32 DUO_BPLAN_BYTES = 32u * 4u;   // [origin]: what a remembered flood adds to its half's sum of n_arr | its rounds << 16
+// FLOOD TABLE.  A record is a function of the topology, the fan-out rule and the picked node alone (see "WHY A RECORD DOES NOT DEPEND ON THE
+// STATE" in sim_kernel_duo), so the memo tables of all wavefronts of all launches of a context are one table.  It is made once per context
+// (msim_duo_make_flood_table): one wavefront of this kernel runs two clusters of the context's configuration on slabs of its own, and its
+// epilogue copies what its recording path has left in LDS (the records, the block plan's totals, mm_known and mm_full) to a device buffer
+// of the context; every later wavefront starts from a copy of that buffer instead of an empty table.  Nothing else changes: an origin the
+// table lacks is recorded by the wavefront that meets it, as before.  The buffer: DUO_TABLE_HDR words of header (mm_known, mm_full, the
+// N and the topology | echoback << 8 it was made for), the records, the totals.
+// -DDUO_NO_FLOOD_TABLE compiles it out for A/B runs (the kernel is then the previous one, instruction for instruction).  The -DDUO_PROF
+// builds leave it out, since their tests count a wavefront's own recordings; -DDUO_PROF_TABLE is the profile build of this path.
+#if defined(DUO_NO_FLOOD_TABLE) || (defined(DUO_PROF) && !defined(DUO_PROF_TABLE))
+constexpr bool DUO_TABLE_ON = false;
+#else
+constexpr bool DUO_TABLE_ON = true;
+#endif
+constexpr u32 DUO_TABLE_HDR = 4u;   // words
+constexpr u32 DUO_TABLE_BYTES = DUO_TABLE_HDR * 4u + DUO_MEMO_BYTES + DUO_BPLAN_BYTES;
+constexpr u32 DUO_TABLE_COPY16 = (DUO_MEMO_BYTES + (DUO_BPLAN_ON ? DUO_BPLAN_BYTES : 0u)) / 16u;   // what a wavefront has of it in LDS, 16 bytes a lane and pass
+static_assert(DUO_MEMO_BYTES % 16u == 0 && DUO_BPLAN_BYTES % 16u == 0 && DUO_TABLE_COPY16 <= 192u, "the table is copied 16 bytes a lane, three passes at most");
 constexpr u32 DUO_SRUN_FAR = 8192u;  // more than one run can add to a cluster's rounds: 31 ops of a block x (a record of at most 255 rounds + 1)
 #ifndef DUO_PAIR_WAIT
 // Wave-rounds.  A wait that ends in a shared op round leaves the two clusters in step (their floods start together, so the next wait is the
@@ -226,6 +244,8 @@ struct DuoParams {
   u32 off_log2;      // RND: byte offset of the Q24 log2 table (one per wavefront, behind both clusters)
   u32 off_dc;        // flood instantiation: byte offset of the block of 32 generator draws inside a cluster's LDS region
   u32 off_memo;      // memo instantiation: byte offset of the wavefront's table of remembered floods (behind both clusters' regions)
+  u32 table_fill;    // memo instantiation: this launch MAKES the flood table: its one wavefront's epilogue writes `table` (else the prologue reads it)
+  u32 *table;        // memo instantiation: the context's flood table (see "FLOOD TABLE"), or null: every wavefront starts with an empty one
 };
 
 // -ln(u), u = (r+1)/2^32, Q16, integer only: the sampler of engine.hip / the oracle over a copy of the table in LDS
@@ -610,6 +630,22 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // (SGPRs); DUO_BPLAN_TOT(origin) = the sum of the origin's record over the half's lanes | its rounds << 16 (LDS, behind the memo table).
   u32 mm_full = 0, bp_vw_lo = 0, bp_vw_hi = 0;
 #define DUO_BPLAN_TOT(org_) (reinterpret_cast<u32 *>(smem + dp.off_memo + DUO_MEMO_BYTES)[(org_) & 31u])
+  // FLOOD TABLE: the wavefront starts from the context's table (see there) instead of an empty one: the records and the totals go from the
+  // buffer to LDS as they lie there, 16 bytes a lane, the two masks come from its header.  The launch that makes the table starts empty.
+  if constexpr (MEMO && DUO_TABLE_ON) {
+    if (dp.table != nullptr && dp.table_fill == 0u) {
+      DUO_LANE_NOW(tb_l);
+      const uint4 *const tb_src = reinterpret_cast<const uint4 *>(dp.table + DUO_TABLE_HDR);
+      uint4 *const tb_dst = reinterpret_cast<uint4 *>(smem + dp.off_memo);
+      uint4 tb_v[3] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+#pragma unroll
+      for (u32 k = 0; k < 3u; k++) if (tb_l + 64u * k < DUO_TABLE_COPY16) tb_v[k] = tb_src[tb_l + 64u * k];
+#pragma unroll
+      for (u32 k = 0; k < 3u; k++) if (tb_l + 64u * k < DUO_TABLE_COPY16) tb_dst[tb_l + 64u * k] = tb_v[k];
+      mm_known = DUO_UNIFORM(dp.table[0]); mm_full = DUO_UNIFORM(dp.table[1]);
+      wave_lds_fence();
+    }
+  }
   // a completed word is SEEN: a quiescent flood half of seen_m_ whose next_value is a multiple of 32 holds in sw the word its last value
   // has just completed, current in HBM; if that is the next word to count and it is all ones in all N node lanes, it is counted.  Called
   // wherever a steady half can stand at such a point: in front of the plan, where the loop takes a broadcast that opens a word, and behind
@@ -2091,6 +2127,18 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #endif
     p.meta[inst_out] = m;
   }
+  // FLOOD TABLE: the launch that makes the table is this one wavefront; what its recording path has left in LDS becomes the context's
+  // table (the row of an origin whose recording never ended is there as well, and no bit of mm_known stands for it)
+  if constexpr (MEMO && DUO_TABLE_ON) {
+    if (dp.table_fill != 0u && dp.table != nullptr) {
+      DUO_LANE_NOW(tf_l);
+      const uint4 *const tf_src = reinterpret_cast<const uint4 *>(smem + dp.off_memo);
+      uint4 *const tf_dst = reinterpret_cast<uint4 *>(dp.table + DUO_TABLE_HDR);
+#pragma unroll
+      for (u32 k = 0; k < 3u; k++) if (tf_l + 64u * k < DUO_TABLE_COPY16) tf_dst[tf_l + 64u * k] = tf_src[tf_l + 64u * k];
+      if (tf_l == 0u) reinterpret_cast<uint4 *>(dp.table)[0] = make_uint4(mm_known, BPLAN ? mm_full : 0u, N, p.cfg.topology | (dp.echoback << 8));
+    }
+  }
 }
 
 }  // namespace
@@ -2140,8 +2188,9 @@ static hipError_t duo_launch(const DuoParams &dp, dim3 grid, size_t lds, hipStre
 }
 
 // Launches the duo kernel for n clusters on `st`; returns MSIM_LAYOUT_DOES_NOT_FIT if the cluster state does not fit (the caller
-// then runs the one-cluster-per-wavefront kernels).
-hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
+// then runs the one-cluster-per-wavefront kernels).  `fill`: the launch that makes the flood table kp.duo_table (product limits; nothing is
+// launched, and *fill_memo stays false, where the configuration does not take the memo instantiation).
+static hipError_t duo_launch_any(const KParams &kp, uint32_t n, hipStream_t st, bool fill, bool *fill_memo) {
   const msim_config &c = kp.cfg;
   DuoParams dp;
   dp.k = kp; dp.n_inst = n;
@@ -2200,7 +2249,24 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   dp.round_limit = (kp.dev_flags & 0x100u) ? 2000000u : ROUND_LIMIT;
   // developer / tests: MSIM_DUO_ROUND_LIMIT=<rounds> stops every cluster of this layout at that round (MSIM_FLAG_ROUND_LIMIT), so that the
   // limit can be made to fall anywhere, e.g. inside a run of reads (read at every launch: a test sweeps it within one process)
-  if (const char *rl = std::getenv("MSIM_DUO_ROUND_LIMIT")) { const unsigned long v = std::strtoul(rl, nullptr, 0); if (v > 0 && v < ROUND_LIMIT) dp.round_limit = (u32)v; }
+  bool dev_limit = false;
+  if (const char *rl = std::getenv("MSIM_DUO_ROUND_LIMIT")) { const unsigned long v = std::strtoul(rl, nullptr, 0); if (v > 0 && v < ROUND_LIMIT) { dp.round_limit = (u32)v; dev_limit = true; } }
+  // the flood table: read by the memo instantiation alone; the launch that makes it runs under the product's round limit.  A launch under
+  // MSIM_DUO_ROUND_LIMIT starts from empty tables, as before: WHERE a cluster that the limit stops is stopped follows the alignment of the
+  // two halves' rounds (a half's limit is looked at where R0's block is entered), a half that replays its first floods is aligned with
+  // its partner otherwise than one that records them, and the limit sweeps of the tests hold builds against each other limit for limit,
+  // stopped instances included (measured with the table under the limits, -DDUO_PAIR_WAIT=2, two headline clusters: the same flags and
+  // unflagged instances everywhere, a stopped cluster stopped up to three rounds later at 37 of the 121 limits; at the default wait none)
+  // MSIM_DUO_TABLE_UNDER_LIMIT=1 (developer / tests, read at every launch like the limit): such a launch reads the table all the same, so that
+  // a test can hold the replay from a table's record against the build without the table near a limit (flags and unflagged instances).
+  if (dev_limit) { const char *tu = std::getenv("MSIM_DUO_TABLE_UNDER_LIMIT"); if (tu && std::strtoul(tu, nullptr, 0) != 0) dev_limit = false; }
+  dp.table = memo && DUO_TABLE_ON && (fill || !dev_limit) ? kp.duo_table : nullptr;   // (a context's table is made whatever the first launch runs under)
+  dp.table_fill = fill ? 1u : 0u;
+  if (fill) {
+    if (!dp.table) return hipSuccess;
+    *fill_memo = true;
+    dp.round_limit = ROUND_LIMIT;
+  }
   size_t lds = 2 * off + (rnd ? 257 * 4 + 12 : 0);
   if (memo) lds += DUO_MEMO_BYTES;
   if (memo && DUO_BPLAN_ON) lds += DUO_BPLAN_BYTES;   // the block plan's totals per origin, behind the table (4736 bytes per wavefront at the headline shape)
@@ -2209,4 +2275,46 @@ hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) {
   if (rnd) return deg4 ? duo_launch<false, true, true>(dp, grid, lds, st) : duo_launch<false, false, true>(dp, grid, lds, st);
   if (lat0) return deg4 ? duo_launch<true, true, false>(dp, grid, lds, st) : duo_launch<true, false, false>(dp, grid, lds, st);
   return deg4 ? duo_launch<false, true, false>(dp, grid, lds, st) : duo_launch<false, false, false>(dp, grid, lds, st);
+}
+
+hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st) { return duo_launch_any(kp, n, st, false, nullptr); }
+
+// Makes the flood table of a context (see "FLOOD TABLE" and wave_common.h): one wavefront, two clusters `first` and `first` + 1 of the
+// configuration on slabs of their own, which are freed again; the table comes from the library's allocator like every slab.
+hipError_t msim_duo_make_flood_table(const KParams &plan_kp, uint64_t first, hipStream_t st, u32 **table, u32 *origins) {
+  *table = nullptr; *origins = 0;
+  const msim_config &c = plan_kp.cfg;
+  if (!(DUO_TABLE_ON && DUO_MEMO_BUILD) || !msim_duo_eligible(c)) return hipSuccess;
+  // (whether the configuration takes the memo instantiation is the launcher's to say: *fill_memo below)
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_rows = up(2 * (size_t)c.max_rows * sizeof(msim_op)), b_pay = up(2 * (size_t)c.max_payload_words * 4);
+  const size_t b_stats = up(2 * sizeof(msim_net_stats)), b_meta = up(2 * sizeof(msim_inst_meta)), b_scr = up(2 * (size_t)plan_kp.scratch_words * 4);
+  unsigned char *slab = nullptr; u32 *tab = nullptr;
+  hipError_t e = msim_dev_malloc(&tab, DUO_TABLE_BYTES);
+  if (e == hipSuccess) e = msim_dev_malloc(&slab, b_rows + b_pay + b_stats + b_meta + b_scr);
+  if (e == hipSuccess) e = hipMemsetAsync(tab, 0, DUO_TABLE_BYTES, st);
+  // (MSIM_POISON: the wavefront's own slabs start from the byte the context's slabs start from, the table does not)
+  if (e == hipSuccess && msim_poison_byte() >= 0) e = hipMemsetAsync(slab, msim_poison_byte(), b_rows + b_pay + b_stats + b_meta + b_scr, st);
+  bool memo = false;
+  if (e == hipSuccess) {
+    KParams kp = plan_kp;
+    kp.first_instance = first;
+    unsigned char *q = slab;
+    kp.rows = reinterpret_cast<msim_op *>(q); q += b_rows;
+    kp.payload = reinterpret_cast<u32 *>(q); q += b_pay;
+    kp.stats = reinterpret_cast<msim_net_stats *>(q); q += b_stats;
+    kp.meta = reinterpret_cast<msim_inst_meta *>(q); q += b_meta;
+    kp.scratch = reinterpret_cast<u32 *>(q);
+    kp.journal = nullptr; kp.duo_table = tab;
+    e = duo_launch_any(kp, 2, st, true, &memo);
+    if (e == MSIM_LAYOUT_DOES_NOT_FIT) e = hipSuccess;   // (the launches of this context take other kernels)
+  }
+  u32 hdr[DUO_TABLE_HDR] = {0, 0, 0, 0};
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && memo) e = hipMemcpy(hdr, tab, sizeof(hdr), hipMemcpyDeviceToHost);
+  if (slab) { const hipError_t ef = msim_dev_free(slab); if (e == hipSuccess) e = ef; }
+  if (e == hipSuccess && memo && (hdr[2] != plan_kp.N || hdr[3] != (c.topology | ((c.node_program == MSIM_NODE_BCAST_FF_ECHOBACK ? 1u : 0u) << 8)))) e = hipErrorUnknown;   // (the wavefront did not reach its epilogue)
+  if (e != hipSuccess || !memo) { if (tab) (void)msim_dev_free(tab); return e; }
+  *table = tab; *origins = hdr[0];
+  return hipSuccess;
 }

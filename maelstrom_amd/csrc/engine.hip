@@ -195,11 +195,26 @@ static const WorkloadCheck *workload_check(uint32_t workload) {
   return nullptr;
 }
 
+// The flood table of the two-clusters-per-wavefront broadcast kernel (duo.hip, "FLOOD TABLE"): what every wavefront of every launch of
+// this context would otherwise record for itself is recorded once, by one wavefront, before the context's first launch.  The host waits
+// for that launch here, once; after it the table is a constant, so launches on any stream need no ordering against it.
+// MSIM_DUO_TABLE_FIRST (developer / tests) = the instance number of the first of that wavefront's two clusters: the table does not depend on it.
+static int ensure_flood_table(msim_ctx *ctx, const LaunchPlan &plan, uint32_t flags) {
+  if (ctx->duo_table_tried || (flags & 0x200u)) return MSIM_OK;   // (bit 9: one cluster per wavefront, no launch reads a table)
+  ctx->duo_table_tried = true;
+  uint64_t first = 0;
+  if (const char *f = std::getenv("MSIM_DUO_TABLE_FIRST")) first = std::strtoull(f, nullptr, 0);
+  u32 origins = 0;
+  MSIM_HIP_TRY(ctx, msim_duo_make_flood_table(plan.kp, first, ctx->stream, &ctx->d_duo_table, &origins));
+  if (ctx->d_duo_table && (flags & 0x1000u)) std::fprintf(stderr, "[duo] flood table: %d of %u origins\n", __builtin_popcount(origins), ctx->cfg.n_nodes);
+  return MSIM_OK;
+}
+
 static int poison_buffers(msim_ctx *ctx, hipStream_t st) {
   const msim_config &c = ctx->cfg;
   // developer check for reads of memory no kernel of this launch wrote: MSIM_POISON=<byte> fills every device buffer of the context
   // with that byte before each launch (HBM comes back from hipMalloc with whatever its last owner left there); results must not depend on it
-  static const int poison = []() { const char *p = std::getenv("MSIM_POISON"); return p ? (int)(std::strtoul(p, nullptr, 0) & 0xFFu) : -1; }();
+  const int poison = msim_poison_byte();
   if (poison >= 0) {
     MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_rows, poison, (size_t)ctx->cap_inst * c.max_rows * sizeof(msim_op), st));
     MSIM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_payload, poison, (size_t)ctx->cap_inst * c.max_payload_words * 4, st));
@@ -250,6 +265,7 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   if (plan.rc != MSIM_OK) { ctx->err = plan.err; return plan.rc; }   // (a configuration that cannot be launched allocates nothing)
   int rc = ensure_buffers(ctx, n, plan);
   if (rc != MSIM_OK) return rc;
+  if ((rc = ensure_flood_table(ctx, plan, flags)) != MSIM_OK) return rc;
   // an armed context queues the checker straight behind this simulation (below, after ev1).  Its scratch grows HERE, in front of the
   // launch: a hipFree / hipMalloc between the two kernels would stall every context's launches.  A failure is msim_check's to report.
   // (the workloads without a row in workload_check: msim_check is one launch of checker.hip's kernel over the slabs)
@@ -259,6 +275,7 @@ static int run_impl(msim_ctx *ctx, uint64_t first, uint32_t n, hipStream_t st, b
   kp.first_instance = first;
   kp.rows = ctx->d_rows; kp.payload = ctx->d_payload; kp.stats = ctx->d_stats; kp.meta = ctx->d_meta;
   kp.scratch = ctx->d_scratch; kp.journal = reinterpret_cast<uint4 *>(ctx->d_journal);
+  kp.duo_table = ctx->d_duo_table;
   // The slabs this launch overwrites are what a zero-copy consumer of the previous run (msim_device_buffers_get) reads — bench.py's
   // sums are queued on the null stream and never waited for.  Since the host no longer waits in msim_check for a check that was queued
   // ahead, it can launch while those kernels still wait for a place on the chip (measured: 3 of 5 benchmark runs then summed rows of
@@ -588,6 +605,7 @@ extern "C" void msim_destroy(msim_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->check_queued && ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // a queued check nobody took still reads the slabs
   free_buffers(ctx);
+  if (ctx->d_duo_table) (void)msim_dev_free(ctx->d_duo_table);
   msim_gather_free(ctx);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

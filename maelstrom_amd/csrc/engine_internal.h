@@ -31,6 +31,9 @@ struct msim_ctx {
   uint64_t scratch_words_per_inst = 0;
   msim_check_result *d_check = nullptr;
   msim_event *d_journal = nullptr;
+  // duo.hip's flood table: made once, before the context's first launch (engine.hip ensure_flood_table), a constant of the configuration
+  // from then on: it outlives the slabs above, MSIM_POISON does not fill it, msim_destroy frees it.  Null where no launch reads one.
+  uint32_t *d_duo_table = nullptr; bool duo_table_tried = false;
   // host (pinned) mirrors
   msim_op *h_rows = nullptr;
   uint32_t *h_payload = nullptr;
@@ -88,7 +91,7 @@ static inline unsigned msim_host_threads() {
 // The developer switches in force for a context: those set through msim_set_dev_flags ORed with MSIM_DEV_FLAGS of the environment
 // (read once per process).  0x100 round limit x20, 0x200 one cluster per wavefront, 0x400 fail instead of falling back to it,
 // 0x800 checkers on the host cores, 0x1000 time the checkers' passes (and count their launches) on stderr and name the kernel each launch
-// took (`[layout] <kernel> <n>`), 0x2000 the checkers' HBM-table kernels / the lin-kv search's tiny pools, 0x10000 at most 7 histories per
+// took (`[layout] <kernel> <n>`) and the flood table a context makes (`[duo] flood table: <k> of <n> origins`, duo.hip), 0x2000 the checkers' HBM-table kernels / the lin-kv search's tiny pools, 0x10000 at most 7 histories per
 // launch in the chunked checker loops (txn LDS and HBM-table passes, rw, unique-ids HBM tables: a partial last chunk, first > 0).  The
 // rw-register classification (rw_check_dev.hip): 0x2000 a matrix of 16 transactions per cyclic component and larger ones to the host,
 // 0x20000 a matrix of 16 with the search in the workspace behind it, as every component beyond 256 has it.  0x40000 the set-full / echo
@@ -97,6 +100,12 @@ static inline unsigned msim_host_threads() {
 static inline uint32_t msim_dev_flags(const msim_ctx *ctx) {
   static const uint32_t env = []() { const char *e = std::getenv("MSIM_DEV_FLAGS"); return e ? (uint32_t)std::strtoul(e, nullptr, 0) : 0u; }();   // (decimal, 0x.. or 0..)
   return env | (ctx ? ctx->dev_flags : 0u);
+}
+
+// MSIM_POISON=<byte> (developer check for reads of memory no kernel of a launch wrote, read once per process): the byte, or -1
+static inline int msim_poison_byte() {
+  static const int poison = []() { const char *p = std::getenv("MSIM_POISON"); return p ? (int)(std::strtoul(p, nullptr, 0) & 0xFFu) : -1; }();
+  return poison;
 }
 
 // engine.hip: compacts the used prefix of every instance's row / payload slab into ctx->d_grows / ctx->d_gpay on the device

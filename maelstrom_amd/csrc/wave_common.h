@@ -43,6 +43,7 @@ struct KParams {
   u32 raft_log_cap;   // raft: entries per node log
   u32 dev_flags;      // developer switches (env MSIM_DEV_FLAGS): 1 = cascade rounds inline, 2 = no lone-operation path
   u32 mk_tcap, mk_ccap;   // multi-key transactional node: thunks a node may create; slots of a node's thunk cache (power of two)
+  u32 *duo_table;     // duo.hip: the context's flood table (msim_duo_make_flood_table), or null; the launch's to fill like the slabs
 };
 
 // ---- RNG (counter-based) ---------------------------------------------------------
@@ -192,6 +193,11 @@ hipError_t msim_launch_kafkag(const KParams &kp, uint32_t n, size_t lds, hipStre
 bool msim_duo_eligible(const msim_config &c);
 uint64_t msim_duo_extra_scratch_words(const msim_config &c);
 hipError_t msim_launch_duo(const KParams &kp, uint32_t n, hipStream_t st);
+// The flood table of a context (see "FLOOD TABLE" in duo.hip): what one wavefront of the memo instantiation records about the floods of
+// this configuration, made once by a launch of that wavefront on `st`, which is waited for.  *table = the device buffer (msim_dev_free
+// frees it), or null where no launch of this configuration would read one; *origins = the origins it remembers.  `first` = the
+// instance number of the first of the wavefront's two clusters (any two give the same table).
+hipError_t msim_duo_make_flood_table(const KParams &plan_kp, uint64_t first, hipStream_t st, u32 **table, u32 *origins);
 // raft4.hip: four Raft clusters per wavefront (lin-kv over the Raft node program, clusters of <= 16 endpoints)
 bool msim_raft4_eligible(const msim_config &c);
 uint64_t msim_raft4_extra_scratch_words(const msim_config &c);

@@ -29,6 +29,9 @@ clusters taken in runs (16 bits), the steady run of csrc/duo.hip; those two figu
 MEMO=1 RUN=1 PLAN=1: the library is that build with -DDUO_PROF_PLAN as well (tools/variant_lib.sh profplan duo.hip -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN -DDUO_PROF_PLAN),
 whose upper instance carries in reserved[2], in place of the recordings dropped: the block plans that took an op (16 bits) and the ops they took (16 bits), the
 block plan of csrc/duo.hip; printed with the ops the runs' loop still took (the runs' reads and broadcasts less the plans' ops).
+(Every -DDUO_PROF build leaves the flood table out unless -DDUO_PROF_TABLE is given as well, see DUO_TABLE_ON in csrc/duo.hip: without it a wavefront records
+its own floods, as the parent of round 21 did; with it, e.g. tools/variant_lib.sh profruntab duo.hip -DDUO_PROF -DDUO_PROF_MEMO -DDUO_PROF_RUN -DDUO_PROF_TABLE, "floods
+recorded" counts what the wavefront still had to record itself.  The switches above read the same words either way.)
 (Every -DDUO_PROF build WITHOUT -DDUO_PROF_RUN leaves the steady run out, see DUO_SRUN_ON in csrc/duo.hip: its figures split the op wave-rounds of the kernel
 without the run by the body that took them; the counts of the kernel as it ships are those of the RUN=1 build.)"""
 import os

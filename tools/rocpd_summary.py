@@ -43,6 +43,12 @@ OURS = ("sim_kernel", "check_kernel", "raft_kernel", "raft4_kernel", "txn_kernel
         "hat8_kernel", "uid8_kernel", "crdt8_kernel", "bcast8_kernel", "dt_kernel", "dt8_kernel", "txn_check_lds_kernel")
 
 
+# Launches of ONE workgroup are left out of the per-dispatch averages: duo.hip's flood table is made by a launch of one wavefront of the
+# simulation kernel itself, once per engine context, and an average over "dispatches" that counts it beside the launches of 2048 is no
+# launch's figure.  (A kernel that is only ever launched with one workgroup then has no row; none of the engine's is.)
+MANY = "where d.grid_size_x > d.workgroup_size_x"
+
+
 def counters_json(paths, out):
     """--counters OUT.json: per-kernel averages per dispatch of every PMC counter collected (all passes), plus the dispatch
     statistics of the kernel trace, for the engine's own kernels — what bench.py's roofline.secondary quotes."""
@@ -55,11 +61,13 @@ def counters_json(paths, out):
         except IndexError:
             continue
         q = (f"select s.display_name, count(*), avg(d.end-d.start), max(d.group_segment_size), max(s.arch_vgpr_count), max(s.sgpr_count), max(d.grid_size_x), max(d.workgroup_size_x) "
-             f"from '{kd}' d join '{ks}' s on d.kernel_id = s.id group by 1")
+             f"from '{kd}' d join '{ks}' s on d.kernel_id = s.id {MANY} group by 1")
+        many = MANY
         try:
             rows = list(con.execute(q))
         except sqlite3.OperationalError:
-            q = q.replace(", max(d.grid_size_x), max(d.workgroup_size_x)", ", 0, 0")
+            q = q.replace(", max(d.grid_size_x), max(d.workgroup_size_x)", ", 0, 0").replace(MANY, "")
+            many = ""
             rows = list(con.execute(q))
         for name, nd, avg, lds, vg, sg, gx, wx in rows:
             if any(k in name for k in OURS):
@@ -74,7 +82,7 @@ def counters_json(paths, out):
         except IndexError:
             continue
         q = (f"select s.display_name, i.name, sum(e.value), count(distinct d.id) from '{pe}' e join '{pi}' i on e.pmc_id = i.id "
-             f"join '{kd}' d on e.event_id = d.event_id join '{ks}' s on d.kernel_id = s.id group by 1, 2")
+             f"join '{kd}' d on e.event_id = d.event_id join '{ks}' s on d.kernel_id = s.id {many} group by 1, 2")
         for name, ctr, tot, nd in con.execute(q):
             if any(k in name for k in OURS):
                 acc.setdefault(name, {"counters_per_dispatch": {}})["counters_per_dispatch"][ctr] = tot / max(nd, 1)
