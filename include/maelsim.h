@@ -811,6 +811,7 @@ const char *msim_last_error(const msim_ctx *ctx);
 void msim_destroy(msim_ctx *ctx);
 
 #include "maelsim_kafka_explain.h"   /* kafka: the explained verdicts (the contract: above msim_check_unique_batch) */
+#include "maelsim_small_explain.h"   /* pn-counter / g-counter, unique-ids, echo: the explained verdicts (the contract: that file's comments) */
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,9 @@ COMM_ID_BYTES = 128
 # kafka_explain_kernel's capacities (csrc/kafka_check_dev.hip): an observation that names an offset or message from KAFKA_EXPLAIN_TABLE_BOUND
 # on, and a history of more than KAFKA_EXPLAIN_MAX_FINDINGS findings, are explained by the host walk
 KAFKA_EXPLAIN_TABLE_BOUND, KAFKA_EXPLAIN_MAX_FINDINGS = 384, 1024
+# unique_explain_kernel's capacity (MSIM_UNIQUE_EXPLAIN_MAX_DUPS: a history of more duplicated ids is explained by the host walk) and
+# pn_explain_kernel's (csrc/pn_check_dev.hip: a window of acceptable values this wide, or wider, is the host walk's)
+UNIQUE_EXPLAIN_MAX_DUPS, PN_EXPLAIN_WINDOW = 1024, 4096
 
 
 class Config(C.Structure):
@@ -153,6 +156,34 @@ class KafkaExplain(C.Structure):
     _fields_ = [("n_findings", C.c_uint32), ("truncated", C.c_uint32), ("count", C.c_uint32 * 10)]
 
 
+class PnRead(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("value", C.c_int32), ("process", C.c_uint32), ("in_set", C.c_uint32)]
+
+
+class PnRange(C.Structure):
+    _fields_ = [("lower", C.c_int64), ("upper", C.c_int64)]
+
+
+class PnExplain(C.Structure):
+    _fields_ = [("n_reads", C.c_uint32), ("n_ranges", C.c_uint32), ("truncated", C.c_uint32), ("reserved", C.c_uint32), ("definite_sum", C.c_int64)]
+
+
+class UniqueDup(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("count", C.c_uint32), ("first_row", C.c_uint32), ("second_row", C.c_uint32)]
+
+
+class UniqueExplain(C.Structure):
+    _fields_ = [("n_dups", C.c_uint32), ("truncated", C.c_uint32)]
+
+
+class EchoError(C.Structure):
+    _fields_ = [("invoke_row", C.c_uint32), ("complete_row", C.c_uint32), ("expected", C.c_uint32), ("received", C.c_uint32)]
+
+
+class EchoExplain(C.Structure):
+    _fields_ = [("n_errors", C.c_uint32), ("truncated", C.c_uint32)]
+
+
 # The one table of records: the header's struct name -> its Structure, field names and order as in include/maelsim.h.  engine.py derives
 # the numpy dtypes from these (np.dtype(Structure)); tests/test_abi_tables.py compiles a probe against the header and compares every
 # size and offset with both.
@@ -251,6 +282,25 @@ KAFKA_EXPLAIN_PROTOTYPES = {
     "msim_explain_kafka": (_i, (_vp, _vp, _vp, _u32, _u32)),
 }
 
+# ... and for include/maelsim_small_explain.h: the explained pn-counter / g-counter, unique-ids and echo verdicts
+# (tests/test_small_explain.py holds these to their header).
+SMALL_EXPLAIN_RECORDS = {"msim_pn_read": PnRead, "msim_pn_range": PnRange, "msim_pn_explain": PnExplain, "msim_unique_dup": UniqueDup,
+                         "msim_unique_explain": UniqueExplain, "msim_echo_error": EchoError, "msim_echo_explain": EchoExplain}
+_small_rows = (_i, (_vp, _u32, _res, _vp, _vp, _u32))
+_small_batch = (_i, (_i, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp))
+_small_ctx = (_i, (_vp, _vp, _vp, _u32, _u32))
+SMALL_EXPLAIN_PROTOTYPES = {
+    "msim_explain_pn_rows": _small_rows,
+    "msim_explain_unique_rows": _small_rows,
+    "msim_explain_echo_rows": (_i, (_vp, _u32, _u32, _res, _vp, _vp, _u32)),
+    "msim_explain_pn_batch": _small_batch,
+    "msim_explain_unique_batch": _small_batch,
+    "msim_explain_echo_batch": (_i, (_i, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp)),
+    "msim_explain_pn": _small_ctx,
+    "msim_explain_unique": _small_ctx,
+    "msim_explain_echo": _small_ctx,
+}
+
 _lib = None
 
 
@@ -263,7 +313,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -m maelstrom_amd.build` (hipcc, gfx950). "
                            "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES, **SMALL_EXPLAIN_PROTOTYPES}.items():
         fn = getattr(lib, name, None)   # MSIM_LIB may name an older build (the A/B tools under tools/ time the parent's): an entry it lacks is skipped, and calling it still raises
         if fn is not None:
             fn.restype, fn.argtypes = restype, list(argtypes)

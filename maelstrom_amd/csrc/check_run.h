@@ -162,6 +162,9 @@ void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const 
 void msim_kafka_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out,
                                       msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings);
 void msim_pn_check_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res);
+void msim_pn_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_pn_explain *hdr, void *records, uint32_t max_records);
+void msim_unique_explain_instance_host(const msim_op *rows, uint32_t n_rows, uint32_t flags, msim_check_result *res, msim_unique_explain *hdr, msim_unique_dup *dups,
+                                       uint32_t max_dups);
 
 // The hand-off: the rows and payload words of the histories `todo` come to the host, analyse(rows, n_rows, payload, n_words, flags, i)
 // — which writes h_out[i] — runs on up to msim_host_threads() threads, the finished records go back to d_out + i.

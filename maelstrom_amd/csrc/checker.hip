@@ -30,9 +30,11 @@
 // Per-element state: three u16 row indices in LDS (8.4 KB for 1408 elements keeps 4096 histories resident).
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "check_dev.h"
 #include "check_run.h"
 #include "engine_internal.h"
 
@@ -224,12 +226,101 @@ int msim_check_launch(msim_ctx *ctx) {
   return rc != MSIM_OK ? rc : msim_check_wait(ctx);
 }
 
+// ---- echo: the explanation of a verdict (msim_explain_echo*; include/maelsim_small_explain.h) ----------------------------------------
+// check_kernel counts the invocations whose completion is not an :ok with the same value; echo_explain_kernel, a kernel of its own over
+// the histories that have such an invocation (`list`), names them: one wavefront per history pairs the rows again by worker thread
+// (process mod C: the table's index; a crashed process's successor, process + C, has the same entry) — in rounds, as check_kernel's
+// pass 1: of a step's 64 rows the earliest pending row of every thread acts on the thread's entry, an invocation opens it, a completion
+// takes it — and notes per invocation row, in LDS, how it ended; a second sweep writes the errors in row order (ballot, prefix count).
+#define ECHO_FINE 0xFFFFu      /* per invocation row: no error (and every row that is no invocation) */
+#define ECHO_NO_OK 0xFFFEu     /* an error without an :ok completion; any other value: the row of the :ok that carries another value */
+struct EchoExplainOut { msim_echo_explain *hdr; msim_echo_error *errors; u32 max_errors; };
+
+__global__ void __launch_bounds__(64) echo_explain_kernel(const msim_op *rows_all, const msim_inst_meta *meta, const u32 *list, u32 max_rows, u32 C, const EchoExplainOut x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char csmem[];
+  u32 *const open = reinterpret_cast<u32 *>(csmem);                         // [C] the thread's open invocation row
+  u32 *const first = open + C;                                              // [C] ds_min target: (round, lane) of the thread's earliest pending row
+  unsigned short *const how = reinterpret_cast<unsigned short *>(first + C);   // [max_rows]
+  const u32 lane = threadIdx.x, hist = list[blockIdx.x];
+  const uint4 *const r = reinterpret_cast<const uint4 *>(rows_all) + (size_t)hist * max_rows;
+  const u32 n = min(meta[hist].n_rows, max_rows);
+  const u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;   // lanes below this one
+  for (u32 i = lane; i < n; i += 64) how[i] = ECHO_FINE;
+  for (u32 i = lane; i < C; i += 64) { open[i] = NONE32; first[i] = 0xFFFFFFFFu; }
+  __syncthreads();
+  u32 round_key = 0x3FFFFFFu;   // decreases with every round: a later round's ds_min beats whatever an earlier one left
+  for (u32 base = 0; base < n; base += 64) {
+    const u32 idx = base + lane;
+    const uint4 row = idx < n ? r[idx] : make_uint4(0, 0, 0, 0);
+    const u32 type = row.z & 3u, proc = row.z >> 12;
+    bool pend = idx < n && proc != MSIM_PROCESS_NEMESIS && ((row.z >> 2) & 31u) == MSIM_F_ECHO;
+    const u32 tt = pend ? proc % C : 0u;
+    for (u64 pm = __ballot(pend); pm; pm = __ballot(pend)) {
+      const u32 key = (round_key << 6) | lane;
+      if (pend) atomicMin(&first[tt], key);
+      wv_fence();
+      if (pend && first[tt] == key) {
+        pend = false;
+        const u32 s = open[tt];
+        if (type == MSIM_T_INVOKE) open[tt] = idx;
+        else {
+          open[tt] = NONE32;
+          if (s != NONE32) { if (type != MSIM_T_OK) how[s] = ECHO_NO_OK; else if (r[s].w != row.w) how[s] = (unsigned short)idx; }
+        }
+      }
+      round_key--;
+      wv_fence();
+    }
+  }
+  __syncthreads();
+  for (u32 i = lane; i < C; i += 64) if (open[i] != NONE32) how[open[i]] = ECHO_NO_OK;   // invocations left without a completion
+  __syncthreads();
+  uint4 *const dst = reinterpret_cast<uint4 *>(x.errors + (size_t)hist * x.max_errors);
+  u32 at = 0;
+  for (u32 base = 0; base < n; base += 64) {
+    const u32 idx = base + lane;
+    const u32 h = idx < n ? how[idx] : ECHO_FINE;
+    const u64 m = __ballot(h != ECHO_FINE);
+    const u32 slot = at + (u32)__popcll(m & lt);
+    if (h != ECHO_FINE && slot < x.max_errors)   // (the slab's bound)
+      dst[slot] = make_uint4(idx, h == ECHO_NO_OK ? MSIM_NO_VALUE : h, r[idx].w, h == ECHO_NO_OK ? MSIM_NO_VALUE : r[h].w);
+    at += (u32)__popcll(m);
+  }
+  if (lane == 0) { x.hdr[hist].n_errors = min(at, x.max_errors); x.hdr[hist].truncated = at > x.max_errors ? 1u : 0u; }
+}
+
+// the caller's arrays of an explaining echo run: a header per history, max_errors records per history
+struct EchoExplainRun { msim_echo_explain *hdr; msim_echo_error *errors; u32 max_errors; };
+
+// Behind check_kernel (whose records lie in d_out): the histories with an error go to echo_explain_kernel.  Without one nothing is
+// launched and nothing allocated.  h_out: the records, fetched here.
+static int echo_explain_run(msim_ctx *ctx, const msim_op *d_rows, const msim_inst_meta *d_meta, const msim_check_result *d_out, u32 max_rows, u32 C, u32 n,
+                            msim_check_result *h_out, hipStream_t st, const EchoExplainRun &xr) {
+  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+  MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+  std::memset(xr.hdr, 0, (size_t)n * sizeof(msim_echo_explain));
+  if (xr.max_errors) std::memset(xr.errors, 0, (size_t)n * xr.max_errors * sizeof(msim_echo_error));
+  std::vector<u32> list;
+  for (u32 i = 0; i < n; i++) if (h_out[i].error_count) list.push_back(i);
+  if (list.empty()) return MSIM_OK;
+  ExplainSlabs<msim_echo_explain, msim_echo_error> xs;
+  DevBuf d_list;
+  if (int rc = xs.alloc(ctx, n, xr.max_errors, xr.hdr, xr.errors)) return rc;
+  if (int rc = xs.clear(ctx, st)) return rc;
+  MSIM_HIP_TRY(ctx, d_list.upload(list.data(), list.size() * 4));
+  const size_t lds = ((size_t)C * 8 + (size_t)max_rows * 2 + 3) & ~(size_t)3;
+  const EchoExplainOut x{xs.hdr(), xs.rec(), xr.max_errors};
+  MSIM_HIP_TRY(ctx, check_dispatch(echo_explain_kernel, lds, (u32)list.size(), st, d_rows, d_meta, static_cast<const u32 *>(d_list.get<u32>()), max_rows, C, x));
+  if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[check] echo_explain_kernel over %zu of %u histories\n", list.size(), n);
+  return xs.fetch(ctx, st);   // (waits: the buffers are freed with this frame)
+}
+
 // Checks `n_histories` broadcast / g-set (set-full) or echo histories given on the host with the device checker of msim_check:
 // history i lies in the slabs rows + i * max_rows (n_rows[i] rows used) and payload + i * max_payload_words.
 // (hdr: msim_explain_set_full_batch's arrays — set_explain_kernel in place of check_kernel, on the same upload)
 static int set_full_batch(int device, uint32_t workload, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows,
                           const uint32_t *payload, uint32_t max_payload_words, uint32_t max_values, uint32_t n_histories, msim_check_result *out,
-                          msim_set_explain *hdr = nullptr, msim_set_element *elements = nullptr, uint32_t max_elements = 0) {
+                          msim_set_explain *hdr = nullptr, msim_set_element *elements = nullptr, uint32_t max_elements = 0, const EchoExplainRun *echo = nullptr) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0 || (!payload && max_payload_words)) return MSIM_E_INVALID;
   if (workload != MSIM_WL_ECHO && workload != MSIM_WL_BROADCAST && workload != MSIM_WL_G_SET) return MSIM_E_INVALID;
   if (check_limits(max_rows, max_values, concurrency)) return MSIM_E_UNSUPPORTED;
@@ -250,6 +341,7 @@ static int set_full_batch(int device, uint32_t workload, uint32_t concurrency, c
     if (int rc = xs.fetch(ctx, nullptr)) return rc;
   } else MSIM_HIP_TRY(ctx, check_dispatch(check_kernel, check_layout(cp), n_histories, nullptr, cp));
   MSIM_HIP_TRY(ctx, hipDeviceSynchronize());
+  if (echo) return echo_explain_run(ctx, cp.rows, cp.meta, cp.out, max_rows, concurrency, n_histories, out, nullptr, *echo);
   MSIM_HIP_TRY(ctx, hipMemcpy(out, cp.out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost));
   return MSIM_OK;
 }
@@ -293,6 +385,26 @@ extern "C" int msim_explain_set_full(msim_ctx *ctx, msim_set_explain *hdr, msim_
   MSIM_HIP_TRY(ctx, hipEventRecord(ctx->ev3, ctx->stream));
   if ((rc = xs.fetch(ctx, ctx->stream)) != MSIM_OK) return rc;
   return msim_check_wait(ctx);
+}
+
+// The explaining echo check of a caller's histories: msim_check_set_full_batch's upload, kernel and records for MSIM_WL_ECHO (rows only:
+// an echo history has no payload words), then echo_explain_kernel over the histories with an error.  *n_host (may be null): always 0.
+extern "C" int msim_explain_echo_batch(int device, uint32_t concurrency, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories,
+                                       msim_check_result *out, msim_echo_explain *hdr, msim_echo_error *errors, uint32_t max_errors, uint32_t *n_host) {
+  if (!hdr || (!errors && max_errors) || n_histories == 0) return MSIM_E_INVALID;
+  if (n_host) *n_host = 0;
+  const EchoExplainRun xr{hdr, errors, max_errors};
+  return set_full_batch(device, MSIM_WL_ECHO, concurrency, rows, n_rows, max_rows, nullptr, 0, 32, n_histories, out, nullptr, nullptr, 0, &xr);
+}
+
+// ... and of the last run where it lies in HBM: msim_check (queued, taken or launched as it would be), then the explanation.
+extern "C" int msim_explain_echo(msim_ctx *ctx, msim_echo_explain *hdr, msim_echo_error *errors, uint32_t max_errors, uint32_t n_out) {
+  if (!ctx || !hdr || (!errors && max_errors)) return MSIM_E_INVALID;
+  const msim_config &c = ctx->cfg;
+  if (int rc = explain_refusal(ctx, "msim_explain_echo", c.workload == MSIM_WL_ECHO, "an echo", n_out)) return rc;
+  if (int rc = msim_check(ctx)) return rc;
+  std::vector<msim_check_result> h_out(ctx->n_inst);
+  return echo_explain_run(ctx, ctx->d_rows, ctx->d_meta, ctx->d_check, c.max_rows, c.concurrency, ctx->n_inst, h_out.data(), ctx->stream, EchoExplainRun{hdr, errors, max_errors});
 }
 
 // ---- maelstrom.checker/availability-checker (checker.clj:6-39) ---------------------------------------------------------

@@ -144,6 +144,8 @@ int msim_check_pn_device(msim_ctx *ctx);
 // pn_check.cpp
 int msim_check_pn_host(msim_ctx *ctx);
 int msim_check_unique_host(msim_ctx *ctx);
+int msim_explain_pn_host(msim_ctx *ctx, msim_pn_explain *hdr, void *records, uint32_t max_records);
+int msim_explain_unique_host(msim_ctx *ctx, msim_unique_explain *hdr, msim_unique_dup *dups, uint32_t max_dups);
 
 // guard.cpp: the library's device allocator — hipMalloc / hipFree unless MSIM_GUARD asks for fenced slabs (developer's electric fence for HBM)
 hipError_t msim_dev_malloc_impl(void **out, size_t bytes);

@@ -137,6 +137,127 @@ __global__ void __launch_bounds__(UNIQ_WG) unique_check_lds_kernel(const UParams
   }
 }
 
+// ---- the explanation (msim_explain_unique*; include/maelsim_small_explain.h): the duplicated ids, how often, the first two rows ----
+// One workgroup per history that has a duplicate (`list`), the id table in LDS or — the histories unique_check_kernel takes — in HBM
+// workspace.  The table is filled as above; the slots seen again are gathered into a list in LDS (any order) and sorted by id, so that
+// a second sweep over the rows finds an acknowledgement's entry by bisection: it counts, and keeps the smallest row (atomicMin).  A
+// third sweep keeps the smallest row that is not the first — two ordered passes, nothing depends on which lane came first.  Then the
+// list is sorted by (count descending, id descending) and written as far as the caller's slab goes.
+constexpr u32 XD_MAX = MSIM_UNIQUE_EXPLAIN_MAX_DUPS;   // duplicated ids the list in LDS holds: a history with more is the host walk's
+
+struct UXOut {
+  msim_unique_explain *hdr; msim_unique_dup *dups; u32 max_dups;
+  u32 *ws;   // HBM route: table_slots id words + table_slots / 32 words of "seen again" bits per history of the launch
+};
+
+template <bool BY_ID> __device__ __forceinline__ bool dup_before(const uint4 a, const uint4 b) {
+  if (BY_ID) return a.x != b.x ? a.x < b.x : a.y < b.y;   // (a padding entry {EMPTY, EMPTY, ..} behind the id EMPTY itself, whose count is still 0)
+  return a.y != b.y ? a.y > b.y : a.x > b.x;
+}
+// bitonic network over n2 (a power of two) entries of `dl`, by the whole workgroup
+template <bool BY_ID> __device__ __forceinline__ void dup_sort(uint4 *dl, u32 n2, u32 tid) {
+  for (u32 k = 2; k <= n2; k <<= 1)
+    for (u32 j = k >> 1; j; j >>= 1) {
+      for (u32 i = tid; i < n2; i += UNIQ_WG) {
+        const u32 l = i ^ j;
+        if (l > i) {
+          const uint4 a = dl[i], b = dl[l];
+          if (dup_before<BY_ID>(b, a) == ((i & k) == 0)) { dl[i] = b; dl[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+}
+// the entry of `id` among the n_d entries sorted by id (n_d: none)
+__device__ __forceinline__ u32 dup_find(const uint4 *dl, u32 n_d, u32 id) {
+  u32 lo = 0, hi = n_d;
+  while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (dl[mid].x < id) lo = mid + 1; else hi = mid; }
+  return lo < n_d && dl[lo].x == id ? lo : n_d;
+}
+
+template <bool LDS_TABLE> __device__ __forceinline__ void unique_explain_body(const UParams &p, const u32 *list, const UXOut &x, unsigned char *smem) {
+  uint4 *const dl = reinterpret_cast<uint4 *>(smem);   // [XD_MAX] {id, count, first row, second row}
+  u32 *const dw = reinterpret_cast<u32 *>(smem);
+  u32 *const hd = dw + 4u * XD_MAX;                    // [4] entries listed, acknowledgements of the id EMPTY
+  const u32 slots = LDS_TABLE ? LDS_SLOTS : p.table_slots;
+  u32 *const tab = LDS_TABLE ? hd + 4 : x.ws + (u64)blockIdx.x * (p.table_slots + p.table_slots / 32u);
+  u32 *const again = tab + slots;
+  const u32 tid = threadIdx.x, hist = list[p.first + blockIdx.x];
+  const uint4 *const r = reinterpret_cast<const uint4 *>(p.rows) + (u64)hist * p.max_rows;
+  const u32 n = p.meta[hist].n_rows;
+  for (u32 i = tid; i < slots; i += UNIQ_WG) tab[i] = EMPTY;
+  for (u32 i = tid; i < slots / 32u; i += UNIQ_WG) again[i] = 0;
+  if (tid < 4) hd[tid] = 0;
+  __syncthreads();
+  // the acknowledged id of row idx (false: the row acknowledges none)
+  auto ack = [&](u32 idx, u32 *id) {
+    const uint4 row = r[idx];
+    *id = row.w;
+    return (row.z >> 12) != MSIM_PROCESS_NEMESIS && ((row.z >> 2) & 31u) == MSIM_F_GENERATE && (row.z & 3u) == MSIM_T_OK;
+  };
+  for (u32 idx = tid; idx < n; idx += UNIQ_WG) {
+    u32 id;
+    if (!ack(idx, &id)) continue;
+    if (id == EMPTY) { atomicAdd(&hd[1], 1u); continue; }   // (the one value the table cannot hold is counted apart)
+    u32 h = (id * 0x9E3779B1u) >> 7;
+    for (u32 probes = 0; probes < slots; probes++, h++) {   // (the host sizes the table for a load factor of 0.6 at most; bounded all the same)
+      h &= slots - 1u;
+      const u32 old = atomicCAS(&tab[h], EMPTY, id);
+      if (old == EMPTY) break;
+      if (old == id) { atomicOr(&again[h >> 5], 1u << (h & 31u)); break; }
+    }
+  }
+  __syncthreads();
+  for (u32 i = tid; i < slots / 32u; i += UNIQ_WG)
+    for (u32 w = again[i]; w; w &= w - 1u) {
+      const u32 k = atomicAdd(&hd[0], 1u);
+      if (k < XD_MAX) dl[k] = make_uint4(tab[i * 32u + (u32)__builtin_ctz(w)], 0u, EMPTY, EMPTY);
+    }
+  __syncthreads();
+  if (tid == 0 && hd[1] >= 2u) { const u32 k = hd[0]; if (k < XD_MAX) dl[k] = make_uint4(EMPTY, 0u, EMPTY, EMPTY); hd[0] = k + 1u; }
+  __syncthreads();
+  const u32 n_d = hd[0];
+  // n_d is what the check's kernels wrote as duplicated_count (the same table, the id EMPTY counted apart alike), and the host hands a
+  // history with more than XD_MAX of them to its walk without listing it here.  Should the two ever disagree, the header says so: no
+  // record, `truncated` set — never a zero header that reads as "no duplicate".
+  if (n_d > XD_MAX) { if (tid == 0) { x.hdr[hist].n_dups = 0; x.hdr[hist].truncated = 1u; } return; }
+  u32 n2 = 1;
+  while (n2 < n_d) n2 <<= 1;
+  for (u32 i = n_d + tid; i < n2; i += UNIQ_WG) dl[i] = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
+  __syncthreads();
+  dup_sort<true>(dl, n2, tid);
+  for (u32 idx = tid; idx < n; idx += UNIQ_WG) {
+    u32 id;
+    if (!ack(idx, &id)) continue;
+    const u32 d = dup_find(dl, n_d, id);
+    if (d < n_d) { atomicAdd(&dw[4u * d + 1u], 1u); atomicMin(&dw[4u * d + 2u], idx); }
+  }
+  __syncthreads();
+  for (u32 idx = tid; idx < n; idx += UNIQ_WG) {
+    u32 id;
+    if (!ack(idx, &id)) continue;
+    const u32 d = dup_find(dl, n_d, id);
+    if (d < n_d && idx != dw[4u * d + 2u]) atomicMin(&dw[4u * d + 3u], idx);
+  }
+  __syncthreads();
+  for (u32 i = n_d + tid; i < n2; i += UNIQ_WG) dl[i] = make_uint4(0u, 0u, 0u, 0u);   // (count 0: behind every entry in the order of the output)
+  __syncthreads();
+  dup_sort<false>(dl, n2, tid);
+  const u32 n_out = min(n_d, x.max_dups);
+  uint4 *const dst = reinterpret_cast<uint4 *>(x.dups + (size_t)hist * x.max_dups);
+  for (u32 i = tid; i < n_out; i += UNIQ_WG) dst[i] = dl[i];
+  if (tid == 0) { x.hdr[hist].n_dups = n_out; x.hdr[hist].truncated = n_d > x.max_dups ? 1u : 0u; }
+}
+
+__global__ void __launch_bounds__(UNIQ_WG) unique_explain_lds_kernel(const UParams p, const u32 *list, const UXOut x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unique_explain_body<true>(p, list, x, smem);
+}
+__global__ void __launch_bounds__(UNIQ_WG) unique_explain_kernel(const UParams p, const u32 *list, const UXOut x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unique_explain_body<false>(p, list, x, smem);
+}
+
 }  // namespace
 
 // `paired`: the histories are the engine's own — every :ok row follows its :invoke row, so at most max_rows / 2 ids are acknowledged;
@@ -167,6 +288,86 @@ static int unique_dev_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *w
   return MSIM_OK;
 }
 
+// the caller's arrays of an explaining run: a header per history, max_dups records per history
+struct UniqueExplainRun { msim_unique_explain *hdr; msim_unique_dup *dups; u32 max_dups; };
+
+// Behind unique_dev_run (whose records lie in up.out): the histories with a duplicate are explained by unique_explain_*_kernel, those
+// with more than XD_MAX duplicated ids by the host walk (*n_host).  Without such a history nothing is launched and nothing allocated.
+static int unique_explain_run(msim_ctx *ctx, UParams up, u32 n, void **ws, size_t *ws_cap, hipStream_t st, bool paired, msim_check_result *h_out,
+                              const UniqueExplainRun &xr, u32 *n_host) {
+  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, up.out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+  MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
+  std::memset(xr.hdr, 0, (size_t)n * sizeof(msim_unique_explain));
+  if (xr.max_dups) std::memset(xr.dups, 0, (size_t)n * xr.max_dups * sizeof(msim_unique_dup));
+  std::vector<u32> list, todo;
+  for (u32 i = 0; i < n; i++) if (h_out[i].duplicated_count) (h_out[i].duplicated_count > XD_MAX ? todo : list).push_back(i);
+  if (n_host) *n_host = (u32)todo.size();
+  if (!list.empty()) {
+    const u32 m = (u32)list.size();
+    ExplainSlabs<msim_unique_explain, msim_unique_dup> xs;   // (on the device only now that some history has a duplicate)
+    DevBuf d_list;
+    if (int rc = xs.alloc(ctx, n, xr.max_dups, xr.hdr, xr.dups)) return rc;
+    if (int rc = xs.clear(ctx, st)) return rc;
+    MSIM_HIP_TRY(ctx, d_list.upload(list.data(), (size_t)m * 4));
+    const u32 *const dl = d_list.get<u32>();
+    UXOut x{xs.hdr(), xs.rec(), xr.max_dups, nullptr};
+    const uint64_t max_ids = paired ? up.max_rows / 2 : up.max_rows;
+    const bool lds_route = max_ids * 10 <= (uint64_t)LDS_SLOTS * 6 && !(msim_dev_flags(ctx) & 0x2000u);   // (as unique_dev_run chooses)
+    const size_t list_lds = (size_t)XD_MAX * 16 + 16;
+    if (lds_route) {
+      const size_t lds = list_lds + ((size_t)LDS_SLOTS + LDS_SLOTS / 32) * 4;
+      MSIM_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&unique_explain_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      up.first = 0;
+      hipLaunchKernelGGL(unique_explain_lds_kernel, dim3(m), dim3(UNIQ_WG), lds, st, up, dl, x);
+      MSIM_HIP_TRY(ctx, hipGetLastError());
+    } else {
+      u32 slots = 64; while (slots < (paired ? up.max_rows : 2 * up.max_rows)) slots <<= 1;
+      up.table_slots = slots;
+      const uint64_t per = (uint64_t)slots * 4 + slots / 8;
+      const u32 chunk = chunk_for(m, per, 4ull << 30, msim_dev_flags(ctx));
+      if (int rc = grow_ws(ctx, ws, ws_cap, (size_t)chunk * per)) return rc;
+      x.ws = static_cast<u32 *>(*ws);
+      hipError_t e;
+      for_chunks(m, chunk, &e, [&](u32 first, u32 count) {   // (one workspace: the chunks follow one another on the stream)
+        up.first = first;
+        hipLaunchKernelGGL(unique_explain_kernel, dim3(count), dim3(UNIQ_WG), list_lds, st, up, dl, x);
+      });
+      MSIM_HIP_TRY(ctx, e);
+    }
+    if (msim_dev_flags(ctx) & 0x1000u) std::fprintf(stderr, "[unique-check] unique_explain_kernel (%s table) over %u of %u histories\n", lds_route ? "LDS" : "HBM", m, n);
+    if (int rc = xs.fetch(ctx, st)) return rc;   // (waits: the buffers are freed with this block)
+  }
+  if (!todo.empty()) {
+    std::vector<msim_inst_meta> hm(n);
+    MSIM_HIP_TRY(ctx, hipMemcpy(hm.data(), up.meta, (size_t)n * sizeof(msim_inst_meta), hipMemcpyDeviceToHost));
+    const int rc = hand_off(ctx, HistorySource{up.rows, nullptr, &hm, up.max_rows, 0, nullptr, nullptr}, n, todo, h_out, up.out,
+                            [&](const msim_op *rows, u32 nr, const u32 *, u32, u32 flags, u32 i) {
+                              msim_unique_explain_instance_host(rows, nr, flags, &h_out[i], &xr.hdr[i], xr.dups + (size_t)i * xr.max_dups, xr.max_dups);
+                            });
+    if (rc != MSIM_OK) return rc;
+  }
+  return MSIM_OK;
+}
+
+// msim_check that also explains.  Towards the context it is msim_check (msim_check_host_rechecks: the histories of more than
+// MSIM_UNIQUE_EXPLAIN_MAX_DUPS duplicated ids, whose records the host walk wrote again); under developer flag 0x800 the host walk explains.
+extern "C" int msim_explain_unique(msim_ctx *ctx, msim_unique_explain *hdr, msim_unique_dup *dups, uint32_t max_dups, uint32_t n_out) {
+  if (!ctx || !hdr || (!dups && max_dups)) return MSIM_E_INVALID;
+  if (int rc = explain_refusal(ctx, "msim_explain_unique", ctx->cfg.workload == MSIM_WL_UNIQUE_IDS, "a unique-ids", n_out)) return rc;
+  if (msim_dev_flags(ctx) & 0x800u) return msim_explain_unique_host(ctx, hdr, dups, max_dups);
+  // msim_check's own route for this workload (engine.hip workload_check): it leaves check_fetched false, so msim_check_results reads
+  // d_check — which hand_off refreshes below — and no pinned copy of the records goes stale
+  if (int rc = msim_check_unique_device(ctx)) return rc;
+  UParams up;
+  std::memset(&up, 0, sizeof up);
+  up.rows = ctx->d_rows; up.meta = ctx->d_meta; up.out = ctx->d_check; up.max_rows = ctx->cfg.max_rows;
+  std::vector<msim_check_result> h_out(ctx->n_inst);
+  u32 redone = 0;
+  if (int rc = unique_explain_run(ctx, up, ctx->n_inst, &ctx->d_check_scratch, &ctx->cap_check_scratch, ctx->stream, true, h_out.data(), UniqueExplainRun{hdr, dups, max_dups}, &redone)) return rc;
+  ctx->lin_host_rechecks = redone;
+  return MSIM_OK;
+}
+
 // msim_check for unique-ids: the histories of the last run, where they lie in HBM.
 int msim_check_unique_device(msim_ctx *ctx) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -185,7 +386,9 @@ int msim_check_unique_device(msim_ctx *ctx) {
 
 // Checks `n_histories` unique-ids histories given on the host, each in a slab of `max_rows` rows (history i at rows + i * max_rows,
 // n_rows[i] of them used), with the device checker of msim_check; out[i] as msim_check_unique_rows would fill it.
-extern "C" int msim_check_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
+// (xr: msim_explain_unique_batch's arrays)
+static int unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out, const UniqueExplainRun *xr,
+                        uint32_t *n_host) {
   if (!rows || !n_rows || !out || n_histories == 0 || max_rows == 0) return MSIM_E_INVALID;
   BatchFrame<SlabBatch> f(device); msim_ctx *ctx = &f.ctx;
   if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, n_rows, max_rows, n_histories)) return rc;
@@ -194,6 +397,17 @@ extern "C" int msim_check_unique_batch(int device, const msim_op *rows, const ui
   std::memset(&up, 0, sizeof up);
   up.rows = f.b.rows.get<msim_op>(); up.meta = f.b.meta.get<msim_inst_meta>(); up.out = f.d_out.get<msim_check_result>(); up.max_rows = max_rows;
   if (int rc = unique_dev_run(ctx, up, n_histories, ws.addr(), &ws_cap, nullptr, false)) return rc;
+  if (xr) return unique_explain_run(ctx, up, n_histories, ws.addr(), &ws_cap, nullptr, false, out, *xr, n_host);
   MSIM_HIP_TRY(ctx, hipMemcpy(out, up.out, (size_t)n_histories * sizeof(msim_check_result), hipMemcpyDeviceToHost));
   return MSIM_OK;
+}
+extern "C" int msim_check_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out) {
+  return unique_batch(device, rows, n_rows, max_rows, n_histories, out, nullptr, nullptr);
+}
+// As msim_check_unique_batch, with the duplicated ids of every history that has one (include/maelsim_small_explain.h).
+extern "C" int msim_explain_unique_batch(int device, const msim_op *rows, const uint32_t *n_rows, uint32_t max_rows, uint32_t n_histories, msim_check_result *out,
+                                         msim_unique_explain *hdr, msim_unique_dup *dups, uint32_t max_dups, uint32_t *n_host) {
+  if (!hdr || (!dups && max_dups)) return MSIM_E_INVALID;
+  const UniqueExplainRun xr{hdr, dups, max_dups};
+  return unique_batch(device, rows, n_rows, max_rows, n_histories, out, &xr, n_host);
 }

@@ -18,6 +18,8 @@ from . import _abi as A
                           A.LatencyDist, A.FStats, A.PerfResult))
 # msim_inst_meta stays written out: its callers know the header's reserved[3] as three words r0, r1, r2 (the oracle's dtype has the same).
 KAFKA_FINDING_DT, KAFKA_EXPLAIN_DT = np.dtype(A.KafkaFinding), np.dtype(A.KafkaExplain)   # (A.KAFKA_EXPLAIN_RECORDS)
+(PN_READ_DT, PN_RANGE_DT, PN_EXPLAIN_DT, UNIQUE_DUP_DT, UNIQUE_EXPLAIN_DT, ECHO_ERROR_DT, ECHO_EXPLAIN_DT) = (
+    np.dtype(s) for s in A.SMALL_EXPLAIN_RECORDS.values())
 META_DT = np.dtype([(n, "<u4") for n in ("n_rows", "n_payload_words", "flags", "n_rounds", "n_events", "r0", "r1", "r2")])
 PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
@@ -236,6 +238,33 @@ class Engine:
         self._chk(self.lib.msim_explain_kafka(self._ctx, hdr.ctypes.data, fs.ctypes.data, max_findings, self.n), "msim_explain_kafka")
         res = self.check_results()
         return [(res[i], hdr[i], fs[i, :int(hdr[i]["n_findings"])].copy()) for i in range(self.n)]
+
+    def _explain_small(self, entry, hdr_dt, rec_dt, cap):
+        hdr = np.zeros(max(self.n, 1), dtype=hdr_dt)
+        recs = np.zeros((max(self.n, 1), max(cap, 1)), dtype=rec_dt)
+        self._chk(getattr(self.lib, entry)(self._ctx, hdr.ctypes.data, recs.ctypes.data, cap, self.n), entry)
+        return self.check_results(), hdr, recs
+
+    def explain_pn(self, max_records=256):
+        """pn-counter / g-counter: check() that also explains (msim_explain_pn): per history of the last run (CHECK_DT record —
+        check_results() holds the same afterwards —, PN_EXPLAIN_DT header, PN_READ_DT final reads, PN_RANGE_DT acceptable ranges; see
+        pn_analysis), read off the device checker's bitmap.  The reads come first in a history's max_records records; a history with
+        more reads and ranges than that has header["truncated"] set."""
+        res, hdr, recs = self._explain_small("msim_explain_pn", PN_EXPLAIN_DT, PN_READ_DT, max_records)
+        return [(res[i], hdr[i]) + _pn_segments(hdr[i], recs[i]) for i in range(self.n)]
+
+    def explain_unique_ids(self, max_dups=48):
+        """unique-ids: check() that also explains (msim_explain_unique): per history of the last run (CHECK_DT record, UNIQUE_EXPLAIN_DT
+        header, UNIQUE_DUP_DT records: the duplicated ids by count descending, then id descending, with the rows of their first two
+        acknowledgements; see unique_ids_analysis), found on the device."""
+        res, hdr, recs = self._explain_small("msim_explain_unique", UNIQUE_EXPLAIN_DT, UNIQUE_DUP_DT, max_dups)
+        return [(res[i], hdr[i], recs[i, :int(hdr[i]["n_dups"])].copy()) for i in range(self.n)]
+
+    def explain_echo(self, max_errors=64):
+        """echo: check() that also explains (msim_explain_echo): per history of the last run (CHECK_DT record, ECHO_EXPLAIN_DT header,
+        ECHO_ERROR_DT records: the invocations the check counts as errors, in row order; see echo_analysis), found on the device."""
+        res, hdr, recs = self._explain_small("msim_explain_echo", ECHO_EXPLAIN_DT, ECHO_ERROR_DT, max_errors)
+        return [(res[i], hdr[i], recs[i, :int(hdr[i]["n_errors"])].copy()) for i in range(self.n)]
 
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
@@ -955,6 +984,131 @@ def set_full_analysis(record, header, elements, rows=None, payload=None, n_nodes
         res["stable-latencies"] = {q: int(v) for q, v in zip(pts, record["stable_latency_ms"])}
     if int(record["lost_count"]):
         res["lost-latencies"] = {q: int(v) for q, v in zip(pts, header["lost_latency_ms"])}
+    if int(header["truncated"]):
+        res["truncated"] = True
+    return res
+
+
+def _pn_segments(hdr, slab):
+    """(PN_READ_DT final reads, PN_RANGE_DT ranges) of one history's slab of 16-byte records"""
+    nr, ng = int(hdr["n_reads"]), int(hdr["n_ranges"])
+    return slab[:nr].copy(), slab[nr:nr + ng].copy().view(PN_RANGE_DT)
+
+
+def _explain_small_history(entry, rows, hdr_dt, rec_dt, cap, *extra):
+    rows = np.ascontiguousarray(rows)
+    out = np.zeros(1, dtype=CHECK_DT)
+    hdr = np.zeros(1, dtype=hdr_dt)
+    slab = np.zeros(max(cap, 1), dtype=rec_dt)
+    _call(entry, rows.ctypes.data, len(rows), *extra, out.ctypes.data_as(C.POINTER(A.CheckResult)), hdr.ctypes.data, slab.ctypes.data, cap)
+    return out[0], hdr[0], slab[:cap]
+
+
+def _explain_small_batch(entry, histories, device, hdr_dt, rec_dt, cap, *extra):
+    """-> (CHECK_DT records, headers, the (histories, cap) slab, n_host)"""
+    slab, nr = _slab_form(histories)
+    n = len(nr)
+    out = np.zeros(n, dtype=CHECK_DT)
+    hdr = np.zeros(n, dtype=hdr_dt)
+    recs = np.zeros((n, max(cap, 1)), dtype=rec_dt)
+    n_host = C.c_uint32()
+    _call(entry, device, *extra, slab.ctypes.data, nr.ctypes.data, slab.shape[1], n, out.ctypes.data, hdr.ctypes.data, recs.ctypes.data, cap, C.addressof(n_host))
+    return out, hdr, recs[:, :cap], n_host.value
+
+
+def explain_pn_history(rows, max_records=256):
+    """The explaining pn-counter / g-counter check of one history on the host (msim_explain_pn_rows; needs no device) -> (CHECK_DT
+    record, PN_EXPLAIN_DT header, PN_READ_DT final reads, PN_RANGE_DT acceptable ranges; include/maelsim_small_explain.h)."""
+    out, hdr, slab = _explain_small_history("msim_explain_pn_rows", rows, PN_EXPLAIN_DT, PN_READ_DT, max_records)
+    return (out, hdr) + _pn_segments(hdr, slab)
+
+
+def explain_pn_batch(histories, device=0, max_records=256, with_n_host=False):
+    """pn-counter / g-counter: check_pn_batch with the explanation written on the device (msim_explain_pn_batch).  Returns (CHECK_DT
+    records, PN_EXPLAIN_DT headers, a list of (final reads, ranges) per history); the whole zero-padded slab of 16-byte records is the
+    list's `.slab`.  with_n_host: also how many histories the host walk explained."""
+    out, hdr, slab, n_host = _explain_small_batch("msim_explain_pn_batch", histories, device, PN_EXPLAIN_DT, PN_READ_DT, max_records)
+    segs = _StepLists(_pn_segments(hdr[i], slab[i]) for i in range(len(out)))
+    segs.slab = slab
+    return (out, hdr, segs, n_host) if with_n_host else (out, hdr, segs)
+
+
+def pn_analysis(record, header, reads, ranges, rows=None, n_nodes=0, workload=A.WL_PN_COUNTER):
+    """The reference's result map (workload/pn_counter.clj:122-125) from one history's record, header, final reads and ranges (pure
+    formatting): {"valid?", "errors" (None where there is none: (seq errors)), "final-reads", "acceptable"}; the errors are the ops
+    as decode_history gives them with `rows`, else row indices.  A truncated header gives what was written, and "truncated": True."""
+    bad = [int(r["row"]) for r in reads if not int(r["in_set"])]
+    if rows is not None and bad:
+        ops = decode_history(rows, np.zeros(1, dtype=np.uint32), n_nodes, workload)
+        bad = [ops[i] for i in bad]
+    res = {"valid?": bool(int(record["valid"])), "errors": bad or None, "final-reads": [int(r["value"]) for r in reads],
+           "acceptable": [[int(g["lower"]), int(g["upper"])] for g in ranges]}
+    if int(header["truncated"]):
+        res["truncated"] = True
+    return res
+
+
+def explain_unique_history(rows, max_dups=48):
+    """The explaining unique-ids check of one history on the host (msim_explain_unique_rows) -> (CHECK_DT record, UNIQUE_EXPLAIN_DT
+    header, UNIQUE_DUP_DT records: the duplicated ids by count descending, then packed id descending)."""
+    out, hdr, slab = _explain_small_history("msim_explain_unique_rows", rows, UNIQUE_EXPLAIN_DT, UNIQUE_DUP_DT, max_dups)
+    return out, hdr, slab[:int(hdr["n_dups"])]
+
+
+def explain_unique_batch(histories, device=0, max_dups=48, with_n_host=False):
+    """unique-ids: check_unique_batch with the explanation written on the device (msim_explain_unique_batch).  Returns (CHECK_DT
+    records, UNIQUE_EXPLAIN_DT headers, a list of UNIQUE_DUP_DT arrays); the whole slab is the list's `.slab`."""
+    out, hdr, slab, n_host = _explain_small_batch("msim_explain_unique_batch", histories, device, UNIQUE_EXPLAIN_DT, UNIQUE_DUP_DT, max_dups)
+    dups = _StepLists(slab[i, :int(hdr[i]["n_dups"])].copy() for i in range(len(out)))
+    dups.slab = slab
+    return (out, hdr, dups, n_host) if with_n_host else (out, hdr, dups)
+
+
+def decode_id(value, node_program=None):
+    """a packed :generate :value as decode_history presents it: a lin-tso timestamp, else a flake id [time count node-id]"""
+    value = int(value)
+    return value if node_program == A.NODE_TSO_IDS else [value >> 20, (value >> 5) & 0x7FFF, f"n{value & 31}"]
+
+
+def unique_ids_analysis(record, header, dups, node_program=None):
+    """[upstream] jepsen.checker/unique-ids' result map from one history's record, header and duplicate records (pure formatting):
+    {"valid?", "attempted-count", "acknowledged-count", "duplicated-count", "duplicated", "range"}.  "duplicated" takes the first 48
+    records — the most often acknowledged ids — and presents them sorted by id, as [id, count] pairs (a flake id is a vector, no key
+    of a Python dict); ids are decoded per node program, as decode_history decodes them."""
+    shown = sorted(((int(d["id"]), int(d["count"])) for d in dups[:48]))
+    lo, hi = (int(v) for v in record["stable_latency_ms"][:2])
+    res = {"valid?": bool(int(record["valid"])), "attempted-count": int(record["attempt_count"]), "acknowledged-count": int(record["ok_count"]),
+           "duplicated-count": int(record["duplicated_count"]), "duplicated": [[decode_id(i, node_program), c] for i, c in shown],
+           "range": [decode_id(lo, node_program), decode_id(hi, node_program)] if int(record["ok_count"]) else [None, None]}
+    if int(header["truncated"]):
+        res["truncated"] = True
+    return res
+
+
+def explain_echo_history(rows, concurrency, max_errors=64):
+    """The explaining echo check of one history on the host (msim_explain_echo_rows) -> (CHECK_DT record, ECHO_EXPLAIN_DT header,
+    ECHO_ERROR_DT records: the invocations that count as errors, ascending by row)."""
+    out, hdr, slab = _explain_small_history("msim_explain_echo_rows", rows, ECHO_EXPLAIN_DT, ECHO_ERROR_DT, max_errors, int(concurrency))
+    return out, hdr, slab[:int(hdr["n_errors"])]
+
+
+def explain_echo_batch(histories, concurrency, device=0, max_errors=64, with_n_host=False):
+    """echo: check_set_full_batch(workload=WL_ECHO) with the explanation written on the device (msim_explain_echo_batch).  Returns
+    (CHECK_DT records, ECHO_EXPLAIN_DT headers, a list of ECHO_ERROR_DT arrays); the whole slab is the list's `.slab`."""
+    out, hdr, slab, n_host = _explain_small_batch("msim_explain_echo_batch", histories, device, ECHO_EXPLAIN_DT, ECHO_ERROR_DT, max_errors, int(concurrency))
+    errs = _StepLists(slab[i, :int(hdr[i]["n_errors"])].copy() for i in range(len(out)))
+    errs.slab = slab
+    return (out, hdr, errs, n_host) if with_n_host else (out, hdr, errs)
+
+
+def echo_analysis(record, header, errors):
+    """workload/echo.clj:62-63's result map from one history's record, header and error records (pure formatting): {"valid?", "errors":
+    [["Expected a message with :echo", v, "But received", v'], ...]} — v the invocation's :value, v' the completion's (an echo_ok body
+    where it was an :ok, else None: a :fail / :info carries no body, a missing completion is nil)."""
+    def body(v):
+        return None if int(v) == A.NO_VALUE else {"type": "echo_ok", "echo": f"Please echo {int(v)}"}
+    res = {"valid?": bool(int(record["valid"])),
+           "errors": [["Expected a message with :echo", f"Please echo {int(e['expected'])}", "But received", body(e["received"])] for e in errors]}
     if int(header["truncated"]):
         res["truncated"] = True
     return res

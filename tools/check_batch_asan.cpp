@@ -152,6 +152,26 @@ int main() {
     for (uint32_t i = 0; i < 4; i++) { ids.rows.push_back(row(2 * i, MSIM_T_INVOKE, MSIM_F_GENERATE, i % 3, 0xFFFFFFFFu)); ids.rows.push_back(row(2 * i + 1, MSIM_T_OK, MSIM_F_GENERATE, i % 3, 5 + (i & 1))); }
     const Slabs un({none, ids, none, ids, none});
     report("msim_check_unique_batch", msim_check_unique_batch(0, un.rows.data(), un.n_rows.data(), un.max_rows, N, out.data()), out);
+    {   // the explained verdicts of the three small checkers: the pn history the host explains beside one of the device's, duplicated ids, echo errors
+      std::vector<msim_pn_explain> ph(N);
+      std::vector<msim_pn_range> pr(N * STEPS);
+      report("msim_explain_pn_batch", msim_explain_pn_batch(0, pn.rows.data(), pn.n_rows.data(), pn.max_rows, N, out.data(), ph.data(), pr.data(), STEPS, &n_host), out, &n_host);
+      std::printf("%-28s reads %u %u, ranges %u %u\n", "", ph[1].n_reads, ph[3].n_reads, ph[1].n_ranges, ph[3].n_ranges);
+      failures += ph[1].n_ranges != 2 || ph[3].n_ranges != 2 || ph[0].n_ranges != 1;
+      std::vector<msim_unique_explain> uh(N);
+      std::vector<msim_unique_dup> ud(N * STEPS);
+      report("msim_explain_unique_batch", msim_explain_unique_batch(0, un.rows.data(), un.n_rows.data(), un.max_rows, N, out.data(), uh.data(), ud.data(), STEPS, &n_host), out, &n_host);
+      std::printf("%-28s duplicated ids %u %u\n", "", uh[1].n_dups, uh[3].n_dups);
+      failures += uh[1].n_dups != 2 || ud[STEPS].id != 6 || ud[STEPS].second_row != 7;
+      History echoes;
+      echoes.rows = {row(0, MSIM_T_INVOKE, MSIM_F_ECHO, 0, 1), row(1, MSIM_T_INVOKE, MSIM_F_ECHO, 1, 2), row(2, MSIM_T_OK, MSIM_F_ECHO, 1, 3), row(3, MSIM_T_FAIL, MSIM_F_ECHO, 0, 1)};
+      const Slabs ec({none, echoes, none, echoes, none});
+      std::vector<msim_echo_explain> eh(N);
+      std::vector<msim_echo_error> ee(N * STEPS);
+      report("msim_explain_echo_batch", msim_explain_echo_batch(0, 3, ec.rows.data(), ec.n_rows.data(), ec.max_rows, N, out.data(), eh.data(), ee.data(), STEPS, &n_host), out, &n_host);
+      std::printf("%-28s errors %u %u\n", "", eh[1].n_errors, eh[3].n_errors);
+      failures += eh[1].n_errors != 2 || ee[STEPS + 1].complete_row != 2;
+    }
     std::vector<msim_perf_result> perf(N);
     std::vector<msim_latency_dist> windows((size_t)N * 4 * MSIM_PERF_MAX_F * 3);
     int rc = msim_check_perf_batch(0, un.rows.data(), un.n_rows.data(), un.max_rows, N, 3, 0, 0, perf.data(), nullptr);
