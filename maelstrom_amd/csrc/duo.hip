@@ -45,26 +45,26 @@
 // round of its own (its rows at its own time, its payload from its own node's set, the time jump, the round count) before the wave-round's
 // one gossip round and the op that ends the run.  The block of 32 generator draws of a cluster lives in LDS there, and what the rare paths
 // derive from the lane number alone (the spill pointer, the instance's key, constant row words) is computed where it is used: the
-// registers that frees are what the run needs at 80 VGPRs (see "READ RUNS" below; -DDUO_NO_PLAN compiles all of it out).
+// registers that frees are what the run needs at 80 VGPRs (see "READ RUNS" below).
 // There, too, the two clusters PAIR their op rounds: a half that is ready for its op while its partner is in the middle of a flood waits
 // (it is parked: the wave-rounds are the partner's gossip rounds) until the partner is ready as well, so that one op wave-round serves
-// both (see "PAIRED OP ROUNDS" at the exit test of the gossip loop; -DDUO_NO_PAIR compiles it out).
+// both (see "PAIRED OP ROUNDS" at the exit test of the gossip loop).
 // And there the flood gossip rounds of a wavefront run in a loop of their own, the FLOOD STRETCH: between two such rounds nothing that R0 and
 // the exit test look at can change unless a half runs out of due envelopes or a parked half's count-down ends, so the loop's back edge
 // tests just that; inside it the flood bodies publish fan-out masks instead of envelopes (see "FLOOD STRETCH" at the flood gossip body and
-// DUO_FLOOD_ARRIVALS; -DDUO_NO_STRETCH compiles both out).
+// DUO_FLOOD_ARRIVALS).
 // That instantiation is TRIMMED of vector instructions the result does not need: no body counts the delivered envelopes (servers_recv follows
 // from the arrivals and what is left undelivered when the cluster stops), a flood's set word goes to HBM once, before something can read it
-// there, and an op wave-round derives its half's offsets once (see "TRIM" in sim_kernel_duo; -DDUO_NO_TRIM compiles it out).
+// there, and an op wave-round derives its half's offsets once (see "TRIM" in sim_kernel_duo).
 // Its op wave-rounds, finally, have a body for the case that pairing has made the rule, the QUIET OP ROUND: every live half acts, from flood
 // mode, so nothing is due or queued anywhere in the wavefront; the gossip part and the exchange are left out, a lane reads off its own
 // adjacency mask whether the picked node's broadcast reaches it, and takes the envelope as the poll would have (see "QUIET OP ROUND" in
-// the op round of sim_kernel_duo; every other op wave-round keeps the superset body; -DDUO_NO_QUIET compiles it out).
+// the op round of sim_kernel_duo; every other op wave-round keeps the superset body).
 // And the round that ends a flood stretch because a half has run out of due envelopes has, in the steady state of the main phase, a path
 // of its own, the STEADY LEAVE: the tail of an op round notes per half (sd_m) that the half's next round can only be an op round's, and
 // for such a half the stretch's exit does what R0's block and the exit test would have done, and nothing else: the time jump, the round
 // count, the count-down, then the park of the dry half or the release of the parked one and the op round of both.  Everything else goes
-// through the loop's head as ever (see "STEADY LEAVE" at the exit of the flood stretch and sd_m; -DDUO_NO_STEADY compiles it out).
+// through the loop's head as ever (see "STEADY LEAVE" at the exit of the flood stretch and sd_m).
 // FLOOD MEMO.  In that instantiation, at last, a flood is simulated ONCE per origin and pair of clusters, then applied.  A quiet op round
 // takes a broadcast only from a quiescent cluster, there is no draw per message and no nemesis, so what the flood does to the cluster
 // (every node's set gains the value's bit, n_arr and rounds rise, nothing is left queued or held) is a function of the topology and the
@@ -93,71 +93,23 @@ namespace {
 __constant__ u32 duo_log2_q24[257];
 
 enum { DK_PLAIN = 0, DK_BCAST = 1, DK_READ = 2, DK_READ_FINAL = 3, DK_INIT = 4, DK_TOPO = 5 };  // kind of an envelope (bits 24-26)
-constexpr u32 DUO_STAGE_ROWS = 128u;
-constexpr u32 DUO_DROP_ONE = 1u << 8;   // TRIM: a lane's my_flags counts the envelopes it dropped in units of this, above the flag bits
+constexpr u32 DUO_DROP_ONE = 1u << 8;   // the flood instantiation: a lane's my_flags counts the envelopes it dropped in units of this, above the flag bits
 static_assert(DUO_DROP_ONE > MSIM_FLAG_JOURNAL_OVERFLOW && DUO_DROP_ONE == 1u << 8, "the drop count lies above every flag, from bit 8 on");
 #ifndef DUO_BAG_N
 #define DUO_BAG_N 16
 #endif
 constexpr u32 DUO_BAG = DUO_BAG_N;   // random latencies: envelopes of a node's queue that live in LDS (a power of two, 4 .. 16; the rest spills to HBM behind a cached minimum)
 // History rows go from their lanes to HBM unstaged (two 16-byte rows per operation; the L2 merges them into lines: WRITE_SIZE stays at the
-// algorithmic bytes): 9.00 -> 8.90 ms per 4096 clusters against staging 64 rows in LDS (-DDUO_STAGED_ROWS keeps that variant for A/B runs).
-#ifdef DUO_STAGED_ROWS
-constexpr bool DUO_DIRECT = false;
-#else
-constexpr bool DUO_DIRECT = true;
-#endif
-// Flood mode of the latency-0 kernel (see "flood mode" in sim_kernel_duo); -DDUO_NO_FLOOD compiles it out for A/B runs.
+// algorithmic bytes): 9.00 -> 8.90 ms per 4096 clusters against staging 64 rows in LDS.
+// The flood instantiation of the latency-0 kernel: flood mode (see "FLOOD MODE" in sim_kernel_duo) and everything built on it, the read runs,
+// the paired op rounds, the flood stretch, the trims, the quiet op round and the steady leave.  -DDUO_NO_FLOOD compiles all of it out: the
+// latency-0, degree <= 4 instantiation is then the generic code the five other instantiations run, the live reference of the tests.
 #ifdef DUO_NO_FLOOD
 constexpr bool DUO_FLOOD_ON = false;
 #else
 constexpr bool DUO_FLOOD_ON = true;
 #endif
-// Read runs of the flood instantiation (see "READ RUNS" in the op round of sim_kernel_duo) and the latency-0 time jump without the
-// minimum over the nodes; -DDUO_NO_PLAN compiles both out for A/B runs.
-#ifdef DUO_NO_PLAN
-constexpr bool DUO_PLAN_ON = false;
-#else
-constexpr bool DUO_PLAN_ON = true;
-#endif
-// Paired op rounds of the flood instantiation (see "PAIRED OP ROUNDS" at the exit test of the gossip loop in sim_kernel_duo): a half that
-// is ready for its op waits up to DUO_PAIR_WAIT wave-rounds for its partner's flood to end; -DDUO_NO_PAIR compiles it out for A/B runs.
-#ifdef DUO_NO_PAIR
-constexpr bool DUO_PAIR_ON = false;
-#else
-constexpr bool DUO_PAIR_ON = true;
-#endif
-// The flood stretch of the paired instantiation (see "FLOOD STRETCH" at the flood gossip body of sim_kernel_duo) and the fan-out masks the
-// flood bodies publish there; -DDUO_NO_STRETCH compiles both out for A/B runs.
-#ifdef DUO_NO_STRETCH
-constexpr bool DUO_STRETCH_ON = false;
-#else
-constexpr bool DUO_STRETCH_ON = true;
-#endif
-// The trims of the stretch instantiation (see "TRIM" in sim_kernel_duo): servers_recv by conservation instead of a count per round, the
-// flood's set word written back once instead of by every handling node, the half's offsets once per op wave-round; -DDUO_NO_TRIM compiles
-// all three out for A/B runs.
-#ifdef DUO_NO_TRIM
-constexpr bool DUO_TRIM_ON = false;
-#else
-constexpr bool DUO_TRIM_ON = true;
-#endif
-// The quiet op round of the trimmed instantiation (see "QUIET OP ROUND" in the op round of sim_kernel_duo): an op wave-round in which every
-// live half acts from flood mode takes a body of its own, without the exchange; -DDUO_NO_QUIET compiles it out for A/B runs.
-#ifdef DUO_NO_QUIET
-constexpr bool DUO_QUIET_ON = false;
-#else
-constexpr bool DUO_QUIET_ON = true;
-#endif
-// The steady leave of the quiet instantiation (see "STEADY LEAVE" at the exit of the flood stretch in sim_kernel_duo): the round that ends a
-// stretch because a half has run out of due envelopes parks that half or goes to the op round without a pass through R0 and the exit
-// test, when an op round has left the half in the state those would find; -DDUO_NO_STEADY compiles it out for A/B runs.
-#ifdef DUO_NO_STEADY
-constexpr bool DUO_STEADY_ON = false;
-#else
-constexpr bool DUO_STEADY_ON = true;
-#endif
-// The flood memo of the steady instantiation (see "FLOOD MEMO" in sim_kernel_duo): a flood from an origin the wavefront has simulated before
+// The flood memo of the flood instantiation (see "FLOOD MEMO" in sim_kernel_duo): a flood from an origin the wavefront has simulated before
 // is applied from the record of that simulation, and two halves with nothing in flight go from one op round to the next directly;
 // -DDUO_NO_MEMO compiles it out for A/B runs (the kernel is then the previous one, instruction for instruction).
 // (the -DDUO_PROF_STRETCH and -DDUO_PROF_STEADY builds count the rounds of simulated floods, inside stretches and at their exits: they leave the
@@ -168,7 +120,7 @@ constexpr bool DUO_MEMO_ON = false;
 constexpr bool DUO_MEMO_ON = true;
 #endif
 // what the kernel's MEMO is for the instantiation that has it: msim_launch_duo gives that one the table's LDS
-constexpr bool DUO_MEMO_BUILD = DUO_MEMO_ON && DUO_STEADY_ON && DUO_QUIET_ON && DUO_TRIM_ON && DUO_STRETCH_ON && DUO_PAIR_ON && DUO_PLAN_ON && DUO_FLOOD_ON;
+constexpr bool DUO_MEMO_BUILD = DUO_MEMO_ON && DUO_FLOOD_ON;
 constexpr u32 DUO_MEMO_BYTES = 32u * 32u * 2u;   // [origin][lane] of 16 bits
 #if defined(DUO_MEMO_VERIFY) && (defined(MSIM_HIPEMU) || defined(DUO_PROF))
 constexpr bool DUO_MEMO_CHECK = true;    // a remembered flood is simulated all the same and compared with its record
@@ -189,7 +141,7 @@ constexpr bool DUO_SRUN_ON = true;
 #endif
 // The block plan of the steady-run instantiation (see "BLOCK PLAN" in front of the steady run's loop in sim_kernel_duo): the ops of a block
 // of draws that the loop would take one after the other are taken at once, lane k planning draw k; -DDUO_NO_BLOCK_PLAN compiles it out for
-// A/B runs (the kernel is then the previous one, instruction for instruction).  The name DUO_PLAN_ON belongs to the read runs' switch above.
+// A/B runs (the kernel is then the previous one, instruction for instruction).
 // -DDUO_BLOCK_PLAN_NO_FACTS (developer / tests) treats every half's sets as not uniform: the plan is compiled in and always declines.
 #ifdef DUO_NO_BLOCK_PLAN
 constexpr bool DUO_BPLAN_ON = false;
@@ -306,12 +258,11 @@ __device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse
 #endif
 __device__ __forceinline__ u32 bperm(u32 byte_addr, u32 v) { return (u32)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v); }
 
-// element idx_ of an array; BYTES32: as the base plus a 32-bit BYTE offset (the whole array is below 4 GiB), the form whose address is the
-// base in SGPRs and one VGPR
-template <bool BYTES32, typename Tp>
+// element idx_ of an array, as the base plus a 32-bit BYTE offset (the whole array is below 4 GiB): the form whose address is the base in
+// SGPRs and one VGPR
+template <typename Tp>
 __device__ __forceinline__ Tp *duo_at(Tp *base, u32 idx) {
-  if constexpr (BYTES32) return reinterpret_cast<Tp *>(reinterpret_cast<unsigned char *>(base) + (size_t)(u32)(idx * (u32)sizeof(Tp)));
-  else return base + (size_t)idx;
+  return reinterpret_cast<Tp *>(reinterpret_cast<unsigned char *>(base) + (size_t)(u32)(idx * (u32)sizeof(Tp)));
 }
 
 // Latency 0: at least 6 wavefronts per SIMD (<= 80 VGPRs), what three launches of 2048 wavefronts in flight need; with the op round
@@ -346,18 +297,18 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   const u32 me16 = dp.echoback ? (64u << 16) : (i << 16);
   const u32 round_limit = dp.round_limit;
 
-  constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;   // the instantiations with a flood mode (see below)
-  constexpr bool RUNS = DUO_PLAN_ON && FLOOD;                    // ... whose op rounds take a run of reads at once
-  constexpr bool PAIR = DUO_PAIR_ON && RUNS;                     // ... and wait for each other, so that one op round serves both halves
-  constexpr bool STRETCH = DUO_STRETCH_ON && PAIR;               // ... and take the gossip rounds of a flood in a loop of their own
-  // TRIM (of the stretch instantiation; every part is output-identical):
+  // The instantiation with a flood mode (see below), and with all that is built on it: its op rounds take a run of reads at once and wait
+  // for each other, so that one op round serves both halves; the gossip rounds of a flood run in a loop of their own; the op wave-round
+  // of quiescent flood halves has a body of its own; a flood stretch is left for a park or an op round without R0 and the exit test.
+  constexpr bool FLOOD = DUO_FLOOD_ON && LAT0 && DEG4 && !RND;
+  // TRIM (of the flood instantiation; every part is output-identical to counting and storing round by round, as the other instantiations do):
   //   (A) n_rsv is not counted round by round.  Every server envelope counted in n_arr at its commit is received exactly once unless it is
   //       still queued or held when its cluster stops, or was dropped at a full queue (MSIM_FLAG_INBOX_OVERFLOW).  At latency 0 a lane's queue and hand hold in_n + sp_n + [deliver_at != INF] envelopes, of which `busy` is its own client's
   //       request (a busy client's request is queued or held: the node completes it in the round it handles it).  The two places that clear
-  //       a stopped half's queue put that number into n_rsv first, an envelope dropped at a full queue adds one (a dropped request: one, which
-  //       `busy` takes off again), and servers_recv = sum(n_arr) - sum(n_rsv): what the count gave, for flagged instances too.
-  //       (QUIET: the two places add that number to the count of dropped envelopes above my_flags' flag bits instead, which the epilogue
-  //        adds to n_rsv anyway: n_rsv is then no register across the rounds, the one the op round's third body needs at 80 VGPRs)
+  //       a stopped half's queue add that number to the count of dropped envelopes above my_flags' flag bits, an envelope dropped at a full
+  //       queue adds one there (a dropped request: one, which `busy` takes off again), the epilogue puts the count into n_rsv, and
+  //       servers_recv = sum(n_arr) - sum(n_rsv): what a count per round gives, for flagged instances too.  n_rsv is thus no register
+  //       across the rounds, the one the op round's third body needs at 80 VGPRs.
   //   (B) the flood bodies do not store sw.  A half in flood mode holds in sw, in EVERY lane, its column's word of value next_value - 1 (word 0
   //       while next_value == 0), and writes it back with one wave-wide store at the points after which its HBM copy can be read: the head
   //       of an op round in which it acts (before the read runs and the read op's copy) and DUO_MATERIALISE.  An acting half in flood
@@ -366,31 +317,26 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   //   (C) the half's 0 / ~0 is derived once per op wave-round and GENERAL body (duo_upm, from a lane number the optimizer cannot see
   //       through, so that nothing of it lives across the gossip loop), and rows and payload are addressed as the wavefront's base plus a
   //       32-bit byte offset (msim_launch_duo checks that the two slabs of a wavefront stay below 4 GiB).
-  constexpr bool TRIM = DUO_TRIM_ON && STRETCH;
-  constexpr bool QUIET = DUO_QUIET_ON && TRIM;                   // ... and give the op wave-round of quiescent flood halves a body of its own
-  constexpr bool STEADY = DUO_STEADY_ON && QUIET;                // ... and leave a flood stretch for a park or an op round without R0 and the exit test
-  constexpr bool MEMO = DUO_MEMO_ON && STEADY;                   // ... and simulate a flood once per origin, then apply what that simulation did
+  constexpr bool MEMO = DUO_MEMO_ON && FLOOD;                    // ... and simulate a flood once per origin, then apply what that simulation did
   constexpr bool SRUN = DUO_SRUN_ON && MEMO && !DUO_MEMO_CHECK;   // ... and take a remembered broadcast as a cluster round of the read runs' loop
   constexpr bool BPLAN = DUO_BPLAN_ON && SRUN;                   // ... and plan the steady ops of a block of draws across the lanes
-  constexpr bool R0_SCHED = DUO_PLAN_ON && LAT0;                // latency 0: a time jump goes to the scheduler's next event
   msim_op *const g_rows = p.rows + (size_t)inst * max_rows;
   u32 *const g_pay = p.payload + (size_t)inst * max_pay;
   // FLOOD: the cluster's rows and payload are addressed like its sets, from the wavefront's base (SGPRs: the lower cluster's) and the
-  // half's 0 / 1, so that no lane keeps a 64-bit pointer to them (the registers: 80 with room for the flood bodies)
-  const bool up_half = hi && real;   // the cluster is the wavefront's second one
+  // half's 0 / ~0, so that no lane keeps a 64-bit pointer to them (the registers: 80 with room for the flood bodies)
   msim_op *const w_rows = p.rows + (size_t)(blockIdx.x * 2u) * max_rows;
   u32 *const w_pay = p.payload + (size_t)(blockIdx.x * 2u) * max_pay;
-  // (RUNS: the half's share of the offset is computed at the access, from a lane number the optimizer cannot see through, so that it is not
-  //  kept in a register across the rounds; only live clusters write rows or payload, and an upper half that holds no cluster is never live)
-#define DUO_UP(x_) (TRIM ? (duo_upm & (x_)) : (u32)(RUNS ? ({ u32 du_l = threadIdx.x; MSIM_OPAQUE(du_l); du_l >= 32u ? (x_) : 0u; }) : (up_half ? (x_) : 0u)))
-#define DUO_UPM_NOW() u32 duo_upm = 0; if (TRIM) { DUO_LANE_NOW(um_l); duo_upm = 0u - (um_l >> 5); }
-#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? duo_at<TRIM>(w_rows, DUO_UP(max_rows) + (idx_)) : g_rows + (idx_))[0])
-#define DUO_PAY(idx_) ((FLOOD ? duo_at<TRIM>(w_pay, DUO_UP(max_pay) + (idx_)) : g_pay + (idx_))[0])
+  // (the half's share of the offset comes from duo_upm, see TRIM (C), so that it is not kept in a register across the rounds; only live
+  //  clusters write rows or payload, and an upper half that holds no cluster is never live)
+#define DUO_UP(x_) (duo_upm & (x_))
+#define DUO_UPM_NOW() u32 duo_upm = 0; if (FLOOD) { DUO_LANE_NOW(um_l); duo_upm = 0u - (um_l >> 5); }
+#define DUO_ROW(idx_) (reinterpret_cast<uint4 *>(FLOOD ? duo_at(w_rows, DUO_UP(max_rows) + (idx_)) : g_rows + (idx_))[0])
+#define DUO_PAY(idx_) ((FLOOD ? duo_at(w_pay, DUO_UP(max_pay) + (idx_)) : g_pay + (idx_))[0])
   // HBM spill behind the LDS ring: {deadline, envelope} pairs in the node's slice of the spill area
   u64 *const my_spill = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)inst * p.scratch_words + p.spill_off) +
                                                     (size_t)(is_node ? i : 0) * p.spill_cap);
 
-  // RUNS: what the rare paths derive from the lane number alone is computed where it is used, from a lane number the optimizer cannot
+  // FLOOD: what the rare paths derive from the lane number alone is computed where it is used, from a lane number the optimizer cannot
   // see through, so that no register holds it across the rounds.  These two are the ONLY second definitions of `lane` and `inst` (above):
   // whoever changes how a lane finds its instance changes them here as well.
 #define DUO_LANE_NOW(l_) u32 l_ = threadIdx.x; MSIM_OPAQUE(l_)
@@ -399,22 +345,21 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // no register pair holds it across the rounds
 #define DUO_MY_SPILL(ptr_)                                                                                                \
     u64 *ptr_ = my_spill;                                                                                                 \
-    if (RUNS) {                                                                                                           \
+    if (MEMO) {                                                                                                           \
+      /* (the memo instantiation: the wavefront's base in SGPRs and a 32-bit byte offset, like the sets; the 64-bit form below took two  \
+         registers more than the superset op round's checked append has to spare there.  The offset fits 32 bits: dp.inst_bytes, the   \
+         distance to the upper cluster's scratch, is below 2 GiB (msim_launch_duo returns MSIM_LAYOUT_DOES_NOT_FIT otherwise), and the    \
+         node's slice starts inside the instance's own spill area, node * spill_cap * 16 < 32 nodes x 65536 envelopes x 16 B = 32 MiB) */ \
       DUO_LANE_NOW(ms_l); const u32 ms_i = ms_l & 31u;                                                                    \
-      if (MEMO) {                                                                                                              \
-        /* (the memo instantiation: the wavefront's base in SGPRs and a 32-bit byte offset, like the sets; the 64-bit form below took two  \
-           registers more than the superset op round's checked append has to spare there.  The offset fits 32 bits: dp.inst_bytes, the   \
-           distance to the upper cluster's scratch, is below 2 GiB (msim_launch_duo returns MSIM_LAYOUT_DOES_NOT_FIT otherwise), and the    \
-           node's slice starts inside the instance's own spill area, node * spill_cap * 16 < 32 nodes x 65536 envelopes x 16 B = 32 MiB) */ \
-        const u32 ms_off = (DUO_INST_OF(ms_l) - blockIdx.x * 2u) * dp.inst_bytes + (ms_i < N ? ms_i : 0u) * p.spill_cap * 16u;          \
-        ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<unsigned char *>(p.scratch + (size_t)(blockIdx.x * 2u) * p.scratch_words + p.spill_off) + (size_t)ms_off); \
-      } else                                                                                                              \
+      const u32 ms_off = (DUO_INST_OF(ms_l) - blockIdx.x * 2u) * dp.inst_bytes + (ms_i < N ? ms_i : 0u) * p.spill_cap * 16u;          \
+      ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<unsigned char *>(p.scratch + (size_t)(blockIdx.x * 2u) * p.scratch_words + p.spill_off) + (size_t)ms_off); \
+    } else if (FLOOD) {                                                                                                   \
+      DUO_LANE_NOW(ms_l); const u32 ms_i = ms_l & 31u;                                                                    \
       ptr_ = reinterpret_cast<u64 *>(reinterpret_cast<uint4 *>(p.scratch + (size_t)DUO_INST_OF(ms_l) * p.scratch_words + p.spill_off) + \
                                      (size_t)(ms_i < N ? ms_i : 0) * p.spill_cap);                                          \
     }
-  // LDS of one cluster: [row staging][32 rings]
+  // LDS of one cluster: [32 rings]
   unsigned char *const hmem = smem + (hi ? dp.half_bytes : 0u);
-  uint4 *const stage = reinterpret_cast<uint4 *>(hmem);
   // The nodes' seen sets: W x 32 words of HBM scratch per cluster, word-major ([word][lane]: lane i's column is node i's set, or a
   // dummy set of a lane that holds no node), so that a wave-wide access to one word of every node's set is one 128-byte line per
   // cluster.  Addressed as the wavefront's base (SGPRs: the set region of its lower cluster) + a 32-bit byte offset per lane; the
@@ -460,13 +405,13 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       if (RND) nb_adj[k] = s < N ? topo_adj(p.cfg.topology, N, s) : 0u;
     }
   }
-  // STRETCH: the four neighbours' node numbers in one register (8 bits each, ascending like nbl), for the flood bodies, and what a node
+  // FLOOD: the four neighbours' node numbers in one register (8 bits each, ascending like nbl), for the flood bodies, and what a node
   // leaves out of its fan-out: the bit of the envelope's src, or nothing without skip-sender
   // (there the generic bodies take an envelope's constant part from it as well: kc's four registers are what the stretch needs)
 #ifdef MSIM_HIPEMU
-  // QUIET leans on the neighbour relation being SYMMETRIC (bit a of adj(b) == bit b of adj(a)), as it is for every shape topo_adj builds
+  // the quiet op round leans on the neighbour relation being SYMMETRIC (bit a of adj(b) == bit b of adj(a)), as it is for every shape topo_adj builds
   // with at most four neighbours (grid, partial grids included, line, tree2/3/4: each edge is set from both ends); see the quiet op round
-  if (QUIET) {
+  if (FLOOD) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const u32 sy_a = bperm(nbl[k], adj);   // the adjacency mask of neighbour k (an unused slot: lane 31's, which is 0 and not looked at)
@@ -475,8 +420,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   }
 #endif
   u32 nbp = 0;
-  if (STRETCH) nbp = (kc[0] >> 16) | (kc[1] >> 8) | kc[2] | (kc[3] << 8);
-#define DUO_KC(k_) (STRETCH ? ({ u32 kc_p = nbp; MSIM_OPAQUE(kc_p); ((kc_p >> (8 * (k_))) & 31u) << 16; }) : kc[k_])   /* (computed where it is used: not hoisted into four registers again) */
+  if (FLOOD) nbp = (kc[0] >> 16) | (kc[1] >> 8) | kc[2] | (kc[3] << 8);
+#define DUO_KC(k_) (FLOOD ? ({ u32 kc_p = nbp; MSIM_OPAQUE(kc_p); ((kc_p >> (8 * (k_))) & 31u) << 16; }) : kc[k_])   /* (computed where it is used: not hoisted into four registers again) */
   const u32 fan_skip = dp.echoback ? 0u : 1u;
 
   // ---- per-lane state: node i and its client (u32 throughout: flags are 0 / 1) ----
@@ -509,23 +454,23 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // lanes share) and so has two registers more for its op rounds.
   u32 dc_base = 0; u64 dc = draw64(key, S_GEN, (u64)i);
   // (addressed from a lane number the optimizer cannot see through: no register holds an address of it across the rounds)
-#define DUO_DCL(idx_) (reinterpret_cast<u64 *>(smem + (TRIM ? (duo_upm & dp.half_bytes) : (u32)({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); dl_l >= 32u ? dp.half_bytes : 0u; })) + dp.off_dc)[idx_])
+#define DUO_DCL(idx_) (reinterpret_cast<u64 *>(smem + (duo_upm & dp.half_bytes) + dp.off_dc)[idx_])
 #define DUO_DCL_MINE() (reinterpret_cast<u64 *>(smem + ({ u32 dl_l = threadIdx.x; MSIM_OPAQUE(dl_l); (dl_l >= 32u ? dp.half_bytes : 0u) + (dl_l & 31u) * 8u; }) + dp.off_dc)[0])
-  if (RUNS) { DUO_DCL_MINE() = dc; dc = 0; wave_lds_fence(); }
+  if (FLOOD) { DUO_DCL_MINE() = dc; dc = 0; wave_lds_fence(); }
 #define DUO_DRAW(k_, hi_, lo_) do {                                                                                       \
-    if (RUNS) { const u64 dd_v = DUO_DCL(((k_) - dc_base) & 31u); hi_ = (u32)(dd_v >> 32); lo_ = (u32)dd_v; }                 \
+    if (FLOOD) { const u64 dd_v = DUO_DCL(((k_) - dc_base) & 31u); hi_ = (u32)(dd_v >> 32); lo_ = (u32)dd_v; }                 \
     else { const u32 dd_at = hbase4 + (((k_) - dc_base) << 2); hi_ = bperm(dd_at, (u32)(dc >> 32)); lo_ = bperm(dd_at, (u32)dc); } \
   } while (0)
 #define DUO_DRAW_REFILL(cond_) do {                                                                                       \
     const bool dr_c = (cond_);                                                                                            \
     if (__ballot(dr_c)) {                                                                                                 \
       u64 dr_key = key;                                                                                                   \
-      if (RUNS) {   /* the instance's key again, from a lane number the optimizer cannot see through: once per 32 ops, no register between them */ \
+      if (FLOOD) {   /* the instance's key again, from a lane number the optimizer cannot see through: once per 32 ops, no register between them */ \
         DUO_LANE_NOW(dr_l);                                                                                               \
         dr_key = mix64(p.cfg.seed + 0x9E3779B97F4A7C15ull * (p.first_instance + DUO_INST_OF(dr_l) + 1));                  \
       }                                                                                                                   \
       const u64 dr_new = draw64(dr_key, S_GEN, (u64)gen_k + i);                                                           \
-      if (RUNS) { if (dr_c) DUO_DCL_MINE() = dr_new; wave_lds_fence(); } else dc = dr_c ? dr_new : dc;                            \
+      if (FLOOD) { if (dr_c) DUO_DCL_MINE() = dr_new; wave_lds_fence(); } else dc = dr_c ? dr_new : dc;                            \
       dc_base = dr_c ? gen_k : dc_base;                                                                                   \
     }                                                                                                                     \
   } while (0)
@@ -557,11 +502,11 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   // GENERAL body first MATERIALISES every such half: its in_n entries are written to the ring and the flag is cleared.
   const bool fl_ok = FLOOD && R >= 8u;
   u64 fl_m = 0;
-  // PAIR: the half that is parked, i.e. ready for its op and waiting for its partner (a lane mask like fl_m; 0: nobody), and the
+  // PAIRED OP ROUNDS: the half that is parked, i.e. ready for its op and waiting for its partner (a lane mask like fl_m; 0: nobody), and the
   // wave-rounds it may still wait (counted down in every wave-round; far from 0 while nobody is parked)
   constexpr u32 PARK_IDLE = 0x7FFFFFFFu;
   u64 park_m = 0; u32 park_left = PARK_IDLE;
-  // STEADY: sd_m = the halves whose next round, once their flood has run dry, can only be an op round's (a lane mask of whole halves like
+  // STEADY LEAVE: sd_m = the halves whose next round, once their flood has run dry, can only be an op round's (a lane mask of whole halves like
   // fl_m).  The tail of an op round sets a half's bit, on the state that round leaves, iff the half acted, no scheduler's view ran, and
   //   the half is in fl_m, next_value < max_values, n_rows + 2 <= max_rows, gen_k - dc_base < 32 (after the refill of the draws), and
   //   phase == PH_MAIN, gen_next < cutoff and busy == 0 in every lane, which hold where the bit is set without a compare (see the tail):
@@ -698,7 +643,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         in_n++;                                                                                                           \
       }                                                                                                                   \
       if (pc_got & !pc_fit) {                                                                                             \
-        if (sp_n >= S) my_flags = (my_flags | MSIM_FLAG_INBOX_OVERFLOW) + (TRIM ? DUO_DROP_ONE : 0u);   /* (TRIM: the dropped envelopes are counted above the flag bits) */ \
+        if (sp_n >= S) my_flags = (my_flags | MSIM_FLAG_INBOX_OVERFLOW) + (FLOOD ? DUO_DROP_ONE : 0u);   /* (FLOOD: the dropped envelopes are counted above the flag bits, see TRIM (A)) */ \
         else { u32 pc_idx = s_head + sp_n; if (pc_idx >= S) pc_idx -= S; DUO_MY_SPILL(pc_sp) pc_sp[pc_idx] = (u64)pc_dl | ((u64)pc_e << 32); sp_n++; } \
       }                                                                                                                   \
     }                                                                                                                     \
@@ -790,17 +735,9 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   } while (0)
   // R3 for a broadcast envelope (gossip or the client's own): dedup against the node's set; pub_ = what the node publishes
   // to its neighbours: bit 31 | value | src to skip << 16, or 0; hball_ = the ballot of handle_, pubb_ = the ballot of pub_ != 0
-#ifdef DUO_NO_SWPF   /* A/B build: the set word is read where it is used */
-#define DUO_SW_PREFETCH() do { } while (0)
-#define DUO_SW_NOW() DUO_SW_LOAD()
-#else
-#define DUO_SW_PREFETCH() DUO_SW_LOAD()
-#define DUO_SW_NOW() do { } while (0)
-#endif
   // (a half in flood mode keeps its set word in the register)
-#define DUO_SW_LOAD() do { const u32 sl_w = DUO_SEEN_WORD(); sw = (FLOOD && lane_in(fl_m)) ? sw : sl_w; } while (0)
+#define DUO_SW_PREFETCH() do { const u32 sl_w = DUO_SEEN_WORD(); sw = (FLOOD && lane_in(fl_m)) ? sw : sl_w; } while (0)
 #define DUO_R3_SEEN(handle_, hball_, pub_, pubb_) do {                                                                    \
-    DUO_SW_NOW();                                                                                                         \
     const u32 r3_bit = 1u << (cm & 31u);                                                                                  \
     const bool r3_new = (handle_) & ((sw & r3_bit) == 0);                                                                 \
     pubb_ = (hball_) & bal((sw & r3_bit) == 0);                                                                           \
@@ -809,49 +746,36 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (FLOOD) sw = r3_new ? (sw | r3_bit) : sw;                                                                          \
   } while (0)
   // ---- the flood bodies' parts (every live half in flood mode) ----
-  // R3: the dedup from the register; the node's one store of its set word stays (reads copy the sets from HBM)
+  // R3: the dedup from the register; the set word is written back later (see DUO_FLOOD_WB and TRIM (B): reads copy the sets from HBM)
 #define DUO_FLOOD_R3(due_n_, due_b_, pub_, pubb_) do {                                                                    \
     const u32 fr_w = sw | (1u << (cm & 31u));                                                                             \
     const bool fr_new = (due_n_) & (fr_w != sw);                                                                          \
     pubb_ = (due_b_) & bal(fr_w != sw);                                                                                   \
-    if (!TRIM) { if (fr_new) DUO_SEEN_WORD() = fr_w; }   /* (TRIM: written back later, see DUO_FLOOD_WB) */                    \
-    if (STRETCH) pub_ = fr_new ? (adj & ~(fan_skip << ((cm >> 16) & 31u))) : 0u;   /* the fan-out mask (see DUO_FLOOD_ARRIVALS) */ \
-    else pub_ = fr_new ? (0x80000000u | (cm & 0x3FFFFFu)) : 0u;                                                           \
+    pub_ = fr_new ? (adj & ~(fan_skip << ((cm >> 16) & 31u))) : 0u;   /* the fan-out mask (see DUO_FLOOD_ARRIVALS) */           \
     sw = fr_new ? fr_w : sw;                                                                                              \
   } while (0)
-  // TRIM: the write-back of sw by the lanes of wb_m_ (halves in flood mode), to the word of value next_value - 1
+  // TRIM (B): the write-back of sw by the lanes of wb_m_ (halves in flood mode), to the word of value next_value - 1
 #define DUO_FLOOD_WB(wb_m_) do {                                                                                          \
     if (lane_in(wb_m_)) DUO_SET(set_lane + (((max(next_value, 1u) - 1u) & 0xFFE0u) << 2)) = sw;                           \
   } while (0)
   // COMMIT: the pulls of DUO_ARRIVALS; the arrivals are only counted, an empty queue's head entry is its first arrival
-  // STRETCH: in the flood bodies a node publishes its FAN-OUT MASK, adj without the envelope's src (all of adj without skip-sender and
+  // In the flood bodies a node publishes its FAN-OUT MASK, adj without the envelope's src (all of adj without skip-sender and
   // for the client's own broadcast; bit 31 is never set: lane 31 holds no node), not the envelope: the value is the flood's, the cluster's
   // next_value - 1, and need not travel.  "Neighbour k sends to me" is bit i of the word pulled from it; the arrivals are the number of
   // such k, and the first arrival's src is the lowest one's node number, from nbp.  The generic bodies keep the envelope format: the
   // publisher and the receivers of one wave-round are always in the same body, so the two formats never meet.
 #define DUO_FLOOD_ARRIVALS(pub_) do {                                                                                     \
-    if (STRETCH) {                                                                                                        \
-      const u32 fa_x[4] = {bperm(nbl[0], pub_), bperm(nbl[1], pub_), bperm(nbl[2], pub_), bperm(nbl[3], pub_)};           \
-      const u32 fa_m = ((fa_x[0] >> i) & 1u) | (((fa_x[1] >> i) & 1u) << 8) | (((fa_x[2] >> i) & 1u) << 16) | (((fa_x[3] >> i) & 1u) << 24); \
-      const u32 fa_src = (nbp >> (u32)__builtin_ctz(fa_m | 0x80000000u)) & 31u;   /* (no arrival: some number; nx means nothing while the queue stays empty) */ \
-      nx = in_n == 0 ? ((next_value - 1u) | (fa_src << 16)) : nx;                                                         \
-      in_n += (u32)__popc(fa_m); n_arr += (u32)__popc(fa_m);                                                              \
-      break;                                                                                                              \
-    }                                                                                                                     \
-    const u32 fa_zk = 0x80000000u | me16;                                                                                 \
     const u32 fa_x[4] = {bperm(nbl[0], pub_), bperm(nbl[1], pub_), bperm(nbl[2], pub_), bperm(nbl[3], pub_)};             \
-    bool fa_g[4]; u32 fa_c = 0;                                                                                           \
-    _Pragma("unroll") for (int fa_k = 0; fa_k < 4; fa_k++) { fa_g[fa_k] = (int)((fa_x[fa_k] & 0x803F0000u) ^ fa_zk) > 0; fa_c += fa_g[fa_k] ? 1u : 0u; } \
-    const u32 fa_fx = fa_g[0] ? fa_x[0] : fa_g[1] ? fa_x[1] : fa_g[2] ? fa_x[2] : fa_x[3];                                \
-    const u32 fa_fk = fa_g[0] ? kc[0] : fa_g[1] ? kc[1] : fa_g[2] ? kc[2] : kc[3];                                        \
-    nx = in_n == 0 ? ((fa_fx & 0xFFFFu) | fa_fk) : nx;                                                                    \
-    in_n += fa_c; n_arr += fa_c;                                                                                          \
+    const u32 fa_m = ((fa_x[0] >> i) & 1u) | (((fa_x[1] >> i) & 1u) << 8) | (((fa_x[2] >> i) & 1u) << 16) | (((fa_x[3] >> i) & 1u) << 24); \
+    const u32 fa_src = (nbp >> (u32)__builtin_ctz(fa_m | 0x80000000u)) & 31u;   /* (no arrival: some number; nx means nothing while the queue stays empty) */ \
+    nx = in_n == 0 ? ((next_value - 1u) | (fa_src << 16)) : nx;                                                           \
+    in_n += (u32)__popc(fa_m); n_arr += (u32)__popc(fa_m);                                                                \
   } while (0)
   // the poll.  At latency 0 a node that holds an envelope has it due (deliver_at is the T of its commit or INF, and T never falls), so
   // after R3 every node is idle: the node takes the head of its queue if there is one.  No ring-head reload, no set-word prefetch.
 #define DUO_FLOOD_POLL() do {                                                                                             \
     const bool fp_can = in_n != 0;                                                                                        \
-    cm = fp_can ? nx : cm; deliver_at = fp_can ? T : INF; if (TRIM) in_n = max(in_n, 1u) - 1u; else in_n -= fp_can ? 1u : 0u; \
+    cm = fp_can ? nx : cm; deliver_at = fp_can ? T : INF; in_n = max(in_n, 1u) - 1u;   /* (one saturating subtraction) */ \
   } while (0)
   // leaving flood mode: the queued envelopes of every half in flood mode go to their ring (nx for each: see above); the fence orders
   // the stores before the reload of the ring head by the poll that follows
@@ -859,7 +783,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     if (FLOOD && fl_m != 0) {                                                                                             \
       PF_MAT_BEGIN                                                                                                        \
       const bool mt_on = lane_in(fl_m);                                                                                   \
-      if (TRIM) DUO_FLOOD_WB(fl_m);                                                                                       \
+      DUO_FLOOD_WB(fl_m);                                                                                                 \
       for (u32 mt_k = 0; __ballot(mt_on & (mt_k < in_n)); mt_k++)                                                         \
         if (mt_on & (mt_k < in_n)) ring32[((head + mt_k) & Rm) * 32u] = nx;                                               \
       wave_lds_fence();                                                                                                   \
@@ -1054,35 +978,35 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       u64 due_b = bal(deliver_at <= T);   // (a mask, not a bool: a bool two paths define is turned into 0 / 1 and compared again)
       bool stuck_any = false;
       {
-        // PAIR: a parked half is quiescent with T at its sched_at: there is nothing for it in this block, so it counts as a half with
+        // PAIRED OP ROUNDS: a parked half is quiescent with T at its sched_at: there is nothing for it in this block, so it counts as a half with
         // something due, and a parked round comes by here only when the partner has nothing due any more (its flood has ended) or the
         // wait has run out.  That is all a parked round adds to a gossip round: one scalar OR, the count-down and its test.  The parked
         // half is not in want_m meanwhile (see the exit test), so the round takes the gossip body; the block puts it back (T stands at
         // its sched_at), and the exit test releases it.
-        const u64 db = PAIR ? due_b | park_m : due_b;
-        if (PAIR) park_left--;
-        if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0 || (PAIR && park_left == 0), 0)) {
+        const u64 db = FLOOD ? due_b | park_m : due_b;
+        if (FLOOD) park_left--;
+        if (__builtin_expect((u32)db == 0 || (u32)(db >> 32) == 0 || (FLOOD && park_left == 0), 0)) {
           {
           const u64 idle_b = alive_m & bal(sched_at > T) & hm2((u32)db == 0, (u32)(db >> 32) == 0);
           if (idle_b) {
             // latency 0: deliver_at is the T of the envelope's commit or INF, and T never falls, so a half with nothing due holds no
             // envelope at all: the next event is the scheduler's
-            const u32 km = R0_SCHED ? sched_at : min(half_min(deliver_at, hi), sched_at);
+            const u32 km = LAT0 ? sched_at : min(half_min(deliver_at, hi), sched_at);
             const u64 stuck_b = idle_b & bal(km == INF);   // nothing will ever happen (oracle: same flag, the round counts)
             const bool stuck = lane_in(stuck_b);
             flags |= stuck ? (u32)MSIM_FLAG_ROUND_LIMIT : 0u;
             sched_at = stuck ? INF : sched_at;
             rounds += stuck ? 1u : 0u;
             alive_m &= ~stuck_b; fg_m &= ~stuck_b; alive_v = stuck ? 0u : alive_v;
-            if (STEADY) sd_m &= ~stuck_b;
+            if (FLOOD) sd_m &= ~stuck_b;
             T = lane_in(idle_b & ~stuck_b) ? km : T;
             stuck_any = stuck_b != 0;
             due_b = bal(deliver_at <= T);
           }
           // the round limit is looked at here and in GENERAL rounds (a stretch of pure gossip always ends in one of the two)
-          // (PAIR: not for a parked half: its round is counted, its op round decided; the limit is looked at again behind its op)
-          fg_m |= alive_m & bal(rounds >= round_limit) & (PAIR ? ~park_m : ~0ull);
-          if (STEADY) sd_m &= ~fg_m;
+          // (not for a parked half: its round is counted, its op round decided; the limit is looked at again behind its op)
+          fg_m |= alive_m & bal(rounds >= round_limit) & (FLOOD ? ~park_m : ~0ull);
+          if (FLOOD) sd_m &= ~fg_m;
           want_m = alive_m & (fg_m | bal(sched_at <= T));
           }
         }
@@ -1091,19 +1015,19 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       const bool due_n = lane_in(due_b);
       // GENERAL if alive & (force_general | sched_at <= T | special), special = due_n & (cm >> 24) != DK_PLAIN
       if (const u64 gw_m = want_m | (alive_m & due_b & bal(cm > 0xFFFFFFu)); gw_m != 0 || stuck_any) {   // (a GENERAL round is a superset of a gossip round: harmless for the other cluster)
-        // PAIR: a parked half (below) is released here, whatever this round turns out to be; its round is not counted again
+        // a parked half (below) is released here, whatever this round turns out to be; its round is not counted again
         bool released = false;
-        if (PAIR && park_m != 0) { alive_v = lane_in(park_m) ? 1u : alive_v; park_m = 0; park_left = PARK_IDLE; released = true; }
+        if (FLOOD && park_m != 0) { alive_v = lane_in(park_m) ? 1u : alive_v; park_m = 0; park_left = PARK_IDLE; released = true; }
         bool parks = false;
         if (LAT0 && !RND && rate > 0 && !stuck_any) {
           // The steady state of latency 0: the scheduler acts right after its time jump, so the acting cluster is quiescent — no envelope
           // due (at latency 0 a node that holds one has it due), hence every node idle with an empty queue and every client free.  Its
           // generator's op is then all the cluster does this round: an op round.  Every half that wants a GENERAL round has to be in
           // that state (main phase, not forced, nothing due, no client busy, room for a value and two rows); else the GENERAL body runs.
-          // (TRIM: each of the five masks is one compare; as bal() they were five compares hoisted to the head of the outer loop and ten
-          //  instructions here that turned the bools into masks again)
+          // (FLOOD: each of the five masks is one compare; as bal() they are five compares hoisted to the head of the outer loop and ten
+          //  instructions here that turn the bools into masks again)
           u64 bz_b, st_m;
-          if (TRIM) {
+          if (FLOOD) {
             bz_b = DUO_BAL_CMP(busy, !=, 0u, 33);
             st_m = ~fg_m & DUO_BAL_CMP(phase, ==, PH_MAIN, 32) & DUO_BAL_CMP(next_value, <, max_values, 36) & DUO_BAL_CMP(n_rows + 2u, <=, max_rows, 37) & DUO_BAL_CMP(gen_k - dc_base, <, 32u, 36) &
                    hm2((u32)due_b == 0 && (u32)bz_b == 0, (u32)(due_b >> 32) == 0 && (u32)(bz_b >> 32) == 0);
@@ -1127,7 +1051,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           // nothing, the poll finds in_n == 0, and n_rsv, n_arr stay.  Nothing st_m looks at changes while it waits, so the releasing
           // test finds it eligible again.  Waiting is bounded twice: by the cap, and at latency 0 by the partner's flood, which handles
           // something in every round until it ends, within the topology's eccentricity + 2 rounds of its op.
-          if (PAIR && !released && op_m != 0 && alive_m == ~0ull && (gw_m == 0xFFFFFFFFull || gw_m == 0xFFFFFFFF00000000ull)) {
+          if (FLOOD && !released && op_m != 0 && alive_m == ~0ull && (gw_m == 0xFFFFFFFFull || gw_m == 0xFFFFFFFF00000000ull)) {
             park_m = gw_m; park_left = (u32)DUO_PAIR_WAIT; want_m &= ~gw_m; op_m = 0; parks = true;
             alive_v = lane_in(gw_m) ? 0u : alive_v;
 #ifdef DUO_PROF
@@ -1137,7 +1061,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         }
         if (!parks) break;
       }
-      if (STRETCH && (alive_m & ~fl_m) == 0) {
+      if (FLOOD && (alive_m & ~fl_m) == 0) {
         // ---- FLOOD STRETCH: the flood gossip rounds of both clusters, one after the other, until something else than such a round is next.
         // This round is a flood gossip round: R0 and the exit test above have been through it.  What they would find in the NEXT one:
         //   * R0's block is entered exactly when a half has nothing due and is not parked, or the count-down reaches 0.  At latency 0 the
@@ -1163,14 +1087,14 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
 #ifdef DUO_PROF
         pf_nst++;
 #endif
-        // (STEADY: a steady park comes back to this wrapper with `continue`; every other stretch passes it once and leaves by the `break`
-        //  at its end.  THE CONVENTION BELOW IS OFF BY ONE ON PURPOSE: under STEADY the stretch's exit keeps park_left and st_more as the
-        //  loop's last park_left-- and st_more++ left them, i.e. with the NEXT round's count-down and count already taken, and the steady
-        //  leave is written on those values (park_left against 0, sl_r1 = rounds with the next round counted, round_limit < sl_r1); where it
-        //  declines it takes both back (park_left++, rounds = sl_r1 - alive_v) so that the loop's head finds what it always found, and the
-        //  -DDUO_PROF counters undo it too (pf_sn, pf_pl).  Written on the values after `park_left++; st_more--` instead, the compiler kept
-        //  wrapper and stretch as two loops and closed the inner one with s_mov + s_branch: a taken branch more on every round's back
-        //  edge (profiles/r31_isa_static.txt).  Whoever changes one of these places changes all of them.)
+        // (a steady park comes back to this wrapper with `continue`; every other stretch passes it once and leaves by the `break` at its
+        //  end.  THE CONVENTION BELOW IS OFF BY ONE ON PURPOSE: the stretch's exit keeps park_left and st_more as the loop's last
+        //  park_left-- and st_more++ left them, i.e. with the NEXT round's count-down and count already taken, and the steady leave is
+        //  written on those values (park_left against 0, sl_r1 = rounds with the next round counted, round_limit < sl_r1); where it declines
+        //  it takes both back (park_left++, rounds = sl_r1 - alive_v) so that the loop's head finds what it expects, and the -DDUO_PROF
+        //  counters allow for it too (pf_wmax).  Written on the values after `park_left++; st_more--` instead, the compiler kept wrapper
+        //  and stretch as two loops and closed the inner one with s_mov + s_branch: a taken branch more on every round's back edge
+        //  (profiles/r31_isa_static.txt).  Whoever changes one of these places changes all of them.)
         for (;;) {
         for (;;) {
           const bool st_n = lane_in(st_due);
@@ -1178,11 +1102,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           if (st_n && lane_in(alive_m) && cm > 0xFFFFFFu) __builtin_trap();   // the flood invariant
 #endif
           u32 pub; u64 pub_b; DUO_FLOOD_R3(st_n, st_due, pub, pub_b);
-          if (!TRIM) n_rsv += st_n ? 1u : 0u;
           if (pub_b) DUO_FLOOD_ARRIVALS(pub);
           st_due = bal(in_n != 0);   // the poll (DUO_FLOOD_POLL without deliver_at): whoever has a queue takes its head
           const bool st_can = lane_in(st_due);
-          cm = st_can ? nx : cm; if (TRIM) in_n = max(in_n, 1u) - 1u; else in_n -= st_can ? 1u : 0u;   /* (TRIM: one saturating subtraction) */
+          cm = st_can ? nx : cm; in_n = max(in_n, 1u) - 1u;   /* (one saturating subtraction) */
           // the back edge: the head of the next round (its count-down, its count) and the test that would send it into R0's block
           const u64 st_db = st_due | park_m;
           park_left--; st_more++;
@@ -1191,20 +1114,18 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           pf_nwave++;
 #endif
         }
-        // (the round that ends the stretch begins at the loop's head: its count-down and its count are taken there; STEADY: they are what the
-        //  steady leave needs, and are taken back where it declines, so that the back edge above keeps its one value of each)
-        if (!STEADY) { park_left++; st_more--; }
+        // (the round that ends the stretch begins at the loop's head: its count-down and its count are taken there; they are what the steady
+        //  leave needs, and are taken back where it declines, so that the back edge above keeps its one value of each)
 #ifdef DUO_PROF
         // one reading per stretch (one per round cost a round of this loop more than the round itself); a half is parked or released at the
         // exit test only, so a stretch is parked as a whole or not at all
-        { const u64 pf_s1 = __builtin_readcyclecounter();   // (STEADY: the steady leave is counted from here)
-          const u32 pf_sn = st_more + (STEADY ? 0u : 1u), pf_pl = park_left + (STEADY ? 1u : 0u);   // (STEADY: the stretch's count-down and count are not taken back)
-          if (pf_parked) { pf_pk += pf_s1 - pf_it; pf_npk += pf_sn; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - pf_pl); }
-          else { pf_fg += pf_s1 - pf_it; pf_nfg += pf_sn; }
-          pf_nstr += pf_sn;
+        { const u64 pf_s1 = __builtin_readcyclecounter();   // (the steady leave is counted from here)
+          // (st_more and park_left stand with the next round's count and count-down taken: the wait so far is one round less than it looks)
+          if (pf_parked) { pf_pk += pf_s1 - pf_it; pf_npk += st_more; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT - park_left); }
+          else { pf_fg += pf_s1 - pf_it; pf_nfg += st_more; }
+          pf_nstr += st_more;
           pf_it = pf_s1; }
 #endif
-        if (!STEADY) rounds += st_more * alive_v;
         deliver_at = lane_in(st_due) ? T : INF;
         // STEADY LEAVE.  The round that is next begins at the loop's head, and when the stretch ended because a half has run dry (dry_m: no
         // lane of it has something due, and it is not parked), nearly all that R0's block and the exit test do there is to find out again
@@ -1226,7 +1147,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         // that is not steady, a finished or absent partner, the count-down at 0, the limit reached) goes to the loop's head as ever,
         // where R0's block is entered by the same test that ended the stretch and rebuilds want_m.  No round, delivery or message is
         // skipped or batched: this removes tests.  All of it sits behind the stretch's exit; the back edge above is untouched.
-        if constexpr (STEADY) {
+        {
           const u64 dry_m = ~park_m & hm2((u32)st_due == 0, (u32)(st_due >> 32) == 0);
           const u32 sl_r1 = rounds + st_more * alive_v;   // the stretch's rounds and the next round's count
           if (alive_m == ~0ull && park_left != 0u && dry_m != 0 && (dry_m & ~(sd_m & ~fg_m)) == 0 &&
@@ -1297,20 +1218,12 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         }
         break;
         }
-        if (STEADY && op_m != 0) break;   // (a steady leave: op_m is 0 wherever else this point is reached, a parking exit test included)
-      } else if (FLOOD && (alive_m & ~fl_m) == 0) {   // ---- a flood gossip round: both clusters only gossip, each inside its flood ----
-        u32 pub; u64 pub_b; DUO_FLOOD_R3(due_n, due_b, pub, pub_b);
-        if (!TRIM) n_rsv += due_n ? 1u : 0u;
-        if (pub_b) DUO_FLOOD_ARRIVALS(pub);
-        DUO_FLOOD_POLL();
-#ifdef DUO_PROF
-        if (pf_parked) { pf_pk += __builtin_readcyclecounter() - pf_it; pf_npk++; pf_wmax = max(pf_wmax, (u32)DUO_PAIR_WAIT + 1u - park_left); } else { pf_fg += __builtin_readcyclecounter() - pf_it; pf_nfg++; }
-#endif
+        if (op_m != 0) break;   // (a steady leave: op_m is 0 wherever else this point is reached, a parking exit test included)
       } else {   // ---- a round in which both clusters only gossip ----
         P2_MARK(0)
         u32 pub; u64 pub_b; DUO_R3_SEEN(due_n, due_b, pub, pub_b);
         deliver_at = due_n ? INF : deliver_at;
-        if (!TRIM) n_rsv += due_n ? 1u : 0u;
+        if (!FLOOD) n_rsv += due_n ? 1u : 0u;
         P2_MARK(1)
         if (pub_b) {
           if (RND) DUO_RND_IDS(pub, false);
@@ -1348,8 +1261,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
           }
         }
       }
-      DUO_UPM_NOW();   // (C)
-      if (TRIM && (op_m & fl_m) != 0) DUO_FLOOD_WB(op_m & fl_m);   // (B): the read runs, the read op's copy read the sets from HBM
+      DUO_UPM_NOW();   // TRIM (C)
+      if (FLOOD && (op_m & fl_m) != 0) DUO_FLOOD_WB(op_m & fl_m);   // TRIM (B): the read runs, the read op's copy read the sets from HBM
       // READ RUNS.  An acting cluster is quiescent, and a read leaves it so: the picked node copies its set to the payload, two rows
       // appear, and the cluster's next round is its generator's next op.  While the op at hand is a read AND the op after it will
       // again be an op round's (its draw is in the cluster's block, it falls before the cutoff, its rows and this read's payload fit,
@@ -1585,7 +1498,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         if (sr_dirty) DUO_FLOOD_WB(sr_dirty);
         DUO_BPLAN_SEEN(op_m & fl_m);   // (a plan or the loop may have ended on a completed word, which the round below may leave behind)
       } else
-      if (RUNS) {
+      if (FLOOD) {
         for (;;) {
           const u32 rr_k = gen_k - dc_base;
           u32 rr_hi, rr_lo; DUO_DRAW(gen_k, rr_hi, rr_lo);
@@ -1631,12 +1544,12 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // updated in place, and the path meets the superset body's only in front of the tail they share.  The tests are scalar, on masks in SGPRs;
       // every other op wave-round (one op, a half outside flood mode, the first op behind a GENERAL body) takes the body below as it is.
       bool quiet = false;
-      if constexpr (QUIET) quiet = fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0;
+      if constexpr (FLOOD) quiet = fl_ok && (alive_m & ~op_m) == 0 && (op_m & ~fl_m) == 0;
       u64 dw_m = 0;   // MEMO: the halves this round leaves with nothing in flight: a read, a replayed broadcast (the quiet body knows them)
 #ifdef DUO_PROF
       bool pf_flr = false;
 #endif
-      if (QUIET && quiet) {
+      if (FLOOD && quiet) {
 #if defined(DUO_PROF) || defined(MSIM_HIPEMU)
         if (op_due != 0 || (opn && ((in_n | sp_n | busy) != 0 || deliver_at != INF))) __builtin_trap();   // the quiet invariant
 #endif
@@ -1735,7 +1648,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       // the word of the nodes' sets that the op's value falls in, fetched first: only the picked node's store at the end of the round
       // waits for it (a broadcast value is fresh — no node has seen it — so the node's dedup does not need it)
       u32 op_w = 0;
-      if (TRIM) {   // (B): the word of value next_value - 1: in sw already in flood mode, and 0 where the op's value opens a new word
+      if (FLOOD) {   // TRIM (B): the word of value next_value - 1: in sw already in flood mode, and 0 where the op's value opens a new word
         op_w = sw;
         if (op_m & ~fl_m) { if (opn && !lane_in(fl_m)) op_w = DUO_SET(set_lane + (((max(next_value, 1u) - 1u) & 0xFFE0u) << 2)); }
       } else
@@ -1755,8 +1668,8 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       u32 pub; u64 pub_b;
       if (fl_round) DUO_FLOOD_R3(due_n, op_due, pub, pub_b);
       else { DUO_R3_SEEN(due_n, op_due, pub, pub_b); deliver_at = due_n ? INF : deliver_at; }
-      if (!TRIM) n_rsv += due_n ? 1u : 0u;
-      pub = bc ? ((STRETCH && fl_round) ? adj : (0x80000000u | (63u << 16) | val)) : pub;   // (the flood bodies publish fan-out masks)
+      if (!FLOOD) n_rsv += due_n ? 1u : 0u;
+      pub = bc ? (fl_round ? adj : (0x80000000u | (63u << 16) | val)) : pub;   // (the flood bodies publish fan-out masks)
       pub_b |= bal(bc);
 #ifdef DUO_PROF
       pf_nbout += half_any(bc) ? 1u : 0u;
@@ -1781,7 +1694,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       }
       // R4: the invocation and the completion row
       if (sel) {
-        u32 r4_i = i; if (RUNS) MSIM_OPAQUE(r4_i);   // (RUNS: the rows' constant words are built here, not kept in registers across the rounds)
+        u32 r4_i = i; if (FLOOD) MSIM_OPAQUE(r4_i);   // (FLOOD: the rows' constant words are built here, not kept in registers across the rounds)
         const u64 tns = (u64)T * 1000ull;
         const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
         const u32 fk = is_rd ? (u32)MSIM_F_READ : (u32)MSIM_F_BROADCAST;
@@ -1790,11 +1703,10 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       }
       n_rows += opn ? 2u : 0u;
       // FLOOD: the picked node's new set word and every other lane's (unchanged) one: what the store writes and what sw becomes
-      if (TRIM) op_w = lane_in(op_m & DUO_BAL_CMP(r_lo & 1u, ==, 0u, 32) & DUO_BAL_CMP(val & 31u, ==, 0u, 32)) ? 0u : op_w;
+      if (FLOOD) op_w = lane_in(op_m & DUO_BAL_CMP(r_lo & 1u, ==, 0u, 32) & DUO_BAL_CMP(val & 31u, ==, 0u, 32)) ? 0u : op_w;
       const u32 op_w1 = FLOOD ? (op_w | (bc ? 1u << (val & 31u) : 0u)) : 0u;
       if (fl_round) {
         if (pub_b) DUO_FLOOD_ARRIVALS(pub);
-        if (!TRIM) { if (bc) DUO_SET(set_lane + ((val & 0xFFE0u) << 2)) = op_w1; }
         DUO_FLOOD_POLL();
       } else {
         if (pub_b) DUO_ARRIVALS(pub);
@@ -1820,18 +1732,18 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
         DUO_SCHED_VIEW(hbusy_b);
         alive_v = lane_in(alive_m) ? 1u : 0u;
         if (~alive_m) {
-          if (!lane_in(alive_m)) { if (QUIET) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE; else if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   /* what stays undelivered (A) */
+          if (!lane_in(alive_m)) { if (FLOOD) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE;   /* what stays undelivered (A) */
                                    deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }
         }
-        if (STEADY) sd_m = 0;
+        if (FLOOD) sd_m = 0;
       } else {
         sched_at = opn ? gen_next : sched_at;
-        // STEADY: the acting halves' bits of sd_m, on the state this round leaves (see sd_m); a half that did not act keeps its bit
+        // STEADY LEAVE: the acting halves' bits of sd_m, on the state this round leaves (see sd_m); a half that did not act keeps its bit
         // (three of sd_m's terms need no compare here.  phase == PH_MAIN and gen_next < cutoff: this is the else branch of the test above,
         //  which has just found both in every lane of every live half.  busy == 0: an acting half had no busy client when this op round was
         //  chosen, by st_m's sixth term or by its bit of sd_m, and an op round leaves busy as it is; looking at it here kept it in a register
         //  through the superset body, which sent that body's rarest path to scratch.  The emulator and -DDUO_PROF builds check all three at the use)
-        if constexpr (STEADY)
+        if constexpr (FLOOD)
           sd_m = (sd_m & ~op_m) | (op_m & fl_m & DUO_BAL_CMP(next_value, <, max_values, 36) & DUO_BAL_CMP(n_rows + 2u, <=, max_rows, 37) & DUO_BAL_CMP(gen_k - dc_base, <, 32u, 36));
       }
 #ifdef DUO_PROF
@@ -1863,15 +1775,15 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     } else {   // ---- a round in which a cluster's scheduler acts or a node handles its client's request ----
     P3_MARK(0)   // [0] = the gossip rounds
     DUO_MATERIALISE();
-    if (STEADY) sd_m = 0;   // (this body changes what the bits stand for, see sd_m)
+    if (FLOOD) sd_m = 0;   // (this body changes what the bits stand for, see sd_m)
 #ifdef DUO_PROF
     if (MEMO) pf_ndrop += ((u32)mm_rec ? 1u : 0u) + ((u32)(mm_rec >> 32) ? 1u : 0u);
 #endif
     if (MEMO) mm_rec = 0;   // (and a flood it takes part in is not recorded, see FLOOD MEMO)
-    // (RUNS: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
+    // (FLOOD: what this body derives from the lane number alone is built here, not kept in registers across the rounds)
     DUO_UPM_NOW();   // TRIM (C)
-    u32 gi = i; if (RUNS) MSIM_OPAQUE(gi);
-    const u32 g_lt = RUNS ? (1u << gi) - 1u : lt;
+    u32 gi = i; if (FLOOD) MSIM_OPAQUE(gi);
+    const u32 g_lt = FLOOD ? (1u << gi) - 1u : lt;
     u32 inv_row = 0, inv_packed = 0, inv_value = 0;
     u32 cmp_row = 0, cmp_packed = 0, cmp_value = 0, cmp_len = 0;
     // ---- R1: scheduler (core.clj:67-80): phase actions, one generated op ----
@@ -1940,7 +1852,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     const u32 v = cm & 0xFFFFu;
     u32 pub; u64 pub_b; DUO_R3_SEEN(due_n & (kind <= DK_BCAST), due_b & bal(kind <= DK_BCAST), pub, pub_b);
     deliver_at = due_n ? INF : deliver_at;
-    if (!TRIM) n_rsv += (due_n && kind == DK_PLAIN) ? 1u : 0u;
+    if (!FLOOD) n_rsv += (due_n && kind == DK_PLAIN) ? 1u : 0u;
     const bool req = due_n && kind != DK_PLAIN;   // a request of this lane's client: handled, answered and completed in this round
     n_cl += req ? 1u : 0u;
     busy = req ? 0u : busy;
@@ -1998,24 +1910,9 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
       if (bal(n_rows + nr > max_rows)) { flags |= ovf ? (u32)MSIM_FLAG_ROWS_OVERFLOW : 0u; alive_m &= ~bal(ovf); }   // (rare: out of rows)
       const u64 tns = (u64)T * 1000ull;
       const u32 tlo = (u32)tns, thi = (u32)(tns >> 32);
-      if (RND || DUO_DIRECT) {   // the bags of the random-latency layout take the LDS a staging area would need: rows go straight to HBM
-        if (inv_row != 0 && !ovf) DUO_ROW(n_rows + __popc(imask & g_lt)) = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row != 0 && !ovf) DUO_ROW(n_rows + ni + __popc(cmask & g_lt)) = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-      } else {
-        if (inv_row != 0 && !ovf) stage[(n_rows + __popc(imask & g_lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi, inv_packed, inv_value);
-        if (cmp_row != 0 && !ovf) stage[(n_rows + ni + __popc(cmask & g_lt)) % DUO_STAGE_ROWS] = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
-      }
+      if (inv_row != 0 && !ovf) DUO_ROW(n_rows + __popc(imask & g_lt)) = make_uint4(tlo, thi, inv_packed, inv_value);
+      if (cmp_row != 0 && !ovf) DUO_ROW(n_rows + ni + __popc(cmask & g_lt)) = make_uint4(tlo, thi | (cmp_len << 16), cmp_packed, cmp_value);
       const u32 new_n = ovf ? n_rows : n_rows + nr;
-      const bool flush = !RND && !DUO_DIRECT && (new_n >> 6) != (n_rows >> 6);   // a 64-row block completed (at most one per round: nr <= 64)
-      if (__ballot(flush)) {
-        wave_lds_fence();
-        if (flush) {
-          const u32 g0 = (n_rows >> 6) * 64u + i;
-          if (g0 < max_rows) reinterpret_cast<uint4 *>(g_rows)[g0] = stage[g0 % DUO_STAGE_ROWS];
-          if (g0 + 32u < max_rows) reinterpret_cast<uint4 *>(g_rows)[g0 + 32u] = stage[(g0 + 32u) % DUO_STAGE_ROWS];
-        }
-        wave_lds_fence();
-      }
       n_rows = new_n;
     }
 
@@ -2033,7 +1930,7 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
     }
     alive_v = lane_in(alive_m) ? 1u : 0u;
     if (~alive_m) {
-      if (!lane_in(alive_m)) { if (QUIET) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE; else if (TRIM) n_rsv += in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy;   // what stays undelivered (A)
+      if (!lane_in(alive_m)) { if (FLOOD) my_flags += (in_n + sp_n + (deliver_at != INF ? 1u : 0u) - busy) * DUO_DROP_ONE;   // what stays undelivered (A)
                                deliver_at = INF; in_n = 0; sp_n = 0; have_creq = 0; bag_used = 0; }   // a finished cluster takes no further part
     }
     P3_MARK(7)   // [7] = the scheduler's view
@@ -2049,30 +1946,24 @@ __global__ void __launch_bounds__(64, LAT0 ? DUO_LAT0_WAVES : 1) sim_kernel_duo(
   const u32 pf_nrunb_all = rdlane(pf_nrunb, 0) + rdlane(pf_nrunb, 32);
 #endif
 
-  // ---- epilogue: the partial row block, net stats, meta ----
+  // ---- epilogue: net stats, meta ----
   __syncthreads();
-  {
-    const u32 g0 = (n_rows >> 6) * 64u + i;
-    if (!RND && !DUO_DIRECT && real && g0 < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0] = stage[g0 % DUO_STAGE_ROWS];
-    if (!RND && !DUO_DIRECT && real && g0 + 32u < n_rows) reinterpret_cast<uint4 *>(g_rows)[g0 + 32u] = stage[(g0 + 32u) % DUO_STAGE_ROWS];
-  }
-  // (a dropped envelope is not received either; QUIET: what a stopped half left undelivered is counted there as well, `- busy` and all, so the
-  //  field is read as a signed number: the sum over a lane is what n_rsv and the drop count gave together)
-  if (QUIET) n_rsv += (u32)((int)my_flags >> 8); else
-  if (TRIM) n_rsv += my_flags / DUO_DROP_ONE;
+  // (FLOOD, see TRIM (A): a dropped envelope is not received either; what a stopped half left undelivered is counted there as well, `- busy`
+  //  and all, so the field is read as a signed number)
+  if (FLOOD) n_rsv += (u32)((int)my_flags >> 8);
   const u32 sc_cl = wave_incl_scan(n_cl), sc_arr = wave_incl_scan(n_arr), sc_rsv = wave_incl_scan(n_rsv);
   const u32 lo_cl = rdlane(sc_cl, 31), lo_arr = rdlane(sc_arr, 31), lo_rsv = rdlane(sc_rsv, 31);
   const u32 t_cl = hi ? rdlane(sc_cl, 63) - lo_cl : lo_cl;
   const u32 t_arr = hi ? rdlane(sc_arr, 63) - lo_arr : lo_arr;
   const u32 t_rsv = hi ? rdlane(sc_rsv, 63) - lo_rsv : lo_rsv;
   for (u32 b = 1; b <= MSIM_FLAG_JOURNAL_OVERFLOW; b <<= 1) if (hb((my_flags & b) != 0, hi)) flags |= b;
-  u32 eo_l = lane; if (RUNS) MSIM_OPAQUE(eo_l);   // (RUNS: not even the lane-derived index is carried through the rounds)
-  const u32 inst_out = RUNS ? blockIdx.x * 2u + (eo_l >> 5) : FLOOD ? inst_raw : inst;   // (real: the same; FLOOD: recomputed from the lane, nothing is kept across the rounds for it)
+  u32 eo_l = lane; if (FLOOD) MSIM_OPAQUE(eo_l);   // (FLOOD: not even the lane-derived index is carried through the rounds)
+  const u32 inst_out = FLOOD ? blockIdx.x * 2u + (eo_l >> 5) : inst;   // (real: the same; FLOOD: recomputed from the lane, nothing is kept across the rounds for it)
   if (real && i == 0) {
     // every client RPC is a request and a reply, each sent and received once (no loss, no timeouts in this layout)
     msim_net_stats st;
     st.clients_send = 2ull * t_cl; st.clients_recv = 2ull * t_cl;
-    st.servers_send = t_arr; st.servers_recv = TRIM ? t_arr - t_rsv : t_rsv;   // (TRIM: n_rsv holds what stayed undelivered)
+    st.servers_send = t_arr; st.servers_recv = FLOOD ? t_arr - t_rsv : t_rsv;   // (FLOOD: n_rsv holds what stayed undelivered, see TRIM (A))
     st.all_send = st.clients_send + st.servers_send; st.all_recv = st.clients_recv + st.servers_recv;
     p.stats[inst_out] = st;
     msim_inst_meta m; m.n_rows = n_rows; m.n_payload_words = n_payload; m.flags = flags; m.n_rounds = rounds;
@@ -2197,7 +2088,7 @@ static hipError_t duo_launch_any(const KParams &kp, uint32_t n, hipStream_t st, 
   const bool rnd = c.latency_dist != MSIM_LAT_CONSTANT;
   const bool lat0 = !rnd && c.latency_mean_ms == 0;
   const uint32_t cap_tot = c.inbox_capacity + c.spill_capacity;
-  // LDS of one cluster = [row staging (not RND)] [queues]; the node sets live in HBM scratch (msim_duo_extra_scratch_words).  The
+  // LDS of one cluster = [queues]; the node sets live in HBM scratch (msim_duo_extra_scratch_words).  The
   // queues are sized by the rule of the layout that kept the sets in LDS too: as many ring entries per node as fit beside the sets in
   // 10 KiB per cluster, at least 8, at most inbox_capacity (rounded up to a power of two); what does not fit goes to the HBM spill area.
   // R, S and with them the fit test below (and so which kernel runs a configuration) are the same as then; only the sets' bytes left.
@@ -2205,8 +2096,7 @@ static hipError_t duo_launch_any(const KParams &kp, uint32_t n, hipStream_t st, 
   // instantiation allow), at most 6.8 KB of LDS each.  The headline shape (lat 0, inbox 6: R = 8) takes 2 KiB per wavefront; constant
   // latency > 0 (R = 16: 8 KiB, 20 per CU = the 5 per SIMD its registers allow) and RND (9.4 KB) shrink by the sets as well.
   const size_t set_bytes_v1 = (((size_t)kp.N * (kp.W | 1u) + 32) * 4 + 15) & ~(size_t)15;   // what the sets took of the LDS budget
-  const size_t stage_bytes = (rnd || DUO_DIRECT) ? 0 : DUO_STAGE_ROWS * 16;   // (rows are staged only in the -DDUO_STAGED_ROWS build)
-  const size_t fixed = set_bytes_v1 + stage_bytes;
+  const size_t fixed = set_bytes_v1;
   const size_t per_entry = rnd ? 0 : (size_t)32 * (lat0 ? 4 : 8);   // (RND: bags of a fixed 16 entries)
   const size_t budget = (20 * 1024 - (rnd ? 257 * 4 + 16 : 0)) / 2;
   uint32_t R = rnd ? DUO_BAG : 8;
@@ -2217,7 +2107,7 @@ static hipError_t duo_launch_any(const KParams &kp, uint32_t n, hipStream_t st, 
   // the spill area is spill_capacity x 16 bytes per node: 8-byte ring entries (constant latency) or 12-byte bag entries (RND)
   if ((size_t)dp.S * (rnd ? 12 : 8) > (size_t)c.spill_capacity * 16) return MSIM_LAYOUT_DOES_NOT_FIT;
   if (rnd) MSIM_UPLOAD_ONCE(duo_log2_q24, msim_log2_q24, sizeof(msim_log2_q24));   // (1 KiB, once per device)
-  size_t off = stage_bytes;
+  size_t off = 0;
   dp.off_ring = (u32)off; off += rnd ? (size_t)(kp.N + 1) * DUO_BAG * 8 : (size_t)32 * R * (lat0 ? 4 : 8);
   dp.off_seq = (u32)off; if (rnd) off += (((size_t)(kp.N + 1) * DUO_BAG * 2) + 15) & ~(size_t)15;
   dp.R = R;
@@ -2238,7 +2128,7 @@ static hipError_t duo_launch_any(const KParams &kp, uint32_t n, hipStream_t st, 
   // the flood instantiation keeps each cluster's block of 32 generator draws in LDS, behind its queues (256 bytes; lat 0 rings are at most
   // 8 KiB per cluster, so this never decides the fit test above: which kernel runs a configuration stays as it was)
   dp.off_dc = 0;
-  if (DUO_PLAN_ON && DUO_FLOOD_ON && lat0 && deg4) { dp.off_dc = (u32)off; off += 32 * 8; dp.half_bytes = (u32)off; }
+  if (DUO_FLOOD_ON && lat0 && deg4) { dp.off_dc = (u32)off; off += 32 * 8; dp.half_bytes = (u32)off; }
   dp.off_log2 = (u32)(2 * off);
   // the memo instantiation's table of remembered floods, one per wavefront, behind both clusters' regions (the headline shape: 2560 + 2048
   // bytes per wavefront, 24 wavefronts per CU as before; the fit test above is not touched: which kernel runs a configuration stays as it was)

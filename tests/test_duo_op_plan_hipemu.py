@@ -22,8 +22,10 @@ whose scheduler's view stops the cluster), and hold a history and payload that a
 must contain limits at which the last three ops the cluster executed were read, read, op and the two limits before each stopped the
 cluster one op earlier: then the three ran in rounds L - 1, L and L + 1, the second read in round L behind the first read of its run,
 where the run's own test of the limit decides.  On the emulator the
-library built with -DDUO_NO_PLAN (no runs: the parent's code) must give the same digests, limit for limit.
-tests/test_duo_op_plan_gpu.py runs all of this on the device (but for the -DDUO_NO_PLAN build)."""
+library built with -DDUO_NO_FLOOD (no flood mode, so no runs, pairs or stretches: the generic code that the other instantiations of the
+kernel run) must give the same digests, limit for limit.  This is the one live build-against-build test of the one-cluster sweep; the
+sweep's digests are also recorded in tests/golden/duo_round_limits.json (see tests/test_duo_trim_hipemu.py).
+tests/test_duo_op_plan_gpu.py runs all of this on the device (but for the -DDUO_NO_FLOOD build)."""
 import ast
 import hashlib
 import json
@@ -185,17 +187,17 @@ def test_duo_read_runs_on_the_emulator_stopped_by_a_capacity(emu_lib):
 def test_duo_read_runs_on_the_emulator_with_a_round_limit_inside_a_run(emu_lib):
     sys.path.insert(0, os.path.join(ROOT, "tools", "hipemu"))
     import build_emu
-    noplan = build_emu.build_variant("noplan", "duo.hip", ["-DDUO_NO_PLAN"])
+    noflood = build_emu.build_variant("noflood", "duo.hip", ["-DDUO_NO_FLOOD"])
     got = {}
-    for tag, lib in (("runs", emu_lib), ("noplan", noplan)):
+    for tag, lib in (("runs", emu_lib), ("noflood", noflood)):
         env = dict(os.environ, MSIM_LIB=lib, HIPEMU_DIVERGENT="1", MSIM_GUARD="3")
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "limits"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
         assert r.returncode == 0, tag + ": " + r.stdout[-3000:] + r.stderr[-3000:]
         got[tag] = json.loads(r.stdout.strip().splitlines()[-1])
     assert got["runs"]["inside"] >= 5, f"only {got['runs']['inside']} limits fell behind the first read of a run"
     assert sorted(got["runs"]["digests"]) == sorted(str(x) for x in LIMITS)
-    diff = [k for k in got["runs"]["digests"] if got["runs"]["digests"][k] != got["noplan"]["digests"][k]]
-    assert not diff, f"the builds with and without read runs differ at the limits {diff[:10]}"
+    diff = [k for k in got["runs"]["digests"] if got["runs"]["digests"][k] != got["noflood"]["digests"][k]]
+    assert not diff, f"the builds with and without flood mode differ at the limits {diff[:10]}"
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 bit for bit against the oracle (history, payload, meta with n_rounds, the six net-stats counters).  Every case is that module's shape
 with a handful of clusters at a time limit of at most 1 s of virtual time (GPU_CASES: the oracle flags none of them, see that module's
 test_no_case_is_flagged); the poisoned cases run with every device buffer filled with 0xA5, in a process of their own; the shapes that
-a capacity stops are compared by their flags.  The comparison with a -DDUO_NO_QUIET build under round limits (clusters stopped with
+a capacity stops are compared by their flags.  The comparison with the recorded sweeps under round limits (clusters stopped with
 envelopes in flight) and the count of quiet op rounds run on the emulator."""
 import os
 import subprocess

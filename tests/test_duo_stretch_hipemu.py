@@ -17,8 +17,9 @@ before the launch, in a process of its own.
 
 STOPS (those of tests/test_duo_pair_ops_hipemu.py: the three capacities at 2 and 4 clusters) are compared by their flags, as everywhere
 in this project.  The round limit: two clusters of the headline shape under MSIM_DUO_ROUND_LIMIT = 40 .. 160 with the conditions of that
-module's check_pair_limits, and the one-cluster sweep of tests/test_duo_op_plan_hipemu.py, whose digests this build and a
--DDUO_NO_STRETCH build must share limit for limit: the limit is looked at at the same rounds as before.
+module's check_pair_limits.  That the limit is looked at at the same rounds as without the stretch is held by the one-cluster sweep of
+tests/test_duo_op_plan_hipemu.py (this build against a -DDUO_NO_FLOOD build, limit for limit) and by the recorded digests of both sweeps
+(tests/golden/duo_round_limits.json, tests/test_duo_trim_hipemu.py).
 
 THE STRETCH HAPPENS (emulator, a -DDUO_PROF -DDUO_PROF_STRETCH build): at the headline shape the rounds taken inside stretches are at
 least 0.9 x (flood gossip rounds + parked rounds), and there are fewer stretches than such rounds.  Beyond that: a stretch ends when
@@ -152,16 +153,6 @@ def test_duo_stretch_on_the_emulator_with_a_round_limit(emu_lib):
     assert "pair limits: OK" in _self(emu_lib, "pair_limits")
 
 
-@pytest.mark.timeout(1800)
-def test_duo_one_cluster_round_limits_are_those_of_the_build_without_the_stretch(emu_lib):
-    from test_duo_op_plan_hipemu import LIMITS
-    plain = _variant("nostretch", ["-DDUO_NO_STRETCH"])
-    got = {tag: json.loads(_self(lib, "limits").strip().splitlines()[-1]) for tag, lib in (("stretch", emu_lib), ("plain", plain))}
-    assert sorted(got["stretch"]) == sorted(str(x) for x in LIMITS)
-    diff = [k for k in got["stretch"] if got["stretch"][k] != got["plain"][k]]
-    assert not diff, f"the builds with and without the flood stretch differ at the limits {diff[:10]}"
-
-
 @pytest.mark.timeout(900)
 def test_duo_flood_rounds_are_taken_in_stretches_on_the_emulator(emu_lib):
     prof = _variant("stretchprof", ["-DDUO_PROF", "-DDUO_PROF_STRETCH"])
@@ -175,10 +166,7 @@ def test_duo_flood_rounds_are_taken_in_stretches_on_the_emulator(emu_lib):
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["limits"]:
-        from test_duo_op_plan_hipemu import limit_sweep
-        print(json.dumps(limit_sweep()[0]))
-    elif sys.argv[1:] == ["stretch"]:
+    if sys.argv[1:] == ["stretch"]:
         print(json.dumps(stretch_counts()))
     elif sys.argv[1:] == ["pair_limits"]:
         check_pair_limits()

@@ -1,8 +1,8 @@
-"""tests/test_duo_trim_hipemu.py's cases on the device: the trims of the stretch instantiation of the two-clusters-per-wavefront broadcast
+"""tests/test_duo_trim_hipemu.py's cases on the device: the trims of the flood instantiation of the two-clusters-per-wavefront broadcast
 kernel (csrc/duo.hip, latency 0: servers_recv by conservation, the flood's set word written back once, the half's offsets once per op
 wave-round), bit for bit against the oracle (history, payload, meta with n_rounds, the six net-stats counters); one case with every
 device buffer poisoned, in a process of its own; and the shapes that a capacity stops, compared by their flags as that module says.
-The comparison with a -DDUO_NO_TRIM build under round limits (clusters stopped with envelopes in flight) runs on the emulator."""
+The comparison with the recorded sweeps under round limits (clusters stopped with envelopes in flight) runs on the emulator."""
 import os
 import subprocess
 import sys

@@ -1,5 +1,5 @@
-"""The trims of the stretch instantiation of the two-clusters-per-wavefront broadcast kernel (csrc/duo.hip, latency 0, at most four
-neighbours; -DDUO_NO_TRIM compiles them out):
+"""The trims of the stretch instantiation of the two-clusters-per-wavefront broadcast kernel (csrc/duo.hip, the flood instantiation: latency 0, at most
+four neighbours):
   (A) no body counts the delivered server envelopes: servers_recv = servers_send - what is queued or held when the cluster stops;
   (B) the flood bodies do not store the node's set word: a half in flood mode writes it back once, at the head of an op round in which it
       acts and when it leaves flood mode, and an acting half takes the op's word from the register;
@@ -14,10 +14,17 @@ boundary (test_no_case_is_flagged checks both, on the oracle alone; a shape that
 stops).  POISONED runs with every device buffer filled with 0xA5 before the launch, in a process of its own: a read that finds a set word
 the deferred store has not written copies poison.  The three capacity stops are compared by their flags, as everywhere in this project.
 
-BUILD AGAINST BUILD.  An unflagged instance never ends with an envelope in flight, so the oracle cannot see a wrong servers_recv or a late
-write-back at a stop.  Under MSIM_DUO_ROUND_LIMIT a cluster stops in the middle of a flood: the one-cluster sweep of
-tests/test_duo_op_plan_hipemu.py and two clusters of the headline shape under the limits 40 .. 160 must give, limit for limit, what a
--DDUO_NO_TRIM build gives (which compiles to the previous kernel): rows, payload, meta and all six net-stats counters.
+THE RECORDED ROUND LIMITS.  An unflagged instance never ends with an envelope in flight, so the oracle cannot see a wrong servers_recv, a
+late write-back, a delivery that skips the queue or a look at the limit in another round at a stop.  Under MSIM_DUO_ROUND_LIMIT a cluster
+stops in the middle of a flood: the one-cluster sweep of tests/test_duo_op_plan_hipemu.py (LIMITS) and two clusters of the headline shape
+under the limits 40 .. 160 (PAIR_LIMITS) must give, limit for limit, what tests/golden/duo_round_limits.json holds: rows, payload, meta
+and all six net-stats counters.  The file is what `python tests/test_duo_trim_hipemu.py limits` printed at commit f51b6dc, the last one
+whose duo.hip could be built with each of its optimisation levels switched off: "one" from the -DDUO_NO_FLOOD emulator build, "pair" from
+the -DDUO_NO_STRETCH emulator build (the oldest level with paired op rounds: pairing changes which rounds a cluster takes beside its
+partner).  At that commit the product build and the builds without the trims, the quiet op round, the steady leave, the memo, the steady
+run, the block plan and the flood table gave the same two sweeps, and every build the same one-cluster sweep.  The one-cluster sweep is
+also held against a live -DDUO_NO_FLOOD build (tests/test_duo_op_plan_hipemu.py).  A deliberate change of these outputs is recorded again
+from the then-current product build, in the commit that makes it, and reviewed as such.
 tests/test_duo_trim_gpu.py runs the cases on the device."""
 import hashlib
 import json
@@ -40,6 +47,7 @@ FEW_VALUES = "{'workload':'broadcast','node_count':25,'rate':100,'time_limit':0.
 ADDED = [ONE_CLUSTER, FEW_VALUES]
 CASES = S.CASES + ADDED
 PAIR_LIMITS = list(range(40, 161))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "duo_round_limits.json")
 NET = ("all_send", "all_recv", "clients_send", "clients_recv", "servers_send", "servers_recv")
 
 
@@ -105,18 +113,21 @@ def test_duo_trim_on_the_emulator_stopped_by_a_capacity(emu_lib):
 
 
 @pytest.mark.timeout(1800)
-def test_duo_trim_round_limits_are_those_of_the_build_without_the_trims(emu_lib):
+def test_duo_round_limits_are_the_recorded_ones(emu_lib):
+    """both sweeps of the product emulator build against tests/golden/duo_round_limits.json (see THE RECORDED ROUND LIMITS above)"""
     from test_duo_op_plan_hipemu import LIMITS
-    plain = _variant("notrim", ["-DDUO_NO_TRIM"])
-    got = {tag: json.loads(_self(lib, "limits").strip().splitlines()[-1]) for tag, lib in (("trim", emu_lib), ("plain", plain))}
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = json.loads(_self(emu_lib, "limits").strip().splitlines()[-1])
+    assert sorted(got) == sorted(want) == ["one", "pair"]
     for sweep, limits in (("one", LIMITS), ("pair", PAIR_LIMITS)):
-        a, b = got["trim"][sweep], got["plain"][sweep]
-        assert sorted(a) == sorted(str(x) for x in limits)
+        a, b = got[sweep], want[sweep]
+        assert sorted(a) == sorted(b) == sorted(str(x) for x in limits)
         assert all(len(row) == 5 + len(NET) for d in a.values() for row in d)
         diff = [k for k in a if a[k] != b[k]]
-        assert not diff, f"{sweep}: the builds with and without the trims differ at the limits {diff[:10]}: {a[diff[0]]} != {b[diff[0]]}"
-    # the sweeps do stop clusters with envelopes in flight: servers_recv < servers_send somewhere
-    assert any(row[-1] < row[-2] for d in got["trim"]["pair"].values() for row in d)
+        assert not diff, f"{sweep}: the build and the recorded sweep differ at the limits {diff[:10]}: {a[diff[0]]} != {b[diff[0]]}"
+    # the pair sweep does stop clusters with envelopes in flight: servers_recv < servers_send somewhere
+    assert any(row[-1] < row[-2] for d in got["pair"].values() for row in d)
 
 
 if __name__ == "__main__":

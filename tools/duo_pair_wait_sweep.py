@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): the sim kernel's time on the library MSIM_LIB names, for the sweep of the duo kernel's wait cap DUO_PAIR_WAIT
-(variants: tools/variant_lib.sh w3 duo.hip -DDUO_PAIR_WAIT=3 ...; nopair: -DDUO_NO_PAIR).  Prints one JSON line per shape: the headline
+(variants: tools/variant_lib.sh w3 duo.hip -DDUO_PAIR_WAIT=3 ...).  Prints one JSON line per shape: the headline
 shape (25 nodes, grid) and the long-flood shape the cap is for (a line of 24 nodes), 4096 instances each, the median of RUNS launches.
     MSIM_LIB=maelstrom_amd/libmaelsim_w3.so python tools/duo_pair_wait_sweep.py w3 >> profiles/r13_pair_wait_sweep.jsonl"""
 import json
