@@ -812,6 +812,7 @@ void msim_destroy(msim_ctx *ctx);
 
 #include "maelsim_kafka_explain.h"   /* kafka: the explained verdicts (the contract: above msim_check_unique_batch) */
 #include "maelsim_small_explain.h"   /* pn-counter / g-counter, unique-ids, echo: the explained verdicts (the contract: that file's comments) */
+#include "maelsim_journal.h"         /* the net journal's messages: sends joined to their recvs, counts, delivery latencies (the contract: that file's comments) */
 
 #ifdef __cplusplus
 }

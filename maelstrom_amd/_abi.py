@@ -184,6 +184,18 @@ class EchoExplain(C.Structure):
     _fields_ = [("n_errors", C.c_uint32), ("truncated", C.c_uint32)]
 
 
+class JournalMsg(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("send_event", C.c_uint32), ("recv_event", C.c_uint32), ("send_time_us", C.c_uint32),
+                ("latency_us", C.c_uint32), ("kind", C.c_uint32), ("route", C.c_uint32), ("a", C.c_uint32)]
+
+
+class JournalSummary(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("n_events", C.c_uint32), ("flags", C.c_uint32), ("n_msgs", C.c_uint32),
+                ("send_count", C.c_uint32 * 3), ("recv_count", C.c_uint32 * 3), ("msg_count", C.c_uint32 * 3), ("undelivered", C.c_uint32 * 3),
+                ("dup_sends", C.c_uint32), ("orphan_recvs", C.c_uint32), ("extra_recvs", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("client_slots", C.c_uint32), ("reserved", C.c_uint32 * 3), ("endpoints", C.c_uint32 * 8), ("latency", LatencyDist * 2)]
+
+
 # The one table of records: the header's struct name -> its Structure, field names and order as in include/maelsim.h.  engine.py derives
 # the numpy dtypes from these (np.dtype(Structure)); tests/test_abi_tables.py compiles a probe against the header and compares every
 # size and offset with both.
@@ -301,6 +313,17 @@ SMALL_EXPLAIN_PROTOTYPES = {
     "msim_explain_echo": _small_ctx,
 }
 
+# ... and for include/maelsim_journal.h: the net journal's messages (tests/test_journal_messages.py holds these to their header).
+JOURNAL_TRUNCATED, JOURNAL_TABLE_TRUNCATED = 1, 2   # MSIM_JOURNAL_*
+JOURNAL_WG = 256   # journal_messages_kernel's workgroup (csrc/journal_dev.hip): the events are swept in blocks of this many
+JOURNAL_RECORDS = {"msim_journal_msg": JournalMsg, "msim_journal_summary": JournalSummary}
+JOURNAL_PROTOTYPES = {
+    "msim_journal_messages_rows": (_i, (_vp, _u32, _u32, _u32, _vp, _vp, _u32)),
+    "msim_journal_messages_batch": (_i, (_i, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp)),
+    "msim_journal_messages": (_i, (_vp, _vp, _vp, _u32, _u32)),
+    "msim_journal_svg_rows": (_i, (_P(Config), _vp, _u32, _s, _sz, _P(_sz))),
+}
+
 _lib = None
 
 
@@ -313,7 +336,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -m maelstrom_amd.build` (hipcc, gfx950). "
                            "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES, **SMALL_EXPLAIN_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES, **SMALL_EXPLAIN_PROTOTYPES, **JOURNAL_PROTOTYPES}.items():
         fn = getattr(lib, name, None)   # MSIM_LIB may name an older build (the A/B tools under tools/ time the parent's): an entry it lacks is skipped, and calling it still raises
         if fn is not None:
             fn.restype, fn.argtypes = restype, list(argtypes)

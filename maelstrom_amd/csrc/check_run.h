@@ -167,9 +167,10 @@ void msim_unique_explain_instance_host(const msim_op *rows, uint32_t n_rows, uin
                                        uint32_t max_dups);
 
 // The hand-off: the rows and payload words of the histories `todo` come to the host, analyse(rows, n_rows, payload, n_words, flags, i)
-// — which writes h_out[i] — runs on up to msim_host_threads() threads, the finished records go back to d_out + i.
-template <class F>
-static inline int hand_off(msim_ctx *ctx, const HistorySource &s, u32 n, const std::vector<u32> &todo, const msim_check_result *h_out, msim_check_result *d_out, F analyse) {
+// — which writes h_out[i] — runs on up to msim_host_threads() threads, the finished records go back to d_out + i.  (R: the record of
+// a history — msim_check_result, or journal_dev.hip's msim_journal_summary over journals, whose 16-byte events go as rows.)
+template <class R, class F>
+static inline int hand_off(msim_ctx *ctx, const HistorySource &s, u32 n, const std::vector<u32> &todo, const R *h_out, R *d_out, F analyse) {
   if (todo.empty()) return MSIM_OK;
   std::vector<uint64_t> ro, po;
   if (!s.hmeta) {
@@ -198,7 +199,7 @@ static inline int hand_off(msim_ctx *ctx, const HistorySource &s, u32 n, const s
       }
     });
   for (auto &x : th) x.join();
-  for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(d_out + i, &h_out[i], sizeof(msim_check_result), hipMemcpyHostToDevice));
+  for (u32 i : todo) MSIM_HIP_TRY(ctx, hipMemcpy(d_out + i, &h_out[i], sizeof(R), hipMemcpyHostToDevice));
   return MSIM_OK;
 }
 
@@ -251,9 +252,9 @@ struct CycleMode {
 // workspace, rounded to 256 bytes) —, each with `bytes_per_history` of the grow-only workspace, as many per launch as `budget` holds:
 // launch(d_list, ws, first, count) for every chunk, then the n records of the launch to h_out, waited for.  Returns the launches made,
 // or an error (< 0).
-template <class F>
+template <class F, class R>
 static inline int chunked_pass(msim_ctx *ctx, u32 m, uint64_t bytes_per_history, uint64_t budget, const std::vector<u32> *list, void **ws_buf, size_t *ws_cap, F launch,
-                               const msim_check_result *d_out, msim_check_result *h_out, u32 n, hipStream_t st) {
+                               const R *d_out, R *h_out, u32 n, hipStream_t st) {
   const size_t list_bytes = list ? ((size_t)m * 4 + 255) & ~(size_t)255 : 0;
   const u32 chunk = chunk_for(m, bytes_per_history, budget, msim_dev_flags(ctx));
   if (int rc = grow_ws(ctx, ws_buf, ws_cap, list_bytes + (size_t)chunk * bytes_per_history)) return rc;
@@ -263,7 +264,7 @@ static inline int chunked_pass(msim_ctx *ctx, u32 m, uint64_t bytes_per_history,
   hipError_t e;
   const u32 launches = for_chunks(m, chunk, &e, [&](u32 first, u32 count) { launch(d_list, ws, first, count); });
   MSIM_HIP_TRY(ctx, e);
-  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(msim_check_result), hipMemcpyDeviceToHost, st));
+  MSIM_HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(R), hipMemcpyDeviceToHost, st));
   MSIM_HIP_TRY(ctx, hipStreamSynchronize(st));
   return (int)launches;
 }

@@ -32,6 +32,7 @@
 
 #include "../../include/maelsim.h"
 #include "engine_limits.h"
+#include "journal_names.h"
 
 namespace {
 
@@ -82,27 +83,8 @@ struct FW {
   void list_header(size_t n) { if (n < 8) raw((uint8_t)(0xE4 + n)); else { raw(0xEC); integer((int64_t)n); } }
 };
 
-// endpoints behind the client slots are services (service.clj:290-296): the proxy's is the one it was pointed at, the single-root
-// transactional node uses lin-kv, the multi-key one lin-kv then lww-kv
-std::string endpoint(uint32_t e, uint32_t n_nodes, uint32_t slots, const msim_config *cfg) {
-  char b[16];
-  if (e < n_nodes) std::snprintf(b, sizeof b, "n%u", e);
-  else if (e < n_nodes + slots) std::snprintf(b, sizeof b, "c%u", e - n_nodes);
-  else {
-    const char *name = "lin-kv";
-    if (cfg->node_program == MSIM_NODE_LIN_KV_PROXY) name = cfg->proxy_service == MSIM_SVC_SEQ_KV ? "seq-kv" : cfg->proxy_service == MSIM_SVC_LWW_KV ? "lww-kv" : "lin-kv";
-    else if ((cfg->node_program == MSIM_NODE_TXN_MULTI_KEY || cfg->node_program == MSIM_NODE_TXN_DATOMIC) && e == n_nodes + slots + 1) name = "lww-kv";
-    else if (cfg->node_program == MSIM_NODE_TSO_IDS) name = "lin-tso";
-    std::snprintf(b, sizeof b, "%s", name);
-  }
-  return b;
-}
-
-const char *const MSG_TYPES[] = {"", "init", "init_ok", "topology", "topology_ok", "echo", "echo_ok", "broadcast", "broadcast_ok", "read", "read_ok",
-                                 "add", "add_ok", "replicate", "write", "write_ok", "cas", "cas_ok", "error", "request_vote", "request_vote_res",
-                                 "append_entries", "append_entries_res", "txn", "txn_ok", "generate", "generate_ok", "replicate_ack", "ts", "ts_ok",
-                                 "send", "send_ok", "poll", "poll_ok", "list_committed_offsets", "list_committed_offsets_ok", "commit_offsets", "commit_offsets_ok",
-                                 "broadcast_many", "broadcast_many_ok"};
+using journal_names::endpoint;
+using journal_names::MSG_TYPES;
 
 bool is_reply(uint32_t t) {
   switch (t) {

@@ -20,6 +20,7 @@ from . import _abi as A
 KAFKA_FINDING_DT, KAFKA_EXPLAIN_DT = np.dtype(A.KafkaFinding), np.dtype(A.KafkaExplain)   # (A.KAFKA_EXPLAIN_RECORDS)
 (PN_READ_DT, PN_RANGE_DT, PN_EXPLAIN_DT, UNIQUE_DUP_DT, UNIQUE_EXPLAIN_DT, ECHO_ERROR_DT, ECHO_EXPLAIN_DT) = (
     np.dtype(s) for s in A.SMALL_EXPLAIN_RECORDS.values())
+JOURNAL_MSG_DT, JOURNAL_SUMMARY_DT = (np.dtype(s) for s in A.JOURNAL_RECORDS.values())
 META_DT = np.dtype([(n, "<u4") for n in ("n_rows", "n_payload_words", "flags", "n_rounds", "n_events", "r0", "r1", "r2")])
 PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
@@ -266,6 +267,18 @@ class Engine:
         res, hdr, recs = self._explain_small("msim_explain_echo", ECHO_EXPLAIN_DT, ECHO_ERROR_DT, max_errors)
         return [(res[i], hdr[i], recs[i, :int(hdr[i]["n_errors"])].copy()) for i in range(self.n)]
 
+    def journal_messages(self, max_msgs):
+        """The net journals of the last run analysed where they lie in HBM (msim_journal_messages; journal_capacity > 0; no fetch needed,
+        and behind run_async no wait): per instance (JOURNAL_SUMMARY_DT summary, JOURNAL_MSG_DT records: one per :send in journal order,
+        the first max_msgs of them, each with the :recv that delivered it or NO_VALUE; see journal_analysis).  The whole zero-padded
+        (instances, max_msgs) slab is the list's `.slab`.  Not a check: check_results() is untouched."""
+        summ = np.zeros(max(self.n, 1), dtype=JOURNAL_SUMMARY_DT)
+        recs = np.zeros((max(self.n, 1), max(max_msgs, 1)), dtype=JOURNAL_MSG_DT)
+        self._chk(self.lib.msim_journal_messages(self._ctx, summ.ctypes.data, recs.ctypes.data if max_msgs else None, max_msgs, self.n), "msim_journal_messages")
+        out = _StepLists((summ[i], recs[i, :min(int(summ[i]["n_msgs"]), max_msgs)].copy()) for i in range(self.n))
+        out.slab = recs[:, :max_msgs]
+        return out
+
     def set_dev_flags(self, flags):
         """Developer switches of this context (msim_set_dev_flags): e.g. 0x200 one cluster per wavefront, 0x800 checkers on the host."""
         self._chk(self.lib.msim_set_dev_flags(self._ctx, int(flags)), "msim_set_dev_flags")
@@ -409,7 +422,9 @@ def decode_journal(events, n_nodes):
 
 def journal_stats(events, n_nodes):
     """maelstrom.net.checker's fold over the journal (net/checker.clj:28-41): send/recv/msg counts for all,
-    clients (a client endpoint involved, util.clj:12-16) and servers."""
+    clients (a client endpoint involved, util.clj:12-16) and servers.  Every endpoint >= n_nodes counts as a client here, the service
+    endpoints behind the client slots (lin-kv, lww-kv, lin-tso) too, which the reference counts as servers: journal_messages_history /
+    journal_analysis draw the classes by the client slots and do not."""
     msg, route = events["msg"], events["route"]
     recv = (msg & 0x80) != 0
     cl = ((route & 0xFF) >= n_nodes) | (((route >> 8) & 0xFF) >= n_nodes)
@@ -418,6 +433,59 @@ def journal_stats(events, n_nodes):
     for name, sel in (("all", np.ones(len(events), bool)), ("clients", cl), ("servers", ~cl)):
         res[name] = {"send-count": int((sel & ~recv).sum()), "recv-count": int((sel & recv).sum()),
                      "msg-count": int(len(np.unique(ids[sel])))}
+    return res
+
+
+def journal_messages_history(events, n_nodes, client_slots, max_msgs=None):
+    """One journal's messages on the host (msim_journal_messages_rows; needs no device; exact for every journal): every :send joined
+    to its :recv -> (JOURNAL_SUMMARY_DT summary, JOURNAL_MSG_DT records, one per :send in journal order: the first max_msgs; None: all).
+    include/maelsim_journal.h is the contract.  client_slots: max(concurrency, n_nodes) for an engine's journal."""
+    events = np.ascontiguousarray(events)
+    cap = len(events) if max_msgs is None else int(max_msgs)
+    summ = np.zeros(1, dtype=JOURNAL_SUMMARY_DT)
+    recs = np.zeros(max(cap, 1), dtype=JOURNAL_MSG_DT)
+    _call("msim_journal_messages_rows", events.ctypes.data, len(events), n_nodes, client_slots, summ.ctypes.data, recs.ctypes.data if cap else None, cap)
+    return summ[0], recs[:min(int(summ[0]["n_msgs"]), cap)]
+
+
+def journal_messages_batch(journals, n_nodes, client_slots, max_msgs, device=0, with_n_host=False):
+    """journal_messages_history over many journals in one device batch (msim_journal_messages_batch).  Returns (JOURNAL_SUMMARY_DT
+    summaries, a list of JOURNAL_MSG_DT arrays); the whole zero-padded (journals, max_msgs) slab is the list's `.slab`.  with_n_host:
+    also how many journals the host walk did instead — exactly those that are not well-formed."""
+    ev, off = _concatenated([np.ascontiguousarray(j) for j in journals], EVENT_DT)
+    n = len(journals)
+    summ = np.zeros(n, dtype=JOURNAL_SUMMARY_DT)
+    recs = np.zeros((n, max(max_msgs, 1)), dtype=JOURNAL_MSG_DT)
+    n_host = C.c_uint32()
+    _call("msim_journal_messages_batch", device, ev.ctypes.data if len(ev) else None, off.ctypes.data, n, n_nodes, client_slots, summ.ctypes.data,
+          recs.ctypes.data if max_msgs else None, max_msgs, C.addressof(n_host))
+    msgs = _StepLists(recs[i, :min(int(summ[i]["n_msgs"]), max_msgs)].copy() for i in range(n))
+    msgs.slab = recs[:, :max_msgs]
+    return (summ, msgs, n_host.value) if with_n_host else (summ, msgs)
+
+
+def journal_analysis(summary, msgs=None, service_names=None):
+    """The :net :stats map of net/checker.clj:28-41 from one journal's summary ({"all" / "clients" / "servers": {"send-count",
+    "recv-count", "msg-count"}}; pure formatting), plus "delivery": the undelivered messages and the latency quantiles per class, the
+    counts that make a journal malformed, the endpoints that occur in sort-clients order (util.clj:18-28: c0 c1 .. n0 n1 .. and the
+    services last, by name — `service_names` names the endpoints behind the client slots in order, else "service<k>").  With `msgs`,
+    "undelivered-ids" lists the ids of the records without a :recv."""
+    res = {name: {"send-count": int(summary["send_count"][k]), "recv-count": int(summary["recv_count"][k]), "msg-count": int(summary["msg_count"][k])}
+           for k, name in enumerate(("all", "clients", "servers"))}
+    n_nodes, slots = int(summary["n_nodes"]), int(summary["client_slots"])
+    eps = [e for e in range(256) if int(summary["endpoints"][e >> 5]) >> (e & 31) & 1]
+    svc = lambda e: service_names[e - n_nodes - slots] if service_names and e - n_nodes - slots < len(service_names) else f"service{e - n_nodes - slots}"
+    names = ([f"c{e - n_nodes}" for e in eps if n_nodes <= e < n_nodes + slots] + [f"n{e}" for e in eps if e < n_nodes]
+             + sorted(svc(e) for e in eps if e >= n_nodes + slots))
+    lat = {name: {"count": int(d["count"]), "sum-us": int(d["sum_us"]), "quantiles-us": {q: int(v) for q, v in zip(PERF_QUANTILES, d["q_us"])}}
+           for name, d in zip(("clients", "servers"), summary["latency"])}
+    res["delivery"] = {"undelivered": {name: int(summary["undelivered"][k]) for k, name in enumerate(("all", "clients", "servers"))},
+                       "latency": lat, "dup-sends": int(summary["dup_sends"]), "orphan-recvs": int(summary["orphan_recvs"]),
+                       "extra-recvs": int(summary["extra_recvs"]), "endpoints": names,
+                       "truncated": bool(int(summary["flags"]) & A.JOURNAL_TRUNCATED), "table-truncated": bool(int(summary["flags"]) & A.JOURNAL_TABLE_TRUNCATED)}
+    if msgs is not None:
+        res["delivery"]["undelivered-ids"] = [int(m["id"]) for m in msgs if int(m["recv_event"]) == A.NO_VALUE]
+    res["valid?"] = bool(int(summary["valid"]) == 1)
     return res
 
 
@@ -1314,6 +1382,17 @@ def journal_fressian(cfg, events, payload):
     buf = (C.c_ubyte * max(need.value, 1))()
     _call("msim_journal_fressian_rows", *args, buf, need.value, None)
     return bytes(buf[: need.value])
+
+
+def journal_svg(cfg, events):
+    """One journal as the reference's Lamport diagram (net/viz.clj:281-325), SVG text: a column per endpoint, a row per event, an arrow
+    per delivered message (msim_journal_svg_rows, csrc/journal_svg.cpp; the first 10000 events behind the init traffic)."""
+    events = np.ascontiguousarray(events)
+    need = C.c_size_t()
+    _call("msim_journal_svg_rows", C.byref(cfg), events.ctypes.data, len(events), None, 0, C.byref(need))
+    buf = C.create_string_buffer(need.value + 1)
+    _call("msim_journal_svg_rows", C.byref(cfg), events.ctypes.data, len(events), buf, need.value, None)
+    return buf.raw[:need.value].decode()
 
 
 def history_edn_native(cfg, rows, payload):
