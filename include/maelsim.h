@@ -552,7 +552,8 @@ int msim_check_rw_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *pay
  *   No cycle: the record is all zeros and no step is written.
  *   Truncation: steps beyond max_steps are not written (the slab there stays zero), `length` keeps the true value — the rule max_keys
  *     follows in msim_explain_lin_kv_batch.
- * Not reported: the key and the values behind a step (the device edges do not carry them), and witnesses for the non-cycle anomalies. */
+ * Not reported: the key and the values behind a step (the device edges do not carry them).  The non-cycle anomalies have their own
+ * witnesses: maelsim_txn_findings.h, included below. */
 enum { MSIM_EDGE_WW = 1u, MSIM_EDGE_WR = 2u, MSIM_EDGE_RW = 4u, MSIM_EDGE_RT = 8u };
 typedef struct msim_cycle_result {   /* 16 bytes, one per history */
   uint32_t anomalies;  /* the cycle bits of the history's record: one of MSIM_ANOMALY_G0 / G1C / G_SINGLE / G2, | MSIM_ANOMALY_REALTIME; 0 = no cycle */
@@ -812,6 +813,7 @@ void msim_destroy(msim_ctx *ctx);
 
 #include "maelsim_kafka_explain.h"   /* kafka: the explained verdicts (the contract: above msim_check_unique_batch) */
 #include "maelsim_small_explain.h"   /* pn-counter / g-counter, unique-ids, echo: the explained verdicts (the contract: that file's comments) */
+#include "maelsim_txn_findings.h"    /* txn-list-append / txn-rw-register: a witness for every non-cycle anomaly (the contract: that file's comments) */
 #include "maelsim_journal.h"         /* the net journal's messages: sends joined to their recvs, counts, delivery latencies (the contract: that file's comments) */
 
 #ifdef __cplusplus

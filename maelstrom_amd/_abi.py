@@ -184,6 +184,16 @@ class EchoExplain(C.Structure):
     _fields_ = [("n_errors", C.c_uint32), ("truncated", C.c_uint32)]
 
 
+class TxnFinding(C.Structure):
+    _fields_ = [("anomaly", C.c_uint32), ("key", C.c_uint32), ("inv_row", C.c_uint32), ("cmp_row", C.c_uint32), ("mop", C.c_uint32),
+                ("other_inv_row", C.c_uint32), ("other_cmp_row", C.c_uint32), ("other_mop", C.c_uint32),
+                ("element", C.c_uint32), ("other_element", C.c_uint32), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TxnExplain(C.Structure):
+    _fields_ = [("n_findings", C.c_uint32), ("truncated", C.c_uint32), ("count", C.c_uint32 * 12), ("reserved", C.c_uint32 * 2)]
+
+
 class JournalMsg(C.Structure):
     _fields_ = [("id", C.c_uint32), ("send_event", C.c_uint32), ("recv_event", C.c_uint32), ("send_time_us", C.c_uint32),
                 ("latency_us", C.c_uint32), ("kind", C.c_uint32), ("route", C.c_uint32), ("a", C.c_uint32)]
@@ -324,6 +334,16 @@ JOURNAL_PROTOTYPES = {
     "msim_journal_svg_rows": (_i, (_P(Config), _vp, _u32, _s, _sz, _P(_sz))),
 }
 
+# ... and for include/maelsim_txn_findings.h: a witness for every non-cycle anomaly of the transactional checkers
+# (tests/test_txn_findings.py holds these to their header).
+TXN_FINDINGS_CAPACITY = 1024   # MSIM_TXN_FINDINGS_CAPACITY: a history of more findings is explained by the host walk
+TXN_FINDINGS_RECORDS = {"msim_txn_finding": TxnFinding, "msim_txn_explain": TxnExplain}
+TXN_FINDINGS_PROTOTYPES = {
+    "msim_explain_txn_findings_rows": (_i, (_u32, _vp, _u32, _vp, _u32, _u32, _res, _vp, _vp, _u32)),
+    "msim_explain_txn_findings_batch": (_i, (_i, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32)),
+    "msim_explain_txn_findings": (_i, (_vp, _vp, _vp, _u32, _u32)),
+}
+
 _lib = None
 
 
@@ -336,7 +356,8 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -m maelstrom_amd.build` (hipcc, gfx950). "
                            "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES, **SMALL_EXPLAIN_PROTOTYPES, **JOURNAL_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **KAFKA_EXPLAIN_PROTOTYPES, **SMALL_EXPLAIN_PROTOTYPES, **JOURNAL_PROTOTYPES,
+                                      **TXN_FINDINGS_PROTOTYPES}.items():
         fn = getattr(lib, name, None)   # MSIM_LIB may name an older build (the A/B tools under tools/ time the parent's): an entry it lacks is skipped, and calling it still raises
         if fn is not None:
             fn.restype, fn.argtypes = restype, list(argtypes)

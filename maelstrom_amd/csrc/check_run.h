@@ -158,6 +158,8 @@ void msim_rw_check_instance_host(const msim_op *rows, uint32_t n_rows, const uin
                                  msim_check_result *res);
 void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
                                     msim_cycle_result *cycle, msim_cycle_step *steps, uint32_t max_steps, bool rw);
+void msim_txn_findings_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                     msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings, bool rw);
 void msim_kafka_check_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out);
 void msim_kafka_explain_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, msim_check_result *out,
                                       msim_kafka_explain *hdr, msim_kafka_finding *findings, uint32_t max_findings);
@@ -243,10 +245,17 @@ typedef ExplainSlabs<msim_cycle_result, msim_cycle_step> CycleSlabs;
 template <class P> static inline void bind_cycles(P &p, const CycleSlabs &w) { p.cycles = w.hdr(); p.steps = w.rec(); p.max_steps = w.max_k; }
 
 // how rw_dev_run / txn_dev_run go beyond the clean passes: `full` the classification on the device; with `witness` its EXPLAIN kernel
+// the non-cycle findings of an explaining rw / txn check (include/maelsim_txn_findings.h): a header, max_findings records per history
+typedef ExplainSlabs<msim_txn_explain, msim_txn_finding> FindingSlabs;
 struct CycleMode {
   bool full = false;
   CycleSlabs *witness = nullptr;
+  FindingSlabs *findings = nullptr;   // (instead of the witness: the *_findings_kernel flavour)
 };
+// rw_check_dev.hip's share of msim_explain_txn_findings_batch / msim_explain_txn_findings (txn_check_dev.hip holds the entries)
+int msim_rw_findings_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets, uint32_t n_histories,
+                           uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings);
+int msim_rw_findings_device(msim_ctx *ctx, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings);
 
 // One chunked pass over `m` histories — all of the launch, or those `list` names (m of them: the list goes to the device in front of the
 // workspace, rounded to 256 bytes) —, each with `bytes_per_history` of the grow-only workspace, as many per launch as `budget` holds:

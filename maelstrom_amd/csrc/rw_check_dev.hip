@@ -56,6 +56,7 @@ struct RParams {
   u32 ccap;                      // rw_classify_kernel: transactions of one strongly connected component the reachability matrix holds (<= CCAP)
   u32 big;                       // rw_classify_kernel: a larger component is searched in the workspace (0: it is the host's, MSIM_DEV_FLAGS bit 13)
   msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // rw_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
+  msim_txn_explain *fhdr; msim_txn_finding *frecs; u32 max_findings;  // rw_findings_kernel: the non-cycle findings (history i's records at frecs + i * max_findings)
 };
 
 // one micro-op = one payload word: f (1 = write), key, value (0xFF: a read of nil)
@@ -64,13 +65,16 @@ struct RParams {
 #define M_VAL(w_) (((w_) >> 16) & 0xFFu)
 
 #include "cycle_classify.inc"
+#include "txn_findings.inc"
 
 
 // FULL = false: the pass that proves a history free of what the model proscribes (rw_check_kernel).  FULL = true: the classification
 // (rw_classify_kernel): every edge kind whatever the model is, the non-cycle anomalies accumulated, the cycles classified — the record
 // of check_rw + finish + classify + judge (txn_check.cpp), field for field.  EXPLAIN (rw_explain_kernel, with FULL): and the witness cycle
-// of the record's cycle class (cycle_classify.inc).
-template <bool FULL, bool EXPLAIN = false>
+// of the record's cycle class (cycle_classify.inc).  FINDINGS (rw_findings_kernel, with FULL): and a witness for every non-cycle anomaly
+// (include/maelsim_txn_findings.h), emitted where the bits are set into the history's region behind `reach` (txn_findings.inc), sorted
+// and written out before the cycles are classified; a history of more than MSIM_TXN_FINDINGS_CAPACITY findings is the host's.
+template <bool FULL, bool EXPLAIN = false, bool FINDINGS = false>
 __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   const u32 lane = threadIdx.x;
   const u64 lt = (1ull << lane) - 1ull;
@@ -92,10 +96,13 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   // FULL only: the edges reversed (radj / roff / rcur), a transaction's state in the searches, the pivot search's pointers
   u32 *const radj = adj + p.emax, *const roff = radj + p.emax, *const rcur = roff + NM + 1, *const st = rcur + NM, *const jump = st + NM;
   // and a 64-bit word per transaction for the search of a component beyond the matrix [NM], on an 8-byte boundary
+  [[maybe_unused]] u64 *const reach_ = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(jump + NM) + 7u) & ~(uintptr_t)7u);
+  [[maybe_unused]] const FRegion F(reinterpret_cast<u32 *>(reach_ + NM));   // FINDINGS only
 
   BLANK_RESULT(res, NEEDS_HOST);
 #define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
   if (n_words >= (1u << 24)) TO_HOST();
+  if constexpr (FINDINGS) { if (lane == 0) *F.cnt = 0; __syncthreads(); }
 
   // ---- A: transactions ---------------------------------------------------------------------------------------------------------
   u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0, anomalies = 0;
@@ -109,6 +116,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
       const bool txn_row = idx < n_rows && proc != MSIM_PROCESS_NEMESIS && f == MSIM_F_TXN;
       const bool outside = txn_row && (u64)woff + len > n_words;   // a payload outside its area: collect() skips the row and says internal
       if (__ballot(outside)) { if constexpr (FULL) anomalies |= MSIM_ANOMALY_INTERNAL; else { bad = true; break; } }
+      if constexpr (FINDINGS) if (outside) f_emit(F, F_INTERNAL, NONE, NONE, NONE, idx, NONE, NONE, NONE, NONE, NONE, NONE, 0);
       const bool is = txn_row && !outside;
       const bool inv = is && type == MSIM_T_INVOKE;
       const u64 im = __ballot(inv);
@@ -161,6 +169,11 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
     for (u32 i = 0; i < wn; i++) { const u32 x = w[i]; if (M_F(x) && M_KEY(x) == k_) v = M_VAL(x); }
     return v;
   };
+  [[maybe_unused]] auto final_mop = [&](u32 t_, u32 k_) -> u32 {   // FINDINGS: the micro-op of that write
+    const u32 *w = pay + t_off[t_]; const u32 wn = t_lt[t_] & 0xFFFFu; u32 at = NONE;
+    for (u32 i = 0; i < wn; i++) { const u32 x = w[i]; if (M_F(x) && M_KEY(x) == k_) at = i; }
+    return at;
+  };
 
   // ---- D/E: edges: pass 0 counts degrees (and finds the non-cycle anomalies), pass 1 fills the CSR ----------------------------------------
   u32 n_edges = 0;
@@ -188,16 +201,22 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
           const u32 px = w[prev]; const bool pnil = M_VAL(px) == 0xFFu;
           const bool same = M_F(px) ? (!nil && val == M_VAL(px)) : (nil == pnil && (nil || val == M_VAL(px)));
           if (!same) anomalies |= MSIM_ANOMALY_INTERNAL;
+          if constexpr (FINDINGS) if (!same && pass == 0)
+            f_emit(F, F_INTERNAL, key, t, t_inv[t], t_cmp[t], k, t_inv[t], t_cmp[t], (u32)prev, nil ? NONE : val, (!M_F(px) && pnil) ? NONE : M_VAL(px), 0);
           continue;
         }
         // an external read
         if (!nil) {
           if (pass == 0) SETBIT(vseen, key, val);
           const u32 wr = writer[key * stride + val];
-          if (wr == NONE || TYPE(wr) == MSIM_T_FAIL) { anomalies |= MSIM_ANOMALY_G1A; }   // garbage / aborted read
-          else {
+          if (wr == NONE || TYPE(wr) == MSIM_T_FAIL) {   // garbage / aborted read
+            anomalies |= MSIM_ANOMALY_G1A;
+            if constexpr (FINDINGS) if (pass == 0) f_emit(F, F_G1A, key, t, t_inv[t], t_cmp[t], k, wr == NONE ? NONE : t_inv[wr], wr == NONE ? NONE : t_cmp[wr], NONE, val, NONE, 0);
+          } else {
             if (wr != t) {
               if (final_of(wr, key) != val) anomalies |= MSIM_ANOMALY_G1B;
+              if constexpr (FINDINGS) if (pass == 0 && final_of(wr, key) != val)
+                f_emit(F, F_G1B, key, t, t_inv[t], t_cmp[t], k, t_inv[wr], t_cmp[wr], final_mop(wr, key), val, final_of(wr, key), 0);
               if (want_wr) ADD(wr, t, E_WR);
             }
             const u32 fw = final_of(t, key);   // writes follow reads
@@ -227,6 +246,20 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
           const u64 roots = alive & ~has_in;
           if (!roots) {
             anomalies |= MSIM_ANOMALY_CYCLIC_VERSIONS;
+            if constexpr (FINDINGS) {   // `alive` holds the cycles and what follows them: a version is on a cycle iff it reaches itself
+              u32 lowest = NONE, on_cycle = 0;
+              for (u64 b = alive; b; b &= b - 1) {
+                const u32 v = (u32)__builtin_ctzll(b);
+                u64 r = ((u64)vsucc[2 * (key * stride + v) + 1] << 32) | vsucc[2 * (key * stride + v)];
+                for (bool grown = true; grown;) {
+                  u64 more = 0;
+                  for (u64 c = r; c; c &= c - 1) { const u32 u = (u32)__builtin_ctzll(c); if (u < stride) more |= ((u64)vsucc[2 * (key * stride + u) + 1] << 32) | vsucc[2 * (key * stride + u)]; }
+                  grown = (more & ~r) != 0; r |= more;
+                }
+                if ((r >> v) & 1ull) { on_cycle++; lowest = min(lowest, v); }
+              }
+              f_emit(F, F_VERSIONS, key, NONE, NONE, NONE, NONE, NONE, NONE, NONE, lowest, NONE, on_cycle);
+            }
             if constexpr (FULL) for (u32 v = 0; v < stride; v++) { vsucc[2 * (key * stride + v)] = 0; vsucc[2 * (key * stride + v) + 1] = 0; }   // the key contributes no ww and no rw edges
             break;
           }
@@ -304,6 +337,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
   }
   anomalies = wv_or(anomalies);
 
+  if constexpr (FINDINGS) { if (!f_finish(F, FOut{p.fhdr, p.frecs, p.max_findings}, hist)) TO_HOST(); }   // (more than the region holds: the host walk's)
   if constexpr (FULL) {
     u64 *const reach = reinterpret_cast<u64 *>((reinterpret_cast<uintptr_t>(jump + NM) + 7u) & ~(uintptr_t)7u);
     const CycleParams cp = {p.out, p.cm, p.proscribed, p.ccap, p.big};
@@ -331,6 +365,7 @@ __device__ __forceinline__ void rw_body(const RParams &p, const u32 hist) {
 __global__ void __launch_bounds__(64) rw_check_kernel(const RParams p) { rw_body<false>(p, p.first + blockIdx.x); }
 __global__ void __launch_bounds__(64) rw_classify_kernel(const RParams p) { rw_body<true>(p, p.list[p.first + blockIdx.x]); }
 __global__ void __launch_bounds__(64) rw_explain_kernel(const RParams p) { rw_body<true, true>(p, p.list[p.first + blockIdx.x]); }
+__global__ void __launch_bounds__(64) rw_findings_kernel(const RParams p) { rw_body<true, false, true>(p, p.list[p.first + blockIdx.x]); }
 
 uint64_t rw_ws_words(u32 nmax, u32 emax, u32 kmax, u32 wmax) { return (uint64_t)nmax * 11 + 4 + 2 * (uint64_t)kmax + 3 * (uint64_t)wmax + emax; }
 
@@ -343,6 +378,9 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
   // mode.witness (msim_explain_rw_batch, msim_explain_txn; with full): the witness cycles, found by rw_explain_kernel in rp.cycles / rp.steps
   CycleSlabs *const wit = mode.full ? mode.witness : nullptr;
   if (wit) { bind_cycles(rp, *wit); if (int rc = wit->clear(ctx, st)) return rc; }
+  // mode.findings (msim_explain_txn_findings*; with full, without witness): the non-cycle findings, written by rw_findings_kernel
+  FindingSlabs *const fnd = mode.full && !wit ? mode.findings : nullptr;
+  if (fnd) { rp.fhdr = fnd->hdr(); rp.frecs = fnd->rec(); rp.max_findings = fnd->max_k; if (int rc = fnd->clear(ctx, st)) return rc; }
   const PassTimer tm(ctx);
   if (rp.kmax == 0 || rp.kmax > KMAX) rp.kmax = KMAX;
   if (rp.wmax == 0 || rp.wmax > WMAX) rp.wmax = WMAX;
@@ -365,19 +403,21 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
   } else todo = needs(h_out, n, [](u32) { return true; });
   if (!todo.empty()) {   // the classification, over the list of histories that need it
     const u32 m = (u32)todo.size();
-    rp.ws_words = rw_ws_words_full(rp.nmax, rp.emax, rp.kmax, rp.wmax);
+    rp.ws_words = rw_ws_words_full(rp.nmax, rp.emax, rp.kmax, rp.wmax) + (fnd ? FWORDS : 0u);   // (the region of findings behind `reach`)
     // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
     // histories reach the search
     rp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     rp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    if ((rc = wit ? pass(m, &todo, rw_explain_kernel) : pass(m, &todo, rw_classify_kernel)) < 0) return rc;
+    if ((rc = pass(m, &todo, fnd ? rw_findings_kernel : wit ? rw_explain_kernel : rw_classify_kernel)) < 0) return rc;
     todo = needs(h_out, n, for_host);
     if (tm.trace) std::fprintf(stderr, "[rw-check] cycle classes of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, (u32)rc, tm.ms(), todo.size());
   }
   if (wit && (rc = wit->fetch(ctx, st)) != MSIM_OK) return rc;
+  if (fnd && (rc = fnd->fetch(ctx, st)) != MSIM_OK) return rc;
   if (!todo.empty()) {
     rc = hand_off(ctx, source_of(rp, hmeta), n, todo, h_out, rp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
-      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], wit->hdr(i), wit->rec(i), rp.max_steps, true);
+      if (fnd) msim_txn_findings_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], fnd->hdr(i), fnd->rec(i), fnd->max_k, true);
+      else if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i], wit->hdr(i), wit->rec(i), rp.max_steps, true);
       else msim_rw_check_instance_host(rows, nr, pay, nw, flags, rp.cm, &h_out[i]);
     });
     if (rc != MSIM_OK) return rc;
@@ -391,7 +431,8 @@ int rw_dev_run(msim_ctx *ctx, RParams rp, u32 n, const std::vector<msim_inst_met
 
 // msim_check for txn-rw-register: the histories of the last run, where they lie in HBM.
 // (cycles / steps / max_steps: msim_explain_txn's witness cycles with every history's full record, whatever msim_set_check_classify says)
-int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+static int rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, msim_txn_explain *fhdr, msim_txn_finding *frecs,
+                     uint32_t max_findings) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
   std::chrono::steady_clock::time_point t0;
@@ -409,31 +450,46 @@ int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_st
   rp.wmax = (u32)std::min<uint64_t>(WMAX, (uint64_t)rp.kmax * (ctx->cfg.max_writes_per_key + 2u));
   CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
+  FindingSlabs fnd;
+  if (fhdr) if (int rc = fnd.alloc(ctx, n, max_findings, fhdr, frecs)) return rc;
   u32 redone = 0;
   int rc = rw_dev_run(ctx, rp, n, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
-                      CycleMode{ctx->check_classify || cycles, cycles ? &wit : nullptr});
+                      CycleMode{ctx->check_classify || cycles || fhdr, cycles ? &wit : nullptr, fhdr ? &fnd : nullptr});
   if (rc != MSIM_OK) return rc;
   finish_check(ctx, t0, redone);
   return MSIM_OK;
+}
+int msim_check_rw_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+  return rw_device(ctx, cycles, steps, max_steps, nullptr, nullptr, 0);
+}
+int msim_rw_findings_device(msim_ctx *ctx, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings) {
+  return rw_device(ctx, nullptr, nullptr, 0, hdr, findings, max_findings);
 }
 
 // Checks `n_histories` rw-register histories given on the host (rows / payload words of history i at row_offsets[i] /
 // payload_offsets[i]) as msim_check does for the histories of a run.
 static int rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                     uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool full,
-                    msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
+                    msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0,
+                    msim_txn_explain *fhdr = nullptr, msim_txn_finding *frecs = nullptr, uint32_t max_findings = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
   if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
   DevBuf ws; size_t ws_cap = 0;
   CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
+  FindingSlabs fnd;
+  if (fhdr) if (int rc = fnd.alloc(ctx, n_histories, max_findings, fhdr, frecs)) return rc;
   RParams rp;
   std::memset(&rp, 0, sizeof rp);
   f.bind(rp);
   rp.nmax = f.b.longest / 2 + 65; rp.emax = rp.nmax * 64; rp.cm = consistency_model;   // (a caller's histories may be dense: a few keys, reads of nil precede every version)
   rp.proscribed = msim_proscribed_anomalies(consistency_model);
-  return rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{full, cycles ? &wit : nullptr});
+  return rw_dev_run(ctx, rp, n_histories, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{full, cycles ? &wit : nullptr, fhdr ? &fnd : nullptr});
+}
+int msim_rw_findings_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets, uint32_t n_histories,
+                           uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings) {
+  return rw_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true, nullptr, nullptr, 0, hdr, findings, max_findings);
 }
 
 extern "C" int msim_check_rw_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,

@@ -46,6 +46,39 @@ struct Scratch {
   std::vector<int> idx, low, comp; std::vector<char> on, seen; std::vector<uint32_t> st, work, pos, q;
 };
 
+// The non-cycle findings of include/maelsim_txn_findings.h, gathered where check_history / check_rw set the bits (null: nobody asked).
+struct Findings {
+  std::vector<msim_txn_finding> v;
+  struct Dup { uint32_t t0, m0, t1, m1, n; };
+  std::vector<Dup> dup;   // (key, element) -> its first two appenders and how many there are
+};
+const uint32_t NV = MSIM_NO_VALUE;
+msim_txn_finding finding(uint32_t anomaly, uint32_t key) {
+  msim_txn_finding f;
+  f.anomaly = anomaly; f.key = key; f.inv_row = f.cmp_row = f.mop = f.other_inv_row = f.other_cmp_row = f.other_mop = f.element = f.other_element = NV;
+  f.count = 0; f.reserved = 0;
+  return f;
+}
+void subject(msim_txn_finding &f, const Txn &t, uint32_t mop) { f.inv_row = (uint32_t)t.inv; f.cmp_row = t.cmp < 0 ? NV : (uint32_t)t.cmp; f.mop = mop; }
+void other(msim_txn_finding &f, const Txn &t, uint32_t mop) { f.other_inv_row = (uint32_t)t.inv; f.other_cmp_row = t.cmp < 0 ? NV : (uint32_t)t.cmp; f.other_mop = mop; }
+// the header and the first max_findings records, in the contract's order (ties — rows outside the payload area — keep their row order)
+void write_findings(Findings &F, msim_txn_explain *hdr, msim_txn_finding *out, uint32_t max_findings) {
+  std::memset(hdr, 0, sizeof *hdr);
+  if (max_findings) std::memset(out, 0, (size_t)max_findings * sizeof *out);
+  auto bit = [](const msim_txn_finding &f) { return (uint32_t)__builtin_ctz(f.anomaly); };
+  std::stable_sort(F.v.begin(), F.v.end(), [&](const msim_txn_finding &a, const msim_txn_finding &b) {
+    if (bit(a) != bit(b)) return bit(a) < bit(b);
+    if (a.key != b.key) return a.key < b.key;
+    if (a.inv_row != b.inv_row) return a.inv_row < b.inv_row;
+    if (a.mop != b.mop) return a.mop < b.mop;
+    return a.count < b.count;
+  });
+  for (const msim_txn_finding &f : F.v) hdr->count[bit(f)]++;
+  hdr->n_findings = (uint32_t)std::min<size_t>(F.v.size(), max_findings);
+  hdr->truncated = F.v.size() > max_findings ? 1u : 0u;
+  for (uint32_t i = 0; i < hdr->n_findings; i++) out[i] = F.v[i];
+}
+
 void parse_txn(Scratch &S, const uint32_t *w, uint32_t n, bool rw) {
   for (uint32_t i = 0; i < n;) {
     const uint32_t h = w[i++];
@@ -132,8 +165,10 @@ uint32_t classify(Scratch &S, uint32_t n, bool rt, uint32_t *in_cycles) {
 
 // pairs invocations with completions: S.txns / S.mops (the completed form of :ok transactions) and the transitively
 // reduced realtime order; returns anomaly bits (a row whose payload lies outside the area)
-uint32_t collect(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, bool rw, msim_check_result *out) {
+uint32_t collect(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, bool rw, msim_check_result *out,
+                 Findings *F = nullptr) {
   std::memset(out, 0, sizeof *out);
+  if (F) { F->v.clear(); F->dup.clear(); }
   S.txns.clear(); S.mops.clear(); S.bytes.clear(); S.rt.clear(); S.frontier.clear(); S.open.clear(); S.edges.clear();
   uint32_t anomalies = 0;
 
@@ -142,7 +177,11 @@ uint32_t collect(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_
     const uint32_t proc = MSIM_OP_PROCESS(r), type = MSIM_OP_TYPE(r);
     if (proc == MSIM_PROCESS_NEMESIS || MSIM_OP_F(r) != MSIM_F_TXN) continue;
     const uint32_t off = r.value, len = MSIM_OP_LEN(r);
-    if ((uint64_t)off + len > n_words) { anomalies |= MSIM_ANOMALY_INTERNAL; continue; }
+    if ((uint64_t)off + len > n_words) {
+      anomalies |= MSIM_ANOMALY_INTERNAL;
+      if (F) { msim_txn_finding f = finding(MSIM_ANOMALY_INTERNAL, NV); f.cmp_row = i; F->v.push_back(f); }
+      continue;
+    }
     if (proc >= S.open.size()) S.open.resize(proc + 64, -1);
     if (type == MSIM_T_INVOKE) {
       out->op_count++;
@@ -278,8 +317,8 @@ void finish(Scratch &S, uint32_t anomalies, uint32_t flags, uint32_t cm, msim_ch
 
 // ---- list-append -------------------------------------------------------------------------------------------------------
 void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out,
-                   const Witness *W = nullptr) {
-  uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, false, out), max_key = 0;
+                   const Witness *W = nullptr, Findings *F = nullptr) {
+  uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, false, out, F), max_key = 0;
   const uint32_t n = (uint32_t)S.txns.size();
   uint32_t max_val = 0;
   for (const Txn &t : S.txns) for (uint32_t k = 0; k < t.n_mops; k++) { const Mop &m = S.mops[t.mop0 + k]; max_key = std::max<uint32_t>(max_key, m.key); if (m.f) max_val = std::max<uint32_t>(max_val, m.val); }
@@ -289,18 +328,32 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
   const uint32_t stride = max_val + 1;
   auto kv = [stride](uint32_t k, uint32_t v) { return k * stride + v; };
   S.writer.assign((size_t)(max_key + 1) * stride, -1);
+  if (F) F->dup.assign((size_t)(max_key + 1) * stride, Findings::Dup{0, 0, 0, 0, 0});
   for (uint32_t t = 0; t < n; t++)
     for (uint32_t k = 0; k < S.txns[t].n_mops; k++) {
       const Mop &m = S.mops[S.txns[t].mop0 + k];
       if (!m.f) continue;
       if (S.writer[kv(m.key, m.val)] >= 0) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;  // the generator never repeats (k, v)
       S.writer[kv(m.key, m.val)] = (int)t;
+      if (F) { Findings::Dup &d = F->dup[kv(m.key, m.val)]; if (d.n == 0) { d.t0 = t; d.m0 = k; } else if (d.n == 1) { d.t1 = t; d.m1 = k; } d.n++; }
     }
+  if (F) for (uint32_t key = 0; key <= max_key; key++) for (uint32_t v = 0; v < stride; v++) {
+    const Findings::Dup &d = F->dup[kv(key, v)];
+    if (d.n < 2) continue;
+    msim_txn_finding f = finding(MSIM_ANOMALY_DUPLICATE_ELEMENTS, key);
+    subject(f, S.txns[d.t0], d.m0); other(f, S.txns[d.t1], d.m1); f.element = v; f.count = d.n;
+    F->v.push_back(f);
+  }
   // last element transaction t appended to key (for G1b)
   auto final_of = [&](uint32_t t, uint32_t key) -> int {
     const Txn &x = S.txns[t]; int v = -1;
     for (uint32_t k = 0; k < x.n_mops; k++) { const Mop &m = S.mops[x.mop0 + k]; if (m.f && m.key == key) v = m.val; }
     return v;
+  };
+  auto final_mop = [&](uint32_t t, uint32_t key) -> uint32_t {
+    const Txn &x = S.txns[t]; uint32_t at = NV;
+    for (uint32_t k = 0; k < x.n_mops; k++) { const Mop &m = S.mops[x.mop0 + k]; if (m.f && m.key == key) at = k; }
+    return at;
   };
   auto is_own = [&](uint32_t t, uint32_t key, uint8_t el) { const int w = S.writer[kv(key, el)]; return w >= 0 && (uint32_t)w == t; };
 
@@ -315,6 +368,14 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
       const uint8_t *l = S.bytes.data() + m.off; const uint32_t len = m.len;
       // duplicates (lists are <= 63 long)
       for (uint32_t a = 0; a < len; a++) for (uint32_t b2 = a + 1; b2 < len; b2++) if (l[a] == l[b2]) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;
+      if (F) {   // the lowest position that repeats an earlier one, and the lowest it repeats
+        bool found = false;
+        for (uint32_t b2 = 1; b2 < len && !found; b2++) for (uint32_t a = 0; a < b2 && !found; a++) if (l[a] == l[b2]) {
+          msim_txn_finding f = finding(MSIM_ANOMALY_DUPLICATE_ELEMENTS, m.key);
+          subject(f, x, k); f.element = l[b2]; f.other_element = b2; f.count = a;
+          F->v.push_back(f); found = true;
+        }
+      }
       // internal consistency: what the transaction's own earlier micro-ops imply for this read
       {
         int prev = -1;  // the latest earlier read of this key
@@ -331,18 +392,38 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
         } else { ok = len >= n_app; at = len - n_app; }  // must end with the own appends
         if (ok) for (uint32_t e = e0, a = 0; e < k; e++) { const Mop &p = S.mops[x.mop0 + e]; if (p.f && p.key == m.key) { if (l[at + a] != p.val) ok = false; a++; } }
         if (!ok) anomalies |= MSIM_ANOMALY_INTERNAL;
+        if (!ok && F) {
+          msim_txn_finding f = finding(MSIM_ANOMALY_INTERNAL, m.key);
+          subject(f, x, k); f.element = len; f.count = n_app;
+          if (prev >= 0) { other(f, x, (uint32_t)prev); f.other_element = S.mops[x.mop0 + (uint32_t)prev].len; }
+          F->v.push_back(f);
+        }
       }
       // the externally visible part of the read: without the transaction's own appends at the tail
       uint32_t ext = len;
       while (ext > 0 && is_own(t, m.key, l[ext - 1])) ext--;
       for (uint32_t e = 0; e < ext; e++) {
         const int w = S.writer[kv(m.key, l[e])];
+        if (F && (w < 0 || S.txns[(size_t)w].type == MSIM_T_FAIL)) {
+          msim_txn_finding f = finding(MSIM_ANOMALY_G1A, m.key);
+          subject(f, x, k); f.element = l[e]; f.count = e;
+          if (w >= 0) other(f, S.txns[(size_t)w], NV);
+          F->v.push_back(f);
+        }
         if (w < 0) { anomalies |= MSIM_ANOMALY_G1A; continue; }                         // an element nobody appended (garbage read)
         if (S.txns[(size_t)w].type == MSIM_T_FAIL) anomalies |= MSIM_ANOMALY_G1A;       // aborted read
       }
       if (ext > 0) {
         const int w = S.writer[kv(m.key, l[ext - 1])];
-        if (w >= 0 && (uint32_t)w != t && final_of((uint32_t)w, m.key) != (int)l[ext - 1]) anomalies |= MSIM_ANOMALY_G1B;
+        if (w >= 0 && (uint32_t)w != t && final_of((uint32_t)w, m.key) != (int)l[ext - 1]) {
+          anomalies |= MSIM_ANOMALY_G1B;
+          if (F) {
+            msim_txn_finding f = finding(MSIM_ANOMALY_G1B, m.key);
+            subject(f, x, k); other(f, S.txns[(size_t)w], final_mop((uint32_t)w, m.key));
+            f.element = l[ext - 1]; f.other_element = (uint32_t)final_of((uint32_t)w, m.key); f.count = ext - 1;
+            F->v.push_back(f);
+          }
+        }
       }
       const int lg = S.longest[m.key];
       if (lg < 0 || S.mops[(size_t)lg].len < len) S.longest[m.key] = (int)(x.mop0 + k);
@@ -360,6 +441,12 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
       if (a < 0 || b2 < 0) continue;
       const bool fa = S.txns[(size_t)a].type == MSIM_T_FAIL, fb = S.txns[(size_t)b2].type == MSIM_T_FAIL;
       if (fa && !fb) anomalies |= MSIM_ANOMALY_DIRTY_UPDATE;
+      if (fa && !fb && F) {
+        msim_txn_finding f = finding(MSIM_ANOMALY_DIRTY_UPDATE, key);
+        subject(f, S.txns[(size_t)b2], NV); other(f, S.txns[(size_t)a], NV);
+        f.element = ord[i + 1]; f.other_element = ord[i]; f.count = i;
+        F->v.push_back(f);
+      }
       if (!fa && !fb) add((uint32_t)a, (uint32_t)b2, E_WW);
     }
   }
@@ -371,7 +458,20 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
       if (m.f || S.longest[m.key] < 0) continue;
       const Mop &lm = S.mops[(size_t)S.longest[m.key]];
       const uint8_t *ord = S.bytes.data() + lm.off, *l = S.bytes.data() + m.off;
-      if (m.len > lm.len || !std::equal(l, l + m.len, ord)) { anomalies |= MSIM_ANOMALY_INCOMPATIBLE_ORDER; continue; }
+      if (m.len > lm.len || !std::equal(l, l + m.len, ord)) {
+        anomalies |= MSIM_ANOMALY_INCOMPATIBLE_ORDER;
+        if (F) {
+          uint32_t lt = 0, lk = 0;   // longest(k)'s transaction and micro-op
+          for (uint32_t u = 0; u < n; u++) if (S.txns[u].type == MSIM_T_OK && (uint32_t)S.longest[m.key] >= S.txns[u].mop0 && (uint32_t)S.longest[m.key] < S.txns[u].mop0 + S.txns[u].n_mops) { lt = u; lk = (uint32_t)S.longest[m.key] - S.txns[u].mop0; }
+          uint32_t d = 0;
+          while (d < m.len && d < lm.len && l[d] == ord[d]) d++;
+          msim_txn_finding f = finding(MSIM_ANOMALY_INCOMPATIBLE_ORDER, m.key);
+          subject(f, x, k); other(f, S.txns[lt], lk);
+          f.count = d; f.element = l[d]; f.other_element = d < lm.len ? ord[d] : NV;
+          F->v.push_back(f);
+        }
+        continue;
+      }
       uint32_t ext = m.len;
       while (ext > 0 && is_own(t, m.key, l[ext - 1])) ext--;
       if (ext > 0) { const int w = S.writer[kv(m.key, l[ext - 1])]; if (w >= 0 && S.txns[(size_t)w].type != MSIM_T_FAIL) add((uint32_t)w, t, E_WR); }
@@ -394,8 +494,8 @@ void check_history(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint3
 // Returns false (out->valid = 2, unknown) when a register value is >= 64: the version graphs below hold 64 versions per key
 // (the engine's generator stops at max-writes-per-key <= 63; externally produced histories may not).
 bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *out,
-              const Witness *W = nullptr) {
-  uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, true, out), max_key = 0;
+              const Witness *W = nullptr, Findings *F = nullptr) {
+  uint32_t anomalies = collect(S, rows, n_rows, payload, n_words, true, out, F), max_key = 0;
   const uint32_t n = (uint32_t)S.txns.size();
   uint32_t max_val = 0;
   for (const Txn &t : S.txns) for (uint32_t k = 0; k < t.n_mops; k++) { const Mop &m = S.mops[t.mop0 + k]; max_key = std::max<uint32_t>(max_key, m.key); max_val = std::max<uint32_t>(max_val, m.val); }
@@ -403,17 +503,31 @@ bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *
   constexpr uint32_t stride = 64u;  // the version graphs below walk versions 0..63 of every key
   auto kv = [](uint32_t k, uint32_t v) { return k * stride + v; };
   S.writer.assign((size_t)(max_key + 1) * stride, -1);
+  if (F) F->dup.assign((size_t)(max_key + 1) * stride, Findings::Dup{0, 0, 0, 0, 0});
   for (uint32_t t = 0; t < n; t++)
     for (uint32_t k = 0; k < S.txns[t].n_mops; k++) {
       const Mop &m = S.mops[S.txns[t].mop0 + k];
       if (!m.f) continue;
       if (S.writer[kv(m.key, m.val)] >= 0) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;  // the generator never repeats (k, v)
       S.writer[kv(m.key, m.val)] = (int)t;
+      if (F) { Findings::Dup &d = F->dup[kv(m.key, m.val)]; if (d.n == 0) { d.t0 = t; d.m0 = k; } else if (d.n == 1) { d.t1 = t; d.m1 = k; } d.n++; }
     }
+  if (F) for (uint32_t key = 0; key <= max_key; key++) for (uint32_t v = 0; v < stride; v++) {
+    const Findings::Dup &d = F->dup[kv(key, v)];
+    if (d.n < 2) continue;
+    msim_txn_finding f = finding(MSIM_ANOMALY_DUPLICATE_ELEMENTS, key);
+    subject(f, S.txns[d.t0], d.m0); other(f, S.txns[d.t1], d.m1); f.element = v; f.count = d.n;
+    F->v.push_back(f);
+  }
   auto final_of = [&](uint32_t t, uint32_t key) -> int {
     const Txn &x = S.txns[t]; int v = -1;
     for (uint32_t k = 0; k < x.n_mops; k++) { const Mop &m = S.mops[x.mop0 + k]; if (m.f && m.key == key) v = m.val; }
     return v;
+  };
+  auto final_mop = [&](uint32_t t, uint32_t key) -> uint32_t {
+    const Txn &x = S.txns[t]; uint32_t at = NV;
+    for (uint32_t k = 0; k < x.n_mops; k++) { const Mop &m = S.mops[x.mop0 + k]; if (m.f && m.key == key) at = k; }
+    return at;
   };
   // external read of `key` by :ok transaction t: -1 none, 0 nil, else the value (values are >= 1)
   auto ext_read = [&](uint32_t t, uint32_t key) -> int {
@@ -440,14 +554,30 @@ bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *
         const Mop &p = S.mops[x.mop0 + (uint32_t)prev];
         const bool same = p.f ? (!m.nil && m.val == p.val) : (m.nil == p.nil && (m.nil || m.val == p.val));
         if (!same) anomalies |= MSIM_ANOMALY_INTERNAL;
+        if (!same && F) {
+          msim_txn_finding f = finding(MSIM_ANOMALY_INTERNAL, m.key);
+          subject(f, x, k); other(f, x, (uint32_t)prev);
+          f.element = m.nil ? NV : m.val; f.other_element = (!p.f && p.nil) ? NV : p.val;
+          F->v.push_back(f);
+        }
         continue;
       }
       if (m.nil) continue;
       S.vseen[m.key] |= 1ull << (m.val & 63);
       const int w = S.writer[kv(m.key, m.val)];
-      if (w < 0 || S.txns[(size_t)w].type == MSIM_T_FAIL) { anomalies |= MSIM_ANOMALY_G1A; continue; }  // garbage / aborted read
+      if (w < 0 || S.txns[(size_t)w].type == MSIM_T_FAIL) {  // garbage / aborted read
+        anomalies |= MSIM_ANOMALY_G1A;
+        if (F) { msim_txn_finding f = finding(MSIM_ANOMALY_G1A, m.key); subject(f, x, k); f.element = m.val; if (w >= 0) other(f, S.txns[(size_t)w], NV); F->v.push_back(f); }
+        continue;
+      }
       if ((uint32_t)w != t) {
         if (final_of((uint32_t)w, m.key) != (int)m.val) anomalies |= MSIM_ANOMALY_G1B;
+        if (F && final_of((uint32_t)w, m.key) != (int)m.val) {
+          msim_txn_finding f = finding(MSIM_ANOMALY_G1B, m.key);
+          subject(f, x, k); other(f, S.txns[(size_t)w], final_mop((uint32_t)w, m.key));
+          f.element = m.val; f.other_element = (uint32_t)final_of((uint32_t)w, m.key);
+          F->v.push_back(f);
+        }
         add((uint32_t)w, t, E_WR);
       }
       // writes follow reads
@@ -471,6 +601,11 @@ bool check_rw(Scratch &S, const msim_op *rows, uint32_t n_rows, const uint32_t *
     }
     bool cyclic = false;
     for (uint32_t v = 0; v < 64; v++) if ((reach[v] >> v) & 1) cyclic = true;
+    if (cyclic && F) {
+      msim_txn_finding f = finding(MSIM_ANOMALY_CYCLIC_VERSIONS, key);
+      for (uint32_t v = 64; v-- > 0;) if ((reach[v] >> v) & 1) { f.element = v; f.count++; }
+      F->v.push_back(f);
+    }
     if (cyclic) { anomalies |= MSIM_ANOMALY_CYCLIC_VERSIONS; for (uint32_t v = 0; v < 64; v++) succ[v] = 0; continue; }
     for (uint32_t v1 = 1; v1 < 64; v1++) {
       const int a = S.writer[kv(key, v1)];
@@ -523,6 +658,31 @@ void msim_txn_explain_instance_host(const msim_op *rows, uint32_t n_rows, const 
   const Witness W = {cycle, steps, max_steps};
   if (rw) (void)check_rw(S, rows, n_rows, payload, n_words, flags, cm, res, &W);
   else check_history(S, rows, n_rows, payload, n_words, flags, cm, res, &W);
+}
+
+// the same with the non-cycle findings (the findings kernels hand over what they cannot finish)
+void msim_txn_findings_instance_host(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t flags, uint32_t cm, msim_check_result *res,
+                                     msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings, bool rw) {
+  thread_local Scratch S;
+  thread_local Findings F;
+  if (rw) (void)check_rw(S, rows, n_rows, payload, n_words, flags, cm, res, nullptr, &F);
+  else check_history(S, rows, n_rows, payload, n_words, flags, cm, res, nullptr, &F);
+  write_findings(F, hdr, findings, max_findings);
+}
+
+extern "C" int msim_explain_txn_findings_rows(uint32_t workload, const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words,
+                                              uint32_t consistency_model, msim_check_result *out, msim_txn_explain *hdr, msim_txn_finding *findings,
+                                              uint32_t max_findings) {
+  if (!rows || !out || !hdr || (!findings && max_findings) || (!payload && n_words) || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
+  if (workload != MSIM_WL_TXN_LIST_APPEND && workload != MSIM_WL_TXN_RW_REGISTER) return MSIM_E_INVALID;
+  Scratch S;
+  Findings F;
+  std::memset(hdr, 0, sizeof *hdr);
+  if (max_findings) std::memset(findings, 0, (size_t)max_findings * sizeof *findings);
+  if (workload == MSIM_WL_TXN_RW_REGISTER) { if (!check_rw(S, rows, n_rows, payload, n_words, 0, consistency_model, out, nullptr, &F)) return MSIM_E_INVALID; }
+  else check_history(S, rows, n_rows, payload, n_words, 0, consistency_model, out, nullptr, &F);
+  write_findings(F, hdr, findings, max_findings);
+  return MSIM_OK;
 }
 
 extern "C" int msim_explain_txn_rows(const msim_op *rows, uint32_t n_rows, const uint32_t *payload, uint32_t n_words, uint32_t consistency_model,

@@ -57,6 +57,7 @@ struct TParams {
   u32 lds_bytes;                 // txn_check_lds_kernel: dynamic LDS of a wavefront
   u32 cm, proscribed, ccap, big; // txn_classify_kernel: the model and what it proscribes; cycle_classify.inc's matrix and search (CycleParams)
   msim_cycle_result *cycles; msim_cycle_step *steps; u32 max_steps;   // txn_explain_kernel: the witness cycles (history i's steps at steps + i * max_steps)
+  msim_txn_explain *fhdr; msim_txn_finding *frecs; u32 max_findings;  // txn_findings_kernel: the non-cycle findings (history i's records at frecs + i * max_findings)
 };
 
 __device__ __forceinline__ u32 elem(const u32 *lw, u32 e) { return (lw[e >> 2] >> (8u * (e & 3u))) & 0xFFu; }
@@ -777,14 +778,21 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(TC_WA
 // (WMAX), more than 64 calls open at once, more transactions than nmax (rows / 2 + 65 of the batch's longest history; rows / 2 + 1 of a
 // run), more edges than 32 nmax — twice txn_check_kernel's, every other capacity is that kernel's.  A strongly connected component may
 // be as large as the history (MSIM_DEV_FLAGS 0x20000: a matrix of 16 and the search behind it; 0x2000: a matrix of 16 and no search).
+// txn_findings_kernel: the same record, and a witness for every non-cycle anomaly (include/maelsim_txn_findings.h; txn_findings.inc).  It
+// hands over what txn_classify_kernel does, and a history of more than MSIM_TXN_FINDINGS_CAPACITY findings.
 #include "cycle_classify.inc"
+#include "txn_findings.inc"
 
 __global__ void __launch_bounds__(64) txn_classify_kernel(const TParams p) {
-  constexpr bool EXPLAIN = false;
+  constexpr bool EXPLAIN = false, FINDINGS = false;
 #include "txn_classify_body.inc"
 }
 __global__ void __launch_bounds__(64) txn_explain_kernel(const TParams p) {
-  constexpr bool EXPLAIN = true;
+  constexpr bool EXPLAIN = true, FINDINGS = false;
+#include "txn_classify_body.inc"
+}
+__global__ void __launch_bounds__(64) txn_findings_kernel(const TParams p) {
+  constexpr bool EXPLAIN = false, FINDINGS = true;
 #include "txn_classify_body.inc"
 }
 
@@ -793,6 +801,7 @@ uint64_t ws_words_for(u32 nmax, u32 emax) { return (uint64_t)nmax * 11 + 4 + KMA
 uint64_t ws_words_lds(u32 nmax) { return (uint64_t)nmax * 6 + 8; }
 uint64_t ws_words_classify(u32 nmax, u32 emax) { return ((uint64_t)nmax * 16 + 4 + 3 * KMAX + WMAX + 2 * (uint64_t)emax + 1) & ~1ull; }   // txn_classify_kernel (even: 64-bit tables)
 uint64_t ws_words_explain(u32 nmax, u32 emax) { return ((uint64_t)nmax * 17 + 4 + 3 * KMAX + WMAX + 2 * (uint64_t)emax + 1) & ~1ull; }    // txn_explain_kernel: and t_inv
+uint64_t ws_words_findings(u32 nmax, u32 emax) { return ws_words_explain(nmax, emax) + FWORDS; }   // txn_findings_kernel: and the region of findings (FWORDS is even)
 
 // LDS of a workgroup of txn_check_lds_kernel: what a history of `nmax` transactions over `keys` keys with elements below `stride`
 // needs with 4.5 dependency edges per transaction, at most 78 KiB (two workgroups per CU)
@@ -809,6 +818,9 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
   // mode.witness (msim_explain_txn*; with full): the witness cycles, found by txn_explain_kernel in tp.cycles / tp.steps
   CycleSlabs *const wit = mode.full ? mode.witness : nullptr;
   if (wit) { bind_cycles(tp, *wit); if (int rc = wit->clear(ctx, st)) return rc; }   // a history the clean passes prove clean keeps the zero record
+  // mode.findings (msim_explain_txn_findings*; with full, without witness): the non-cycle findings, written by txn_findings_kernel
+  FindingSlabs *const fnd = mode.full && !wit ? mode.findings : nullptr;
+  if (fnd) { tp.fhdr = fnd->hdr(); tp.frecs = fnd->rec(); tp.max_findings = fnd->max_k; if (int rc = fnd->clear(ctx, st)) return rc; }
   // Which kernel takes the first pass: the one with its tables in LDS, a workgroup of sixteen wavefronts per history.  Measured on cfg5,
   // 32768 histories (profiles/r03b_cfg5_txn_check_*, r03k_cfg5_txn_check.txt, r03x_txn_check.txt): tables in an HBM workspace, one
   // wavefront per history: 82 GB of HBM traffic, 130 ms (64 histories in flight per CU); tables in LDS (78 KiB: two histories per CU),
@@ -850,20 +862,22 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
   if (mode.full && !todo.empty()) {   // the full analysis on the device, over the list of histories that need it
     const u32 m = (u32)todo.size();
     tp.emax *= 2;   // (a clean history has few edges per transaction; one without isolation has more)
-    tp.ws_words = wit ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
+    tp.ws_words = fnd ? ws_words_findings(tp.nmax, tp.emax) : wit ? ws_words_explain(tp.nmax, tp.emax) : ws_words_classify(tp.nmax, tp.emax);
     tp.cm = cm; tp.proscribed = msim_proscribed_anomalies(cm);
     // MSIM_DEV_FLAGS bit 13: a tiny matrix and no search beyond it, so that tests reach the host; bit 17: a tiny matrix, so that small
     // histories reach the search (as for rw_classify_kernel)
     tp.ccap = (msim_dev_flags(ctx) & 0x22000u) ? 16u : CCAP;
     tp.big = (msim_dev_flags(ctx) & 0x2000u) ? 0u : 1u;
-    if ((rc = wit ? pass(m, &todo, txn_explain_kernel, 64, 0) : pass(m, &todo, txn_classify_kernel, 64, 0)) < 0) return rc;
+    if ((rc = pass(m, &todo, fnd ? txn_findings_kernel : wit ? txn_explain_kernel : txn_classify_kernel, 64, 0)) < 0) return rc;
     todo = needs(h_out, n, for_host);
     if (tm.trace) std::fprintf(stderr, "[txn-classify] full analysis of %u histories (%u launches): done at %.2f ms, %zu for the host\n", m, (u32)rc, tm.ms(), todo.size());
   }
   if (wit && (rc = wit->fetch(ctx, st)) != MSIM_OK) return rc;
+  if (fnd && (rc = fnd->fetch(ctx, st)) != MSIM_OK) return rc;
   if (!todo.empty()) {
     rc = hand_off(ctx, source_of(tp, hmeta), n, todo, h_out, tp.out, [&](const msim_op *rows, u32 nr, const u32 *pay, u32 nw, u32 flags, u32 i) {
-      if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], wit->hdr(i), wit->rec(i), tp.max_steps, false);
+      if (fnd) msim_txn_findings_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], fnd->hdr(i), fnd->rec(i), fnd->max_k, false);
+      else if (wit) msim_txn_explain_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i], wit->hdr(i), wit->rec(i), tp.max_steps, false);
       else msim_txn_check_instance_host(rows, nr, pay, nw, flags, cm, &h_out[i]);
     });
     if (rc != MSIM_OK) return rc;
@@ -878,7 +892,8 @@ int txn_dev_run(msim_ctx *ctx, TParams tp, u32 n, u32 cm, const std::vector<msim
 // msim_check for txn-list-append: the histories of the last run, where they lie in HBM.
 // (cycles / steps / max_steps: msim_explain_txn's witness cycles, a slab of max_steps per history, with the full analysis on the device
 // whatever msim_set_check_classify says; null / null / 0: the plain check)
-int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+static int txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps, msim_txn_explain *fhdr, msim_txn_finding *frecs,
+                      uint32_t max_findings) {
   MSIM_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const u32 n = ctx->n_inst;
   std::chrono::steady_clock::time_point t0;
@@ -892,31 +907,39 @@ int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_s
   tp.lds_bytes = lds_bytes_for(tp.nmax, ctx->cfg.max_values, ctx->cfg.max_writes_per_key + 1);
   CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n, max_steps, cycles, steps)) return rc;
+  FindingSlabs fnd;
+  if (fhdr) if (int rc = fnd.alloc(ctx, n, max_findings, fhdr, frecs)) return rc;
   u32 redone = 0;
   int rc = txn_dev_run(ctx, tp, n, ctx->cfg.consistency_model, &hm, ctx->h_check, ctx->stream, &redone, &ctx->d_check_scratch, &ctx->cap_check_scratch,
-                       CycleMode{ctx->check_classify || cycles, cycles ? &wit : nullptr});
+                       CycleMode{ctx->check_classify || cycles || fhdr, cycles ? &wit : nullptr, fhdr ? &fnd : nullptr});
   if (rc != MSIM_OK) return rc;
   finish_check(ctx, t0, redone);
   return MSIM_OK;
+}
+int msim_check_txn_device(msim_ctx *ctx, msim_cycle_result *cycles, msim_cycle_step *steps, uint32_t max_steps) {
+  return txn_device(ctx, cycles, steps, max_steps, nullptr, nullptr, 0);
 }
 
 // Checks `n_histories` list-append histories given on the host (rows / payload words of history i at row_offsets[i] /
 // payload_offsets[i]) with the device pass of msim_check on HIP device `device`; out[i] as msim_check_txn_rows would fill it.
 static int txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
                      uint32_t n_histories, uint32_t consistency_model, msim_check_result *out, uint32_t *n_host, bool classify,
-                     msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0) {
+                     msim_cycle_result *cycles = nullptr, msim_cycle_step *steps = nullptr, uint32_t max_steps = 0,
+                     msim_txn_explain *fhdr = nullptr, msim_txn_finding *frecs = nullptr, uint32_t max_findings = 0) {
   if (!rows || !row_offsets || !payload_offsets || !out || n_histories == 0 || consistency_model > MSIM_CM_READ_UNCOMMITTED) return MSIM_E_INVALID;
   BatchFrame<OffsetsBatch> f(device); msim_ctx *ctx = &f.ctx;
   if (int rc = f.begin(n_histories, sizeof(msim_check_result), rows, row_offsets, payload, payload_offsets, n_histories, 0x7FFFFFFFull)) return rc;
   DevBuf ws; size_t ws_cap = 0;
   CycleSlabs wit;
   if (cycles) if (int rc = wit.alloc(ctx, n_histories, max_steps, cycles, steps)) return rc;
+  FindingSlabs fnd;
+  if (fhdr) if (int rc = fnd.alloc(ctx, n_histories, max_findings, fhdr, frecs)) return rc;
   TParams tp;
   std::memset(&tp, 0, sizeof tp);
   f.bind(tp);
   tp.nmax = f.b.longest / 2 + 65; tp.emax = tp.nmax * 16; tp.max_steps = max_steps;
   tp.lds_bytes = lds_bytes_for(tp.nmax, std::min<u32>(KMAX, tp.nmax * 2 + 16), 17);
-  return txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{classify, cycles ? &wit : nullptr});
+  return txn_dev_run(ctx, tp, n_histories, consistency_model, nullptr, out, nullptr, n_host, ws.addr(), &ws_cap, CycleMode{classify, cycles ? &wit : nullptr, fhdr ? &fnd : nullptr});
 }
 
 extern "C" int msim_check_txn_batch(int device, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload, const uint64_t *payload_offsets,
@@ -944,4 +967,23 @@ extern "C" int msim_explain_txn(msim_ctx *ctx, msim_cycle_result *cycles, msim_c
   const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
   if (int rc = explain_refusal(ctx, "msim_explain_txn", rw || ctx->cfg.workload == MSIM_WL_TXN_LIST_APPEND, "a txn-list-append or txn-rw-register", n_out)) return rc;
   return rw ? msim_check_rw_device(ctx, cycles, steps, max_steps) : msim_check_txn_device(ctx, cycles, steps, max_steps);
+}
+
+// msim_classify_txn_batch / msim_classify_rw_batch with a witness for every non-cycle anomaly (txn_findings_kernel / rw_findings_kernel;
+// include/maelsim_txn_findings.h).
+extern "C" int msim_explain_txn_findings_batch(int device, uint32_t workload, const msim_op *rows, const uint64_t *row_offsets, const uint32_t *payload,
+                                               const uint64_t *payload_offsets, uint32_t n_histories, uint32_t consistency_model, msim_check_result *out,
+                                               uint32_t *n_host, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings) {
+  if (!hdr || (!findings && max_findings)) return MSIM_E_INVALID;
+  if (workload == MSIM_WL_TXN_RW_REGISTER)
+    return msim_rw_findings_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, hdr, findings, max_findings);
+  if (workload != MSIM_WL_TXN_LIST_APPEND) return MSIM_E_INVALID;
+  return txn_batch(device, rows, row_offsets, payload, payload_offsets, n_histories, consistency_model, out, n_host, true, nullptr, nullptr, 0, hdr, findings, max_findings);
+}
+
+extern "C" int msim_explain_txn_findings(msim_ctx *ctx, msim_txn_explain *hdr, msim_txn_finding *findings, uint32_t max_findings, uint32_t n_out) {
+  if (!ctx || !hdr || (!findings && max_findings)) return MSIM_E_INVALID;
+  const bool rw = ctx->cfg.workload == MSIM_WL_TXN_RW_REGISTER;
+  if (int rc = explain_refusal(ctx, "msim_explain_txn_findings", rw || ctx->cfg.workload == MSIM_WL_TXN_LIST_APPEND, "a txn-list-append or txn-rw-register", n_out)) return rc;
+  return rw ? msim_rw_findings_device(ctx, hdr, findings, max_findings) : txn_device(ctx, nullptr, nullptr, 0, hdr, findings, max_findings);
 }

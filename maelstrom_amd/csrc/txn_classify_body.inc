@@ -3,6 +3,8 @@
 // (txn_explain_kernel): the same record, and the witness cycle of its cycle class (cycle_classify.inc); the workspace then keeps every
 // transaction's :invoke row as well (t_inv, behind the reversed edges).  A body included into the two kernels, not a function of its
 // own: as a function it compiled txn_classify_kernel to other code than it had (61 for 63 vector registers, 65 more instructions).
+// FINDINGS (txn_findings_kernel; a constant of the including kernel as EXPLAIN is): where passes D and E OR a non-cycle bit they also
+// emit a record into the history's region behind t_inv (txn_findings.inc), sorted and written out before the cycles are classified.
   const u32 lane = threadIdx.x, hist = p.list[p.first + blockIdx.x];
   const u64 lt = (1ull << lane) - 1ull;
   HIST_VIEW(p, hist);
@@ -20,11 +22,13 @@
   u32 *const longest = jump + NM;            // [KMAX] (len + 1) << 24 | first payload word of the list
   u32 *const writer = longest + KMAX;        // [WMAX]
   u32 *const adj = writer + WMAX, *const radj = adj + p.emax;   // [emax] each
-  [[maybe_unused]] u32 *const t_inv = radj + p.emax;          // [NM] EXPLAIN only
+  [[maybe_unused]] u32 *const t_inv = radj + p.emax;          // [NM] EXPLAIN and FINDINGS only
+  [[maybe_unused]] const FRegion F(t_inv + NM);               // FINDINGS only
 
   BLANK_RESULT(res, NEEDS_HOST);
 #define TO_HOST() do { if (lane == 0) p.out[hist] = res; return; } while (0)
   if (n_words >= (1u << 24) || NM > 0xFFFFFFu) TO_HOST();
+  if constexpr (FINDINGS) { if (lane == 0) *F.cnt = 0; __syncthreads(); }
 
   // ---- A: transactions ---------------------------------------------------------------------------------------------------------
   u32 n = 0, c_ok = 0, c_fail = 0, c_info = 0;
@@ -41,7 +45,7 @@
       const u64 im = __ballot(inv);
       const u32 my_t = n + (u32)__popcll(im & lt);
       if (n + (u32)__popcll(im) > NM) { bad = true; break; }
-      if (inv) { t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); t_first[my_t] = 0; if constexpr (EXPLAIN) t_inv[my_t] = idx; }   // never completed = indeterminate
+      if (inv) { t_cmp[my_t] = NONE; t_off[my_t] = woff; t_lt[my_t] = len | (MSIM_T_INFO << 16); t_first[my_t] = 0; if constexpr (EXPLAIN || FINDINGS) t_inv[my_t] = idx; }   // never completed = indeterminate
 #include "txn_pairing.inc"
       if (bad) break;
       n += (u32)__popcll(im);
@@ -84,10 +88,17 @@
       const Mop m = next_mop(w, wn, i);
       if (m.f) continue;
       { u64 s0 = 0, s1 = 0, s2 = 0, s3 = 0;   // duplicates
+        [[maybe_unused]] bool dup_told = false;
         for (u32 e = 0; e < m.len; e++) {
           const u32 x = elem(m.list, e); const u64 b = 1ull << (x & 63u); const u32 q = x >> 6;
           const u64 s = q == 0 ? s0 : q == 1 ? s1 : q == 2 ? s2 : s3;
           if (s & b) anomalies |= MSIM_ANOMALY_DUPLICATE_ELEMENTS;
+          if constexpr (FINDINGS) if ((s & b) && !dup_told) {   // the lowest position that repeats an earlier one, and the lowest it repeats
+            dup_told = true;
+            u32 a = 0;
+            while (elem(m.list, a) != x) a++;
+            f_emit(F, F_DUPLICATE, m.key, t, t_inv[t], t_cmp[t], k, NONE, NONE, NONE, x, e, a);
+          }
           s0 |= q == 0 ? b : 0; s1 |= q == 1 ? b : 0; s2 |= q == 2 ? b : 0; s3 |= q == 3 ? b : 0;
         } }
       { int prev = -1; Mop pm = m; u32 e_i = 0, e_k = 0;   // internal consistency: what the transaction's own earlier micro-ops imply for this read
@@ -99,16 +110,31 @@
         if (prev >= 0) { ok = m.len == pm.len + n_app; if (ok) for (u32 e = 0; e < pm.len; e++) ok &= elem(m.list, e) == elem(pm.list, e); at = pm.len; }
         else { ok = m.len >= n_app; at = m.len - n_app; }
         if (ok) { u32 a = 0; for (e_i = 0, e_k = 0; e_k < k; e_k++) { const Mop q = next_mop(w, wn, e_i); if (e_k >= e0 && q.f && q.key == m.key) { if (elem(m.list, at + a) != q.val) ok = false; a++; } } }
-        if (!ok) anomalies |= MSIM_ANOMALY_INTERNAL; }
+        if (!ok) anomalies |= MSIM_ANOMALY_INTERNAL;
+        if constexpr (FINDINGS) if (!ok) {
+          const bool pr = prev >= 0;
+          f_emit(F, F_INTERNAL, m.key, t, t_inv[t], t_cmp[t], k, pr ? t_inv[t] : NONE, pr ? t_cmp[t] : NONE, pr ? (u32)prev : NONE, m.len, pr ? pm.len : NONE, n_app);
+        } }
       u32 ext = m.len;   // the externally visible part: without the transaction's own appends at the tail
       while (ext > 0 && WRITER(m.key, elem(m.list, ext - 1)) == t) ext--;
-      for (u32 e = 0; e < ext; e++) { const u32 wr = WRITER(m.key, elem(m.list, e)); if (wr == NONE || TYPE(wr) == MSIM_T_FAIL) anomalies |= MSIM_ANOMALY_G1A; }
+      for (u32 e = 0; e < ext; e++) {
+        const u32 wr = WRITER(m.key, elem(m.list, e));
+        if (wr == NONE || TYPE(wr) == MSIM_T_FAIL) {
+          anomalies |= MSIM_ANOMALY_G1A;
+          if constexpr (FINDINGS) f_emit(F, F_G1A, m.key, t, t_inv[t], t_cmp[t], k, wr == NONE ? NONE : t_inv[wr], wr == NONE ? NONE : t_cmp[wr], NONE, elem(m.list, e), NONE, e);
+        }
+      }
       if (ext > 0) {   // G1b: the last visible element must be its writer's last append to the key
         const u32 last = elem(m.list, ext - 1), wr = WRITER(m.key, last);
         if (wr != NONE && wr != t) {
           const u32 *w2 = pay + t_off[wr]; const u32 wn2 = t_lt[wr] & 0xFFFFu; u32 fin = NONE;
           for (u32 i2 = 0; i2 < wn2;) { const Mop q = next_mop(w2, wn2, i2); if (q.f && q.key == m.key) fin = q.val; }
           if (fin != last) anomalies |= MSIM_ANOMALY_G1B;
+          if constexpr (FINDINGS) if (fin != last) {
+            u32 fin_k = NONE, k2 = 0;   // the micro-op of that last append
+            for (u32 i2 = 0; i2 < wn2; k2++) { const Mop q = next_mop(w2, wn2, i2); if (q.f && q.key == m.key) fin_k = k2; }
+            f_emit(F, F_G1B, m.key, t, t_inv[t], t_cmp[t], k, t_inv[wr], t_cmp[wr], fin_k, last, fin, ext - 1u);
+          }
         }
       }
       // the key's longest read; among equals the first in (transaction, micro-op) order
@@ -145,13 +171,14 @@
         if (a == NONE || b == NONE) continue;
         const bool fa = TYPE(a) == MSIM_T_FAIL, fb = TYPE(b) == MSIM_T_FAIL;
         if (fa && !fb) anomalies |= MSIM_ANOMALY_DIRTY_UPDATE;
+        if constexpr (FINDINGS) if (fa && !fb && pass == 0) f_emit(F, F_DIRTY, key, b, t_inv[b], t_cmp[b], NONE, t_inv[a], t_cmp[a], NONE, elem(ord, i + 1), elem(ord, i), i);
         if (!fa && !fb) ADD(a, b, E_WW);
       }
     }
     for (u32 t = lane; t < n; t += 64) {   // wr / rw per read of an :ok transaction; its realtime successors
       if (TYPE(t) != MSIM_T_OK) continue;
       const u32 *w = pay + t_off[t]; const u32 wn = t_lt[t] & 0xFFFFu;
-      for (u32 i = 0; i < wn;) {
+      for ([[maybe_unused]] u32 i = 0, k = 0; i < wn; k++) {
         const Mop m = next_mop(w, wn, i);
         if (m.f) continue;
         const u32 L = longest[m.key];
@@ -159,6 +186,13 @@
         const u32 llen = (L >> 24) - 1u; const u32 *ord = pay + (L & 0xFFFFFFu);
         bool pre = m.len <= llen;
         if (pre) for (u32 e = 0; e < m.len; e++) pre &= elem(m.list, e) == elem(ord, e);
+        if constexpr (FINDINGS) if (!pre && pass == 0) {   // against longest(k): where the two lists part
+          const u64 L64 = long64[m.key];
+          const u32 lt_ = 0xFFFFFFu - (u32)((L64 >> 16) & 0xFFFFFFu), lk = 0xFFFFu - (u32)(L64 & 0xFFFFu);
+          u32 d = 0;
+          while (d < m.len && d < llen && elem(m.list, d) == elem(ord, d)) d++;
+          f_emit(F, F_ORDER, m.key, t, t_inv[t], t_cmp[t], k, t_inv[lt_], t_cmp[lt_], lk, elem(m.list, d), d < llen ? elem(ord, d) : NONE, d);
+        }
         if (!pre) { anomalies |= MSIM_ANOMALY_INCOMPATIBLE_ORDER; continue; }
         u32 ext = m.len;
         while (ext > 0 && WRITER(m.key, elem(m.list, ext - 1)) == t) ext--;
@@ -189,6 +223,7 @@
     }
   }
   anomalies = wv_or(anomalies);
+  if constexpr (FINDINGS) { if (!f_finish(F, FOut{p.fhdr, p.frecs, p.max_findings}, hist)) TO_HOST(); }   // (more than the region holds: the host walk's)
   const CycleParams cp = {p.out, p.cm, p.proscribed, p.ccap, p.big};
   if constexpr (EXPLAIN) {
     const CycleWitness cw = {p.cycles, p.steps, p.max_steps, t_inv, t_cmp};

@@ -21,6 +21,7 @@ KAFKA_FINDING_DT, KAFKA_EXPLAIN_DT = np.dtype(A.KafkaFinding), np.dtype(A.KafkaE
 (PN_READ_DT, PN_RANGE_DT, PN_EXPLAIN_DT, UNIQUE_DUP_DT, UNIQUE_EXPLAIN_DT, ECHO_ERROR_DT, ECHO_EXPLAIN_DT) = (
     np.dtype(s) for s in A.SMALL_EXPLAIN_RECORDS.values())
 JOURNAL_MSG_DT, JOURNAL_SUMMARY_DT = (np.dtype(s) for s in A.JOURNAL_RECORDS.values())
+TXN_FINDING_DT, TXN_EXPLAIN_DT = (np.dtype(s) for s in A.TXN_FINDINGS_RECORDS.values())
 META_DT = np.dtype([(n, "<u4") for n in ("n_rows", "n_payload_words", "flags", "n_rounds", "n_events", "r0", "r1", "r2")])
 PERF_QUANTILES = (0, 0.5, 0.95, 0.99, 1)
 
@@ -217,6 +218,18 @@ class Engine:
         self._chk(self.lib.msim_explain_txn(self._ctx, cycles.ctypes.data, steps.ctypes.data, max_steps, self.n), "msim_explain_txn")
         res = self.check_results()
         return [(res[i], cycles[i], steps[i, :int(cycles[i]["n_steps"])].copy()) for i in range(self.n)]
+
+    def explain_txn_findings(self, max_findings=64):
+        """txn-list-append / txn-rw-register: check(classify=True) that also explains the NON-CYCLE anomalies (msim_explain_txn_findings):
+        per history of the last run (CHECK_DT record — check_results() holds the same afterwards —, TXN_EXPLAIN_DT header,
+        TXN_FINDING_DT records: one witness per anomaly in the order include/maelsim_txn_findings.h defines; see txn_findings_analysis),
+        found on the device.  A history with more findings than max_findings has header["truncated"] set; header["count"] is always
+        the true number per anomaly."""
+        hdr = np.zeros(max(self.n, 1), dtype=TXN_EXPLAIN_DT)
+        fs = np.zeros((max(self.n, 1), max(max_findings, 1)), dtype=TXN_FINDING_DT)
+        self._chk(self.lib.msim_explain_txn_findings(self._ctx, hdr.ctypes.data, fs.ctypes.data, max_findings, self.n), "msim_explain_txn_findings")
+        res = self.check_results()
+        return [(res[i], hdr[i], fs[i, :int(hdr[i]["n_findings"])].copy()) for i in range(self.n)]
 
     def explain_set_full(self, max_elements=256):
         """broadcast / g-set: check() that also explains (msim_explain_set_full): per history of the last run (CHECK_DT record —
@@ -1287,6 +1300,100 @@ def txn_cycle_analysis(rows, payload, cycle, steps, n_nodes=0, rw=False):
     if int(cycle["length"]) > len(steps):
         entry["truncated"] = int(cycle["length"])
     return {"anomalies": {name: [entry]}}
+
+
+def explain_txn_findings_history(rows, payload, workload="txn-list-append", consistency_model="strict-serializable", max_findings=64):
+    """The host analysis of one list-append / rw-register history with a witness for every non-cycle anomaly
+    (msim_explain_txn_findings_rows; needs no device) -> (CHECK_DT record — what msim_check_txn_rows / msim_check_rw_rows write —,
+    TXN_EXPLAIN_DT header, TXN_FINDING_DT records as include/maelsim_txn_findings.h defines them, in its order).  The whole zero-padded
+    slab of max_findings records is the returned array's `.base`."""
+    rows = np.ascontiguousarray(rows); payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    out = np.zeros(1, dtype=CHECK_DT)
+    hdr = np.zeros(1, dtype=TXN_EXPLAIN_DT)
+    slab = np.zeros(max(max_findings, 1), dtype=TXN_FINDING_DT)
+    _call("msim_explain_txn_findings_rows", WORKLOADS[workload], rows.ctypes.data, len(rows), payload.ctypes.data, len(payload),
+          CONSISTENCY_MODELS[consistency_model], out.ctypes.data_as(C.POINTER(A.CheckResult)), hdr.ctypes.data, slab.ctypes.data, max_findings)
+    return out[0], hdr[0], slab[:int(hdr[0]["n_findings"])]
+
+
+def explain_txn_findings_batch(histories, workload="txn-list-append", consistency_model="strict-serializable", device=0, max_findings=64,
+                               with_n_host=False):
+    """classify_txn_batch / classify_rw_batch with the non-cycle findings written on the device (msim_explain_txn_findings_batch;
+    txn_findings_kernel / rw_findings_kernel).  Returns (CHECK_DT records, TXN_EXPLAIN_DT headers, a list of TXN_FINDING_DT arrays — the
+    records written per history, whose `.slab` is the whole zero-padded (histories, max_findings) array)[, how many histories went to
+    the host walk: the hand-overs of the classify entries, and more than A.TXN_FINDINGS_CAPACITY findings]."""
+    rows, ro, pay, po = _offsets_form(histories)
+    n = len(ro) - 1
+    out = np.zeros(n, dtype=CHECK_DT)
+    hdr = np.zeros(n, dtype=TXN_EXPLAIN_DT)
+    slab = np.zeros((n, max(max_findings, 1)), dtype=TXN_FINDING_DT)
+    n_host = C.c_uint32()
+    _call("msim_explain_txn_findings_batch", device, WORKLOADS[workload], rows.ctypes.data, ro.ctypes.data, pay.ctypes.data, po.ctypes.data, n,
+          CONSISTENCY_MODELS[consistency_model], out.ctypes.data, C.byref(n_host), hdr.ctypes.data, slab.ctypes.data, max_findings)
+    fs = _StepLists(slab[i, :int(hdr[i]["n_findings"])].copy() for i in range(n))
+    fs.slab = slab[:, :max_findings]
+    return (out, hdr, fs, n_host.value) if with_n_host else (out, hdr, fs)
+
+
+def txn_findings_analysis(rows, payload, header, findings, rw=False, n_nodes=0):
+    """elle's :anomalies map for the non-cycle findings of one history (pure formatting): {"anomalies": {"internal": [{"op", "mop",
+    "expected"}], "incompatible-order": [{"key", "values": [list(m), ord(k)]}], "G1a": [{"op", "mop", "element", "writer"}], "G1b":
+    [... "writer", "writer-final"], "duplicate-elements": [...], "dirty-update": [...], "cyclic-versions": [{"key", "element",
+    "count"}]}}.  Ops are decode_history's (a transaction's completion; its invocation where it never completed); `expected` of a
+    list-append internal finding is the earlier read's list followed by the transaction's own appends since, or ["...", *appends]
+    without an earlier read; a list marked "truncated" names the true number of findings where the slab held fewer."""
+    ops = decode_history(rows, payload, n_nodes, A.WL_TXN_RW_REGISTER if rw else A.WL_TXN_LIST_APPEND)
+    NV = A.NO_VALUE
+
+    def party(inv, cmp_):
+        """(the op shown, the transaction's form)"""
+        if inv == NV:
+            return (ops[cmp_] if cmp_ != NV else None), None
+        done = cmp_ != NV
+        form = ops[cmp_] if done and (int(rows["packed"][cmp_]) & 3) == A.T_OK else ops[inv]
+        return (ops[cmp_] if done else ops[inv]), form["value"]
+
+    def val(x):
+        return None if x == NV else x
+
+    out = {}
+    for f in findings:
+        f = {k: int(f[k]) for k in f.dtype.names}
+        name = A.ANOMALIES[f["anomaly"]]
+        op, form = party(f["inv_row"], f["cmp_row"])
+        w_op, w_form = party(f["other_inv_row"], f["other_cmp_row"])
+        mop = form[f["mop"]] if form is not None and f["mop"] != NV else None
+        if name == "internal":
+            e = {"op": op, "mop": mop}
+            if mop is not None and not rw:
+                since = 0 if f["other_mop"] == NV else f["other_mop"] + 1
+                own = [m[2] for m in form[since:f["mop"]] if m[0] == ":append" and m[1] == f["key"]]
+                e["expected"] = (["..."] if f["other_mop"] == NV else list(form[f["other_mop"]][2] or [])) + own
+            elif mop is not None:
+                e["expected"] = val(f["other_element"])
+        elif name == "incompatible-order":
+            e = {"key": f["key"], "values": [mop[2], w_form[f["other_mop"]][2]]}
+        elif name == "cyclic-versions":
+            e = {"key": f["key"], "element": f["element"] or None, "count": f["count"]}
+        elif name == "dirty-update":
+            e = {"key": f["key"], "op": op, "element": f["element"], "writer": w_op, "aborted-element": f["other_element"]}
+        elif name == "duplicate-elements":
+            e = {"op": op, "mop": mop, "key": f["key"], "element": f["element"]}
+            if w_op is not None:
+                e.update({"other-op": w_op, "other-mop": w_form[f["other_mop"]], "count": f["count"]})
+            else:
+                e["positions"] = [f["count"], f["other_element"]]
+        else:   # G1a, G1b
+            e = {"op": op, "mop": mop, "key": f["key"], "element": f["element"], "writer": w_op}
+            if name == "G1b":
+                e["writer-final"] = f["other_element"]
+        out.setdefault(name, []).append(e)
+    bits = {b: n for b, n in A.ANOMALIES.items()}
+    for b, name in bits.items():
+        true_n = int(header["count"][b.bit_length() - 1])
+        if true_n > len(out.get(name, [])):
+            out.setdefault(name, []).append({"truncated": true_n})
+    return {"anomalies": out}
 
 
 def anomaly_census(results):

@@ -32,6 +32,7 @@ def _deps_digest():
     h = hashlib.sha256((CXX + " ".join(FLAGS)).encode())
     deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
     deps += [os.path.join(ROOT, "include", "maelsim.h"), os.path.join(ROOT, "include", "maelsim_kafka_explain.h"), os.path.join(ROOT, "include", "maelsim_small_explain.h"), os.path.join(ROOT, "include", "maelsim_journal.h"),
+             os.path.join(ROOT, "include", "maelsim_txn_findings.h"),
              os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "rccl", "rccl.h")]
     for d in deps:
         with open(d, "rb") as f:
